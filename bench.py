@@ -27,6 +27,10 @@ Kodak pictures (tests/golden/kodak24.npz: pixels of datasets/kodak/kodim01..24.p
 "Average:" figures.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
+
+`--dump-outputs DIR`: behind the last timed region, what its last iteration left in the fitter (parameters, Adam moments,
+render, projection of the updated gaussians) goes to DIR/<name>.npy.  Inputs are seeded, so two builds run with the
+same arguments can be compared array for array (two runs of one build at the default workload: equal bit for bit).
 """
 import argparse
 import json
@@ -40,7 +44,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E: 8.0 TB/s spec
 EVENT_STRIDE = 2      # every 2nd tile pass of the event-carrying regions has a HIP event pair attached
 REPEATS = 5           # timed regions of `steps` iterations each; the median is reported
 SIMDS, CLOCK_GHZ = 1024, 2.4  # 256 CUs x 4 SIMDs; shader clock under this load (tools/clock_probe.sh: 2.40 GHz)
@@ -75,6 +79,9 @@ def parse(argv=None):
                         "separate HIP streams of this GPU (extra information, not `value`)")
     p.add_argument("--train-step", action="store_true",
                    help="also time the quantisation-aware iterations of BASELINE config 5 after the timed region")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write what the last timed iteration left in the fitter to DIR/<name>.npy (float32; ranks of a "
+                        "multi-GPU run add _rank<r> to the name)")
     return p.parse_args(argv)
 
 
@@ -198,6 +205,8 @@ def run_rank(args):
         # (fast_fwdbwd_kernel<1, 0, false>) -- and is reported beside the dominant kernel, not averaged into it.
         first_of_call += [(EVENT_STRIDE * j) % fit.max_call == 0 for j in range(per_region)]
     fit.check_status()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fitter_outputs(fit), "" if world == 1 else f"_rank{rank}")
     first_pass_us = [u for u, f in zip(kernel_us, first_of_call) if f]
     if fit.tx * fit.ty <= 1536 and len(first_pass_us) < len(kernel_us):
         kernel_us = [u for u, f in zip(kernel_us, first_of_call) if not f]
@@ -299,6 +308,42 @@ def run_rank(args):
     if world > 1:
         barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def fitter_outputs(fit):
+    """What a caller of NativeFitter.train() holds when the call is over, as host arrays: the parameters the last
+    iteration's Adam step wrote and its moments, the render and the per-tile squared error of that iteration, and the
+    projection of the updated gaussians that closes it (radii and tile counts are small integers, exact in float32)."""
+    import torch
+    torch.cuda.synchronize(fit.dev)
+    n = fit.n
+    out = {"xyz": fit.xyz, "cholesky": fit.chol, "features_dc": fit.feat,
+           "adam_m_xyz": fit.m_xyz, "adam_v_xyz": fit.v_xyz, "adam_m_cholesky": fit.m_chol, "adam_v_cholesky": fit.v_chol,
+           "adam_m_features_dc": fit.m_feat, "adam_v_features_dc": fit.v_feat,
+           "out_img": fit.out_img, "tile_sse": fit.tile_sse,
+           "xys": fit.xys[:n], "conics": fit.conics[:n], "radii": fit.radii[:n], "num_tiles_hit": fit.nth[:n]}
+    return {k: v.detach().to("cpu", torch.float32).numpy() for k, v in out.items()}
+
+
+def dump_outputs(path, arrays, suffix="", limit=DUMP_LIMIT_BYTES):
+    """Write every array as <path>/<name><suffix>.npy, float32 (float64 stays float64).  When the files would pass
+    `limit` bytes in all, each array is cut down by the same factor to a sample of its flattened elements drawn
+    with a fixed seed (sorted indices, so that two runs keep the same elements in the same order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+              for k, a in arrays.items()}
+    header = 128  # of an .npy file holding an array of these ranks
+    total = sum(a.nbytes for a in arrays.values())
+    room = limit - header * len(arrays)
+    for i, (name, a) in enumerate(sorted(arrays.items())):
+        if total > room:
+            keep = max(1, int(a.size * (room / total)))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(i).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
 
 
 def make_fitter(gt, xyz, L, col, n, h, w, **kw):

@@ -8,12 +8,17 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# what --dump-outputs writes (N gaussians, H x W pixels, T tiles of 16 x 16)
+DUMP_SHAPES = {"xyz": ("N", 2), "cholesky": ("N", 3), "features_dc": ("N", 3), "adam_m_xyz": ("N", 2),
+               "adam_v_xyz": ("N", 2), "adam_m_cholesky": ("N", 3), "adam_v_cholesky": ("N", 3),
+               "adam_m_features_dc": ("N", 3), "adam_v_features_dc": ("N", 3), "out_img": ("H", "W", 3),
+               "tile_sse": ("T",), "xys": ("N", 2), "conics": ("N", 3), "radii": ("N",), "num_tiles_hit": ("N",)}
 
 
-def test_bench_line_has_the_contract_fields():
+def test_bench_line_has_the_contract_fields(tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "24", "--warmup", "4",
            "--num-points", "3000", "--height", "96", "--width", "144", "--cpu-seconds", "1.5", "--images", "2",
-           "--image-iterations", "200", "--images-per-gpu", "2"]
+           "--image-iterations", "200", "--images-per-gpu", "2", "--dump-outputs", str(tmp_path / "dump")]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -71,6 +76,37 @@ def test_bench_line_has_the_contract_fields():
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1
     assert c["single_thread"]["cores"] == 1 and c["single_thread"]["value"] > 0
     assert c["config1_train_loop"]["value"] > 0 and "N=2500" in c["config1_train_loop"]["sample"]
+    # --dump-outputs: the fitter's arrays behind the last timed iteration, whole at this size
+    import numpy as np
+    dump = {f[:-4]: np.load(tmp_path / "dump" / f) for f in os.listdir(tmp_path / "dump")}
+    assert sorted(dump) == sorted(DUMP_SHAPES) and all(a.dtype == np.float32 for a in dump.values())
+    shapes = {k: tuple({"N": 3000, "H": 96, "W": 144, "T": 6 * 9}.get(x, x) for x in v) for k, v in DUMP_SHAPES.items()}
+    assert {k: a.shape for k, a in dump.items()} == shapes
+    assert all(np.isfinite(a).all() for a in dump.values())
+    assert int(dump["num_tiles_hit"].sum()) == d["config"]["num_intersects_rank0"]  # the projection of the last step
+    assert dump["out_img"].std() > 0.01 and np.abs(dump["adam_m_xyz"]).max() > 0 and dump["adam_v_cholesky"].min() >= 0
+
+
+def test_dumped_outputs_repeat_from_run_to_run_and_follow_steps(tmp_path):
+    """The same arguments give the same inputs, so two runs dump the same arrays (bit for bit where it was measured, the
+    default workload; the bound here leaves room for a float sum taken in another order); another --steps trains for
+    another number of iterations and lands elsewhere."""
+    import numpy as np
+
+    def run(name, steps):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "4",
+               "--num-points", "3000", "--height", "96", "--width", "144", "--images", "0", "--no-cpu-baseline",
+               "--no-batched", "--no-static", "--no-dropin", "--dump-outputs", str(tmp_path / name)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])["steps"] == steps
+        return {k: np.load(tmp_path / name / (k + ".npy")) for k in DUMP_SHAPES}
+
+    a, b, c = run("a", 24), run("b", 24), run("c", 12)
+    for k in ("xyz", "cholesky", "features_dc", "out_img", "xys", "conics"):
+        scale = np.abs(a[k]).max()
+        assert np.abs(a[k] - b[k]).max() <= 1e-4 * scale, k
+        assert np.abs(a[k] - c[k]).max() > 1e-3 * scale, k  # 4 + 10 x 12 iterations against 4 + 10 x 24
 
 
 def test_gpus_flag_starts_the_ranks_itself():

@@ -69,3 +69,29 @@ def test_stored_counters_exist_for_the_kernels_bench_names():
         assert source.startswith("stored:"), source
     valu = bench.valu_roofline(cases[0][0], 50000, 512, 768, 18.0)
     assert valu.get("insts_per_image", 0) > 1e6, valu
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_above_the_limit(tmp_path):
+    """dump_outputs(): one float32 / float64 .npy per array; above the byte limit every array shrinks to a sample of
+    its elements that is the same from call to call, and the files stay under the limit."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    arrays = {"ids": np.arange(12, dtype=np.int32).reshape(3, 4), "img": rng.random((40, 60, 3)).astype(np.float32),
+              "wide": rng.random((500, 2))}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["ids", "img", "wide"]
+    assert got["ids"].dtype == np.float32 and got["img"].dtype == np.float32 and got["wide"].dtype == np.float64
+    assert all(np.array_equal(got[k], arrays[k]) for k in arrays)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, suffix="_rank1", limit=9000)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["ids_rank1.npy", "img_rank1.npy", "wide_rank1.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= 9000
+    for f in files:
+        a, b = np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f)
+        full = arrays[f[:-len("_rank1.npy")]]
+        assert a.ndim == 1 and 0 < a.size < full.size and np.array_equal(a, b)
+        assert np.isin(a, full.astype(a.dtype)).all()
