@@ -73,6 +73,10 @@ SIGNATURES.update({
     "gi2d_quant_compress": [_p, _i, _p, _p, _p, _p, _p],
     "gi2d_quant_decompress": [_p, _i, _p, _p, _p, _p],
     "gi2d_quant_half": [_sz, _p, _p, _p],
+    # packed stream (gaussianimage_plus_amd/codec.py)
+    "gi2d_codec_pack": [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p],
+    "gi2d_codec_decode_bin": [_i, _i, _i, _i, _i, _i, _p, _p, _sz, _f, _u, _u, _i, _i, _f, _p, _p, _p, _p, _p, _p, _sz,
+                              _p, _p],
 })
 SIZE_FUNCS = {
     "gi2d_fast_workspace_bytes": [_i, _i, _i],
@@ -83,6 +87,7 @@ SIZE_FUNCS = {
     "gi2d_densify_scratch_bytes": [_p, _i],
     "gi2d_batch_bytes": [_i],
     "gi2d_train_inbox_bytes": [_i, _i],
+    "gi2d_codec_payload_bytes": [_i, _i, _i, _i, _i, _i],
 }
 STRING_FUNCS = ["gi2d_version", "gi2d_last_error_string"]
 

@@ -53,7 +53,7 @@ static std::string dev_switches() {
 extern "C" {
 const char *gi2d_version(void) {
     static const std::string v = [] {
-        std::string s = "gi2d 0.2.0 (gfx950)";
+        std::string s = "gi2d 0.3.0 (gfx950)";
         const std::string d = gi2d::dev_switches();
         if (!d.empty()) s += " dev[" + d + "]";
         return s;

@@ -1,0 +1,268 @@
+// Packed bitstream of a fitted image (include/gi2d.h "packed stream"; the format table is in INTEGRATION.md):
+//
+//   pack        integer codes of the 8 channels (the float tensors compress_wo_ec() returns) -> payload dwords.  One
+//               workgroup packs 256 records: they are exactly 8 R dwords and start dword-aligned, so the group is ORed
+//               together in LDS (a field touches one or two dwords) and leaves as coalesced dword stores -- no global
+//               atomic, no pre-zeroed buffer, every payload dword written exactly once.  Once per image: not a hot path.
+//   decode+bin  one lane per gaussian: reads its record (at most five aligned dwords, 64 lanes = 2 R contiguous dwords),
+//               peels the fields off with funnel shifts, dequantises with the quantisers' own arithmetic (quant_dequant),
+//               projects (project_values) and bins (bin_projected) -- the front of the fused fast path with the stream in
+//               place of the parameter arrays.  gi2d_fast_rasterize_forward on the same workspace draws the picture.
+//
+// Nothing here is read through a pointer computed from stream CONTENT: record positions follow from (N, R) alone, and
+// every load index is clamped to the dwords the entry has checked the payload to hold.
+#include <string>
+
+#include "gi2d_fast_internal.h"
+#include "gi2d_quant_core.h"
+
+namespace gi2d {
+
+#define GI2D_CODEC_FIELDS 8
+#define GI2D_CODEC_MAX_RECORD 128                                  /* bits */
+#define GI2D_CODEC_MAX_LOADS ((31 + GI2D_CODEC_MAX_RECORD + 31) / 32) /* dwords a record can touch: 5 */
+#define GI2D_CODEC_PACK_BLOCK 256
+
+// Field layout of a record, the same for every gaussian of a stream (kernel argument: scalar registers).
+struct CodecLayout {
+    int width[GI2D_CODEC_FIELDS];  // bits per field, record order
+    int qmin[GI2D_CODEC_FIELDS];   // stored value = code - qmin (non-zero for the signed rotation only)
+    int record_bits;               // R
+    int loads;                     // ceil((31 + R) / 32)
+};
+struct CodecSide {
+    float scale[GI2D_CODEC_FIELDS], beta[GI2D_CODEC_FIELDS];
+};
+
+// ---------------------------------------------------------------------------------------------------------- pack
+// codes: xy f32[N,2], p0 f32[N,3] (covariance rows) or f32[N,2] (scaling), p1 f32[N] (rotation; scale-rot only),
+// rgb f32[N,3].  Field k of record g: value (int)code - qmin, masked to its width.
+template <int KIND>
+__global__ __launch_bounds__(GI2D_CODEC_PACK_BLOCK) void codec_pack_kernel(
+    int n, CodecLayout lay, const float *__restrict__ xy, const float *__restrict__ p0, const float *__restrict__ p1,
+    const float *__restrict__ rgb, uint32_t *__restrict__ payload, long long total_dwords) {
+    __shared__ uint32_t grp[GI2D_CODEC_PACK_BLOCK * GI2D_CODEC_MAX_RECORD / 32];
+    const int tid = threadIdx.x;
+    const int group_dwords = GI2D_CODEC_PACK_BLOCK / 32 * lay.record_bits;
+    for (int i = tid; i < group_dwords; i += GI2D_CODEC_PACK_BLOCK) grp[i] = 0u;
+    __syncthreads();
+    const long long g = (long long)blockIdx.x * GI2D_CODEC_PACK_BLOCK + tid;
+    if (g < n) {
+        float c[GI2D_CODEC_FIELDS];
+        c[0] = xy[2 * g], c[1] = xy[2 * g + 1];
+        if (KIND == kScaleRot)
+            c[2] = p0[2 * g], c[3] = p0[2 * g + 1], c[4] = p1[g];
+        else
+            c[2] = p0[3 * g], c[3] = p0[3 * g + 1], c[4] = p0[3 * g + 2];
+        c[5] = rgb[3 * g], c[6] = rgb[3 * g + 1], c[7] = rgb[3 * g + 2];
+        int bit = tid * lay.record_bits;  // within the group: < 256 * 128
+#pragma unroll
+        for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
+            const int w = lay.width[k];
+            const uint32_t v = (uint32_t)((int)c[k] - lay.qmin[k]) & ((1u << w) - 1u);
+            const int d = bit >> 5, s = bit & 31;
+            atomicOr(&grp[d], v << s);
+            if (s + w > 32) atomicOr(&grp[d + 1], v >> (32 - s));
+            bit += w;
+        }
+    }
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * group_dwords;
+    for (int i = tid; i < group_dwords; i += GI2D_CODEC_PACK_BLOCK)
+        if (base + i < total_dwords) payload[base + i] = grp[i];  // (the last group: zero padding up to the dword)
+}
+
+// ---------------------------------------------------------------------------------------------------- decode + bin
+// The low `w` bits of the 128-bit little-endian number r, which is then shifted right by w (w <= 16).
+__device__ __forceinline__ uint32_t codec_take(uint32_t (&r)[4], int w) {
+    const uint32_t v = r[0] & ((1u << w) - 1u);
+    r[0] = __builtin_amdgcn_alignbit(r[1], r[0], (uint32_t)w);
+    r[1] = __builtin_amdgcn_alignbit(r[2], r[1], (uint32_t)w);
+    r[2] = __builtin_amdgcn_alignbit(r[3], r[2], (uint32_t)w);
+    r[3] >>= w;
+    return v;
+}
+
+struct CodecOut {  // optional per-gaussian outputs (all may be NULL)
+    float2 *xys;
+    int32_t *radii;
+    float *conics;
+    int32_t *num_tiles_hit;
+    float *colors;
+};
+
+template <int KIND>
+__global__ __launch_bounds__(256) void codec_decode_bin_kernel(
+    int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
+    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, CodecOut out, BinTarget bt) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    begin_binning(g, bt.status);
+    const BinRecs recs = recs_for_binning(bt.recs, g == 0);
+    if (g >= n) return;
+    const PrevBox old_box = bt.prev_box[g];
+    // the record: dwords first, first + 1, ... (all requested before the first use; `loads` is the same for every lane)
+    const long long bit0 = (long long)g * lay.record_bits;
+    const long long first = bit0 >> 5;
+    uint32_t w[GI2D_CODEC_MAX_LOADS];
+#pragma unroll
+    for (int j = 0; j < GI2D_CODEC_MAX_LOADS; ++j) {
+        const long long d = first + j;
+        w[j] = j < lay.loads ? payload[d < last_dword ? d : last_dword] : 0u;
+    }
+    const uint32_t s0 = (uint32_t)bit0 & 31u;
+    uint32_t r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], s0);
+    float v[GI2D_CODEC_FIELDS];
+#pragma unroll
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
+        const float code = (float)((int)codec_take(r, lay.width[k]) + lay.qmin[k]);
+        // the variances of a covariance row are log-quantised (HybirdQuant), everything else is LSQ
+        v[k] = (KIND == kCovariance && (k == 2 || k == 4)) ? quant_dequant<GI2D_QUANT_LOG>(code, side.scale[k], side.beta[k])
+                                                          : quant_dequant<GI2D_QUANT_LSQ>(code, side.scale[k], side.beta[k]);
+    }
+    const ProjOut o = project_values<KIND>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h, tiles_x,
+                                           tiles_y, radius_clip);
+    if (out.xys) out.xys[g] = o.xy;
+    if (out.radii) out.radii[g] = o.radius;
+    if (out.conics) out.conics[3 * g] = o.k0, out.conics[3 * g + 1] = o.k1, out.conics[3 * g + 2] = o.k2;
+    if (out.num_tiles_hit) out.num_tiles_hit[g] = o.tiles_hit;
+    if (out.colors) out.colors[3 * g] = v[5], out.colors[3 * g + 1] = v[6], out.colors[3 * g + 2] = v[7];
+    bin_projected(g, o, 1.f, v[5], v[6], v[7], tiles_x, tiles_y, radius_clip, old_box, bt.prev_box, bt.lists, recs);
+}
+
+// Layout of a stream's records from its header fields; false (and the error set) if they are not a valid format-1 layout.
+static bool codec_layout(const char *what, int kind, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                         CodecLayout &lay) {
+    if (kind != kCovariance && kind != kScaleRot) {
+        set_error((std::string(what) + ": model kind must be 1 (covariance) or 2 (scale-rot)").c_str());
+        return false;
+    }
+    const bool rs = kind == kScaleRot;
+    const int bits[4] = {xy_bits, p0_bits, rs ? p1_bits : 1, color_bits};
+    for (int b : bits)
+        if (b < 1 || b > 16) {
+            set_error((std::string(what) + ": field widths must be 1..16 bits").c_str());
+            return false;
+        }
+    if (!rs && p1_bits != 0) {
+        set_error((std::string(what) + ": the covariance model has no rotation field (its width must be 0)").c_str());
+        return false;
+    }
+    const int width[GI2D_CODEC_FIELDS] = {xy_bits, xy_bits, p0_bits, p0_bits, rs ? p1_bits : p0_bits,
+                                          color_bits, color_bits, color_bits};
+    lay.record_bits = 0;
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
+        lay.width[k] = width[k];
+        lay.qmin[k] = 0;
+        lay.record_bits += width[k];
+    }
+    if (rs) lay.qmin[4] = -(1 << (p1_bits - 1));  // the rotation quantiser is signed
+    lay.loads = (31 + lay.record_bits + 31) / 32;
+    if (lay.record_bits > GI2D_CODEC_MAX_RECORD) {
+        set_error((std::string(what) + ": a record is more than 128 bits").c_str());
+        return false;
+    }
+    return true;
+}
+static inline long long codec_dwords(long long n, int record_bits) { return (n * record_bits + 31) / 32; }
+
+}  // namespace gi2d
+
+using namespace gi2d;
+
+extern "C" {
+
+size_t gi2d_codec_payload_bytes(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits) {
+    CodecLayout lay;
+    if (n < 0 || !codec_layout("codec payload bytes", kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return 0;
+    return (size_t)codec_dwords(n, lay.record_bits) * 4;
+}
+
+int gi2d_codec_pack(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, const float *code_xy,
+                    const float *code_p0, const float *code_p1, const float *code_rgb, void *payload,
+                    size_t payload_bytes, gi2d_stream_t st) {
+    CodecLayout lay;
+    if (!codec_layout("codec pack", kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 0) {
+        set_error("codec pack: negative size");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    const long long need = codec_dwords(n, lay.record_bits);
+    if (payload_bytes < (size_t)need * 4) {
+        set_error("codec pack: payload buffer smaller than 4 * ceil(N * R / 32) bytes");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    if (n == 0) return GI2D_OK;
+    if (!code_xy || !code_p0 || !code_rgb || !payload || (kind == kScaleRot && !code_p1) || ((uintptr_t)payload & 3)) {
+        set_error("codec pack: null or misaligned pointer");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    const dim3 grid((unsigned)((n + GI2D_CODEC_PACK_BLOCK - 1) / GI2D_CODEC_PACK_BLOCK)), block(GI2D_CODEC_PACK_BLOCK);
+    if (kind == kCovariance)
+        hipLaunchKernelGGL(codec_pack_kernel<kCovariance>, grid, block, 0, (hipStream_t)st, n, lay, code_xy, code_p0,
+                           code_p1, code_rgb, (uint32_t *)payload, need);
+    else
+        hipLaunchKernelGGL(codec_pack_kernel<kScaleRot>, grid, block, 0, (hipStream_t)st, n, lay, code_xy, code_p0,
+                           code_p1, code_rgb, (uint32_t *)payload, need);
+    return check_launch("codec pack");
+}
+
+int gi2d_codec_decode_bin(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                          const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
+                          unsigned h, unsigned w_, int tiles_x, int tiles_y, float radius_clip, float *xys,
+                          int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors, void *ws,
+                          size_t ws_bytes, int32_t *status, gi2d_stream_t st) {
+    CodecLayout lay;
+    if (!codec_layout("codec decode", kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 0 || tiles_x < 0 || tiles_y < 0) {
+        set_error("codec decode: negative size");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    const long long need = codec_dwords(n, lay.record_bits);
+    if (payload_bytes < (size_t)need * 4) {
+        set_error("codec decode: payload shorter than 4 * ceil(N * R / 32) bytes");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    if (!side_host || !status || !ws || (n > 0 && (!payload || ((uintptr_t)payload & 3)))) {
+        set_error("codec decode: null or misaligned pointer");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    if ((long long)tiles_x * GI2D_TILE < (long long)w_ || (long long)tiles_y * GI2D_TILE < (long long)h) {
+        set_error("codec decode: tile grid does not cover the image");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    if ((long long)tiles_x * tiles_y * GI2D_FAST_LROW > 0x7fffffffLL || (long long)n * GI2D_FAST_S > 0x7fffffffLL ||
+        tiles_x > 0xffff || tiles_y > 0xffff) {
+        set_error("codec decode: problem too large for 32-bit slot indices");
+        return GI2D_ERR_UNSUPPORTED;
+    }
+    if (ws_bytes < carve_fast(nullptr, n, tiles_x * tiles_y).bytes) {
+        set_error("codec decode: workspace too small");
+        return GI2D_ERR_WORKSPACE_TOO_SMALL;
+    }
+    CodecSide side;
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) side.scale[k] = side_host[2 * k], side.beta[k] = side_host[2 * k + 1];
+    FastWs w = carve_fast(ws, n, tiles_x * tiles_y);
+    BinTarget bt;
+    bt.colors = bt.opacities = nullptr;  // colour comes from the record, opacity is 1
+    bt.prev_box = w.prev_box;
+    bt.lists = w.lists;
+    bt.recs = rec_sets(w, n);
+    bt.status = status;
+    const CodecOut out{(float2 *)xys, radii, conics, num_tiles_hit, colors};
+    const int bs = per_gaussian_block(n);
+    const dim3 grid((n + bs - 1) / bs > 0 ? (n + bs - 1) / bs : 1), block(bs);
+    const long long last = need > 0 ? need - 1 : 0;
+    if (kind == kCovariance)
+        hipLaunchKernelGGL(codec_decode_bin_kernel<kCovariance>, grid, block, 0, (hipStream_t)st, n, lay, side,
+                           (const uint32_t *)payload, last, clip_coe, (float)w_, (float)h, tiles_x, tiles_y,
+                           radius_clip, out, bt);
+    else
+        hipLaunchKernelGGL(codec_decode_bin_kernel<kScaleRot>, grid, block, 0, (hipStream_t)st, n, lay, side,
+                           (const uint32_t *)payload, last, clip_coe, (float)w_, (float)h, tiles_x, tiles_y,
+                           radius_clip, out, bt);
+    return check_launch("codec decode");
+}
+
+}  // extern "C"

@@ -31,35 +31,36 @@ struct ProjOut {
     int mnx, mny, mxx, mxy;  // tile box (valid when tiles_hit > 0)
 };
 
-// foward2d.cu:12-69 / :130-187 / :192-288 for gaussian idx; culled gaussians give all-zero outputs.
+// foward2d.cu:12-69 / :130-187 / :192-288 on VALUES: the mean m and the gaussian's three shape numbers -- (l11, l21, l22)
+// Cholesky, (cxx, cxy, cyy) covariance, (scale x, scale y, rotation) scale-rot; culled gaussians give all-zero outputs.
+// project_one below feeds it from arrays; a kernel that forms the numbers itself (the stream decoder, gi2d_codec.hip)
+// calls it directly.
 template <int KIND>
-__device__ __forceinline__ ProjOut project_one(int idx, float clip_coe, const float2 *__restrict__ means2d,
-                                               const float *__restrict__ p0, const float *__restrict__ p1,
-                                               float img_w, float img_h, int tiles_x, int tiles_y,
-                                               float radius_clip) {
+__device__ __forceinline__ ProjOut project_values(float clip_coe, const float2 m, float q0, float q1, float q2,
+                                                  float img_w, float img_h, int tiles_x, int tiles_y,
+                                                  float radius_clip) {
 #pragma clang fp contract(off)
-    const float2 m = means2d[idx];
     float cx, cy, cxx, cxy, cyy;
     if (KIND == kCholesky) {  // foward2d.cu:41-48
         cx = 0.5f * img_w * m.x + 0.5f * img_w;
         cy = 0.5f * img_h * m.y + 0.5f * img_h;
-        const float l11 = p0[3 * idx], l21 = p0[3 * idx + 1], l22 = p0[3 * idx + 2];
+        const float l11 = q0, l21 = q1, l22 = q2;
         cxx = l11 * l11;
         cxy = l11 * l21;
         cyy = l21 * l21 + l22 * l22;
     } else if (KIND == kCovariance) {  // foward2d.cu:226-236
         cx = m.x;
         cy = m.y;
-        cxx = p0[3 * idx];
-        cxy = p0[3 * idx + 1];
-        cyy = p0[3 * idx + 2];
+        cxx = q0;
+        cxy = q1;
+        cyy = q2;
     } else {  // foward2d.cu:155-164, helpers.cuh:579-598
         cx = m.x;
         cy = m.y;
-        const float rot = p1[idx];
+        const float rot = q2;
         const float c = cosf(rot), s = sinf(rot);
         const M2 R{{c, -s, s, c}};
-        const M2 S{{p0[2 * idx], 0.f, 0.f, p0[2 * idx + 1]}};
+        const M2 S{{q0, 0.f, 0.f, q1}};
         const M2 M = mul(R, S);
         const M2 T = mul(M, tr(M));
         cxx = T.v[0];
@@ -85,6 +86,27 @@ __device__ __forceinline__ ProjOut project_one(int idx, float clip_coe, const fl
         if (area > 0) o.tiles_hit = area;
     }
     return o;
+}
+
+// The same for gaussian idx of the operator's input arrays (p0: 3 floats per gaussian, or 2 scales with the rotation
+// in p1).
+template <int KIND>
+__device__ __forceinline__ ProjOut project_one(int idx, float clip_coe, const float2 *__restrict__ means2d,
+                                               const float *__restrict__ p0, const float *__restrict__ p1,
+                                               float img_w, float img_h, int tiles_x, int tiles_y,
+                                               float radius_clip) {
+    const float2 m = means2d[idx];
+    float q0, q1, q2;
+    if (KIND == kScaleRot) {
+        q2 = p1[idx];
+        q0 = p0[2 * idx];
+        q1 = p0[2 * idx + 1];
+    } else {
+        q0 = p0[3 * idx];
+        q1 = p0[3 * idx + 1];
+        q2 = p0[3 * idx + 2];
+    }
+    return project_values<KIND>(clip_coe, m, q0, q1, q2, img_w, img_h, tiles_x, tiles_y, radius_clip);
 }
 
 // helpers.cuh:384-395 cov2d_to_conic_vjp

@@ -133,8 +133,9 @@ __global__ __launch_bounds__(256) void quant_decompress_kernel(QuantSpecDev sp, 
     if (r >= n) return;
     for (int c = 0; c < sp.channels; ++c) {
         const size_t i = (size_t)r * sp.channels + c;
-        const float lin = code[i] * params[4 * c] + params[4 * c + 1];
-        out[i] = sp.kind[c] == GI2D_QUANT_LOG ? expf(lin) : lin;
+        const float v = code[i], scale = params[4 * c], beta = params[4 * c + 1];
+        out[i] = sp.kind[c] == GI2D_QUANT_LOG ? quant_dequant<GI2D_QUANT_LOG>(v, scale, beta)
+                                              : quant_dequant<GI2D_QUANT_LSQ>(v, scale, beta);
     }
 }
 

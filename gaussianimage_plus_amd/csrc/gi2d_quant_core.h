@@ -13,6 +13,16 @@ namespace gi2d {
 
 __device__ __forceinline__ float quant_log_of(float x) { return logf(fabsf(x) + GI2D_QUANT_LOG_EPS); }
 
+// code -> value: UniformQuantizer.decompress :154-156 / LogQuantizer.decompress :257-259.  The one place this is written
+// down: quant_eval, the stand-alone decompress kernel (gi2d_quant.hip) and the stream decoder (gi2d_codec.hip) all call
+// it, so a decoded stream carries the very bits the fit was trained on.
+template <int KIND>
+__device__ __forceinline__ float quant_dequant(float code, float scale, float beta) {
+#pragma clang fp contract(off)
+    const float lin = code * scale + beta;
+    return KIND == GI2D_QUANT_LOG ? expf(lin) : lin;
+}
+
 struct QuantEval {
     float raw;      // (t - beta) / scale before the clamp, t = x (LSQ) or log(|x| + 1e-6) (log)
     float code;     // round(clamp(raw))  -- the value ste() yields
@@ -28,8 +38,7 @@ __device__ __forceinline__ QuantEval quant_eval(float x, float scale, float beta
     e.raw = (t - beta) / scale;
     e.inside = e.raw >= qmin && e.raw <= qmax;
     e.code = rintf(fminf(fmaxf(e.raw, qmin), qmax));
-    const float lin = e.code * scale + beta;
-    e.dequant = KIND == GI2D_QUANT_LOG ? expf(lin) : lin;
+    e.dequant = quant_dequant<KIND>(e.code, scale, beta);
     return e;
 }
 

@@ -675,6 +675,12 @@ class NativeFitter:
             out["bpp_wc"] = out["position_bpp"] + out["cholesky_bpp_wc"] + out["feature_dc_bpp_wc"]
         return out
 
+    def encode(self) -> bytes:
+        """The packed stream of the quantised model (gaussianimage_plus_amd/codec.py): codec.decode() turns it back into
+        the picture decompress_wo_ec() renders, in any process."""
+        from . import codec
+        return codec.encode(self)
+
     # ------------------------------------------------------------------ rotation-scale codec
     def _compress_wo_ec_rs(self) -> Dict[str, torch.Tensor]:
         """models/gaussianimage_rs.py:486-495 by intent: integer codes of every attribute.  (As written the model file

@@ -578,6 +578,38 @@ int gi2d_quant_decompress(const gi2d_quant_spec *spec_host, int num_rows, const 
                           const float *params, float *out, gi2d_stream_t stream);
 int gi2d_quant_half(size_t count, const float *x, float *y, gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ packed stream of a fitted image (format 1)
+ * What turns the integer codes of a quantised fit (NativeFitter.compress_wo_ec) into bytes and bytes into a picture
+ * without the fitter: gaussianimage_plus_amd/codec.py wraps these calls and owns the 40-byte header + 64 bytes of side
+ * information in front of the payload (INTEGRATION.md has the table).  A record is the 8 fields of one gaussian,
+ *   kind 1 (covariance)  x, y | a, b, c | r, g, b    widths xy, p0, p0, p0, colour; a, c log-quantised, b LSQ (HybirdQuant)
+ *   kind 2 (scale-rot)   x, y | sx, sy | rot | r, g, b   widths xy, p0, p0, p1, colour; rot SIGNED (stored as code - qmin)
+ * R = sum of the widths <= 128 bits (each 1..16; p1_bits = 0 for kind 1); record g starts at payload bit g * R, payload
+ * bit i is bit i & 31 of little-endian dword i >> 5, fields LSB-first; the payload is 4 * ceil(N * R / 32) bytes
+ * (gi2d_codec_payload_bytes; 0 for an invalid layout).  Every entry checks its arguments before it launches anything.
+ *   gi2d_codec_pack        code_xy f32[N,2], code_p0 f32[N,3] (kind 1) or f32[N,2] (kind 2), code_p1 f32[N] (kind 2),
+ *                          code_rgb f32[N,3] -- integer codes as floats, on the device -> the payload's dwords (every one
+ *                          written; `payload` 4-byte aligned, payload_bytes >= the size above).
+ *   gi2d_codec_decode_bin  the binning call of the fused fast path fed from a stream: per gaussian, record -> codes ->
+ *                          code * scale + beta (exp of that on the log channels: gi2d_quant_decompress's arithmetic) ->
+ *                          projection (gi2d_project_gaussians_2d_covariance_forward / _scale_rot_forward) -> binning step
+ *                          with the record's colour and opacity 1, in ONE launch.  side_host: HOST f32[16], (scale, beta)
+ *                          of the 8 fields in record order (the stream's side information as it stands).  workspace /
+ *                          status as for gi2d_fast_project_bin (same contract: gi2d_fast_workspace_init first,
+ *                          gi2d_fast_rasterize_forward behind it; a tile row overflow is reported by that tile pass and
+ *                          answered with gi2d_bin_gaussians + the plain ops).  xys f32[N,2], radii i32[N], conics
+ *                          f32[N,3], num_tiles_hit i32[N], colors f32[N,3]: optional outputs (NULL = not wanted).
+ *                          No load address depends on the payload's content, and none lies beyond payload_bytes. */
+size_t gi2d_codec_payload_bytes(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits);
+int gi2d_codec_pack(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                    const float *code_xy, const float *code_p0, const float *code_p1, const float *code_rgb,
+                    void *payload, size_t payload_bytes, gi2d_stream_t stream);
+int gi2d_codec_decode_bin(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                          const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
+                          unsigned img_height, unsigned img_width, int tiles_x, int tiles_y, float radius_clip,
+                          float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors,
+                          void *workspace, size_t workspace_bytes, int32_t *status, gi2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

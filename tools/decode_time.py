@@ -1,0 +1,99 @@
+"""Decode time of a packed stream (gaussianimage_plus_amd/codec.py) on one 768x512 picture: one JSON line.
+
+For N = 5 000 and N = 50 000 (covariance model, 12 / 10 / 6 bits), microseconds per decode
+    device  payload already on the device (Decoder.upload): workspace reset + decode/bin + forward + clamp
+    bytes   from host bytes: header parse, CRC, one host-to-device copy, the same launches
+    legacy  the same encoding through NativeFitter.decompress_wo_ec (quantiser decompress launches, the projection and
+            rasterize operators with their allocations)
+each the median of five timed regions after warm-up.  A region is a host clock around `reps` back-to-back decodes that
+ends in a device synchronise: no event pairs inside it (a pair costs the queue about 5 us per dispatch).
+The gaussians are those of a short quantised fit, so tile populations are a real picture's.
+
+    python tools/decode_time.py [--reps 200] [--trace]
+--trace decodes a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for
+the per-kernel split (profiles/decode_kernel_stats.csv).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from gaussianimage_plus_amd import _lib, codec  # noqa: E402
+from gaussianimage_plus_amd.launch import synthetic_image  # noqa: E402
+from gaussianimage_plus_amd.trainer import NativeFitter  # noqa: E402
+
+H, W = 512, 768
+
+
+def fitted(n, iters):
+    gt = synthetic_image(H, W, 3).cuda()
+    fit = NativeFitter(gt, num_points=n, kind="covariance", lr=0.018, eps=1e-15, track_best=True)
+    fit.train(iters)
+    fit.load_best()
+    fit.enable_quantize(12, 10, 6)
+    fit.train(iters)
+    fit.check_status()
+    fit.load_best()
+    return fit, gt
+
+
+def median_us(fn, reps, regions=5):
+    for _ in range(max(10, reps // 10)):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(regions):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) / reps * 1e6)
+    return statistics.median(out), min(out), max(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[5000, 50000])
+    ap.add_argument("--trace", action="store_true")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "decode_time.py needs the GPU"
+    res = {"tool": "decode_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
+           "bits": [12, 10, 6], "reps": a.reps, "regions": 5, "sizes": {}}
+    for n in a.sizes:
+        fit, gt = fitted(n, a.iters)
+        fit.compress_wo_ec()  # drops what its covariance check drops from the model: the next two calls see one population
+        blob = fit.encode()
+        enc = fit.compress_wo_ec()
+        dec = codec.Decoder("cuda:0")
+        up = dec.upload(blob)
+        out = torch.empty(H, W, 3, device="cuda:0")
+        want = fit.decompress_wo_ec(enc)
+        assert torch.equal(dec.decode(up, out=out), want) and torch.equal(dec.decode(blob), want)
+        if a.trace:
+            for _ in range(50):
+                dec.decode(up, out=out)
+            torch.cuda.synchronize()
+            continue
+        info = codec.info(blob)
+        row = {"gaussians": fit.n, "stream_bytes": len(blob), "bpp": round(info["bpp"], 5),
+               "psnr_db": round(10 * torch.log10(1.0 / torch.nn.functional.mse_loss(want, gt)).item(), 3)}
+        for key, fn in (("device", lambda: dec.decode(up, out=out)), ("bytes", lambda: dec.decode(blob, out=out)),
+                        ("legacy", lambda: fit.decompress_wo_ec(enc))):
+            med, lo, hi = median_us(fn, a.reps)
+            row[key + "_us"] = round(med, 2)
+            row[key + "_us_range"] = [round(lo, 2), round(hi, 2)]
+        row["decodes_per_second_device"] = round(1e6 / row["device_us"], 1)
+        res["sizes"][str(n)] = row
+    if not a.trace:
+        print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

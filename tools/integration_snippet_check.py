@@ -1,4 +1,4 @@
-"""Development aid: the INTEGRATION.md section 5 snippets, run end to end on a small image."""
+"""Development aid: the INTEGRATION.md section 5 and 6 snippets, run end to end on a small image."""
 import sys; import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from gaussianimage_plus_amd.launch import synthetic_image
@@ -9,6 +9,12 @@ for _ in fit.fit_quantize_schedule(600, warmup_iter=400, bits=(12, 10, 6), prune
     pass
 fit.check_status(); print("best", fit.load_best())
 enc = fit.compress_wo_ec(); img = fit.decompress_wo_ec(enc); print(fit.analysis_wo_ec(enc, entropy_estimate=True))
+# INTEGRATION.md section 6 "Packed stream"
+from gaussianimage_plus_amd import codec
+blob = fit.encode(); codec.save("/tmp/picture.gi2d", blob); print("stream", len(blob), "bytes, bpp", codec.info(blob)["bpp"])
+img2 = codec.decode(codec.load("/tmp/picture.gi2d"), device="cuda:0")
+assert torch.equal(img2, fit.decompress_wo_ec(fit.compress_wo_ec()))
+assert len(codec.Decoder("cuda:0").decode_many([blob, blob])) == 2
 import gaussianimage_plus_amd.quantize as q
 sys.modules["quantize"] = q
 from quantize import *
