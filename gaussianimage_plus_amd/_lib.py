@@ -77,6 +77,10 @@ SIGNATURES.update({
     "gi2d_codec_pack": [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p],
     "gi2d_codec_decode_bin": [_i, _i, _i, _i, _i, _i, _p, _p, _sz, _f, _u, _u, _i, _i, _f, _p, _p, _p, _p, _p, _p, _sz,
                               _p, _p],
+    # rANS payload (payload coding 1)
+    "gi2d_codec_histogram": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p],
+    "gi2d_codec_rans_encode": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _sz, _p, _sz, _p, _p],
+    "gi2d_codec_rans_expand": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _p, _sz, _sz, _p, _sz, _p, _i, _p],
 })
 SIZE_FUNCS = {
     "gi2d_fast_workspace_bytes": [_i, _i, _i],
@@ -88,6 +92,7 @@ SIZE_FUNCS = {
     "gi2d_batch_bytes": [_i],
     "gi2d_train_inbox_bytes": [_i, _i],
     "gi2d_codec_payload_bytes": [_i, _i, _i, _i, _i, _i],
+    "gi2d_codec_rans_scratch_bytes": [_i, _i, _i, _i, _i, _i, _i, _u],
 }
 STRING_FUNCS = ["gi2d_version", "gi2d_last_error_string"]
 

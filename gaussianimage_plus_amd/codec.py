@@ -7,6 +7,8 @@
     img  = dec.decode(blob, out=None)
     imgs = dec.decode_many(blobs)
     codec.save(path, blob); blob = codec.load(path)
+    small = codec.encode(fitter, coding="rans")  # the same codes, entropy coded (payload coding 1); decodes the same way
+    small = codec.recode(blob, "rans"); codec.recode(small, "fixed") == blob
 
 Decoding needs no fitter, no target image and no optimizer state: this module imports neither `trainer` nor `quantize`.
 A decode is three native launches on buffers the Decoder owns -- gi2d_fast_workspace_init, gi2d_codec_decode_bin
@@ -18,12 +20,19 @@ one 16x16 tile) is rendered again through the capacity-free ops, so a valid stre
 Format version 1 (little-endian; INTEGRATION.md "Packed stream" has the record layout):
 
     0  magic "GI2D" | 4 version = 1 | 5 model kind (1 covariance, 2 scale-rot) | 6 payload coding (0 = fixed-length
-       fields) | 7 reserved (0) | 8 u32 width, u32 height | 16 u32 N | 20 u8 bits[4]: xy, cov / scaling, rotation (0 for
+       fields, 1 = rANS container, below) | 7 reserved (0) | 8 u32 width, u32 height | 16 u32 N | 20 u8 bits[4]: xy, cov / scaling, rotation (0 for
        covariance), colour | 24 f32 clip_coe, f32 radius_clip | 32 u32 payload bytes | 36 u32 CRC-32 (zlib) of side
        information + payload | 40 side information: (scale, beta) f32 pairs of the 8 fields | 104 payload
 
-Everything in a header is validated on the host before a byte reaches the GPU (ValueError), and the kernels compute no
-address from stream content.
+Payload coding 1 carries the integers of coding 0 entropy coded (INTEGRATION.md has the container table): a field of
+width w is split into hi = v >> max(0, w - 8), a symbol of a 12-bit rANS model stored in the stream, and raw low bits; a
+chunk of 2^k records (k = 8..12) is one wave's work, one coder state per lane over a shared stream of 16-bit words.
+gi2d_codec_rans_expand (csrc/gi2d_rans.hip) turns the chunks back into the coding-0 payload in a buffer the Decoder owns,
+and the launches above run on it unchanged: the picture is that of the coding-0 stream with the same codes.
+
+Everything in a header is validated on the host before a byte reaches the GPU (ValueError) -- for coding 1 also the tag,
+the field mask, the model section, the chunk directory and every chunk's size against N and the widths -- and the
+kernels compute no address from stream content that is not masked or clamped to the stream's own buffers.
 """
 from __future__ import annotations
 
@@ -45,6 +54,15 @@ SIDE_BYTES = 64
 KIND_COVARIANCE, KIND_SCALE_ROT = 1, 2  # ProjKind numbering of the C ABI
 _KIND_NAMES = {KIND_COVARIANCE: "covariance", KIND_SCALE_ROT: "scale_rot"}
 _HEADER = struct.Struct("<4sBBBBIII4BffII")
+CODING_FIXED, CODING_RANS = 0, 1
+_CODING_NAMES = {CODING_FIXED: "fixed", CODING_RANS: "rans"}
+RANS_TAG = b"rANS"
+RANS_VERSION = 1
+RANS_PROB_BITS = 12
+RANS_TOTAL = 1 << RANS_PROB_BITS
+RANS_TABLE_BYTES = RANS_TOTAL + 2 * 258  # device table of a coded field: u8 symbol of slot | u16 cumulative frequency
+DEFAULT_CHUNK_LOG2 = 10                  # 1024 records per chunk (README "Decode": what smaller and larger chunks cost)
+_RANS_HEAD = struct.Struct("<4sBBBBII")
 _MAX_PIXELS = 1 << 28  # a header asking for more is refused rather than turned into a workspace allocation
 _TILE = 16
 assert _HEADER.size == HEADER_BYTES
@@ -57,6 +75,171 @@ def _record_bits(kind: int, bits: Sequence[int]) -> int:
 
 def _payload_bytes(kind: int, n: int, bits: Sequence[int]) -> int:
     return 4 * ((n * _record_bits(kind, bits) + 31) // 32)
+
+
+def _widths(kind: int, bits: Sequence[int]) -> List[int]:
+    xy, p0, p1, col = bits
+    return [xy, xy, p0, p0, p1 if kind == KIND_SCALE_ROT else p0, col, col, col]
+
+
+def _coding_id(coding) -> int:
+    for cid, name in _CODING_NAMES.items():
+        if coding == cid or coding == name:
+            return cid
+    raise ValueError(f"payload coding {coding!r}: 'fixed' (0) or 'rans' (1)")
+
+
+# ------------------------------------------------------------------------------------- rANS container (pure host)
+_LOG2_Q16: List[int] = []
+
+
+def _log2_q16(v: int) -> int:
+    """floor(65536 * log2(v)) for 1 <= v <= 4096, by integer squaring: the same on every machine."""
+    if not _LOG2_Q16:
+        for x in range(RANS_TOTAL + 1):
+            if x == 0:
+                _LOG2_Q16.append(0)
+                continue
+            n = x.bit_length() - 1
+            m, r = x << (31 - n), n << 16          # m in [2^31, 2^32)
+            for i in range(16):
+                m = (m * m) >> 31                   # in [2^31, 2^33)
+                if m >> 32:
+                    m >>= 1
+                    r |= 1 << (15 - i)
+            _LOG2_Q16.append(r)
+    return _LOG2_Q16[v]
+
+
+def _normalise(counts: np.ndarray) -> np.ndarray:
+    """Counts -> frequencies that sum to 4096, every occurring symbol >= 1: floor shares, then largest remainder (ties:
+    lower symbol first); if the floor of 1 for rare symbols overshoots, the smallest remainders above 1 give back."""
+    c = counts.astype(np.int64)
+    total = int(c.sum())
+    f = c * RANS_TOTAL // total
+    rem = c * RANS_TOTAL % total
+    bumped = (c > 0) & (f == 0)
+    f[bumped] = 1
+    rem[bumped] = -1
+    sym = np.arange(len(c))
+    diff = RANS_TOTAL - int(f.sum())
+    if diff > 0:
+        order = np.lexsort((sym, -rem))            # remainder descending, symbol ascending
+        f[order[:diff]] += 1
+    while diff < 0:
+        order = [i for i in np.lexsort((sym, rem)) if f[i] > 1]
+        take = order[:-diff]
+        f[take] -= 1
+        diff += len(take)
+    return f
+
+
+def rans_model(hist, widths: Sequence[int]):
+    """Per-field model of a rANS payload from the counts of the hi parts (hist[k][s], 8 x 256; gi2d_codec_histogram or
+    numpy) -> (mask, tables): bit k of `mask` set = field k is entropy coded, tables[k] = (first symbol, frequencies as
+    int array summing to 4096) for a coded field and None for a raw one.  A field is coded when its ideal code length
+    under the normalised table plus the table's bytes is smaller than its raw hi bits.  Integer arithmetic only."""
+    hist = np.asarray(hist, dtype=np.int64).reshape(8, 256)
+    mask, tables = 0, []
+    for k, w in enumerate(widths):
+        c = hist[k]
+        hi_bits = min(int(w), 8)
+        n = int(c.sum())
+        used = np.nonzero(c)[0]
+        tables.append(None)
+        if n == 0 or used[-1] >= (1 << hi_bits):
+            if n:
+                raise ValueError(f"rans_model: field {k} of {w} bits has symbols beyond {(1 << hi_bits) - 1}")
+            continue
+        first, a = int(used[0]), int(used[-1] - used[0] + 1)
+        f = _normalise(c[first:first + a])
+        cost_q16 = sum(int(c[first + i]) * ((RANS_PROB_BITS << 16) - _log2_q16(int(f[i]))) for i in range(a) if f[i])
+        entry_bytes = (6 + 2 * a + 3) & ~3
+        if ((cost_q16 + 0xFFFF) >> 16) + 8 * entry_bytes < n * hi_bits:
+            mask |= 1 << k
+            tables[k] = (first, f)
+    return mask, tables
+
+
+def _rans_head(n: int, widths: Sequence[int], chunk_log2: int, mask: int, tables) -> bytes:
+    """Container header + model section of a rANS payload."""
+    model = b""
+    for k, w in enumerate(widths):
+        if mask >> k & 1:
+            first, f = tables[k]
+            entry = struct.pack("<BBHH", max(0, w - 8), 0, first, len(f)) + np.asarray(f, "<u2").tobytes()
+            model += entry + b"\0" * (-len(entry) % 4)
+    chunks = (n + (1 << chunk_log2) - 1) >> chunk_log2
+    return _RANS_HEAD.pack(RANS_TAG, RANS_VERSION, RANS_PROB_BITS, chunk_log2, mask, chunks, len(model)) + model
+
+
+def _rans_device_tables(widths: Sequence[int], mask: int, tables) -> np.ndarray:
+    """The device tables of the coded fields (include/gi2d.h "rANS payload"), uint8 [ncoded * 4612]."""
+    out = []
+    for k in range(8):
+        if mask >> k & 1:
+            first, f = tables[k]
+            f = np.asarray(f, np.int64)
+            cum = np.full(258, RANS_TOTAL, np.uint16)
+            cum[:first + 1] = 0
+            cum[first + 1:first + 1 + len(f)] = np.cumsum(f)
+            out.append(np.repeat(np.arange(first, first + len(f)).astype(np.uint8), f).tobytes() + cum.tobytes())
+    return np.frombuffer(b"".join(out), np.uint8)
+
+
+def _parse_rans(p: memoryview, n: int, widths: Sequence[int]) -> Dict[str, object]:
+    """The container of a rANS payload, checked in full: everything that positions data on the device."""
+    bad = lambda why: ValueError("GI2D stream: rANS payload: " + why)
+    if len(p) < _RANS_HEAD.size:
+        raise bad("shorter than its header")
+    tag, version, prob, chunk_log2, mask, chunks, model_bytes = _RANS_HEAD.unpack_from(p, 0)
+    if tag != RANS_TAG:
+        raise bad("bad tag")
+    if version != RANS_VERSION:
+        raise bad(f"container version {version} is not supported")
+    if prob != RANS_PROB_BITS:
+        raise bad(f"{prob} probability bits (this decoder reads {RANS_PROB_BITS})")
+    if not 8 <= chunk_log2 <= 12:
+        raise bad("log2(records per chunk) outside 8..12")
+    if chunks != (n + (1 << chunk_log2) - 1) >> chunk_log2:
+        raise bad("chunk count does not match N")
+    if model_bytes % 4 or _RANS_HEAD.size + model_bytes + 4 * (chunks + 1) > len(p):
+        raise bad("model section and chunk directory do not fit the payload")
+    pos, end, tables = _RANS_HEAD.size, _RANS_HEAD.size + model_bytes, [None] * 8
+    for k, w in enumerate(widths):
+        if not mask >> k & 1:
+            continue
+        if pos + 6 > end:
+            raise bad(f"the model section has no table for coded field {k}")
+        lo, zero, first, a = struct.unpack_from("<BBHH", p, pos)
+        if lo != max(0, w - 8) or zero != 0 or not 1 <= a <= 256 or first + a > 1 << (w - lo):
+            raise bad(f"bad table header of field {k}")
+        if pos + 6 + 2 * a > end:
+            raise bad(f"table of field {k} runs past the model section")
+        f = np.frombuffer(p, "<u2", a, pos + 6).astype(np.int64)
+        if int(f.sum()) != RANS_TOTAL:
+            raise bad(f"frequencies of field {k} do not sum to {RANS_TOTAL}")
+        pos += (6 + 2 * a + 3) & ~3
+        tables[k] = (first, f)
+    if pos != end:
+        raise bad("model section longer than its tables")
+    directory = np.frombuffer(p, "<u4", chunks + 1, end).astype(np.int64)
+    data_offset = end + 4 * (chunks + 1)
+    data_bytes = len(p) - data_offset
+    if directory[0] != 0 or directory[-1] != data_bytes or (np.diff(directory) < 0).any() or (directory % 4).any():
+        raise bad("chunk directory is not 0 .. chunk bytes, non-decreasing, in multiples of 4")
+    ncoded = bin(mask).count("1")
+    raw_bits = sum(max(0, w - 8) if mask >> k & 1 else w for k, w in enumerate(widths))
+    records = np.full(chunks, 1 << chunk_log2, np.int64)
+    records[-1] = n - ((chunks - 1) << chunk_log2)
+    least = 4 * (64 + (records * raw_bits + 31) // 32)
+    most = least + 4 * ((records * ncoded + 1) // 2)
+    sizes = np.diff(directory)
+    if (sizes < least).any() or (sizes > most).any():
+        raise bad("a chunk is shorter than its states and raw section, or longer than its records can make it")
+    return dict(chunk_log2=chunk_log2, coded_mask=mask, chunks=chunks, tables=tables, directory_offset=end,
+                data_offset=data_offset, data_bytes=data_bytes, max_chunk_bytes=int(sizes.max()),
+                field_modes=["rans" if mask >> k & 1 else "raw" for k in range(8)])
 
 
 def _parse(blob) -> Dict[str, object]:
@@ -74,8 +257,8 @@ def _parse(blob) -> Dict[str, object]:
         raise ValueError(f"GI2D stream: format version {version} is not supported (this decoder reads version {VERSION})")
     if kind not in _KIND_NAMES:
         raise ValueError(f"GI2D stream: model kind {kind} has no quantised form (1 covariance, 2 scale-rot)")
-    if coding != 0:
-        raise ValueError(f"GI2D stream: payload coding {coding} is not supported (0 = fixed-length fields)")
+    if coding not in _CODING_NAMES:
+        raise ValueError(f"GI2D stream: payload coding {coding} is not supported (0 = fixed-length fields, 1 = rANS)")
     if reserved != 0:
         raise ValueError("GI2D stream: reserved header byte is not 0")
     bits = (b0, b1, b2, b3)
@@ -88,8 +271,11 @@ def _parse(blob) -> Dict[str, object]:
         raise ValueError(f"GI2D stream: bad image size {width}x{height}")
     if n < 1:
         raise ValueError("GI2D stream: no gaussians")
-    if nbytes != _payload_bytes(kind, n, bits):
+    fixed_bytes = _payload_bytes(kind, n, bits)
+    if coding == CODING_FIXED and nbytes != fixed_bytes:
         raise ValueError("GI2D stream: payload size does not match N and the field widths")
+    if nbytes % 4:
+        raise ValueError("GI2D stream: payload size is not a multiple of 4")
     if len(blob) != HEADER_BYTES + SIDE_BYTES + nbytes:
         raise ValueError("GI2D stream: truncated, or trailing bytes behind the payload")
     if zlib.crc32(memoryview(blob)[HEADER_BYTES:]) & 0xFFFFFFFF != crc:
@@ -97,15 +283,22 @@ def _parse(blob) -> Dict[str, object]:
     side = struct.unpack_from("<16f", blob, HEADER_BYTES)
     if not all(math.isfinite(v) for v in side + (clip_coe, radius_clip)):
         raise ValueError("GI2D stream: non-finite quantiser parameter or clip value")
-    return dict(version=version, kind=kind, kind_name=_KIND_NAMES[kind], coding=coding, width=width, height=height,
-                num_points=n, bits=bits, clip_coe=clip_coe, radius_clip=radius_clip, payload_bytes=nbytes, crc=crc,
-                side=side, record_bits=_record_bits(kind, bits))
+    h = dict(version=version, kind=kind, kind_name=_KIND_NAMES[kind], coding=coding, coding_name=_CODING_NAMES[coding],
+             width=width, height=height, num_points=n, bits=bits, clip_coe=clip_coe, radius_clip=radius_clip,
+             payload_bytes=nbytes, fixed_payload_bytes=fixed_bytes, crc=crc, side=side,
+             record_bits=_record_bits(kind, bits), field_modes=["raw"] * 8)
+    if coding == CODING_RANS:
+        h.update(_parse_rans(memoryview(blob)[HEADER_BYTES + SIDE_BYTES:], n, _widths(kind, bits)))
+    return h
 
 
 def info(blob) -> Dict[str, object]:
-    """Every header field of a stream plus `payload_bits`, `bpp` (side information + payload: what
-    NativeFitter.analysis_wo_ec reports, rounded up to the payload's dword padding) and `bpp_with_header`."""
+    """Every header field of a stream plus `payload_bits`, `bpp` (side information + payload: for coding 0 what
+    NativeFitter.analysis_wo_ec reports, rounded up to the payload's dword padding; for coding 1 the entropy-coded size
+    with its tables, directory and coder states) and `bpp_with_header`.  `coding_name` is "fixed" or "rans", `field_modes`
+    says per field of a record whether its high bits are entropy coded ("rans") or stored as they are ("raw")."""
     h = _parse(blob)
+    h.pop("tables", None)
     hw = h["width"] * h["height"]
     h["payload_bits"] = 8 * h["payload_bytes"]
     h["bpp"] = 8 * (SIDE_BYTES + h["payload_bytes"]) / hw
@@ -149,22 +342,67 @@ def pack_codes(kind: int, bits: Sequence[int], code_xy: torch.Tensor, code_p0: t
     return payload
 
 
+def payload_histogram(kind: int, n: int, bits: Sequence[int], payload: torch.Tensor) -> torch.Tensor:
+    """Counts of the hi parts (value >> max(0, width - 8)) of the 8 fields of a coding-0 payload on the GPU -> int64
+    [8, 256] on the same device (gi2d_codec_histogram)."""
+    hist = torch.empty(8, 256, dtype=torch.int32, device=payload.device)
+    with torch.cuda.device(payload.device):
+        _lib.call("gi2d_codec_histogram", kind, n, *[int(b) for b in bits], C.c_void_p(payload.data_ptr()),
+                  payload.numel(), C.c_void_p(hist.data_ptr()), _stream(payload.device))
+    return hist.long()
+
+
+def rans_encode_payload(kind: int, n: int, bits: Sequence[int], payload: torch.Tensor,
+                        chunk_log2: int = DEFAULT_CHUNK_LOG2) -> bytes:
+    """Coding-0 payload on the GPU (uint8 tensor) -> the bytes of the rANS payload that carries the same records: device
+    histogram, rans_model on the host, gi2d_codec_rans_encode, the chunks gathered behind their directory."""
+    dev = payload.device
+    if dev.type != "cuda":
+        raise RuntimeError("gaussianimage_plus_amd.codec: the payload must live on the GPU (no CPU fallback)")
+    if not 8 <= int(chunk_log2) <= 12:
+        raise ValueError("chunk_log2: 8..12 (256 .. 4096 records per chunk)")
+    widths, b = _widths(kind, bits), [int(x) for x in bits]
+    mask, tables = rans_model(payload_histogram(kind, n, bits, payload).cpu().numpy(), widths)
+    head = _rans_head(n, widths, chunk_log2, mask, tables)
+    chunks = (n + (1 << chunk_log2) - 1) >> chunk_log2
+    with torch.cuda.device(dev):
+        nscratch = int(_lib.load().gi2d_codec_rans_scratch_bytes(kind, n, *b, chunk_log2, mask))
+        stride = nscratch // chunks
+        dtab = torch.from_numpy(_rans_device_tables(widths, mask, tables).copy()).to(dev)
+        scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+        lengths = torch.empty(chunks, dtype=torch.int32, device=dev)
+        _lib.call("gi2d_codec_rans_encode", kind, n, *b, chunk_log2, mask, C.c_void_p(dtab.data_ptr()), dtab.numel(),
+                  C.c_void_p(payload.data_ptr()), payload.numel(), C.c_void_p(scratch.data_ptr()), nscratch,
+                  C.c_void_p(lengths.data_ptr()), _stream(dev))
+        if bool((lengths < 0).any()):
+            raise RuntimeError("gi2d_codec_rans_encode met a symbol its tables give no frequency")
+        ends = torch.cumsum(lengths.long(), 0)
+        at = torch.arange(int(ends[-1]), device=dev)
+        chunk = torch.searchsorted(ends, at, right=True)
+        data = scratch[chunk * stride + at - (ends - lengths)[chunk]]
+        directory = np.concatenate([[0], ends.cpu().numpy()]).astype("<u4").tobytes()
+        return head + directory + data.cpu().numpy().tobytes()
+
+
 def assemble(kind: int, width: int, height: int, n: int, bits: Sequence[int], clip_coe: float, radius_clip: float,
-             side: Sequence[float], payload: bytes) -> bytes:
+             side: Sequence[float], payload: bytes, coding: int = CODING_FIXED) -> bytes:
     """Header + side information + payload (pure host)."""
     side_b = struct.pack("<16f", *[float(v) for v in side])
     crc = zlib.crc32(side_b + payload) & 0xFFFFFFFF
-    head = _HEADER.pack(MAGIC, VERSION, kind, 0, 0, width, height, n, *[int(b) for b in bits], float(clip_coe),
+    head = _HEADER.pack(MAGIC, VERSION, kind, coding, 0, width, height, n, *[int(b) for b in bits], float(clip_coe),
                         float(radius_clip), len(payload), crc)
     return head + side_b + payload
 
 
-def encode(fitter) -> bytes:
-    """The stream of a quantised fit: fitter.compress_wo_ec(), the device bit-packer, the header.  The gaussians keep
+def encode(fitter, coding: str = "fixed", chunk_log2: int = DEFAULT_CHUNK_LOG2) -> bytes:
+    """The stream of a quantised fit: fitter.compress_wo_ec(), the device bit-packer, the header; coding="rans" entropy
+    codes the packed records on the device (`chunk_log2`: log2 of the records per chunk, 8..12) -- same codes, same
+    picture, fewer bytes.  The gaussians keep
     the order compress_wo_ec() leaves them in (the rasterizer sums a tile in ascending id order: the order is part of
     the picture's bits), and the clip values are the ones fitter.decompress_wo_ec() renders with.  This IS one
     compress_wo_ec() call, side effects included: gaussians whose quantised covariance is not positive definite leave
     the model, and the log ranges of a LATER compress_wo_ec() are those of the rows that are left."""
+    coding = _coding_id(coding)
     if getattr(fitter, "quant", None) is None:
         raise ValueError("codec.encode: the fitter has no quantisers yet (enable_quantize / fit_quantize_schedule first)")
     if fitter.kind not in ("covariance", "scale_rot"):
@@ -191,12 +429,40 @@ def encode(fitter) -> bytes:
     side = torch.stack([scale, beta], dim=1).reshape(-1).cpu().tolist()  # (scale, beta) pairs, record order
     n = int(enc["quant_means"].shape[0])
     payload = pack_codes(kind, bits, enc["quant_means"], p0, p1, enc["feature_dc_index"])
-    return assemble(kind, int(fitter.w), int(fitter.h), n, bits, clip_coe, float(fitter.state.radius_clip), side,
-                    payload.cpu().numpy().tobytes())
+    data = (rans_encode_payload(kind, n, bits, payload, chunk_log2) if coding == CODING_RANS
+            else payload.cpu().numpy().tobytes())
+    return assemble(kind, int(fitter.w), int(fitter.h), n, bits, clip_coe, float(fitter.state.radius_clip), side, data,
+                    coding)
+
+
+def recode(blob, coding: str, device: Union[str, torch.device] = "cuda:0", chunk_log2: int = DEFAULT_CHUNK_LOG2) -> bytes:
+    """A stream in the other payload coding, without a fitter: the same header fields, side information and integers.
+    recode(recode(b, "rans"), "fixed") == b."""
+    coding = _coding_id(coding)
+    h = _parse(blob)
+    dec = Decoder(device)
+    with torch.cuda.device(dec.dev):
+        fixed = dec.fixed_payload(dec.upload(blob))
+        data = (rans_encode_payload(h["kind"], h["num_points"], h["bits"], fixed, chunk_log2) if coding == CODING_RANS
+                else fixed.cpu().numpy().tobytes())
+    return assemble(h["kind"], h["width"], h["height"], h["num_points"], h["bits"], h["clip_coe"], h["radius_clip"],
+                    h["side"], data, coding)
+
+
+_STATUS_WORDS = 8
+
+
+def _staged(blob, h) -> List[np.ndarray]:
+    """What of a stream goes to the device: its payload and, for a rANS payload, the tables of the coded fields."""
+    parts = [np.frombuffer(blob, np.uint8, h["payload_bytes"], HEADER_BYTES + SIDE_BYTES)]
+    if h["coding"] == CODING_RANS:
+        parts.append(_rans_device_tables(_widths(h["kind"], h["bits"]), h["coded_mask"], h["tables"]))
+    return parts
 
 
 class DeviceStream:
-    """A parsed stream whose payload already lives on the GPU (Decoder.upload)."""
+    """A parsed stream whose payload already lives on the GPU (Decoder.upload); behind a rANS payload lie the device
+    tables of its coded fields."""
 
     def __init__(self, header: Dict[str, object], payload: torch.Tensor):
         self.header, self.payload = header, payload
@@ -217,7 +483,10 @@ class Decoder:
         self._ws = torch.empty(0, dtype=torch.uint8, device=self.dev)
         self._payload = torch.empty(0, dtype=torch.uint8, device=self.dev)
         self._host = torch.empty(0, dtype=torch.uint8).pin_memory()
-        self._status = torch.zeros(1, 4, dtype=torch.int32, device=self.dev)
+        self._expanded = torch.empty(0, dtype=torch.uint8, device=self.dev)  # coding-0 payloads of the rANS streams
+        # per stream: words 0..3 belong to the binning step and the tile pass (1 = overflow), word 4 to the rANS expansion
+        self._status = torch.zeros(1, _STATUS_WORDS, dtype=torch.int32, device=self.dev)
+        self._token = 0  # the expansion raises word 4 to the token of its decode: no reset launch between decodes
         self._background = torch.ones(3, dtype=torch.float32, device=self.dev)  # the rasterize wrappers' default
 
     # ---------------------------------------------------------------------------------------------- buffers
@@ -229,19 +498,21 @@ class Decoder:
 
     def _stage(self, blobs, headers) -> List[torch.Tensor]:
         """Payloads of `blobs` -> device (one pinned staging buffer, one asynchronous copy per stream)."""
-        offs, total = [], 0
-        for h in headers:
+        offs, total, parts = [], 0, [_staged(blob, h) for blob, h in zip(blobs, headers)]
+        for p in parts:
             offs.append(total)
-            total += (h["payload_bytes"] + 255) & ~255
+            total += (sum(len(x) for x in p) + 255) & ~255
         if self._host.numel() < total:
             self._host = torch.empty(total, dtype=torch.uint8).pin_memory()
         if self._payload.numel() < total:
             self._payload = torch.empty(total, dtype=torch.uint8, device=self.dev)
         host = self._host.numpy()
         out = []
-        for blob, h, o in zip(blobs, headers, offs):
-            nb = h["payload_bytes"]
-            host[o:o + nb] = np.frombuffer(blob, np.uint8, nb, HEADER_BYTES + SIDE_BYTES)
+        for p, o in zip(parts, offs):
+            nb = 0
+            for x in p:
+                host[o + nb:o + nb + len(x)] = x
+                nb += len(x)
             dst = self._payload[o:o + nb]
             dst.copy_(self._host[o:o + nb], non_blocking=True)
             out.append(dst)
@@ -250,13 +521,52 @@ class Decoder:
     def upload(self, blob) -> DeviceStream:
         """Parse a stream and copy its payload to the device (a buffer of its own), for repeated decodes."""
         h = _parse(blob)
-        nb = h["payload_bytes"]
-        host = torch.from_numpy(np.frombuffer(blob, np.uint8, nb, HEADER_BYTES + SIDE_BYTES).copy())
-        return DeviceStream(h, host.to(self.dev))
+        return DeviceStream(h, torch.from_numpy(np.concatenate(_staged(blob, h))).to(self.dev))
+
+    def _expand(self, h, payload: torch.Tensor, status: torch.Tensor, fixed: Optional[torch.Tensor]) -> torch.Tensor:
+        """rANS payload (+ tables) on the device -> its coding-0 payload in `fixed` (gi2d_codec_rans_expand)."""
+        nb, nf = h["payload_bytes"], h["fixed_payload_bytes"]
+        if fixed is None:
+            fixed = torch.empty(nf, dtype=torch.uint8, device=self.dev)
+        at = lambda off: C.c_void_p(payload.data_ptr() + off)
+        b = h["bits"]
+        _lib.call("gi2d_codec_rans_expand", h["kind"], h["num_points"], b[0], b[1], b[2], b[3], h["chunk_log2"],
+                  h["coded_mask"], at(nb), payload.numel() - nb, at(h["directory_offset"]), at(h["data_offset"]),
+                  h["data_bytes"], h["max_chunk_bytes"], C.c_void_p(fixed.data_ptr()), nf,
+                  C.c_void_p(status.data_ptr() + 16), self._token, _stream(self.dev))
+        return fixed
+
+    def _next_token(self) -> None:
+        self._token += 1
+        if self._token >= 1 << 30:  # start over on a clean slate long before the word could wrap
+            self._status.zero_()
+            self._token = 1
+
+    def _check_expanded(self, word: int) -> None:
+        if word == self._token:
+            raise ValueError("GI2D stream: rANS payload: a coder state did not return to its start value (the chunk data "
+                             "is not what an encoder wrote)")
+
+    def fixed_payload(self, stream) -> torch.Tensor:
+        """The coding-0 payload of a stream, on the device (a tensor of its own): the stream's own bytes for coding 0,
+        the expansion for coding 1."""
+        ds = stream if isinstance(stream, DeviceStream) else self.upload(stream)
+        h = ds.header
+        if h["coding"] == CODING_FIXED:
+            return ds.payload.clone()
+        with torch.cuda.device(self.dev):
+            self._next_token()
+            fixed = self._expand(h, ds.payload, self._status[0], None)
+            self._check_expanded(int(self._status[0, 4]))
+        return fixed
 
     # ---------------------------------------------------------------------------------------------- launches
-    def _enqueue(self, h, payload: torch.Tensor, status: torch.Tensor, out: torch.Tensor, aux=None) -> None:
-        """workspace reset + decode/bin + forward + clamp on the current stream; no allocation, no host sync."""
+    def _enqueue(self, h, payload: torch.Tensor, status: torch.Tensor, out: torch.Tensor, aux=None,
+                 fixed: Optional[torch.Tensor] = None) -> None:
+        """(rANS expansion into `fixed` +) workspace reset + decode/bin + forward + clamp on the current stream; no host
+        sync, and no allocation when a rANS stream is given its `fixed` buffer."""
+        if h["coding"] == CODING_RANS:
+            payload = self._expand(h, payload, status, fixed)
         n, w, hh = h["num_points"], h["width"], h["height"]
         tx, ty = (w + _TILE - 1) // _TILE, (hh + _TILE - 1) // _TILE
         b = h["bits"]
@@ -266,7 +576,7 @@ class Decoder:
         a = [C.c_void_p(t.data_ptr()) for t in aux] if aux is not None else [None] * 5
         _lib.call("gi2d_fast_workspace_init", ws, nws, n, tx, ty, st)
         _lib.call("gi2d_codec_decode_bin", h["kind"], n, b[0], b[1], b[2], b[3], side, C.c_void_p(payload.data_ptr()),
-                  h["payload_bytes"], h["clip_coe"], hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3], a[4], ws,
+                  h["fixed_payload_bytes"], h["clip_coe"], hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3], a[4], ws,
                   nws, C.c_void_p(status.data_ptr()), st)
         _lib.call("gi2d_fast_rasterize_forward", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws,
                   C.c_void_p(status.data_ptr()), None, None, C.c_void_p(out.data_ptr()), st)
@@ -288,7 +598,10 @@ class Decoder:
             self._reserve_workspace(h)
             aux = self._aux(h["num_points"])
             img = self._out(h, None)
+            self._next_token()
             self._enqueue(h, ds.payload, self._status[0], img, aux)
+            if h["coding"] == CODING_RANS:
+                self._check_expanded(int(self._status[0, 4]))
         return dict(zip(("xys", "radii", "conics", "num_tiles_hit", "colors"), aux), image=img)
 
     def _aux(self, n: int):
@@ -330,15 +643,25 @@ class Decoder:
                 for i, p in zip(raw, self._stage([streams[i] for i in raw], [headers[i] for i in raw])):
                     payloads[i] = p
             if self._status.shape[0] < len(streams):
-                self._status = torch.zeros(len(streams), 4, dtype=torch.int32, device=self.dev)
-            for h in headers:
-                self._reserve_workspace(h)
-            images = [self._out(h, None if outs is None else outs[i]) for i, h in enumerate(headers)]
+                self._status = torch.zeros(len(streams), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
+            fixed, total = [None] * len(streams), 0
             for i, h in enumerate(headers):
-                self._enqueue(h, payloads[i], self._status[i], images[i])
-            overflow = self._status[:len(streams), 1].tolist()  # the one host wait of a decode
-            for i, flag in enumerate(overflow):
-                if flag:
+                self._reserve_workspace(h)
+                if h["coding"] == CODING_RANS:
+                    fixed[i] = (total, h["fixed_payload_bytes"])
+                    total += (h["fixed_payload_bytes"] + 255) & ~255
+            if self._expanded.numel() < total:
+                self._expanded = torch.empty(total, dtype=torch.uint8, device=self.dev)
+            fixed = [None if f is None else self._expanded[f[0]:f[0] + f[1]] for f in fixed]
+            images = [self._out(h, None if outs is None else outs[i]) for i, h in enumerate(headers)]
+            self._next_token()
+            for i, h in enumerate(headers):
+                self._enqueue(h, payloads[i], self._status[i], images[i], fixed=fixed[i])
+            status = self._status[:len(streams), 1:5].tolist()  # the one host wait of a decode: overflow, .., .., rANS
+            for i, (overflow, _, _, expanded) in enumerate(status):
+                if headers[i]["coding"] == CODING_RANS:
+                    self._check_expanded(expanded)
+                if overflow:
                     self._exact(headers[i], payloads[i], images[i])
         return images
 

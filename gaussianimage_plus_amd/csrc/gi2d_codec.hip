@@ -11,28 +11,11 @@
 //
 // Nothing here is read through a pointer computed from stream CONTENT: record positions follow from (N, R) alone, and
 // every load index is clamped to the dwords the entry has checked the payload to hold.
-#include <string>
-
+#include "gi2d_codec_layout.h"
 #include "gi2d_fast_internal.h"
 #include "gi2d_quant_core.h"
 
 namespace gi2d {
-
-#define GI2D_CODEC_FIELDS 8
-#define GI2D_CODEC_MAX_RECORD 128                                  /* bits */
-#define GI2D_CODEC_MAX_LOADS ((31 + GI2D_CODEC_MAX_RECORD + 31) / 32) /* dwords a record can touch: 5 */
-#define GI2D_CODEC_PACK_BLOCK 256
-
-// Field layout of a record, the same for every gaussian of a stream (kernel argument: scalar registers).
-struct CodecLayout {
-    int width[GI2D_CODEC_FIELDS];  // bits per field, record order
-    int qmin[GI2D_CODEC_FIELDS];   // stored value = code - qmin (non-zero for the signed rotation only)
-    int record_bits;               // R
-    int loads;                     // ceil((31 + R) / 32)
-};
-struct CodecSide {
-    float scale[GI2D_CODEC_FIELDS], beta[GI2D_CODEC_FIELDS];
-};
 
 // ---------------------------------------------------------------------------------------------------------- pack
 // codes: xy f32[N,2], p0 f32[N,3] (covariance rows) or f32[N,2] (scaling), p1 f32[N] (rotation; scale-rot only),
@@ -73,16 +56,6 @@ __global__ __launch_bounds__(GI2D_CODEC_PACK_BLOCK) void codec_pack_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------- decode + bin
-// The low `w` bits of the 128-bit little-endian number r, which is then shifted right by w (w <= 16).
-__device__ __forceinline__ uint32_t codec_take(uint32_t (&r)[4], int w) {
-    const uint32_t v = r[0] & ((1u << w) - 1u);
-    r[0] = __builtin_amdgcn_alignbit(r[1], r[0], (uint32_t)w);
-    r[1] = __builtin_amdgcn_alignbit(r[2], r[1], (uint32_t)w);
-    r[2] = __builtin_amdgcn_alignbit(r[3], r[2], (uint32_t)w);
-    r[3] >>= w;
-    return v;
-}
-
 struct CodecOut {  // optional per-gaussian outputs (all may be NULL)
     float2 *xys;
     int32_t *radii;
@@ -130,42 +103,6 @@ __global__ __launch_bounds__(256) void codec_decode_bin_kernel(
     if (out.colors) out.colors[3 * g] = v[5], out.colors[3 * g + 1] = v[6], out.colors[3 * g + 2] = v[7];
     bin_projected(g, o, 1.f, v[5], v[6], v[7], tiles_x, tiles_y, radius_clip, old_box, bt.prev_box, bt.lists, recs);
 }
-
-// Layout of a stream's records from its header fields; false (and the error set) if they are not a valid format-1 layout.
-static bool codec_layout(const char *what, int kind, int xy_bits, int p0_bits, int p1_bits, int color_bits,
-                         CodecLayout &lay) {
-    if (kind != kCovariance && kind != kScaleRot) {
-        set_error((std::string(what) + ": model kind must be 1 (covariance) or 2 (scale-rot)").c_str());
-        return false;
-    }
-    const bool rs = kind == kScaleRot;
-    const int bits[4] = {xy_bits, p0_bits, rs ? p1_bits : 1, color_bits};
-    for (int b : bits)
-        if (b < 1 || b > 16) {
-            set_error((std::string(what) + ": field widths must be 1..16 bits").c_str());
-            return false;
-        }
-    if (!rs && p1_bits != 0) {
-        set_error((std::string(what) + ": the covariance model has no rotation field (its width must be 0)").c_str());
-        return false;
-    }
-    const int width[GI2D_CODEC_FIELDS] = {xy_bits, xy_bits, p0_bits, p0_bits, rs ? p1_bits : p0_bits,
-                                          color_bits, color_bits, color_bits};
-    lay.record_bits = 0;
-    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
-        lay.width[k] = width[k];
-        lay.qmin[k] = 0;
-        lay.record_bits += width[k];
-    }
-    if (rs) lay.qmin[4] = -(1 << (p1_bits - 1));  // the rotation quantiser is signed
-    lay.loads = (31 + lay.record_bits + 31) / 32;
-    if (lay.record_bits > GI2D_CODEC_MAX_RECORD) {
-        set_error((std::string(what) + ": a record is more than 128 bits").c_str());
-        return false;
-    }
-    return true;
-}
-static inline long long codec_dwords(long long n, int record_bits) { return (n * record_bits + 31) / 32; }
 
 }  // namespace gi2d
 

@@ -1,0 +1,460 @@
+// Payload coding 1 of the packed stream: the fixed-length records of coding 0, entropy coded (include/gi2d.h "rANS
+// payload"; the container table is in INTEGRATION.md).
+//
+// A field of width w is split into hi = v >> lo_bits (the symbol, at most 8 bits) and lo (stored raw).  One CHUNK of
+// 2^chunk_log2 records is one wave's work: lane l owns records base + 64 j + l and one 32-bit rANS state (12 probability
+// bits, 16-bit renormalisation: a step moves at most one word per lane).  The wave walks j ascending and the coded fields
+// ascending; in a step the lanes that need a word take consecutive words of the chunk's shared word stream in ascending
+// lane order (__ballot + the popcount of the lanes below).  The encoder runs the same steps backwards.
+//
+//   histogram  coding-0 payload -> u32[8][256] counts of the hi parts (LDS atomics, one flush per workgroup)
+//   encode     coding-0 payload + tables -> per chunk: 64 final states | raw section | words, and its length.  The wave
+//              writes its words backwards into LDS and copies the chunk out.  Once per image: not a hot path.
+//   expand     coded chunks -> the coding-0 payload, byte for byte.  The hot kernel: several waves per workgroup share the
+//              tables in LDS; a chunk (states, raw section, words) is staged into LDS with coalesced loads, so the decode
+//              loop has no global load; 64 records (2 R dwords, dword aligned) are ORed together in LDS and leave as
+//              coalesced dword stores.
+//
+// Device tables, per coded field in record order (GI2D_RANS_TABLE_BYTES each, built by the host from the stream's
+// validated model section): u8 symbol of slot [4096] | u16 cumulative frequency of symbol [258] (entries 256, 257 = 4096).
+//
+// Every index that comes from stream content is masked or clamped: the slot to 12 bits, the symbol is a byte and indexes
+// 258 entries, a word position to the wave's staging area, a chunk's offset and length to the chunk data and the staging
+// area.  A stream with nonsense inside decodes to nonsense records inside its own buffers.
+#include "gi2d_codec_layout.h"
+
+namespace gi2d {
+
+#define GI2D_RANS_PROB_BITS 12
+#define GI2D_RANS_SLOTS (1 << GI2D_RANS_PROB_BITS)
+#define GI2D_RANS_LOW 65536u /* states live in [2^16, 2^32) */
+#define GI2D_RANS_TABLE_BYTES (GI2D_RANS_SLOTS + 2 * 258)
+#define GI2D_RANS_TABLE_DWORDS (GI2D_RANS_TABLE_BYTES / 4)
+#define GI2D_RANS_STATIC_LDS (64 * 1024) /* what a launch gets without asking for more */
+#define GI2D_RANS_MAX_LDS (160 * 1024)
+
+struct RansLayout {
+    CodecLayout rec;
+    int lo[GI2D_CODEC_FIELDS];    // raw low bits of a field: max(0, width - 8)
+    int rawb[GI2D_CODEC_FIELDS];  // bits of the field in the raw section: lo if coded, the whole width if not
+    unsigned mask;                // bit k: field k is entropy coded
+    int ncoded;
+    int raw_bits;   // R_raw
+    int raw_loads;  // dwords a lane's raw bits can touch
+    int chunk_log2;
+};
+
+static bool rans_layout(const char *what, int kind, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                        int chunk_log2, unsigned mask, RansLayout &L) {
+    if (!codec_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, L.rec)) return false;
+    if (chunk_log2 < 8 || chunk_log2 > 12 || mask > 0xffu) {
+        set_error((std::string(what) + ": log2(records per chunk) must be 8..12 and the field mask 8 bits").c_str());
+        return false;
+    }
+    L.mask = mask;
+    L.chunk_log2 = chunk_log2;
+    L.ncoded = L.raw_bits = 0;
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
+        const int w = L.rec.width[k];
+        L.lo[k] = w > 8 ? w - 8 : 0;
+        const bool coded = (mask >> k) & 1u;
+        L.rawb[k] = coded ? L.lo[k] : w;
+        L.ncoded += coded;
+        L.raw_bits += L.rawb[k];
+    }
+    L.raw_loads = L.raw_bits ? (31 + L.raw_bits + 31) / 32 : 0;
+    return true;
+}
+static inline int rans_chunks(long long n, int chunk_log2) { return (int)((n + (1ll << chunk_log2) - 1) >> chunk_log2); }
+// dwords of a full chunk's raw section / most words a chunk can hold / dwords of the largest chunk
+static inline int rans_raw_cap(const RansLayout &L) { return ((L.raw_bits << L.chunk_log2) + 31) / 32; }
+static inline int rans_word_cap(const RansLayout &L) { return L.ncoded << L.chunk_log2; }
+static inline int rans_chunk_cap(const RansLayout &L) { return 64 + rans_raw_cap(L) + (rans_word_cap(L) + 1) / 2; }
+
+// The lanes of ONE wave hand data to each other through LDS here.  LDS operations of a wave complete in order, so all
+// this has to do is keep the compiler from moving them across the point -- and it must not wait for the global stores
+// in flight, which a workgroup-scope fence does (the flush of 64 records would cost a store round trip per group).
+__device__ __forceinline__ void wave_lds_sync() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Record g of a coding-0 payload as a 128-bit little-endian number (the load of codec_decode_bin_kernel).
+__device__ __forceinline__ void rans_load_record(const uint32_t *__restrict__ payload, long long g,
+                                                 const CodecLayout &lay, long long last_dword, uint32_t (&r)[4]) {
+    const long long bit0 = g * lay.record_bits;
+    const long long first = bit0 >> 5;
+    uint32_t w[GI2D_CODEC_MAX_LOADS];
+#pragma unroll
+    for (int j = 0; j < GI2D_CODEC_MAX_LOADS; ++j) {
+        const long long d = first + j;
+        w[j] = j < lay.loads ? payload[d < last_dword ? d : last_dword] : 0u;
+    }
+    const uint32_t s0 = (uint32_t)bit0 & 31u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], s0);
+}
+
+// Appends the w-bit value v (1 <= w <= 16) to a record that grows down from bit 127 ...
+__device__ __forceinline__ void rans_push(uint32_t (&r)[4], uint32_t v, int w) {
+    r[0] = __builtin_amdgcn_alignbit(r[1], r[0], (uint32_t)w);
+    r[1] = __builtin_amdgcn_alignbit(r[2], r[1], (uint32_t)w);
+    r[2] = __builtin_amdgcn_alignbit(r[3], r[2], (uint32_t)w);
+    r[3] = (r[3] >> w) | (v << (32 - w));
+}
+// ... and moves the `bits` bits pushed so far down to bit 0.
+__device__ __forceinline__ void rans_settle(uint32_t (&r)[4], int bits) {
+    int sh = 128 - bits;
+    for (; sh >= 32; sh -= 32) r[0] = r[1], r[1] = r[2], r[2] = r[3], r[3] = 0u;
+    r[0] = __builtin_amdgcn_alignbit(r[1], r[0], (uint32_t)sh);
+    r[1] = __builtin_amdgcn_alignbit(r[2], r[1], (uint32_t)sh);
+    r[2] = __builtin_amdgcn_alignbit(r[3], r[2], (uint32_t)sh);
+    r[3] >>= sh;
+}
+// ORs the 128-bit number r into the LDS dwords `area[0, area_dwords)` at bit position `bit`.
+__device__ __forceinline__ void rans_or_into(uint32_t *area, int area_dwords, int bit, const uint32_t (&r)[4]) {
+    const int d0 = bit >> 5, s = bit & 31;
+    uint32_t prev = 0u;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const uint32_t cur = i < 4 ? r[i] : 0u;
+        const uint32_t e = (uint32_t)(((((uint64_t)cur << 32) | prev) << s) >> 32);
+        if (e != 0u && d0 + i < area_dwords) atomicOr(&area[d0 + i], e);
+        prev = cur;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ histogram
+__global__ __launch_bounds__(256) void rans_histogram_kernel(int n, RansLayout L, const uint32_t *__restrict__ payload,
+                                                             long long last_dword, uint32_t *__restrict__ hist) {
+    __shared__ uint32_t h[GI2D_CODEC_FIELDS * 256];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < GI2D_CODEC_FIELDS * 256; i += 256) h[i] = 0u;
+    __syncthreads();
+    for (long long g = (long long)blockIdx.x * 256 + tid; g < n; g += (long long)gridDim.x * 256) {
+        uint32_t r[4];
+        rans_load_record(payload, g, L.rec, last_dword, r);
+#pragma unroll
+        for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
+            const uint32_t v = codec_take(r, L.rec.width[k]);
+            atomicAdd(&h[k * 256 + ((v >> L.lo[k]) & 255u)], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < GI2D_CODEC_FIELDS * 256; i += 256)
+        if (h[i]) atomicAdd(&hist[i], h[i]);
+}
+
+// --------------------------------------------------------------------------------------------------------- encode
+struct RansEncodeArgs {
+    RansLayout L;
+    int n;
+    const uint32_t *payload;  // coding 0
+    long long last_dword;
+    const uint16_t *tables;   // device tables (only the cumulative frequencies are read)
+    uint32_t *out;            // chunk c at dword c * stride
+    int stride, raw_cap, word_cap;
+    uint32_t *lengths;        // bytes of chunk c; 0xffffffff: a symbol of frequency 0 (tables of another payload)
+};
+
+__global__ __launch_bounds__(64) void rans_encode_kernel(RansEncodeArgs a) {
+    extern __shared__ __align__(16) uint32_t lds[];
+    const int lane = threadIdx.x, c = blockIdx.x;
+    uint32_t *raw = lds;
+    uint16_t *words = (uint16_t *)(lds + a.raw_cap);
+    const int crec = 1 << a.L.chunk_log2;
+    const long long base = (long long)c * crec;
+    const int records = (int)min((long long)crec, (long long)a.n - base);
+    const int raw_dw = (records * a.L.raw_bits + 31) >> 5;
+    for (int i = lane; i < raw_dw; i += 64) raw[i] = 0u;
+    wave_lds_sync();
+    uint32_t x = GI2D_RANS_LOW;
+    int wend = a.word_cap;
+    bool bad = false;
+    for (int j = ((records + 63) >> 6) - 1; j >= 0; --j) {
+        const int rl = j * 64 + lane;
+        const bool active = rl < records;
+        uint32_t r[4], v[GI2D_CODEC_FIELDS];
+        rans_load_record(a.payload, active ? base + rl : base, a.L.rec, a.last_dword, r);
+        uint32_t rr[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
+            v[k] = codec_take(r, a.L.rec.width[k]);
+            if (a.L.rawb[k]) rans_push(rr, v[k] & ((1u << a.L.rawb[k]) - 1u), a.L.rawb[k]);
+        }
+        if (a.L.raw_bits && active) {
+            rans_settle(rr, a.L.raw_bits);
+            rans_or_into(raw, raw_dw, rl * a.L.raw_bits, rr);
+        }
+#pragma unroll
+        for (int k = GI2D_CODEC_FIELDS - 1; k >= 0; --k) {
+            if (!((a.L.mask >> k) & 1u)) continue;
+            const int t = __popc(a.L.mask & ((1u << k) - 1u));
+            const uint16_t *cum = a.tables + t * (GI2D_RANS_TABLE_BYTES / 2) + GI2D_RANS_SLOTS / 2;
+            const uint32_t s = (v[k] >> a.L.lo[k]) & 255u;
+            const uint32_t c0 = cum[s];
+            uint32_t f = (uint32_t)cum[s + 1] - c0;
+            if (active && (f == 0u || f > GI2D_RANS_SLOTS)) bad = true;
+            if (f == 0u || f > GI2D_RANS_SLOTS) f = 1u;
+            const bool emit = active && (uint64_t)x >= ((uint64_t)f << 20);
+            const unsigned long long m = __ballot(emit);
+            const int cnt = __popcll(m);
+            if (emit) {
+                const int p = wend - cnt + __popcll(m & lanemask_lt());
+                if (p >= 0) words[p] = (uint16_t)(x & 0xffffu);
+                x >>= 16;
+            }
+            wend = max(wend - cnt, 0);
+            if (active) x = ((x / f) << 12) + x % f + c0;
+        }
+    }
+    wave_lds_sync();
+    const int nwords = a.word_cap - wend;
+    uint32_t *out = a.out + (long long)c * a.stride;
+    out[lane] = x;
+    for (int i = lane; i < raw_dw; i += 64) out[64 + i] = raw[i];
+    const int wdw = (nwords + 1) >> 1;
+    for (int i = lane; i < wdw; i += 64) {
+        const uint32_t lo = words[wend + 2 * i];
+        const uint32_t hi = 2 * i + 1 < nwords ? words[wend + 2 * i + 1] : 0u;
+        out[64 + raw_dw + i] = lo | (hi << 16);
+    }
+    const bool any_bad = __ballot(bad) != 0ull;
+    if (lane == 0) a.lengths[c] = any_bad ? 0xffffffffu : 4u * (uint32_t)(64 + raw_dw + wdw);
+}
+
+// --------------------------------------------------------------------------------------------------------- expand
+struct RansExpandArgs {
+    RansLayout L;
+    int n, chunks;
+    const uint32_t *tables;  // ncoded * GI2D_RANS_TABLE_DWORDS
+    const uint32_t *dir;     // chunks + 1 byte offsets into the chunk data
+    const uint32_t *data;
+    uint32_t data_dwords;
+    int in_cap;              // dwords of a wave's staging area (>= the largest chunk)
+    uint32_t *out;           // coding-0 payload
+    long long out_dwords;
+    int32_t *status;         // raised to `token` if an active lane does not end at 2^16
+    int token;
+};
+
+__global__ __launch_bounds__(256) void rans_expand_kernel(RansExpandArgs a) {
+    extern __shared__ __align__(16) uint32_t lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
+    const int table_dw = a.L.ncoded * GI2D_RANS_TABLE_DWORDS;
+    for (int i = tid; i < table_dw; i += blockDim.x) lds[i] = a.tables[i];
+    const int R = a.L.rec.record_bits, group_dw = 2 * R;  // 64 records: dword aligned
+    uint32_t *in = lds + table_dw + wave * (a.in_cap + group_dw);
+    uint32_t *grp = in + a.in_cap;
+    const int c = blockIdx.x * waves + wave;
+    if (c < a.chunks) {
+        // the chunk: states | raw section | words, as it lies in the stream
+        const uint32_t o0 = min(a.dir[c] >> 2, a.data_dwords), o1 = min(a.dir[c + 1] >> 2, a.data_dwords);
+        const uint32_t len = o1 > o0 ? min(o1 - o0, (uint32_t)a.in_cap) : 0u;
+        for (uint32_t i = lane; i < len; i += 64) in[i] = a.data[o0 + i];
+        for (int i = lane; i < group_dw; i += 64) grp[i] = 0u;
+    }
+    __syncthreads();
+    if (c >= a.chunks) return;
+    const int crec = 1 << a.L.chunk_log2;
+    const long long base = (long long)c * crec;
+    const int records = (int)min((long long)crec, (long long)a.n - base);
+    const int raw_dw = (records * a.L.raw_bits + 31) >> 5;
+    const int last_in = a.in_cap - 1, last_word = 2 * a.in_cap - 1;
+    const uint16_t *in16 = (const uint16_t *)in;
+    const uint8_t *tab8 = (const uint8_t *)lds;
+    const uint16_t *tab16 = (const uint16_t *)lds;
+    uint32_t x = in[lane];
+    int wpos = 2 * (64 + raw_dw);  // u16 index of the next word
+    const unsigned long long below = lanemask_lt();
+    const long long out_base = (base * R) >> 5;
+    const int J = (records + 63) >> 6;
+    for (int j = 0; j < J; ++j) {
+        const int rl = j * 64 + lane;
+        const bool active = rl < records;
+        uint32_t r[4] = {0u, 0u, 0u, 0u};
+        if (a.L.raw_bits) {
+            const int bit0 = rl * a.L.raw_bits, first = 64 + (bit0 >> 5);
+            uint32_t w[GI2D_CODEC_MAX_LOADS];
+#pragma unroll
+            for (int q = 0; q < GI2D_CODEC_MAX_LOADS; ++q) w[q] = q < a.L.raw_loads ? in[min(first + q, last_in)] : 0u;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) r[q] = __builtin_amdgcn_alignbit(w[q + 1], w[q], (uint32_t)bit0 & 31u);
+        }
+        uint32_t rec[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
+            const int w = a.L.rec.width[k];
+            uint32_t v;
+            if ((a.L.mask >> k) & 1u) {
+                const int t = __popc(a.L.mask & ((1u << k) - 1u));
+                const uint32_t slot = x & (GI2D_RANS_SLOTS - 1u);
+                const uint32_t s = tab8[t * GI2D_RANS_TABLE_BYTES + slot];
+                const uint16_t *cum = tab16 + t * (GI2D_RANS_TABLE_BYTES / 2) + GI2D_RANS_SLOTS / 2;
+                const uint32_t c0 = cum[s], c1 = cum[s + 1];
+                uint32_t xn = (c1 - c0) * (x >> GI2D_RANS_PROB_BITS) + slot - c0;
+                const bool need = active && xn < GI2D_RANS_LOW;
+                // (no branch around the word read: with 64 lanes some lane needs a word in nearly every step)
+                const unsigned long long m = __ballot(need);
+                const uint32_t word = in16[min(wpos + (int)__popcll(m & below), last_word)];
+                wpos += __popcll(m);
+                x = need ? (xn << 16) | word : active ? xn : x;
+                v = (s << a.L.lo[k]) | codec_take(r, a.L.lo[k]);
+            } else {
+                v = codec_take(r, w);
+            }
+            rans_push(rec, v & ((1u << w) - 1u), w);
+        }
+        rans_settle(rec, R);
+        if (active) rans_or_into(grp, group_dw, lane * R, rec);
+        wave_lds_sync();
+        const long long gd0 = out_base + (long long)j * group_dw;
+        for (int i = lane; i < group_dw; i += 64) {
+            const uint32_t d = grp[i];
+            grp[i] = 0u;
+            if (gd0 + i < a.out_dwords) a.out[gd0 + i] = d;
+        }
+        wave_lds_sync();
+    }
+    const bool bad = lane < records && x != GI2D_RANS_LOW;
+    if (__ballot(bad) != 0ull && lane == 0) atomicMax(a.status, a.token);
+}
+
+// A launch that needs more than 64 KB of LDS asks for it first (a CU has 160 KB).
+template <typename K>
+static bool rans_reserve_lds(const char *what, K kernel, size_t bytes) {
+    if (bytes <= GI2D_RANS_STATIC_LDS) return true;
+    if (bytes > GI2D_RANS_MAX_LDS ||
+        hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error((std::string(what) + ": the chunk does not fit the LDS of a compute unit").c_str());
+        return false;
+    }
+    return true;
+}
+
+}  // namespace gi2d
+
+using namespace gi2d;
+
+extern "C" {
+
+size_t gi2d_codec_rans_scratch_bytes(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                                     int chunk_log2, unsigned coded_mask) {
+    RansLayout L;
+    if (n < 0 || !rans_layout("codec rans scratch bytes", kind, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2,
+                              coded_mask, L))
+        return 0;
+    return (size_t)rans_chunks(n, chunk_log2) * rans_chunk_cap(L) * 4;
+}
+
+int gi2d_codec_histogram(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, const void *payload,
+                         size_t payload_bytes, uint32_t *hist, gi2d_stream_t st) {
+    RansLayout L;
+    if (!rans_layout("codec histogram", kind, xy_bits, p0_bits, p1_bits, color_bits, 8, 0u, L))
+        return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 0) {
+        set_error("codec histogram: negative size");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    const long long need = codec_dwords(n, L.rec.record_bits);
+    if (payload_bytes < (size_t)need * 4) {
+        set_error("codec histogram: payload shorter than 4 * ceil(N * R / 32) bytes");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    if (!hist || ((uintptr_t)hist & 3) || (n > 0 && (!payload || ((uintptr_t)payload & 3)))) {
+        set_error("codec histogram: null or misaligned pointer");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    hipError_t e = hipMemsetAsync(hist, 0, GI2D_CODEC_FIELDS * 256 * sizeof(uint32_t), (hipStream_t)st);
+    if (e != hipSuccess) return (int)e;
+    if (n == 0) return GI2D_OK;
+    const int groups = (n + 255) / 256;
+    hipLaunchKernelGGL(rans_histogram_kernel, dim3(groups < 256 ? groups : 256), dim3(256), 0, (hipStream_t)st, n, L,
+                       (const uint32_t *)payload, need - 1, hist);
+    return check_launch("codec histogram");
+}
+
+int gi2d_codec_rans_encode(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, int chunk_log2,
+                           unsigned coded_mask, const void *tables, size_t tables_bytes, const void *payload,
+                           size_t payload_bytes, void *scratch, size_t scratch_bytes, uint32_t *lengths,
+                           gi2d_stream_t st) {
+    RansLayout L;
+    if (!rans_layout("codec rans encode", kind, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask, L))
+        return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 1) {
+        set_error("codec rans encode: no gaussians");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    const long long need = codec_dwords(n, L.rec.record_bits);
+    const int chunks = rans_chunks(n, chunk_log2), stride = rans_chunk_cap(L);
+    if (payload_bytes < (size_t)need * 4 || tables_bytes != (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES) {
+        set_error("codec rans encode: payload shorter than 4 * ceil(N * R / 32) bytes, or tables not one per coded field");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    if (scratch_bytes < (size_t)chunks * stride * 4) {
+        set_error("codec rans encode: scratch smaller than gi2d_codec_rans_scratch_bytes");
+        return GI2D_ERR_WORKSPACE_TOO_SMALL;
+    }
+    if (!payload || !scratch || !lengths || (L.ncoded && !tables) || (((uintptr_t)payload | (uintptr_t)scratch |
+                                                                       (uintptr_t)lengths | (uintptr_t)tables) & 3)) {
+        set_error("codec rans encode: null or misaligned pointer");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    RansEncodeArgs a;
+    a.L = L, a.n = n, a.payload = (const uint32_t *)payload, a.last_dword = need - 1;
+    a.tables = (const uint16_t *)tables, a.out = (uint32_t *)scratch, a.stride = stride;
+    a.raw_cap = rans_raw_cap(L), a.word_cap = rans_word_cap(L), a.lengths = lengths;
+    const size_t lds = (size_t)a.raw_cap * 4 + (size_t)a.word_cap * 2 + 16;
+    if (!rans_reserve_lds("codec rans encode", rans_encode_kernel, lds)) return GI2D_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(rans_encode_kernel, dim3(chunks), dim3(64), lds, (hipStream_t)st, a);
+    return check_launch("codec rans encode");
+}
+
+int gi2d_codec_rans_expand(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, int chunk_log2,
+                           unsigned coded_mask, const void *tables, size_t tables_bytes, const void *directory,
+                           const void *chunk_data, size_t chunk_data_bytes, size_t max_chunk_bytes, void *payload,
+                           size_t payload_bytes, int32_t *status, int token, gi2d_stream_t st) {
+    RansLayout L;
+    if (!rans_layout("codec rans expand", kind, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask, L))
+        return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 1) {
+        set_error("codec rans expand: no gaussians");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    const long long need = codec_dwords(n, L.rec.record_bits);
+    const int chunks = rans_chunks(n, chunk_log2);
+    if (payload_bytes < (size_t)need * 4 || tables_bytes != (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES) {
+        set_error("codec rans expand: output shorter than 4 * ceil(N * R / 32) bytes, or tables not one per coded field");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    // every chunk holds its states and raw section; none is longer than the largest the coder can make
+    const int full = 64 + rans_raw_cap(L);
+    const int tail_records = n - ((chunks - 1) << chunk_log2);
+    const int smallest = chunks > 1 ? full : 64 + (tail_records * L.raw_bits + 31) / 32;
+    if ((max_chunk_bytes & 3) || max_chunk_bytes < (size_t)smallest * 4 || max_chunk_bytes > (size_t)rans_chunk_cap(L) * 4 ||
+        (chunk_data_bytes & 3) || chunk_data_bytes > 0xffffffffull || chunk_data_bytes < max_chunk_bytes) {
+        set_error("codec rans expand: chunk sizes do not fit N, the field widths and the chunk size");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    if (!directory || !chunk_data || !payload || !status || (L.ncoded && !tables) ||
+        (((uintptr_t)directory | (uintptr_t)chunk_data | (uintptr_t)payload | (uintptr_t)status | (uintptr_t)tables) & 3)) {
+        set_error("codec rans expand: null or misaligned pointer");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    RansExpandArgs a;
+    a.L = L, a.n = n, a.chunks = chunks, a.tables = (const uint32_t *)tables, a.dir = (const uint32_t *)directory;
+    a.data = (const uint32_t *)chunk_data, a.data_dwords = (uint32_t)(chunk_data_bytes / 4);
+    a.in_cap = (int)(max_chunk_bytes / 4), a.out = (uint32_t *)payload, a.out_dwords = need;
+    a.status = status, a.token = token;
+    const size_t table_b = (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES;
+    const size_t wave_b = ((size_t)a.in_cap + 2 * L.rec.record_bits) * 4;
+    int waves = 4;
+    while (waves > 1 && (table_b + waves * wave_b > GI2D_RANS_STATIC_LDS || waves > chunks)) waves >>= 1;
+    const size_t lds = table_b + waves * wave_b;
+    if (!rans_reserve_lds("codec rans expand", rans_expand_kernel, lds)) return GI2D_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(rans_expand_kernel, dim3((chunks + waves - 1) / waves), dim3(64 * waves), lds, (hipStream_t)st, a);
+    return check_launch("codec rans expand");
+}
+
+}  // extern "C"

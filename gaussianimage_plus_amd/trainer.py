@@ -675,11 +675,11 @@ class NativeFitter:
             out["bpp_wc"] = out["position_bpp"] + out["cholesky_bpp_wc"] + out["feature_dc_bpp_wc"]
         return out
 
-    def encode(self) -> bytes:
+    def encode(self, coding: str = "fixed") -> bytes:
         """The packed stream of the quantised model (gaussianimage_plus_amd/codec.py): codec.decode() turns it back into
-        the picture decompress_wo_ec() renders, in any process."""
+        the picture decompress_wo_ec() renders, in any process.  coding="rans": the same codes entropy coded."""
         from . import codec
-        return codec.encode(self)
+        return codec.encode(self, coding=coding)
 
     # ------------------------------------------------------------------ rotation-scale codec
     def _compress_wo_ec_rs(self) -> Dict[str, torch.Tensor]:

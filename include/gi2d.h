@@ -610,6 +610,42 @@ int gi2d_codec_decode_bin(int kind, int num_points, int xy_bits, int p0_bits, in
                           float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors,
                           void *workspace, size_t workspace_bytes, int32_t *status, gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ rANS payload (payload coding 1 of format 1)
+ * The records of coding 0, entropy coded: gaussianimage_plus_amd/codec.py owns the container (tag "rANS", model section,
+ * chunk directory, chunk data; INTEGRATION.md has the table) and validates all of it on the host.  A field of width w is
+ * split into hi = v >> lo_bits (lo_bits = max(0, w - 8); the symbol) and lo (raw); coded_mask bit k = field k (record
+ * order) is entropy coded, a clear bit stores the whole field raw.  A chunk is 2^chunk_log2 records (8..12) and one
+ * wave's work: lane l owns records base + 64 j + l and one 32-bit state in [2^16, 2^32) (12 probability bits, 16-bit
+ * words); a chunk's bytes are 64 u32 final states | raw section (records x R_raw bits, LSB-first, dword padded) | u16
+ * words in decoding order, padded to 4 bytes.
+ *   tables   DEVICE, one per coded field in record order, 4612 bytes each: u8 symbol of slot [4096] | u16 cumulative
+ *            frequency of symbol [258] (entries 256 and 257 = 4096).  Built by the host from a validated model section.
+ *   gi2d_codec_histogram    coding-0 payload -> hist u32[8][256] (device, zeroed by the call): counts of the hi parts.
+ *   gi2d_codec_rans_encode  coding-0 payload + tables -> chunk c at scratch + c * (scratch bytes / chunks), lengths[c]
+ *                           its bytes (device u32[chunks]; 0xffffffff: a symbol the tables give frequency 0).  scratch
+ *                           is gi2d_codec_rans_scratch_bytes (0 for an invalid layout); the caller compacts the chunks.
+ *   gi2d_codec_rans_expand  directory (device u32[chunks + 1] byte offsets into chunk_data) + chunk_data -> the coding-0
+ *                           payload (every dword written), which gi2d_codec_decode_bin reads next.  max_chunk_bytes: the
+ *                           largest chunk of the directory (sizes the LDS staging of a wave).  `status`: ONE device word
+ *                           raised to `token` (atomic max) if some lane does not end at 2^16 -- the stream's content
+ *                           is not what an encoder wrote; callers pass a token larger than any before.  Offsets, lengths,
+ *                           slots, symbols and word positions read from the stream are clamped or masked on the device:
+ *                           no content reaches beyond chunk_data, the tables or the output.
+ * Every entry checks its arguments before it launches anything. */
+size_t gi2d_codec_rans_scratch_bytes(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                                     int chunk_log2, unsigned coded_mask);
+int gi2d_codec_histogram(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                         const void *payload, size_t payload_bytes, uint32_t *hist, gi2d_stream_t stream);
+int gi2d_codec_rans_encode(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                           int chunk_log2, unsigned coded_mask, const void *tables, size_t tables_bytes,
+                           const void *payload, size_t payload_bytes, void *scratch, size_t scratch_bytes,
+                           uint32_t *lengths, gi2d_stream_t stream);
+int gi2d_codec_rans_expand(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                           int chunk_log2, unsigned coded_mask, const void *tables, size_t tables_bytes,
+                           const void *directory, const void *chunk_data, size_t chunk_data_bytes,
+                           size_t max_chunk_bytes, void *payload, size_t payload_bytes, int32_t *status, int token,
+                           gi2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

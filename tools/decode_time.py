@@ -5,11 +5,14 @@ For N = 5 000 and N = 50 000 (covariance model, 12 / 10 / 6 bits), microseconds 
     bytes   from host bytes: header parse, CRC, one host-to-device copy, the same launches
     legacy  the same encoding through NativeFitter.decompress_wo_ec (quantiser decompress launches, the projection and
             rasterize operators with their allocations)
-each the median of five timed regions after warm-up.  A region is a host clock around `reps` back-to-back decodes that
+each the median of five timed regions after warm-up.  --coding rans adds, per chunk size of --chunk-log2, the same
+stream entropy coded (payload coding 1): its bytes and bpp next to analysis_wo_ec(entropy_estimate=True)'s bpp_wc, and
+its decode times (`device`: expansion kernel + the launches above; `bytes`: also the smaller CRC and copy, and the host
+building the model tables).  A region is a host clock around `reps` back-to-back decodes that
 ends in a device synchronise: no event pairs inside it (a pair costs the queue about 5 us per dispatch).
 The gaussians are those of a short quantised fit, so tile populations are a real picture's.
 
-    python tools/decode_time.py [--reps 200] [--trace]
+    python tools/decode_time.py [--reps 200] [--coding fixed|rans] [--chunk-log2 10 8 12] [--trace]
 --trace decodes a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for
 the per-kernel split (profiles/decode_kernel_stats.csv).
 """
@@ -61,6 +64,8 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--sizes", type=int, nargs="+", default=[5000, 50000])
+    ap.add_argument("--coding", choices=["fixed", "rans"], default="fixed")
+    ap.add_argument("--chunk-log2", type=int, nargs="+", default=[codec.DEFAULT_CHUNK_LOG2])
     ap.add_argument("--trace", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_time.py needs the GPU"
@@ -76,9 +81,16 @@ def main():
         out = torch.empty(H, W, 3, device="cuda:0")
         want = fit.decompress_wo_ec(enc)
         assert torch.equal(dec.decode(up, out=out), want) and torch.equal(dec.decode(blob), want)
+        coded = {}
+        if a.coding == "rans":
+            for k in a.chunk_log2:
+                coded[k] = codec.recode(blob, "rans", chunk_log2=k)
+                assert torch.equal(dec.decode(coded[k]), want) and codec.recode(coded[k], "fixed") == blob
         if a.trace:
-            for _ in range(50):
-                dec.decode(up, out=out)
+            ups = [up] + [dec.upload(c) for c in coded.values()]
+            for u in ups:
+                for _ in range(50):
+                    dec.decode(u, out=out)
             torch.cuda.synchronize()
             continue
         info = codec.info(blob)
@@ -90,6 +102,18 @@ def main():
             row[key + "_us"] = round(med, 2)
             row[key + "_us_range"] = [round(lo, 2), round(hi, 2)]
         row["decodes_per_second_device"] = round(1e6 / row["device_us"], 1)
+        if coded:
+            row["bpp_wc_estimate"] = round(fit.analysis_wo_ec(enc, entropy_estimate=True)["bpp_wc"], 5)
+            row["rans"] = {}
+        for k, c in coded.items():
+            ci, cup = codec.info(c), dec.upload(c)
+            r = {"stream_bytes": len(c), "bpp": round(ci["bpp"], 5), "ratio": round(len(c) / len(blob), 4),
+                 "field_modes": ci["field_modes"], "chunks": ci["chunks"]}
+            for key, fn in (("device", lambda: dec.decode(cup, out=out)), ("bytes", lambda: dec.decode(c, out=out))):
+                med, lo, hi = median_us(fn, a.reps)
+                r[key + "_us"] = round(med, 2)
+                r[key + "_us_range"] = [round(lo, 2), round(hi, 2)]
+            row["rans"][str(k)] = r
         res["sizes"][str(n)] = row
     if not a.trace:
         print(json.dumps(res))
