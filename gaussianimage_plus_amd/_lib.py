@@ -81,6 +81,11 @@ SIGNATURES.update({
     "gi2d_codec_histogram": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p],
     "gi2d_codec_rans_encode": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _sz, _p, _sz, _p, _p],
     "gi2d_codec_rans_expand": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _p, _sz, _sz, _p, _sz, _p, _i, _p],
+    # SSIM / MS-SSIM (gaussianimage_plus_amd/metrics.py; the batched entries take struct gi2d_ssim_pair[])
+    "gi2d_ssim_forward": [_p, _p, _p, _p, _i, _i, _i, _p, _f, _f, _f, _i, _p, _i, _p, _p, _sz, _p],
+    "gi2d_ssim_backward": [_p, _p, _p, _p, _i, _i, _i, _p, _f, _f, _f, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p],
+    "gi2d_ssim_forward_batched": [_i, _p, _i, _p, _f, _f, _f, _i, _p, _i, _p, _p, _sz, _p],
+    "gi2d_ssim_backward_batched": [_i, _p, _i, _p, _f, _f, _f, _i, _p, _i, _p, _p, _p, _sz, _p],
 })
 SIZE_FUNCS = {
     "gi2d_fast_workspace_bytes": [_i, _i, _i],
@@ -93,6 +98,8 @@ SIZE_FUNCS = {
     "gi2d_train_inbox_bytes": [_i, _i],
     "gi2d_codec_payload_bytes": [_i, _i, _i, _i, _i, _i],
     "gi2d_codec_rans_scratch_bytes": [_i, _i, _i, _i, _i, _i, _i, _u],
+    "gi2d_ssim_workspace_bytes": [_i, _i, _i, _i],
+    "gi2d_ssim_batch_workspace_bytes": [_i, _p, _i, _i],
 }
 STRING_FUNCS = ["gi2d_version", "gi2d_last_error_string"]
 

@@ -26,6 +26,9 @@ import torch.distributed as dist
 
 # per-image results of the quantised loop that ride along in the same five-float-style all-reduce
 CODEC_KEYS = ("bpp", "position_bpp", "cholesky_bpp", "feature_dc_bpp", "bpp_wc", "psnr_decoded")
+# MS-SSIM of the render and of the decoded image (train.py:190, train_quantize.py:213,256): an image too small for five
+# scales reports NaN and is left out of the average's count (no image with a value: no average)
+SSIM_KEYS = ("ms_ssim", "ms_ssim_decoded")
 
 
 def partition(num_items: int, rank: int, world_size: int) -> List[int]:
@@ -36,7 +39,8 @@ def partition(num_items: int, rank: int, world_size: int) -> List[int]:
 def reduce_metrics(local: Dict[str, float], device="cpu") -> Dict[str, float]:
     """Sum the per-rank totals (psnr, train seconds, eval seconds, gaussians, images) across ranks with one
     all-reduce and return the averages the reference logs."""
-    keys = ["psnr", "train_s", "eval_s", "num_gaussians", "count"] + list(CODEC_KEYS)
+    keys = ["psnr", "train_s", "eval_s", "num_gaussians", "count"] + list(CODEC_KEYS) + \
+        [k + suffix for k in SSIM_KEYS for suffix in ("", "_count")]
     t = torch.tensor([float(local.get(k, 0.0)) for k in keys], dtype=torch.float64, device=device)
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
@@ -47,6 +51,9 @@ def reduce_metrics(local: Dict[str, float], device="cpu") -> Dict[str, float]:
            "sum_train_s": tot["train_s"]}
     for k in CODEC_KEYS:  # train_quantize.py:411-420 averages the sizes over the images too
         out["avg_" + k] = tot[k] / n
+    for k in SSIM_KEYS:  # over the images that reported one (no entry when none did)
+        if tot[k + "_count"] > 0:
+            out["avg_" + k] = tot[k] / tot[k + "_count"]
     return out
 
 
@@ -66,6 +73,11 @@ def run_sharded(items: Sequence, fit_one: Callable[[int, object], Dict[str, floa
             rows.append((i, r))
             for key in ("psnr", "eval_s", "num_gaussians") + CODEC_KEYS:
                 local[key] = local.get(key, 0.0) + float(r.get(key, 0.0))
+            for key in SSIM_KEYS:
+                v = float(r.get(key, float("nan")))
+                if not math.isnan(v):
+                    local[key] = local.get(key, 0.0) + v
+                    local[key + "_count"] = local.get(key + "_count", 0.0) + 1
             if not shared or k == 0:
                 local["train_s"] += float(r.get("train_s", 0.0))
             local["count"] += 1
@@ -198,7 +210,7 @@ def fit_images_native(gts: Sequence[torch.Tensor], num_points: int, iterations: 
                         live.remove(i)
     torch.cuda.synchronize(dev)
     train_s = time.time() - t0
-    out = []
+    out, renders, decoded = [], [], []
     for f, st in zip(fitters, streams):
         with torch.cuda.stream(st):
             f.check_status()
@@ -216,6 +228,7 @@ def fit_images_native(gts: Sequence[torch.Tensor], num_points: int, iterations: 
             st.synchronize()
             eval_s = (time.time() - t0) / max(int(eval_renders), 1)
             mse = torch.nn.functional.mse_loss(img, f.gt).item()
+            renders.append(img)
         row = {"psnr": 10 * math.log10(1.0 / max(mse, 1e-12)), "train_s": train_s, "eval_s": eval_s,
                "num_gaussians": f.n, "final_num_gaussians": final_n, "mse": mse}
         if quantize:  # train_quantize.py:239-270 encode(): codes, decoded render, size
@@ -224,8 +237,17 @@ def fit_images_native(gts: Sequence[torch.Tensor], num_points: int, iterations: 
                 dec = f.decompress_wo_ec(enc)
                 row.update(f.analysis_wo_ec(enc, entropy_estimate=True))
                 row["psnr_decoded"] = 10 * math.log10(1.0 / max(torch.nn.functional.mse_loss(dec, f.gt).item(), 1e-12))
+                decoded.append(dec)
                 row["num_gaussians"] = f.n
         out.append(row)
+    # the second quality number of every results line (train.py:190, train_quantize.py:213,256): one batched call for all
+    # renders, one for all decoded images (every stream above has been waited for by its .item() reads)
+    from . import metrics
+    metric = metrics._metric_of(gts[0])
+    for key, pictures in (("ms_ssim", renders), ("ms_ssim_decoded", decoded)):
+        if pictures:
+            for row, v in zip(out, metric.ms_ssim_many(pictures, [f.gt for f in fitters]).tolist()):
+                row[key] = v
     return out
 
 
@@ -436,10 +458,11 @@ def main(argv=None):
         print(f"[rank {rank}] image {i}: {img.shape[0]}x{img.shape[1]}, PSNR:{r['psnr']:.4f}, "
               f"Training:{r['train_s']:.4f}s, Eval:{r['eval_s']:.8f}s, FPS:{1.0 / r['eval_s']:.4f}, "
               f"gaussians:{int(r['num_gaussians'])}" +
+              (f", MS_SSIM:{r['ms_ssim']:.6f}" if "ms_ssim" in r else "") +
               (f", bpp:{r['bpp']:.4f} (position {r['position_bpp']:.4f}, cholesky {r['cholesky_bpp']:.4f}, "
                f"feature_dc {r['feature_dc_bpp']:.4f})" +
                (f", entropy-coded estimate bpp_wc:{r['bpp_wc']:.4f}" if "bpp_wc" in r else "") +
-               f", decoded PSNR:{r['psnr_decoded']:.4f}" if "bpp" in r else ""),
+               f", decoded PSNR:{r['psnr_decoded']:.4f}, decoded MS_SSIM:{r['ms_ssim_decoded']:.6f}" if "bpp" in r else ""),
               flush=True)
 
     def fit_one(i, img):
@@ -467,13 +490,14 @@ def main(argv=None):
     if rank == 0:
         sizes = sorted({(int(im.shape[1]), int(im.shape[0])) for im in images})
         size = f"{sizes[0][0]}x{sizes[0][1]}" if len(sizes) == 1 else f"{len(sizes)} image sizes"
-        print(f"Average: {size}, PSNR:{out['avg_psnr']:.4f}, Training:{out['avg_train_s']:.4f}s, "
+        print(f"Average: {size}, PSNR:{out['avg_psnr']:.4f}, MS_SSIM:{out.get('avg_ms_ssim', float('nan')):.6f}, Training:{out['avg_train_s']:.4f}s, "
               f"Eval:{out['avg_eval_s']:.8f}s, FPS:{1.0 / max(out['avg_eval_s'], 1e-12):.4f}, "
               f"images:{out['images']}, gpus:{world}, wall:{wall:.2f}s, images/sec:{out['images'] / wall:.4f}" +
               (f", bpp:{out['avg_bpp']:.4f}" +
                # the rotation-scale model has no entropy-coded size (models/gaussianimage_rs.py has no analysis_wc)
                (f", bpp_wc (estimate):{out['avg_bpp_wc']:.4f}" if out["avg_bpp_wc"] > 0 else "") +
-               f", decoded PSNR:{out['avg_psnr_decoded']:.4f}" if args.quantize else ""), flush=True)
+               f", decoded PSNR:{out['avg_psnr_decoded']:.4f}, decoded MS_SSIM:{out.get('avg_ms_ssim_decoded', float('nan')):.6f}"
+               if args.quantize else ""), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -320,6 +320,17 @@ class NativeFitter:
         mse = torch.nn.functional.mse_loss(self.render(), self.gt).item()
         return 10 * math.log10(1.0 / max(mse, 1e-12))
 
+    def ssim(self, **kw) -> float:
+        """SSIM of the current render against the target (metrics.ssim; one host read, like psnr())."""
+        from . import metrics
+        return float(metrics.ssim(self.render(), self.gt, data_range=1, size_average=True, **kw).item())
+
+    def ms_ssim(self, **kw) -> float:
+        """MS-SSIM of the current render against the target, the number train.py:190 logs next to the PSNR
+        (metrics.ms_ssim; one host read).  The image must be large enough for five scales: min(H, W) > 160."""
+        from . import metrics
+        return float(metrics.ms_ssim(self.render(), self.gt, data_range=1, size_average=True, **kw).item())
+
     def check_status(self):
         """Raises if any step since the last check overflowed a tile bucket (sticky flag status[2])."""
         now, sticky = self.status[1:3].tolist()
@@ -849,6 +860,19 @@ class BatchFitter:
         self.max_call = 256
 
     iteration = property(lambda self: self.fitters[0].iteration)
+
+    def ms_ssim(self, **kw):
+        """MS-SSIM of every fitter's current render against its target: one batched metric call for the whole batch
+        (metrics.Metric.ms_ssim_many), one host read.  A list of floats; NaN for an image too small for five scales."""
+        from . import metrics
+        renders = [f.render() for f in self.fitters]
+        return metrics._metric_of(renders[0]).ms_ssim_many(renders, [f.gt for f in self.fitters], **kw).tolist()
+
+    def ssim(self, **kw):
+        """The same for single-scale SSIM."""
+        from . import metrics
+        renders = [f.render() for f in self.fitters]
+        return metrics._metric_of(renders[0]).ssim_many(renders, [f.gt for f in self.fitters], **kw).tolist()
 
     def train(self, iterations: int) -> None:
         """`iterations` training iterations of every image (asynchronous: only kernel launches)."""

@@ -646,6 +646,55 @@ int gi2d_codec_rans_expand(int kind, int num_points, int xy_bits, int p0_bits, i
                            size_t max_chunk_bytes, void *payload, size_t payload_bytes, int32_t *status, int token,
                            gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ structural similarity (SSIM, MS-SSIM)
+ * The reference's second quality number and the structural terms of its losses (train.py:190 ms_ssim(render, gt,
+ * data_range=1, size_average=True); models/utils.py:60-80), csrc/gi2d_ssim.hip; DESIGN.md 3.9 restates the arithmetic.
+ * An image is three channels of fp32 addressed by element strides (pixel, channel, row): {3, 1, 3 W} reads [H,W,3],
+ * {1, H W, W} reads [1,3,H,W].  X is the prediction, Y the target (no gradient).  win: odd, 3 .. 11, taps_host its
+ * HOST f32[win] filter; C1 = (k1 data_range)^2, C2 = (k2 data_range)^2; levels = 1 (SSIM; `nonnegative` clamps a
+ * channel's mean at 0) or 5 (MS-SSIM, weights_host HOST f32[5]).  A side smaller than the window is an error, and so
+ * is min(H, W) <= (win - 1) * 16 with five levels.  All sums run in a fixed order: results repeat bit for bit, and an
+ * image's numbers do not depend on the batch it runs in.
+ *   result   DEVICE f32[GI2D_SSIM_RESULT_FLOATS] per image: [0] the mean over channels, [1..3] the value of each
+ *            channel, then four [5][3] tables by (scale, channel): mean ssim at 4, mean cs at 19, d value / d mean ssim
+ *            at 34, d value / d mean cs at 49 (zero where a relu cut).  Written by the last kernel of the forward call;
+ *            there is no host wait inside any call.
+ *   workspace  gi2d_ssim_workspace_bytes / gi2d_ssim_batch_workspace_bytes (0 and an error message for invalid sizes),
+ *            256-byte aligned.  The backward call reads what the forward call on the SAME workspace and arguments left
+ *            there (the pooled images); nothing else may use it in between.
+ *   backward   grad_result DEVICE f32[3] per image: dL / d value of each channel.  grad_x (strides as for x) receives
+ *            dL/dX; every element of the image is written.
+ * The batched entries take a HOST array of 1 .. GI2D_SSIM_MAX_BATCH pairs of any sizes; results / grad_results are
+ * [k][GI2D_SSIM_RESULT_FLOATS] / [k][3]. */
+#define GI2D_SSIM_MAX_LEVELS 5
+#define GI2D_SSIM_MAX_BATCH 64
+#define GI2D_SSIM_RESULT_FLOATS 64
+typedef struct gi2d_ssim_pair {
+    const float *x, *y;
+    float *grad_x; /* backward only */
+    int64_t x_stride[3], y_stride[3], grad_stride[3];
+    int32_t width, height;
+} gi2d_ssim_pair;
+size_t gi2d_ssim_workspace_bytes(int width, int height, int levels, int win);
+size_t gi2d_ssim_batch_workspace_bytes(int k, const gi2d_ssim_pair *pairs_host, int levels, int win);
+int gi2d_ssim_forward(const float *x, const int64_t *x_stride_host, const float *y, const int64_t *y_stride_host,
+                      int width, int height, int win, const float *taps_host, float data_range, float k1, float k2,
+                      int levels, const float *weights_host, int nonnegative, float *result, void *workspace,
+                      size_t workspace_bytes, gi2d_stream_t stream);
+int gi2d_ssim_backward(const float *x, const int64_t *x_stride_host, const float *y, const int64_t *y_stride_host,
+                       int width, int height, int win, const float *taps_host, float data_range, float k1, float k2,
+                       int levels, const float *weights_host, int nonnegative, const float *result,
+                       const float *grad_result, float *grad_x, const int64_t *grad_stride_host, void *workspace,
+                       size_t workspace_bytes, gi2d_stream_t stream);
+int gi2d_ssim_forward_batched(int k, const gi2d_ssim_pair *pairs_host, int win, const float *taps_host,
+                              float data_range, float k1, float k2, int levels, const float *weights_host,
+                              int nonnegative, float *results, void *workspace, size_t workspace_bytes,
+                              gi2d_stream_t stream);
+int gi2d_ssim_backward_batched(int k, const gi2d_ssim_pair *pairs_host, int win, const float *taps_host,
+                               float data_range, float k1, float k2, int levels, const float *weights_host,
+                               int nonnegative, const float *results, const float *grad_results, void *workspace,
+                               size_t workspace_bytes, gi2d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
