@@ -28,6 +28,13 @@ Kodak pictures (tests/golden/kodak24.npz: pixels of datasets/kodak/kodim01..24.p
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline needs and no more: set-up, warm-up, the
+timed regions, `--dump-outputs`, the line with `value` / `ms_per_step`.  Everything else this file measures -- the tile
+pass's own time from HIP events and the `roofline` blocks built on it, `static_scene_step`, `dropin_autograd_step`,
+`batched`, `images_per_s`, `cpu_baseline`, the optional `quantized_train_step` and `concurrent_images` -- runs under
+`--full` (some 40 seconds in all at the defaults).  The timed regions, what they start from and the dumped arrays
+are the same in both.
+
 `--dump-outputs DIR`: behind the last timed region, what its last iteration left in the fitter (parameters, Adam moments,
 render, projection of the updated gaussians) goes to DIR/<name>.npy.  Inputs are seeded, so two builds run with the
 same arguments can be compared array for array (two runs of one build at the default workload: equal bit for bit).
@@ -55,6 +62,10 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: kernel times from HIP events and the roofline blocks, static_scene_step, "
+                        "dropin_autograd_step, batched, images_per_s, cpu_baseline (each has its own switch below; "
+                        "without --full none of them runs)")
     p.add_argument("--num-points", type=int, default=50000)
     p.add_argument("--height", type=int, default=512)
     p.add_argument("--width", type=int, default=768)
@@ -82,7 +93,10 @@ def parse(argv=None):
     p.add_argument("--dump-outputs", metavar="DIR",
                    help="write what the last timed iteration left in the fitter to DIR/<name>.npy (float32; ranks of a "
                         "multi-GPU run add _rank<r> to the name)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if not args.full and (args.train_step or args.images_per_gpu_probe):
+        p.error("--train-step and --images-per-gpu-probe add to the --full run: give --full as well")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ N ranks from one command
@@ -127,7 +141,6 @@ def main(argv=None):
 
 
 def run_rank(args):
-    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -173,12 +186,12 @@ def run_rank(args):
     # The timed region -- exactly `steps` iterations as ONE call, a barrier + synchronize on both sides, max over ranks
     # -- is taken REPEATS times and the median reported: the shared boxes show queue stalls of tens of ms once in a few
     # hundred ms of runtime (measurement hazard), which would multiply a single 0.7 ms region.
-    # Between two of them the SAME region is taken once more with HIP start/stop events attached to every
+    # Between two of them, under --full, the SAME region is taken once more with HIP start/stop events attached to every
     # EVENT_STRIDE-th tile-pass dispatch (gi2d_timer_*: the kernel's own begin/end timestamps on the launch stream) --
     # the dominant kernel's duration for `roofline`.  The two are kept apart because an event pair is not free: the
     # queue spends about 5 us on every dispatch that carries one (round 6, measured: 28.3 us per iteration with a pair on
     # every 2nd tile pass, 26.7 on every 5th, 25.7 without), which rounds 1-5 charged to `value`.  Both kinds are
-    # reported (`ms_per_step`, `ms_per_step_event_regions`).
+    # reported (`ms_per_step`, `ms_per_step_event_regions`).  A plain run takes that region without events or a reading.
     def timed_region():
         barrier()
         t0 = time.perf_counter()
@@ -193,6 +206,13 @@ def run_rank(args):
     regions, event_regions, kernel_us, first_of_call = [], [], [], []
     for _ in range(REPEATS):
         regions.append(timed_region())
+        if not args.full:
+            # a plain run reports no kernel time; it still takes the region that lies between two timed ones (same
+            # kernels, same arguments, same barriers, no event pair, its time not kept), so that every timed region
+            # starts from the scene and the idle queue it starts from under --full and --dump-outputs writes the same
+            # arrays.  (Without the barrier behind it the next region read 0.4 us per iteration more at --steps 20.)
+            timed_region()
+            continue
         timers = _lib.TilePassTimers(per_region)
         timers.arm(EVENT_STRIDE)
         event_regions.append(timed_region())
@@ -207,9 +227,6 @@ def run_rank(args):
     fit.check_status()
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, fitter_outputs(fit), "" if world == 1 else f"_rank{rank}")
-    first_pass_us = [u for u, f in zip(kernel_us, first_of_call) if f]
-    if fit.tx * fit.ty <= 1536 and len(first_pass_us) < len(kernel_us):
-        kernel_us = [u for u, f in zip(kernel_us, first_of_call) if not f]
     m = int(fit.nth[:n].sum().item())  # tile intersections of the last projection (drifts as the gaussians move)
 
     ms = torch.tensor([float(m)], dtype=torch.float64, device=red_dev)
@@ -218,27 +235,9 @@ def run_rank(args):
     elapsed = sorted(regions)[len(regions) // 2]
     value = world * args.steps / elapsed
 
-    images = images_per_s(args, rank, world, dev, red_dev, barrier) if args.images > 0 else None
+    images = images_per_s(args, rank, world, dev, red_dev, barrier) if (args.full and args.images > 0) else None
 
     if rank == 0:
-        avg_us = float(np.mean(kernel_us))
-        pair_bytes = 80 * m + 36 * h * w + 36 * n  # SURVEY 8d north-star figure (fwd + bwd rasterize)
-        achieved = pair_bytes / (avg_us * 1e-6) / 1e9
-        # one launch of the general form up to one residency round of the chip (1536 tiles); larger images run the tile
-        # pass in two launches -- the small form, then the general one on the tiles it passed over (csrc/gi2d_fast.hip):
-        # the events bracket both, the stored counters are summed over both
-        # (which of the two the timed calls took: gi2d_batch_tile_pass_form on the fitter's workspace -- two launches
-        # while at most one row in sixteen is fuller than the small form's 128 candidates)
-        two = bool(_lib.load().gi2d_batch_tile_pass_form(fit.ws.data_ptr()))
-        # (third template argument: built with the code that takes entrants out of the tiles' inboxes -- every tile
-        # pass of a single-image call but its first; csrc/gi2d_fast_internal.h::Inbox)
-        kernel = "gi2d::fast_fwdbwd_kernel<1, 1, false> + gi2d::fast_fwdbwd_kernel<1, 2, false>" if two else \
-            ("gi2d::fast_fwdbwd_kernel<1, 0, true>" if fit.tx * fit.ty <= 1536 else "gi2d::fast_fwdbwd_kernel<1, 0, false>")
-        traffic, traffic_src = pmc_traffic(kernel, n, h, w)
-        # the counters were collected at the intersection count of THAT run (the scene drifts while it trains, and a
-        # 20-step run sits at another M than a 200-step one): the wasted-traffic ratio is formed like for like
-        traffic_m = stored_num_intersects(n, h, w)
-        traffic_ratio = (traffic / (80 * traffic_m + 36 * h * w + 36 * n)) if (traffic and traffic_m) else None
         line = {
             "metric": f"training iters/sec (fwd+bwd rasterize) at N Gaussians, {w}x{h}",
             "value": value,
@@ -249,15 +248,19 @@ def run_rank(args):
             "repeats": REPEATS,
             "ms_per_step": elapsed / args.steps * 1e3,
             "ms_per_step_each_region": [r / args.steps * 1e3 for r in regions],
+        }
+        if args.full:
             # the same region with a HIP event pair on every EVENT_STRIDE-th tile pass (where `roofline` gets its kernel
             # time from): what rounds 1-5 reported as ms_per_step
-            "ms_per_step_event_regions": sorted(event_regions)[len(event_regions) // 2] / args.steps * 1e3,
-            "event_stride": EVENT_STRIDE,
+            line["ms_per_step_event_regions"] = sorted(event_regions)[len(event_regions) // 2] / args.steps * 1e3
+            line["event_stride"] = EVENT_STRIDE
+        line.update({
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f32",
-            "data": "synthetic" if (args.images <= 0 or args.synthetic_images) else
+            "full": bool(args.full),
+            "data": "synthetic" if (not args.full or args.images <= 0 or args.synthetic_images) else
                     "synthetic (step metric, batched); kodak (images_per_s)",
             "config": {
                 "workload": f"Cholesky model, N={n} Gaussians, {w}x{h}, one image per GPU, whole training iterations with "
@@ -270,44 +273,76 @@ def run_rank(args):
                              "gradient reduce + project bwd + Adam of this iteration fused with activations + project + "
                              "binning of the next) on persistent HBM buffers, eager launches on the current HIP stream",
             },
-            "roofline": {
-                "bound": "hbm", "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                "traffic_measured_at_num_intersects": traffic_m, "traffic_over_algorithmic_at_that_count": traffic_ratio,
-                "algorithmic_bytes_per_launch": pair_bytes, "avg_kernel_us": avg_us,
-                "min_kernel_us": float(np.min(kernel_us)), "kernel_samples": len(kernel_us),
-                "first_pass_of_a_call": {"kernel": "gi2d::fast_fwdbwd_kernel<1, 0, false>", "samples": len(first_pass_us),
-                                         "avg_kernel_us": float(np.mean(first_pass_us)) if first_pass_us else None},
-                "note": "not HBM-bound: each staged gaussian is reused by up to 256 pixels, so the tile pass is bound by "
-                        "instruction issue and dependent latency (roofline_valu; DESIGN.md 3.4)",
-            },
-            "roofline_valu": valu_roofline(kernel, n, h, w, avg_us),
-            "rasterize_pair": {
-                "fwdbwd_kernel_us": avg_us, "algorithmic_bytes": pair_bytes, "achieved_GBps": achieved,
-                # every staged (tile, gaussian) entry against every pixel of its tile, forward + backward: the NOMINAL
-                # pair count of the reference's loops (forward.cu:650, backward.cu:1258), not evaluated work
-                "nominal_pairs_per_s": 2 * 256.0 * m / (avg_us * 1e-6),
-                "note": "HIP start/stop events of the tile-pass kernel inside timed calls of the same loop "
-                        "(ms_per_step_event_regions)"},
-        }
-        if not args.no_static:
-            line["static_scene_step"] = static_scene_rate(xyz, L, col, op, gt, n, h, w, dev)
-        if not args.no_dropin:
-            line["dropin_autograd_step"] = dropin_autograd_rate(gt, n)
-        if not args.no_batched:
-            line["batched"] = batched_rate(n, h, w, dev)
-        if images is not None:
-            line["images_per_s"] = images
-        if args.train_step:
-            line["quantized_train_step"] = quantized_train_step_rate(gt, dev)
-        if args.images_per_gpu_probe:
-            line["concurrent_images"] = concurrent_images_rate(n, h, w, dev)
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(xyz, L, col, op, gt_np, h, w, args.cpu_seconds)
+        })
+        if args.full:
+            line.update(tile_pass_blocks(fit, kernel_us, first_of_call, m, n, h, w))
+            if not args.no_static:
+                line["static_scene_step"] = static_scene_rate(xyz, L, col, op, gt, n, h, w, dev)
+            if not args.no_dropin:
+                line["dropin_autograd_step"] = dropin_autograd_rate(gt, n)
+            if not args.no_batched:
+                line["batched"] = batched_rate(n, h, w, dev)
+            if images is not None:
+                line["images_per_s"] = images
+            if args.train_step:
+                line["quantized_train_step"] = quantized_train_step_rate(gt, dev)
+            if args.images_per_gpu_probe:
+                line["concurrent_images"] = concurrent_images_rate(n, h, w, dev)
+            if not args.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = cpu_baseline(xyz, L, col, op, gt_np, h, w, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if world > 1:
         barrier()
         dist.destroy_process_group()
+
+
+def tile_pass_blocks(fit, kernel_us, first_of_call, m, n, h, w):
+    """--full: `roofline`, `roofline_valu` and `rasterize_pair` from the tile pass's own time, as the event pairs of the
+    event-carrying regions gave it (`first_of_call[j]`: sample j sat on the first tile pass of a C-ABI call)."""
+    import numpy as np
+    from gaussianimage_plus_amd import _lib
+    first_pass_us = [u for u, f in zip(kernel_us, first_of_call) if f]
+    if fit.tx * fit.ty <= 1536 and len(first_pass_us) < len(kernel_us):
+        kernel_us = [u for u, f in zip(kernel_us, first_of_call) if not f]
+    avg_us = float(np.mean(kernel_us))
+    pair_bytes = 80 * m + 36 * h * w + 36 * n  # SURVEY 8d north-star figure (fwd + bwd rasterize)
+    achieved = pair_bytes / (avg_us * 1e-6) / 1e9
+    # one launch of the general form up to one residency round of the chip (1536 tiles); larger images run the tile
+    # pass in two launches -- the small form, then the general one on the tiles it passed over (csrc/gi2d_fast.hip):
+    # the events bracket both, the stored counters are summed over both
+    # (which of the two the timed calls took: gi2d_batch_tile_pass_form on the fitter's workspace -- two launches
+    # while at most one row in sixteen is fuller than the small form's 128 candidates)
+    two = bool(_lib.load().gi2d_batch_tile_pass_form(fit.ws.data_ptr()))
+    # (third template argument: built with the code that takes entrants out of the tiles' inboxes -- every tile
+    # pass of a single-image call but its first; csrc/gi2d_fast_internal.h::Inbox)
+    kernel = "gi2d::fast_fwdbwd_kernel<1, 1, false> + gi2d::fast_fwdbwd_kernel<1, 2, false>" if two else \
+        ("gi2d::fast_fwdbwd_kernel<1, 0, true>" if fit.tx * fit.ty <= 1536 else "gi2d::fast_fwdbwd_kernel<1, 0, false>")
+    traffic, traffic_src = pmc_traffic(kernel, n, h, w)
+    # the counters were collected at the intersection count of THAT run (the scene drifts while it trains, and a
+    # 20-step run sits at another M than a 200-step one): the wasted-traffic ratio is formed like for like
+    traffic_m = stored_num_intersects(n, h, w)
+    traffic_ratio = (traffic / (80 * traffic_m + 36 * h * w + 36 * n)) if (traffic and traffic_m) else None
+    return {
+        "roofline": {
+            "bound": "hbm", "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+            "traffic_measured_at_num_intersects": traffic_m, "traffic_over_algorithmic_at_that_count": traffic_ratio,
+            "algorithmic_bytes_per_launch": pair_bytes, "avg_kernel_us": avg_us,
+            "min_kernel_us": float(np.min(kernel_us)), "kernel_samples": len(kernel_us),
+            "first_pass_of_a_call": {"kernel": "gi2d::fast_fwdbwd_kernel<1, 0, false>", "samples": len(first_pass_us),
+                                     "avg_kernel_us": float(np.mean(first_pass_us)) if first_pass_us else None},
+            "note": "not HBM-bound: each staged gaussian is reused by up to 256 pixels, so the tile pass is bound by "
+                    "instruction issue and dependent latency (roofline_valu; DESIGN.md 3.4)",
+        },
+        "roofline_valu": valu_roofline(kernel, n, h, w, avg_us),
+        "rasterize_pair": {
+            "fwdbwd_kernel_us": avg_us, "algorithmic_bytes": pair_bytes, "achieved_GBps": achieved,
+            # every staged (tile, gaussian) entry against every pixel of its tile, forward + backward: the NOMINAL
+            # pair count of the reference's loops (forward.cu:650, backward.cu:1258), not evaluated work
+            "nominal_pairs_per_s": 2 * 256.0 * m / (avg_us * 1e-6),
+            "note": "HIP start/stop events of the tile-pass kernel inside timed calls of the same loop "
+                    "(ms_per_step_event_regions)"},
+    }
 
 
 DUMP_LIMIT_BYTES = 64 * 1000 * 1000

@@ -1,4 +1,5 @@
-"""GPU: bench.py prints ONE JSON line with the fields the driver and the judge read (small workload, short CPU leg)."""
+"""GPU: bench.py prints ONE JSON line with the fields the driver and the judge read (small workload, short CPU leg):
+the headline alone from a plain run, every other block under --full."""
 import json
 import os
 import subprocess
@@ -16,7 +17,7 @@ DUMP_SHAPES = {"xyz": ("N", 2), "cholesky": ("N", 3), "features_dc": ("N", 3), "
 
 
 def test_bench_line_has_the_contract_fields(tmp_path):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "24", "--warmup", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "24", "--warmup", "4", "--full",
            "--num-points", "3000", "--height", "96", "--width", "144", "--cpu-seconds", "1.5", "--images", "2",
            "--image-iterations", "200", "--images-per-gpu", "2", "--dump-outputs", str(tmp_path / "dump")]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
@@ -28,7 +29,7 @@ def test_bench_line_has_the_contract_fields(tmp_path):
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
     assert d["n_gpus"] == 1 and d["steps"] == 24 and d["warmup"] == 4 and d["higher_is_better"] is True
-    assert d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "f32"
+    assert d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "f32" and d["full"] is True
     assert d["data"].startswith("synthetic") and "kodak" in d["data"]
     assert "optimizer ON" in d["config"]["workload"]  # the timed loop trains: parameters move every step
     assert "workload" in d["config"] and "model" not in d["config"]
@@ -109,10 +110,56 @@ def test_dumped_outputs_repeat_from_run_to_run_and_follow_steps(tmp_path):
         assert np.abs(a[k] - c[k]).max() > 1e-3 * scale, k  # 4 + 10 x 12 iterations against 4 + 10 x 24
 
 
+# what only a --full run measures and reports
+FULL_ONLY = ("ms_per_step_event_regions", "event_stride", "roofline", "roofline_valu", "rasterize_pair", "static_scene_step",
+             "dropin_autograd_step", "batched", "images_per_s", "quantized_train_step", "concurrent_images", "cpu_baseline")
+
+
+def test_plain_run_reports_the_headline_alone_and_full_times_the_same_regions(tmp_path):
+    """Without --full the line carries the headline and its workload and none of the other blocks, even where their own
+    switches ask for them; with --full (here every leg but the tile pass's event timing switched off) the timed regions
+    start from the same scenes, so both runs dump the same arrays."""
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "24", "--warmup", "4",
+            "--num-points", "3000", "--height", "96", "--width", "144"]
+    legs_off = ["--images", "0", "--no-cpu-baseline", "--no-batched", "--no-static", "--no-dropin"]
+
+    def run(name, extra):
+        out = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True,
+                             timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0]), {k: np.load(tmp_path / name / (k + ".npy")) for k in DUMP_SHAPES}
+
+    d, plain = run("plain", ["--images", "2", "--image-iterations", "200", "--cpu-seconds", "1.5"])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "repeats", "ms_per_step", "ms_per_step_each_region",
+                "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert key in d, key
+    assert [key for key in FULL_ONLY if key in d] == [] and d["full"] is False
+    assert d["n_gpus"] == 1 and d["steps"] == 24 and d["warmup"] == 4 and d["higher_is_better"] is True
+    assert d["unit"] == "iters/s" and d["dtype"] == "f32" and d["data"] == "synthetic" and d["metric"].endswith("144x96")
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    assert d["repeats"] == 5 and len(d["ms_per_step_each_region"]) == 5
+    assert sorted(d["ms_per_step_each_region"])[2] == d["ms_per_step"]  # the median region
+    assert "optimizer ON" in d["config"]["workload"] and d["config"]["num_points"] == 3000
+    assert int(plain["num_tiles_hit"].sum()) == d["config"]["num_intersects_rank0"]
+    f, full = run("full", ["--full"] + legs_off)
+    assert f["full"] is True and f["roofline"]["kernel_samples"] == 55 and f["ms_per_step_event_regions"] > 0
+    assert [key for key in FULL_ONLY if key in f] == ["ms_per_step_event_regions", "event_stride", "roofline",
+                                                      "roofline_valu", "rasterize_pair"]
+    assert {k: v for k, v in f.items() if k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup")} == \
+        {k: v for k, v in d.items() if k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup")}
+    for k in DUMP_SHAPES:  # 4 + 10 x 24 iterations either way (the bound: a float sum taken in another order)
+        assert plain[k].shape == full[k].shape, k
+    for k in ("xyz", "cholesky", "features_dc", "out_img", "xys", "conics"):
+        assert np.abs(plain[k] - full[k]).max() <= 1e-4 * np.abs(full[k]).max(), k
+
+
 def test_gpus_flag_starts_the_ranks_itself():
     """`python bench.py --gpus 2` with no launcher around it: the parent starts two ranks (here both on the one GPU of
     the box, rendezvous over gloo) and relays rank 0's line, which must say n_gpus = 2 and carry the whole-job rate."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "16", "--warmup", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "16", "--warmup", "4", "--full",
            "--num-points", "3000", "--height", "96", "--width", "144", "--images", "2", "--image-iterations", "100",
            "--images-per-gpu", "1", "--no-batched"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}

@@ -53,6 +53,22 @@ def test_launch_ranks_sets_the_rendezvous_environment(tmp_path, monkeypatch):
     assert all(r[-4:] == ["--gpus", "3", "--steps", "5"] for r in rows)
 
 
+def test_full_is_off_by_default_and_the_optional_legs_ask_for_it(capsys):
+    """A plain run measures the headline alone: --full is off unless given, the per-leg switches stay accepted without
+    it, and the two legs that are off by default refuse to be asked for without it rather than be dropped in silence."""
+    import pytest
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"]).full is False
+    assert bench.parse(["--images", "0", "--no-cpu-baseline", "--no-batched", "--no-static", "--no-dropin"]).full is False
+    args = bench.parse(["--full", "--train-step", "--images-per-gpu-probe"])
+    assert args.full is True and args.train_step and args.images_per_gpu_probe
+    for flag in ("--train-step", "--images-per-gpu-probe"):
+        with pytest.raises(SystemExit) as e:
+            bench.parse([flag])
+        assert e.value.code == 2 and "--full" in capsys.readouterr().err
+
+
 def test_stored_counters_exist_for_the_kernels_bench_names():
     """bench.py copies `roofline.traffic` (and the VALU counters) from profiles/traffic.json by KERNEL NAME; a kernel that
     gains a template argument silently turns the figure into null.  The names the default run, BASELINE config 4 and the

@@ -4,7 +4,7 @@
 #   gpurun -- 'bash tools/ab_multi.sh product base product base'    ("product" = the library in the tree, any other name
 #   = build/variants/<name>/libgi2d_hip.so, built before the snapshot was sent)
 cd ${GRAFT_REPO_ROOT:-.}
-A="--no-cpu-baseline --images 0 --no-batched --no-static --no-dropin"
+A="--full --no-cpu-baseline --images 0 --no-batched --no-static --no-dropin"
 run() {
   python bench.py $A 2>/dev/null | python -c "import json,sys; b=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('  headline us/step', round(1e3*b['ms_per_step'],2), 'tile pass avg', round(b['roofline']['avg_kernel_us'],2), 'min', round(b['roofline']['min_kernel_us'],2))"
   python tools/batched_bench_scene.py 24 2>/dev/null | python -c "import json,sys; r=json.loads([l for l in sys.stdin if l.startswith('{')][-1])['per_k'][0]; print('  K=24 tile pass per image', round(r['tile_pass_us_per_image'],2), 'iteration', round(r['us_per_image_iteration'],2), r['tile_pass_form'][:12])"

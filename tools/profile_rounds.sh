@@ -18,7 +18,7 @@ ROUND=${ROUND:-6}
 OUT=$REPO/gpurun_out/rp$ROUND
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-HEAD="--no-cpu-baseline --images 0 --no-batched --no-static --no-dropin"
+HEAD="--full --no-cpu-baseline --images 0 --no-batched --no-static --no-dropin"
 C4="$HEAD --height 1356 --width 2040"
 stats() { # name, program...
   local name=$1; shift
@@ -68,9 +68,9 @@ python3 $REPO/tools/profile_autograd_loop.py 50000 500 > $OUT/dropin_profile.txt
 python3 $REPO/tools/kodak_fit.py 24 50000 3 > $OUT/kodak50k.out 2>&1 || true
 (cd $REPO && python3 tools/lane_model.py > $OUT/lane_model.json 2> /dev/null) || true
 echo "dropin + kodak done"
-cd $REPO && python3 bench.py > $OUT/bench_plain.json 2> $OUT/bench_plain.err
+cd $REPO && python3 bench.py --full > $OUT/bench_plain.json 2> $OUT/bench_plain.err
 python3 bench.py $C4 > $OUT/c4_plain.json 2> /dev/null          # (no profiler: the c4 figures DESIGN.md quotes)
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --images 0 --no-batched --no-static --no-dropin > $OUT/bench_driverlike.json 2> /dev/null
+python3 bench.py $HEAD --steps 20 --warmup 5 > $OUT/bench_driverlike.json 2> /dev/null
 python3 tools/kodak_fit.py 3 50000 3 > $OUT/kodak_shards.out 2>&1 || true
 python3 tools/kodak_fit.py 6 50000 3 >> $OUT/kodak_shards.out 2>&1 || true
 python3 tools/kodak_fit.py 12 50000 3 >> $OUT/kodak_shards.out 2>&1 || true
