@@ -13,6 +13,7 @@
 //
 // The glue the reference runs as ~25 small PyTorch kernels plus two host syncs per iteration
 // (models/gaussianimage_cholesky.py:302-317) is folded into the kernels either side of the rasterizer.
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -1348,7 +1349,15 @@ using namespace gi2d;
             GI2D_DISPATCH_RU2(kCovariance, more, adan); \
     } while (0)
 
-extern "C" {
+// model of the quantised kernels (1 covariance, 2 rotation-scale) -> GI2D_LAUNCH_QUANT(M)
+#define GI2D_DISPATCH_QUANT(kind)  \
+    do {                           \
+        if ((kind) == 2) {         \
+            GI2D_LAUNCH_QUANT(2);  \
+        } else {                   \
+            GI2D_LAUNCH_QUANT(1);  \
+        }                          \
+    } while (0)
 
 static TrainParams params_of(const gi2d_train_state *s) {
     TrainParams P;
@@ -1374,13 +1383,24 @@ static TrainParams params_of(const gi2d_train_state *s) {
     return P;
 }
 
-static int train_check(const gi2d_train_state *s, int &tx, int &ty) {
+// Who looks at a state: selects train_check's tests and names the entry in their messages.
+enum TrainEntry { kStateOnly, kSteps, kStepsBatched };
+
+static int train_refuse(TrainEntry entry, int rc, const char *what) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "train steps%s: %s", entry == kStepsBatched ? " (batched)" : "", what);
+    set_error(msg);
+    return rc;
+}
+
+// Every test on ONE state (what compares the images of a batch with each other is gi2d_train_steps_batched's own; the
+// quantisers' fields: quant_of).  kStateOnly: the state and its workspace, all a render or an empty call looks at.
+static int train_check(const gi2d_train_state *s, TrainEntry entry) {
     if (!s || s->kind < 0 || s->kind > 2 || s->num_points < 0 || s->img_height <= 0 || s->img_width <= 0) {
         set_error("train: bad state");
         return GI2D_ERR_INVALID_ARGUMENT;
     }
-    tx = (s->img_width + GI2D_TILE - 1) / GI2D_TILE;
-    ty = (s->img_height + GI2D_TILE - 1) / GI2D_TILE;
+    const int tx = (s->img_width + GI2D_TILE - 1) / GI2D_TILE, ty = (s->img_height + GI2D_TILE - 1) / GI2D_TILE;
     if (!s->xyz || !s->chol || !s->feat || !s->opacity || !s->bound || !s->m_xyz || !s->v_xyz || !s->m_chol ||
         !s->v_chol || !s->m_feat || !s->v_feat || !s->gt || !s->xys || !s->conics || !s->radii ||
         !s->num_tiles_hit || !s->out_img || !s->tile_sse || !s->status) {
@@ -1391,6 +1411,18 @@ static int train_check(const gi2d_train_state *s, int &tx, int &ty) {
         set_error("train: workspace too small");
         return GI2D_ERR_WORKSPACE_TOO_SMALL;
     }
+    if (entry == kStateOnly) return GI2D_OK;
+    // (an optimizer out of range: an invalid argument to the single-image entry, unsupported to the batched one -- as found)
+    if (s->optimizer < 0 || s->optimizer > 1)
+        return train_refuse(entry, entry == kStepsBatched ? GI2D_ERR_UNSUPPORTED : GI2D_ERR_INVALID_ARGUMENT,
+                            "unknown optimizer");
+    if (s->optimizer == 1 && (!s->d_xyz || !s->d_chol || !s->d_feat || !s->pg_xyz || !s->pg_chol || !s->pg_feat))
+        return train_refuse(entry, GI2D_ERR_INVALID_ARGUMENT, "Adan without its extra state (d_*, pg_*)");
+    if (s->best_sse &&
+        (!s->best_xyz || !s->best_chol || !s->best_feat || !s->best_info || (s->bound_stride && !s->best_bound)))
+        return train_refuse(entry, GI2D_ERR_INVALID_ARGUMENT, "best_sse given without the snapshot buffers");
+    if (s->quant && s->quant->first_step < 1)
+        return train_refuse(entry, GI2D_ERR_INVALID_ARGUMENT, "quantiser optimizer step must be >= 1");
     return GI2D_OK;
 }
 
@@ -1436,21 +1468,6 @@ static UpdateArgs update_args_of(const gi2d_train_state *s, const FastWs &w, int
     return u;
 }
 
-static void train_launch_project_fill(const gi2d_train_state *s, const FastWs &w, const TrainParams &, int tx,
-                                      int ty, hipStream_t st) {
-    const int n = s->num_points;
-    const int bs = per_gaussian_block(n);
-    const dim3 gg((n + bs - 1) / bs), bb(bs);
-    const UpdateArgs u = update_args_of(s, w, tx, ty);
-    if (s->kind == 2)
-        hipLaunchKernelGGL(train_project_fill_kernel<kScaleRot>, gg, bb, 0, st, u);
-    else if (s->kind == 0)
-        hipLaunchKernelGGL(train_project_fill_kernel<kCholesky>, gg, bb, 0, st, u);
-    else
-        hipLaunchKernelGGL(train_project_fill_kernel<kCovariance>, gg, bb, 0, st, u);
-}
-
-
 static AdamStep make_adam_step(double lr, double beta1, double beta2, double beta3, float eps, int step, bool adan_opt) {
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     const double bc3 = 1.0 - pow(beta3, (double)step);
@@ -1468,6 +1485,25 @@ static AdamStep make_adam_step(double lr, double beta1, double beta2, double bet
     a.first = step == 1;
     return a;
 }
+
+// The optimizer constants of iteration `it` of a call that starts at Adam step `first_step`: a[] of the gaussians'
+// groups (xyz, cholesky, colour) and, for a quantised state, aq[] of its quantisers (xy, covariance, colour), which
+// count their own steps.  lr[3]: the groups' learning rates, constant over the call.
+struct IterSteps {
+    AdamStep a[3], aq[3];
+};
+static IterSteps iter_steps(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps,
+                            int first_step, int it) {
+    IterSteps r = {};
+    const gi2d_train_quant *q = s->quant;  // (quantisation-aware iterations use Adam: quant_of)
+    for (int k = 0; k < 3; ++k) {
+        r.a[k] = make_adam_step(lr[k], beta1, beta2, q ? 0.0 : s->beta3, eps, first_step + it, !q && s->optimizer == 1);
+        if (q) r.aq[k] = make_adam_step(q->lr[k], q->beta1, q->beta2, 0.0, q->eps[k], q->first_step + it, false);
+    }
+    return r;
+}
+// what the range-only closing launch of a call's start gets in their place (it updates nothing)
+static AdamStep idle_adam_step() { return make_adam_step(0.0, 0.9, 0.999, 0.0, 1.f, 1, false); }
 
 static int quant_of(const gi2d_train_state *s, QuantTrain &Q) {
     const gi2d_train_quant *q = s->quant;
@@ -1502,171 +1538,136 @@ static int quant_of(const gi2d_train_state *s, QuantTrain &Q) {
     return GI2D_OK;
 }
 
-// launch shape of the per-gaussian kernels of a quantisation-aware iteration; rows = partial rows (waves) they leave
-struct QuantLaunch {
-    int bs, blocks, rows;
+// What the launches on one image need, worked out once per call from a state that passed train_check.
+struct ImagePlan {
+    int tx, ty;
+    FastWs w;
+    float grad_scale;  // of the L2 loss: 2 / (3 H W)
+    UpdateArgs u;
+    QuantTrain q;    // zeros unless the state is quantisation-aware
+    int bs, blocks;  // launch shape of the per-gaussian kernels on this image alone (a batch has one for all its images)
 };
-static QuantLaunch quant_launch_of(int n) {
-    QuantLaunch l;
-    l.bs = per_gaussian_block(n);
-    l.blocks = (n + l.bs - 1) / l.bs;
-    l.rows = l.blocks * (l.bs / 64);
-    return l;
+static int image_plan(const gi2d_train_state *s, ImagePlan &p) {
+    p.tx = (s->img_width + GI2D_TILE - 1) / GI2D_TILE, p.ty = (s->img_height + GI2D_TILE - 1) / GI2D_TILE;
+    p.w = carve_fast(s->workspace, s->num_points, p.tx * p.ty);
+    p.grad_scale = 2.f / (3.f * (float)s->img_height * (float)s->img_width);
+    p.u = update_args_of(s, p.w, p.tx, p.ty);
+    p.bs = per_gaussian_block(s->num_points);
+    p.blocks = (s->num_points + p.bs - 1) / p.bs;
+    std::memset(&p.q, 0, sizeof(QuantTrain));
+    return s->quant ? quant_of(s, p.q) : GI2D_OK;
 }
-// log range of the current variances (covariance model, start of a call)
-static void train_launch_quant_range(const UpdateArgs &u, const QuantTrain &Q, hipStream_t st) {
-    const QuantLaunch l = quant_launch_of(u.n);
-    const AdamStep z = make_adam_step(0.0, 0.9, 0.999, 0.0, 1.f, 1, false);
-    hipLaunchKernelGGL(train_quant_range_kernel, dim3(l.blocks), dim3(l.bs), 0, st, u, Q);
-    hipLaunchKernelGGL(train_quant_finish_kernel<0>, dim3(1), dim3(256), 0, st, l.rows, u, Q, z, z, z, z, 0);
+
+// activations + projection + fill
+static void train_launch_project_fill(int kind, const ImagePlan &p, hipStream_t st) {
+    const dim3 gg(p.blocks), bb(p.bs);
+    if (kind == 2)
+        hipLaunchKernelGGL(train_project_fill_kernel<kScaleRot>, gg, bb, 0, st, p.u);
+    else if (kind == 0)
+        hipLaunchKernelGGL(train_project_fill_kernel<kCholesky>, gg, bb, 0, st, p.u);
+    else
+        hipLaunchKernelGGL(train_project_fill_kernel<kCovariance>, gg, bb, 0, st, p.u);
+}
+// log range of the current variances (covariance model, start of a call); the closing step (one workgroup) reads the
+// partial rows -- one per wave -- the per-gaussian launch left
+static void train_launch_quant_range(const ImagePlan &p, hipStream_t st) {
+    const AdamStep z = idle_adam_step();
+    hipLaunchKernelGGL(train_quant_range_kernel, dim3(p.blocks), dim3(p.bs), 0, st, p.u, p.q);
+    hipLaunchKernelGGL(train_quant_finish_kernel<0>, dim3(1), dim3(256), 0, st, p.blocks * (p.bs / 64), p.u, p.q, z, z, z,
+                       z, 0);
 }
 // activations / quantisers + projection + fill
-static void train_launch_project_fill_quant(int model, const UpdateArgs &u, const QuantTrain &Q, hipStream_t st) {
-    const QuantLaunch l = quant_launch_of(u.n);
-    if (model == 2)
-        hipLaunchKernelGGL(train_project_fill_quant_kernel<2>, dim3(l.blocks), dim3(l.bs), 0, st, u, Q);
-    else
-        hipLaunchKernelGGL(train_project_fill_quant_kernel<1>, dim3(l.blocks), dim3(l.bs), 0, st, u, Q);
+static void train_launch_project_fill_quant(int kind, const ImagePlan &p, hipStream_t st) {
+#define GI2D_LAUNCH_QUANT(M) \
+    hipLaunchKernelGGL(train_project_fill_quant_kernel<M>, dim3(p.blocks), dim3(p.bs), 0, st, p.u, p.q)
+    GI2D_DISPATCH_QUANT(kind);
+#undef GI2D_LAUNCH_QUANT
 }
+
+extern "C" {
 
 // Forward only (render): activations + projection + fill + rasterize into state->out_img.
 int gi2d_train_render(const gi2d_train_state *s, gi2d_stream_t st_) {
-    int tx, ty;
-    int rc = train_check(s, tx, ty);
+    int rc = train_check(s, kStateOnly);
+    if (rc != GI2D_OK || s->num_points == 0) return rc;
+    ImagePlan p;
+    rc = image_plan(s, p);
     if (rc != GI2D_OK) return rc;
     hipStream_t st = (hipStream_t)st_;
-    const int n = s->num_points;
-    if (n == 0) return GI2D_OK;
-    FastWs w = carve_fast(s->workspace, n, tx * ty);
-    const TrainParams P = params_of(s);
-    if (s->quant) {  // forward_quantize (models/gaussianimage_covariance.py:384-410)
-        QuantTrain Q;
-        rc = quant_of(s, Q);
-        if (rc != GI2D_OK) return rc;
-        const UpdateArgs uq = update_args_of(s, w, tx, ty);
-        if (s->kind != 2) train_launch_quant_range(uq, Q, st);  // (the RS model's ranges are learned values)
-        train_launch_project_fill_quant(s->kind, uq, Q, st);  // GaussianImage_RS.forward_quantize: models/gaussianimage_rs.py:443-471
-        return gi2d_fast_rasterize_forward(n, tx, ty, (unsigned)s->img_width, (unsigned)s->img_height, nullptr,
-                                           s->workspace, s->workspace_bytes, s->status, nullptr, nullptr, s->out_img,
-                                           st_);
+    if (s->quant) {  // forward_quantize (models/gaussianimage_covariance.py:384-410, models/gaussianimage_rs.py:443-471)
+        if (s->kind != 2) train_launch_quant_range(p, st);  // (the RS model's ranges are learned values)
+        train_launch_project_fill_quant(s->kind, p, st);
+    } else {
+        train_launch_project_fill(s->kind, p, st);
     }
-    train_launch_project_fill(s, w, P, tx, ty, st);
-    return gi2d_fast_rasterize_forward(n, tx, ty, (unsigned)s->img_width, (unsigned)s->img_height, nullptr, s->workspace,
-                                       s->workspace_bytes, s->status, nullptr, nullptr, s->out_img, st_);
+    return gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, (unsigned)s->img_width, (unsigned)s->img_height,
+                                       nullptr, s->workspace, s->workspace_bytes, s->status, nullptr, nullptr, s->out_img,
+                                       st_);
 }
 
-// `count` full iterations: render, L2 loss gradient + backward, Adam update.  lr[3] / first_step are host values:
+// `count` full iterations: render, L2 loss gradient + backward, optimizer update.  lr[3] / first_step are host values:
 // learning rates of the xyz / cholesky / colour groups (constant over the call) and the 1-based Adam step count of
-// the first iteration.  Launches: project+fill once, then per iteration the tile pass and the update kernel, which
-// also projects and bins the updated gaussians for the following iteration (all but the last) -- 2*count + 1.
+// the first iteration.  Launches of a plain fit: project+fill once, then per iteration the tile pass and the update
+// kernel, which also projects and bins the updated gaussians for the following iteration (all but the last) --
+// 2*count + 1.  Of a quantisation-aware one (train_iter_quantize): the log range once (covariance model), then per
+// iteration project+fill behind the quantisers, tile pass, update kernel and its closing step.
+// gi2d_train_steps_batched issues the same sequence for K images per launch.
 int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps,
                      int first_step, int count, gi2d_stream_t st_) {
-    int tx, ty;
-    int rc = train_check(s, tx, ty);
+    const bool idle = count <= 0 || (s && s->num_points == 0);  // nothing to launch: only the state itself is looked at
+    int rc = train_check(s, idle ? kStateOnly : kSteps);
+    if (rc != GI2D_OK || idle) return rc;
+    if (!lr || first_step < 1) return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT, "bad lr/step");
+    ImagePlan p;
+    rc = image_plan(s, p);
     if (rc != GI2D_OK) return rc;
     hipStream_t st = (hipStream_t)st_;
-    const int n = s->num_points;
-    if (n == 0 || count <= 0) return GI2D_OK;
-    if (!lr || first_step < 1) {
-        set_error("train steps: bad lr/step");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    FastWs w = carve_fast(s->workspace, n, tx * ty);
-    const TrainParams P = params_of(s);
-    const float grad_scale = 2.f / (3.f * (float)s->img_height * (float)s->img_width);
-    BestSnap best;
-    best.xyz = s->best_xyz;
-    best.chol = s->best_chol;
-    best.feat = s->best_feat;
-    best.bound = s->bound_stride ? s->best_bound : nullptr;
-    best.sse = s->best_sse;
-    best.info = s->best_info;
-    best.tile_sse = s->tile_sse;
-    best.num_tiles = tx * ty;
-    if (best.sse && (!best.xyz || !best.chol || !best.feat || !best.info || (s->bound_stride && !s->best_bound))) {
-        set_error("train steps: best_sse given without the snapshot buffers");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    const bool adan_opt = s->optimizer == 1;
-    if (s->optimizer < 0 || s->optimizer > 1 ||
-        (adan_opt && (!s->d_xyz || !s->d_chol || !s->d_feat || !s->pg_xyz || !s->pg_chol || !s->pg_feat))) {
-        set_error("train steps: unknown optimizer, or Adan without its extra state (d_*, pg_*)");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
+    const bool quantised = s->quant != nullptr;
     // a large image's tile passes run as two launches while the previous call on this workspace saw at most one row in
     // sixteen above the small form's capacity (gi2d_fast.hip: pass_form_begin)
-    const long long tiles = (long long)tx * ty;
+    const long long tiles = (long long)p.tx * p.ty;
     const int form = single_pass_begin(s->workspace, tiles, st);
-    if (s->quant) {
-        QuantTrain Q;
-        rc = quant_of(s, Q);
-        if (rc != GI2D_OK) return rc;
-        const gi2d_train_quant *q = s->quant;
-        if (q->first_step < 1) {
-            set_error("train steps: quantiser optimizer step must be >= 1");
-            return GI2D_ERR_INVALID_ARGUMENT;
-        }
-        const UpdateArgs uq = update_args_of(s, w, tx, ty);
-        const QuantLaunch l = quant_launch_of(n);
-        const int model = s->kind == 2 ? 2 : 1;
-        if (model == 1) train_launch_quant_range(uq, Q, st);
-        for (int it = 0; it < count; ++it) {
-            const int step = first_step + it, qstep = q->first_step + it;
-            train_launch_project_fill_quant(model, uq, Q, st);
-            rc = fast_forward_backward_form(n, tx, ty, (unsigned)s->img_width, (unsigned)s->img_height, nullptr, nullptr,
-                                            s->gt, grad_scale, s->tile_sse, s->workspace, s->workspace_bytes, s->status,
-                                            s->out_img, st_, form);
-            if (rc != GI2D_OK) return rc;
-            AdamStep a[3], aq[3];
-            for (int k = 0; k < 3; ++k) {
-                a[k] = make_adam_step(lr[k], beta1, beta2, 0.0, eps, step, false);
-                aq[k] = make_adam_step(q->lr[k], q->beta1, q->beta2, 0.0, q->eps[k], qstep, false);
-            }
-            if (model == 2) {
-                hipLaunchKernelGGL(train_reduce_update_quant_kernel<2>, dim3(l.blocks), dim3(l.bs), 0, st, uq, Q, a[0],
-                                   a[1], a[2], step);
-                hipLaunchKernelGGL(train_quant_finish_kernel<2>, dim3(1), dim3(256), 0, st, l.rows, uq, Q, a[1], aq[0],
-                                   aq[1], aq[2], step);
-            } else {
-                hipLaunchKernelGGL(train_reduce_update_quant_kernel<1>, dim3(l.blocks), dim3(l.bs), 0, st, uq, Q, a[0],
-                                   a[1], a[2], step);
-                hipLaunchKernelGGL(train_quant_finish_kernel<1>, dim3(1), dim3(256), 0, st, l.rows, uq, Q, a[1], aq[0],
-                                   aq[1], aq[2], step);
-            }
-        }
-        single_pass_end(s->workspace, w, tiles, st);
-        return check_launch("train steps (quantised)");
-    }
-    const UpdateArgs u = update_args_of(s, w, tx, ty);
-    const int bs = per_gaussian_block(n);
-    const dim3 gg((n + bs - 1) / bs + 1), bb(bs);  // + 1: the workgroup that orders the tiles
-    train_launch_project_fill(s, w, P, tx, ty, st);
+    // The inboxes: one image of at most GI2D_INBOX_MAX_TILES tiles, i.e. a tile pass of the general form throughout,
+    // whose caller brought the inboxes' buffer (gi2d_train_state::inbox), in a plain fit.  The update kernel delivers
+    // through them when another iteration follows, and the tile pass of that iteration -- never the first of a call,
+    // which follows the projection kernel -- is the one built to take entrants in.
+    float4 *const inbox = quantised ? nullptr : p.u.next.inbox;
+    const dim3 gg(p.blocks + (quantised ? 0 : 1)), bb(p.bs);  // + 1: the workgroup that orders the tiles (plain fits)
+    if (!quantised)
+        train_launch_project_fill(s->kind, p, st);
+    else if (s->kind != 2)
+        train_launch_quant_range(p, st);
     for (int it = 0; it < count; ++it) {
         const int step = first_step + it;
-        // (the inboxes: one image of at most GI2D_INBOX_MAX_TILES tiles, i.e. a tile pass of the general form throughout;
-        // the update kernel delivers through them when another iteration follows, and the tile pass of that iteration --
-        // never the first of a call, which follows the projection kernel -- is the one built to take entrants in)
-        // ... and whose caller brought the inboxes' buffer: gi2d_train_state::inbox)
-        const bool small_image = u.next.inbox != nullptr;
-        rc = fast_forward_backward_form(n, tx, ty, (unsigned)s->img_width, (unsigned)s->img_height, nullptr, nullptr,
-                                        s->gt, grad_scale, s->tile_sse, s->workspace, s->workspace_bytes, s->status,
-                                        s->out_img, st_, form, it > 0 ? u.next.inbox : nullptr);
+        if (quantised) train_launch_project_fill_quant(s->kind, p, st);
+        rc = fast_forward_backward_form(s->num_points, p.tx, p.ty, (unsigned)s->img_width, (unsigned)s->img_height, nullptr,
+                                        nullptr, s->gt, p.grad_scale, s->tile_sse, s->workspace, s->workspace_bytes,
+                                        s->status, s->out_img, st_, form, it > 0 ? inbox : nullptr);
         if (rc != GI2D_OK) return rc;
-        AdamStep a[3];
-        for (int q = 0; q < 3; ++q) a[q] = make_adam_step(lr[q], beta1, beta2, s->beta3, eps, step, adan_opt);
+        const IterSteps t = iter_steps(s, lr, beta1, beta2, eps, first_step, it);
+        const AdamStep *a = t.a, *aq = t.aq;
+        if (quantised) {
+#define GI2D_LAUNCH_QUANT(M)                                                                                          \
+    hipLaunchKernelGGL(train_reduce_update_quant_kernel<M>, gg, bb, 0, st, p.u, p.q, a[0], a[1], a[2], step);         \
+    hipLaunchKernelGGL(train_quant_finish_kernel<M>, dim3(1), dim3(256), 0, st, p.blocks * (p.bs / 64), p.u, p.q, a[1], \
+                       aq[0], aq[1], aq[2], step)
+            GI2D_DISPATCH_QUANT(s->kind);
+#undef GI2D_LAUNCH_QUANT
+            continue;
+        }
         const bool more = it + 1 < count;
-        const bool inbox = more && small_image;
-#define GI2D_LAUNCH_RU(K, F, A)                                                                                      \
-    do {                                                                                                             \
-        if (F && inbox)                                                                                              \
-            hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A, F>), gg, bb, 0, st, u, a[0], a[1], a[2], step);  \
-        else                                                                                                         \
-            hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A>), gg, bb, 0, st, u, a[0], a[1], a[2], step);     \
+        const bool deliver = more && inbox != nullptr;
+#define GI2D_LAUNCH_RU(K, F, A)                                                                                       \
+    do {                                                                                                              \
+        if (F && deliver)                                                                                             \
+            hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A, F>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step); \
+        else                                                                                                          \
+            hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step);    \
     } while (0)
-        GI2D_DISPATCH_RU(s->kind, more, adan_opt);
+        GI2D_DISPATCH_RU(s->kind, more, s->optimizer == 1);
 #undef GI2D_LAUNCH_RU
     }
-    single_pass_end(s->workspace, w, tiles, st);
+    single_pass_end(s->workspace, p.w, tiles, st);
     return check_launch("train steps");
 }
 
@@ -1683,157 +1684,110 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
                              const double *lr, double beta1, double beta2, float eps, int first_step, int count,
                              gi2d_stream_t st_) {
     hipStream_t st = (hipStream_t)st_;
-    if (num_images < 1 || num_images > GI2D_BATCH_MAX || !states) {
-        set_error("train steps (batched): 1 .. 64 images per launch");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    if (!batch || batch_bytes < gi2d_batch_bytes(num_images) || ((uintptr_t)batch & 15)) {
-        set_error("train steps (batched): batch table too small (gi2d_batch_bytes) or not 16-byte aligned");
-        return GI2D_ERR_WORKSPACE_TOO_SMALL;
-    }
+    if (num_images < 1 || num_images > GI2D_BATCH_MAX || !states)
+        return train_refuse(kStepsBatched, GI2D_ERR_INVALID_ARGUMENT, "1 .. 64 images per launch");
+    if (!batch || batch_bytes < gi2d_batch_bytes(num_images) || ((uintptr_t)batch & 15))
+        return train_refuse(kStepsBatched, GI2D_ERR_WORKSPACE_TOO_SMALL,
+                            "batch table too small (gi2d_batch_bytes) or not 16-byte aligned");
     if (count <= 0) return GI2D_OK;
-    if (!lr || first_step < 1) {
-        set_error("train steps (batched): bad lr/step");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
+    if (!lr || first_step < 1) return train_refuse(kStepsBatched, GI2D_ERR_INVALID_ARGUMENT, "bad lr/step");
     const gi2d_train_state *s0 = states[0];
     BatchHead head;
     std::memset(&head, 0, sizeof(head));
+    // the table: tile-pass and per-gaussian workgroup ranges, one argument block per image
+    std::vector<BatchImage> host_imgs((size_t)num_images);
     long long total_n = 0;
     bool uniform = true;
-    int tiles0 = 0;
+    int tile_blocks = 0, tiles0 = 0;
     for (int k = 0; k < num_images; ++k) {
         const gi2d_train_state *s = states[k];
-        int tx, ty;
-        int rc = train_check(s, tx, ty);
+        int rc = train_check(s, kStepsBatched);
         if (rc != GI2D_OK) return rc;
-        if (s->kind != s0->kind || s->optimizer != s0->optimizer || s->beta3 != s0->beta3 || s->optimizer < 0 ||
-            s->optimizer > 1 || (s->quant != nullptr) != (s0->quant != nullptr)) {
-            set_error("train steps (batched): the images of a batch share model kind and optimizer, and are all "
-                      "quantisation-aware or none");
-            return GI2D_ERR_UNSUPPORTED;
-        }
+        if (s->kind != s0->kind || s->optimizer != s0->optimizer || s->beta3 != s0->beta3 ||
+            (s->quant != nullptr) != (s0->quant != nullptr))
+            return train_refuse(kStepsBatched, GI2D_ERR_UNSUPPORTED,
+                                "the images of a batch share model kind and optimizer, and are all "
+                                "quantisation-aware or none");
         if (s->quant) {
             const gi2d_train_quant *q = s->quant, *q0 = s0->quant;
             bool same = q->xy_bits == q0->xy_bits && q->cov_bits == q0->cov_bits && q->color_bits == q0->color_bits &&
                         q->rot_bits == q0->rot_bits && q->beta1 == q0->beta1 && q->beta2 == q0->beta2 &&
                         q->first_step == q0->first_step;
             for (int c = 0; c < 3; ++c) same = same && q->lr[c] == q0->lr[c] && q->eps[c] == q0->eps[c];
-            if (!same) {
-                set_error("train steps (batched): the quantisers of a batch share bit depths, learning rates, eps, betas "
-                          "and step count");
-                return GI2D_ERR_UNSUPPORTED;
-            }
-            if (q->first_step < 1) {
-                set_error("train steps (batched): quantiser optimizer step must be >= 1");
-                return GI2D_ERR_INVALID_ARGUMENT;
-            }
-            if (s->optimizer != 0) {
-                set_error("train steps (batched): quantisation-aware iterations use Adam");
-                return GI2D_ERR_UNSUPPORTED;
-            }
+            if (!same)
+                return train_refuse(kStepsBatched, GI2D_ERR_UNSUPPORTED,
+                                    "the quantisers of a batch share bit depths, learning rates, eps, betas and step count");
         }
-        if (s->optimizer == 1 && (!s->d_xyz || !s->d_chol || !s->d_feat || !s->pg_xyz || !s->pg_chol || !s->pg_feat)) {
-            set_error("train steps (batched): Adan without its extra state (d_*, pg_*)");
-            return GI2D_ERR_INVALID_ARGUMENT;
-        }
-        if (s->best_sse && (!s->best_xyz || !s->best_chol || !s->best_feat || !s->best_info ||
-                            (s->bound_stride && !s->best_bound))) {
-            set_error("train steps (batched): best_sse given without the snapshot buffers");
-            return GI2D_ERR_INVALID_ARGUMENT;
-        }
-        total_n += s->num_points;
-        if (k == 0) tiles0 = tx * ty;
-        uniform = uniform && tx * ty == tiles0;
-    }
-    const bool adan_opt = s0->optimizer == 1, quantised = s0->quant != nullptr;
-    const int bs = per_gaussian_block((int)(total_n > 0x7fffffff ? 0x7fffffff : total_n));
-    BatchTable b = carve_batch(batch, num_images);
-    // the table: tile-pass and per-gaussian workgroup ranges, one argument block per image
-    int tile_blocks = 0, pg_blocks = 0;
-    std::vector<BatchImage> host_imgs((size_t)num_images);
-    for (int k = 0; k < num_images; ++k) {
-        const gi2d_train_state *s = states[k];
-        const int tx = (s->img_width + GI2D_TILE - 1) / GI2D_TILE, ty = (s->img_height + GI2D_TILE - 1) / GI2D_TILE;
-        const int n = s->num_points;
-        FastWs w = carve_fast(s->workspace, n, tx * ty);
-        const float grad_scale = 2.f / (3.f * (float)s->img_height * (float)s->img_width);
-        host_imgs[k].t = tile_pass_args(w, n, tx, ty, s->img_width, s->img_height, s->status, s->out_img, s->gt,
-                                        grad_scale, s->tile_sse);
-        host_imgs[k].u = update_args_of(s, w, tx, ty);
-        std::memset(&host_imgs[k].q, 0, sizeof(QuantTrain));
-        if (quantised) {
-            int rc = quant_of(s, host_imgs[k].q);
-            if (rc != GI2D_OK) return rc;
-        }
+        ImagePlan p;
+        rc = image_plan(s, p);
+        if (rc != GI2D_OK) return rc;
+        host_imgs[k].t = tile_pass_args(p.w, s->num_points, p.tx, p.ty, s->img_width, s->img_height, s->status,
+                                        s->out_img, s->gt, p.grad_scale, s->tile_sse);
+        host_imgs[k].u = p.u;
+        host_imgs[k].q = p.q;
         head.tile_start[k] = tile_blocks;
-        head.pg_start[k] = pg_blocks;
-        tile_blocks += tx * ty;
-        // plain fitting: + 1, the workgroup that orders the tiles (the quantised update kernels have none)
-        pg_blocks += (n + bs - 1) / bs + (quantised ? 0 : 1);
+        tile_blocks += p.tx * p.ty;
+        if (k == 0) tiles0 = p.tx * p.ty;
+        uniform = uniform && p.tx * p.ty == tiles0;
+        total_n += s->num_points;
     }
     head.tile_start[num_images] = tile_blocks;
+    const int bs = per_gaussian_block((int)(total_n > 0x7fffffff ? 0x7fffffff : total_n));
+    int pg_blocks = 0;
+    for (int k = 0; k < num_images; ++k) {
+        head.pg_start[k] = pg_blocks;
+        // plain fitting: + 1, the workgroup that orders the tiles (the quantised update kernels have none)
+        pg_blocks += (states[k]->num_points + bs - 1) / bs + (s0->quant ? 0 : 1);
+    }
     head.pg_start[num_images] = pg_blocks;
+    const BatchTable b = carve_batch(batch, num_images);
     write_batch_table(b, host_imgs.data(), num_images, head, st);
-    const int two_phase = batch_pass_begin(batch, tile_blocks, st);
+    // the same sequence as gi2d_train_steps; the kernels find their image's argument blocks in the table
+    const int form = batch_pass_begin(batch, tile_blocks, st);
+    const bool quantised = s0->quant != nullptr;
     const BatchImage *imgs = b.img;
     const int *pg_start = b.head->pg_start;
-    const dim3 gg((unsigned)pg_blocks), bb(bs);
-    if (quantised) {
-        // train_iter_quantize for every image of the batch: four launches per iteration, whatever the number of images
-        const gi2d_train_quant *q = s0->quant;
-        const int model = s0->kind == 2 ? 2 : 1, wpb = bs / 64;
-        const dim3 gi((unsigned)num_images), b256(256);
-        if (model == 1) {
-            const AdamStep z = make_adam_step(0.0, 0.9, 0.999, 0.0, 1.f, 1, false);
-            hipLaunchKernelGGL(train_quant_range_batched_kernel, gg, bb, 0, st, imgs, pg_start, num_images);
-            hipLaunchKernelGGL(train_quant_finish_batched_kernel<0>, gi, b256, 0, st, imgs, pg_start, wpb, z, z, z, z, 0);
-        }
-        for (int it = 0; it < count; ++it) {
-            const int step = first_step + it, qstep = q->first_step + it;
-            if (model == 2)
-                hipLaunchKernelGGL(train_project_fill_quant_batched_kernel<2>, gg, bb, 0, st, imgs, pg_start, num_images);
-            else
-                hipLaunchKernelGGL(train_project_fill_quant_batched_kernel<1>, gg, bb, 0, st, imgs, pg_start, num_images);
-            int rc = launch_tile_pass_batched(1, b, num_images, tile_blocks, uniform ? tiles0 : 0, two_phase, st);
-            if (rc != GI2D_OK) return rc;
-            AdamStep a[3], aq[3];
-            for (int k = 0; k < 3; ++k) {
-                a[k] = make_adam_step(lr[k], beta1, beta2, 0.0, eps, step, false);
-                aq[k] = make_adam_step(q->lr[k], q->beta1, q->beta2, 0.0, q->eps[k], qstep, false);
-            }
-            if (model == 2) {
-                hipLaunchKernelGGL(train_reduce_update_quant_batched_kernel<2>, gg, bb, 0, st, imgs, pg_start, num_images,
-                                   a[0], a[1], a[2], step);
-                hipLaunchKernelGGL(train_quant_finish_batched_kernel<2>, gi, b256, 0, st, imgs, pg_start, wpb, a[1], aq[0],
-                                   aq[1], aq[2], step);
-            } else {
-                hipLaunchKernelGGL(train_reduce_update_quant_batched_kernel<1>, gg, bb, 0, st, imgs, pg_start, num_images,
-                                   a[0], a[1], a[2], step);
-                hipLaunchKernelGGL(train_quant_finish_batched_kernel<1>, gi, b256, 0, st, imgs, pg_start, wpb, a[1], aq[0],
-                                   aq[1], aq[2], step);
-            }
-        }
-        batch_pass_end(batch, b, num_images, tile_blocks, st);
-        return check_launch("train steps (batched, quantised)");
+    const dim3 gg((unsigned)pg_blocks), bb(bs), gi((unsigned)num_images), b256(256);  // gi: closing steps, one workgroup per image
+    const int wpb = bs / 64;
+    if (!quantised) {
+        if (s0->kind == 2)
+            hipLaunchKernelGGL(train_project_fill_batched_kernel<kScaleRot>, gg, bb, 0, st, imgs, pg_start, num_images);
+        else if (s0->kind == 0)
+            hipLaunchKernelGGL(train_project_fill_batched_kernel<kCholesky>, gg, bb, 0, st, imgs, pg_start, num_images);
+        else
+            hipLaunchKernelGGL(train_project_fill_batched_kernel<kCovariance>, gg, bb, 0, st, imgs, pg_start, num_images);
+    } else if (s0->kind != 2) {
+        const AdamStep z = idle_adam_step();
+        hipLaunchKernelGGL(train_quant_range_batched_kernel, gg, bb, 0, st, imgs, pg_start, num_images);
+        hipLaunchKernelGGL(train_quant_finish_batched_kernel<0>, gi, b256, 0, st, imgs, pg_start, wpb, z, z, z, z, 0);
     }
-    if (s0->kind == 2)
-        hipLaunchKernelGGL(train_project_fill_batched_kernel<kScaleRot>, gg, bb, 0, st, imgs, pg_start, num_images);
-    else if (s0->kind == 0)
-        hipLaunchKernelGGL(train_project_fill_batched_kernel<kCholesky>, gg, bb, 0, st, imgs, pg_start, num_images);
-    else
-        hipLaunchKernelGGL(train_project_fill_batched_kernel<kCovariance>, gg, bb, 0, st, imgs, pg_start, num_images);
     for (int it = 0; it < count; ++it) {
         const int step = first_step + it;
-        int rc = launch_tile_pass_batched(1, b, num_images, tile_blocks, uniform ? tiles0 : 0, two_phase, st);
+        if (quantised) {
+#define GI2D_LAUNCH_QUANT(M) \
+    hipLaunchKernelGGL(train_project_fill_quant_batched_kernel<M>, gg, bb, 0, st, imgs, pg_start, num_images)
+            GI2D_DISPATCH_QUANT(s0->kind);
+#undef GI2D_LAUNCH_QUANT
+        }
+        int rc = launch_tile_pass_batched(1, b, num_images, tile_blocks, uniform ? tiles0 : 0, form, st);
         if (rc != GI2D_OK) return rc;
-        AdamStep a[3];
-        for (int q = 0; q < 3; ++q) a[q] = make_adam_step(lr[q], beta1, beta2, s0->beta3, eps, step, adan_opt);
+        const IterSteps t = iter_steps(s0, lr, beta1, beta2, eps, first_step, it);
+        const AdamStep *a = t.a, *aq = t.aq;
+        if (quantised) {
+#define GI2D_LAUNCH_QUANT(M)                                                                                           \
+    hipLaunchKernelGGL(train_reduce_update_quant_batched_kernel<M>, gg, bb, 0, st, imgs, pg_start, num_images, a[0],   \
+                       a[1], a[2], step);                                                                              \
+    hipLaunchKernelGGL(train_quant_finish_batched_kernel<M>, gi, b256, 0, st, imgs, pg_start, wpb, a[1], aq[0], aq[1], \
+                       aq[2], step)
+            GI2D_DISPATCH_QUANT(s0->kind);
+#undef GI2D_LAUNCH_QUANT
+            continue;
+        }
         const bool more = it + 1 < count;
 #define GI2D_LAUNCH_RU(K, F, A)                                                                                       \
     hipLaunchKernelGGL((train_reduce_update_batched_kernel<K, F, A>), gg, bb, 0, st, imgs, pg_start, num_images, a[0], \
                        a[1], a[2], step)
-        GI2D_DISPATCH_RU(s0->kind, more, adan_opt);
+        GI2D_DISPATCH_RU(s0->kind, more, s0->optimizer == 1);
 #undef GI2D_LAUNCH_RU
     }
     batch_pass_end(batch, b, num_images, tile_blocks, st);

@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -117,6 +117,62 @@ def quantized_gaussian_code_length_bits(codes: torch.Tensor) -> float:
     p = p / p.sum()
     p = p * (1 - p.numel() * 2.0 ** -24) + 2.0 ** -24
     return float(-torch.log2(p[(c.long() - lo)]).sum())
+
+
+# The fitting schedules, written once over `fitters` that run in lockstep and the `train` callable that advances them all
+# (one NativeFitter and its train, or the members of a BatchFitter and its batched train).  `tagged`: a batch, whose log
+# lines about one image name it.
+def _image_log(log, i: int, tagged: bool):
+    return (lambda m: log(f"[image {i}] {m}")) if log and tagged else log
+
+
+def _fit_schedule(fitters, train, tagged: bool, iterations: int, prune_iter: int = 100, grow_iter: int = 5000,
+                  adaptive_add: bool = True, max_points: Optional[int] = None, log=None, chunk: Optional[int] = None,
+                  total_iterations: Optional[int] = None):
+    """NativeFitter.fit_schedule / BatchFitter.fit_schedule: the stretches between two events are `train` calls, the
+    events per-image calls on the same stream."""
+    f0 = fitters[0]
+    start = f0.iteration
+    end = start + int(iterations)
+    total = int(iterations) if total_iterations is None else int(total_iterations)
+    while f0.iteration < end:
+        local = f0.iteration - start
+        train(f0._next_stop(local, end - start, prune_iter, grow_iter, adaptive_add, chunk) - local)
+        local = f0.iteration - start
+        for i, f in enumerate(fitters):
+            f._schedule_events(local, total, prune_iter, grow_iter, adaptive_add, max_points, _image_log(log, i, tagged))
+        yield local
+    for f in fitters:
+        f._schedule_end(log)
+
+
+def _fit_quantize_schedule(fitters, train, tagged: bool, iterations: int, warmup_iter: int, bits=(12, 10, 6),
+                           chunk: Optional[int] = None, log=None, **kw):
+    """NativeFitter.fit_quantize_schedule / BatchFitter.fit_quantize_schedule: the warm-up and the quantisation-aware
+    iterations in lockstep, the switch between them per image."""
+    assert all(f.track_best for f in fitters), "the switch to quantisation-aware fitting starts from the best warm-up model"
+    f0 = fitters[0]
+    warm = max(0, min(int(warmup_iter), int(iterations)) - 1)
+    start = f0.iteration
+    # every multiple of prune_iter / grow_iter below warmup_iter is <= warm, so the warm-up call sees them all
+    yield from _fit_schedule(fitters, train, tagged, warm, chunk=chunk, log=log, total_iterations=int(iterations), **kw)
+    for i, f in enumerate(fitters):
+        f.load_best()
+        f.prune_non_definite()
+        f.sync_population()  # the quantisers are initialised from the live rows
+        f.enable_quantize(*bits)
+        if log:
+            _image_log(log, i, tagged)(f"iter {f.iteration - start + 1}: warm-up finished, quantisation-aware from here "
+                                       f"({f.n} gaussians)")
+    left = max(0, int(iterations) - 1 - warm)
+    while left > 0:
+        step = min(left, int(chunk)) if chunk else left
+        train(step)
+        left -= step
+        yield f0.iteration - start
+    for f in fitters:
+        f.prune_non_definite()
+        f.sync_population()
 
 
 class NativeFitter:
@@ -271,6 +327,24 @@ class NativeFitter:
         """StepLR(step_size=lr_step, gamma=lr_gamma), stepped once per iteration after the optimizer."""
         return self.lr * self.lr_gamma ** ((self.iteration - self.opt_start) // self.lr_step)
 
+    def _plan_call(self, left: int, lr3, max_call: int, fitters) -> Tuple[int, int]:
+        """Plan the next C-ABI call of `train` with `left` iterations to go: one stretch of constant learning rates
+        (StepLR changes the gaussians' every `lr_step` iterations, the quantiser optimizers' every `q_lr_step`), at most
+        `max_call` iterations.  Writes the learning rate into `lr3` and the quantisers' learning rate and step count
+        into the state of every fitter of `fitters` (this one, or the batch that shares its schedule); returns the
+        1-based optimizer step of the call's first iteration and its iteration count."""
+        lr3[0] = lr3[1] = lr3[2] = self.current_lr()
+        done = self.iteration - self.opt_start
+        count = min(left, self.lr_step - done % self.lr_step, max_call)
+        if self.quant is not None:  # the quantiser optimizers have their own StepLR (step 10000, gamma 0.5)
+            qdone = self.iteration - self.quant_start
+            count = min(count, self.q_lr_step - qdone % self.q_lr_step)
+            qlr = self.q_lr * self.q_lr_gamma ** (qdone // self.q_lr_step)
+            for f in fitters:
+                f.quant.lr[0] = f.quant.lr[1] = f.quant.lr[2] = qlr
+                f.quant.first_step = qdone + 1
+        return done + 1, count
+
     def train(self, iterations: int) -> None:
         """Run `iterations` training iterations (asynchronous: only kernel launches).  One C-ABI call per stretch
         of constant learning rate (StepLR changes it every `lr_step` iterations), at most `max_call` iterations each."""
@@ -286,19 +360,11 @@ class NativeFitter:
             if nbytes:  # (0: an image of more than 1 536 tiles does without)
                 self.inbox = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
                 self.state.inbox, self.state.inbox_bytes = self.inbox.data_ptr(), nbytes
+        fitters = (self,)
         with torch.cuda.device(self.dev):
             while left > 0:
-                lr = self.current_lr()
-                self._lr3[0] = self._lr3[1] = self._lr3[2] = lr
-                done = self.iteration - self.opt_start
-                count = min(left, self.lr_step - done % self.lr_step, self.max_call)
-                if self.quant is not None:  # the quantiser optimizers have their own StepLR (step 10000, gamma 0.5)
-                    qdone = self.iteration - self.quant_start
-                    count = min(count, self.q_lr_step - qdone % self.q_lr_step)
-                    qlr = self.q_lr * self.q_lr_gamma ** (qdone // self.q_lr_step)
-                    self.quant.lr[0] = self.quant.lr[1] = self.quant.lr[2] = qlr
-                    self.quant.first_step = qdone + 1
-                rc = self._steps_fn(self._state_ref, self._lr3, b1, b2, self.eps, done + 1, count, st)
+                first_step, count = self._plan_call(left, self._lr3, self.max_call, fitters)
+                rc = self._steps_fn(self._state_ref, self._lr3, b1, b2, self.eps, first_step, count, st)
                 if rc != 0:
                     self._check(rc, "gi2d_train_steps")
                 self.iteration += count
@@ -773,16 +839,8 @@ class NativeFitter:
         interleave several fitters on several HIP streams (launch.py).  `total_iterations`: the run's total count, which
         the growth budget refers to (train.py:91 `iter == self.iterations - grow_iter`), when this call covers only a
         part of it (fit_quantize_schedule's warm-up); default = `iterations`."""
-        start = self.iteration
-        end = start + int(iterations)
-        total = int(iterations) if total_iterations is None else int(total_iterations)
-        while self.iteration < end:
-            local = self.iteration - start
-            self.train(self._next_stop(local, end - start, prune_iter, grow_iter, adaptive_add, chunk) - local)
-            local = self.iteration - start
-            self._schedule_events(local, total, prune_iter, grow_iter, adaptive_add, max_points, log)
-            yield local
-        self._schedule_end(log)
+        return _fit_schedule((self,), self.train, False, iterations, prune_iter, grow_iter, adaptive_add, max_points, log,
+                             chunk, total_iterations)
 
     def fit_quantize_schedule(self, iterations: int, warmup_iter: int, bits=(12, 10, 6), chunk: Optional[int] = None,
                               log=None, **kw):
@@ -793,28 +851,7 @@ class NativeFitter:
         non-definite prune closes the loop (:175).  train_quantize.py prunes BEFORE it snapshots the best model
         (:158-168), so its warm-up snapshot never holds a non-definite gaussian; the on-device snapshot here is taken
         inside the update kernel, i.e. before the prune, so the restored model is pruned once more at the switch."""
-        assert self.track_best, "the switch to quantisation-aware fitting starts from the best warm-up model"
-        warm = max(0, min(int(warmup_iter), int(iterations)) - 1)
-        start = self.iteration
-
-        # every multiple of prune_iter / grow_iter below warmup_iter is <= warm, so the warm-up call sees them all
-        sched = self.fit_schedule(warm, chunk=chunk, log=log, total_iterations=int(iterations), **kw)
-        for local in sched:
-            yield local
-        self.load_best()
-        self.prune_non_definite()
-        self.sync_population()  # the quantisers are initialised from the live rows
-        self.enable_quantize(*bits)
-        if log:
-            log(f"iter {self.iteration - start + 1}: warm-up finished, quantisation-aware from here ({self.n} gaussians)")
-        left = max(0, int(iterations) - 1 - warm)
-        while left > 0:
-            step = min(left, int(chunk)) if chunk else left
-            self.train(step)
-            left -= step
-            yield self.iteration - start
-        self.prune_non_definite()
-        self.sync_population()
+        return _fit_quantize_schedule((self,), self.train, False, iterations, warmup_iter, bits, chunk, log, **kw)
 
     def fit(self, iterations: int, **kw) -> None:
         """Run fit_schedule to the end (same keyword arguments)."""
@@ -882,19 +919,9 @@ class BatchFitter:
         left = int(iterations)
         with torch.cuda.device(self.dev):
             while left > 0:
-                lr = f0.current_lr()
-                self._lr3[0] = self._lr3[1] = self._lr3[2] = lr
-                done = f0.iteration - f0.opt_start
-                count = min(left, f0.lr_step - done % f0.lr_step, self.max_call)
-                if f0.quant is not None:  # the quantiser optimizers' own StepLR (NativeFitter.train)
-                    qdone = f0.iteration - f0.quant_start
-                    count = min(count, f0.q_lr_step - qdone % f0.q_lr_step)
-                    qlr = f0.q_lr * f0.q_lr_gamma ** (qdone // f0.q_lr_step)
-                    for f in self.fitters:
-                        f.quant.lr[0] = f.quant.lr[1] = f.quant.lr[2] = qlr
-                        f.quant.first_step = qdone + 1
+                first_step, count = f0._plan_call(left, self._lr3, self.max_call, self.fitters)
                 rc = self._fn(len(self.fitters), self._states, self.table.data_ptr(), self.table.numel(), self._lr3,
-                              b1, b2, f0.eps, done + 1, count, st)
+                              b1, b2, f0.eps, first_step, count, st)
                 if rc != 0:
                     f0._check(rc, "gi2d_train_steps_batched")
                 for f in self.fitters:
@@ -906,50 +933,14 @@ class BatchFitter:
                      total_iterations: Optional[int] = None):
         """NativeFitter.fit_schedule for the whole batch (same arguments): the stretches between two events are batched
         calls, the events (prune every `prune_iter`, grow every `grow_iter`) per-image calls on the same stream."""
-        f0 = self.fitters[0]
-        start = f0.iteration
-        end = start + int(iterations)
-        total = int(iterations) if total_iterations is None else int(total_iterations)
-        while f0.iteration < end:
-            local = f0.iteration - start
-            self.train(f0._next_stop(local, end - start, prune_iter, grow_iter, adaptive_add, chunk) - local)
-            local = f0.iteration - start
-            for i, f in enumerate(self.fitters):
-                f._schedule_events(local, total, prune_iter, grow_iter, adaptive_add, max_points,
-                                   (lambda m, i=i: log(f"[image {i}] {m}")) if log else None)
-            yield local
-        for f in self.fitters:
-            f._schedule_end(log)
+        return _fit_schedule(self.fitters, self.train, True, iterations, prune_iter, grow_iter, adaptive_add, max_points,
+                             log, chunk, total_iterations)
 
-    def fit(self, iterations: int, **kw) -> None:
-        for _ in self.fit_schedule(iterations, **kw):
-            pass
+    fit = NativeFitter.fit
 
     def fit_quantize_schedule(self, iterations: int, warmup_iter: int, bits=(12, 10, 6), chunk: Optional[int] = None,
                               log=None, **kw):
         """NativeFitter.fit_quantize_schedule for the whole batch: the plain warm-up in lockstep (fit_schedule), the
         switch per image (best warm-up model, prune, quantisers initialised from its own data), then quantisation-aware
         iterations in lockstep -- four launches per iteration for all images (gi2d_train_steps_batched)."""
-        f0 = self.fitters[0]
-        assert all(f.track_best for f in self.fitters)
-        warm = max(0, min(int(warmup_iter), int(iterations)) - 1)
-        start = f0.iteration
-        for local in self.fit_schedule(warm, chunk=chunk, log=log, total_iterations=int(iterations), **kw):
-            yield local
-        for i, f in enumerate(self.fitters):
-            f.load_best()
-            f.prune_non_definite()
-            f.sync_population()  # the quantisers are initialised from the live rows
-            f.enable_quantize(*bits)
-            if log:
-                log(f"[image {i}] iter {f.iteration - start + 1}: warm-up finished, quantisation-aware from here "
-                    f"({f.n} gaussians)")
-        left = max(0, int(iterations) - 1 - warm)
-        while left > 0:
-            step = min(left, int(chunk)) if chunk else left
-            self.train(step)
-            left -= step
-            yield f0.iteration - start
-        for f in self.fitters:
-            f.prune_non_definite()
-            f.sync_population()
+        return _fit_quantize_schedule(self.fitters, self.train, True, iterations, warmup_iter, bits, chunk, log, **kw)
