@@ -71,6 +71,8 @@ struct TilePassArgs {
     int32_t *big_tile;  // two-phase tile pass: which tiles the small form left to the general one (FastWs::big_tile)
     float4 *inbox;      // the tiles' inboxes (gi2d_train_state::inbox; nullptr: none)
     int write_through;  // single-image launches of one residency round: rows and image leave as sc1 stores (store16)
+    int leave_image;    // single-image launches: this pass does not store out_img (fused_tile; a batched launch says so
+                        // in a kernel argument: its table is written once per call)
 };
 
 // One image's arguments of the per-gaussian fitting kernels (project+fill, reduce+update).
@@ -100,6 +102,7 @@ static inline TilePassArgs tile_pass_args(const FastWs &w, int n, int tiles_x, i
     a.lists = w.lists;
     a.inbox = w.inbox_recs;
     a.write_through = 0;
+    a.leave_image = 0;
     a.tile_bins = (int2 *)w.tile_bins;
     a.partial_g = w.partial_g;
     a.partial_big = w.partial_big;
@@ -177,8 +180,10 @@ void write_batch_table(const BatchTable &table, const BatchImage *imgs, int k_im
 // `total_blocks` = head->tile_start[K] workgroups; uniform_tiles > 0: every image has that many tiles.
 // `form` (batch_pass_begin says which): 0 one launch of the general form; 1 / 2 the small form on every tile it can serve,
 // then the general form on the rest -- 2: the last pass that reported found such tiles (the second launch is shaped for work).
+// `leave_image`: no image of the batch stores its out_img in this pass (fused_tile): an iteration of a fitting call
+// that is not the call's last.
 int launch_tile_pass_batched(int mode, const BatchTable &b, int k_images, int total_blocks, int uniform_tiles,
-                             int form, hipStream_t st);
+                             int form, hipStream_t st, bool leave_image);
 // Bracket of one C-ABI call's batched tile passes on table `batch`: _begin answers "which form?" (as above) from what the
 // previous call on the same table reported (without waiting for anything), _end queues the read-back of this call's
 // report.  (The same bracket for a single image of more than one residency round of tiles, keyed by its workspace;
@@ -186,10 +191,12 @@ int launch_tile_pass_batched(int mode, const BatchTable &b, int k_images, int to
 int single_pass_begin(const void *ws, long long tiles, hipStream_t st);
 void single_pass_end(const void *ws, const FastWs &w, long long tiles, hipStream_t st);
 // gi2d_fast_rasterize_forward_backward with the form given: 1 / 2 two launches, 0 one, -1 the C entry's own rule
+// inbox: the tiles' inboxes to take entrants out of (fast_fwdbwd_kernel), or null
+// leave_image: out_img is not written (neither by the tiles nor as the background image): the caller's last pass stores it
 int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned img_w, unsigned img_h, const float *background,
                                const float *v_output, const float *target, float grad_scale, float *tile_sse, void *ws,
                                size_t ws_bytes, int32_t *status, float *out_img, gi2d_stream_t st, int form,
-                               float4 *inbox = nullptr);  // inbox: the tiles' inboxes to take entrants out of (fast_fwdbwd_kernel)
+                               float4 *inbox, bool leave_image);
 int batch_pass_begin(const void *batch, int total_blocks, hipStream_t st);
 void batch_pass_end(const void *batch, const BatchTable &b, int k_images, int total_blocks, hipStream_t st);
 

@@ -243,8 +243,8 @@ __global__ __launch_bounds__(256) void fast_ws_init_kernel(int num_tiles, int n,
 // (the INBOX instantiation: one image of at most one residency round), 2 when `wt` says so (the general-form kernel of a
 // single image: the launch code knows the tile count).
 template <int MODE, int PHASE, bool INBOX = false, int WTMODE = 0>
-__device__ __forceinline__ void tile_pass_workgroup(const TilePassArgs &a, int slot, bool first, bool mark_big = false,
-                                                    bool wt = false) {
+__device__ __forceinline__ void tile_pass_workgroup(const TilePassArgs &a, int slot, bool first, bool leave_image,
+                                                    bool mark_big = false, bool wt = false) {
     constexpr int CAP = PHASE == 1 ? GI2D_SMALL_CAP : GI2D_TILE_LIST_CAP;
     __shared__ FusedLdsT<CAP> sm;
     int tile;
@@ -269,11 +269,11 @@ __device__ __forceinline__ void tile_pass_workgroup(const TilePassArgs &a, int s
     if (WTMODE == 1 || (WTMODE == 2 && wt))  // workgroup-uniform (launch-uniform)
         fused_tile<MODE, CAP, PHASE == 2 ? 1 : GI2D_FWD_UNROLL, INBOX, WTMODE != 0>(
             sm, tile, a.tiles_x, a.tiles_y, a.img_w, a.img_h, recs, a.lists, a.tile_bins, a.partial_g, a.partial_big, a.status,
-            a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib);
+            a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib, leave_image);
     else
         fused_tile<MODE, CAP, PHASE == 2 ? 1 : GI2D_FWD_UNROLL, INBOX, false>(
             sm, tile, a.tiles_x, a.tiles_y, a.img_w, a.img_h, recs, a.lists, a.tile_bins, a.partial_g, a.partial_big, a.status,
-            a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib);
+            a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib, leave_image);
 }
 
 // Phase 2 finds nothing to do on the scenes the two-phase form is for (large images: sparse rows), and ten thousand
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256, GI2D_PHASE_OCC(PHASE)) void fast_fwdbwd_kernel
         while (todo) {  // workgroup-uniform: every wave computed the same mask
             const int slot = s0 + __builtin_ctzll(todo) * stride;
             todo &= todo - 1;
-            tile_pass_workgroup<MODE, PHASE>(a, slot, false);
+            tile_pass_workgroup<MODE, PHASE>(a, slot, false, a.leave_image != 0);
             __syncthreads();  // the next tile stages into the same LDS
         }
     } else {
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256, GI2D_PHASE_OCC(PHASE)) void fast_fwdbwd_kernel
         // (the small form of a single LARGE image -- phase 1 of two launches at 2040x1356 -- measured with write-through
         // rows, image and both: 54.97 -> 55.6-55.7 us; seven residency rounds overlap their stores already)
         tile_pass_workgroup<MODE, PHASE, INBOX, INBOX ? 1 : (PHASE == 0 ? 2 : 0)>(
-            a, (int)blockIdx.x, blockIdx.x == 0, tiles > GI2D_TWO_PHASE_TILES, a.write_through != 0);
+            a, (int)blockIdx.x, blockIdx.x == 0, a.leave_image != 0, tiles > GI2D_TWO_PHASE_TILES, a.write_through != 0);
     }
 }
 
@@ -390,7 +390,7 @@ __device__ __forceinline__ void batched_slot_of_lane(int b, const int *__restric
 template <int MODE, int PHASE>
 __global__ __launch_bounds__(256, GI2D_PHASE_OCC(PHASE)) void fast_fwdbwd_batched_kernel(
     const BatchImage *__restrict__ imgs, const BatchHead *__restrict__ head, int k_images, int uniform_tiles,
-    int xcd_map) {
+    int xcd_map, int leave_image) {
     const int *tile_start = head->tile_start;
     int k, local;
     if (PHASE == 2) {
@@ -407,7 +407,7 @@ __global__ __launch_bounds__(256, GI2D_PHASE_OCC(PHASE)) void fast_fwdbwd_batche
             const int b = s0 + __builtin_ctzll(todo) * stride;
             todo &= todo - 1;
             batched_slot(b, tile_start, k_images, uniform_tiles, xcd_map, k, local);
-            tile_pass_workgroup<MODE, PHASE>(imgs[k].t, local, false);
+            tile_pass_workgroup<MODE, PHASE>(imgs[k].t, local, false, leave_image != 0);
             __syncthreads();
         }
     } else {
@@ -415,7 +415,7 @@ __global__ __launch_bounds__(256, GI2D_PHASE_OCC(PHASE)) void fast_fwdbwd_batche
         // (a SMALL batch in the general form -- K = 3 / 4: three to four residency rounds -- measured with write-through
         // stores: K = 4 12.95 -> 13.75 us per image, the 12-image Kodak shard 1.39 -> 1.31 images/s: only a launch of ONE
         // residency round, whose stores all fall into its last third, gains from them)
-        tile_pass_workgroup<MODE, PHASE>(imgs[k].t, local, local == 0, true);
+        tile_pass_workgroup<MODE, PHASE>(imgs[k].t, local, local == 0, leave_image != 0, true);
     }
 }
 
@@ -611,7 +611,8 @@ static void launch_between(K kernel, dim3 grid, dim3 block, hipStream_t st, hipE
         hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
 }
 int launch_tile_pass_batched(int mode, const BatchTable &b, int k_images, int total_blocks, int uniform_tiles,
-                             int form, hipStream_t st) {
+                             int form, hipStream_t st, bool leave_image) {
+    const int leave = leave_image ? 1 : 0;
     if (total_blocks <= 0) return GI2D_OK;
     int xcd_map = 0;  // images placed on the XCDs whole (see the kernel): a multiple of 8
     if (uniform_tiles > 0) xcd_map = k_images & ~7;
@@ -622,21 +623,21 @@ int launch_tile_pass_batched(int mode, const BatchTable &b, int k_images, int to
         const dim3 grid2(phase2_blocks(total_blocks, form == 2));
         if (mode == 0) {
             launch_between((fast_fwdbwd_batched_kernel<0, 1>), grid, block, st, tm ? tm->begin : nullptr, nullptr, imgs,
-                           b.head, k_images, uniform_tiles, xcd_map);
+                           b.head, k_images, uniform_tiles, xcd_map, leave);
             launch_between((fast_fwdbwd_batched_kernel<0, 2>), grid2, block, st, nullptr, tm ? tm->end : nullptr, imgs,
-                           b.head, k_images, uniform_tiles, xcd_map);
+                           b.head, k_images, uniform_tiles, xcd_map, leave);
         } else {
             launch_between((fast_fwdbwd_batched_kernel<1, 1>), grid, block, st, tm ? tm->begin : nullptr, nullptr, imgs,
-                           b.head, k_images, uniform_tiles, xcd_map);
+                           b.head, k_images, uniform_tiles, xcd_map, leave);
             launch_between((fast_fwdbwd_batched_kernel<1, 2>), grid2, block, st, nullptr, tm ? tm->end : nullptr, imgs,
-                           b.head, k_images, uniform_tiles, xcd_map);
+                           b.head, k_images, uniform_tiles, xcd_map, leave);
         }
     } else if (mode == 0) {
         GI2D_LAUNCH_TIMED((fast_fwdbwd_batched_kernel<0, 0>), grid, block, st, imgs, b.head, k_images, uniform_tiles,
-                          xcd_map);
+                          xcd_map, leave);
     } else {
         GI2D_LAUNCH_TIMED((fast_fwdbwd_batched_kernel<1, 0>), grid, block, st, imgs, b.head, k_images, uniform_tiles,
-                          xcd_map);
+                          xcd_map, leave);
     }
     return check_launch("batched tile pass");
 }
@@ -952,7 +953,7 @@ int gi2d_fast_rasterize_forward_backward(int n, int tiles_x, int tiles_y, unsign
                                          float grad_scale, float *tile_sse, void *ws, size_t ws_bytes,
                                          int32_t *status, float *out_img, gi2d_stream_t st) {
     return gi2d::fast_forward_backward_form(n, tiles_x, tiles_y, w_, h, background, v_output, target, grad_scale, tile_sse,
-                                            ws, ws_bytes, status, out_img, st, -1, nullptr);
+                                            ws, ws_bytes, status, out_img, st, -1, nullptr, false);
 }
 }  // extern "C"
 
@@ -963,7 +964,7 @@ namespace gi2d {
 int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned w_, unsigned h, const float *background,
                                const float *v_output, const float *target, float grad_scale, float *tile_sse, void *ws,
                                size_t ws_bytes, int32_t *status, float *out_img, gi2d_stream_t st, int form,
-                               float4 *inbox) {
+                               float4 *inbox, bool leave_image) {
     int rc = check_ws("fast rasterize forward+backward: workspace too small", ws, ws_bytes, n, tiles_x, tiles_y);
     if (rc != GI2D_OK) return rc;
     const long long t = (long long)tiles_x * tiles_y;
@@ -985,6 +986,7 @@ int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned w_, uns
                                     v_output ? v_output : target, v_output ? 0.f : grad_scale,
                                     v_output ? nullptr : tile_sse);
     a.write_through = wt ? 1 : 0;
+    a.leave_image = leave_image ? 1 : 0;
     const dim3 grid((unsigned)t), block(256);
     if (form < 0) form = pass_form_override() >= 0 ? pass_form_override() : 1;
     if (two_phase_tile_pass(t) && form >= 1) {
@@ -1006,7 +1008,7 @@ int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned w_, uns
     } else {
         GI2D_LAUNCH_TIMED((fast_fwdbwd_kernel<1, 0>), grid, block, (hipStream_t)st, a);
     }
-    if (background)
+    if (background && !leave_image)
         hipLaunchKernelGGL(fast_background_kernel, dim3(256), dim3(256), 0, (hipStream_t)st, (int)w_, (int)h,
                            status, background, out_img);
     return check_launch("fast rasterize forward+backward");
@@ -1072,7 +1074,7 @@ int gi2d_fast_rasterize_forward_backward_batched(int num_images, const gi2d_fast
     write_batch_table(b, host_imgs.data(), num_images, head, (hipStream_t)st);
     const int two_phase = batch_pass_begin(batch, blocks, (hipStream_t)st);
     const int rc = launch_tile_pass_batched(given ? 0 : 1, b, num_images, blocks, uniform ? tiles0 : 0, two_phase,
-                                            (hipStream_t)st);
+                                            (hipStream_t)st, false);
     batch_pass_end(batch, b, num_images, blocks, (hipStream_t)st);
     return rc;
 }

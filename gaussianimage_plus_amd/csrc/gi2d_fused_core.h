@@ -126,13 +126,21 @@ static_assert(offsetof(FusedLdsSmall, slot) >= offsetof(FusedLdsSmall, part) &&
 //         with loss_type "L2"), and tile_sse[tile] receives the tile's sum of squared errors (fixed order).
 // INBOX: see tile_list_head.
 // WT: gradient rows and image leave as write-through stores (gi2d_raster_core.h::store16): the single-image launches.
+// leave_image (workgroup-uniform, a launch's kernel argument): this pass does not store `out_img` -- an iteration of a
+// fitting call that is not the call's last (gi2d_train_steps[_batched]).  Nothing on the device reads the image: gradient
+// and squared error come from the pixel in registers, so every other result is that of the storing pass, from the same
+// instructions (a run-time switch on purpose: ONE body serves the iterations that store and those that do not, so a call
+// of K iterations stays bitwise equal to K calls of one).
 template <int MODE, int CAP = GI2D_TILE_LIST_CAP, int FWD_UNROLL = GI2D_FWD_UNROLL, bool INBOX = false, bool WT = false>
 __device__ __forceinline__ void fused_tile(
     FusedLdsT<CAP> &sm, int tile, int tiles_x, int tiles_y, int img_w, int img_h, const float4 *__restrict__ recs,
     int32_t *__restrict__ lists, int2 *__restrict__ tile_bins,
     float4 *__restrict__ partial_g, float4 *__restrict__ partial_big, int32_t *__restrict__ status,
     float *__restrict__ out_img, const float *__restrict__ vsrc, float grad_scale, float *__restrict__ tile_sse,
-    const HeadRow head_row, const Inbox &ib) {
+    const HeadRow head_row, const Inbox &ib, bool leave_image = false) {
+#ifdef GI2D_KNOCK_CALL_STORES /* development aid: what the stores a fitting call can leave out cost at most (no image at all) */
+    leave_image = true;
+#endif
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int pool_rows = tiles_x * tiles_y * GI2D_TILE_LIST_CAP;  // rows of `partial_big`, the row pool (PrevBox)
     static_assert(CAP <= GI2D_TILE_LIST_CAP, "at most the reference's 256 entries of a tile are rasterized");
@@ -228,11 +236,13 @@ __device__ __forceinline__ void fused_tile(
         return;
     }
 #endif
-    if (WT && (img_w & 3) == 0 && (reinterpret_cast<uintptr_t>(out_img) & 15) == 0 && (tx + 1) * GI2D_TILE <= img_w &&
-        (ty + 1) * GI2D_TILE <= img_h)  // tile-uniform: rows of 16-byte pieces, a tile inside the image
-        fwd_store_pixels_wt(o0, o1, o2, tx, ty, img_w, mybuf, out_img);
-    else
-        fwd_store_pixels(o0, o1, o2, tx, ty, img_w, img_h, out_img);
+    if (!leave_image) {  // (else: the caller reads the image a later pass of the same call stores)
+        if (WT && (img_w & 3) == 0 && (reinterpret_cast<uintptr_t>(out_img) & 15) == 0 && (tx + 1) * GI2D_TILE <= img_w &&
+            (ty + 1) * GI2D_TILE <= img_h)  // tile-uniform: rows of 16-byte pieces, a tile inside the image
+            fwd_store_pixels_wt(o0, o1, o2, tx, ty, img_w, mybuf, out_img);
+        else
+            fwd_store_pixels(o0, o1, o2, tx, ty, img_w, img_h, out_img);
+    }
 
     // ---- this pixel's gradient
     float v0 = p0, v1 = p1, v2 = p2, sse = 0.f;

@@ -331,11 +331,17 @@ __device__ __forceinline__ bool best_decision(const BestSnap &best, const SseLoa
 // workgroup (`order_block`) that computes the next iteration's tile order (gi2d_fast_internal.h).
 // INBOX: entered tiles take the gaussian through their inbox where that is possible (the single-image kernel).
 // ALONE: the launch serves one image (its waves have things to wait for and nothing to do meanwhile).
+// store_proj (FILL_NEXT; launch-uniform, a kernel argument): the projection's `xys` and `num_tiles_hit` are stored -- the
+// last binning update kernel of a call.  No kernel of a fit reads the two (the tile pass works from the records, the
+// next update kernel reads radii and conics): they are outputs for the caller, who looks once the call is complete.
 template <int KIND, bool FILL_NEXT, bool ADAN, bool INBOX = false, bool ALONE = INBOX>
 __device__ __forceinline__ void train_reduce_update_body(int block, bool order_block, const UpdateArgs &u,
                                                          const AdamStep &a_xyz, const AdamStep &a_chol,
-                                                         const AdamStep &a_feat, int step) {
+                                                         const AdamStep &a_feat, int step, bool store_proj) {
 #pragma clang fp contract(off)
+#ifdef GI2D_KNOCK_CALL_STORES /* development aid: see fused_tile */
+    store_proj = false;
+#endif
     const int tiles_x = u.tiles_x, tiles_y = u.tiles_y;
     if (order_block) {
         // Tile populations drift slowly along a fit: the order is renewed every 16th step, and then unconditionally --
@@ -530,10 +536,10 @@ __device__ __forceinline__ void train_reduce_update_body(int block, bool order_b
         // store of the lane, then the list stores that need the atomics' results.
         bin_projected<INBOX>(g, o, opac_next, new_feat.a, new_feat.b, new_feat.c, tiles_x, tiles_y, radius_clip, pbox,
                             next.prev_box, next.lists, recs, [&] {
-                                xys[g] = o.xy;
+                                if (store_proj) xys[g] = o.xy;
                                 radii[g] = o.radius;
                                 store_row3(conics, g, o.k0, o.k1, o.k2);
-                                next.num_tiles_hit[g] = o.tiles_hit;
+                                if (store_proj) next.num_tiles_hit[g] = o.tiles_hit;
                                 store_rest();
                             }, &inbox);
     } else {
@@ -546,10 +552,10 @@ __device__ __forceinline__ void train_reduce_update_body(int block, bool order_b
 // tiles twice, +0.6 us at 2040x1356)
 template <int KIND, bool FILL_NEXT, bool ADAN, bool INBOX = false>
 __global__ __launch_bounds__(256) void train_reduce_update_kernel(UpdateArgs u, AdamStep a_xyz, AdamStep a_chol,
-                                                                  AdamStep a_feat, int step) {
+                                                                  AdamStep a_feat, int step, int store_proj) {
     static_assert(FILL_NEXT || !INBOX, "only a binning update kernel has entrants to deliver");
     train_reduce_update_body<KIND, FILL_NEXT, ADAN, INBOX, true>((int)blockIdx.x, blockIdx.x == gridDim.x - 1, u, a_xyz, a_chol,
-                                                           a_feat, step);
+                                                           a_feat, step, store_proj != 0);
 }
 // K images in one launch (gi2d_batch.h): image k owns workgroups [pg_start[k], pg_start[k + 1]), the last of them its
 // tile-ordering workgroup.  All images are at the same optimizer step with the same learning rates.
@@ -557,11 +563,12 @@ template <int KIND, bool FILL_NEXT, bool ADAN>
 __global__ __launch_bounds__(256) void train_reduce_update_batched_kernel(const BatchImage *__restrict__ imgs,
                                                                           const int *__restrict__ pg_start,
                                                                           int k_images, AdamStep a_xyz, AdamStep a_chol,
-                                                                          AdamStep a_feat, int step) {
+                                                                          AdamStep a_feat, int step, int store_proj) {
     const int k = batch_find(pg_start, k_images, (int)blockIdx.x);
     const int local = __builtin_amdgcn_readfirstlane((int)blockIdx.x - pg_start[k]);
     const int last = __builtin_amdgcn_readfirstlane(pg_start[k + 1] - pg_start[k] - 1);
-    train_reduce_update_body<KIND, FILL_NEXT, ADAN>(local, local == last, imgs[k].u, a_xyz, a_chol, a_feat, step);
+    train_reduce_update_body<KIND, FILL_NEXT, ADAN>(local, local == last, imgs[k].u, a_xyz, a_chol, a_feat, step,
+                                                    store_proj != 0);
 }
 
 
@@ -620,7 +627,12 @@ __device__ __forceinline__ void quantise_row(const TrainParams &P, const QuantTr
 // The kernels of a quantisation-aware iteration as functions of (workgroup index within the image, the image's argument
 // blocks): the single-image kernels pass blockIdx.x and their kernel arguments, the batched ones their image's entry of
 // the batch table (gi2d_batch.h).
-__device__ __forceinline__ void project_fill_quant_body(int block, const UpdateArgs &u, const QuantTrain &Q) {
+// store_proj: as train_reduce_update_body's -- the call's last projection (and every render) stores xys / num_tiles_hit
+__device__ __forceinline__ void project_fill_quant_body(int block, const UpdateArgs &u, const QuantTrain &Q,
+                                                        bool store_proj) {
+#ifdef GI2D_KNOCK_CALL_STORES
+    store_proj = false;
+#endif
     const TrainParams &P = u.P;
     const int n = live_n(P, u.n);
     const float clip_coe = u.next.clip_coe, img_w = u.img_w, img_h = u.img_h, radius_clip = u.radius_clip;
@@ -645,12 +657,12 @@ __device__ __forceinline__ void project_fill_quant_body(int block, const UpdateA
     for (int q = 0; q < 3; ++q) Q.qfeat[3 * g + q] = r.col[q].dequant;
     const ProjOut o =
         project_one<kCovariance>(0, clip_coe, &mean, par, nullptr, img_w, img_h, tiles_x, tiles_y, radius_clip);
-    xys[g] = o.xy;
+    if (store_proj) xys[g] = o.xy;
     radii[g] = o.radius;
     conics[3 * g] = o.k0;
     conics[3 * g + 1] = o.k1;
     conics[3 * g + 2] = o.k2;
-    num_tiles_hit[g] = o.tiles_hit;
+    if (store_proj) num_tiles_hit[g] = o.tiles_hit;
     bin_projected(g, o, opac, r.col[0].dequant, r.col[1].dequant, r.col[2].dequant, tiles_x, tiles_y, radius_clip,
                   old_box, prev_box, lists, recs);
 }
@@ -1022,7 +1034,11 @@ __device__ __forceinline__ void quantise_row_rs(const QuantTrain &Q, const Quant
     for (int q = 0; q < 3; ++q) r.col[q] = quant_eval<GI2D_QUANT_LSQ>(cin[q], v.fs[q], v.fb[q], 0.f, Q.qmax_col);
 }
 
-__device__ __forceinline__ void project_fill_quant_rs_body(int block, const UpdateArgs &u, const QuantTrain &Q) {
+__device__ __forceinline__ void project_fill_quant_rs_body(int block, const UpdateArgs &u, const QuantTrain &Q,
+                                                           bool store_proj) {
+#ifdef GI2D_KNOCK_CALL_STORES
+    store_proj = false;
+#endif
     const TrainParams &P = u.P;
     const int n = live_n(P, u.n);
     const float clip_coe = u.next.clip_coe, img_w = u.img_w, img_h = u.img_h, radius_clip = u.radius_clip;
@@ -1046,12 +1062,12 @@ __device__ __forceinline__ void project_fill_quant_rs_body(int block, const Upda
     store_row3(Q.qfeat, g, r.col[0].dequant, r.col[1].dequant, r.col[2].dequant);
     const ProjOut o =
         project_one<kScaleRot>(0, clip_coe, &mean, par, &par[2], img_w, img_h, tiles_x, tiles_y, radius_clip);
-    xys[g] = o.xy;
+    if (store_proj) xys[g] = o.xy;
     radii[g] = o.radius;
     conics[3 * g] = o.k0;
     conics[3 * g + 1] = o.k1;
     conics[3 * g + 2] = o.k2;
-    num_tiles_hit[g] = o.tiles_hit;
+    if (store_proj) num_tiles_hit[g] = o.tiles_hit;
     bin_projected(g, o, opac, r.col[0].dequant, r.col[1].dequant, r.col[2].dequant, tiles_x, tiles_y, radius_clip,
                   old_box, prev_box, lists, recs);
 }
@@ -1206,22 +1222,22 @@ __device__ __forceinline__ void quant_finish_rs(int blocks, const QuantTrain &Q,
 // kernel instead (ticket + device-scope fences) was measured and dropped: on this 8-XCD part every workgroup's release
 // fence writes its L2 back, which made the update kernel 17 us slower to save a 4 us launch.
 template <int MODEL>
-__global__ __launch_bounds__(256) void train_project_fill_quant_kernel(UpdateArgs u, QuantTrain Q) {
+__global__ __launch_bounds__(256) void train_project_fill_quant_kernel(UpdateArgs u, QuantTrain Q, int store_proj) {
     if (MODEL == 2)
-        project_fill_quant_rs_body((int)blockIdx.x, u, Q);
+        project_fill_quant_rs_body((int)blockIdx.x, u, Q, store_proj != 0);
     else
-        project_fill_quant_body((int)blockIdx.x, u, Q);
+        project_fill_quant_body((int)blockIdx.x, u, Q, store_proj != 0);
 }
 template <int MODEL>
 __global__ __launch_bounds__(256) void train_project_fill_quant_batched_kernel(const BatchImage *__restrict__ imgs,
                                                                                const int *__restrict__ pg_start,
-                                                                               int k_images) {
+                                                                               int k_images, int store_proj) {
     const int k = batch_find(pg_start, k_images, (int)blockIdx.x);
     const int local = __builtin_amdgcn_readfirstlane((int)blockIdx.x - pg_start[k]);
     if (MODEL == 2)
-        project_fill_quant_rs_body(local, imgs[k].u, imgs[k].q);
+        project_fill_quant_rs_body(local, imgs[k].u, imgs[k].q, store_proj != 0);
     else
-        project_fill_quant_body(local, imgs[k].u, imgs[k].q);
+        project_fill_quant_body(local, imgs[k].u, imgs[k].q, store_proj != 0);
 }
 template <int MODEL>
 __global__ __launch_bounds__(256) void train_reduce_update_quant_kernel(UpdateArgs u, QuantTrain Q, AdamStep a_xyz,
@@ -1577,9 +1593,9 @@ static void train_launch_quant_range(const ImagePlan &p, hipStream_t st) {
                        z, 0);
 }
 // activations / quantisers + projection + fill
-static void train_launch_project_fill_quant(int kind, const ImagePlan &p, hipStream_t st) {
+static void train_launch_project_fill_quant(int kind, const ImagePlan &p, hipStream_t st, bool store_proj) {
 #define GI2D_LAUNCH_QUANT(M) \
-    hipLaunchKernelGGL(train_project_fill_quant_kernel<M>, dim3(p.blocks), dim3(p.bs), 0, st, p.u, p.q)
+    hipLaunchKernelGGL(train_project_fill_quant_kernel<M>, dim3(p.blocks), dim3(p.bs), 0, st, p.u, p.q, store_proj ? 1 : 0)
     GI2D_DISPATCH_QUANT(kind);
 #undef GI2D_LAUNCH_QUANT
 }
@@ -1596,7 +1612,7 @@ int gi2d_train_render(const gi2d_train_state *s, gi2d_stream_t st_) {
     hipStream_t st = (hipStream_t)st_;
     if (s->quant) {  // forward_quantize (models/gaussianimage_covariance.py:384-410, models/gaussianimage_rs.py:443-471)
         if (s->kind != 2) train_launch_quant_range(p, st);  // (the RS model's ranges are learned values)
-        train_launch_project_fill_quant(s->kind, p, st);
+        train_launch_project_fill_quant(s->kind, p, st, true);
     } else {
         train_launch_project_fill(s->kind, p, st);
     }
@@ -1639,10 +1655,14 @@ int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, 
         train_launch_quant_range(p, st);
     for (int it = 0; it < count; ++it) {
         const int step = first_step + it;
-        if (quantised) train_launch_project_fill_quant(s->kind, p, st);
+        // Outputs the caller reads behind the call are stored by the call's LAST render only: out_img by the last tile
+        // pass, xys / num_tiles_hit by the last projection -- the last binning update kernel (iteration count - 2; the
+        // opening projection kernel when count == 1), in a quantised fit the last iteration's own projection kernel.
+        const bool last = it + 1 == count;
+        if (quantised) train_launch_project_fill_quant(s->kind, p, st, last);
         rc = fast_forward_backward_form(s->num_points, p.tx, p.ty, (unsigned)s->img_width, (unsigned)s->img_height, nullptr,
                                         nullptr, s->gt, p.grad_scale, s->tile_sse, s->workspace, s->workspace_bytes,
-                                        s->status, s->out_img, st_, form, it > 0 ? inbox : nullptr);
+                                        s->status, s->out_img, st_, form, it > 0 ? inbox : nullptr, !last);
         if (rc != GI2D_OK) return rc;
         const IterSteps t = iter_steps(s, lr, beta1, beta2, eps, first_step, it);
         const AdamStep *a = t.a, *aq = t.aq;
@@ -1657,12 +1677,15 @@ int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, 
         }
         const bool more = it + 1 < count;
         const bool deliver = more && inbox != nullptr;
+        const int store_proj = it + 2 == count ? 1 : 0;
 #define GI2D_LAUNCH_RU(K, F, A)                                                                                       \
     do {                                                                                                              \
         if (F && deliver)                                                                                             \
-            hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A, F>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step); \
+            hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A, F>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step,  \
+                               store_proj);                                                                           \
         else                                                                                                          \
-            hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step);    \
+            hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step,     \
+                               store_proj);                                                                           \
     } while (0)
         GI2D_DISPATCH_RU(s->kind, more, s->optimizer == 1);
 #undef GI2D_LAUNCH_RU
@@ -1763,13 +1786,15 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
     }
     for (int it = 0; it < count; ++it) {
         const int step = first_step + it;
+        const bool last = it + 1 == count;  // (what the call's last render alone stores: see gi2d_train_steps)
         if (quantised) {
-#define GI2D_LAUNCH_QUANT(M) \
-    hipLaunchKernelGGL(train_project_fill_quant_batched_kernel<M>, gg, bb, 0, st, imgs, pg_start, num_images)
+#define GI2D_LAUNCH_QUANT(M)                                                                                   \
+    hipLaunchKernelGGL(train_project_fill_quant_batched_kernel<M>, gg, bb, 0, st, imgs, pg_start, num_images, \
+                       last ? 1 : 0)
             GI2D_DISPATCH_QUANT(s0->kind);
 #undef GI2D_LAUNCH_QUANT
         }
-        int rc = launch_tile_pass_batched(1, b, num_images, tile_blocks, uniform ? tiles0 : 0, form, st);
+        int rc = launch_tile_pass_batched(1, b, num_images, tile_blocks, uniform ? tiles0 : 0, form, st, !last);
         if (rc != GI2D_OK) return rc;
         const IterSteps t = iter_steps(s0, lr, beta1, beta2, eps, first_step, it);
         const AdamStep *a = t.a, *aq = t.aq;
@@ -1784,9 +1809,10 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
             continue;
         }
         const bool more = it + 1 < count;
+        const int store_proj = it + 2 == count ? 1 : 0;
 #define GI2D_LAUNCH_RU(K, F, A)                                                                                       \
     hipLaunchKernelGGL((train_reduce_update_batched_kernel<K, F, A>), gg, bb, 0, st, imgs, pg_start, num_images, a[0], \
-                       a[1], a[2], step)
+                       a[1], a[2], step, store_proj)
         GI2D_DISPATCH_RU(s0->kind, more, s0->optimizer == 1);
 #undef GI2D_LAUNCH_RU
     }

@@ -397,6 +397,10 @@ int gi2d_timer_elapsed_us(void *timer, float *microseconds);
  *   gt    f32[H,W,3] target image; out_img f32[H,W,3] last render (pre-clamp)
  *   tile_sse f32[tiles] per-tile sum of squared errors of clamp(out_img) vs gt (for PSNR)
  *   xys/conics/radii/num_tiles_hit: projection outputs of the last render
+ *   out_img, xys and num_tiles_hit are outputs for the caller only (no kernel of a fit reads them), so a call of
+ *   several iterations (gi2d_train_steps, gi2d_train_steps_batched) stores them ONCE, from its last render: they hold
+ *   that render's values once the call's work on the stream is complete; while a call of more than one iteration
+ *   is running their contents are unspecified.  (conics, radii and tile_sse are written by every iteration.)
  *   status i32[4], workspace: as for the fast path (gi2d_fast_workspace_bytes/_init)
  *   dbg_grads f32[N,8] or NULL: gradients w.r.t. (xyz, chol, feat) of the last step (tests)
  * gi2d_train_step(state, lr[3], beta1, beta2, eps, step): lr = learning rates of the
