@@ -77,6 +77,8 @@ SIGNATURES.update({
     "gi2d_codec_pack": [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p],
     "gi2d_codec_decode_bin": [_i, _i, _i, _i, _i, _i, _p, _p, _sz, _f, _u, _u, _i, _i, _f, _p, _p, _p, _p, _p, _p, _sz,
                               _p, _p],
+    "gi2d_codec_decode_bin_view": [_i, _i, _i, _i, _i, _i, _p, _p, _sz, _f, _u, _u, _f, _f, _f, _u, _u, _i, _i, _f, _p, _p,
+                                   _p, _p, _p, _p, _sz, _p, _p],
     # rANS payload (payload coding 1)
     "gi2d_codec_histogram": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p],
     "gi2d_codec_rans_encode": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _sz, _p, _sz, _p, _p],

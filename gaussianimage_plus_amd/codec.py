@@ -9,6 +9,9 @@
     codec.save(path, blob); blob = codec.load(path)
     small = codec.encode(fitter, coding="rans")  # the same codes, entropy coded (payload coding 1); decodes the same way
     small = codec.recode(blob, "rans"); codec.recode(small, "fixed") == blob
+    v    = codec.View(x0, y0, width, height, scale=4.0)   # a window on the fitted function, magnified (1 <= scale <= 64)
+    part = dec.decode(blob, view=v)              # f32 [v.height, v.width, 3]; only the window's tiles are drawn
+    parts = dec.decode_views(blob, [v, codec.View.full(codec.info(blob))])
 
 Decoding needs no fitter, no target image and no optimizer state: this module imports neither `trainer` nor `quantize`.
 A decode is three native launches on buffers the Decoder owns -- gi2d_fast_workspace_init, gi2d_codec_decode_bin
@@ -16,6 +19,12 @@ A decode is three native launches on buffers the Decoder owns -- gi2d_fast_works
 [0, 1] that NativeFitter.decompress_wo_ec applies; the picture is bit-identical to that method's.  The tile-overflow
 status is looked at ONCE, after the image has been enqueued; an overflowing stream (more than 1024 candidate gaussians in
 one 16x16 tile) is rendered again through the capacity-free ops, so a valid stream always decodes.
+
+A view is a decoder argument, never stream content.  Output pixel (row i, column j) samples the fitted
+function at source position (x0 + j / scale, y0 + i / scale): every dequantised gaussian is moved and scaled into the
+window's pixel grid (view_parameters states the arithmetic) and the same operators draw the transformed gaussians at the
+window's size (gi2d_codec_decode_bin_view).  Tile boxes, the 256 entries of a tile and the pair test are those of the
+window's own tile grid, so a view is not pixel for pixel a crop or a resampling of the full decode.
 
 Format version 1 (little-endian; INTEGRATION.md "Packed stream" has the record layout):
 
@@ -37,6 +46,7 @@ kernels compute no address from stream content that is not masked or clamped to 
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 import struct
 import zlib
@@ -449,6 +459,107 @@ def recode(blob, coding: str, device: Union[str, torch.device] = "cuda:0", chunk
                     h["side"], data, coding)
 
 
+MAX_VIEW_SCALE = 64.0
+MAX_VIEW_TILES = 16384  # the fast-path workspace grows with the tiles; a viewer composes larger outputs from several views
+
+
+@dataclasses.dataclass(frozen=True)
+class View:
+    """A window on the fitted function: output pixel (row i, column j) of a `height` x `width` picture samples source
+    position (x0 + j / scale, y0 + i / scale).  x0, y0 (sub-pixel origins allowed) and scale are kept as the float32
+    values the kernel receives.  ValueError unless scale is finite and 1 <= scale <= 64 (a reduced view would put more
+    than the 256 entries into a tile that the reference's rule keeps; no prefilter is built), the origin is finite and
+    not negative, the size is at least 1 x 1 and ceil(width / 16) * ceil(height / 16) <= 16384 tiles.  Whether the window
+    lies inside a picture is checked against the stream's header by the decoder (`check`)."""
+    x0: float
+    y0: float
+    width: int
+    height: int
+    scale: float = 1.0
+
+    def __post_init__(self):
+        for name in ("x0", "y0", "scale"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"View: {name} must be a number, not {type(v).__name__}")
+            v = float(v)
+            if not math.isfinite(v):
+                raise ValueError(f"View: {name} = {v} is not finite")
+            object.__setattr__(self, name, float(np.float32(v)))
+        for name in ("width", "height"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"View: {name} must be an integer, not {type(v).__name__}")
+            object.__setattr__(self, name, int(v))
+        if not 1.0 <= self.scale <= MAX_VIEW_SCALE:
+            raise ValueError(f"View: scale {self.scale} outside 1 .. {MAX_VIEW_SCALE:g} (a reduced view overfills the 256 "
+                             "entries of a tile and the reference's rule truncates it; there is no prefilter)")
+        if self.x0 < 0 or self.y0 < 0:
+            raise ValueError(f"View: negative origin ({self.x0}, {self.y0})")
+        if self.width < 1 or self.height < 1:
+            raise ValueError(f"View: empty output {self.width}x{self.height}")
+        if self.tiles[0] * self.tiles[1] > MAX_VIEW_TILES:
+            raise ValueError(f"View: {self.width}x{self.height} is more than {MAX_VIEW_TILES} tiles of 16x16 (compose a "
+                             "larger output from several views)")
+
+    @property
+    def tiles(self):
+        return (self.width + _TILE - 1) // _TILE, (self.height + _TILE - 1) // _TILE
+
+    @classmethod
+    def full(cls, header) -> "View":
+        """The identity view of a stream (header: codec.info(blob) or a DeviceStream's): decodes to decode()'s bits."""
+        return cls(0.0, 0.0, header["width"], header["height"], 1.0)
+
+    def check(self, header) -> "View":
+        """ValueError unless the window lies inside the picture: x0 + width / scale <= the picture's width, the same for y."""
+        if (self.x0 + self.width / self.scale > header["width"] or self.y0 + self.height / self.scale > header["height"]):
+            raise ValueError(f"View: the window ({self.x0}, {self.y0}) + {self.width}x{self.height} / {self.scale} reaches "
+                             f"beyond the {header['width']}x{header['height']} picture")
+        return self
+
+    def radius_clip(self, header) -> float:
+        """What the projection and the binning step of this view are given: the stream's radius_clip * scale (float32), so
+        that a gaussian the full decode drops as too small stays dropped."""
+        return float(np.float32(header["radius_clip"]) * np.float32(self.scale))
+
+
+def _checked_view(view, h) -> Optional[View]:
+    if view is None:
+        return None
+    if not isinstance(view, View):
+        raise ValueError("view: a codec.View (or None for the whole picture at its own size)")
+    return view.check(h)
+
+
+def view_parameters(kind: int, values, view: View):
+    """The specification of a view on the dequantised gaussians.  values: float32 [N, 8] in record order (numpy array or
+    torch tensor; the log channels already through exp) -> the same kind of array, transformed in separate float32
+    operations, in this order:
+        x' = (x - x0) * scale, y' = (y - y0) * scale
+        covariance model: s2 = scale * scale, then (cxx, cxy, cyy) * s2
+        scale-rot model:  (sx, sy) * scale; the rotation as it is
+        colour as it is (opacity stays 1, clip_coe as in the header).
+    The view is the picture the operators draw for these gaussians at view.height x view.width with radius_clip =
+    view.radius_clip(header)."""
+    if kind not in _KIND_NAMES:
+        raise ValueError(f"view_parameters: model kind {kind} (1 covariance, 2 scale-rot)")
+    if tuple(values.shape[1:]) != (8,) or "float32" not in str(values.dtype):
+        raise ValueError("view_parameters: a float32 [N, 8] array")
+    is_torch = isinstance(values, torch.Tensor)
+    num = float if is_torch else np.float32  # a tensor takes a Python scalar at its own precision
+    x0, y0, sc = num(view.x0), num(view.y0), num(view.scale)
+    s2 = num(np.float32(view.scale) * np.float32(view.scale))
+    out = values.clone() if is_torch else np.array(values, np.float32)
+    out[:, 0] = (values[:, 0] - x0) * sc
+    out[:, 1] = (values[:, 1] - y0) * sc
+    if kind == KIND_COVARIANCE:
+        out[:, 2:5] = values[:, 2:5] * s2
+    else:
+        out[:, 2:4] = values[:, 2:4] * sc
+    return out
+
+
 _STATUS_WORDS = 8
 
 
@@ -487,11 +598,12 @@ class Decoder:
         # per stream: words 0..3 belong to the binning step and the tile pass (1 = overflow), word 4 to the rANS expansion
         self._status = torch.zeros(1, _STATUS_WORDS, dtype=torch.int32, device=self.dev)
         self._token = 0  # the expansion raises word 4 to the token of its decode: no reset launch between decodes
+        self.expansions = 0  # rANS payloads expanded so far (gi2d_codec_rans_expand launches)
         self._background = torch.ones(3, dtype=torch.float32, device=self.dev)  # the rasterize wrappers' default
 
     # ---------------------------------------------------------------------------------------------- buffers
-    def _reserve_workspace(self, h) -> None:
-        tx, ty = (h["width"] + _TILE - 1) // _TILE, (h["height"] + _TILE - 1) // _TILE
+    def _reserve_workspace(self, h, view: Optional[View] = None) -> None:
+        tx, ty = view.tiles if view is not None else ((h["width"] + _TILE - 1) // _TILE, (h["height"] + _TILE - 1) // _TILE)
         need = int(_lib.load().gi2d_fast_workspace_bytes(h["num_points"], tx, ty))
         if self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
@@ -534,6 +646,7 @@ class Decoder:
                   h["coded_mask"], at(nb), payload.numel() - nb, at(h["directory_offset"]), at(h["data_offset"]),
                   h["data_bytes"], h["max_chunk_bytes"], C.c_void_p(fixed.data_ptr()), nf,
                   C.c_void_p(status.data_ptr() + 16), self._token, _stream(self.dev))
+        self.expansions += 1
         return fixed
 
     def _next_token(self) -> None:
@@ -562,12 +675,18 @@ class Decoder:
 
     # ---------------------------------------------------------------------------------------------- launches
     def _enqueue(self, h, payload: torch.Tensor, status: torch.Tensor, out: torch.Tensor, aux=None,
-                 fixed: Optional[torch.Tensor] = None) -> None:
+                 fixed: Optional[torch.Tensor] = None, view: Optional[View] = None) -> None:
         """(rANS expansion into `fixed` +) workspace reset + decode/bin + forward + clamp on the current stream; no host
         sync, and no allocation when a rANS stream is given its `fixed` buffer."""
         if h["coding"] == CODING_RANS:
             payload = self._expand(h, payload, status, fixed)
-        n, w, hh = h["num_points"], h["width"], h["height"]
+        self._launch(h, payload, status, out, aux, view)
+
+    def _launch(self, h, payload: torch.Tensor, status: torch.Tensor, out: torch.Tensor, aux=None,
+                view: Optional[View] = None) -> None:
+        """Workspace reset + decode/bin + forward + clamp of a coding-0 payload; with a view, at the view's size."""
+        n = h["num_points"]
+        w, hh = (h["width"], h["height"]) if view is None else (view.width, view.height)
         tx, ty = (w + _TILE - 1) // _TILE, (hh + _TILE - 1) // _TILE
         b = h["bits"]
         side = (C.c_float * 16)(*h["side"])
@@ -575,31 +694,39 @@ class Decoder:
         st = _stream(self.dev)
         a = [C.c_void_p(t.data_ptr()) for t in aux] if aux is not None else [None] * 5
         _lib.call("gi2d_fast_workspace_init", ws, nws, n, tx, ty, st)
-        _lib.call("gi2d_codec_decode_bin", h["kind"], n, b[0], b[1], b[2], b[3], side, C.c_void_p(payload.data_ptr()),
-                  h["fixed_payload_bytes"], h["clip_coe"], hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3], a[4], ws,
-                  nws, C.c_void_p(status.data_ptr()), st)
+        if view is None:
+            _lib.call("gi2d_codec_decode_bin", h["kind"], n, b[0], b[1], b[2], b[3], side, C.c_void_p(payload.data_ptr()),
+                      h["fixed_payload_bytes"], h["clip_coe"], hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3],
+                      a[4], ws, nws, C.c_void_p(status.data_ptr()), st)
+        else:
+            _lib.call("gi2d_codec_decode_bin_view", h["kind"], n, b[0], b[1], b[2], b[3], side,
+                      C.c_void_p(payload.data_ptr()), h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"],
+                      view.x0, view.y0, view.scale, hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3], a[4], ws, nws,
+                      C.c_void_p(status.data_ptr()), st)
         _lib.call("gi2d_fast_rasterize_forward", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws,
                   C.c_void_p(status.data_ptr()), None, None, C.c_void_p(out.data_ptr()), st)
         out.clamp_(0, 1)
 
-    def _out(self, h, out: Optional[torch.Tensor]) -> torch.Tensor:
-        shape = (h["height"], h["width"], 3)
+    def _out(self, h, out: Optional[torch.Tensor], view: Optional[View] = None) -> torch.Tensor:
+        shape = (h["height"], h["width"], 3) if view is None else (view.height, view.width, 3)
         if out is None:
             return torch.empty(shape, dtype=torch.float32, device=self.dev)
         if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.dev or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {self.dev}")
         return out
 
-    def decode_geometry(self, stream) -> Dict[str, torch.Tensor]:
-        """What the decode kernel makes of every gaussian: xys, radii, conics, num_tiles_hit, colors (tests, tools)."""
+    def decode_geometry(self, stream, view: Optional[View] = None) -> Dict[str, torch.Tensor]:
+        """What the decode kernel makes of every gaussian: xys, radii, conics, num_tiles_hit, colors (tests, tools); with
+        a view, the transformed geometry in the view's pixel grid."""
         ds = stream if isinstance(stream, DeviceStream) else self.upload(stream)
         h = ds.header
+        view = _checked_view(view, h)
         with torch.cuda.device(self.dev):
-            self._reserve_workspace(h)
+            self._reserve_workspace(h, view)
             aux = self._aux(h["num_points"])
-            img = self._out(h, None)
+            img = self._out(h, None, view)
             self._next_token()
-            self._enqueue(h, ds.payload, self._status[0], img, aux)
+            self._enqueue(h, ds.payload, self._status[0], img, aux, view=view)
             if h["coding"] == CODING_RANS:
                 self._check_expanded(int(self._status[0, 4]))
         return dict(zip(("xys", "radii", "conics", "num_tiles_hit", "colors"), aux), image=img)
@@ -609,25 +736,72 @@ class Decoder:
         i = lambda *s: torch.empty(s, dtype=torch.int32, device=self.dev)
         return [f(n, 2), i(n), f(n, 3), i(n), f(n, 3)]
 
-    def _exact(self, h, payload: torch.Tensor, out: torch.Tensor) -> None:
+    def _exact(self, h, payload: torch.Tensor, out: torch.Tensor, view: Optional[View] = None,
+               expanded: bool = False) -> None:
         """A tile row overflowed: the same picture through the capacity-free ops (gi2d_bin_gaussians + the plain
-        rasterizer), fed with the decode kernel's per-gaussian outputs."""
+        rasterizer), fed with the decode kernel's per-gaussian outputs (for a view: the transformed geometry, at the
+        view's size and with its radius_clip).  expanded: `payload` is already the coding-0 payload."""
         from .gsplat import _raster_common as rc
-        n, w, hh = h["num_points"], h["width"], h["height"]
+        n = h["num_points"]
+        w, hh = (h["width"], h["height"]) if view is None else (view.width, view.height)
+        radius_clip = h["radius_clip"] if view is None else view.radius_clip(h)
         aux = self._aux(n)
         scratch = torch.empty_like(out)
-        self._enqueue(h, payload, self._status[0], scratch, aux)
+        if expanded:
+            self._launch(h, payload, self._status[0], scratch, aux, view)
+        else:
+            self._enqueue(h, payload, self._status[0], scratch, aux, view=view)
         xys, radii, conics, _, colors = aux
         tb = rc.tile_bounds_of(hh, w, _TILE, _TILE)
         opacity = torch.ones(n, 1, dtype=torch.float32, device=self.dev)
         img = rc._exact_forward(h["kind"] == KIND_COVARIANCE, xys, radii, conics, colors, opacity, hh, w, tb,
-                                (_TILE, _TILE, 1), (w, hh, 1), self._background, h["radius_clip"], False)[0]
+                                (_TILE, _TILE, 1), (w, hh, 1), self._background, radius_clip, False)[0]
         torch.clamp(img, 0, 1, out=out)
 
     # ---------------------------------------------------------------------------------------------- public
-    def decode(self, stream, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """bytes (or an uploaded DeviceStream) -> f32 [H, W, 3] in [0, 1]; `out`: a tensor to write into."""
-        return self.decode_many([stream], None if out is None else [out])[0]
+    def decode(self, stream, out: Optional[torch.Tensor] = None, view: Optional[View] = None) -> torch.Tensor:
+        """bytes (or an uploaded DeviceStream) -> f32 [H, W, 3] in [0, 1]; `out`: a tensor to write into.  view: a
+        codec.View -> f32 [view.height, view.width, 3], the window of the fitted function it names (View.full: the
+        bits of the plain decode, through the view kernel)."""
+        if view is None:
+            return self.decode_many([stream], None if out is None else [out])[0]
+        return self.decode_views(stream, [view], None if out is None else [out])[0]
+
+    def decode_views(self, stream, views: Sequence[View], outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+        """Several views of ONE stream back to back on the current stream of the device: the payload is staged once, a
+        rANS payload expanded once, the workspace reserved for the largest view, and the statuses are read once, at the
+        end."""
+        views = list(views)
+        h = stream.header if isinstance(stream, DeviceStream) else _parse(stream)
+        for v in views:  # all checked before any launch
+            if v is None:
+                raise ValueError("decode_views: every entry is a codec.View")
+            _checked_view(v, h)
+        if outs is not None and len(outs) != len(views):
+            raise ValueError("decode_views: one output tensor per view")
+        if not views:
+            return []
+        with torch.cuda.device(self.dev):
+            payload = stream.payload if isinstance(stream, DeviceStream) else self._stage([stream], [h])[0]
+            if self._status.shape[0] < len(views):
+                self._status = torch.zeros(len(views), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
+            for v in views:
+                self._reserve_workspace(h, v)
+            images = [self._out(h, None if outs is None else outs[i], v) for i, v in enumerate(views)]
+            self._next_token()
+            if h["coding"] == CODING_RANS:
+                if self._expanded.numel() < h["fixed_payload_bytes"]:
+                    self._expanded = torch.empty(h["fixed_payload_bytes"], dtype=torch.uint8, device=self.dev)
+                payload = self._expand(h, payload, self._status[0], self._expanded[:h["fixed_payload_bytes"]])
+            for i, v in enumerate(views):
+                self._launch(h, payload, self._status[i], images[i], None, v)
+            status = self._status[:len(views), 1:5].tolist()  # the one host wait: overflow per view, rANS in row 0
+            if h["coding"] == CODING_RANS:
+                self._check_expanded(status[0][3])
+            for i, (overflow, _, _, _) in enumerate(status):
+                if overflow:
+                    self._exact(h, payload, images[i], views[i], expanded=True)
+        return images
 
     def decode_many(self, streams, outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
         """Streams decoded back to back on the current stream of the device; the overflow statuses are read once, at the
@@ -669,12 +843,13 @@ class Decoder:
 _decoders: Dict[torch.device, Decoder] = {}
 
 
-def decode(blob, device: Union[str, torch.device] = "cuda:0", out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """One-shot decode (a Decoder per device is kept behind the scenes)."""
-    _parse(blob)  # a malformed stream is refused before a device is even touched
+def decode(blob, device: Union[str, torch.device] = "cuda:0", out: Optional[torch.Tensor] = None,
+           view: Optional[View] = None) -> torch.Tensor:
+    """One-shot decode (a Decoder per device is kept behind the scenes); view: a codec.View of the picture."""
+    _checked_view(view, _parse(blob))  # a malformed stream or view is refused before a device is even touched
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
     if dev not in _decoders:
         _decoders[dev] = Decoder(dev)
-    return _decoders[dev].decode(blob, out=out)
+    return _decoders[dev].decode(blob, out=out, view=view)

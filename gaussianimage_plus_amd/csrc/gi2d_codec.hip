@@ -8,9 +8,15 @@
 //               peels the fields off with funnel shifts, dequantises with the quantisers' own arithmetic (quant_dequant),
 //               projects (project_values) and bins (bin_projected) -- the front of the fused fast path with the stream in
 //               place of the parameter arrays.  gi2d_fast_rasterize_forward on the same workspace draws the picture.
+//   view        the same launch with a window on the fitted function: between dequantisation and
+//               projection every gaussian is moved and scaled into the window's pixel grid (view_transform), and the
+//               projection, the binning step and the tile pass run at the WINDOW's size.  A template flag of the
+//               same kernel: the full decode's instantiations keep their instructions.
 //
 // Nothing here is read through a pointer computed from stream CONTENT: record positions follow from (N, R) alone, and
 // every load index is clamped to the dwords the entry has checked the payload to hold.
+#include <cmath>
+
 #include "gi2d_codec_layout.h"
 #include "gi2d_fast_internal.h"
 #include "gi2d_quant_core.h"
@@ -64,10 +70,33 @@ struct CodecOut {  // optional per-gaussian outputs (all may be NULL)
     float *colors;
 };
 
+// A window on the fitted function: output pixel (row i, column j) samples source position (x0 + j / scale,
+// y0 + i / scale).  Carried out on the gaussians, in separate fp32 operations (codec.view_parameters restates them):
+//   x' = (x - x0) * scale, y' = (y - y0) * scale; covariance entries * (scale * scale); the two scales of the scale-rot
+//   model * scale, its rotation as it is; colour untouched.
+struct CodecView {
+    float x0, y0, scale;
+};
 template <int KIND>
+__device__ __forceinline__ void view_transform(float (&v)[GI2D_CODEC_FIELDS], const CodecView vw) {
+#pragma clang fp contract(off)
+    v[0] = (v[0] - vw.x0) * vw.scale;
+    v[1] = (v[1] - vw.y0) * vw.scale;
+    if (KIND == kCovariance) {
+        const float s2 = vw.scale * vw.scale;
+        v[2] = v[2] * s2, v[3] = v[3] * s2, v[4] = v[4] * s2;
+    } else {
+        v[2] = v[2] * vw.scale, v[3] = v[3] * vw.scale;
+    }
+}
+
+// img_w / img_h / tiles / radius_clip: those of the picture that is drawn (for a view: the window's size and the
+// header's radius_clip * scale, so that what the full decode drops as too small stays dropped).  VIEW = false never reads
+// `vw`: the full decode's instantiations have the instructions they had before there were views.
+template <int KIND, bool VIEW>
 __global__ __launch_bounds__(256) void codec_decode_bin_kernel(
     int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
-    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, CodecOut out, BinTarget bt) {
+    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, CodecOut out, BinTarget bt, CodecView vw) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     begin_binning(g, bt.status);
     const BinRecs recs = recs_for_binning(bt.recs, g == 0);
@@ -94,6 +123,7 @@ __global__ __launch_bounds__(256) void codec_decode_bin_kernel(
         v[k] = (KIND == kCovariance && (k == 2 || k == 4)) ? quant_dequant<GI2D_QUANT_LOG>(code, side.scale[k], side.beta[k])
                                                           : quant_dequant<GI2D_QUANT_LSQ>(code, side.scale[k], side.beta[k]);
     }
+    if (VIEW) view_transform<KIND>(v, vw);
     const ProjOut o = project_values<KIND>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h, tiles_x,
                                            tiles_y, radius_clip);
     if (out.xys) out.xys[g] = o.xy;
@@ -107,6 +137,64 @@ __global__ __launch_bounds__(256) void codec_decode_bin_kernel(
 }  // namespace gi2d
 
 using namespace gi2d;
+
+#define GI2D_CODEC_VIEW_MAX_SCALE 64
+#define GI2D_CODEC_VIEW_MAX_TILES 16384
+
+// Checks and launch shared by the two decode entries.  h, w_, tiles, radius_clip: those of the picture that is drawn;
+// view: the window of gi2d_codec_decode_bin_view (already checked), NULL for the full decode.
+static int codec_decode_launch(const char *what, const CodecView *view, int kind, int n, int xy_bits, int p0_bits,
+                               int p1_bits, int color_bits, const float *side_host, const void *payload,
+                               size_t payload_bytes, float clip_coe, unsigned h, unsigned w_, int tiles_x, int tiles_y,
+                               float radius_clip, float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit,
+                               float *colors, void *ws, size_t ws_bytes, int32_t *status, gi2d_stream_t st) {
+    const auto fail = [&](const char *why, int rc) {
+        set_error((std::string(what) + ": " + why).c_str());
+        return rc;
+    };
+    CodecLayout lay;
+    if (!codec_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 0 || tiles_x < 0 || tiles_y < 0) return fail("negative size", GI2D_ERR_INVALID_ARGUMENT);
+    const long long need = codec_dwords(n, lay.record_bits);
+    if (payload_bytes < (size_t)need * 4)
+        return fail("payload shorter than 4 * ceil(N * R / 32) bytes", GI2D_ERR_INVALID_ARGUMENT);
+    if (!side_host || !status || !ws || (n > 0 && (!payload || ((uintptr_t)payload & 3))))
+        return fail("null or misaligned pointer", GI2D_ERR_INVALID_ARGUMENT);
+    if ((long long)tiles_x * GI2D_TILE < (long long)w_ || (long long)tiles_y * GI2D_TILE < (long long)h)
+        return fail("tile grid does not cover the image", GI2D_ERR_INVALID_ARGUMENT);
+    if ((long long)tiles_x * tiles_y * GI2D_FAST_LROW > 0x7fffffffLL || (long long)n * GI2D_FAST_S > 0x7fffffffLL ||
+        tiles_x > 0xffff || tiles_y > 0xffff)
+        return fail("problem too large for 32-bit slot indices", GI2D_ERR_UNSUPPORTED);
+    if (ws_bytes < carve_fast(nullptr, n, tiles_x * tiles_y).bytes)
+        return fail("workspace too small", GI2D_ERR_WORKSPACE_TOO_SMALL);
+    CodecSide side;
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) side.scale[k] = side_host[2 * k], side.beta[k] = side_host[2 * k + 1];
+    FastWs w = carve_fast(ws, n, tiles_x * tiles_y);
+    BinTarget bt;
+    bt.colors = bt.opacities = nullptr;  // colour comes from the record, opacity is 1
+    bt.prev_box = w.prev_box;
+    bt.lists = w.lists;
+    bt.recs = rec_sets(w, n);
+    bt.status = status;
+    const CodecOut out{(float2 *)xys, radii, conics, num_tiles_hit, colors};
+    const int bs = per_gaussian_block(n);
+    const dim3 grid((n + bs - 1) / bs > 0 ? (n + bs - 1) / bs : 1), block(bs);
+    const long long last = need > 0 ? need - 1 : 0;
+    const CodecView vw = view ? *view : CodecView{0.f, 0.f, 1.f};
+#define GI2D_CODEC_DECODE(KIND, VIEW)                                                                                  \
+    hipLaunchKernelGGL((codec_decode_bin_kernel<KIND, VIEW>), grid, block, 0, (hipStream_t)st, n, lay, side,            \
+                       (const uint32_t *)payload, last, clip_coe, (float)w_, (float)h, tiles_x, tiles_y, radius_clip,  \
+                       out, bt, vw)
+    if (view) {
+        if (kind == kCovariance) GI2D_CODEC_DECODE(kCovariance, true);
+        else GI2D_CODEC_DECODE(kScaleRot, true);
+    } else {
+        if (kind == kCovariance) GI2D_CODEC_DECODE(kCovariance, false);
+        else GI2D_CODEC_DECODE(kScaleRot, false);
+    }
+#undef GI2D_CODEC_DECODE
+    return check_launch(what);
+}
 
 extern "C" {
 
@@ -150,56 +238,39 @@ int gi2d_codec_decode_bin(int kind, int n, int xy_bits, int p0_bits, int p1_bits
                           unsigned h, unsigned w_, int tiles_x, int tiles_y, float radius_clip, float *xys,
                           int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors, void *ws,
                           size_t ws_bytes, int32_t *status, gi2d_stream_t st) {
-    CodecLayout lay;
-    if (!codec_layout("codec decode", kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
-    if (n < 0 || tiles_x < 0 || tiles_y < 0) {
-        set_error("codec decode: negative size");
+    return codec_decode_launch("codec decode", nullptr, kind, n, xy_bits, p0_bits, p1_bits, color_bits, side_host,
+                               payload, payload_bytes, clip_coe, h, w_, tiles_x, tiles_y, radius_clip, xys, radii,
+                               conics, num_tiles_hit, colors, ws, ws_bytes, status, st);
+}
+
+int gi2d_codec_decode_bin_view(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                               const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
+                               unsigned h, unsigned w_, float x0, float y0, float scale, unsigned out_h, unsigned out_w,
+                               int tiles_x, int tiles_y, float radius_clip, float *xys, int32_t *radii, float *conics,
+                               int32_t *num_tiles_hit, float *colors, void *ws, size_t ws_bytes, int32_t *status,
+                               gi2d_stream_t st) {
+    // the conditions on a view, in double on the fp32 values the kernel receives
+    const char *why = nullptr;
+    if (!std::isfinite(scale) || scale < 1.f || scale > (float)GI2D_CODEC_VIEW_MAX_SCALE)
+        why = "codec decode view: scale must be finite and in 1 .. 64 (a reduced view overfills the 256 entries of a tile)";
+    else if (!std::isfinite(x0) || !std::isfinite(y0) || x0 < 0.f || y0 < 0.f)
+        why = "codec decode view: the origin must be finite and not negative";
+    else if (out_w < 1 || out_h < 1)
+        why = "codec decode view: empty output";
+    else if ((double)x0 + (double)out_w / (double)scale > (double)w_ ||
+             (double)y0 + (double)out_h / (double)scale > (double)h)
+        why = "codec decode view: the window reaches beyond the picture";
+    else if (((unsigned long long)out_w + GI2D_TILE - 1) / GI2D_TILE * (((unsigned long long)out_h + GI2D_TILE - 1) / GI2D_TILE) >
+             (unsigned long long)GI2D_CODEC_VIEW_MAX_TILES)
+        why = "codec decode view: more than 16384 tiles in one view (compose larger outputs from several views)";
+    if (why) {
+        set_error(why);
         return GI2D_ERR_INVALID_ARGUMENT;
     }
-    const long long need = codec_dwords(n, lay.record_bits);
-    if (payload_bytes < (size_t)need * 4) {
-        set_error("codec decode: payload shorter than 4 * ceil(N * R / 32) bytes");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    if (!side_host || !status || !ws || (n > 0 && (!payload || ((uintptr_t)payload & 3)))) {
-        set_error("codec decode: null or misaligned pointer");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    if ((long long)tiles_x * GI2D_TILE < (long long)w_ || (long long)tiles_y * GI2D_TILE < (long long)h) {
-        set_error("codec decode: tile grid does not cover the image");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    if ((long long)tiles_x * tiles_y * GI2D_FAST_LROW > 0x7fffffffLL || (long long)n * GI2D_FAST_S > 0x7fffffffLL ||
-        tiles_x > 0xffff || tiles_y > 0xffff) {
-        set_error("codec decode: problem too large for 32-bit slot indices");
-        return GI2D_ERR_UNSUPPORTED;
-    }
-    if (ws_bytes < carve_fast(nullptr, n, tiles_x * tiles_y).bytes) {
-        set_error("codec decode: workspace too small");
-        return GI2D_ERR_WORKSPACE_TOO_SMALL;
-    }
-    CodecSide side;
-    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) side.scale[k] = side_host[2 * k], side.beta[k] = side_host[2 * k + 1];
-    FastWs w = carve_fast(ws, n, tiles_x * tiles_y);
-    BinTarget bt;
-    bt.colors = bt.opacities = nullptr;  // colour comes from the record, opacity is 1
-    bt.prev_box = w.prev_box;
-    bt.lists = w.lists;
-    bt.recs = rec_sets(w, n);
-    bt.status = status;
-    const CodecOut out{(float2 *)xys, radii, conics, num_tiles_hit, colors};
-    const int bs = per_gaussian_block(n);
-    const dim3 grid((n + bs - 1) / bs > 0 ? (n + bs - 1) / bs : 1), block(bs);
-    const long long last = need > 0 ? need - 1 : 0;
-    if (kind == kCovariance)
-        hipLaunchKernelGGL(codec_decode_bin_kernel<kCovariance>, grid, block, 0, (hipStream_t)st, n, lay, side,
-                           (const uint32_t *)payload, last, clip_coe, (float)w_, (float)h, tiles_x, tiles_y,
-                           radius_clip, out, bt);
-    else
-        hipLaunchKernelGGL(codec_decode_bin_kernel<kScaleRot>, grid, block, 0, (hipStream_t)st, n, lay, side,
-                           (const uint32_t *)payload, last, clip_coe, (float)w_, (float)h, tiles_x, tiles_y,
-                           radius_clip, out, bt);
-    return check_launch("codec decode");
+    const CodecView vw{x0, y0, scale};
+    return codec_decode_launch("codec decode view", &vw, kind, n, xy_bits, p0_bits, p1_bits, color_bits, side_host,
+                               payload, payload_bytes, clip_coe, out_h, out_w, tiles_x, tiles_y, radius_clip * scale, xys,
+                               radii, conics, num_tiles_hit, colors, ws, ws_bytes, status, st);
 }
 
 }  // extern "C"

@@ -603,7 +603,19 @@ int gi2d_quant_half(size_t count, const float *x, float *y, gi2d_stream_t stream
  *                          gi2d_fast_rasterize_forward behind it; a tile row overflow is reported by that tile pass and
  *                          answered with gi2d_bin_gaussians + the plain ops).  xys f32[N,2], radii i32[N], conics
  *                          f32[N,3], num_tiles_hit i32[N], colors f32[N,3]: optional outputs (NULL = not wanted).
- *                          No load address depends on the payload's content, and none lies beyond payload_bytes. */
+ *                          No load address depends on the payload's content, and none lies beyond payload_bytes.
+ *   gi2d_codec_decode_bin_view  the same launch for a WINDOW on the fitted function: output pixel (row i,
+ *                          column j) of an out_height x out_width picture samples source position (x0 + j / scale,
+ *                          y0 + i / scale).  Every dequantised gaussian is transformed in separate fp32 operations --
+ *                          x' = (x - x0) * scale, y' = (y - y0) * scale; covariance entries * (scale * scale), or the two
+ *                          scales of kind 2 * scale (rotation, colour, clip_coe untouched) -- and projected and binned at
+ *                          the window's size with radius_clip * scale (radius_clip: the stream's own value).  tiles_x /
+ *                          tiles_y, the workspace and the gi2d_fast_rasterize_forward call behind it are those of the
+ *                          WINDOW; the optional outputs report the transformed geometry.  Refused (-1) before anything
+ *                          is launched: scale not finite or outside 1 .. 64; x0, y0 not finite or negative; an empty
+ *                          output; x0 + out_width / scale > img_width or y0 + out_height / scale > img_height; more
+ *                          than 16384 tiles (ceil(out_width / 16) * ceil(out_height / 16)).  The identity window
+ *                          (0, 0, 1, img_height, img_width) gives the bits of gi2d_codec_decode_bin. */
 size_t gi2d_codec_payload_bytes(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits);
 int gi2d_codec_pack(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
                     const float *code_xy, const float *code_p0, const float *code_p1, const float *code_rgb,
@@ -613,6 +625,12 @@ int gi2d_codec_decode_bin(int kind, int num_points, int xy_bits, int p0_bits, in
                           unsigned img_height, unsigned img_width, int tiles_x, int tiles_y, float radius_clip,
                           float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors,
                           void *workspace, size_t workspace_bytes, int32_t *status, gi2d_stream_t stream);
+int gi2d_codec_decode_bin_view(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                               const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
+                               unsigned img_height, unsigned img_width, float x0, float y0, float scale,
+                               unsigned out_height, unsigned out_width, int tiles_x, int tiles_y, float radius_clip,
+                               float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors,
+                               void *workspace, size_t workspace_bytes, int32_t *status, gi2d_stream_t stream);
 
 /* ------------------------------------------------------------------ rANS payload (payload coding 1 of format 1)
  * The records of coding 0, entropy coded: gaussianimage_plus_amd/codec.py owns the container (tag "rANS", model section,

@@ -12,7 +12,14 @@ building the model tables).  A region is a host clock around `reps` back-to-back
 ends in a device synchronise: no event pairs inside it (a pair costs the queue about 5 us per dispatch).
 The gaussians are those of a short quantised fit, so tile populations are a real picture's.
 
+--view x0,y0,w,h,scale (repeatable) adds, per view, the time of Decoder.decode(stream, view=...) on the uploaded stream
+(`view_us`) next to the only route there is without views (`route_us`): the full decode followed by a crop in torch
+(scale 1: the same pixels where no tile box cuts a gaussian) or by torch.nn.functional.interpolate of the crop (bilinear,
+the window's source pixels -> the view's size: pixels interpolated, not the function evaluated).  Same regions, same
+discipline.
+
     python tools/decode_time.py [--reps 200] [--coding fixed|rans] [--chunk-log2 10 8 12] [--trace]
+                                [--view 256,128,256,256,1 --view 256,128,1024,1024,4 --view 0,0,1536,1024,2]
 --trace decodes a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for
 the per-kernel split (profiles/decode_kernel_stats.csv).
 """
@@ -56,7 +63,26 @@ def median_us(fn, reps, regions=5):
             fn()
         torch.cuda.synchronize()
         out.append((time.perf_counter() - t0) / reps * 1e6)
-    return statistics.median(out), min(out), max(out)
+    return statistics.median(out), min(out), max(out), out
+
+
+def parse_view(text):
+    x0, y0, w, h, scale = text.split(",")
+    return codec.View(float(x0), float(y0), int(w), int(h), float(scale))
+
+
+def route_without_views(dec, up, full, view):
+    """What a caller without views does for the same window: full decode, then crop (and resample) in torch."""
+    x0, y0 = int(view.x0), int(view.y0)
+    sw, sh = max(1, round(view.width / view.scale)), max(1, round(view.height / view.scale))
+
+    def run():
+        crop = dec.decode(up, out=full)[y0:y0 + sh, x0:x0 + sw]
+        if view.scale == 1.0:
+            return crop.contiguous()
+        return torch.nn.functional.interpolate(crop.permute(2, 0, 1)[None], size=(view.height, view.width),
+                                               mode="bilinear", align_corners=False)
+    return run
 
 
 def main():
@@ -67,6 +93,7 @@ def main():
     ap.add_argument("--coding", choices=["fixed", "rans"], default="fixed")
     ap.add_argument("--chunk-log2", type=int, nargs="+", default=[codec.DEFAULT_CHUNK_LOG2])
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--view", type=parse_view, action="append", default=[], metavar="x0,y0,w,h,scale")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_time.py needs the GPU"
     res = {"tool": "decode_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
@@ -98,9 +125,10 @@ def main():
                "psnr_db": round(10 * torch.log10(1.0 / torch.nn.functional.mse_loss(want, gt)).item(), 3)}
         for key, fn in (("device", lambda: dec.decode(up, out=out)), ("bytes", lambda: dec.decode(blob, out=out)),
                         ("legacy", lambda: fit.decompress_wo_ec(enc))):
-            med, lo, hi = median_us(fn, a.reps)
+            med, lo, hi, regions = median_us(fn, a.reps)
             row[key + "_us"] = round(med, 2)
             row[key + "_us_range"] = [round(lo, 2), round(hi, 2)]
+            row[key + "_us_regions"] = [round(r, 2) for r in regions]
         row["decodes_per_second_device"] = round(1e6 / row["device_us"], 1)
         if coded:
             row["bpp_wc_estimate"] = round(fit.analysis_wo_ec(enc, entropy_estimate=True)["bpp_wc"], 5)
@@ -110,10 +138,25 @@ def main():
             r = {"stream_bytes": len(c), "bpp": round(ci["bpp"], 5), "ratio": round(len(c) / len(blob), 4),
                  "field_modes": ci["field_modes"], "chunks": ci["chunks"]}
             for key, fn in (("device", lambda: dec.decode(cup, out=out)), ("bytes", lambda: dec.decode(c, out=out))):
-                med, lo, hi = median_us(fn, a.reps)
+                med, lo, hi, _ = median_us(fn, a.reps)
                 r[key + "_us"] = round(med, 2)
                 r[key + "_us_range"] = [round(lo, 2), round(hi, 2)]
             row["rans"][str(k)] = r
+        if a.view:
+            row["views"] = []
+        for v in a.view:
+            vout = torch.empty(v.height, v.width, 3, device="cuda:0")
+            g = dec.decode_geometry(up, view=v)
+            assert torch.equal(dec.decode(up, out=vout, view=v), g["image"])
+            r = {"view": [v.x0, v.y0, v.width, v.height, v.scale], "tiles": v.tiles[0] * v.tiles[1],
+                 "gaussians_in_view": int((g["num_tiles_hit"] > 0).sum())}
+            for key, fn in (("view", lambda: dec.decode(up, out=vout, view=v)),
+                            ("route", route_without_views(dec, up, out, v))):
+                med, lo, hi, regions = median_us(fn, a.reps)
+                r[key + "_us"] = round(med, 2)
+                r[key + "_us_range"] = [round(lo, 2), round(hi, 2)]
+                r[key + "_us_regions"] = [round(x, 2) for x in regions]
+            row["views"].append(r)
         res["sizes"][str(n)] = row
     if not a.trace:
         print(json.dumps(res))
