@@ -18,7 +18,8 @@ A decode is three native launches on buffers the Decoder owns -- gi2d_fast_works
 (record -> dequantise -> project -> bin, csrc/gi2d_codec.hip) and gi2d_fast_rasterize_forward -- plus the clamp to
 [0, 1] that NativeFitter.decompress_wo_ec applies; the picture is bit-identical to that method's.  The tile-overflow
 status is looked at ONCE, after the image has been enqueued; an overflowing stream (more than 1024 candidate gaussians in
-one 16x16 tile) is rendered again through the capacity-free ops, so a valid stream always decodes.
+one 16x16 tile) is rendered again through the capacity-free ops, so a valid stream always decodes.  Every decode call
+(decode, decode_many, decode_views, decode_geometry) is one host driver, Decoder._run, on a list of pictures.
 
 A view is a decoder argument, never stream content.  Output pixel (row i, column j) samples the fitted
 function at source position (x0 + j / scale, y0 + i / scale): every dequantised gaussian is moved and scaled into the
@@ -50,7 +51,7 @@ import dataclasses
 import math
 import struct
 import zlib
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, List, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -459,6 +460,10 @@ def recode(blob, coding: str, device: Union[str, torch.device] = "cuda:0", chunk
                     h["side"], data, coding)
 
 
+def _tiles(pixels: int) -> int:
+    return (pixels + _TILE - 1) // _TILE
+
+
 MAX_VIEW_SCALE = 64.0
 MAX_VIEW_TILES = 16384  # the fast-path workspace grows with the tiles; a viewer composes larger outputs from several views
 
@@ -504,7 +509,7 @@ class View:
 
     @property
     def tiles(self):
-        return (self.width + _TILE - 1) // _TILE, (self.height + _TILE - 1) // _TILE
+        return _tiles(self.width), _tiles(self.height)
 
     @classmethod
     def full(cls, header) -> "View":
@@ -524,8 +529,10 @@ class View:
         return float(np.float32(header["radius_clip"]) * np.float32(self.scale))
 
 
-def _checked_view(view, h) -> Optional[View]:
+def _checked_view(view, h, required: bool = False) -> Optional[View]:
     if view is None:
+        if required:
+            raise ValueError("decode_views: every entry is a codec.View")
         return None
     if not isinstance(view, View):
         raise ValueError("view: a codec.View (or None for the whole picture at its own size)")
@@ -560,7 +567,27 @@ def view_parameters(kind: int, values, view: View):
     return out
 
 
+class _Picture(NamedTuple):
+    """What one launch sequence draws, derived once (_picture) from (header, view or None)."""
+    header: Dict[str, object]
+    view: Optional[View]  # None: the whole picture at its own size, through the full decode's entry
+    width: int
+    height: int
+    tx: int
+    ty: int
+
+    @property
+    def radius_clip(self) -> float:  # what the capacity-free ops of the fallback are given
+        return self.header["radius_clip"] if self.view is None else self.view.radius_clip(self.header)
+
+
+def _picture(h, view: Optional[View]) -> _Picture:
+    w, hh = (h["width"], h["height"]) if view is None else (view.width, view.height)
+    return _Picture(h, view, w, hh, _tiles(w), _tiles(hh))
+
+
 _STATUS_WORDS = 8
+_STATUS_ROW = 4 * _STATUS_WORDS  # bytes; a launch is given the device address of its row, a plain integer
 
 
 def _staged(blob, h) -> List[np.ndarray]:
@@ -582,7 +609,7 @@ class DeviceStream:
 class Decoder:
     """Decodes streams on one device.  Payload staging, the fast-path workspace and the status words are kept between
     calls and regrown only when a stream needs more; nothing of one stream survives into the next (the workspace is
-    re-initialised on the device at the start of every decode)."""
+    re-initialised on the device at the start of every picture)."""
 
     def __init__(self, device: Union[str, torch.device] = "cuda:0"):
         self.dev = torch.device(device)
@@ -595,32 +622,38 @@ class Decoder:
         self._payload = torch.empty(0, dtype=torch.uint8, device=self.dev)
         self._host = torch.empty(0, dtype=torch.uint8).pin_memory()
         self._expanded = torch.empty(0, dtype=torch.uint8, device=self.dev)  # coding-0 payloads of the rANS streams
-        # per stream: words 0..3 belong to the binning step and the tile pass (1 = overflow), word 4 to the rANS expansion
+        # per picture: words 0..3 belong to the binning step and the tile pass (1 = overflow), word 4 to the rANS expansion
         self._status = torch.zeros(1, _STATUS_WORDS, dtype=torch.int32, device=self.dev)
         self._token = 0  # the expansion raises word 4 to the token of its decode: no reset launch between decodes
         self.expansions = 0  # rANS payloads expanded so far (gi2d_codec_rans_expand launches)
         self._background = torch.ones(3, dtype=torch.float32, device=self.dev)  # the rasterize wrappers' default
 
     # ---------------------------------------------------------------------------------------------- buffers
-    def _reserve_workspace(self, h, view: Optional[View] = None) -> None:
-        tx, ty = view.tiles if view is not None else ((h["width"] + _TILE - 1) // _TILE, (h["height"] + _TILE - 1) // _TILE)
-        need = int(_lib.load().gi2d_fast_workspace_bytes(h["num_points"], tx, ty))
+    def _reserve_workspace(self, pictures: Sequence[_Picture]) -> None:
+        size = _lib.load().gi2d_fast_workspace_bytes
+        need = max(int(size(p.header["num_points"], p.tx, p.ty)) for p in pictures)
         if self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
 
-    def _stage(self, blobs, headers) -> List[torch.Tensor]:
-        """Payloads of `blobs` -> device (one pinned staging buffer, one asynchronous copy per stream)."""
-        offs, total, parts = [], 0, [_staged(blob, h) for blob, h in zip(blobs, headers)]
+    def _stage(self, streams, headers) -> List[torch.Tensor]:
+        """Payloads of `streams` on the device: a DeviceStream's own, host bytes through one pinned staging buffer (one
+        asynchronous copy per stream)."""
+        offs, total = [], 0
+        parts = [None if isinstance(s, DeviceStream) else _staged(s, h) for s, h in zip(streams, headers)]
         for p in parts:
             offs.append(total)
-            total += (sum(len(x) for x in p) + 255) & ~255
+            if p is not None:
+                total += (sum(len(x) for x in p) + 255) & ~255
         if self._host.numel() < total:
             self._host = torch.empty(total, dtype=torch.uint8).pin_memory()
         if self._payload.numel() < total:
             self._payload = torch.empty(total, dtype=torch.uint8, device=self.dev)
-        host = self._host.numpy()
+        host = self._host.numpy() if total else None
         out = []
-        for p, o in zip(parts, offs):
+        for s, p, o in zip(streams, parts, offs):
+            if p is None:
+                out.append(s.payload)
+                continue
             nb = 0
             for x in p:
                 host[o + nb:o + nb + len(x)] = x
@@ -635,17 +668,16 @@ class Decoder:
         h = _parse(blob)
         return DeviceStream(h, torch.from_numpy(np.concatenate(_staged(blob, h))).to(self.dev))
 
-    def _expand(self, h, payload: torch.Tensor, status: torch.Tensor, fixed: Optional[torch.Tensor]) -> torch.Tensor:
-        """rANS payload (+ tables) on the device -> its coding-0 payload in `fixed` (gi2d_codec_rans_expand)."""
-        nb, nf = h["payload_bytes"], h["fixed_payload_bytes"]
-        if fixed is None:
-            fixed = torch.empty(nf, dtype=torch.uint8, device=self.dev)
+    def _expand(self, h, payload: torch.Tensor, status: int, fixed: torch.Tensor) -> torch.Tensor:
+        """rANS payload (+ tables) on the device -> its coding-0 payload in `fixed` (gi2d_codec_rans_expand); word 4 of
+        the status row at `status` is raised to the token if a coder state does not return to its start value."""
+        nb = h["payload_bytes"]
         at = lambda off: C.c_void_p(payload.data_ptr() + off)
         b = h["bits"]
         _lib.call("gi2d_codec_rans_expand", h["kind"], h["num_points"], b[0], b[1], b[2], b[3], h["chunk_log2"],
                   h["coded_mask"], at(nb), payload.numel() - nb, at(h["directory_offset"]), at(h["data_offset"]),
-                  h["data_bytes"], h["max_chunk_bytes"], C.c_void_p(fixed.data_ptr()), nf,
-                  C.c_void_p(status.data_ptr() + 16), self._token, _stream(self.dev))
+                  h["data_bytes"], h["max_chunk_bytes"], C.c_void_p(fixed.data_ptr()), fixed.numel(),
+                  status + 16, self._token, _stream(self.dev))
         self.expansions += 1
         return fixed
 
@@ -669,25 +701,17 @@ class Decoder:
             return ds.payload.clone()
         with torch.cuda.device(self.dev):
             self._next_token()
-            fixed = self._expand(h, ds.payload, self._status[0], None)
+            fixed = self._expand(h, ds.payload, self._status.data_ptr(),
+                                 torch.empty(h["fixed_payload_bytes"], dtype=torch.uint8, device=self.dev))
             self._check_expanded(int(self._status[0, 4]))
         return fixed
 
     # ---------------------------------------------------------------------------------------------- launches
-    def _enqueue(self, h, payload: torch.Tensor, status: torch.Tensor, out: torch.Tensor, aux=None,
-                 fixed: Optional[torch.Tensor] = None, view: Optional[View] = None) -> None:
-        """(rANS expansion into `fixed` +) workspace reset + decode/bin + forward + clamp on the current stream; no host
-        sync, and no allocation when a rANS stream is given its `fixed` buffer."""
-        if h["coding"] == CODING_RANS:
-            payload = self._expand(h, payload, status, fixed)
-        self._launch(h, payload, status, out, aux, view)
-
-    def _launch(self, h, payload: torch.Tensor, status: torch.Tensor, out: torch.Tensor, aux=None,
-                view: Optional[View] = None) -> None:
-        """Workspace reset + decode/bin + forward + clamp of a coding-0 payload; with a view, at the view's size."""
+    def _launch(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, aux=None) -> None:
+        """Workspace reset + decode/bin + forward + clamp of a coding-0 payload on the current stream, at the picture's
+        size, with the status row at `status`; no host sync and no allocation."""
+        h, view, w, hh, tx, ty = pic
         n = h["num_points"]
-        w, hh = (h["width"], h["height"]) if view is None else (view.width, view.height)
-        tx, ty = (w + _TILE - 1) // _TILE, (hh + _TILE - 1) // _TILE
         b = h["bits"]
         side = (C.c_float * 16)(*h["side"])
         ws, nws = C.c_void_p(self._ws.data_ptr()), self._ws.numel()
@@ -697,66 +721,93 @@ class Decoder:
         if view is None:
             _lib.call("gi2d_codec_decode_bin", h["kind"], n, b[0], b[1], b[2], b[3], side, C.c_void_p(payload.data_ptr()),
                       h["fixed_payload_bytes"], h["clip_coe"], hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3],
-                      a[4], ws, nws, C.c_void_p(status.data_ptr()), st)
+                      a[4], ws, nws, status, st)
         else:
             _lib.call("gi2d_codec_decode_bin_view", h["kind"], n, b[0], b[1], b[2], b[3], side,
                       C.c_void_p(payload.data_ptr()), h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"],
                       view.x0, view.y0, view.scale, hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3], a[4], ws, nws,
-                      C.c_void_p(status.data_ptr()), st)
+                      status, st)
         _lib.call("gi2d_fast_rasterize_forward", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws,
-                  C.c_void_p(status.data_ptr()), None, None, C.c_void_p(out.data_ptr()), st)
+                  status, None, None, C.c_void_p(out.data_ptr()), st)
         out.clamp_(0, 1)
 
-    def _out(self, h, out: Optional[torch.Tensor], view: Optional[View] = None) -> torch.Tensor:
-        shape = (h["height"], h["width"], 3) if view is None else (view.height, view.width, 3)
+    def _out(self, pic: _Picture, out: Optional[torch.Tensor]) -> torch.Tensor:
+        shape = (pic.height, pic.width, 3)
         if out is None:
             return torch.empty(shape, dtype=torch.float32, device=self.dev)
         if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.dev or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {self.dev}")
         return out
 
-    def decode_geometry(self, stream, view: Optional[View] = None) -> Dict[str, torch.Tensor]:
-        """What the decode kernel makes of every gaussian: xys, radii, conics, num_tiles_hit, colors (tests, tools); with
-        a view, the transformed geometry in the view's pixel grid."""
-        ds = stream if isinstance(stream, DeviceStream) else self.upload(stream)
-        h = ds.header
-        view = _checked_view(view, h)
-        with torch.cuda.device(self.dev):
-            self._reserve_workspace(h, view)
-            aux = self._aux(h["num_points"])
-            img = self._out(h, None, view)
-            self._next_token()
-            self._enqueue(h, ds.payload, self._status[0], img, aux, view=view)
-            if h["coding"] == CODING_RANS:
-                self._check_expanded(int(self._status[0, 4]))
-        return dict(zip(("xys", "radii", "conics", "num_tiles_hit", "colors"), aux), image=img)
-
     def _aux(self, n: int):
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)
         i = lambda *s: torch.empty(s, dtype=torch.int32, device=self.dev)
         return [f(n, 2), i(n), f(n, 3), i(n), f(n, 3)]
 
-    def _exact(self, h, payload: torch.Tensor, out: torch.Tensor, view: Optional[View] = None,
-               expanded: bool = False) -> None:
+    def _exact(self, pic: _Picture, fixed: torch.Tensor, out: torch.Tensor) -> None:
         """A tile row overflowed: the same picture through the capacity-free ops (gi2d_bin_gaussians + the plain
-        rasterizer), fed with the decode kernel's per-gaussian outputs (for a view: the transformed geometry, at the
-        view's size and with its radius_clip).  expanded: `payload` is already the coding-0 payload."""
+        rasterizer), fed with the decode kernel's per-gaussian outputs for the coding-0 payload `fixed` (for a view: the
+        transformed geometry, at the view's size and with its radius_clip)."""
         from .gsplat import _raster_common as rc
+        h, w, hh = pic.header, pic.width, pic.height
         n = h["num_points"]
-        w, hh = (h["width"], h["height"]) if view is None else (view.width, view.height)
-        radius_clip = h["radius_clip"] if view is None else view.radius_clip(h)
         aux = self._aux(n)
-        scratch = torch.empty_like(out)
-        if expanded:
-            self._launch(h, payload, self._status[0], scratch, aux, view)
-        else:
-            self._enqueue(h, payload, self._status[0], scratch, aux, view=view)
+        self._launch(pic, fixed, self._status.data_ptr(), torch.empty_like(out), aux)
         xys, radii, conics, _, colors = aux
         tb = rc.tile_bounds_of(hh, w, _TILE, _TILE)
         opacity = torch.ones(n, 1, dtype=torch.float32, device=self.dev)
         img = rc._exact_forward(h["kind"] == KIND_COVARIANCE, xys, radii, conics, colors, opacity, hh, w, tb,
-                                (_TILE, _TILE, 1), (w, hh, 1), self._background, radius_clip, False)[0]
+                                (_TILE, _TILE, 1), (w, hh, 1), self._background, pic.radius_clip, False)[0]
         torch.clamp(img, 0, 1, out=out)
+
+    def _run(self, groups, outs: Optional[Sequence[torch.Tensor]] = None, views_only: bool = False,
+             geometry: bool = False):
+        """The host driver of every decode call -> (images, aux).  groups: [(stream, [view or None, ...])], a picture per
+        entry; `outs`: a tensor per picture, in call order.  Everything is parsed and checked before anything touches
+        the device; a rANS payload is expanded once per group, into its slice of `_expanded` (valid until the next call);
+        every picture has its own status row, and the rows are read in ONE host wait behind the last picture; a picture
+        whose tile row overflowed is then drawn again (_exact).  geometry (one group, one picture): the per-gaussian
+        outputs of the decode kernel are kept, and the picture stays the fast path's own."""
+        who, what = ("decode_views", "view") if views_only else ("decode_many", "stream")
+        streams = [s for s, _ in groups]
+        headers = [s.header if isinstance(s, DeviceStream) else _parse(s) for s in streams]
+        pictures = [_picture(h, _checked_view(v, h, views_only)) for h, (_, views) in zip(headers, groups) for v in views]
+        if outs is not None and len(outs) != len(pictures):
+            raise ValueError(f"{who}: one output tensor per {what}")
+        if not pictures:
+            return [], None
+        with torch.cuda.device(self.dev):
+            payloads = self._stage(streams, headers)
+            if self._status.shape[0] < len(pictures):
+                self._status = torch.zeros(len(pictures), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
+            self._reserve_workspace(pictures)
+            slices, total = [], 0
+            for h in headers:
+                slices.append(total)
+                total += (h["fixed_payload_bytes"] + 255) & ~255 if h["coding"] == CODING_RANS else 0
+            if self._expanded.numel() < total:
+                self._expanded = torch.empty(total, dtype=torch.uint8, device=self.dev)
+            images = [self._out(p, None if outs is None else outs[i]) for i, p in enumerate(pictures)]
+            aux = self._aux(headers[0]["num_points"]) if geometry else None
+            self._next_token()
+            row0 = self._status.data_ptr()
+            coded, fixed = [], []  # rows that carry an expansion's status word; the coding-0 payload of every picture
+            for h, payload, s, (_, views) in zip(headers, payloads, slices, groups):
+                if h["coding"] == CODING_RANS:
+                    coded.append(len(fixed))  # the row of the group's first picture
+                    payload = self._expand(h, payload, row0 + _STATUS_ROW * len(fixed),
+                                           self._expanded[s:s + h["fixed_payload_bytes"]])
+                for _ in views:
+                    row = len(fixed)
+                    self._launch(pictures[row], payload, row0 + _STATUS_ROW * row, images[row], aux)
+                    fixed.append(payload)
+            status = self._status[:len(pictures), 1:5].tolist()  # the one host wait of a call: overflow, .., .., rANS
+            for row in coded:
+                self._check_expanded(status[row][3])
+            for row, (overflow, _, _, _) in enumerate(status):
+                if overflow and not geometry:
+                    self._exact(pictures[row], fixed[row], images[row])
+        return images, aux
 
     # ---------------------------------------------------------------------------------------------- public
     def decode(self, stream, out: Optional[torch.Tensor] = None, view: Optional[View] = None) -> torch.Tensor:
@@ -771,73 +822,19 @@ class Decoder:
         """Several views of ONE stream back to back on the current stream of the device: the payload is staged once, a
         rANS payload expanded once, the workspace reserved for the largest view, and the statuses are read once, at the
         end."""
-        views = list(views)
-        h = stream.header if isinstance(stream, DeviceStream) else _parse(stream)
-        for v in views:  # all checked before any launch
-            if v is None:
-                raise ValueError("decode_views: every entry is a codec.View")
-            _checked_view(v, h)
-        if outs is not None and len(outs) != len(views):
-            raise ValueError("decode_views: one output tensor per view")
-        if not views:
-            return []
-        with torch.cuda.device(self.dev):
-            payload = stream.payload if isinstance(stream, DeviceStream) else self._stage([stream], [h])[0]
-            if self._status.shape[0] < len(views):
-                self._status = torch.zeros(len(views), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
-            for v in views:
-                self._reserve_workspace(h, v)
-            images = [self._out(h, None if outs is None else outs[i], v) for i, v in enumerate(views)]
-            self._next_token()
-            if h["coding"] == CODING_RANS:
-                if self._expanded.numel() < h["fixed_payload_bytes"]:
-                    self._expanded = torch.empty(h["fixed_payload_bytes"], dtype=torch.uint8, device=self.dev)
-                payload = self._expand(h, payload, self._status[0], self._expanded[:h["fixed_payload_bytes"]])
-            for i, v in enumerate(views):
-                self._launch(h, payload, self._status[i], images[i], None, v)
-            status = self._status[:len(views), 1:5].tolist()  # the one host wait: overflow per view, rANS in row 0
-            if h["coding"] == CODING_RANS:
-                self._check_expanded(status[0][3])
-            for i, (overflow, _, _, _) in enumerate(status):
-                if overflow:
-                    self._exact(h, payload, images[i], views[i], expanded=True)
-        return images
+        return self._run([(stream, list(views))], outs, views_only=True)[0]
 
     def decode_many(self, streams, outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
         """Streams decoded back to back on the current stream of the device; the overflow statuses are read once, at the
         end."""
-        streams = list(streams)
-        raw = [i for i, s in enumerate(streams) if not isinstance(s, DeviceStream)]
-        headers = [s.header if isinstance(s, DeviceStream) else _parse(s) for s in streams]  # all checked before any launch
-        if outs is not None and len(outs) != len(streams):
-            raise ValueError("decode_many: one output tensor per stream")
-        with torch.cuda.device(self.dev):
-            payloads = [s.payload if isinstance(s, DeviceStream) else None for s in streams]
-            if raw:
-                for i, p in zip(raw, self._stage([streams[i] for i in raw], [headers[i] for i in raw])):
-                    payloads[i] = p
-            if self._status.shape[0] < len(streams):
-                self._status = torch.zeros(len(streams), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
-            fixed, total = [None] * len(streams), 0
-            for i, h in enumerate(headers):
-                self._reserve_workspace(h)
-                if h["coding"] == CODING_RANS:
-                    fixed[i] = (total, h["fixed_payload_bytes"])
-                    total += (h["fixed_payload_bytes"] + 255) & ~255
-            if self._expanded.numel() < total:
-                self._expanded = torch.empty(total, dtype=torch.uint8, device=self.dev)
-            fixed = [None if f is None else self._expanded[f[0]:f[0] + f[1]] for f in fixed]
-            images = [self._out(h, None if outs is None else outs[i]) for i, h in enumerate(headers)]
-            self._next_token()
-            for i, h in enumerate(headers):
-                self._enqueue(h, payloads[i], self._status[i], images[i], fixed=fixed[i])
-            status = self._status[:len(streams), 1:5].tolist()  # the one host wait of a decode: overflow, .., .., rANS
-            for i, (overflow, _, _, expanded) in enumerate(status):
-                if headers[i]["coding"] == CODING_RANS:
-                    self._check_expanded(expanded)
-                if overflow:
-                    self._exact(headers[i], payloads[i], images[i])
-        return images
+        return self._run([(s, (None,)) for s in streams], outs)[0]
+
+    def decode_geometry(self, stream, view: Optional[View] = None) -> Dict[str, torch.Tensor]:
+        """What the decode kernel makes of every gaussian: xys, radii, conics, num_tiles_hit, colors (tests, tools); with
+        a view, the transformed geometry in the view's pixel grid.  `image` is the fast path's own picture: a crowded
+        tile is not drawn again."""
+        images, aux = self._run([(stream, (view,))], geometry=True)
+        return dict(zip(("xys", "radii", "conics", "num_tiles_hit", "colors"), aux), image=images[0])
 
 
 _decoders: Dict[torch.device, Decoder] = {}

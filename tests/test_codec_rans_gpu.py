@@ -152,8 +152,8 @@ def test_decode_many_mixes_codings_and_a_decoder_is_reused_across_shapes():
         assert torch.equal(dec.decode(s), want)
 
 
-def test_crowded_tile_fallback_takes_a_coded_stream():
-    """More than 1024 candidates in one tile: the capacity-free path is fed from the expanded payload."""
+def crowded_streams():
+    """(fixed, coded): the same 2600 gaussians, more than 1024 of them candidates of one tile."""
     from gaussianimage_plus_amd import codec
     n = 2600
     values = peaked_values(n, 3)
@@ -161,10 +161,35 @@ def test_crowded_tile_fallback_takes_a_coded_stream():
     fixed = fixed_stream(1, COV[1], values)
     coded = codec.recode(fixed, "rans", device=DEV)
     assert codec.info(coded)["coded_mask"] != 0
+    return fixed, coded
+
+
+def test_crowded_tile_fallback_takes_a_coded_stream():
+    """More than 1024 candidates in one tile: the capacity-free path is fed from the expanded payload."""
+    from gaussianimage_plus_amd import codec
+    fixed, coded = crowded_streams()
     dec = codec.Decoder(DEV)
     a, b = dec.decode(coded), dec.decode(fixed)
     assert int(dec._status[0, 1]) != 0, "the stream was meant to overflow a tile row"
     assert torch.equal(a, b)
+
+
+def test_decode_many_falls_back_between_fast_path_pictures():
+    """The fallback at an index other than 0, for a coded stream on the expansion the call already made, with fast-path
+    pictures before, between and behind: every picture is the one a fresh Decoder gives for its stream alone."""
+    from gaussianimage_plus_amd import codec
+    crowded_fixed, crowded_coded = crowded_streams()
+    streams = [fixed_golden("cov"), crowded_coded, golden()["rs_blob"].tobytes(), crowded_fixed]
+    single = [codec.Decoder(DEV).decode(s) for s in streams]
+    dec = codec.Decoder(DEV)
+    many = dec.decode_many(streams)
+    assert [int(w) != 0 for w in dec._status[1:4, 1]] == [True, False, True], "streams 1 and 3 were meant to overflow"
+    for i, (a, b) in enumerate(zip(many, single)):
+        assert torch.equal(a, b), i
+    assert torch.equal(many[1], many[3])
+    # the decoder is as good as new afterwards
+    for s in (golden()["peaked_blob"].tobytes(), fixed_golden("odd")):
+        assert torch.equal(dec.decode(s), codec.Decoder(DEV).decode(s))
 
 
 def test_a_fresh_process_decodes_a_coded_file(tmp_path):

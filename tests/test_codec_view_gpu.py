@@ -282,15 +282,21 @@ def test_decode_views_equals_single_view_decodes(name):
 
 
 # ---------------------------------------------------------------------------------------------------- 5. fallback
+def crowded_view():
+    """(stream, view): more candidates in one tile of the view than a tile row holds."""
+    from gaussianimage_plus_amd import _lib, codec
+    n, W, H = _lib.load().gi2d_fast_tile_capacity() + 500, 64, 48
+    blob = random_stream(CO.KIND_COVARIANCE, (12, 10, 0, 6), n, W, H, 5, spread=0.2)  # all centres within 12.8 x 9.6 px
+    return blob, codec.View(0.5, 0.25, 48, 40, 2.0)
+
+
 def test_crowded_view_decodes_through_the_fallback(oracle):
     """More candidates in one tile of the VIEW than a tile row holds: the view's picture comes from the capacity-free
     ops on the transformed gaussians."""
-    from gaussianimage_plus_amd import _lib, codec
+    from gaussianimage_plus_amd import codec
     import gaussianimage_plus_amd.gsplat as gs
-    cap = _lib.load().gi2d_fast_tile_capacity()
-    n, W, H = cap + 500, 64, 48
-    blob = random_stream(CO.KIND_COVARIANCE, (12, 10, 0, 6), n, W, H, 5, spread=0.2)  # all centres within 12.8 x 9.6 px
-    view = codec.View(0.5, 0.25, 48, 40, 2.0)
+    blob, view = crowded_view()
+    n = codec.info(blob)["num_points"]
     dec = codec.Decoder(DEV)
     got = dec.decode(blob, view=view).clone()
     assert dec.decode_geometry(blob, view=view) is not None and dec._status[0, 1].item() != 0, "the tile row did overflow"
@@ -313,6 +319,28 @@ def test_crowded_view_decodes_through_the_fallback(oracle):
     # the decoder is as good as new afterwards
     small = golden("cov")
     assert torch.equal(dec.decode(small), codec.Decoder(DEV).decode(small))
+
+
+def test_decode_views_falls_back_between_fast_path_views():
+    """A crowded view between two ordinary ones of a coded stream: the fallback draws it from the one expansion of the
+    call, and every view is the one a fresh Decoder gives for it alone."""
+    from gaussianimage_plus_amd import codec
+    blob, crowded = crowded_view()
+    coded = codec.recode(blob, "rans", device=DEV)
+    # the CPU oracle counts 269 and 460 gaussians in the fullest tile of the two ordinary views, 1524 in the crowded one's
+    views = [codec.View(24, 18, 32, 24, 1.0), crowded, codec.View(21.5, 16.25, 47, 35, 2.0)]
+    single = []
+    for v in views:
+        fresh = codec.Decoder(DEV)
+        single.append(fresh.decode(blob, view=v).clone())
+        fresh.decode_geometry(blob, view=v)
+        assert (fresh._status[0, 1].item() != 0) == (v is crowded), "only the middle view was meant to overflow"
+    dec = codec.Decoder(DEV)
+    before = dec.expansions
+    many = dec.decode_views(coded, views)
+    assert dec.expansions == before + 1
+    for v, a, b in zip(views, many, single):
+        assert a.shape == (v.height, v.width, 3) and torch.equal(a, b) and float(a.min()) < 1.0, v
 
 
 # -------------------------------------------------------------------------------------------------- 6. empty view
