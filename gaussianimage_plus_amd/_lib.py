@@ -83,6 +83,12 @@ SIGNATURES.update({
     "gi2d_codec_histogram": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p],
     "gi2d_codec_rans_encode": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _sz, _p, _sz, _p, _p],
     "gi2d_codec_rans_expand": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _p, _sz, _sz, _p, _sz, _p, _i, _p],
+    # ... with differenced position fields (payload coding 2), and position order
+    "gi2d_codec_histogram_delta": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _p],
+    "gi2d_codec_rans_encode_delta": [_i, _i, _i, _i, _i, _i, _i, _u, _u, _p, _sz, _p, _sz, _p, _sz, _p, _p],
+    "gi2d_codec_rans_expand_delta": [_i, _i, _i, _i, _i, _i, _i, _u, _u, _p, _sz, _p, _p, _sz, _sz, _p, _sz, _p, _i, _p],
+    "gi2d_codec_position_keys": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p],
+    "gi2d_codec_gather": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p, _sz, _p],
     # SSIM / MS-SSIM (gaussianimage_plus_amd/metrics.py; the batched entries take struct gi2d_ssim_pair[])
     "gi2d_ssim_forward": [_p, _p, _p, _p, _i, _i, _i, _p, _f, _f, _f, _i, _p, _i, _p, _p, _sz, _p],
     "gi2d_ssim_backward": [_p, _p, _p, _p, _i, _i, _i, _p, _f, _f, _f, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p],

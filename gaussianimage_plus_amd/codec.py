@@ -9,6 +9,8 @@
     codec.save(path, blob); blob = codec.load(path)
     small = codec.encode(fitter, coding="rans")  # the same codes, entropy coded (payload coding 1); decodes the same way
     small = codec.recode(blob, "rans"); codec.recode(small, "fixed") == blob
+    tiny = codec.encode(fitter, coding="rans-delta", order="position")   # gaussians sorted by position, positions coded as
+                                                 # differences (payload coding 2); the sum is the same, its order is not
     v    = codec.View(x0, y0, width, height, scale=4.0)   # a window on the fitted function, magnified (1 <= scale <= 64)
     part = dec.decode(blob, view=v)              # f32 [v.height, v.width, 3]; only the window's tiles are drawn
     parts = dec.decode_views(blob, [v, codec.View.full(codec.info(blob))])
@@ -30,7 +32,7 @@ window's own tile grid, so a view is not pixel for pixel a crop or a resampling 
 Format version 1 (little-endian; INTEGRATION.md "Packed stream" has the record layout):
 
     0  magic "GI2D" | 4 version = 1 | 5 model kind (1 covariance, 2 scale-rot) | 6 payload coding (0 = fixed-length
-       fields, 1 = rANS container, below) | 7 reserved (0) | 8 u32 width, u32 height | 16 u32 N | 20 u8 bits[4]: xy, cov / scaling, rotation (0 for
+       fields, 1 = rANS container, 2 = rANS container with differenced positions, below) | 7 reserved (0) | 8 u32 width, u32 height | 16 u32 N | 20 u8 bits[4]: xy, cov / scaling, rotation (0 for
        covariance), colour | 24 f32 clip_coe, f32 radius_clip | 32 u32 payload bytes | 36 u32 CRC-32 (zlib) of side
        information + payload | 40 side information: (scale, beta) f32 pairs of the 8 fields | 104 payload
 
@@ -39,6 +41,13 @@ width w is split into hi = v >> max(0, w - 8), a symbol of a 12-bit rANS model s
 chunk of 2^k records (k = 8..12) is one wave's work, one coder state per lane over a shared stream of 16-bit words.
 gi2d_codec_rans_expand (csrc/gi2d_rans.hip) turns the chunks back into the coding-0 payload in a buffer the Decoder owns,
 and the launches above run on it unchanged: the picture is that of the coding-0 stream with the same codes.
+
+Payload coding 2 ("rans-delta") is that container under the tag "rANd", and the byte of a table header that coding 1
+keeps 0 names the field's transform: 1 = the symbol of record g is (hi(g) - hi(g - 1)) mod 2^hb, except for the first
+record of a chunk, which keeps hi(g).  Only the two position fields may carry it.  It pays on a stream in POSITION ORDER
+(order="position": the stable sort by the key hi(y) * 2^hb + hi(x), position_order states it in numpy), where the
+differences of y are nearly always 0 and those of x small; the decoder checks no order, an unsorted stream gains nothing
+and the model then picks no differenced field.
 
 Everything in a header is validated on the host before a byte reaches the GPU (ValueError) -- for coding 1 also the tag,
 the field mask, the model section, the chunk directory and every chunk's size against N and the widths -- and the
@@ -65,9 +74,11 @@ SIDE_BYTES = 64
 KIND_COVARIANCE, KIND_SCALE_ROT = 1, 2  # ProjKind numbering of the C ABI
 _KIND_NAMES = {KIND_COVARIANCE: "covariance", KIND_SCALE_ROT: "scale_rot"}
 _HEADER = struct.Struct("<4sBBBBIII4BffII")
-CODING_FIXED, CODING_RANS = 0, 1
-_CODING_NAMES = {CODING_FIXED: "fixed", CODING_RANS: "rans"}
+CODING_FIXED, CODING_RANS, CODING_RANS_DELTA = 0, 1, 2
+_CODING_NAMES = {CODING_FIXED: "fixed", CODING_RANS: "rans", CODING_RANS_DELTA: "rans-delta"}
 RANS_TAG = b"rANS"
+RANS_DELTA_TAG = b"rANd"
+_RANS_TAGS = {CODING_RANS: RANS_TAG, CODING_RANS_DELTA: RANS_DELTA_TAG}
 RANS_VERSION = 1
 RANS_PROB_BITS = 12
 RANS_TOTAL = 1 << RANS_PROB_BITS
@@ -97,7 +108,26 @@ def _coding_id(coding) -> int:
     for cid, name in _CODING_NAMES.items():
         if coding == cid or coding == name:
             return cid
-    raise ValueError(f"payload coding {coding!r}: 'fixed' (0) or 'rans' (1)")
+    raise ValueError(f"payload coding {coding!r}: 'fixed' (0), 'rans' (1) or 'rans-delta' (2)")
+
+
+def _order_id(order, allow_none: bool = False) -> bool:
+    """True for position order."""
+    if order == "position":
+        return True
+    if order == "fit" or (allow_none and order is None):
+        return False
+    raise ValueError(f"order {order!r}: " + ("None (as it is) or 'position'" if allow_none else "'fit' or 'position'"))
+
+
+def position_order(codes_xy, xy_bits: int) -> np.ndarray:
+    """The permutation of position order, on the host: codes_xy integer [N, 2] (the stored x, y of the records, what
+    compress_wo_ec() returns as quant_means) -> int64 [N], record g of the ordered stream is record result[g] of the
+    source.  The key of a record is hi(y) * 2^hb + hi(x) with hi(v) = v >> max(0, xy_bits - 8), hb = min(xy_bits, 8); the
+    order is the STABLE ascending sort by it (ties keep their earlier order)."""
+    xy = np.asarray(codes_xy).astype(np.int64).reshape(-1, 2)
+    lo, hb = max(0, int(xy_bits) - 8), min(int(xy_bits), 8)
+    return np.argsort(((xy[:, 1] >> lo) << hb) | (xy[:, 0] >> lo), kind="stable")
 
 
 # ------------------------------------------------------------------------------------- rANS container (pure host)
@@ -145,6 +175,23 @@ def _normalise(counts: np.ndarray) -> np.ndarray:
     return f
 
 
+def _field_model(c: np.ndarray, k: int, w: int):
+    """Counts of one field's symbols -> (bits of the field when coded: code length + table, first symbol, frequencies),
+    or None where there is nothing to code."""
+    hi_bits = min(int(w), 8)
+    n = int(c.sum())
+    used = np.nonzero(c)[0]
+    if n == 0 or used[-1] >= (1 << hi_bits):
+        if n:
+            raise ValueError(f"rans_model: field {k} of {w} bits has symbols beyond {(1 << hi_bits) - 1}")
+        return None
+    first, a = int(used[0]), int(used[-1] - used[0] + 1)
+    f = _normalise(c[first:first + a])
+    cost_q16 = sum(int(c[first + i]) * ((RANS_PROB_BITS << 16) - _log2_q16(int(f[i]))) for i in range(a) if f[i])
+    entry_bytes = (6 + 2 * a + 3) & ~3
+    return ((cost_q16 + 0xFFFF) >> 16) + 8 * entry_bytes, first, f
+
+
 def rans_model(hist, widths: Sequence[int]):
     """Per-field model of a rANS payload from the counts of the hi parts (hist[k][s], 8 x 256; gi2d_codec_histogram or
     numpy) -> (mask, tables): bit k of `mask` set = field k is entropy coded, tables[k] = (first symbol, frequencies as
@@ -153,35 +200,48 @@ def rans_model(hist, widths: Sequence[int]):
     hist = np.asarray(hist, dtype=np.int64).reshape(8, 256)
     mask, tables = 0, []
     for k, w in enumerate(widths):
-        c = hist[k]
-        hi_bits = min(int(w), 8)
-        n = int(c.sum())
-        used = np.nonzero(c)[0]
         tables.append(None)
-        if n == 0 or used[-1] >= (1 << hi_bits):
-            if n:
-                raise ValueError(f"rans_model: field {k} of {w} bits has symbols beyond {(1 << hi_bits) - 1}")
-            continue
-        first, a = int(used[0]), int(used[-1] - used[0] + 1)
-        f = _normalise(c[first:first + a])
-        cost_q16 = sum(int(c[first + i]) * ((RANS_PROB_BITS << 16) - _log2_q16(int(f[i]))) for i in range(a) if f[i])
-        entry_bytes = (6 + 2 * a + 3) & ~3
-        if ((cost_q16 + 0xFFFF) >> 16) + 8 * entry_bytes < n * hi_bits:
+        m = _field_model(hist[k], k, w)
+        if m is not None and m[0] < int(hist[k].sum()) * min(int(w), 8):
             mask |= 1 << k
-            tables[k] = (first, f)
+            tables[k] = m[1:]
     return mask, tables
 
 
-def _rans_head(n: int, widths: Sequence[int], chunk_log2: int, mask: int, tables) -> bytes:
-    """Container header + model section of a rANS payload."""
+def rans_model_delta(hist, delta_hist, widths: Sequence[int]):
+    """The model of a payload of coding 2 -> (mask, delta_mask, tables).  hist as for rans_model; delta_hist[k][s], k = 0, 1:
+    the counts of the DIFFERENCED symbols of the two position fields (gi2d_codec_histogram_delta or numpy; they depend
+    on the chunk size, the first record of a chunk keeps its hi part).  A position field is stored raw, coded plain or
+    coded differenced, whichever the cost rule of rans_model makes smallest (ties: the earlier of the three); bit k of
+    `delta_mask` set = differenced, and tables[k] is then the table of the differenced symbols.  Fields 2..7: rans_model."""
+    hist = np.asarray(hist, dtype=np.int64).reshape(8, 256)
+    delta_hist = np.asarray(delta_hist, dtype=np.int64).reshape(-1, 256)
+    mask, tables = rans_model(hist, widths)
+    delta_mask = 0
+    for k in (0, 1):
+        n, hi_bits = int(hist[k].sum()), min(int(widths[k]), 8)
+        if int(delta_hist[k].sum()) != n:
+            raise ValueError(f"rans_model_delta: the two histograms of field {k} count different numbers of records")
+        best = n * hi_bits if tables[k] is None else _field_model(hist[k], k, widths[k])[0]  # what rans_model settled for
+        m = _field_model(delta_hist[k], k, widths[k])
+        if m is not None and m[0] < best:
+            mask |= 1 << k
+            delta_mask |= 1 << k
+            tables[k] = m[1:]
+    return mask, delta_mask, tables
+
+
+def _rans_head(n: int, widths: Sequence[int], chunk_log2: int, mask: int, tables, coding: int = CODING_RANS,
+               delta_mask: int = 0) -> bytes:
+    """Container header + model section of a rANS payload (coding 2: its tag, and the transform byte of every table)."""
     model = b""
     for k, w in enumerate(widths):
         if mask >> k & 1:
             first, f = tables[k]
-            entry = struct.pack("<BBHH", max(0, w - 8), 0, first, len(f)) + np.asarray(f, "<u2").tobytes()
+            entry = struct.pack("<BBHH", max(0, w - 8), delta_mask >> k & 1, first, len(f)) + np.asarray(f, "<u2").tobytes()
             model += entry + b"\0" * (-len(entry) % 4)
     chunks = (n + (1 << chunk_log2) - 1) >> chunk_log2
-    return _RANS_HEAD.pack(RANS_TAG, RANS_VERSION, RANS_PROB_BITS, chunk_log2, mask, chunks, len(model)) + model
+    return _RANS_HEAD.pack(_RANS_TAGS[coding], RANS_VERSION, RANS_PROB_BITS, chunk_log2, mask, chunks, len(model)) + model
 
 
 def _rans_device_tables(widths: Sequence[int], mask: int, tables) -> np.ndarray:
@@ -198,13 +258,14 @@ def _rans_device_tables(widths: Sequence[int], mask: int, tables) -> np.ndarray:
     return np.frombuffer(b"".join(out), np.uint8)
 
 
-def _parse_rans(p: memoryview, n: int, widths: Sequence[int]) -> Dict[str, object]:
-    """The container of a rANS payload, checked in full: everything that positions data on the device."""
+def _parse_rans(p: memoryview, n: int, widths: Sequence[int], coding: int = CODING_RANS) -> Dict[str, object]:
+    """The container of a rANS payload, checked in full: everything that positions data on the device.  Coding 2 differs
+    in its tag and in the transform byte of a table header (1 = differenced, fields 0 and 1 only), which coding 1 keeps 0."""
     bad = lambda why: ValueError("GI2D stream: rANS payload: " + why)
     if len(p) < _RANS_HEAD.size:
         raise bad("shorter than its header")
     tag, version, prob, chunk_log2, mask, chunks, model_bytes = _RANS_HEAD.unpack_from(p, 0)
-    if tag != RANS_TAG:
+    if tag != _RANS_TAGS[coding]:
         raise bad("bad tag")
     if version != RANS_VERSION:
         raise bad(f"container version {version} is not supported")
@@ -216,15 +277,18 @@ def _parse_rans(p: memoryview, n: int, widths: Sequence[int]) -> Dict[str, objec
         raise bad("chunk count does not match N")
     if model_bytes % 4 or _RANS_HEAD.size + model_bytes + 4 * (chunks + 1) > len(p):
         raise bad("model section and chunk directory do not fit the payload")
-    pos, end, tables = _RANS_HEAD.size, _RANS_HEAD.size + model_bytes, [None] * 8
+    pos, end, tables, delta_mask = _RANS_HEAD.size, _RANS_HEAD.size + model_bytes, [None] * 8, 0
     for k, w in enumerate(widths):
         if not mask >> k & 1:
             continue
         if pos + 6 > end:
             raise bad(f"the model section has no table for coded field {k}")
-        lo, zero, first, a = struct.unpack_from("<BBHH", p, pos)
-        if lo != max(0, w - 8) or zero != 0 or not 1 <= a <= 256 or first + a > 1 << (w - lo):
+        lo, transform, first, a = struct.unpack_from("<BBHH", p, pos)
+        if transform > (1 if coding == CODING_RANS_DELTA and k < 2 else 0):
+            raise bad(f"transform {transform} of field {k} (1 = differenced: coding 2, fields 0 and 1 only)")
+        if lo != max(0, w - 8) or not 1 <= a <= 256 or first + a > 1 << (w - lo):
             raise bad(f"bad table header of field {k}")
+        delta_mask |= transform << k
         if pos + 6 + 2 * a > end:
             raise bad(f"table of field {k} runs past the model section")
         f = np.frombuffer(p, "<u2", a, pos + 6).astype(np.int64)
@@ -249,8 +313,8 @@ def _parse_rans(p: memoryview, n: int, widths: Sequence[int]) -> Dict[str, objec
     if (sizes < least).any() or (sizes > most).any():
         raise bad("a chunk is shorter than its states and raw section, or longer than its records can make it")
     return dict(chunk_log2=chunk_log2, coded_mask=mask, chunks=chunks, tables=tables, directory_offset=end,
-                data_offset=data_offset, data_bytes=data_bytes, max_chunk_bytes=int(sizes.max()),
-                field_modes=["rans" if mask >> k & 1 else "raw" for k in range(8)])
+                data_offset=data_offset, data_bytes=data_bytes, max_chunk_bytes=int(sizes.max()), delta_mask=delta_mask,
+                field_modes=["rans-delta" if delta_mask >> k & 1 else "rans" if mask >> k & 1 else "raw" for k in range(8)])
 
 
 def _parse(blob) -> Dict[str, object]:
@@ -269,7 +333,8 @@ def _parse(blob) -> Dict[str, object]:
     if kind not in _KIND_NAMES:
         raise ValueError(f"GI2D stream: model kind {kind} has no quantised form (1 covariance, 2 scale-rot)")
     if coding not in _CODING_NAMES:
-        raise ValueError(f"GI2D stream: payload coding {coding} is not supported (0 = fixed-length fields, 1 = rANS)")
+        raise ValueError(f"GI2D stream: payload coding {coding} is not supported (0 = fixed-length fields, 1 = rANS, "
+                         "2 = rANS with differenced positions)")
     if reserved != 0:
         raise ValueError("GI2D stream: reserved header byte is not 0")
     bits = (b0, b1, b2, b3)
@@ -298,16 +363,17 @@ def _parse(blob) -> Dict[str, object]:
              width=width, height=height, num_points=n, bits=bits, clip_coe=clip_coe, radius_clip=radius_clip,
              payload_bytes=nbytes, fixed_payload_bytes=fixed_bytes, crc=crc, side=side,
              record_bits=_record_bits(kind, bits), field_modes=["raw"] * 8)
-    if coding == CODING_RANS:
-        h.update(_parse_rans(memoryview(blob)[HEADER_BYTES + SIDE_BYTES:], n, _widths(kind, bits)))
+    if coding != CODING_FIXED:
+        h.update(_parse_rans(memoryview(blob)[HEADER_BYTES + SIDE_BYTES:], n, _widths(kind, bits), coding))
     return h
 
 
 def info(blob) -> Dict[str, object]:
     """Every header field of a stream plus `payload_bits`, `bpp` (side information + payload: for coding 0 what
     NativeFitter.analysis_wo_ec reports, rounded up to the payload's dword padding; for coding 1 the entropy-coded size
-    with its tables, directory and coder states) and `bpp_with_header`.  `coding_name` is "fixed" or "rans", `field_modes`
-    says per field of a record whether its high bits are entropy coded ("rans") or stored as they are ("raw")."""
+    with its tables, directory and coder states) and `bpp_with_header`.  `coding_name` is "fixed", "rans" or "rans-delta",
+    `field_modes` says per field of a record whether its high bits are entropy coded ("rans"), entropy coded as the
+    difference from the record before ("rans-delta") or stored as they are ("raw")."""
     h = _parse(blob)
     h.pop("tables", None)
     hw = h["width"] * h["height"]
@@ -353,28 +419,76 @@ def pack_codes(kind: int, bits: Sequence[int], code_xy: torch.Tensor, code_p0: t
     return payload
 
 
-def payload_histogram(kind: int, n: int, bits: Sequence[int], payload: torch.Tensor) -> torch.Tensor:
+def payload_histogram(kind: int, n: int, bits: Sequence[int], payload: torch.Tensor, chunk_log2: Optional[int] = None,
+                      delta_mask: int = 0) -> torch.Tensor:
     """Counts of the hi parts (value >> max(0, width - 8)) of the 8 fields of a coding-0 payload on the GPU -> int64
-    [8, 256] on the same device (gi2d_codec_histogram)."""
+    [8, 256] on the same device (gi2d_codec_histogram).  With `chunk_log2`: the symbols of the position fields in
+    `delta_mask` are counted differenced, as coding 2 stores them in chunks of that size (gi2d_codec_histogram_delta)."""
     hist = torch.empty(8, 256, dtype=torch.int32, device=payload.device)
     with torch.cuda.device(payload.device):
-        _lib.call("gi2d_codec_histogram", kind, n, *[int(b) for b in bits], C.c_void_p(payload.data_ptr()),
-                  payload.numel(), C.c_void_p(hist.data_ptr()), _stream(payload.device))
+        if chunk_log2 is None:
+            _lib.call("gi2d_codec_histogram", kind, n, *[int(b) for b in bits], C.c_void_p(payload.data_ptr()),
+                      payload.numel(), C.c_void_p(hist.data_ptr()), _stream(payload.device))
+        else:
+            _lib.call("gi2d_codec_histogram_delta", kind, n, *[int(b) for b in bits], int(chunk_log2), int(delta_mask),
+                      C.c_void_p(payload.data_ptr()), payload.numel(), C.c_void_p(hist.data_ptr()),
+                      _stream(payload.device))
     return hist.long()
 
 
+def position_keys(kind: int, n: int, bits: Sequence[int], payload: torch.Tensor) -> torch.Tensor:
+    """The position keys of the records of a coding-0 payload on the GPU -> int32 [N] (gi2d_codec_position_keys)."""
+    keys = torch.empty(n, dtype=torch.int32, device=payload.device)
+    with torch.cuda.device(payload.device):
+        _lib.call("gi2d_codec_position_keys", kind, n, *[int(b) for b in bits], C.c_void_p(payload.data_ptr()),
+                  payload.numel(), C.c_void_p(keys.data_ptr()), _stream(payload.device))
+    return keys
+
+
+def gather_records(kind: int, n: int, bits: Sequence[int], payload: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
+    """The coding-0 payload whose record g is record perm[g] of `payload` (both on the GPU; perm: N integers, entries
+    clamped to [0, N)) -- gi2d_codec_gather."""
+    if perm.numel() != n or perm.device != payload.device:
+        raise ValueError("gather_records: one index per record, on the payload's device")
+    perm = perm.to(torch.int32).contiguous()
+    out = torch.empty(_payload_bytes(kind, n, bits), dtype=torch.uint8, device=payload.device)
+    with torch.cuda.device(payload.device):
+        _lib.call("gi2d_codec_gather", kind, n, *[int(b) for b in bits], C.c_void_p(payload.data_ptr()), payload.numel(),
+                  C.c_void_p(perm.data_ptr()), C.c_void_p(out.data_ptr()), out.numel(), _stream(payload.device))
+    return out
+
+
+def position_ordered(kind: int, n: int, bits: Sequence[int], payload: torch.Tensor) -> torch.Tensor:
+    """A coding-0 payload on the GPU in position order (position_order): device keys, torch's stable sort, device gather."""
+    perm = torch.sort(position_keys(kind, n, bits, payload), stable=True).indices
+    return gather_records(kind, n, bits, payload, perm)
+
+
 def rans_encode_payload(kind: int, n: int, bits: Sequence[int], payload: torch.Tensor,
-                        chunk_log2: int = DEFAULT_CHUNK_LOG2) -> bytes:
+                        chunk_log2: int = DEFAULT_CHUNK_LOG2, coding: int = CODING_RANS, model=None) -> bytes:
     """Coding-0 payload on the GPU (uint8 tensor) -> the bytes of the rANS payload that carries the same records: device
-    histogram, rans_model on the host, gi2d_codec_rans_encode, the chunks gathered behind their directory."""
+    histogram, rans_model on the host, gi2d_codec_rans_encode, the chunks gathered behind their directory.  coding =
+    CODING_RANS_DELTA: also the histogram of the differenced position symbols, rans_model_delta, and the _delta encoder.
+    model: (mask, delta_mask, tables) to code with instead of the model's own choice (every symbol needs a frequency)."""
     dev = payload.device
     if dev.type != "cuda":
         raise RuntimeError("gaussianimage_plus_amd.codec: the payload must live on the GPU (no CPU fallback)")
     if not 8 <= int(chunk_log2) <= 12:
         raise ValueError("chunk_log2: 8..12 (256 .. 4096 records per chunk)")
     widths, b = _widths(kind, bits), [int(x) for x in bits]
-    mask, tables = rans_model(payload_histogram(kind, n, bits, payload).cpu().numpy(), widths)
-    head = _rans_head(n, widths, chunk_log2, mask, tables)
+    if coding not in _RANS_TAGS:
+        raise ValueError("rans_encode_payload: coding 1 (rans) or 2 (rans-delta)")
+    hist = payload_histogram(kind, n, bits, payload).cpu().numpy() if model is None else None
+    if model is not None:
+        mask, delta_mask, tables = model
+        if delta_mask and coding != CODING_RANS_DELTA:
+            raise ValueError("rans_encode_payload: only coding 2 has differenced fields")
+    elif coding == CODING_RANS_DELTA:
+        mask, delta_mask, tables = rans_model_delta(hist, payload_histogram(kind, n, bits, payload, chunk_log2, 3).cpu().numpy(),
+                                                    widths)
+    else:
+        (mask, tables), delta_mask = rans_model(hist, widths), 0
+    head = _rans_head(n, widths, chunk_log2, mask, tables, coding, delta_mask)
     chunks = (n + (1 << chunk_log2) - 1) >> chunk_log2
     with torch.cuda.device(dev):
         nscratch = int(_lib.load().gi2d_codec_rans_scratch_bytes(kind, n, *b, chunk_log2, mask))
@@ -382,7 +496,9 @@ def rans_encode_payload(kind: int, n: int, bits: Sequence[int], payload: torch.T
         dtab = torch.from_numpy(_rans_device_tables(widths, mask, tables).copy()).to(dev)
         scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
         lengths = torch.empty(chunks, dtype=torch.int32, device=dev)
-        _lib.call("gi2d_codec_rans_encode", kind, n, *b, chunk_log2, mask, C.c_void_p(dtab.data_ptr()), dtab.numel(),
+        entry = (("gi2d_codec_rans_encode_delta", kind, n, *b, chunk_log2, mask, delta_mask) if coding == CODING_RANS_DELTA
+                 else ("gi2d_codec_rans_encode", kind, n, *b, chunk_log2, mask))
+        _lib.call(*entry, C.c_void_p(dtab.data_ptr()), dtab.numel(),
                   C.c_void_p(payload.data_ptr()), payload.numel(), C.c_void_p(scratch.data_ptr()), nscratch,
                   C.c_void_p(lengths.data_ptr()), _stream(dev))
         if bool((lengths < 0).any()):
@@ -405,15 +521,21 @@ def assemble(kind: int, width: int, height: int, n: int, bits: Sequence[int], cl
     return head + side_b + payload
 
 
-def encode(fitter, coding: str = "fixed", chunk_log2: int = DEFAULT_CHUNK_LOG2) -> bytes:
+def encode(fitter, coding: str = "fixed", chunk_log2: int = DEFAULT_CHUNK_LOG2, order: str = "fit") -> bytes:
     """The stream of a quantised fit: fitter.compress_wo_ec(), the device bit-packer, the header; coding="rans" entropy
     codes the packed records on the device (`chunk_log2`: log2 of the records per chunk, 8..12) -- same codes, same
-    picture, fewer bytes.  The gaussians keep
-    the order compress_wo_ec() leaves them in (the rasterizer sums a tile in ascending id order: the order is part of
-    the picture's bits), and the clip values are the ones fitter.decompress_wo_ec() renders with.  This IS one
+    picture, fewer bytes; coding="rans-delta" also codes the position fields as differences from the record before
+    where that is smaller (payload coding 2), which it is in position order.  order="fit" (the default): the gaussians
+    keep the order compress_wo_ec() leaves them in (the rasterizer sums a tile in ascending id order: the order is part of
+    the picture's bits).  order="position": the packed records are put into position order (position_order: keys, a
+    stable sort and a gather on the device, between the packer and the coding step).  The decoded picture is then
+    fitter.decompress_wo_ec() of the encoding PERMUTED by position_order(quant_means, xy_bits), bit for bit; from the
+    fit-order picture it differs in the order of the float32 sums only, as long as no tile holds more than 256 entries (a
+    fuller tile keeps its 256 lowest ids, and the ids are the order).  The clip values are the ones
+    fitter.decompress_wo_ec() renders with.  This IS one
     compress_wo_ec() call, side effects included: gaussians whose quantised covariance is not positive definite leave
     the model, and the log ranges of a LATER compress_wo_ec() are those of the rows that are left."""
-    coding = _coding_id(coding)
+    coding, by_position = _coding_id(coding), _order_id(order)
     if getattr(fitter, "quant", None) is None:
         raise ValueError("codec.encode: the fitter has no quantisers yet (enable_quantize / fit_quantize_schedule first)")
     if fitter.kind not in ("covariance", "scale_rot"):
@@ -440,22 +562,28 @@ def encode(fitter, coding: str = "fixed", chunk_log2: int = DEFAULT_CHUNK_LOG2) 
     side = torch.stack([scale, beta], dim=1).reshape(-1).cpu().tolist()  # (scale, beta) pairs, record order
     n = int(enc["quant_means"].shape[0])
     payload = pack_codes(kind, bits, enc["quant_means"], p0, p1, enc["feature_dc_index"])
-    data = (rans_encode_payload(kind, n, bits, payload, chunk_log2) if coding == CODING_RANS
+    if by_position:
+        payload = position_ordered(kind, n, bits, payload)
+    data = (rans_encode_payload(kind, n, bits, payload, chunk_log2, coding) if coding != CODING_FIXED
             else payload.cpu().numpy().tobytes())
     return assemble(kind, int(fitter.w), int(fitter.h), n, bits, clip_coe, float(fitter.state.radius_clip), side, data,
                     coding)
 
 
-def recode(blob, coding: str, device: Union[str, torch.device] = "cuda:0", chunk_log2: int = DEFAULT_CHUNK_LOG2) -> bytes:
-    """A stream in the other payload coding, without a fitter: the same header fields, side information and integers.
-    recode(recode(b, "rans"), "fixed") == b."""
-    coding = _coding_id(coding)
+def recode(blob, coding: str, device: Union[str, torch.device] = "cuda:0", chunk_log2: int = DEFAULT_CHUNK_LOG2,
+           order: Optional[str] = None) -> bytes:
+    """A stream in another payload coding, without a fitter: the same header fields, side information and integers.
+    recode(recode(b, "rans"), "fixed") == b, and the same with "rans-delta".  order=None keeps the records in the
+    stream's order; order="position" puts them into position order first (encode says what that means for the picture)."""
+    coding, by_position = _coding_id(coding), _order_id(order, allow_none=True)
     h = _parse(blob)
     dec = Decoder(device)
     with torch.cuda.device(dec.dev):
         fixed = dec.fixed_payload(dec.upload(blob))
-        data = (rans_encode_payload(h["kind"], h["num_points"], h["bits"], fixed, chunk_log2) if coding == CODING_RANS
-                else fixed.cpu().numpy().tobytes())
+        if by_position:
+            fixed = position_ordered(h["kind"], h["num_points"], h["bits"], fixed)
+        data = (rans_encode_payload(h["kind"], h["num_points"], h["bits"], fixed, chunk_log2, coding)
+                if coding != CODING_FIXED else fixed.cpu().numpy().tobytes())
     return assemble(h["kind"], h["width"], h["height"], h["num_points"], h["bits"], h["clip_coe"], h["radius_clip"],
                     h["side"], data, coding)
 
@@ -593,7 +721,7 @@ _STATUS_ROW = 4 * _STATUS_WORDS  # bytes; a launch is given the device address o
 def _staged(blob, h) -> List[np.ndarray]:
     """What of a stream goes to the device: its payload and, for a rANS payload, the tables of the coded fields."""
     parts = [np.frombuffer(blob, np.uint8, h["payload_bytes"], HEADER_BYTES + SIDE_BYTES)]
-    if h["coding"] == CODING_RANS:
+    if h["coding"] != CODING_FIXED:
         parts.append(_rans_device_tables(_widths(h["kind"], h["bits"]), h["coded_mask"], h["tables"]))
     return parts
 
@@ -669,13 +797,16 @@ class Decoder:
         return DeviceStream(h, torch.from_numpy(np.concatenate(_staged(blob, h))).to(self.dev))
 
     def _expand(self, h, payload: torch.Tensor, status: int, fixed: torch.Tensor) -> torch.Tensor:
-        """rANS payload (+ tables) on the device -> its coding-0 payload in `fixed` (gi2d_codec_rans_expand); word 4 of
+        """rANS payload (+ tables) on the device -> its coding-0 payload in `fixed` (gi2d_codec_rans_expand, or
+        gi2d_codec_rans_expand_delta for coding 2: the one place of the decoder that tells the two apart); word 4 of
         the status row at `status` is raised to the token if a coder state does not return to its start value."""
         nb = h["payload_bytes"]
         at = lambda off: C.c_void_p(payload.data_ptr() + off)
         b = h["bits"]
-        _lib.call("gi2d_codec_rans_expand", h["kind"], h["num_points"], b[0], b[1], b[2], b[3], h["chunk_log2"],
-                  h["coded_mask"], at(nb), payload.numel() - nb, at(h["directory_offset"]), at(h["data_offset"]),
+        entry = (("gi2d_codec_rans_expand_delta", h["coded_mask"], h["delta_mask"]) if h["coding"] == CODING_RANS_DELTA
+                 else ("gi2d_codec_rans_expand", h["coded_mask"]))
+        _lib.call(entry[0], h["kind"], h["num_points"], b[0], b[1], b[2], b[3], h["chunk_log2"],
+                  *entry[1:], at(nb), payload.numel() - nb, at(h["directory_offset"]), at(h["data_offset"]),
                   h["data_bytes"], h["max_chunk_bytes"], C.c_void_p(fixed.data_ptr()), fixed.numel(),
                   status + 16, self._token, _stream(self.dev))
         self.expansions += 1
@@ -694,7 +825,7 @@ class Decoder:
 
     def fixed_payload(self, stream) -> torch.Tensor:
         """The coding-0 payload of a stream, on the device (a tensor of its own): the stream's own bytes for coding 0,
-        the expansion for coding 1."""
+        the expansion for codings 1 and 2 (the records in the stream's order)."""
         ds = stream if isinstance(stream, DeviceStream) else self.upload(stream)
         h = ds.header
         if h["coding"] == CODING_FIXED:
@@ -784,7 +915,7 @@ class Decoder:
             slices, total = [], 0
             for h in headers:
                 slices.append(total)
-                total += (h["fixed_payload_bytes"] + 255) & ~255 if h["coding"] == CODING_RANS else 0
+                total += (h["fixed_payload_bytes"] + 255) & ~255 if h["coding"] != CODING_FIXED else 0
             if self._expanded.numel() < total:
                 self._expanded = torch.empty(total, dtype=torch.uint8, device=self.dev)
             images = [self._out(p, None if outs is None else outs[i]) for i, p in enumerate(pictures)]
@@ -793,7 +924,7 @@ class Decoder:
             row0 = self._status.data_ptr()
             coded, fixed = [], []  # rows that carry an expansion's status word; the coding-0 payload of every picture
             for h, payload, s, (_, views) in zip(headers, payloads, slices, groups):
-                if h["coding"] == CODING_RANS:
+                if h["coding"] != CODING_FIXED:
                     coded.append(len(fixed))  # the row of the group's first picture
                     payload = self._expand(h, payload, row0 + _STATUS_ROW * len(fixed),
                                            self._expanded[s:s + h["fixed_payload_bytes"]])

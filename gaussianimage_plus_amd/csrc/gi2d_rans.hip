@@ -1,5 +1,6 @@
-// Payload coding 1 of the packed stream: the fixed-length records of coding 0, entropy coded (include/gi2d.h "rANS
-// payload"; the container table is in INTEGRATION.md).
+// Payload codings 1 and 2 of the packed stream: the fixed-length records of coding 0, entropy coded (include/gi2d.h
+// "rANS payload"; the container table is in INTEGRATION.md), and the two kernels that put a coding-0 payload into
+// position order (keys, gather) so that coding 2 has something to gain.
 //
 // A field of width w is split into hi = v >> lo_bits (the symbol, at most 8 bits) and lo (stored raw).  One CHUNK of
 // 2^chunk_log2 records is one wave's work: lane l owns records base + 64 j + l and one 32-bit rANS state (12 probability
@@ -14,6 +15,12 @@
 //              tables in LDS; a chunk (states, raw section, words) is staged into LDS with coalesced loads, so the decode
 //              loop has no global load; 64 records (2 R dwords, dword aligned) are ORed together in LDS and leave as
 //              coalesced dword stores.
+//
+// Coding 2 (the DELTA instantiations; `dmask` bit k = field k, k < 2, is differenced): the symbol of a position field is
+// the difference of its hi part from the previous record's, mod 2^hb; the first record of a chunk keeps its hi part.  The
+// histogram and the encoder also load record g - 1; the expansion undoes the differences with an inclusive wave scan per
+// group of 64 records (both fields in one register, 16 bits apart) plus the carry out of the group before.  DELTA = false
+// never reads `dmask`: the coding-1 instantiations keep the instructions they had.
 //
 // Device tables, per coded field in record order (GI2D_RANS_TABLE_BYTES each, built by the host from the stream's
 // validated model section): u8 symbol of slot [4096] | u16 cumulative frequency of symbol [258] (entries 256, 257 = 4096).
@@ -125,8 +132,10 @@ __device__ __forceinline__ void rans_or_into(uint32_t *area, int area_dwords, in
 }
 
 // ------------------------------------------------------------------------------------------------------ histogram
+template <bool DELTA>
 __global__ __launch_bounds__(256) void rans_histogram_kernel(int n, RansLayout L, const uint32_t *__restrict__ payload,
-                                                             long long last_dword, uint32_t *__restrict__ hist) {
+                                                             long long last_dword, uint32_t *__restrict__ hist,
+                                                             unsigned dmask) {
     __shared__ uint32_t h[GI2D_CODEC_FIELDS * 256];
     const int tid = threadIdx.x;
     for (int i = tid; i < GI2D_CODEC_FIELDS * 256; i += 256) h[i] = 0u;
@@ -134,10 +143,19 @@ __global__ __launch_bounds__(256) void rans_histogram_kernel(int n, RansLayout L
     for (long long g = (long long)blockIdx.x * 256 + tid; g < n; g += (long long)gridDim.x * 256) {
         uint32_t r[4];
         rans_load_record(payload, g, L.rec, last_dword, r);
+        uint32_t prev[2] = {0u, 0u};  // DELTA: hi parts of the position fields of record g - 1 (0 at the start of a chunk)
+        if (DELTA && (g & ((1ll << L.chunk_log2) - 1)) != 0) {
+            uint32_t q[4];
+            rans_load_record(payload, g - 1, L.rec, last_dword, q);
+            prev[0] = codec_take(q, L.rec.width[0]) >> L.lo[0];
+            prev[1] = codec_take(q, L.rec.width[1]) >> L.lo[1];
+        }
 #pragma unroll
         for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
             const uint32_t v = codec_take(r, L.rec.width[k]);
-            atomicAdd(&h[k * 256 + ((v >> L.lo[k]) & 255u)], 1u);
+            uint32_t s = (v >> L.lo[k]) & 255u;
+            if (DELTA && k < 2 && ((dmask >> k) & 1u)) s = (s - prev[k]) & ((1u << (L.rec.width[k] - L.lo[k])) - 1u);
+            atomicAdd(&h[k * 256 + s], 1u);
         }
     }
     __syncthreads();
@@ -155,8 +173,10 @@ struct RansEncodeArgs {
     uint32_t *out;            // chunk c at dword c * stride
     int stride, raw_cap, word_cap;
     uint32_t *lengths;        // bytes of chunk c; 0xffffffff: a symbol of frequency 0 (tables of another payload)
+    unsigned dmask;           // DELTA only: the differenced fields
 };
 
+template <bool DELTA>
 __global__ __launch_bounds__(64) void rans_encode_kernel(RansEncodeArgs a) {
     extern __shared__ __align__(16) uint32_t lds[];
     const int lane = threadIdx.x, c = blockIdx.x;
@@ -186,12 +206,21 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(RansEncodeArgs a) {
             rans_settle(rr, a.L.raw_bits);
             rans_or_into(raw, raw_dw, rl * a.L.raw_bits, rr);
         }
+        uint32_t prev[2] = {0u, 0u};  // DELTA: hi parts of the position fields of the record before (0 for the chunk's first)
+        if (DELTA) {
+            uint32_t q[4];
+            rans_load_record(a.payload, active && rl > 0 ? base + rl - 1 : base, a.L.rec, a.last_dword, q);
+            const uint32_t p0 = codec_take(q, a.L.rec.width[0]) >> a.L.lo[0];
+            const uint32_t p1 = codec_take(q, a.L.rec.width[1]) >> a.L.lo[1];
+            if (rl > 0) prev[0] = p0, prev[1] = p1;
+        }
 #pragma unroll
         for (int k = GI2D_CODEC_FIELDS - 1; k >= 0; --k) {
             if (!((a.L.mask >> k) & 1u)) continue;
             const int t = __popc(a.L.mask & ((1u << k) - 1u));
             const uint16_t *cum = a.tables + t * (GI2D_RANS_TABLE_BYTES / 2) + GI2D_RANS_SLOTS / 2;
-            const uint32_t s = (v[k] >> a.L.lo[k]) & 255u;
+            uint32_t s = (v[k] >> a.L.lo[k]) & 255u;
+            if (DELTA && k < 2 && ((a.dmask >> k) & 1u)) s = (s - prev[k]) & ((1u << (a.L.rec.width[k] - a.L.lo[k])) - 1u);
             const uint32_t c0 = cum[s];
             uint32_t f = (uint32_t)cum[s + 1] - c0;
             if (active && (f == 0u || f > GI2D_RANS_SLOTS)) bad = true;
@@ -236,8 +265,10 @@ struct RansExpandArgs {
     long long out_dwords;
     int32_t *status;         // raised to `token` if an active lane does not end at 2^16
     int token;
+    unsigned dmask;          // DELTA only: the differenced fields
 };
 
+template <bool DELTA>
 __global__ __launch_bounds__(256) void rans_expand_kernel(RansExpandArgs a) {
     extern __shared__ __align__(16) uint32_t lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
@@ -269,6 +300,9 @@ __global__ __launch_bounds__(256) void rans_expand_kernel(RansExpandArgs a) {
     const unsigned long long below = lanemask_lt();
     const long long out_base = (base * R) >> 5;
     const int J = (records + 63) >> 6;
+    // DELTA: the hi parts of the position fields of the record before this group, field 0 in bits 0..15, field 1 in
+    // bits 16..31 (0 in front of the chunk's first record); wave uniform
+    uint32_t carry = 0u;
     for (int j = 0; j < J; ++j) {
         const int rl = j * 64 + lane;
         const bool active = rl < records;
@@ -282,6 +316,7 @@ __global__ __launch_bounds__(256) void rans_expand_kernel(RansExpandArgs a) {
             for (int q = 0; q < 4; ++q) r[q] = __builtin_amdgcn_alignbit(w[q + 1], w[q], (uint32_t)bit0 & 31u);
         }
         uint32_t rec[4] = {0u, 0u, 0u, 0u};
+        uint32_t diff = 0u, v0 = 0u;  // DELTA: the lane's differenced symbols, packed like `carry`; field 0 waits for field 1
 #pragma unroll
         for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
             const int w = a.L.rec.width[k];
@@ -300,8 +335,30 @@ __global__ __launch_bounds__(256) void rans_expand_kernel(RansExpandArgs a) {
                 wpos += __popcll(m);
                 x = need ? (xn << 16) | word : active ? xn : x;
                 v = (s << a.L.lo[k]) | codec_take(r, a.L.lo[k]);
+                // lanes past the last record add nothing to the scan
+                if (DELTA && k < 2 && ((a.dmask >> k) & 1u) && active) diff |= s << (16 * k);
             } else {
                 v = codec_take(r, w);
+            }
+            if (DELTA && k == 0) {
+                v0 = v;
+                continue;
+            }
+            if (DELTA && k == 1) {
+                // inclusive scan of the 64 lanes' symbols (a sum stays below 64 * 255 + 255: the halves do not meet), the
+                // carry of the group before, every hi part mod 2^hb; outside any lane-divergent branch
+                uint32_t t = diff;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t up = __shfl_up(t, d);
+                    t += lane >= d ? up : 0u;
+                }
+                t += carry;
+                const uint32_t hbm = (1u << (w - a.L.lo[1])) - 1u, lom = (1u << a.L.lo[1]) - 1u;  // fields 0 and 1: one width
+                carry = (uint32_t)__builtin_amdgcn_readlane((int)t, 63) & (hbm | (hbm << 16));
+                if (a.dmask & 1u) v0 = ((t & hbm) << a.L.lo[0]) | (v0 & lom);
+                if (a.dmask & 2u) v = (((t >> 16) & hbm) << a.L.lo[1]) | (v & lom);
+                rans_push(rec, v0 & ((1u << w) - 1u), w);
             }
             rans_push(rec, v & ((1u << w) - 1u), w);
         }
@@ -320,6 +377,49 @@ __global__ __launch_bounds__(256) void rans_expand_kernel(RansExpandArgs a) {
     if (__ballot(bad) != 0ull && lane == 0) atomicMax(a.status, a.token);
 }
 
+// ------------------------------------------------------------------------------------------------- position order
+// The position key of every record of a coding-0 payload: hi(y) * 2^hb + hi(x), the hi parts as the coder splits them.
+__global__ __launch_bounds__(256) void codec_position_keys_kernel(int n, RansLayout L, const uint32_t *__restrict__ payload,
+                                                                  long long last_dword, int32_t *__restrict__ keys) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    uint32_t r[4];
+    rans_load_record(payload, g, L.rec, last_dword, r);
+    const uint32_t x = codec_take(r, L.rec.width[0]) >> L.lo[0];
+    const uint32_t y = codec_take(r, L.rec.width[1]) >> L.lo[1];
+    keys[g] = (int32_t)((y << (L.rec.width[0] - L.lo[0])) | x);
+}
+
+// Record g of `out` = record perm[g] of `payload`.  Built like the pack kernel: the 256 records of a workgroup are
+// exactly 8 R dwords and start dword aligned, so they are ORed together in LDS and leave as coalesced dword stores --
+// every output dword, the zero padding behind the last record included, is written exactly once.
+__global__ __launch_bounds__(GI2D_CODEC_PACK_BLOCK) void codec_gather_kernel(
+    int n, CodecLayout lay, const uint32_t *__restrict__ payload, long long last_dword, const int32_t *__restrict__ perm,
+    uint32_t *__restrict__ out, long long total_dwords) {
+    __shared__ uint32_t grp[GI2D_CODEC_PACK_BLOCK * GI2D_CODEC_MAX_RECORD / 32];
+    const int tid = threadIdx.x;
+    const int group_dwords = GI2D_CODEC_PACK_BLOCK / 32 * lay.record_bits;
+    for (int i = tid; i < group_dwords; i += GI2D_CODEC_PACK_BLOCK) grp[i] = 0u;
+    __syncthreads();
+    const long long g = (long long)blockIdx.x * GI2D_CODEC_PACK_BLOCK + tid;
+    if (g < n) {
+        const int src = min(max(perm[g], 0), n - 1);  // an index from a caller's array: clamped before it forms an address
+        uint32_t r[4];
+        rans_load_record(payload, src, lay, last_dword, r);
+        // the load brings the start of the next record along: keep R bits
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int keep = lay.record_bits - 32 * j;
+            r[j] = keep >= 32 ? r[j] : keep > 0 ? r[j] & ((1u << keep) - 1u) : 0u;
+        }
+        rans_or_into(grp, group_dwords, tid * lay.record_bits, r);
+    }
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * group_dwords;
+    for (int i = tid; i < group_dwords; i += GI2D_CODEC_PACK_BLOCK)
+        if (base + i < total_dwords) out[base + i] = grp[i];
+}
+
 // A launch that needs more than 64 KB of LDS asks for it first (a CU has 160 KB).
 template <typename K>
 static bool rans_reserve_lds(const char *what, K kernel, size_t bytes) {
@@ -331,6 +431,125 @@ static bool rans_reserve_lds(const char *what, K kernel, size_t bytes) {
         return false;
     }
     return true;
+}
+
+static int rans_fail(const char *what, const char *why, int rc) {
+    set_error((std::string(what) + ": " + why).c_str());
+    return rc;
+}
+// Only the position fields can be differenced, and a differenced field is a coded field.
+static bool rans_delta_mask_ok(const char *what, unsigned coded_mask, unsigned delta_mask) {
+    if ((delta_mask & ~3u) || (delta_mask & ~coded_mask)) {
+        rans_fail(what, "only the coded fields among 0 and 1 can be differenced", GI2D_ERR_INVALID_ARGUMENT);
+        return false;
+    }
+    return true;
+}
+
+// The entries of coding 1 and coding 2 share their checks and launches; delta_mask = 0 takes the coding-1 kernels.
+static int rans_histogram(const char *what, int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                          int chunk_log2, unsigned delta_mask, const void *payload, size_t payload_bytes, uint32_t *hist,
+                          gi2d_stream_t st) {
+    RansLayout L;
+    if (!rans_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, 0u, L)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (!rans_delta_mask_ok(what, 3u, delta_mask)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 0) return rans_fail(what, "negative size", GI2D_ERR_INVALID_ARGUMENT);
+    const long long need = codec_dwords(n, L.rec.record_bits);
+    if (payload_bytes < (size_t)need * 4)
+        return rans_fail(what, "payload shorter than 4 * ceil(N * R / 32) bytes", GI2D_ERR_INVALID_ARGUMENT);
+    if (!hist || ((uintptr_t)hist & 3) || (n > 0 && (!payload || ((uintptr_t)payload & 3))))
+        return rans_fail(what, "null or misaligned pointer", GI2D_ERR_INVALID_ARGUMENT);
+    hipError_t e = hipMemsetAsync(hist, 0, GI2D_CODEC_FIELDS * 256 * sizeof(uint32_t), (hipStream_t)st);
+    if (e != hipSuccess) return (int)e;
+    if (n == 0) return GI2D_OK;
+    const int groups = (n + 255) / 256;
+    const dim3 grid(groups < 256 ? groups : 256), block(256);
+    if (delta_mask)
+        hipLaunchKernelGGL(rans_histogram_kernel<true>, grid, block, 0, (hipStream_t)st, n, L, (const uint32_t *)payload,
+                           need - 1, hist, delta_mask);
+    else
+        hipLaunchKernelGGL(rans_histogram_kernel<false>, grid, block, 0, (hipStream_t)st, n, L, (const uint32_t *)payload,
+                           need - 1, hist, 0u);
+    return check_launch(what);
+}
+
+static int rans_encode(const char *what, int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                       int chunk_log2, unsigned coded_mask, unsigned delta_mask, const void *tables, size_t tables_bytes,
+                       const void *payload, size_t payload_bytes, void *scratch, size_t scratch_bytes, uint32_t *lengths,
+                       gi2d_stream_t st) {
+    RansLayout L;
+    if (!rans_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask, L))
+        return GI2D_ERR_INVALID_ARGUMENT;
+    if (!rans_delta_mask_ok(what, coded_mask, delta_mask)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 1) return rans_fail(what, "no gaussians", GI2D_ERR_INVALID_ARGUMENT);
+    const long long need = codec_dwords(n, L.rec.record_bits);
+    const int chunks = rans_chunks(n, chunk_log2), stride = rans_chunk_cap(L);
+    if (payload_bytes < (size_t)need * 4 || tables_bytes != (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES)
+        return rans_fail(what, "payload shorter than 4 * ceil(N * R / 32) bytes, or tables not one per coded field",
+                         GI2D_ERR_INVALID_ARGUMENT);
+    if (scratch_bytes < (size_t)chunks * stride * 4)
+        return rans_fail(what, "scratch smaller than gi2d_codec_rans_scratch_bytes", GI2D_ERR_WORKSPACE_TOO_SMALL);
+    if (!payload || !scratch || !lengths || (L.ncoded && !tables) || (((uintptr_t)payload | (uintptr_t)scratch |
+                                                                       (uintptr_t)lengths | (uintptr_t)tables) & 3))
+        return rans_fail(what, "null or misaligned pointer", GI2D_ERR_INVALID_ARGUMENT);
+    RansEncodeArgs a;
+    a.L = L, a.n = n, a.payload = (const uint32_t *)payload, a.last_dword = need - 1;
+    a.tables = (const uint16_t *)tables, a.out = (uint32_t *)scratch, a.stride = stride;
+    a.raw_cap = rans_raw_cap(L), a.word_cap = rans_word_cap(L), a.lengths = lengths, a.dmask = delta_mask;
+    const size_t lds = (size_t)a.raw_cap * 4 + (size_t)a.word_cap * 2 + 16;
+    if (delta_mask) {
+        if (!rans_reserve_lds(what, rans_encode_kernel<true>, lds)) return GI2D_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(rans_encode_kernel<true>, dim3(chunks), dim3(64), lds, (hipStream_t)st, a);
+    } else {
+        if (!rans_reserve_lds(what, rans_encode_kernel<false>, lds)) return GI2D_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(rans_encode_kernel<false>, dim3(chunks), dim3(64), lds, (hipStream_t)st, a);
+    }
+    return check_launch(what);
+}
+
+static int rans_expand(const char *what, int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                       int chunk_log2, unsigned coded_mask, unsigned delta_mask, const void *tables, size_t tables_bytes,
+                       const void *directory, const void *chunk_data, size_t chunk_data_bytes, size_t max_chunk_bytes,
+                       void *payload, size_t payload_bytes, int32_t *status, int token, gi2d_stream_t st) {
+    RansLayout L;
+    if (!rans_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask, L))
+        return GI2D_ERR_INVALID_ARGUMENT;
+    if (!rans_delta_mask_ok(what, coded_mask, delta_mask)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 1) return rans_fail(what, "no gaussians", GI2D_ERR_INVALID_ARGUMENT);
+    const long long need = codec_dwords(n, L.rec.record_bits);
+    const int chunks = rans_chunks(n, chunk_log2);
+    if (payload_bytes < (size_t)need * 4 || tables_bytes != (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES)
+        return rans_fail(what, "output shorter than 4 * ceil(N * R / 32) bytes, or tables not one per coded field",
+                         GI2D_ERR_INVALID_ARGUMENT);
+    // every chunk holds its states and raw section; none is longer than the largest the coder can make
+    const int full = 64 + rans_raw_cap(L);
+    const int tail_records = n - ((chunks - 1) << chunk_log2);
+    const int smallest = chunks > 1 ? full : 64 + (tail_records * L.raw_bits + 31) / 32;
+    if ((max_chunk_bytes & 3) || max_chunk_bytes < (size_t)smallest * 4 || max_chunk_bytes > (size_t)rans_chunk_cap(L) * 4 ||
+        (chunk_data_bytes & 3) || chunk_data_bytes > 0xffffffffull || chunk_data_bytes < max_chunk_bytes)
+        return rans_fail(what, "chunk sizes do not fit N, the field widths and the chunk size", GI2D_ERR_INVALID_ARGUMENT);
+    if (!directory || !chunk_data || !payload || !status || (L.ncoded && !tables) ||
+        (((uintptr_t)directory | (uintptr_t)chunk_data | (uintptr_t)payload | (uintptr_t)status | (uintptr_t)tables) & 3))
+        return rans_fail(what, "null or misaligned pointer", GI2D_ERR_INVALID_ARGUMENT);
+    RansExpandArgs a;
+    a.L = L, a.n = n, a.chunks = chunks, a.tables = (const uint32_t *)tables, a.dir = (const uint32_t *)directory;
+    a.data = (const uint32_t *)chunk_data, a.data_dwords = (uint32_t)(chunk_data_bytes / 4);
+    a.in_cap = (int)(max_chunk_bytes / 4), a.out = (uint32_t *)payload, a.out_dwords = need;
+    a.status = status, a.token = token, a.dmask = delta_mask;
+    const size_t table_b = (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES;
+    const size_t wave_b = ((size_t)a.in_cap + 2 * L.rec.record_bits) * 4;
+    int waves = 4;
+    while (waves > 1 && (table_b + waves * wave_b > GI2D_RANS_STATIC_LDS || waves > chunks)) waves >>= 1;
+    const size_t lds = table_b + waves * wave_b;
+    const dim3 grid((chunks + waves - 1) / waves), block(64 * waves);
+    if (delta_mask) {
+        if (!rans_reserve_lds(what, rans_expand_kernel<true>, lds)) return GI2D_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(rans_expand_kernel<true>, grid, block, lds, (hipStream_t)st, a);
+    } else {
+        if (!rans_reserve_lds(what, rans_expand_kernel<false>, lds)) return GI2D_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(rans_expand_kernel<false>, grid, block, lds, (hipStream_t)st, a);
+    }
+    return check_launch(what);
 }
 
 }  // namespace gi2d
@@ -350,111 +569,86 @@ size_t gi2d_codec_rans_scratch_bytes(int kind, int n, int xy_bits, int p0_bits, 
 
 int gi2d_codec_histogram(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, const void *payload,
                          size_t payload_bytes, uint32_t *hist, gi2d_stream_t st) {
-    RansLayout L;
-    if (!rans_layout("codec histogram", kind, xy_bits, p0_bits, p1_bits, color_bits, 8, 0u, L))
-        return GI2D_ERR_INVALID_ARGUMENT;
-    if (n < 0) {
-        set_error("codec histogram: negative size");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    const long long need = codec_dwords(n, L.rec.record_bits);
-    if (payload_bytes < (size_t)need * 4) {
-        set_error("codec histogram: payload shorter than 4 * ceil(N * R / 32) bytes");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    if (!hist || ((uintptr_t)hist & 3) || (n > 0 && (!payload || ((uintptr_t)payload & 3)))) {
-        set_error("codec histogram: null or misaligned pointer");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    hipError_t e = hipMemsetAsync(hist, 0, GI2D_CODEC_FIELDS * 256 * sizeof(uint32_t), (hipStream_t)st);
-    if (e != hipSuccess) return (int)e;
-    if (n == 0) return GI2D_OK;
-    const int groups = (n + 255) / 256;
-    hipLaunchKernelGGL(rans_histogram_kernel, dim3(groups < 256 ? groups : 256), dim3(256), 0, (hipStream_t)st, n, L,
-                       (const uint32_t *)payload, need - 1, hist);
-    return check_launch("codec histogram");
+    return rans_histogram("codec histogram", kind, n, xy_bits, p0_bits, p1_bits, color_bits, 8, 0u, payload,
+                          payload_bytes, hist, st);
+}
+
+int gi2d_codec_histogram_delta(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, int chunk_log2,
+                               unsigned delta_mask, const void *payload, size_t payload_bytes, uint32_t *hist,
+                               gi2d_stream_t st) {
+    return rans_histogram("codec histogram delta", kind, n, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, delta_mask,
+                          payload, payload_bytes, hist, st);
 }
 
 int gi2d_codec_rans_encode(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, int chunk_log2,
                            unsigned coded_mask, const void *tables, size_t tables_bytes, const void *payload,
                            size_t payload_bytes, void *scratch, size_t scratch_bytes, uint32_t *lengths,
                            gi2d_stream_t st) {
-    RansLayout L;
-    if (!rans_layout("codec rans encode", kind, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask, L))
-        return GI2D_ERR_INVALID_ARGUMENT;
-    if (n < 1) {
-        set_error("codec rans encode: no gaussians");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    const long long need = codec_dwords(n, L.rec.record_bits);
-    const int chunks = rans_chunks(n, chunk_log2), stride = rans_chunk_cap(L);
-    if (payload_bytes < (size_t)need * 4 || tables_bytes != (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES) {
-        set_error("codec rans encode: payload shorter than 4 * ceil(N * R / 32) bytes, or tables not one per coded field");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    if (scratch_bytes < (size_t)chunks * stride * 4) {
-        set_error("codec rans encode: scratch smaller than gi2d_codec_rans_scratch_bytes");
-        return GI2D_ERR_WORKSPACE_TOO_SMALL;
-    }
-    if (!payload || !scratch || !lengths || (L.ncoded && !tables) || (((uintptr_t)payload | (uintptr_t)scratch |
-                                                                       (uintptr_t)lengths | (uintptr_t)tables) & 3)) {
-        set_error("codec rans encode: null or misaligned pointer");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    RansEncodeArgs a;
-    a.L = L, a.n = n, a.payload = (const uint32_t *)payload, a.last_dword = need - 1;
-    a.tables = (const uint16_t *)tables, a.out = (uint32_t *)scratch, a.stride = stride;
-    a.raw_cap = rans_raw_cap(L), a.word_cap = rans_word_cap(L), a.lengths = lengths;
-    const size_t lds = (size_t)a.raw_cap * 4 + (size_t)a.word_cap * 2 + 16;
-    if (!rans_reserve_lds("codec rans encode", rans_encode_kernel, lds)) return GI2D_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(rans_encode_kernel, dim3(chunks), dim3(64), lds, (hipStream_t)st, a);
-    return check_launch("codec rans encode");
+    return rans_encode("codec rans encode", kind, n, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask, 0u,
+                       tables, tables_bytes, payload, payload_bytes, scratch, scratch_bytes, lengths, st);
+}
+
+int gi2d_codec_rans_encode_delta(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, int chunk_log2,
+                                 unsigned coded_mask, unsigned delta_mask, const void *tables, size_t tables_bytes,
+                                 const void *payload, size_t payload_bytes, void *scratch, size_t scratch_bytes,
+                                 uint32_t *lengths, gi2d_stream_t st) {
+    return rans_encode("codec rans encode delta", kind, n, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask,
+                       delta_mask, tables, tables_bytes, payload, payload_bytes, scratch, scratch_bytes, lengths, st);
 }
 
 int gi2d_codec_rans_expand(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, int chunk_log2,
                            unsigned coded_mask, const void *tables, size_t tables_bytes, const void *directory,
                            const void *chunk_data, size_t chunk_data_bytes, size_t max_chunk_bytes, void *payload,
                            size_t payload_bytes, int32_t *status, int token, gi2d_stream_t st) {
+    return rans_expand("codec rans expand", kind, n, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask, 0u,
+                       tables, tables_bytes, directory, chunk_data, chunk_data_bytes, max_chunk_bytes, payload,
+                       payload_bytes, status, token, st);
+}
+
+int gi2d_codec_rans_expand_delta(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, int chunk_log2,
+                                 unsigned coded_mask, unsigned delta_mask, const void *tables, size_t tables_bytes,
+                                 const void *directory, const void *chunk_data, size_t chunk_data_bytes,
+                                 size_t max_chunk_bytes, void *payload, size_t payload_bytes, int32_t *status, int token,
+                                 gi2d_stream_t st) {
+    return rans_expand("codec rans expand delta", kind, n, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask,
+                       delta_mask, tables, tables_bytes, directory, chunk_data, chunk_data_bytes, max_chunk_bytes,
+                       payload, payload_bytes, status, token, st);
+}
+
+int gi2d_codec_position_keys(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, const void *payload,
+                             size_t payload_bytes, int32_t *keys, gi2d_stream_t st) {
+    const char *what = "codec position keys";
     RansLayout L;
-    if (!rans_layout("codec rans expand", kind, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask, L))
-        return GI2D_ERR_INVALID_ARGUMENT;
-    if (n < 1) {
-        set_error("codec rans expand: no gaussians");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
+    if (!rans_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, 8, 0u, L)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 0) return rans_fail(what, "negative size", GI2D_ERR_INVALID_ARGUMENT);
     const long long need = codec_dwords(n, L.rec.record_bits);
-    const int chunks = rans_chunks(n, chunk_log2);
-    if (payload_bytes < (size_t)need * 4 || tables_bytes != (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES) {
-        set_error("codec rans expand: output shorter than 4 * ceil(N * R / 32) bytes, or tables not one per coded field");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    // every chunk holds its states and raw section; none is longer than the largest the coder can make
-    const int full = 64 + rans_raw_cap(L);
-    const int tail_records = n - ((chunks - 1) << chunk_log2);
-    const int smallest = chunks > 1 ? full : 64 + (tail_records * L.raw_bits + 31) / 32;
-    if ((max_chunk_bytes & 3) || max_chunk_bytes < (size_t)smallest * 4 || max_chunk_bytes > (size_t)rans_chunk_cap(L) * 4 ||
-        (chunk_data_bytes & 3) || chunk_data_bytes > 0xffffffffull || chunk_data_bytes < max_chunk_bytes) {
-        set_error("codec rans expand: chunk sizes do not fit N, the field widths and the chunk size");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    if (!directory || !chunk_data || !payload || !status || (L.ncoded && !tables) ||
-        (((uintptr_t)directory | (uintptr_t)chunk_data | (uintptr_t)payload | (uintptr_t)status | (uintptr_t)tables) & 3)) {
-        set_error("codec rans expand: null or misaligned pointer");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    RansExpandArgs a;
-    a.L = L, a.n = n, a.chunks = chunks, a.tables = (const uint32_t *)tables, a.dir = (const uint32_t *)directory;
-    a.data = (const uint32_t *)chunk_data, a.data_dwords = (uint32_t)(chunk_data_bytes / 4);
-    a.in_cap = (int)(max_chunk_bytes / 4), a.out = (uint32_t *)payload, a.out_dwords = need;
-    a.status = status, a.token = token;
-    const size_t table_b = (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES;
-    const size_t wave_b = ((size_t)a.in_cap + 2 * L.rec.record_bits) * 4;
-    int waves = 4;
-    while (waves > 1 && (table_b + waves * wave_b > GI2D_RANS_STATIC_LDS || waves > chunks)) waves >>= 1;
-    const size_t lds = table_b + waves * wave_b;
-    if (!rans_reserve_lds("codec rans expand", rans_expand_kernel, lds)) return GI2D_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(rans_expand_kernel, dim3((chunks + waves - 1) / waves), dim3(64 * waves), lds, (hipStream_t)st, a);
-    return check_launch("codec rans expand");
+    if (payload_bytes < (size_t)need * 4)
+        return rans_fail(what, "payload shorter than 4 * ceil(N * R / 32) bytes", GI2D_ERR_INVALID_ARGUMENT);
+    if (n == 0) return GI2D_OK;
+    if (!payload || !keys || (((uintptr_t)payload | (uintptr_t)keys) & 3))
+        return rans_fail(what, "null or misaligned pointer", GI2D_ERR_INVALID_ARGUMENT);
+    hipLaunchKernelGGL(codec_position_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)st, n, L,
+                       (const uint32_t *)payload, need - 1, keys);
+    return check_launch(what);
+}
+
+int gi2d_codec_gather(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, const void *payload,
+                      size_t payload_bytes, const int32_t *perm, void *out, size_t out_bytes, gi2d_stream_t st) {
+    const char *what = "codec gather";
+    CodecLayout lay;
+    if (!codec_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 0) return rans_fail(what, "negative size", GI2D_ERR_INVALID_ARGUMENT);
+    const long long need = codec_dwords(n, lay.record_bits);
+    if (payload_bytes < (size_t)need * 4 || out_bytes < (size_t)need * 4)
+        return rans_fail(what, "payload or output shorter than 4 * ceil(N * R / 32) bytes", GI2D_ERR_INVALID_ARGUMENT);
+    if (n == 0) return GI2D_OK;
+    if (!payload || !perm || !out || payload == out ||
+        (((uintptr_t)payload | (uintptr_t)perm | (uintptr_t)out) & 3))
+        return rans_fail(what, "null or misaligned pointer, or the output is the input", GI2D_ERR_INVALID_ARGUMENT);
+    hipLaunchKernelGGL(codec_gather_kernel, dim3((n + GI2D_CODEC_PACK_BLOCK - 1) / GI2D_CODEC_PACK_BLOCK),
+                       dim3(GI2D_CODEC_PACK_BLOCK), 0, (hipStream_t)st, n, lay, (const uint32_t *)payload, need - 1, perm,
+                       (uint32_t *)out, need);
+    return check_launch(what);
 }
 
 }  // extern "C"

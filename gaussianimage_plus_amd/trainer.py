@@ -752,11 +752,13 @@ class NativeFitter:
             out["bpp_wc"] = out["position_bpp"] + out["cholesky_bpp_wc"] + out["feature_dc_bpp_wc"]
         return out
 
-    def encode(self, coding: str = "fixed") -> bytes:
+    def encode(self, coding: str = "fixed", order: str = "fit") -> bytes:
         """The packed stream of the quantised model (gaussianimage_plus_amd/codec.py): codec.decode() turns it back into
-        the picture decompress_wo_ec() renders, in any process.  coding="rans": the same codes entropy coded."""
+        the picture decompress_wo_ec() renders, in any process.  coding="rans": the same codes entropy coded;
+        coding="rans-delta", order="position": the gaussians in position order, their positions coded as differences
+        (codec.encode says what the order means for the picture)."""
         from . import codec
-        return codec.encode(self, coding=coding)
+        return codec.encode(self, coding=coding, order=order)
 
     # ------------------------------------------------------------------ rotation-scale codec
     def _compress_wo_ec_rs(self) -> Dict[str, torch.Tensor]:

@@ -632,7 +632,7 @@ int gi2d_codec_decode_bin_view(int kind, int num_points, int xy_bits, int p0_bit
                                float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors,
                                void *workspace, size_t workspace_bytes, int32_t *status, gi2d_stream_t stream);
 
-/* ------------------------------------------------------------------ rANS payload (payload coding 1 of format 1)
+/* ------------------------------------------------------------------ rANS payload (payload codings 1 and 2 of format 1)
  * The records of coding 0, entropy coded: gaussianimage_plus_amd/codec.py owns the container (tag "rANS", model section,
  * chunk directory, chunk data; INTEGRATION.md has the table) and validates all of it on the host.  A field of width w is
  * split into hi = v >> lo_bits (lo_bits = max(0, w - 8); the symbol) and lo (raw); coded_mask bit k = field k (record
@@ -653,6 +653,20 @@ int gi2d_codec_decode_bin_view(int kind, int num_points, int xy_bits, int p0_bit
  *                           is not what an encoder wrote; callers pass a token larger than any before.  Offsets, lengths,
  *                           slots, symbols and word positions read from the stream are clamped or masked on the device:
  *                           no content reaches beyond chunk_data, the tables or the output.
+ *
+ * Payload coding 2 (tag "rANd") is the same container with DIFFERENCED position fields: delta_mask bit k (k = 0, 1 only,
+ * and only where coded_mask has the bit) = the symbol of field k is (hi(g) - hi(g - 1)) mod 2^hb, hb = min(w, 8), except for
+ * the first record of a chunk, whose symbol is hi(g); lo bits, states, words and sizes are those of coding 1.  The _delta
+ * entries are the entries above plus delta_mask (and chunk_log2 for the histogram, whose counts then depend on where the
+ * chunks start); delta_mask = 0 gives the results of the entries above.  The expansion undoes the differences with a scan
+ * across the 64 lanes of a wave; it checks no order -- the transform is a bijection on payloads.
+ *
+ * Position order (what makes coding 2 worth it): the position key of a record is hi(y) * 2^hb + hi(x); the caller sorts the
+ * keys (stable) and gathers.
+ *   gi2d_codec_position_keys  coding-0 payload -> keys i32[N] (device).
+ *   gi2d_codec_gather         coding-0 payload + perm i32[N] (device) -> out, the coding-0 payload whose record g is the
+ *                             source's record perm[g] (entries clamped to [0, N)); every dword of out written once, the
+ *                             padding included; out must not be the input, out_bytes >= 4 * ceil(N * R / 32).
  * Every entry checks its arguments before it launches anything. */
 size_t gi2d_codec_rans_scratch_bytes(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
                                      int chunk_log2, unsigned coded_mask);
@@ -667,6 +681,23 @@ int gi2d_codec_rans_expand(int kind, int num_points, int xy_bits, int p0_bits, i
                            const void *directory, const void *chunk_data, size_t chunk_data_bytes,
                            size_t max_chunk_bytes, void *payload, size_t payload_bytes, int32_t *status, int token,
                            gi2d_stream_t stream);
+int gi2d_codec_histogram_delta(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                               int chunk_log2, unsigned delta_mask, const void *payload, size_t payload_bytes,
+                               uint32_t *hist, gi2d_stream_t stream);
+int gi2d_codec_rans_encode_delta(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                                 int chunk_log2, unsigned coded_mask, unsigned delta_mask, const void *tables,
+                                 size_t tables_bytes, const void *payload, size_t payload_bytes, void *scratch,
+                                 size_t scratch_bytes, uint32_t *lengths, gi2d_stream_t stream);
+int gi2d_codec_rans_expand_delta(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                                 int chunk_log2, unsigned coded_mask, unsigned delta_mask, const void *tables,
+                                 size_t tables_bytes, const void *directory, const void *chunk_data,
+                                 size_t chunk_data_bytes, size_t max_chunk_bytes, void *payload, size_t payload_bytes,
+                                 int32_t *status, int token, gi2d_stream_t stream);
+int gi2d_codec_position_keys(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                             const void *payload, size_t payload_bytes, int32_t *keys, gi2d_stream_t stream);
+int gi2d_codec_gather(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                      const void *payload, size_t payload_bytes, const int32_t *perm, void *out, size_t out_bytes,
+                      gi2d_stream_t stream);
 
 /* ------------------------------------------------------------------ structural similarity (SSIM, MS-SSIM)
  * The reference's second quality number and the structural terms of its losses (train.py:190 ms_ssim(render, gt,

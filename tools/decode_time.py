@@ -12,13 +12,19 @@ building the model tables).  A region is a host clock around `reps` back-to-back
 ends in a device synchronise: no event pairs inside it (a pair costs the queue about 5 us per dispatch).
 The gaussians are those of a short quantised fit, so tile populations are a real picture's.
 
+--coding rans-delta adds `orders`: per --order (fit, position) the fixed, rans and rans-delta (payload coding 2) streams
+of the same fit in that order -- bytes, decode times with the payload on the device and from host bytes, and
+`expand_us`, the expansion kernel alone (back-to-back launches into one buffer) -- plus, for position order, the largest
+pixel difference from the fit-order picture and both PSNRs.
+
 --view x0,y0,w,h,scale (repeatable) adds, per view, the time of Decoder.decode(stream, view=...) on the uploaded stream
 (`view_us`) next to the only route there is without views (`route_us`): the full decode followed by a crop in torch
 (scale 1: the same pixels where no tile box cuts a gaussian) or by torch.nn.functional.interpolate of the crop (bilinear,
 the window's source pixels -> the view's size: pixels interpolated, not the function evaluated).  Same regions, same
 discipline.
 
-    python tools/decode_time.py [--reps 200] [--coding fixed|rans] [--chunk-log2 10 8 12] [--trace]
+    python tools/decode_time.py [--reps 200] [--coding fixed|rans|rans-delta] [--order fit position]
+                                [--chunk-log2 10 8 12] [--trace]
                                 [--view 256,128,256,256,1 --view 256,128,1024,1024,4 --view 0,0,1536,1024,2]
 --trace decodes a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for
 the per-kernel split (profiles/decode_kernel_stats.csv).
@@ -66,6 +72,45 @@ def median_us(fn, reps, regions=5):
     return statistics.median(out), min(out), max(out), out
 
 
+def timed(row, key, fn, reps):
+    med, lo, hi, regions = median_us(fn, reps)
+    row[key + "_us"] = round(med, 2)
+    row[key + "_us_range"] = [round(lo, 2), round(hi, 2)]
+    row[key + "_us_regions"] = [round(r, 2) for r in regions]
+
+
+def orders_block(a, fit, gt, dec, blob, out):
+    """The fixed, rans and rans-delta streams of one fit per record order."""
+    psnr = lambda x: round(10 * torch.log10(1.0 / torch.nn.functional.mse_loss(x, gt)).item(), 4)
+    in_fit = dec.decode(blob).clone()
+    block = {}
+    for order in a.order:
+        fixed = blob if order == "fit" else codec.recode(blob, "fixed", order="position")
+        want = dec.decode(fixed).clone()
+        entry = {"psnr_db": psnr(want), "streams": {}}
+        if order == "position":
+            entry["max_abs_difference_from_fit_order"] = float((want - in_fit).abs().max())
+            entry["psnr_db_fit_order"] = psnr(in_fit)
+        streams = {"fixed": fixed}
+        for k in a.chunk_log2:
+            streams[f"rans/{k}"] = codec.recode(fixed, "rans", chunk_log2=k)
+            streams[f"rans-delta/{k}"] = codec.recode(fixed, "rans-delta", chunk_log2=k)
+        for name, c in streams.items():
+            assert torch.equal(dec.decode(c), want) and codec.recode(c, "fixed") == fixed
+            ci, cup = codec.info(c), dec.upload(c)
+            r = {"stream_bytes": len(c), "bpp": round(ci["bpp"], 5), "ratio_to_fixed": round(len(c) / len(fixed), 4),
+                 "field_modes": ci["field_modes"]}
+            timed(r, "device", lambda: dec.decode(cup, out=out), a.reps)
+            timed(r, "bytes", lambda: dec.decode(c, out=out), a.reps)
+            if name != "fixed":
+                buf = torch.empty(ci["fixed_payload_bytes"], dtype=torch.uint8, device="cuda:0")
+                dec._next_token()
+                timed(r, "expand", lambda: dec._expand(cup.header, cup.payload, dec._status.data_ptr(), buf), a.reps)
+            entry["streams"][name] = r
+        block[order] = entry
+    return block
+
+
 def parse_view(text):
     x0, y0, w, h, scale = text.split(",")
     return codec.View(float(x0), float(y0), int(w), int(h), float(scale))
@@ -90,7 +135,8 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--sizes", type=int, nargs="+", default=[5000, 50000])
-    ap.add_argument("--coding", choices=["fixed", "rans"], default="fixed")
+    ap.add_argument("--coding", choices=["fixed", "rans", "rans-delta"], default="fixed")
+    ap.add_argument("--order", choices=["fit", "position"], nargs="+", default=["fit"])
     ap.add_argument("--chunk-log2", type=int, nargs="+", default=[codec.DEFAULT_CHUNK_LOG2])
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--view", type=parse_view, action="append", default=[], metavar="x0,y0,w,h,scale")
@@ -113,6 +159,10 @@ def main():
             for k in a.chunk_log2:
                 coded[k] = codec.recode(blob, "rans", chunk_log2=k)
                 assert torch.equal(dec.decode(coded[k]), want) and codec.recode(coded[k], "fixed") == blob
+        if a.coding == "rans-delta" and a.trace:
+            for k in a.chunk_log2:
+                for order in a.order:
+                    coded[(k, order)] = codec.recode(blob, "rans-delta", chunk_log2=k, order=None if order == "fit" else order)
         if a.trace:
             ups = [up] + [dec.upload(c) for c in coded.values()]
             for u in ups:
@@ -142,6 +192,8 @@ def main():
                 r[key + "_us"] = round(med, 2)
                 r[key + "_us_range"] = [round(lo, 2), round(hi, 2)]
             row["rans"][str(k)] = r
+        if a.coding == "rans-delta":
+            row["orders"] = orders_block(a, fit, gt, dec, blob, out)
         if a.view:
             row["views"] = []
         for v in a.view:
