@@ -79,6 +79,10 @@ SIGNATURES.update({
                               _p, _p],
     "gi2d_codec_decode_bin_view": [_i, _i, _i, _i, _i, _i, _p, _p, _sz, _f, _u, _u, _f, _f, _f, _u, _u, _i, _i, _f, _p, _p,
                                    _p, _p, _p, _p, _sz, _p, _p],
+    # reduced views: per-gaussian decode with the analytic prefilter, and the forward over tile lists of any length
+    "gi2d_codec_decode_overview": [_i, _i, _i, _i, _i, _i, _p, _p, _sz, _f, _u, _u, _f, _f, _f, _f, _u, _u, _i, _i, _f, _p,
+                                   _p, _p, _p, _p, _p],
+    "gi2d_rasterize_forward_long": [_i, _i, _i, _i, _u, _u, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p],
     # rANS payload (payload coding 1)
     "gi2d_codec_histogram": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p],
     "gi2d_codec_rans_encode": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _sz, _p, _sz, _p, _p],

@@ -14,6 +14,8 @@
     v    = codec.View(x0, y0, width, height, scale=4.0)   # a window on the fitted function, magnified (1 <= scale <= 64)
     part = dec.decode(blob, view=v)              # f32 [v.height, v.width, 3]; only the window's tiles are drawn
     parts = dec.decode_views(blob, [v, codec.View.full(codec.info(blob))])
+    ov   = codec.Overview.thumbnail(codec.info(blob), 4)   # the picture reduced by 4, analytically low-passed (1/64 <= scale < 1)
+    small = dec.decode(blob, view=ov)            # f32 [H // 4, W // 4, 3]; Views and Overviews may be mixed in decode_views
 
 Decoding needs no fitter, no target image and no optimizer state: this module imports neither `trainer` nor `quantize`.
 A decode is three native launches on buffers the Decoder owns -- gi2d_fast_workspace_init, gi2d_codec_decode_bin
@@ -28,6 +30,14 @@ function at source position (x0 + j / scale, y0 + i / scale): every dequantised 
 window's pixel grid (view_parameters states the arithmetic) and the same operators draw the transformed gaussians at the
 window's size (gi2d_codec_decode_bin_view).  Tile boxes, the 256 entries of a tile and the pair test are those of the
 window's own tile grid, so a view is not pixel for pixel a crop or a resampling of the full decode.
+
+An overview (codec.Overview) is the same argument for scale < 1.  A gaussian convolved with a gaussian is a
+gaussian, so the low-pass a reduced picture needs is closed-form: every gaussian gets the filter's variance added to its
+covariance and its colour rescaled so that its mass stays (overview_parameters states the arithmetic).  A reduced tile
+holds far more than 256 gaussians, so an overview has launches of its own -- gi2d_codec_decode_overview (record ->
+transformed gaussian -> covariance projection), the capacity-free gi2d_bin_gaussians, and gi2d_rasterize_forward_long, which
+walks every tile list to its end (csrc/gi2d_codec_overview.hip) -- on buffers the Decoder keeps; the binning status joins
+the picture's status row, and a picture whose lists did not fit their buffer is drawn again with room for all of them.
 
 Format version 1 (little-endian; INTEGRATION.md "Packed stream" has the record layout):
 
@@ -601,7 +611,8 @@ class View:
     """A window on the fitted function: output pixel (row i, column j) of a `height` x `width` picture samples source
     position (x0 + j / scale, y0 + i / scale).  x0, y0 (sub-pixel origins allowed) and scale are kept as the float32
     values the kernel receives.  ValueError unless scale is finite and 1 <= scale <= 64 (a reduced view would put more
-    than the 256 entries into a tile that the reference's rule keeps; no prefilter is built), the origin is finite and
+    than the 256 entries into a tile that the reference's rule keeps; no prefilter is built: codec.Overview is the reduced
+    view, with launches of its own), the origin is finite and
     not negative, the size is at least 1 x 1 and ceil(width / 16) * ceil(height / 16) <= 16384 tiles.  Whether the window
     lies inside a picture is checked against the stream's header by the decoder (`check`)."""
     x0: float
@@ -657,13 +668,100 @@ class View:
         return float(np.float32(header["radius_clip"]) * np.float32(self.scale))
 
 
-def _checked_view(view, h, required: bool = False) -> Optional[View]:
+MIN_OVERVIEW_SCALE = 1.0 / 64.0
+MAX_OVERVIEW_PREFILTER = 4.0
+
+
+@dataclasses.dataclass(frozen=True)
+class Overview:
+    """A REDUCED view of the fitted function (DESIGN.md 3.8 "Overviews"): output pixel (row i, column j) of a `height` x
+    `width` picture samples the function, low-passed with an isotropic gaussian, at source position (x0 + j / scale,
+    y0 + i / scale).  x0, y0, scale and prefilter are kept as the float32 values the kernel receives.  prefilter is the
+    VARIANCE of the low-pass in output pixels^2; None: (1 - scale * scale) / 12 in float32 -- the second moment of the
+    1/scale x 1/scale block of unit-spaced samples an average pool takes, in output pixels; 0: no filter (point sampling,
+    but every tile still consumes its whole list).  ValueError unless scale is finite and 1/64 <= scale < 1 (View
+    magnifies), prefilter is finite and 0 <= prefilter <= 4, the origin is finite, the size is at least 1 x 1 and
+    ceil(width / 16) * ceil(height / 16) <= 16384 tiles.  Whether the footprints of its pixels lie inside a picture is
+    checked against the stream's header by the decoder (`check`)."""
+    x0: float
+    y0: float
+    width: int
+    height: int
+    scale: float
+    prefilter: Optional[float] = None
+
+    def __post_init__(self):
+        for name in ("x0", "y0", "scale", "prefilter"):
+            v = getattr(self, name)
+            if name == "prefilter" and v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"Overview: {name} must be a number, not {type(v).__name__}")
+            v = float(v)
+            if not math.isfinite(v):
+                raise ValueError(f"Overview: {name} = {v} is not finite")
+            object.__setattr__(self, name, float(np.float32(v)))
+        for name in ("width", "height"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"Overview: {name} must be an integer, not {type(v).__name__}")
+            object.__setattr__(self, name, int(v))
+        if not MIN_OVERVIEW_SCALE <= self.scale < 1.0:
+            raise ValueError(f"Overview: scale {self.scale} outside 1/64 <= scale < 1 (codec.View magnifies)")
+        if self.prefilter is None:
+            s = np.float32(self.scale)
+            object.__setattr__(self, "prefilter", float((np.float32(1) - s * s) / np.float32(12)))
+        if not 0.0 <= self.prefilter <= MAX_OVERVIEW_PREFILTER:
+            raise ValueError(f"Overview: prefilter variance {self.prefilter} outside 0 .. {MAX_OVERVIEW_PREFILTER:g} "
+                             "output pixels^2")
+        if self.width < 1 or self.height < 1:
+            raise ValueError(f"Overview: empty output {self.width}x{self.height}")
+        if self.tiles[0] * self.tiles[1] > MAX_VIEW_TILES:
+            raise ValueError(f"Overview: {self.width}x{self.height} is more than {MAX_VIEW_TILES} tiles of 16x16 (compose "
+                             "a larger output from several overviews)")
+
+    @property
+    def tiles(self):
+        return _tiles(self.width), _tiles(self.height)
+
+    @classmethod
+    def thumbnail(cls, header, factor: int) -> "Overview":
+        """The picture reduced by an integer `factor` (2..64) to (W // factor) x (H // factor): output pixel centres sit
+        on the centres of the factor x factor blocks of source pixels, as an average pool's do.  scale is the float32
+        nearest 1 / factor, or the next one above it where that lies below 1 / factor: the step 1 / scale is then never
+        longer than `factor`, so the thumbnail passes `check` for every factor and picture size."""
+        if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or not 2 <= factor <= 64:
+            raise ValueError(f"Overview.thumbnail: factor {factor!r} is not an integer in 2 .. 64")
+        factor = int(factor)
+        scale = np.float32(1.0 / factor)
+        if float(scale) * factor < 1.0:  # (exact in double: a 24-bit by a 7-bit integer)
+            scale = np.nextafter(scale, np.float32(1))
+        c = (factor - 1) / 2
+        return cls(c, c, header["width"] // factor, header["height"] // factor, float(scale))
+
+    def check(self, header) -> "Overview":
+        """ValueError unless the footprint of every output pixel lies inside the picture's sample grid: with
+        m = (1 / scale - 1) / 2, in double on the float32 values, x0 - m >= 0 and x0 + (width - 1) / scale + m <= the
+        picture's width - 1, the same for y."""
+        m = (1.0 / self.scale - 1.0) / 2.0
+        if (self.x0 - m < 0.0 or self.x0 + (self.width - 1) / self.scale + m > header["width"] - 1.0 or
+                self.y0 - m < 0.0 or self.y0 + (self.height - 1) / self.scale + m > header["height"] - 1.0):
+            raise ValueError(f"Overview: the footprints of ({self.x0}, {self.y0}) + {self.width}x{self.height} / "
+                             f"{self.scale} reach beyond the sample grid of the {header['width']}x{header['height']} picture")
+        return self
+
+    def radius_clip(self, header) -> float:
+        """The stream's radius_clip * scale (float32): View's rule."""
+        return float(np.float32(header["radius_clip"]) * np.float32(self.scale))
+
+
+def _checked_view(view, h, required: bool = False) -> Optional[Union[View, Overview]]:
     if view is None:
         if required:
-            raise ValueError("decode_views: every entry is a codec.View")
+            raise ValueError("decode_views: every entry is a codec.View or a codec.Overview")
         return None
-    if not isinstance(view, View):
-        raise ValueError("view: a codec.View (or None for the whole picture at its own size)")
+    if not isinstance(view, (View, Overview)):
+        raise ValueError("view: a codec.View or codec.Overview (or None for the whole picture at its own size)")
     return view.check(h)
 
 
@@ -695,10 +793,68 @@ def view_parameters(kind: int, values, view: View):
     return out
 
 
+def overview_parameters(kind: int, values, ov: Overview):
+    """The specification of an overview on the dequantised gaussians.  values: float32 [N, 8] in record order (numpy
+    array or torch tensor; the log channels already through exp) -> float32 [N, 8] of the same kind of array IN THE
+    COVARIANCE MODEL'S LAYOUT for either kind: x', y', cxx', cxy', cyy', r', g', b'.  Separate float32 operations, in this
+    order:
+        x' = (x - x0) * scale, y' = (y - y0) * scale
+        covariance model: s2 = scale * scale, then (cxx, cxy, cyy) = (cxx, cxy, cyy) * s2
+        scale-rot model:  sx = sx * scale, sy = sy * scale, c = cos(rot), s = sin(rot), then M = R S with
+                          R = [[c, s], [-s, c]] and T = M M^T as the projection's 2x2 product forms them (every entry the
+                          sum of two products, the zero terms of S included):
+                              m00 = c * sx + s * 0,  m10 = -s * sx + c * 0,  m01 = c * 0 + s * sy,  m11 = -s * 0 + c * sy
+                              cxx = m00 * m00 + m01 * m01,  cxy = m10 * m00 + m11 * m01,  cyy = m10 * m10 + m11 * m11
+        det0 = cxx * cyy - cxy * cxy
+        cxx' = cxx + prefilter, cyy' = cyy + prefilter, cxy' = cxy
+        det1 = cxx' * cyy' - cxy' * cxy'
+        g = sqrt(max(det0, 0) / det1)            (the mass is kept: 2 pi sqrt(det1) g = 2 pi sqrt(det0))
+        colour' = colour * g                     (into the colour: opacity stays 1, so the 1/255 pair test cuts every
+                                                  gaussian at the same relative level)
+    The overview is the picture the operators draw for these gaussians AS COVARIANCE-MODEL GAUSSIANS at ov.height x
+    ov.width with the header's clip_coe and radius_clip = ov.radius_clip(header), every tile consuming its whole list in
+    ascending id order, clamped to [0, 1]; all ones if no gaussian reaches the window."""
+    if kind not in _KIND_NAMES:
+        raise ValueError(f"overview_parameters: model kind {kind} (1 covariance, 2 scale-rot)")
+    if tuple(values.shape[1:]) != (8,) or "float32" not in str(values.dtype):
+        raise ValueError("overview_parameters: a float32 [N, 8] array")
+    is_torch = isinstance(values, torch.Tensor)
+    if is_torch and values.device.type == "cpu":
+        # torch's vectorised CPU sqrt and cos / sin are neither correctly rounded nor numpy's: a host tensor takes the
+        # numpy form, a device tensor the device's own functions (the ones the kernel calls)
+        return torch.from_numpy(overview_parameters(kind, values.detach().numpy(), ov))
+    num = float if is_torch else np.float32  # a tensor takes a Python scalar at its own precision
+    x0, y0, sc, pf = num(ov.x0), num(ov.y0), num(ov.scale), num(ov.prefilter)
+    out = values.clone() if is_torch else np.array(values, np.float32)
+    out[:, 0] = (values[:, 0] - x0) * sc
+    out[:, 1] = (values[:, 1] - y0) * sc
+    if kind == KIND_COVARIANCE:
+        s2 = num(np.float32(ov.scale) * np.float32(ov.scale))
+        cxx, cxy, cyy = values[:, 2] * s2, values[:, 3] * s2, values[:, 4] * s2
+    else:
+        sx, sy = values[:, 2] * sc, values[:, 3] * sc
+        c, s = (torch.cos(values[:, 4]), torch.sin(values[:, 4])) if is_torch else (np.cos(values[:, 4]), np.sin(values[:, 4]))
+        zero = num(0.0)
+        m00, m10 = c * sx + s * zero, -s * sx + c * zero
+        m01, m11 = c * zero + s * sy, -s * zero + c * sy
+        cxx, cxy, cyy = m00 * m00 + m01 * m01, m10 * m00 + m11 * m01, m10 * m10 + m11 * m11
+    det0 = cxx * cyy - cxy * cxy
+    cxx, cyy = cxx + pf, cyy + pf
+    det1 = cxx * cyy - cxy * cxy
+    if is_torch:
+        g = torch.sqrt(torch.clamp(det0, min=0.0) / det1)
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            g = np.sqrt(np.maximum(det0, np.float32(0)) / det1)
+    out[:, 2], out[:, 3], out[:, 4] = cxx, cxy, cyy
+    out[:, 5:8] = values[:, 5:8] * g[:, None]
+    return out
+
+
 class _Picture(NamedTuple):
     """What one launch sequence draws, derived once (_picture) from (header, view or None)."""
     header: Dict[str, object]
-    view: Optional[View]  # None: the whole picture at its own size, through the full decode's entry
+    view: Optional[Union[View, Overview]]  # None: the whole picture at its own size, through the full decode's entry
     width: int
     height: int
     tx: int
@@ -755,13 +911,39 @@ class Decoder:
         self._token = 0  # the expansion raises word 4 to the token of its decode: no reset launch between decodes
         self.expansions = 0  # rANS payloads expanded so far (gi2d_codec_rans_expand launches)
         self._background = torch.ones(3, dtype=torch.float32, device=self.dev)  # the rasterize wrappers' default
+        # overviews: per-gaussian arrays, tile lists and the binning workspace (_reserve_overview), regrown when needed
+        self._ov: Dict[str, torch.Tensor] = {}
+        self.overview_capacity: Optional[int] = None  # entries the tile lists of an overview start with (None: see below)
+        self._overview_m = 0  # the largest number of intersections an overview of this Decoder has had
 
     # ---------------------------------------------------------------------------------------------- buffers
     def _reserve_workspace(self, pictures: Sequence[_Picture]) -> None:
         size = _lib.load().gi2d_fast_workspace_bytes
-        need = max(int(size(p.header["num_points"], p.tx, p.ty)) for p in pictures)
+        need = max([int(size(p.header["num_points"], p.tx, p.ty)) for p in pictures if not isinstance(p.view, Overview)],
+                   default=0)
         if self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+
+    def _overview_list_capacity(self, n: int) -> int:
+        """Entries the tile lists of an overview of n gaussians are first given: overview_capacity if set, else
+        max(4 n, the largest count seen); a picture that needs more is drawn again with exactly what it needs."""
+        return max(1, int(self.overview_capacity)) if self.overview_capacity is not None else max(4 * n, self._overview_m)
+
+    def _reserve_overview(self, pictures: Sequence[_Picture], capacity: Optional[int] = None) -> None:
+        """The buffers of the overviews among `pictures`, each at least as large as the largest of them needs."""
+        ovs = [p for p in pictures if isinstance(p.view, Overview)]
+        if not ovs:
+            return
+        n = max(p.header["num_points"] for p in ovs)
+        tiles = max(p.tx * p.ty for p in ovs)
+        cap = capacity if capacity is not None else self._overview_list_capacity(n)
+        need = dict(xys=(2 * n, torch.float32), radii=(n, torch.int32), conics=(3 * n, torch.float32),
+                    num_tiles_hit=(n, torch.int32), colors=(3 * n, torch.float32), ids=(cap, torch.int32),
+                    bins=(2 * tiles, torch.int32),
+                    binws=(int(_lib.load().gi2d_bin_workspace_bytes(cap, tiles)), torch.uint8))
+        for key, (count, dtype) in need.items():
+            if key not in self._ov or self._ov[key].numel() < count:
+                self._ov[key] = torch.empty(count, dtype=dtype, device=self.dev)
 
     def _stage(self, streams, headers) -> List[torch.Tensor]:
         """Payloads of `streams` on the device: a DeviceStream's own, host bytes through one pinned staging buffer (one
@@ -842,6 +1024,8 @@ class Decoder:
         """Workspace reset + decode/bin + forward + clamp of a coding-0 payload on the current stream, at the picture's
         size, with the status row at `status`; no host sync and no allocation."""
         h, view, w, hh, tx, ty = pic
+        if isinstance(view, Overview):
+            return self._launch_overview(pic, payload, status, out, aux)
         n = h["num_points"]
         b = h["bits"]
         side = (C.c_float * 16)(*h["side"])
@@ -861,6 +1045,31 @@ class Decoder:
         _lib.call("gi2d_fast_rasterize_forward", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws,
                   status, None, None, C.c_void_p(out.data_ptr()), st)
         out.clamp_(0, 1)
+
+    def _launch_overview(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, aux=None,
+                         capacity: Optional[int] = None) -> None:
+        """An overview of a coding-0 payload on the current stream: gi2d_codec_decode_overview (record -> transformed,
+        prefiltered gaussian -> covariance projection), gi2d_bin_gaussians into lists of `capacity` entries (its status
+        {count, overflow} goes to words 0 and 1 of the row at `status`), gi2d_rasterize_forward_long (whole lists, clamp
+        fused, ones if the count is 0); no host sync and no allocation (_reserve_overview has been called)."""
+        h, ov, w, hh, tx, ty = pic
+        n = h["num_points"]
+        b = h["bits"]
+        cap = capacity if capacity is not None else self._overview_list_capacity(n)
+        side = (C.c_float * 16)(*h["side"])
+        st = _stream(self.dev)
+        o = self._ov
+        geo = [C.c_void_p(t.data_ptr()) for t in
+               (aux if aux is not None else [o[k] for k in ("xys", "radii", "conics", "num_tiles_hit", "colors")])]
+        ids, bins = C.c_void_p(o["ids"].data_ptr()), C.c_void_p(o["bins"].data_ptr())
+        assert o["ids"].numel() >= cap and o["bins"].numel() >= 2 * tx * ty
+        _lib.call("gi2d_codec_decode_overview", h["kind"], n, b[0], b[1], b[2], b[3], side, C.c_void_p(payload.data_ptr()),
+                  h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"], ov.x0, ov.y0, ov.scale, ov.prefilter,
+                  hh, w, tx, ty, h["radius_clip"], geo[0], geo[1], geo[2], geo[3], geo[4], st)
+        _lib.call("gi2d_bin_gaussians", n, cap, geo[0], geo[1], tx, ty, ov.radius_clip(h), ids, bins, status,
+                  C.c_void_p(o["binws"].data_ptr()), o["binws"].numel(), st)
+        _lib.call("gi2d_rasterize_forward_long", n, cap, tx, ty, w, hh, ids, bins, tx * ty, geo[0], geo[2], geo[4], None,
+                  status, C.c_void_p(out.data_ptr()), st)
 
     def _out(self, pic: _Picture, out: Optional[torch.Tensor]) -> torch.Tensor:
         shape = (pic.height, pic.width, 3)
@@ -897,7 +1106,8 @@ class Decoder:
         entry; `outs`: a tensor per picture, in call order.  Everything is parsed and checked before anything touches
         the device; a rANS payload is expanded once per group, into its slice of `_expanded` (valid until the next call);
         every picture has its own status row, and the rows are read in ONE host wait behind the last picture; a picture
-        whose tile row overflowed is then drawn again (_exact).  geometry (one group, one picture): the per-gaussian
+        whose tile row overflowed is then drawn again (_exact), an overview whose tile lists outgrew their buffer likewise
+        (_launch_overview with the count the status row reports).  geometry (one group, one picture): the per-gaussian
         outputs of the decode kernel are kept, and the picture stays the fast path's own."""
         who, what = ("decode_views", "view") if views_only else ("decode_many", "stream")
         streams = [s for s, _ in groups]
@@ -912,6 +1122,7 @@ class Decoder:
             if self._status.shape[0] < len(pictures):
                 self._status = torch.zeros(len(pictures), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
             self._reserve_workspace(pictures)
+            self._reserve_overview(pictures)
             slices, total = [], 0
             for h in headers:
                 slices.append(total)
@@ -932,11 +1143,16 @@ class Decoder:
                     row = len(fixed)
                     self._launch(pictures[row], payload, row0 + _STATUS_ROW * row, images[row], aux)
                     fixed.append(payload)
-            status = self._status[:len(pictures), 1:5].tolist()  # the one host wait of a call: overflow, .., .., rANS
+            status = self._status[:len(pictures), 0:5].tolist()  # the one host wait of a call: M, overflow, .., .., rANS
             for row in coded:
-                self._check_expanded(status[row][3])
-            for row, (overflow, _, _, _) in enumerate(status):
-                if overflow and not geometry:
+                self._check_expanded(status[row][4])
+            for row, (m, overflow, _, _, _) in enumerate(status):
+                if isinstance(pictures[row].view, Overview):
+                    self._overview_m = max(self._overview_m, m)
+                    if overflow:  # the lists were cut at the capacity: the same picture again with room for all m
+                        self._reserve_overview([pictures[row]], m)
+                        self._launch_overview(pictures[row], fixed[row], row0 + _STATUS_ROW * row, images[row], aux, m)
+                elif overflow and not geometry:
                     self._exact(pictures[row], fixed[row], images[row])
         return images, aux
 
@@ -944,7 +1160,7 @@ class Decoder:
     def decode(self, stream, out: Optional[torch.Tensor] = None, view: Optional[View] = None) -> torch.Tensor:
         """bytes (or an uploaded DeviceStream) -> f32 [H, W, 3] in [0, 1]; `out`: a tensor to write into.  view: a
         codec.View -> f32 [view.height, view.width, 3], the window of the fitted function it names (View.full: the
-        bits of the plain decode, through the view kernel)."""
+        bits of the plain decode, through the view kernel); a codec.Overview -> the reduced, low-passed picture it names."""
         if view is None:
             return self.decode_many([stream], None if out is None else [out])[0]
         return self.decode_views(stream, [view], None if out is None else [out])[0]
@@ -952,7 +1168,7 @@ class Decoder:
     def decode_views(self, stream, views: Sequence[View], outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
         """Several views of ONE stream back to back on the current stream of the device: the payload is staged once, a
         rANS payload expanded once, the workspace reserved for the largest view, and the statuses are read once, at the
-        end."""
+        end.  Views and Overviews may be mixed."""
         return self._run([(stream, list(views))], outs, views_only=True)[0]
 
     def decode_many(self, streams, outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
@@ -963,7 +1179,8 @@ class Decoder:
     def decode_geometry(self, stream, view: Optional[View] = None) -> Dict[str, torch.Tensor]:
         """What the decode kernel makes of every gaussian: xys, radii, conics, num_tiles_hit, colors (tests, tools); with
         a view, the transformed geometry in the view's pixel grid.  `image` is the fast path's own picture: a crowded
-        tile is not drawn again."""
+        tile is not drawn again.  With an Overview: the covariance projection of the transformed, prefiltered gaussians,
+        `colors` rescaled, and `image` the overview itself (drawn again if its lists outgrew their buffer)."""
         images, aux = self._run([(stream, (view,))], geometry=True)
         return dict(zip(("xys", "radii", "conics", "num_tiles_hit", "colors"), aux), image=images[0])
 
@@ -973,7 +1190,8 @@ _decoders: Dict[torch.device, Decoder] = {}
 
 def decode(blob, device: Union[str, torch.device] = "cuda:0", out: Optional[torch.Tensor] = None,
            view: Optional[View] = None) -> torch.Tensor:
-    """One-shot decode (a Decoder per device is kept behind the scenes); view: a codec.View of the picture."""
+    """One-shot decode (a Decoder per device is kept behind the scenes); view: a codec.View or codec.Overview of the
+    picture."""
     _checked_view(view, _parse(blob))  # a malformed stream or view is refused before a device is even touched
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:

@@ -1,0 +1,314 @@
+// Reduced views ("overviews") of a packed stream (include/gi2d.h "reduced views"):
+//
+//   decode      one lane per gaussian: record -> dequantised values exactly as the full decode forms them -> the overview
+//               transform (move and scale into the output grid, add the low-pass's variance to the covariance, fold the
+//               lost peak height into the colour: codec.overview_parameters restates the arithmetic) -> the COVARIANCE
+//               projection for either model kind.  Writes the five per-gaussian arrays gi2d_bin_gaussians and the forward
+//               below consume; no fast-path workspace.
+//   forward     one workgroup per 16x16 tile, one pixel per lane, the tile's WHOLE list walked in batches of 256 entries
+//               staged through LDS (a reduced view puts a thousand and more entries into a tile; every other forward in
+//               the tree stops at GI2D_TILE_LIST_CAP).  Each wave owns a 16x4 strip and, per staged batch, keeps only the
+//               entries whose alpha >= 1/255 box (gi2d_common.h::cull_extent, the box of the other forward kernels) meets
+//               its strip and the tile's columns: a ballot compaction that preserves list order, so a pixel's sum is formed
+//               in list order and repeats bit for bit.  A dropped entry fails the pair test at every pixel of the strip
+//               (am = 0 there), so for finite colours the picture is that of the walk without the skip.  At scale 1/8 a
+//               gaussian reaches 2-3 pixels of a tile whose list holds every gaussian of 128x128 source pixels: DESIGN.md
+//               3.8 has the measured rows with and without the skip.
+//
+// Nothing is read through an address formed from unchecked content: record positions follow from (N, R), list bounds
+// are clamped to the capacity of the id buffer and ids to [0, N).
+#include <cmath>
+
+#include "gi2d_codec_layout.h"
+#include "gi2d_quant_core.h"
+
+namespace gi2d {
+
+struct CodecOverview {
+    float x0, y0, scale, prefilter;
+};
+struct OverviewOut {
+    float2 *xys;
+    int32_t *radii;
+    float *conics;
+    int32_t *num_tiles_hit;
+    float *colors;
+};
+
+// v: the dequantised record.  -> centre, covariance and colour of the gaussian in the overview's pixel grid, every step a
+// separate fp32 operation in the order codec.overview_parameters states.
+template <int KIND>
+__device__ __forceinline__ void overview_transform(float (&v)[GI2D_CODEC_FIELDS], const CodecOverview ov) {
+#pragma clang fp contract(off)
+    v[0] = (v[0] - ov.x0) * ov.scale;
+    v[1] = (v[1] - ov.y0) * ov.scale;
+    float cxx, cxy, cyy;
+    if (KIND == kCovariance) {
+        const float s2 = ov.scale * ov.scale;
+        cxx = v[2] * s2, cxy = v[3] * s2, cyy = v[4] * s2;
+    } else {  // project_values<kScaleRot>: R = [[cos, sin], [-sin, cos]], M = R S, M M^T
+        const float sx = v[2] * ov.scale, sy = v[3] * ov.scale;
+        const float c = cosf(v[4]), s = sinf(v[4]);
+        const M2 R{{c, -s, s, c}};
+        const M2 S{{sx, 0.f, 0.f, sy}};
+        const M2 M = mul(R, S);
+        const M2 T = mul(M, tr(M));
+        cxx = T.v[0], cxy = T.v[1], cyy = T.v[3];
+    }
+    const float det0 = cxx * cyy - cxy * cxy;
+    cxx = cxx + ov.prefilter;
+    cyy = cyy + ov.prefilter;
+    const float det1 = cxx * cyy - cxy * cxy;
+    const float g = sqrtf(fmaxf(det0, 0.f) / det1);
+    v[2] = cxx, v[3] = cxy, v[4] = cyy;
+    v[5] = v[5] * g, v[6] = v[6] * g, v[7] = v[7] * g;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void codec_decode_overview_kernel(
+    int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
+    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, OverviewOut out, CodecOverview ov) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    // the record, as the full decode reads it: dwords first, first + 1, ..., every index clamped to the payload
+    const long long bit0 = (long long)g * lay.record_bits;
+    const long long first = bit0 >> 5;
+    uint32_t w[GI2D_CODEC_MAX_LOADS];
+#pragma unroll
+    for (int j = 0; j < GI2D_CODEC_MAX_LOADS; ++j) {
+        const long long d = first + j;
+        w[j] = j < lay.loads ? payload[d < last_dword ? d : last_dword] : 0u;
+    }
+    const uint32_t s0 = (uint32_t)bit0 & 31u;
+    uint32_t r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], s0);
+    float v[GI2D_CODEC_FIELDS];
+#pragma unroll
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
+        const float code = (float)((int)codec_take(r, lay.width[k]) + lay.qmin[k]);
+        v[k] = (KIND == kCovariance && (k == 2 || k == 4)) ? quant_dequant<GI2D_QUANT_LOG>(code, side.scale[k], side.beta[k])
+                                                          : quant_dequant<GI2D_QUANT_LSQ>(code, side.scale[k], side.beta[k]);
+    }
+    overview_transform<KIND>(v, ov);
+    const ProjOut o = project_values<kCovariance>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h,
+                                                  tiles_x, tiles_y, radius_clip);
+    out.xys[g] = o.xy;
+    out.radii[g] = o.radius;
+    out.conics[3 * g] = o.k0, out.conics[3 * g + 1] = o.k1, out.conics[3 * g + 2] = o.k2;
+    out.num_tiles_hit[g] = o.tiles_hit;
+    out.colors[3 * g] = v[5], out.colors[3 * g + 1] = v[6], out.colors[3 * g + 2] = v[7];
+}
+
+// ------------------------------------------------------------------------------------------- forward, any list length
+#define GI2D_LONG_BATCH 256
+struct LongLds {
+    float4 a[GI2D_LONG_BATCH];               // gx, gy, ha, hb   (conic pre-scaled: scale_conic)
+    float4 b[GI2D_LONG_BATCH];               // hc, opacity, cr, cg
+    float2 c[GI2D_LONG_BATCH];               // cb, AlphaRule::lim
+    float2 reach[GI2D_LONG_BATCH];           // half extents of the alpha >= 1/255 box (cull_extent)
+    unsigned char keep[4][GI2D_LONG_BATCH];  // per wave: the batch entries its strip keeps, ascending
+};
+
+// one staged entry on this lane's pixel: the arithmetic of gi2d_raster_core.h::fwd_trips, one pixel per lane
+template <bool CLAMP>
+__device__ __forceinline__ void long_pair(const LongLds &sm, int k, float px, float py, float &o0, float &o1, float &o2) {
+    const float4 A = sm.a[k], B = sm.b[k];
+    const float2 Cc = sm.c[k];
+    const unsigned lim = (unsigned)__float_as_int(Cc.y);
+    const float dy = A.y - py;
+    const float bdy = A.w * dy, cdy2 = __builtin_fmaf(B.x * dy, dy, 0.f);
+    const float dx = A.x - px;
+    const float sig = __builtin_fmaf(dx, __builtin_fmaf(A.z, dx, bdy), cdy2);
+    const float tt = B.y * pair_vis(sig);
+    const bool ok = CLAMP ? pair_lands_odd(sig, tt, lim) : pair_lands(sig, lim);
+    float am = ok ? tt : 0.f;
+    if (CLAMP) am = fminf(1.f, am);
+    o0 = __builtin_fmaf(B.z, am, o0);
+    o1 = __builtin_fmaf(B.w, am, o1);
+    o2 = __builtin_fmaf(Cc.x, am, o2);
+}
+
+// torch.clamp(x, 0, 1): a NaN stays a NaN
+__device__ __forceinline__ float clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
+
+template <bool SKIP>
+__global__ __launch_bounds__(256) void raster_fwd_long_kernel(
+    int n, int capacity, int tiles_x, int img_w, int img_h, const int32_t *__restrict__ gids_sorted,
+    const int2 *__restrict__ tile_bins, int tile_bins_rows, const float2 *__restrict__ xys,
+    const float *__restrict__ conics, const float *__restrict__ colors, const float *__restrict__ opacities,
+    const int32_t *__restrict__ status, float *__restrict__ out_img) {
+    __shared__ LongLds sm;
+    const int tile = blockIdx.x;
+    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int j = tx * GI2D_TILE + (lane & 15), i = ty * GI2D_TILE + wv * 4 + (lane >> 4);
+    const bool inside = i < img_h && j < img_w;
+    const size_t pix = (size_t)i * img_w + j;
+    if (status != nullptr && status[0] < 1) {  // not a single intersection: the background picture (ones)
+        if (inside) out_img[3 * pix] = 1.f, out_img[3 * pix + 1] = 1.f, out_img[3 * pix + 2] = 1.f;
+        return;
+    }
+    int2 range = make_int2(0, 0);
+    if (tile < tile_bins_rows) range = tile_bins[tile];
+    const int start = min(max(range.x, 0), capacity);
+    const int end = min(max(range.y, start), capacity);
+    const float px = (float)j, py = (float)i;
+    // what this wave's strip and the tile's columns span (clipped to the picture)
+    const float sy0 = (float)(ty * GI2D_TILE + wv * 4), sy1 = fminf(sy0 + 3.f, (float)(img_h - 1));
+    const float sx0 = (float)(tx * GI2D_TILE), sx1 = fminf(sx0 + 15.f, (float)(img_w - 1));
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+    for (int base = start; base < end; base += GI2D_LONG_BATCH) {
+        const int m = min(GI2D_LONG_BATCH, end - base);
+        bool clamp = false;
+        if (tid < m) {
+            const int g = min(max(gids_sorted[base + tid], 0), n - 1);
+            const float2 xy = xys[g];
+            const float a = conics[3 * g], b = conics[3 * g + 1], c = conics[3 * g + 2];
+            const float op = opacities ? opacities[g] : 1.f;
+            const AlphaRule ar = alpha_rule(xy.x, xy.y, a, b, c, op);
+            const ConicS s = scale_conic(a, b, c);
+            clamp = ar.clamp;
+            sm.a[tid] = make_float4(xy.x, xy.y, s.ha, s.hb);
+            sm.b[tid] = make_float4(s.hc, op, colors[3 * g], colors[3 * g + 1]);
+            sm.c[tid] = make_float2(colors[3 * g + 2], __int_as_float((int)ar.lim));
+            if (SKIP) {
+                float hx, hy;
+                cull_extent(xy.x, xy.y, a, b, c, op, hx, hy);
+                sm.reach[tid] = make_float2(hx, hy);
+            }
+        }
+        const bool clamp_any = __syncthreads_or(clamp) != 0;  // (also the barrier behind the staging stores)
+        if (SKIP) {
+            int kept = 0;
+            for (int c0 = 0; c0 < m; c0 += 64) {
+                const int k = c0 + lane;
+                bool keep = false;
+                if (k < m) {
+                    const float2 h = sm.reach[k];
+                    const float4 A = sm.a[k];
+                    // hx < 0: can never land; GI2D_CULL_FULL: no finite box, every pixel is evaluated
+                    keep = h.x >= 0.f && (h.x >= GI2D_CULL_FULL || (A.y - h.y <= sy1 && A.y + h.y >= sy0 &&
+                                                                    A.x - h.x <= sx1 && A.x + h.x >= sx0));
+                }
+                const unsigned long long mask = __ballot(keep);
+                if (keep) sm.keep[wv][kept + __popcll(mask & lanemask_lt())] = (unsigned char)k;
+                kept += __popcll(mask);
+            }
+            __builtin_amdgcn_wave_barrier();  // wave-private list: DS ops of one wave complete in order
+            if (clamp_any) {
+#pragma unroll 4
+                for (int t = 0; t < kept; ++t) long_pair<true>(sm, sm.keep[wv][t], px, py, o0, o1, o2);
+            } else {
+#pragma unroll 4
+                for (int t = 0; t < kept; ++t) long_pair<false>(sm, sm.keep[wv][t], px, py, o0, o1, o2);
+            }
+        } else {
+            if (clamp_any) {
+#pragma unroll 4
+                for (int k = 0; k < m; ++k) long_pair<true>(sm, k, px, py, o0, o1, o2);
+            } else {
+#pragma unroll 4
+                for (int k = 0; k < m; ++k) long_pair<false>(sm, k, px, py, o0, o1, o2);
+            }
+        }
+        __syncthreads();  // the batch is consumed: the next one may be staged
+    }
+    if (inside) {
+        out_img[3 * pix] = clamp01(o0);
+        out_img[3 * pix + 1] = clamp01(o1);
+        out_img[3 * pix + 2] = clamp01(o2);
+    }
+}
+
+}  // namespace gi2d
+
+using namespace gi2d;
+
+#define GI2D_CODEC_OVERVIEW_MIN_SCALE (1.0f / 64.0f)
+#define GI2D_CODEC_OVERVIEW_MAX_PREFILTER 4.0f
+#define GI2D_CODEC_OVERVIEW_MAX_TILES 16384
+
+extern "C" {
+
+int gi2d_codec_decode_overview(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                               const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
+                               unsigned h, unsigned w_, float x0, float y0, float scale, float prefilter,
+                               unsigned out_h, unsigned out_w, int tiles_x, int tiles_y, float radius_clip, float *xys,
+                               int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors, gi2d_stream_t st) {
+    const char *what = "codec decode overview";
+    const auto fail = [&](const char *why) {
+        set_error((std::string(what) + ": " + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    };
+    // the conditions on an overview, in double on the fp32 values the kernel receives
+    if (!std::isfinite(scale) || scale < GI2D_CODEC_OVERVIEW_MIN_SCALE || !(scale < 1.f))
+        return fail("scale must be finite and in 1/64 <= scale < 1 (gi2d_codec_decode_bin_view magnifies)");
+    if (!std::isfinite(prefilter) || prefilter < 0.f || prefilter > GI2D_CODEC_OVERVIEW_MAX_PREFILTER)
+        return fail("the prefilter variance must be finite and in 0 .. 4 output pixels^2");
+    if (!std::isfinite(x0) || !std::isfinite(y0)) return fail("the origin must be finite");
+    if (out_w < 1 || out_h < 1) return fail("empty output");
+    if (((unsigned long long)out_w + GI2D_TILE - 1) / GI2D_TILE * (((unsigned long long)out_h + GI2D_TILE - 1) / GI2D_TILE) >
+        (unsigned long long)GI2D_CODEC_OVERVIEW_MAX_TILES)
+        return fail("more than 16384 tiles in one overview (compose larger outputs from several)");
+    const double sc = (double)scale, m = (1.0 / sc - 1.0) / 2.0;
+    if ((double)x0 - m < 0.0 || (double)x0 + (double)(out_w - 1) / sc + m > (double)w_ - 1.0 ||
+        (double)y0 - m < 0.0 || (double)y0 + (double)(out_h - 1) / sc + m > (double)h - 1.0)
+        return fail("the footprint of an output pixel reaches beyond the picture's sample grid");
+    // ... and those of the full decode
+    CodecLayout lay;
+    if (!codec_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 0 || tiles_x < 0 || tiles_y < 0) return fail("negative size");
+    const long long need = codec_dwords(n, lay.record_bits);
+    if (payload_bytes < (size_t)need * 4) return fail("payload shorter than 4 * ceil(N * R / 32) bytes");
+    if (!side_host || (n > 0 && (!payload || ((uintptr_t)payload & 3) || !xys || !radii || !conics || !num_tiles_hit || !colors)))
+        return fail("null or misaligned pointer");
+    if ((long long)tiles_x * GI2D_TILE < (long long)out_w || (long long)tiles_y * GI2D_TILE < (long long)out_h)
+        return fail("tile grid does not cover the image");
+    if (n == 0) return GI2D_OK;
+    CodecSide side;
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) side.scale[k] = side_host[2 * k], side.beta[k] = side_host[2 * k + 1];
+    const OverviewOut out{(float2 *)xys, radii, conics, num_tiles_hit, colors};
+    const CodecOverview ov{x0, y0, scale, prefilter};
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (kind == kCovariance)
+        hipLaunchKernelGGL(codec_decode_overview_kernel<kCovariance>, grid, block, 0, (hipStream_t)st, n, lay, side,
+                           (const uint32_t *)payload, need - 1, clip_coe, (float)out_w, (float)out_h, tiles_x, tiles_y,
+                           radius_clip * scale, out, ov);
+    else
+        hipLaunchKernelGGL(codec_decode_overview_kernel<kScaleRot>, grid, block, 0, (hipStream_t)st, n, lay, side,
+                           (const uint32_t *)payload, need - 1, clip_coe, (float)out_w, (float)out_h, tiles_x, tiles_y,
+                           radius_clip * scale, out, ov);
+    return check_launch(what);
+}
+
+int gi2d_rasterize_forward_long(int n, int capacity, int tiles_x, int tiles_y, unsigned w, unsigned h,
+                                const int32_t *gids, const int32_t *bins, int rows, const float *xys, const float *conics,
+                                const float *colors, const float *opac, const int32_t *status, float *out_img,
+                                gi2d_stream_t st) {
+    const char *what = "rasterize forward long";
+    const auto fail = [&](const char *why) {
+        set_error((std::string(what) + ": " + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    };
+    if (n < 0 || capacity < 0 || tiles_x < 0 || tiles_y < 0 || rows < 0) return fail("negative size");
+    if (capacity > 0x7fffffff - GI2D_LONG_BATCH) return fail("capacity too large for 32-bit list positions");
+    if ((long long)tiles_x * GI2D_TILE < (long long)w || (long long)tiles_y * GI2D_TILE < (long long)h)
+        return fail("tile grid does not cover the image");
+    const long long t = (long long)tiles_x * tiles_y;
+    if (t == 0 || w == 0 || h == 0) return GI2D_OK;
+    if (t > 0x7fffffffLL || w > 0x7fffffffu || h > 0x7fffffffu) return fail("tile grid too large");
+    if (n == 0) capacity = 0, rows = 0;  // no gaussian: no list is read
+    if (!out_img || (rows > 0 && !bins) || (capacity > 0 && rows > 0 && (!gids || !xys || !conics || !colors)))
+        return fail("null pointer");
+#ifdef GI2D_LONG_NO_SKIP /* development variant: the walk without the per-wave skip (timing aid) */
+    const auto kernel = raster_fwd_long_kernel<false>;
+#else
+    const auto kernel = raster_fwd_long_kernel<true>;
+#endif
+    hipLaunchKernelGGL(kernel, dim3((unsigned)t), dim3(256), 0, (hipStream_t)st, n, capacity, tiles_x, (int)w, (int)h,
+                       gids, (const int2 *)bins, rows, (const float2 *)xys, conics, colors, opac, status, out_img);
+    return check_launch(what);
+}
+
+}  // extern "C"

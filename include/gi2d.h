@@ -632,6 +632,43 @@ int gi2d_codec_decode_bin_view(int kind, int num_points, int xy_bits, int p0_bit
                                float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors,
                                void *workspace, size_t workspace_bytes, int32_t *status, gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ reduced views of a packed stream
+ * An OVERVIEW samples the fitted function, low-passed with an isotropic gaussian, on a grid coarser than the picture's:
+ * output pixel (row i, column j) is the prefiltered function at (x0 + j / scale, y0 + i / scale), 1/64 <= scale < 1.
+ * Three calls on caller-owned buffers, all sync-free: gi2d_codec_decode_overview -> gi2d_bin_gaussians ->
+ * gi2d_rasterize_forward_long.  No fast-path workspace, no 256-entry rule.
+ *   gi2d_codec_decode_overview  per gaussian: record -> dequantised values (as gi2d_codec_decode_bin) -> in separate fp32
+ *                          operations  x' = (x - x0) * scale, y' = (y - y0) * scale;  covariance entries * (scale * scale)
+ *                          (kind 2: the two scales * scale, then the covariance as the scale-rot projection builds it);
+ *                          det0 = cxx cyy - cxy cxy;  cxx += prefilter, cyy += prefilter;  det1 likewise;
+ *                          colour *= sqrt(max(det0, 0) / det1)  (the gaussian's mass is kept, its opacity stays 1)
+ *                          -> covariance projection (gi2d_project_gaussians_2d_covariance_forward, for EITHER kind) at
+ *                          out_height x out_width with radius_clip * scale (radius_clip: the stream's own value).
+ *                          xys f32[N,2], radii i32[N], conics f32[N,3], num_tiles_hit i32[N], colors f32[N,3]: all
+ *                          required.  prefilter: variance of the low-pass in output pixels^2.  Refused (-1) before
+ *                          anything is launched: scale not finite or outside 1/64 <= scale < 1; prefilter not finite or
+ *                          outside 0 .. 4; x0, y0 not finite; an empty output; more than 16384 tiles; a footprint outside
+ *                          the picture's sample grid -- with m = (1 / scale - 1) / 2 in double on the fp32 values,
+ *                          x0 - m < 0 or x0 + (out_width - 1) / scale + m > img_width - 1, the same for y; and what
+ *                          gi2d_codec_decode_bin refuses (kind, widths, payload size, pointers, tile grid).
+ *   gi2d_rasterize_forward_long  the additive forward over gaussian_ids_sorted / tile_bins with EVERY entry of a tile's
+ *                          list consumed, in list order (no GI2D_TILE_LIST_CAP): same pair test as the ops above (sigma
+ *                          < 0 or alpha < 1/255 skipped, alpha = min(1, opacity * exp(-sigma))), the result clamped to
+ *                          [0, 1] as it is stored.  capacity: entries gaussian_ids_sorted holds (list bounds are clamped
+ *                          to it, ids to [0, num_points)).  opacities f32[N], NULL = all 1.  status: the binning call's
+ *                          status words on the device (NULL = not looked at); status[0] < 1 (no intersection at all)
+ *                          writes ones everywhere.  No atomics: a picture repeats bit for bit. */
+int gi2d_codec_decode_overview(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                               const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
+                               unsigned img_height, unsigned img_width, float x0, float y0, float scale, float prefilter,
+                               unsigned out_height, unsigned out_width, int tiles_x, int tiles_y, float radius_clip,
+                               float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors,
+                               gi2d_stream_t stream);
+int gi2d_rasterize_forward_long(int num_points, int capacity, int tiles_x, int tiles_y, unsigned img_width,
+                                unsigned img_height, const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                                int tile_bins_rows, const float *xys, const float *conics, const float *colors,
+                                const float *opacities, const int32_t *status, float *out_img, gi2d_stream_t stream);
+
 /* ------------------------------------------------------------------ rANS payload (payload codings 1 and 2 of format 1)
  * The records of coding 0, entropy coded: gaussianimage_plus_amd/codec.py owns the container (tag "rANS", model section,
  * chunk directory, chunk data; INTEGRATION.md has the table) and validates all of it on the host.  A field of width w is

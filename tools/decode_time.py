@@ -23,9 +23,16 @@ pixel difference from the fit-order picture and both PSNRs.
 the window's source pixels -> the view's size: pixels interpolated, not the function evaluated).  Same regions, same
 discipline.
 
+--overview adds, per fit, three Overview.thumbnail rows (factors 2, 4, 8): the time of Decoder.decode(stream, view=thumbnail)
+on the uploaded stream (`overview_us`: per-gaussian kernel, capacity-free binning, the forward over whole tile lists) next
+to the only route there is without overviews (`route_us`): the full decode followed by torch.nn.functional.interpolate
+(mode="area") to the thumbnail's size.  Same regions, same discipline; --out-json writes the JSON line to a file too
+(profiles/decode_overview_time.json).
+
     python tools/decode_time.py [--reps 200] [--coding fixed|rans|rans-delta] [--order fit position]
                                 [--chunk-log2 10 8 12] [--trace]
                                 [--view 256,128,256,256,1 --view 256,128,1024,1024,4 --view 0,0,1536,1024,2]
+                                [--overview] [--out-json profiles/decode_overview_time.json]
 --trace decodes a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for
 the per-kernel split (profiles/decode_kernel_stats.csv).
 """
@@ -130,6 +137,32 @@ def route_without_views(dec, up, full, view):
     return run
 
 
+def route_without_overviews(dec, up, full, ov):
+    """What a caller without overviews does for a thumbnail: full decode, then an area resampling in torch."""
+    def run():
+        img = dec.decode(up, out=full)
+        return torch.nn.functional.interpolate(img.permute(2, 0, 1)[None], size=(ov.height, ov.width), mode="area")
+    return run
+
+
+def overview_rows(a, dec, up, full):
+    rows = []
+    for factor in (2, 4, 8):
+        ov = codec.Overview.thumbnail(up.header, factor)
+        vout = torch.empty(ov.height, ov.width, 3, device="cuda:0")
+        g = dec.decode_geometry(up, view=ov)
+        assert torch.equal(dec.decode(up, out=vout, view=ov), g["image"])
+        intersections = int(dec._status[0, 0])  # word 0 of the picture's status row: the binning step's count
+        pooled = route_without_overviews(dec, up, full, ov)()[0].permute(1, 2, 0)
+        r = {"factor": factor, "overview": [ov.x0, ov.y0, ov.width, ov.height, ov.scale, ov.prefilter],
+             "tiles": ov.tiles[0] * ov.tiles[1], "intersections": intersections,
+             "psnr_db_against_area_route": round(10 * torch.log10(1.0 / torch.nn.functional.mse_loss(vout, pooled)).item(), 3)}
+        timed(r, "overview", lambda: dec.decode(up, out=vout, view=ov), a.reps)
+        timed(r, "route", route_without_overviews(dec, up, full, ov), a.reps)
+        rows.append(r)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
@@ -140,6 +173,8 @@ def main():
     ap.add_argument("--chunk-log2", type=int, nargs="+", default=[codec.DEFAULT_CHUNK_LOG2])
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--view", type=parse_view, action="append", default=[], metavar="x0,y0,w,h,scale")
+    ap.add_argument("--overview", action="store_true")
+    ap.add_argument("--out-json", default=None, metavar="PATH")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_time.py needs the GPU"
     res = {"tool": "decode_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
@@ -209,9 +244,15 @@ def main():
                 r[key + "_us_range"] = [round(lo, 2), round(hi, 2)]
                 r[key + "_us_regions"] = [round(x, 2) for x in regions]
             row["views"].append(r)
+        if a.overview:
+            row["overviews"] = overview_rows(a, dec, up, out)
         res["sizes"][str(n)] = row
     if not a.trace:
         print(json.dumps(res))
+        if a.out_json:
+            with open(a.out_json, "w") as f:
+                json.dump(res, f, indent=1)
+                f.write("\n")
 
 
 if __name__ == "__main__":
