@@ -83,6 +83,10 @@ SIGNATURES.update({
     "gi2d_codec_decode_overview": [_i, _i, _i, _i, _i, _i, _p, _p, _sz, _f, _u, _u, _f, _f, _f, _f, _u, _u, _i, _i, _f, _p,
                                    _p, _p, _p, _p, _p],
     "gi2d_rasterize_forward_long": [_i, _i, _i, _i, _u, _u, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p],
+    # picture formats of a decode: the decode's own tile pass, the overview forward and the conversion kernel
+    "gi2d_codec_draw": [_i, _i, _i, _u, _u, _p, _p, _sz, _p, _i, _i, _p, _p],
+    "gi2d_rasterize_forward_long_as": [_i, _i, _i, _i, _u, _u, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p],
+    "gi2d_codec_convert": [_i, _i, _u, _u, _p, _p, _p],
     # rANS payload (payload coding 1)
     "gi2d_codec_histogram": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p],
     "gi2d_codec_rans_encode": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _sz, _p, _sz, _p, _p],

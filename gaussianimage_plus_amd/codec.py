@@ -16,6 +16,9 @@
     parts = dec.decode_views(blob, [v, codec.View.full(codec.info(blob))])
     ov   = codec.Overview.thumbnail(codec.info(blob), 4)   # the picture reduced by 4, analytically low-passed (1/64 <= scale < 1)
     small = dec.decode(blob, view=ov)            # f32 [H // 4, W // 4, 3]; Views and Overviews may be mixed in decode_views
+    rgba = dec.decode(blob, dtype=torch.uint8, layout="hwc4")    # u8 [H, W, 4], alpha 255: what a viewer or a file writer takes
+    x    = dec.decode(blob, dtype=torch.float16, layout="chw")   # f16 [3, H, W]: what a network takes (any view, any call)
+    codec.convert(img, torch.uint8, "hwc4")      # the same conversion in plain torch, on any device: its specification
 
 Decoding needs no fitter, no target image and no optimizer state: this module imports neither `trainer` nor `quantize`.
 A decode is three native launches on buffers the Decoder owns -- gi2d_fast_workspace_init, gi2d_codec_decode_bin
@@ -38,6 +41,15 @@ holds far more than 256 gaussians, so an overview has launches of its own -- gi2
 transformed gaussian -> covariance projection), the capacity-free gi2d_bin_gaussians, and gi2d_rasterize_forward_long, which
 walks every tile list to its end (csrc/gi2d_codec_overview.hip) -- on buffers the Decoder keeps; the binning status joins
 the picture's status row, and a picture whose lists did not fit their buffer is drawn again with room for all of them.
+
+A picture FORMAT (DESIGN.md 3.8 "Picture formats") is a decoder argument too: dtype float32, float16 or uint8 times layout
+"hwc" [H, W, 3], "chw" [3, H, W] or "hwc4" [H, W, 4] (channel 3 = the element of 1.0).  `convert` states the arithmetic:
+clamp to [0, 1], then as it is / rounded to nearest even / rint(c * 255) with NaN -> 0.  With dtype and layout both None a
+call makes exactly the launches above.  With either given (the other defaults to float32 / "hwc") the picture is drawn by
+the decode's own tile pass, gi2d_codec_draw (csrc/gi2d_codec_draw.hip) -- the forward without the packed records and
+gradient rows that only a fit reads, ending in the clamp, the conversion and the layout -- or, for an overview, by
+gi2d_rasterize_forward_long_as; there is no clamp launch, and the values are `convert` of the default call's, bit for bit.
+The fallbacks draw in float32 and end in gi2d_codec_convert.
 
 Format version 1 (little-endian; INTEGRATION.md "Packed stream" has the record layout):
 
@@ -851,6 +863,72 @@ def overview_parameters(kind: int, values, ov: Overview):
     return out
 
 
+PIXEL_DTYPES = {torch.float32: 0, torch.float16: 1, torch.uint8: 2}  # GI2D_PIXEL_* of the C ABI
+LAYOUTS = {"hwc": 0, "chw": 1, "hwc4": 2}                            # GI2D_LAYOUT_*
+
+
+class _Format(NamedTuple):
+    """A picture format, checked (_format)."""
+    dtype: torch.dtype
+    layout: str
+
+    @property
+    def ids(self):  # (dtype, layout) as the C ABI numbers them
+        return PIXEL_DTYPES[self.dtype], LAYOUTS[self.layout]
+
+    def shape(self, height: int, width: int):
+        return {"hwc": (height, width, 3), "chw": (3, height, width), "hwc4": (height, width, 4)}[self.layout]
+
+
+_DEFAULT_FORMAT = _Format(torch.float32, "hwc")
+
+
+def _format(dtype, layout) -> Optional[_Format]:
+    """(dtype, layout) of a decode call -> None for (None, None): the picture and the launches there were before there
+    were formats; else the format, a missing half defaulting to float32 / "hwc".  ValueError for anything else."""
+    if dtype is None and layout is None:
+        return None
+    dtype = torch.float32 if dtype is None else dtype
+    layout = "hwc" if layout is None else layout
+    if not isinstance(dtype, torch.dtype) or dtype not in PIXEL_DTYPES:
+        raise ValueError(f"dtype {dtype!r}: torch.float32, torch.float16 or torch.uint8")
+    if not isinstance(layout, str) or layout not in LAYOUTS:
+        raise ValueError(f"layout {layout!r}: 'hwc' [H, W, 3], 'chw' [3, H, W] or 'hwc4' [H, W, 4]")
+    return _Format(dtype, layout)
+
+
+def _check_out(out, shape, dtype: torch.dtype, dev: Optional[torch.device] = None) -> None:
+    """ValueError unless `out` can take a picture of that shape and type (dev None: wherever it lives)."""
+    if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype
+            or (dev is not None and out.device != dev) or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {tuple(shape)}"
+                         + (f" on {dev}" if dev is not None else ""))
+
+
+def convert(img: torch.Tensor, dtype=None, layout=None) -> torch.Tensor:
+    """The specification of a picture format, in plain torch on any device: float32 [H, W, 3] (a decoded picture, or any
+    values) -> the tensor decode(dtype=, layout=) gives for it.  With c = img.clamp(0, 1) (a NaN stays a NaN):
+        torch.float32   c
+        torch.float16   c.to(torch.float16)                      (round to nearest even)
+        torch.uint8     (c * 255).round().to(torch.uint8)        (one float32 multiply, round half to even); NaN -> 0
+    and layout "hwc": [H, W, 3], "chw": [3, H, W], "hwc4": [H, W, 4] with channel 3 the element of 1.0 (1.0, 1.0, 255).
+    A new contiguous tensor.  The kernels do this in gi2d_pixel_format.h::pixel_convert."""
+    fmt = _format(dtype, layout) or _DEFAULT_FORMAT
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.float32 or img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError("convert: a float32 [H, W, 3] tensor")
+    c = img.clamp(0, 1)
+    if fmt.dtype == torch.uint8:
+        c = torch.where(torch.isnan(c), torch.zeros_like(c), c * 255.0).round().to(torch.uint8)
+    elif fmt.dtype == torch.float16:
+        c = c.to(torch.float16)
+    if fmt.layout == "chw":
+        return c.permute(2, 0, 1).contiguous()
+    if fmt.layout == "hwc4":
+        one = 255 if fmt.dtype == torch.uint8 else 1.0
+        return torch.cat([c, torch.full_like(c[..., :1], one)], dim=2).contiguous()
+    return c.contiguous()
+
+
 class _Picture(NamedTuple):
     """What one launch sequence draws, derived once (_picture) from (header, view or None)."""
     header: Dict[str, object]
@@ -1020,12 +1098,14 @@ class Decoder:
         return fixed
 
     # ---------------------------------------------------------------------------------------------- launches
-    def _launch(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, aux=None) -> None:
+    def _launch(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, aux=None,
+                fmt: Optional[_Format] = None) -> None:
         """Workspace reset + decode/bin + forward + clamp of a coding-0 payload on the current stream, at the picture's
-        size, with the status row at `status`; no host sync and no allocation."""
+        size, with the status row at `status`; no host sync and no allocation.  With a format: workspace reset +
+        decode/bin + gi2d_codec_draw, whose epilogue is the clamp, the conversion and the layout."""
         h, view, w, hh, tx, ty = pic
         if isinstance(view, Overview):
-            return self._launch_overview(pic, payload, status, out, aux)
+            return self._launch_overview(pic, payload, status, out, aux, fmt=fmt)
         n = h["num_points"]
         b = h["bits"]
         side = (C.c_float * 16)(*h["side"])
@@ -1042,16 +1122,21 @@ class Decoder:
                       C.c_void_p(payload.data_ptr()), h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"],
                       view.x0, view.y0, view.scale, hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3], a[4], ws, nws,
                       status, st)
+        if fmt is not None:
+            _lib.call("gi2d_codec_draw", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws, status,
+                      *fmt.ids, C.c_void_p(out.data_ptr()), st)
+            return
         _lib.call("gi2d_fast_rasterize_forward", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws,
                   status, None, None, C.c_void_p(out.data_ptr()), st)
         out.clamp_(0, 1)
 
     def _launch_overview(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, aux=None,
-                         capacity: Optional[int] = None) -> None:
+                         capacity: Optional[int] = None, fmt: Optional[_Format] = None) -> None:
         """An overview of a coding-0 payload on the current stream: gi2d_codec_decode_overview (record -> transformed,
         prefiltered gaussian -> covariance projection), gi2d_bin_gaussians into lists of `capacity` entries (its status
         {count, overflow} goes to words 0 and 1 of the row at `status`), gi2d_rasterize_forward_long (whole lists, clamp
-        fused, ones if the count is 0); no host sync and no allocation (_reserve_overview has been called)."""
+        fused, ones if the count is 0; with a format gi2d_rasterize_forward_long_as, the same kernel ending in the
+        format's stores); no host sync and no allocation (_reserve_overview has been called)."""
         h, ov, w, hh, tx, ty = pic
         n = h["num_points"]
         b = h["bits"]
@@ -1068,15 +1153,19 @@ class Decoder:
                   hh, w, tx, ty, h["radius_clip"], geo[0], geo[1], geo[2], geo[3], geo[4], st)
         _lib.call("gi2d_bin_gaussians", n, cap, geo[0], geo[1], tx, ty, ov.radius_clip(h), ids, bins, status,
                   C.c_void_p(o["binws"].data_ptr()), o["binws"].numel(), st)
+        if fmt is not None:
+            _lib.call("gi2d_rasterize_forward_long_as", n, cap, tx, ty, w, hh, ids, bins, tx * ty, geo[0], geo[2], geo[4],
+                      None, status, *fmt.ids, C.c_void_p(out.data_ptr()), st)
+            return
         _lib.call("gi2d_rasterize_forward_long", n, cap, tx, ty, w, hh, ids, bins, tx * ty, geo[0], geo[2], geo[4], None,
                   status, C.c_void_p(out.data_ptr()), st)
 
-    def _out(self, pic: _Picture, out: Optional[torch.Tensor]) -> torch.Tensor:
-        shape = (pic.height, pic.width, 3)
+    def _out(self, pic: _Picture, out: Optional[torch.Tensor], fmt: Optional[_Format] = None) -> torch.Tensor:
+        fmt = fmt or _DEFAULT_FORMAT
+        shape = fmt.shape(pic.height, pic.width)
         if out is None:
-            return torch.empty(shape, dtype=torch.float32, device=self.dev)
-        if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.dev or not out.is_contiguous():
-            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {self.dev}")
+            return torch.empty(shape, dtype=fmt.dtype, device=self.dev)
+        _check_out(out, shape, fmt.dtype, self.dev)
         return out
 
     def _aux(self, n: int):
@@ -1084,31 +1173,38 @@ class Decoder:
         i = lambda *s: torch.empty(s, dtype=torch.int32, device=self.dev)
         return [f(n, 2), i(n), f(n, 3), i(n), f(n, 3)]
 
-    def _exact(self, pic: _Picture, fixed: torch.Tensor, out: torch.Tensor) -> None:
+    def _exact(self, pic: _Picture, fixed: torch.Tensor, out: torch.Tensor, fmt: Optional[_Format] = None) -> None:
         """A tile row overflowed: the same picture through the capacity-free ops (gi2d_bin_gaussians + the plain
         rasterizer), fed with the decode kernel's per-gaussian outputs for the coding-0 payload `fixed` (for a view: the
-        transformed geometry, at the view's size and with its radius_clip)."""
+        transformed geometry, at the view's size and with its radius_clip).  With a format the float32 picture is
+        converted into `out` by gi2d_codec_convert."""
         from .gsplat import _raster_common as rc
         h, w, hh = pic.header, pic.width, pic.height
         n = h["num_points"]
         aux = self._aux(n)
-        self._launch(pic, fixed, self._status.data_ptr(), torch.empty_like(out), aux)
+        self._launch(pic, fixed, self._status.data_ptr(), torch.empty(hh, w, 3, dtype=torch.float32, device=self.dev), aux)
         xys, radii, conics, _, colors = aux
         tb = rc.tile_bounds_of(hh, w, _TILE, _TILE)
         opacity = torch.ones(n, 1, dtype=torch.float32, device=self.dev)
         img = rc._exact_forward(h["kind"] == KIND_COVARIANCE, xys, radii, conics, colors, opacity, hh, w, tb,
                                 (_TILE, _TILE, 1), (w, hh, 1), self._background, pic.radius_clip, False)[0]
-        torch.clamp(img, 0, 1, out=out)
+        if fmt is None:
+            torch.clamp(img, 0, 1, out=out)
+        else:
+            img = img.contiguous()
+            _lib.call("gi2d_codec_convert", *fmt.ids, hh, w, C.c_void_p(img.data_ptr()), C.c_void_p(out.data_ptr()),
+                      _stream(self.dev))
 
     def _run(self, groups, outs: Optional[Sequence[torch.Tensor]] = None, views_only: bool = False,
-             geometry: bool = False):
+             geometry: bool = False, fmt: Optional[_Format] = None):
         """The host driver of every decode call -> (images, aux).  groups: [(stream, [view or None, ...])], a picture per
         entry; `outs`: a tensor per picture, in call order.  Everything is parsed and checked before anything touches
         the device; a rANS payload is expanded once per group, into its slice of `_expanded` (valid until the next call);
         every picture has its own status row, and the rows are read in ONE host wait behind the last picture; a picture
         whose tile row overflowed is then drawn again (_exact), an overview whose tile lists outgrew their buffer likewise
         (_launch_overview with the count the status row reports).  geometry (one group, one picture): the per-gaussian
-        outputs of the decode kernel are kept, and the picture stays the fast path's own."""
+        outputs of the decode kernel are kept, and the picture stays the fast path's own.  fmt: the pictures' format
+        (None: float32 [H, W, 3] through the launches there were before there were formats)."""
         who, what = ("decode_views", "view") if views_only else ("decode_many", "stream")
         streams = [s for s, _ in groups]
         headers = [s.header if isinstance(s, DeviceStream) else _parse(s) for s in streams]
@@ -1129,7 +1225,7 @@ class Decoder:
                 total += (h["fixed_payload_bytes"] + 255) & ~255 if h["coding"] != CODING_FIXED else 0
             if self._expanded.numel() < total:
                 self._expanded = torch.empty(total, dtype=torch.uint8, device=self.dev)
-            images = [self._out(p, None if outs is None else outs[i]) for i, p in enumerate(pictures)]
+            images = [self._out(p, None if outs is None else outs[i], fmt) for i, p in enumerate(pictures)]
             aux = self._aux(headers[0]["num_points"]) if geometry else None
             self._next_token()
             row0 = self._status.data_ptr()
@@ -1141,7 +1237,7 @@ class Decoder:
                                            self._expanded[s:s + h["fixed_payload_bytes"]])
                 for _ in views:
                     row = len(fixed)
-                    self._launch(pictures[row], payload, row0 + _STATUS_ROW * row, images[row], aux)
+                    self._launch(pictures[row], payload, row0 + _STATUS_ROW * row, images[row], aux, fmt)
                     fixed.append(payload)
             status = self._status[:len(pictures), 0:5].tolist()  # the one host wait of a call: M, overflow, .., .., rANS
             for row in coded:
@@ -1151,30 +1247,34 @@ class Decoder:
                     self._overview_m = max(self._overview_m, m)
                     if overflow:  # the lists were cut at the capacity: the same picture again with room for all m
                         self._reserve_overview([pictures[row]], m)
-                        self._launch_overview(pictures[row], fixed[row], row0 + _STATUS_ROW * row, images[row], aux, m)
+                        self._launch_overview(pictures[row], fixed[row], row0 + _STATUS_ROW * row, images[row], aux, m, fmt)
                 elif overflow and not geometry:
-                    self._exact(pictures[row], fixed[row], images[row])
+                    self._exact(pictures[row], fixed[row], images[row], fmt)
         return images, aux
 
     # ---------------------------------------------------------------------------------------------- public
-    def decode(self, stream, out: Optional[torch.Tensor] = None, view: Optional[View] = None) -> torch.Tensor:
+    def decode(self, stream, out: Optional[torch.Tensor] = None, view: Optional[View] = None, dtype=None,
+               layout=None) -> torch.Tensor:
         """bytes (or an uploaded DeviceStream) -> f32 [H, W, 3] in [0, 1]; `out`: a tensor to write into.  view: a
         codec.View -> f32 [view.height, view.width, 3], the window of the fitted function it names (View.full: the
-        bits of the plain decode, through the view kernel); a codec.Overview -> the reduced, low-passed picture it names."""
+        bits of the plain decode, through the view kernel); a codec.Overview -> the reduced, low-passed picture it names.
+        dtype (torch.float32, torch.float16, torch.uint8), layout ("hwc", "chw", "hwc4"): the picture's format --
+        codec.convert of the picture above, written by the draw kernel itself; `out` must have the format's shape and type."""
         if view is None:
-            return self.decode_many([stream], None if out is None else [out])[0]
-        return self.decode_views(stream, [view], None if out is None else [out])[0]
+            return self.decode_many([stream], None if out is None else [out], dtype=dtype, layout=layout)[0]
+        return self.decode_views(stream, [view], None if out is None else [out], dtype=dtype, layout=layout)[0]
 
-    def decode_views(self, stream, views: Sequence[View], outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    def decode_views(self, stream, views: Sequence[View], outs: Optional[Sequence[torch.Tensor]] = None, dtype=None,
+                     layout=None) -> List[torch.Tensor]:
         """Several views of ONE stream back to back on the current stream of the device: the payload is staged once, a
         rANS payload expanded once, the workspace reserved for the largest view, and the statuses are read once, at the
-        end.  Views and Overviews may be mixed."""
-        return self._run([(stream, list(views))], outs, views_only=True)[0]
+        end.  Views and Overviews may be mixed.  dtype, layout: the format of every picture (decode)."""
+        return self._run([(stream, list(views))], outs, views_only=True, fmt=_format(dtype, layout))[0]
 
-    def decode_many(self, streams, outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    def decode_many(self, streams, outs: Optional[Sequence[torch.Tensor]] = None, dtype=None, layout=None) -> List[torch.Tensor]:
         """Streams decoded back to back on the current stream of the device; the overflow statuses are read once, at the
-        end."""
-        return self._run([(s, (None,)) for s in streams], outs)[0]
+        end.  dtype, layout: the format of every picture (decode)."""
+        return self._run([(s, (None,)) for s in streams], outs, fmt=_format(dtype, layout))[0]
 
     def decode_geometry(self, stream, view: Optional[View] = None) -> Dict[str, torch.Tensor]:
         """What the decode kernel makes of every gaussian: xys, radii, conics, num_tiles_hit, colors (tests, tools); with
@@ -1189,13 +1289,18 @@ _decoders: Dict[torch.device, Decoder] = {}
 
 
 def decode(blob, device: Union[str, torch.device] = "cuda:0", out: Optional[torch.Tensor] = None,
-           view: Optional[View] = None) -> torch.Tensor:
+           view: Optional[View] = None, dtype=None, layout=None) -> torch.Tensor:
     """One-shot decode (a Decoder per device is kept behind the scenes); view: a codec.View or codec.Overview of the
-    picture."""
-    _checked_view(view, _parse(blob))  # a malformed stream or view is refused before a device is even touched
+    picture; dtype, layout: the picture's format (Decoder.decode)."""
+    h = _parse(blob)
+    view = _checked_view(view, h)  # a malformed stream, view, format or `out` is refused before a device is even touched
+    fmt = _format(dtype, layout)
+    if out is not None:
+        pic = _picture(h, view)
+        _check_out(out, (fmt or _DEFAULT_FORMAT).shape(pic.height, pic.width), (fmt or _DEFAULT_FORMAT).dtype)
     dev = torch.device(device)
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
     if dev not in _decoders:
         _decoders[dev] = Decoder(dev)
-    return _decoders[dev].decode(blob, out=out, view=view)
+    return _decoders[dev].decode(blob, out=out, view=view, dtype=dtype, layout=layout)

@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "gi2d_codec_layout.h"
+#include "gi2d_pixel_format.h"
 #include "gi2d_quant_core.h"
 
 namespace gi2d {
@@ -132,12 +133,18 @@ __device__ __forceinline__ void long_pair(const LongLds &sm, int k, float px, fl
 // torch.clamp(x, 0, 1): a NaN stays a NaN
 __device__ __forceinline__ float clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
 
-template <bool SKIP>
+static_assert(sizeof(float4) * GI2D_LONG_BATCH >= 4 * GI2D_PIXEL_STAGE_BYTES, "LongLds::a holds the four waves' staged strips");
+
+// DTYPE, LAYOUT: the picture format (gi2d_pixel_format.h).  float32 "hwc" is the kernel as it was before there were formats:
+// its epilogue is spelled out below, clamp01 and three dword stores per lane.
+template <bool SKIP, int DTYPE = GI2D_PIXEL_F32, int LAYOUT = GI2D_LAYOUT_HWC>
 __global__ __launch_bounds__(256) void raster_fwd_long_kernel(
     int n, int capacity, int tiles_x, int img_w, int img_h, const int32_t *__restrict__ gids_sorted,
     const int2 *__restrict__ tile_bins, int tile_bins_rows, const float2 *__restrict__ xys,
     const float *__restrict__ conics, const float *__restrict__ colors, const float *__restrict__ opacities,
-    const int32_t *__restrict__ status, float *__restrict__ out_img) {
+    const int32_t *__restrict__ status, void *__restrict__ out) {
+    constexpr bool PLAIN = DTYPE == GI2D_PIXEL_F32 && LAYOUT == GI2D_LAYOUT_HWC;
+    float *out_img = reinterpret_cast<float *>(out);  // (PLAIN only)
     __shared__ LongLds sm;
     const int tile = blockIdx.x;
     const int tx = tile % tiles_x, ty = tile / tiles_x;
@@ -146,7 +153,13 @@ __global__ __launch_bounds__(256) void raster_fwd_long_kernel(
     const bool inside = i < img_h && j < img_w;
     const size_t pix = (size_t)i * img_w + j;
     if (status != nullptr && status[0] < 1) {  // not a single intersection: the background picture (ones)
-        if (inside) out_img[3 * pix] = 1.f, out_img[3 * pix + 1] = 1.f, out_img[3 * pix + 2] = 1.f;
+        if constexpr (PLAIN) {
+            if (inside) out_img[3 * pix] = 1.f, out_img[3 * pix + 1] = 1.f, out_img[3 * pix + 2] = 1.f;
+        } else {  // (nothing has been staged: any part of the LDS is free)
+            pixel_store_strip<DTYPE, LAYOUT>(1.f, 1.f, 1.f, lane & 15, lane >> 4, tx, ty * GI2D_TILE + wv * 4, img_w, img_h,
+                                             (tx + 1) * GI2D_TILE <= img_w && (ty + 1) * GI2D_TILE <= img_h,
+                                             reinterpret_cast<char *>(sm.a) + wv * GI2D_PIXEL_STAGE_BYTES, out);
+        }
         return;
     }
     int2 range = make_int2(0, 0);
@@ -214,10 +227,16 @@ __global__ __launch_bounds__(256) void raster_fwd_long_kernel(
         }
         __syncthreads();  // the batch is consumed: the next one may be staged
     }
-    if (inside) {
-        out_img[3 * pix] = clamp01(o0);
-        out_img[3 * pix + 1] = clamp01(o1);
-        out_img[3 * pix + 2] = clamp01(o2);
+    if constexpr (PLAIN) {
+        if (inside) {
+            out_img[3 * pix] = clamp01(o0);
+            out_img[3 * pix + 1] = clamp01(o1);
+            out_img[3 * pix + 2] = clamp01(o2);
+        }
+    } else {  // (every batch is consumed -- the loop ends behind a workgroup barrier -- so the staging arrays are free)
+        pixel_store_strip<DTYPE, LAYOUT>(o0, o1, o2, lane & 15, lane >> 4, tx, ty * GI2D_TILE + wv * 4, img_w, img_h,
+                                         (tx + 1) * GI2D_TILE <= img_w && (ty + 1) * GI2D_TILE <= img_h,
+                                         reinterpret_cast<char *>(sm.a) + wv * GI2D_PIXEL_STAGE_BYTES, out);
     }
 }
 
@@ -282,15 +301,16 @@ int gi2d_codec_decode_overview(int kind, int n, int xy_bits, int p0_bits, int p1
     return check_launch(what);
 }
 
-int gi2d_rasterize_forward_long(int n, int capacity, int tiles_x, int tiles_y, unsigned w, unsigned h,
-                                const int32_t *gids, const int32_t *bins, int rows, const float *xys, const float *conics,
-                                const float *colors, const float *opac, const int32_t *status, float *out_img,
-                                gi2d_stream_t st) {
+int gi2d_rasterize_forward_long_as(int n, int capacity, int tiles_x, int tiles_y, unsigned w, unsigned h,
+                                   const int32_t *gids, const int32_t *bins, int rows, const float *xys,
+                                   const float *conics, const float *colors, const float *opac, const int32_t *status,
+                                   int dtype, int layout, void *out, gi2d_stream_t st) {
     const char *what = "rasterize forward long";
     const auto fail = [&](const char *why) {
         set_error((std::string(what) + ": " + why).c_str());
         return GI2D_ERR_INVALID_ARGUMENT;
     };
+    if (!pixel_format_ok(dtype, layout)) return fail("unknown picture format (dtype 0..2, layout 0..2)");
     if (n < 0 || capacity < 0 || tiles_x < 0 || tiles_y < 0 || rows < 0) return fail("negative size");
     if (capacity > 0x7fffffff - GI2D_LONG_BATCH) return fail("capacity too large for 32-bit list positions");
     if ((long long)tiles_x * GI2D_TILE < (long long)w || (long long)tiles_y * GI2D_TILE < (long long)h)
@@ -299,16 +319,28 @@ int gi2d_rasterize_forward_long(int n, int capacity, int tiles_x, int tiles_y, u
     if (t == 0 || w == 0 || h == 0) return GI2D_OK;
     if (t > 0x7fffffffLL || w > 0x7fffffffu || h > 0x7fffffffu) return fail("tile grid too large");
     if (n == 0) capacity = 0, rows = 0;  // no gaussian: no list is read
-    if (!out_img || (rows > 0 && !bins) || (capacity > 0 && rows > 0 && (!gids || !xys || !conics || !colors)))
+    if (!out || (rows > 0 && !bins) || (capacity > 0 && rows > 0 && (!gids || !xys || !conics || !colors)))
         return fail("null pointer");
 #ifdef GI2D_LONG_NO_SKIP /* development variant: the walk without the per-wave skip (timing aid) */
-    const auto kernel = raster_fwd_long_kernel<false>;
+    constexpr bool skip = false;
 #else
-    const auto kernel = raster_fwd_long_kernel<true>;
+    constexpr bool skip = true;
 #endif
-    hipLaunchKernelGGL(kernel, dim3((unsigned)t), dim3(256), 0, (hipStream_t)st, n, capacity, tiles_x, (int)w, (int)h,
-                       gids, (const int2 *)bins, rows, (const float2 *)xys, conics, colors, opac, status, out_img);
+#define GI2D_LONG(D, L)                                                                                                  \
+    hipLaunchKernelGGL((raster_fwd_long_kernel<skip, D, L>), dim3((unsigned)t), dim3(256), 0, (hipStream_t)st, n,        \
+                       capacity, tiles_x, (int)w, (int)h, gids, (const int2 *)bins, rows, (const float2 *)xys, conics,   \
+                       colors, opac, status, out)
+    GI2D_FOR_FORMAT(dtype, layout, GI2D_LONG)
+#undef GI2D_LONG
     return check_launch(what);
+}
+
+int gi2d_rasterize_forward_long(int n, int capacity, int tiles_x, int tiles_y, unsigned w, unsigned h,
+                                const int32_t *gids, const int32_t *bins, int rows, const float *xys, const float *conics,
+                                const float *colors, const float *opac, const int32_t *status, float *out_img,
+                                gi2d_stream_t st) {
+    return gi2d_rasterize_forward_long_as(n, capacity, tiles_x, tiles_y, w, h, gids, bins, rows, xys, conics, colors, opac,
+                                          status, GI2D_PIXEL_F32, GI2D_LAYOUT_HWC, out_img, st);
 }
 
 }  // extern "C"

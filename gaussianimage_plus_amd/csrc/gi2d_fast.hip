@@ -541,23 +541,6 @@ __global__ __launch_bounds__(256) void fast_reduce_project_kernel(
     store_proj_grad(g, KIND == kScaleRot, r, v_cov2d, v_mean2d, v_p0, v_p1);
 }
 
-static int check_ws(const char *what, void *ws, size_t ws_bytes, int n, int tiles_x, int tiles_y) {
-    if (n < 0 || tiles_x < 0 || tiles_y < 0) {
-        set_error("fast path: negative size");
-        return GI2D_ERR_INVALID_ARGUMENT;
-    }
-    if ((long long)tiles_x * tiles_y * GI2D_FAST_LROW > 0x7fffffffLL || (long long)n * GI2D_FAST_S > 0x7fffffffLL ||
-        tiles_x > 0xffff || tiles_y > 0xffff) {
-        set_error("fast path: problem too large for 32-bit slot indices");
-        return GI2D_ERR_UNSUPPORTED;
-    }
-    if (!ws || ws_bytes < carve_fast(nullptr, n, tiles_x * tiles_y).bytes) {
-        set_error(what);
-        return GI2D_ERR_WORKSPACE_TOO_SMALL;
-    }
-    return GI2D_OK;
-}
-
 }  // namespace gi2d
 
 using namespace gi2d;

@@ -218,6 +218,23 @@ static inline bool wt_fits(const FastWs &w, int num_tiles, size_t image_bytes) {
     const size_t packed_span = (size_t)(num_tiles > 0 ? num_tiles : 1) * GI2D_TILE_LIST_CAP * sizeof(GaussRec);
     return rows_span < 0xffff0000ull && packed_span < 0xffff0000ull && image_bytes < 0xffff0000ull;
 }
+// What every C entry on a fast-path workspace checks first (`what`: its message for a workspace that is too small).
+static inline int check_ws(const char *what, void *ws, size_t ws_bytes, int n, int tiles_x, int tiles_y) {
+    if (n < 0 || tiles_x < 0 || tiles_y < 0) {
+        set_error("fast path: negative size");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    if ((long long)tiles_x * tiles_y * GI2D_FAST_LROW > 0x7fffffffLL || (long long)n * GI2D_FAST_S > 0x7fffffffLL ||
+        tiles_x > 0xffff || tiles_y > 0xffff) {
+        set_error("fast path: problem too large for 32-bit slot indices");
+        return GI2D_ERR_UNSUPPORTED;
+    }
+    if (!ws || ws_bytes < carve_fast(nullptr, n, tiles_x * tiles_y).bytes) {
+        set_error(what);
+        return GI2D_ERR_WORKSPACE_TOO_SMALL;
+    }
+    return GI2D_OK;
+}
 // Bytes of the inbox buffer of an image of `num_tiles` tiles (0: such an image does without, Inbox above).
 static inline size_t inbox_bytes(long long num_tiles) {
     if (num_tiles < 1 || num_tiles > GI2D_INBOX_MAX_TILES) return 0;

@@ -669,6 +669,46 @@ int gi2d_rasterize_forward_long(int num_points, int capacity, int tiles_x, int t
                                 int tile_bins_rows, const float *xys, const float *conics, const float *colors,
                                 const float *opacities, const int32_t *status, float *out_img, gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ picture formats of a decode
+ * A decoded picture leaves in one of nine formats, an element type times a layout.  With
+ * clamp(x) = x < 0 ? 0 : (x > 1 ? 1 : x)  (torch.clamp(x, 0, 1): a NaN stays a NaN) an element is
+ *   GI2D_PIXEL_F32   clamp(x)
+ *   GI2D_PIXEL_F16   clamp(x) rounded to nearest even        (torch: x.clamp(0, 1).to(torch.float16))
+ *   GI2D_PIXEL_U8    rint(clamp(x) * 255.0f), narrowed: ONE fp32 multiply, round half to even, never + 0.5 and truncate;
+ *                    NaN -> 0                                 (torch: (x.clamp(0, 1) * 255).round().to(torch.uint8))
+ * and the layouts are
+ *   GI2D_LAYOUT_HWC  [H, W, 3]      GI2D_LAYOUT_CHW  [3, H, W]      GI2D_LAYOUT_HWC4  [H, W, 4], channel 3 = the element of 1.0
+ * (1.0f, 1.0h, 255).  `out` is a contiguous array of that shape and type whose base is aligned to its element size and
+ * nothing more: every store wider than an element is guarded by a test of the base, the row pitch and the tile's place in
+ * the image, and nothing is written outside the array.  F32 / HWC is the picture the calls without a format give, clamped.
+ *   gi2d_codec_draw   the decode's own tile pass on a workspace that gi2d_codec_decode_bin or gi2d_codec_decode_bin_view
+ *                     has filled: the arguments of gi2d_fast_rasterize_forward without final_Ts / final_idx, plus the
+ *                     format.  Same list head, staging and pixel routine, so the fp32 sums are that call's bit for bit, and
+ *                     lists, tile_bins, record-set versions and status words (overflow, "any member", the background
+ *                     picture when nothing intersects) are left as that call leaves them; it writes no packed record and no
+ *                     gradient row, so no backward pass can follow it.  The clamp, the conversion and the layout are the
+ *                     kernel's epilogue.
+ *   gi2d_rasterize_forward_long_as   gi2d_rasterize_forward_long with a format (that call is F32 / HWC of this one).
+ *   gi2d_codec_convert   src f32[H,W,3] -> dst in the format, one pixel per lane (what a decoder's fallback ends in).
+ * All three refuse (-1, gi2d_last_error_string set) before any HIP call: a dtype or layout outside 0..2, a NULL out / src /
+ * dst / status / workspace, a tile grid that does not cover the image. */
+#define GI2D_PIXEL_F32 0
+#define GI2D_PIXEL_F16 1
+#define GI2D_PIXEL_U8 2
+#define GI2D_LAYOUT_HWC 0
+#define GI2D_LAYOUT_CHW 1
+#define GI2D_LAYOUT_HWC4 2
+int gi2d_codec_draw(int num_points, int tiles_x, int tiles_y, unsigned img_width, unsigned img_height,
+                    const float *background, void *workspace, size_t workspace_bytes, int32_t *status, int dtype,
+                    int layout, void *out, gi2d_stream_t stream);
+int gi2d_rasterize_forward_long_as(int num_points, int capacity, int tiles_x, int tiles_y, unsigned img_width,
+                                   unsigned img_height, const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                                   int tile_bins_rows, const float *xys, const float *conics, const float *colors,
+                                   const float *opacities, const int32_t *status, int dtype, int layout, void *out,
+                                   gi2d_stream_t stream);
+int gi2d_codec_convert(int dtype, int layout, unsigned img_height, unsigned img_width, const float *src_hwc, void *dst,
+                       gi2d_stream_t stream);
+
 /* ------------------------------------------------------------------ rANS payload (payload codings 1 and 2 of format 1)
  * The records of coding 0, entropy coded: gaussianimage_plus_amd/codec.py owns the container (tag "rANS", model section,
  * chunk directory, chunk data; INTEGRATION.md has the table) and validates all of it on the host.  A field of width w is

@@ -29,10 +29,19 @@ to the only route there is without overviews (`route_us`): the full decode follo
 (mode="area") to the thumbnail's size.  Same regions, same discipline; --out-json writes the JSON line to a file too
 (profiles/decode_overview_time.json).
 
+--format DTYPE,LAYOUT (repeatable; float32 | float16 | uint8, hwc | chw | hwc4) adds, per fit and format, with the payload
+on the device: `format_us`, Decoder.decode(stream, dtype=, layout=) -- workspace reset + decode/bin + the decode's own
+draw kernel, which ends in the clamp, the conversion and the layout -- next to `route_us`, the only other route: today's
+float32 decode followed by codec.convert in torch.  For float32,hwc the row also holds `default_us`, today's default
+decode (fitting forward + clamp launch), timed in the same run: the draw kernel against it is the number that decides
+which of the two the default should be.  With --trace the formats are decoded too, so that the kernel trace holds the
+draw kernel next to fast_fwd_kernel and the clamp.  Same regions, same discipline (profiles/decode_format_time.json).
+
     python tools/decode_time.py [--reps 200] [--coding fixed|rans|rans-delta] [--order fit position]
                                 [--chunk-log2 10 8 12] [--trace]
                                 [--view 256,128,256,256,1 --view 256,128,1024,1024,4 --view 0,0,1536,1024,2]
                                 [--overview] [--out-json profiles/decode_overview_time.json]
+                                [--format uint8,hwc4 --format float16,chw --format float32,hwc]
 --trace decodes a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for
 the per-kernel split (profiles/decode_kernel_stats.csv).
 """
@@ -163,6 +172,29 @@ def overview_rows(a, dec, up, full):
     return rows
 
 
+def parse_format(text):
+    dtype, layout = text.split(",")
+    dtypes = {"float32": torch.float32, "float16": torch.float16, "uint8": torch.uint8}
+    if dtype not in dtypes or layout not in codec.LAYOUTS:
+        raise argparse.ArgumentTypeError(f"{text!r}: float32 | float16 | uint8, then hwc | chw | hwc4")
+    return dtypes[dtype], layout
+
+
+def format_rows(a, dec, up, full):
+    rows = []
+    for dtype, layout in a.format:
+        ref = dec.decode(up, out=full)
+        fout = torch.empty_like(codec.convert(ref, dtype, layout))
+        assert torch.equal(dec.decode(up, out=fout, dtype=dtype, layout=layout), codec.convert(ref, dtype, layout))
+        r = {"dtype": str(dtype).replace("torch.", ""), "layout": layout, "bytes_per_picture": fout.numel() * fout.element_size()}
+        timed(r, "format", lambda: dec.decode(up, out=fout, dtype=dtype, layout=layout), a.reps)
+        timed(r, "route", lambda: codec.convert(dec.decode(up, out=full), dtype, layout), a.reps)
+        if (dtype, layout) == (torch.float32, "hwc"):
+            timed(r, "default", lambda: dec.decode(up, out=full), a.reps)
+        rows.append(r)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
@@ -174,6 +206,7 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--view", type=parse_view, action="append", default=[], metavar="x0,y0,w,h,scale")
     ap.add_argument("--overview", action="store_true")
+    ap.add_argument("--format", type=parse_format, action="append", default=[], metavar="DTYPE,LAYOUT")
     ap.add_argument("--out-json", default=None, metavar="PATH")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_time.py needs the GPU"
@@ -203,6 +236,9 @@ def main():
             for u in ups:
                 for _ in range(50):
                     dec.decode(u, out=out)
+            for dtype, layout in a.format:
+                for _ in range(50):
+                    dec.decode(up, dtype=dtype, layout=layout)
             torch.cuda.synchronize()
             continue
         info = codec.info(blob)
@@ -246,6 +282,8 @@ def main():
             row["views"].append(r)
         if a.overview:
             row["overviews"] = overview_rows(a, dec, up, out)
+        if a.format:
+            row["formats"] = format_rows(a, dec, up, out)
         res["sizes"][str(n)] = row
     if not a.trace:
         print(json.dumps(res))
