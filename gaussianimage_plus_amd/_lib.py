@@ -87,6 +87,8 @@ SIGNATURES.update({
     "gi2d_codec_draw": [_i, _i, _i, _u, _u, _p, _p, _sz, _p, _i, _i, _p, _p],
     "gi2d_rasterize_forward_long_as": [_i, _i, _i, _i, _u, _u, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p],
     "gi2d_codec_convert": [_i, _i, _u, _u, _p, _p, _p],
+    # several pictures per decode launch: host array of struct gi2d_codec_picture (gaussianimage_plus_amd/codec.py::_CPicture)
+    "gi2d_codec_decode_batch": [_i, _p, _p, _sz, _u, _u, _i, _i, _p, _i, _i, _p, _p],
     # rANS payload (payload coding 1)
     "gi2d_codec_histogram": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p],
     "gi2d_codec_rans_encode": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _sz, _p, _sz, _p, _p],
@@ -113,6 +115,8 @@ SIZE_FUNCS = {
     "gi2d_batch_bytes": [_i],
     "gi2d_train_inbox_bytes": [_i, _i],
     "gi2d_codec_payload_bytes": [_i, _i, _i, _i, _i, _i],
+    "gi2d_codec_batch_bytes": [_i],
+    "gi2d_codec_decode_workspace_bytes": [_i, _i, _i],
     "gi2d_codec_rans_scratch_bytes": [_i, _i, _i, _i, _i, _i, _i, _u],
     "gi2d_ssim_workspace_bytes": [_i, _i, _i, _i],
     "gi2d_ssim_batch_workspace_bytes": [_i, _p, _i, _i],

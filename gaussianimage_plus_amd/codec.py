@@ -19,6 +19,9 @@
     rgba = dec.decode(blob, dtype=torch.uint8, layout="hwc4")    # u8 [H, W, 4], alpha 255: what a viewer or a file writer takes
     x    = dec.decode(blob, dtype=torch.float16, layout="chw")   # f16 [3, H, W]: what a network takes (any view, any call)
     codec.convert(img, torch.uint8, "hwc4")      # the same conversion in plain torch, on any device: its specification
+    crops = [codec.View(x0, y0, 224, 224) for x0, y0 in origins]                  # one window per stream, all at one size
+    batch = dec.decode_batch(blobs, crops, dtype=torch.float16, layout="chw")     # f16 [K, 3, 224, 224]: a network's batch,
+                                                 # three launches per 64 pictures, picture k bit for bit decode(blobs[k], view=crops[k], ...)
 
 Decoding needs no fitter, no target image and no optimizer state: this module imports neither `trainer` nor `quantize`.
 A decode is three native launches on buffers the Decoder owns -- gi2d_fast_workspace_init, gi2d_codec_decode_bin
@@ -27,6 +30,8 @@ A decode is three native launches on buffers the Decoder owns -- gi2d_fast_works
 status is looked at ONCE, after the image has been enqueued; an overflowing stream (more than 1024 candidate gaussians in
 one 16x16 tile) is rendered again through the capacity-free ops, so a valid stream always decodes.  Every decode call
 (decode, decode_many, decode_views, decode_geometry) is one host driver, Decoder._run, on a list of pictures.
+decode_batch draws its pictures together: gi2d_codec_decode_batch (csrc/gi2d_codec_batch.hip) makes the reset, the
+decode/bin and the draw launch once for up to 64 pictures, each with a decode workspace and a status row of its own.
 
 A view is a decoder argument, never stream content.  Output pixel (row i, column j) samples the fitted
 function at source position (x0 + j / scale, y0 + i / scale): every dequantised gaussian is moved and scaled into the
@@ -82,7 +87,7 @@ import dataclasses
 import math
 import struct
 import zlib
-from typing import Dict, List, NamedTuple, Optional, Sequence, Union
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -948,6 +953,40 @@ def _picture(h, view: Optional[View]) -> _Picture:
     return _Picture(h, view, w, hh, _tiles(w), _tiles(hh))
 
 
+BATCH_MAX = 64  # GI2D_BATCH_MAX: pictures per gi2d_codec_decode_batch call
+
+
+def batch_shape(headers, views=None) -> Tuple[int, int]:
+    """(height, width) of the pictures of a decode_batch call, on the host: headers are parsed streams (codec.info, or
+    a DeviceStream's header), views None or one entry per header (None, a codec.View or a codec.Overview, each checked
+    against its header).  ValueError for an empty batch, a views list of another length, an entry that is no view, and
+    for the first picture whose size is not picture 0's."""
+    headers = list(headers)
+    if not headers:
+        raise ValueError("decode_batch: an empty batch has no size")
+    views = [None] * len(headers) if views is None else list(views)
+    if len(views) != len(headers):
+        raise ValueError(f"decode_batch: {len(views)} views for {len(headers)} streams (one entry per stream, or views=None)")
+    size = None
+    for k, (h, v) in enumerate(zip(headers, views)):
+        p = _picture(h, _checked_view(v, h))
+        if size is None:
+            size = (p.height, p.width)
+        elif (p.height, p.width) != size:
+            raise ValueError(f"decode_batch: picture {k} is {p.width}x{p.height}, picture 0 is {size[1]}x{size[0]}: every "
+                             "picture of a batch has one size (give the others a codec.View)")
+    return size
+
+
+class _CPicture(C.Structure):
+    """struct gi2d_codec_picture of include/gi2d.h."""
+    _fields_ = [("kind", C.c_int), ("num_points", C.c_int), ("xy_bits", C.c_int), ("p0_bits", C.c_int),
+                ("p1_bits", C.c_int), ("color_bits", C.c_int), ("side", C.c_float * 16), ("payload", C.c_void_p),
+                ("payload_bytes", C.c_size_t), ("clip_coe", C.c_float), ("img_height", C.c_uint), ("img_width", C.c_uint),
+                ("view", C.c_int), ("x0", C.c_float), ("y0", C.c_float), ("scale", C.c_float), ("radius_clip", C.c_float),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("status", C.c_void_p)]
+
+
 _STATUS_WORDS = 8
 _STATUS_ROW = 4 * _STATUS_WORDS  # bytes; a launch is given the device address of its row, a plain integer
 
@@ -993,6 +1032,10 @@ class Decoder:
         self._ov: Dict[str, torch.Tensor] = {}
         self.overview_capacity: Optional[int] = None  # entries the tile lists of an overview start with (None: see below)
         self._overview_m = 0  # the largest number of intersections an overview of this Decoder has had
+        # decode_batch: the pictures' decode workspaces side by side and the device table, regrown when a call needs more
+        self._batch_ws = torch.empty(0, dtype=torch.uint8, device=self.dev)
+        self._batch_table = torch.empty(0, dtype=torch.uint8, device=self.dev)
+        self.batch_redrawn: List[int] = []  # pictures of the last decode_batch call that were drawn again (overflow)
 
     # ---------------------------------------------------------------------------------------------- buffers
     def _reserve_workspace(self, pictures: Sequence[_Picture]) -> None:
@@ -1252,6 +1295,110 @@ class Decoder:
                     self._exact(pictures[row], fixed[row], images[row], fmt)
         return images, aux
 
+    # ---------------------------------------------------------------------------------------------- batches
+    def _batch_groups(self, pictures: Sequence[_Picture]):
+        """The rows gi2d_codec_decode_batch draws together: runs of consecutive pictures that are no overviews (a call
+        writes its pictures one behind the other), at most BATCH_MAX each -> [(rows, [workspace bytes of each])]."""
+        size = _lib.load().gi2d_codec_decode_workspace_bytes
+        groups = []
+        for row, p in enumerate(pictures):
+            if isinstance(p.view, Overview):
+                continue
+            if not groups or groups[-1][0][-1] != row - 1 or len(groups[-1][0]) == BATCH_MAX:
+                groups.append(([], []))
+            groups[-1][0].append(row)
+            groups[-1][1].append((int(size(p.header["num_points"], p.tx, p.ty)) + 255) & ~255)
+        return groups
+
+    def _launch_batch(self, rows, sizes, pictures, fixed, row0: int, out: torch.Tensor, fmt: _Format) -> None:
+        """gi2d_codec_decode_batch for pictures `rows` (consecutive) of a call: table writers, workspace reset, decode/bin
+        and draw, each once for all of them; no host sync and no allocation."""
+        arr = (_CPicture * len(rows))()
+        ws = self._batch_ws.data_ptr()
+        for d, row, nws in zip(arr, rows, sizes):
+            h, view, _, _, _, _ = pictures[row]
+            b = h["bits"]
+            d.kind, d.num_points, d.xy_bits, d.p0_bits, d.p1_bits, d.color_bits = h["kind"], h["num_points"], *b
+            d.side = (C.c_float * 16)(*h["side"])
+            d.payload, d.payload_bytes = fixed[row].data_ptr(), h["fixed_payload_bytes"]
+            d.clip_coe, d.img_height, d.img_width = h["clip_coe"], h["height"], h["width"]
+            if view is not None:
+                d.view, d.x0, d.y0, d.scale = 1, view.x0, view.y0, view.scale
+            d.radius_clip = pictures[row].radius_clip
+            d.workspace, d.workspace_bytes, d.status = ws, nws, row0 + _STATUS_ROW * row
+            ws += nws
+        p = pictures[rows[0]]
+        _lib.call("gi2d_codec_decode_batch", len(rows), arr, C.c_void_p(self._batch_table.data_ptr()),
+                  self._batch_table.numel(), p.height, p.width, p.tx, p.ty, C.c_void_p(self._background.data_ptr()),
+                  *fmt.ids, C.c_void_p(out[rows[0]].data_ptr()), _stream(self.dev))
+
+    def decode_batch(self, streams, views=None, out: Optional[torch.Tensor] = None, dtype=None, layout=None) -> torch.Tensor:
+        """K streams (bytes or uploaded DeviceStreams, any coding) -> ONE tensor [K, *format shape]: picture k is, bit for
+        bit, decode(streams[k], view=views[k], dtype=dtype or torch.float32, layout=layout or "hwc").  views: None, or K
+        entries, each None, a codec.View or a codec.Overview; every picture must come out at one height x width
+        (batch_shape).  Pictures that are no overviews are drawn by gi2d_codec_decode_batch, up to 64 per call: three
+        launches for all of them instead of three each.  An Overview has launches of its own kind and is drawn into its
+        slice as decode draws it.  out: a contiguous tensor of that shape and the format's dtype on this device.  The
+        status rows are read in one host wait behind the last launch; a picture whose tile row overflowed is drawn again
+        into its slice (batch_redrawn lists them), its neighbours are left alone."""
+        streams = list(streams)
+        headers = [s.header if isinstance(s, DeviceStream) else _parse(s) for s in streams]
+        views = [None] * len(headers) if views is None else list(views)
+        height, width = batch_shape(headers, views)
+        pictures = [_picture(h, v) for h, v in zip(headers, views)]
+        fmt = _format(dtype, layout) or _DEFAULT_FORMAT
+        shape = (len(pictures),) + tuple(fmt.shape(height, width))
+        if out is not None:
+            _check_out(out, shape, fmt.dtype, self.dev)
+        groups = self._batch_groups(pictures)
+        with torch.cuda.device(self.dev):
+            payloads = self._stage(streams, headers)
+            if self._status.shape[0] < len(pictures):
+                self._status = torch.zeros(len(pictures), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
+            self._reserve_overview(pictures)
+            need = max([sum(sizes) for _, sizes in groups], default=0)
+            if self._batch_ws.numel() < need:
+                self._batch_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            need = int(_lib.load().gi2d_codec_batch_bytes(max([len(rows) for rows, _ in groups], default=1)))
+            if self._batch_table.numel() < need:
+                self._batch_table = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            slices, total = [], 0
+            for h in headers:
+                slices.append(total)
+                total += (h["fixed_payload_bytes"] + 255) & ~255 if h["coding"] != CODING_FIXED else 0
+            if self._expanded.numel() < total:
+                self._expanded = torch.empty(total, dtype=torch.uint8, device=self.dev)
+            if out is None:
+                out = torch.empty(shape, dtype=fmt.dtype, device=self.dev)
+            self._next_token()
+            row0 = self._status.data_ptr()
+            fixed = []  # the coding-0 payload of every picture
+            for row, (h, payload, s) in enumerate(zip(headers, payloads, slices)):
+                if h["coding"] != CODING_FIXED:
+                    payload = self._expand(h, payload, row0 + _STATUS_ROW * row, self._expanded[s:s + h["fixed_payload_bytes"]])
+                fixed.append(payload)
+            for row, p in enumerate(pictures):
+                if isinstance(p.view, Overview):
+                    self._launch_overview(p, fixed[row], row0 + _STATUS_ROW * row, out[row], fmt=fmt)
+            for rows, sizes in groups:
+                self._launch_batch(rows, sizes, pictures, fixed, row0, out, fmt)
+            status = self._status[:len(pictures), 0:5].tolist()  # the one host wait of a call
+            self.batch_redrawn = []
+            for row, (h, (m, overflow, _, _, word)) in enumerate(zip(headers, status)):
+                if h["coding"] != CODING_FIXED:
+                    self._check_expanded(word)
+                if isinstance(pictures[row].view, Overview):
+                    self._overview_m = max(self._overview_m, m)
+                    if overflow:
+                        self._reserve_overview([pictures[row]], m)
+                        self._launch_overview(pictures[row], fixed[row], row0 + _STATUS_ROW * row, out[row], None, m, fmt)
+                        self.batch_redrawn.append(row)
+                elif overflow:
+                    self._reserve_workspace([pictures[row]])
+                    self._exact(pictures[row], fixed[row], out[row], fmt)
+                    self.batch_redrawn.append(row)
+        return out
+
     # ---------------------------------------------------------------------------------------------- public
     def decode(self, stream, out: Optional[torch.Tensor] = None, view: Optional[View] = None, dtype=None,
                layout=None) -> torch.Tensor:
@@ -1304,3 +1451,20 @@ def decode(blob, device: Union[str, torch.device] = "cuda:0", out: Optional[torc
     if dev not in _decoders:
         _decoders[dev] = Decoder(dev)
     return _decoders[dev].decode(blob, out=out, view=view, dtype=dtype, layout=layout)
+
+
+def decode_batch(blobs, device: Union[str, torch.device] = "cuda:0", views=None, out: Optional[torch.Tensor] = None,
+                 dtype=None, layout=None) -> torch.Tensor:
+    """One-shot Decoder.decode_batch (the Decoder kept per device): K streams -> one [K, *format shape] tensor."""
+    blobs, views = list(blobs), None if views is None else list(views)
+    # malformed streams, views, sizes, formats and `out` are refused before a device is even touched
+    height, width = batch_shape([b.header if isinstance(b, DeviceStream) else _parse(b) for b in blobs], views)
+    fmt = _format(dtype, layout) or _DEFAULT_FORMAT
+    if out is not None:
+        _check_out(out, (len(blobs),) + tuple(fmt.shape(height, width)), fmt.dtype)
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if dev not in _decoders:
+        _decoders[dev] = Decoder(dev)
+    return _decoders[dev].decode_batch(blobs, views=views, out=out, dtype=dtype, layout=layout)

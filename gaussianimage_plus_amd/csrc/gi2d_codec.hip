@@ -17,9 +17,7 @@
 // every load index is clamped to the dwords the entry has checked the payload to hold.
 #include <cmath>
 
-#include "gi2d_codec_layout.h"
-#include "gi2d_fast_internal.h"
-#include "gi2d_quant_core.h"
+#include "gi2d_codec_core.h"
 
 namespace gi2d {
 
@@ -62,34 +60,7 @@ __global__ __launch_bounds__(GI2D_CODEC_PACK_BLOCK) void codec_pack_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------- decode + bin
-struct CodecOut {  // optional per-gaussian outputs (all may be NULL)
-    float2 *xys;
-    int32_t *radii;
-    float *conics;
-    int32_t *num_tiles_hit;
-    float *colors;
-};
-
-// A window on the fitted function: output pixel (row i, column j) samples source position (x0 + j / scale,
-// y0 + i / scale).  Carried out on the gaussians, in separate fp32 operations (codec.view_parameters restates them):
-//   x' = (x - x0) * scale, y' = (y - y0) * scale; covariance entries * (scale * scale); the two scales of the scale-rot
-//   model * scale, its rotation as it is; colour untouched.
-struct CodecView {
-    float x0, y0, scale;
-};
-template <int KIND>
-__device__ __forceinline__ void view_transform(float (&v)[GI2D_CODEC_FIELDS], const CodecView vw) {
-#pragma clang fp contract(off)
-    v[0] = (v[0] - vw.x0) * vw.scale;
-    v[1] = (v[1] - vw.y0) * vw.scale;
-    if (KIND == kCovariance) {
-        const float s2 = vw.scale * vw.scale;
-        v[2] = v[2] * s2, v[3] = v[3] * s2, v[4] = v[4] * s2;
-    } else {
-        v[2] = v[2] * vw.scale, v[3] = v[3] * vw.scale;
-    }
-}
-
+// (CodecOut, CodecView, view_transform and the per-gaussian body: gi2d_codec_core.h, shared with the batched decode)
 // img_w / img_h / tiles / radius_clip: those of the picture that is drawn (for a view: the window's size and the
 // header's radius_clip * scale, so that what the full decode drops as too small stays dropped).  VIEW = false never reads
 // `vw`: the full decode's instantiations have the instructions they had before there were views.
@@ -97,49 +68,13 @@ template <int KIND, bool VIEW>
 __global__ __launch_bounds__(256) void codec_decode_bin_kernel(
     int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
     float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, CodecOut out, BinTarget bt, CodecView vw) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    begin_binning(g, bt.status);
-    const BinRecs recs = recs_for_binning(bt.recs, g == 0);
-    if (g >= n) return;
-    const PrevBox old_box = bt.prev_box[g];
-    // the record: dwords first, first + 1, ... (all requested before the first use; `loads` is the same for every lane)
-    const long long bit0 = (long long)g * lay.record_bits;
-    const long long first = bit0 >> 5;
-    uint32_t w[GI2D_CODEC_MAX_LOADS];
-#pragma unroll
-    for (int j = 0; j < GI2D_CODEC_MAX_LOADS; ++j) {
-        const long long d = first + j;
-        w[j] = j < lay.loads ? payload[d < last_dword ? d : last_dword] : 0u;
-    }
-    const uint32_t s0 = (uint32_t)bit0 & 31u;
-    uint32_t r[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], s0);
-    float v[GI2D_CODEC_FIELDS];
-#pragma unroll
-    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
-        const float code = (float)((int)codec_take(r, lay.width[k]) + lay.qmin[k]);
-        // the variances of a covariance row are log-quantised (HybirdQuant), everything else is LSQ
-        v[k] = (KIND == kCovariance && (k == 2 || k == 4)) ? quant_dequant<GI2D_QUANT_LOG>(code, side.scale[k], side.beta[k])
-                                                          : quant_dequant<GI2D_QUANT_LSQ>(code, side.scale[k], side.beta[k]);
-    }
-    if (VIEW) view_transform<KIND>(v, vw);
-    const ProjOut o = project_values<KIND>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h, tiles_x,
-                                           tiles_y, radius_clip);
-    if (out.xys) out.xys[g] = o.xy;
-    if (out.radii) out.radii[g] = o.radius;
-    if (out.conics) out.conics[3 * g] = o.k0, out.conics[3 * g + 1] = o.k1, out.conics[3 * g + 2] = o.k2;
-    if (out.num_tiles_hit) out.num_tiles_hit[g] = o.tiles_hit;
-    if (out.colors) out.colors[3 * g] = v[5], out.colors[3 * g + 1] = v[6], out.colors[3 * g + 2] = v[7];
-    bin_projected(g, o, 1.f, v[5], v[6], v[7], tiles_x, tiles_y, radius_clip, old_box, bt.prev_box, bt.lists, recs);
+    codec_decode_bin_one<KIND, VIEW>(blockIdx.x * blockDim.x + threadIdx.x, n, lay, side, payload, last_dword, clip_coe, img_w,
+                                     img_h, tiles_x, tiles_y, radius_clip, out, bt, vw);
 }
 
 }  // namespace gi2d
 
 using namespace gi2d;
-
-#define GI2D_CODEC_VIEW_MAX_SCALE 64
-#define GI2D_CODEC_VIEW_MAX_TILES 16384
 
 // Checks and launch shared by the two decode entries.  h, w_, tiles, radius_clip: those of the picture that is drawn;
 // view: the window of gi2d_codec_decode_bin_view (already checked), NULL for the full decode.
@@ -249,22 +184,8 @@ int gi2d_codec_decode_bin_view(int kind, int n, int xy_bits, int p0_bits, int p1
                                int tiles_x, int tiles_y, float radius_clip, float *xys, int32_t *radii, float *conics,
                                int32_t *num_tiles_hit, float *colors, void *ws, size_t ws_bytes, int32_t *status,
                                gi2d_stream_t st) {
-    // the conditions on a view, in double on the fp32 values the kernel receives
-    const char *why = nullptr;
-    if (!std::isfinite(scale) || scale < 1.f || scale > (float)GI2D_CODEC_VIEW_MAX_SCALE)
-        why = "codec decode view: scale must be finite and in 1 .. 64 (a reduced view overfills the 256 entries of a tile)";
-    else if (!std::isfinite(x0) || !std::isfinite(y0) || x0 < 0.f || y0 < 0.f)
-        why = "codec decode view: the origin must be finite and not negative";
-    else if (out_w < 1 || out_h < 1)
-        why = "codec decode view: empty output";
-    else if ((double)x0 + (double)out_w / (double)scale > (double)w_ ||
-             (double)y0 + (double)out_h / (double)scale > (double)h)
-        why = "codec decode view: the window reaches beyond the picture";
-    else if (((unsigned long long)out_w + GI2D_TILE - 1) / GI2D_TILE * (((unsigned long long)out_h + GI2D_TILE - 1) / GI2D_TILE) >
-             (unsigned long long)GI2D_CODEC_VIEW_MAX_TILES)
-        why = "codec decode view: more than 16384 tiles in one view (compose larger outputs from several views)";
-    if (why) {
-        set_error(why);
+    if (const char *why = codec_view_refused(x0, y0, scale, out_h, out_w, h, w_)) {
+        set_error((std::string("codec decode view: ") + why).c_str());
         return GI2D_ERR_INVALID_ARGUMENT;
     }
     const CodecView vw{x0, y0, scale};

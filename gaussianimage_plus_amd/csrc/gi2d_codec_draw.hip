@@ -10,48 +10,11 @@
 // Both convert through gi2d_pixel_format.h::pixel_convert, the one definition of the arithmetic.
 #include <string>
 
-#include "gi2d_fast_internal.h"
-#include "gi2d_pixel_format.h"
+#include "gi2d_codec_core.h"
 
 namespace gi2d {
 
-static_assert(sizeof(float) * GI2D_FWD_PAIRBUF >= GI2D_PIXEL_STAGE_BYTES, "a wave stages its strip in its pair buffer");
-static_assert(sizeof(float4) * GI2D_FWD_PAIRBUF >= sizeof(int) * GI2D_FAST_C, "the id buffer of the list head overlays the pair buffers");
-
-// phases 2-4 of the forward for one tile whose `len` (<= 256) entries are staged in ascending order: the sibling of
-// gi2d_raster_core.h::fwd_rasterize_staged<false> that stores a formatted picture.  Must be called by all 256 lanes
-// after a __syncthreads() that follows the staging.
-template <int DTYPE, int LAYOUT>
-__device__ __forceinline__ void draw_rasterize_staged(FwdLds &sm, int len, int tx, int ty, int img_w, int img_h,
-                                                      bool background_fill, const float *__restrict__ background,
-                                                      void *__restrict__ out) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int lx = fwd_lane_col(lane), r = lane >> 4;  // the pixel this lane holds after the forward
-    const int i0 = ty * GI2D_TILE + wv * 4;
-    float *mybuf = reinterpret_cast<float *>(sm.pairbuf) + wv * GI2D_FWD_PAIRBUF_OF(false);
-    float o0, o1, o2;
-    int last_k;
-    fwd_pixel_half_lists<false>(
-        sm.lists[wv], mybuf, len, [&](int k) { return sm.cullw[k]; },
-        [&](int k) {
-            const float4 A = sm.AB[2 * k], B = sm.AB[2 * k + 1];
-            FwdRec rec;
-            rec.gx = A.x, rec.gy = A.y, rec.ha = A.z, rec.hb = A.w, rec.hc = B.x, rec.op = B.y, rec.cr = B.z, rec.cg = B.w;
-            const float2 c = sm.C[k];
-            rec.cb = c.x, rec.lim = (unsigned)__float_as_int(c.y);
-            return rec;
-        },
-        (float)(tx * GI2D_TILE), (float)(i0 + r), o0, o1, o2, last_k);
-    if (background_fill) {  // rasterize_sum_plus.py:110-118: no intersections at all -> image = background
-        o0 = background[0];
-        o1 = background[1];
-        o2 = background[2];
-    }
-    // (the pair buffer is free: the wave's trips are done -- fwd_pixel_half_lists ends behind a wave barrier)
-    const bool tile_inside = (tx + 1) * GI2D_TILE <= img_w && (ty + 1) * GI2D_TILE <= img_h;
-    pixel_store_strip<DTYPE, LAYOUT>(o0, o1, o2, lx, r, tx, i0, img_w, img_h, tile_inside, mybuf, out);
-}
-
+// (draw_rasterize_staged and the tile's body, codec_draw_tile: gi2d_codec_core.h, shared with the batched decode)
 template <int DTYPE, int LAYOUT>
 __global__ __launch_bounds__(256) void codec_draw_kernel(
     int tiles_x, int tiles_y, int img_w, int img_h, RecSets rs, const float *__restrict__ background,
@@ -59,32 +22,8 @@ __global__ __launch_bounds__(256) void codec_draw_kernel(
     float4 *__restrict__ partial_big, int32_t *__restrict__ status, void *__restrict__ out) {
     __shared__ FwdLds sm;
     __shared__ int grp[32];
-    int *ids = reinterpret_cast<int *>(sm.pairbuf);  // id buffer of the head: dead before the pair buffers are first written
-    const int tile = blockIdx.x;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int tid = threadIdx.x;
-    const float4 *recs = recs_for_tile_pass(rs, blockIdx.x == 0 && tid == 0);
-    if (tid == 0) fwd_stage_dummy(sm);
-    const float tx0 = (float)(tx * GI2D_TILE), ty0 = (float)(ty * GI2D_TILE);
-    const int L = tile_list_head<false>(
-        ids, grp, tile, tx, ty, recs, lists, tile_bins, status, [&](int, const BinRec &br) { return br; },
-        [&](int rank, int g, const BinRec &br) {
-            const GaussRec &r = br.r;
-            // no gradient row is written, but a row pool that ran out is reported as the fitting forward reports it
-            // (partial_row raises the status word and touches nothing else)
-            (void)partial_row(partial_slot(g, br.box, tx, ty, br.pool), partial_g, partial_big,
-                              tiles_x * tiles_y * GI2D_TILE_LIST_CAP, status);
-            if (rank < GI2D_TILE_LIST_CAP) {
-                const AlphaRule ar = alpha_rule(r.gx, r.gy, r.a, r.b, r.c, r.opac);
-                fwd_stage_entry(sm, rank, r, cull_word_ext(r.gx, r.gy, br.hx, br.hy, tx0, ty0, img_h, ar.clamp), ar.lim);
-            }
-        }, Inbox{nullptr}, head_row_load(lists, tile, false));
-    __syncthreads();
-    const int len = L > GI2D_TILE_LIST_CAP ? GI2D_TILE_LIST_CAP : L;
-    // "no intersection at all" (image = background): what the binning step noted (fast_fwd_kernel has the reasoning)
-    const bool nothing = background != nullptr && !tile_pass_has_members(rs);
-    draw_rasterize_staged<DTYPE, LAYOUT>(sm, len, tx, ty, img_w, img_h, nothing, background, out);
-    if (tid == 0 && L > 0) status[0] = 1;
+    codec_draw_tile<DTYPE, LAYOUT>(sm, grp, (int)blockIdx.x, blockIdx.x == 0, tiles_x, tiles_y, img_w, img_h, rs, background,
+                                   lists, tile_bins, partial_g, partial_big, status, out);
 }
 
 template <int DTYPE, int LAYOUT>

@@ -709,6 +709,52 @@ int gi2d_rasterize_forward_long_as(int num_points, int capacity, int tiles_x, in
 int gi2d_codec_convert(int dtype, int layout, unsigned img_height, unsigned img_width, const float *src_hwc, void *dst,
                        gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ batched decode (DESIGN.md 3.8 "Batches")
+ * K streams -> K pictures of ONE size and format in three launches: what the batched fitting calls above do for a fit,
+ * for the decoder.  Picture k is, bit for bit, what workspace init + gi2d_codec_decode_bin (view = 0) or
+ * gi2d_codec_decode_bin_view (view = 1) + gi2d_codec_draw give for the same stream: the batched kernels are made of the
+ * same device routines, and a workgroup looks its picture up in a table in HBM.
+ *   gi2d_codec_picture   one picture: the stream (kind, N, bit widths, the 16 side-information floats, coding-0 payload on
+ *                        the device, clip_coe, the SOURCE picture's size), its window (view = 0: the whole picture, whose
+ *                        size must then be the call's; view = 1: x0, y0, scale as in gi2d_codec_decode_bin_view),
+ *                        radius_clip as the kernels are to use it (the stream's value; for a view the stream's value *
+ *                        scale in fp32, the product gi2d_codec_decode_bin_view forms itself), its own workspace of
+ *                        gi2d_codec_decode_workspace_bytes(N, tiles_x, tiles_y) bytes (16-byte aligned) and its own status
+ *                        row (words 0..3 as the single-picture calls leave them).
+ *   gi2d_codec_decode_workspace_bytes   the decode workspace: list rows, tile bins, previous boxes, version words and the two
+ *                        record sets of a fast-path workspace -- what the three kernels touch -- without a fit's packed
+ *                        records, gradient rows and row pool.  NOT a workspace for any other fast-path call.  A size
+ *                        query (0 for a negative argument).
+ *   gi2d_codec_batch_bytes   the device table of a call of `num_pictures` (16-byte aligned), rewritten by every call with
+ *                        stream-ordered kernels that carry it as kernel arguments; a size query.
+ *   gi2d_codec_decode_batch   1 <= num_pictures <= 64.  Picture k is written at out + k * (bytes of one picture of the
+ *                        format); out_height, out_width, the tile grid, the format and the background (3 floats on the
+ *                        device, or NULL) are the call's.  After the table's writers: a reset of all K workspaces, one
+ *                        decode/bin kernel over sum(max(1, ceil(N_k / 256))) workgroups, one draw kernel over K * tiles_x *
+ *                        tiles_y workgroups; no host synchronisation, capturable in a graph.  Refuses (-1,
+ *                        gi2d_last_error_string set) before any HIP call: K out of range, a NULL pointer, an unknown format,
+ *                        a tile grid that does not cover the picture, a table or workspace that is too small, a stream or a
+ *                        view the single-picture calls refuse, two pictures that share a workspace or a status row. */
+typedef struct gi2d_codec_picture {
+    int kind, num_points, xy_bits, p0_bits, p1_bits, color_bits;
+    float side[16];
+    const void *payload;
+    size_t payload_bytes;
+    float clip_coe;
+    unsigned img_height, img_width;
+    int view;
+    float x0, y0, scale;
+    float radius_clip;
+    void *workspace;
+    size_t workspace_bytes;
+    int32_t *status;
+} gi2d_codec_picture;
+size_t gi2d_codec_batch_bytes(int num_pictures);
+size_t gi2d_codec_decode_workspace_bytes(int num_points, int tiles_x, int tiles_y);
+int gi2d_codec_decode_batch(int num_pictures, const gi2d_codec_picture *pictures, void *batch, size_t batch_bytes,
+                            unsigned out_height, unsigned out_width, int tiles_x, int tiles_y, const float *background,
+                            int dtype, int layout, void *out, gi2d_stream_t stream);
+
 /* ------------------------------------------------------------------ rANS payload (payload codings 1 and 2 of format 1)
  * The records of coding 0, entropy coded: gaussianimage_plus_amd/codec.py owns the container (tag "rANS", model section,
  * chunk directory, chunk data; INTEGRATION.md has the table) and validates all of it on the host.  A field of width w is

@@ -37,11 +37,17 @@ decode (fitting forward + clamp launch), timed in the same run: the draw kernel 
 which of the two the default should be.  With --trace the formats are decoded too, so that the kernel trace holds the
 draw kernel next to fast_fwd_kernel and the clamp.  Same regions, same discipline (profiles/decode_format_time.json).
 
+--batch adds, per fit, `batches`: Decoder.decode_batch of K = 1, 8 and 64 uploaded streams in float16 "chw" (`batch_us`) next
+to Decoder.decode_many of the same streams in the same format (`many_us`), and K = 64 with a 224x224 codec.View per
+picture at distinct origins, scale 1, next to Decoder.decode_views of the same views -- all as microseconds PER PICTURE
+(a region is `reps` calls of K pictures).  Same regions, same discipline (profiles/decode_batch_time.json).  With --trace
+the K = 64 batch and the 64 single decodes are run a few times, for the per-kernel split.
+
     python tools/decode_time.py [--reps 200] [--coding fixed|rans|rans-delta] [--order fit position]
                                 [--chunk-log2 10 8 12] [--trace]
                                 [--view 256,128,256,256,1 --view 256,128,1024,1024,4 --view 0,0,1536,1024,2]
                                 [--overview] [--out-json profiles/decode_overview_time.json]
-                                [--format uint8,hwc4 --format float16,chw --format float32,hwc]
+                                [--format uint8,hwc4 --format float16,chw --format float32,hwc] [--batch]
 --trace decodes a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for
 the per-kernel split (profiles/decode_kernel_stats.csv).
 """
@@ -195,6 +201,35 @@ def format_rows(a, dec, up, full):
     return rows
 
 
+BATCH_FORMAT = dict(dtype=torch.float16, layout="chw")
+
+
+def batch_views(k):
+    """k 224x224 windows of the 768x512 picture at distinct origins, scale 1."""
+    return [codec.View(68.0 * (i % 8) + 0.5 * (i // 8), 36.0 * (i // 8) + 0.25 * (i % 8), 224, 224, 1.0) for i in range(k)]
+
+
+def batch_rows(a, dec, up):
+    rows = []
+    for k, views in ((1, None), (8, None), (64, None), (64, batch_views(64))):
+        streams = [up] * k
+        out = dec.decode_batch(streams, views, **BATCH_FORMAT).clone()
+        if views is None:
+            many = lambda: dec.decode_many(streams, **BATCH_FORMAT)
+        else:
+            many = lambda: dec.decode_views(up, views, **BATCH_FORMAT)
+        assert torch.equal(torch.stack(many()), out)
+        r = {"pictures": k, "view": None if views is None else [224, 224, 1.0], "format": ["float16", "chw"],
+             "launches_batch": 3 + -(-k // 14) + 1, "launches_many": 3 * k}
+        for key, fn in (("batch", lambda: dec.decode_batch(streams, views, out=out, **BATCH_FORMAT)), ("many", many)):
+            med, lo, hi, regions = median_us(fn, a.reps)
+            r[key + "_us"] = round(med / k, 2)  # per picture
+            r[key + "_us_range"] = [round(lo / k, 2), round(hi / k, 2)]
+            r[key + "_us_regions"] = [round(x / k, 2) for x in regions]
+        rows.append(r)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
@@ -207,6 +242,7 @@ def main():
     ap.add_argument("--view", type=parse_view, action="append", default=[], metavar="x0,y0,w,h,scale")
     ap.add_argument("--overview", action="store_true")
     ap.add_argument("--format", type=parse_format, action="append", default=[], metavar="DTYPE,LAYOUT")
+    ap.add_argument("--batch", action="store_true")
     ap.add_argument("--out-json", default=None, metavar="PATH")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_time.py needs the GPU"
@@ -239,6 +275,10 @@ def main():
             for dtype, layout in a.format:
                 for _ in range(50):
                     dec.decode(up, dtype=dtype, layout=layout)
+            if a.batch:
+                for _ in range(10):
+                    dec.decode_batch([up] * 64, **BATCH_FORMAT)
+                    dec.decode_many([up] * 64, **BATCH_FORMAT)
             torch.cuda.synchronize()
             continue
         info = codec.info(blob)
@@ -284,6 +324,8 @@ def main():
             row["overviews"] = overview_rows(a, dec, up, out)
         if a.format:
             row["formats"] = format_rows(a, dec, up, out)
+        if a.batch:
+            row["batches"] = batch_rows(a, dec, up)
         res["sizes"][str(n)] = row
     if not a.trace:
         print(json.dumps(res))
