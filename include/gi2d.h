@@ -520,9 +520,12 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
  *                     optional) accumulates the number dropped.  Nothing moves when nothing is pruned.
  *   gi2d_train_grow   add_sample_positions + densification_postfix (train.py:85-118, :307-350 of the model): the
  *                     k = max(0, min(budget_cap, max_points - live count)) pixels of the last render (out_img) with the
- *                     largest summed absolute error, in (error descending, pixel index ascending) order, become
+ *                     largest summed absolute error, in (error descending, pixel index ascending) order -- of the
+ *                     pixels that tie with the k-th largest error, the lowest indices -- become
  *                     centres of new gaussians with covariance rand3[r] + (0.5, 0, 0.5), colour 0, opacity 1, zero
  *                     optimizer moments and the low-pass bound of the new population; non-definite draws are skipped.
+ *                     k is further clamped to rand_rows and to the number of pixels: a budget above that number takes
+ *                     every pixel once.  Nothing moves and neither count changes when k is 0.
  *                     rand3 f32[rand_rows,3]: uniform numbers (row r belongs to the r-th selected pixel); budget_cap =
  *                     1000, or max_points at the last growth step of a run (train.py:91-97); *added (device, optional)
  *                     accumulates the number appended.
