@@ -104,11 +104,15 @@ SIGNATURES.update({
     "gi2d_ssim_backward": [_p, _p, _p, _p, _i, _i, _i, _p, _f, _f, _f, _i, _p, _i, _p, _p, _p, _p, _p, _sz, _p],
     "gi2d_ssim_forward_batched": [_i, _p, _i, _p, _f, _f, _f, _i, _p, _i, _p, _p, _sz, _p],
     "gi2d_ssim_backward_batched": [_i, _p, _i, _p, _f, _f, _f, _i, _p, _i, _p, _p, _p, _sz, _p],
+    # N-channel sum rasterizer (1..GI2D_ND_MAX_CHANNELS colour channels; gsplat.cuda.nd_rasterize_sum_*)
+    "gi2d_nd_rasterize_sum_forward": [_i, _i, _u, _u, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "gi2d_nd_rasterize_sum_backward": [_i, _i, _u, _u, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p],
 })
 SIZE_FUNCS = {
     "gi2d_fast_workspace_bytes": [_i, _i, _i],
     "gi2d_sort_workspace_bytes": [_i, _i],
     "gi2d_rasterize_backward_workspace_bytes": [_i, _i],
+    "gi2d_nd_rasterize_backward_workspace_bytes": [_i, _i, _i],
     "gi2d_bin_workspace_bytes": [_i, _i],
     "gi2d_quant_workspace_bytes": [_i],
     "gi2d_densify_scratch_bytes": [_p, _i],

@@ -23,6 +23,7 @@
 // Roofline: algorithmic HBM bytes are 40*M + 20*H*W (fwd) and 40*M + 16*H*W + 36*N (bwd)
 // (SURVEY 8d); every staged gaussian is reused by up to 256 pixels, so the kernels are bound by
 // VALU issue (v_exp_f32 + ~25 fp32 ops per pixel-gaussian pair), not by HBM.
+#include "gi2d_gidx.h"
 #include "gi2d_raster_core.h"
 
 namespace gi2d {
@@ -181,26 +182,8 @@ __global__ __launch_bounds__(256) void gather_bbox_kernel(
     if (g < n) store_grads(g, acc, v_xy, v_conic, v_rgb, v_opacity, v_abs_xy);
 }
 
-// Generic form: rebuild the gaussian-major index from gaussian_ids_sorted.
-__global__ __launch_bounds__(256) void gidx_count_kernel(int m, int n,
-                                                         const int32_t *__restrict__ gids_sorted,
-                                                         int32_t *__restrict__ counts) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= m) return;
-    const int g = gids_sorted[p];
-    if (g >= 0 && g < n) atomicAdd(&counts[g], 1);
-}
-__global__ __launch_bounds__(256) void gidx_scatter_kernel(int m, int n,
-                                                           const int32_t *__restrict__ gids_sorted,
-                                                           const int32_t *__restrict__ start,
-                                                           int32_t *__restrict__ cursor,
-                                                           int32_t *__restrict__ gslots) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= m) return;
-    const int g = gids_sorted[p];
-    if (g < 0 || g >= n) return;
-    gslots[start[g] + atomicAdd(&cursor[g], 1)] = p;
-}
+// Generic form: rebuild the gaussian-major index from gaussian_ids_sorted (gi2d_gidx.h: gidx_count_kernel,
+// gidx_scatter_kernel -- shared with the N-channel backward).
 #define GI2D_ORDERED_MAX 64 /* gaussians on <= 64 tiles are summed in ascending position order */
 __global__ __launch_bounds__(256) void gather_generic_kernel(int n, int m,
                                                              const int32_t *__restrict__ start,
@@ -259,9 +242,6 @@ static BwdWs carve_bwd_ws(void *base, int n, int m) {
     w.bytes = off;
     return w;
 }
-
-int launch_exclusive_scan_with_cursor(int n, const int32_t *counts, int32_t *start, int32_t *cursor,
-                                      hipStream_t st);  // gi2d_binning.hip
 
 static int raster_forward(int tiles_x, int tiles_y, unsigned w, unsigned h, const int32_t *gids,
                           const int32_t *bins, int rows, const float *xys, const float *conics,

@@ -329,6 +329,73 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> rasterize_sum_plus_backward(
     return std::make_tuple(o.v_xy, o.v_conic, o.v_colors, o.v_opacity);
 }
 
+// ------------------------------------------------------------------------------------------ N-channel sum rasterizer
+int nd_channels(const Tensor &colors) {
+    TORCH_CHECK(colors.dim() == 2, "colors must have 2 dimensions");  // bindings.cu:877-879
+    const int64_t c = colors.size(1);
+    TORCH_CHECK(c >= 1 && c <= GI2D_ND_MAX_CHANNELS, "colors has ", c, " channels; supported are 1..",
+                GI2D_ND_MAX_CHANNELS, " (GI2D_ND_MAX_CHANNELS)");
+    return (int)c;
+}
+// bindings.cu:776-842 -> (out_img[H,W,C], final_Ts, final_idx)
+std::tuple<Tensor, Tensor, Tensor> nd_rasterize_sum_forward(dim3_t tile_bounds, dim3_t block, dim3_t img_size, Tensor &gids,
+                                                            Tensor &tile_bins, Tensor &xys, Tensor &conics,
+                                                            Tensor &colors, Tensor &opacities, Tensor &background,
+                                                            const c10::optional<Tensor> &num_intersects_dev) {
+    GI2D_CHECK_I32(gids);
+    GI2D_CHECK_I32(tile_bins);
+    GI2D_CHECK_F32(xys);
+    GI2D_CHECK_F32(conics);
+    GI2D_CHECK_F32(colors);
+    GI2D_CHECK_F32(opacities);
+    GI2D_CHECK_F32(background);
+    check_block(block);
+    const int c = nd_channels(colors);
+    TORCH_CHECK(background.numel() == c, "background must have ", c, " elements, got ", background.numel());
+    const int w = std::get<0>(img_size), h = std::get<1>(img_size);
+    Tensor out_img = f32(xys, {h, w, c}), final_Ts = f32(xys, {h, w}), final_idx = i32(xys, {h, w});
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(xys.device());
+    check(gi2d_nd_rasterize_sum_forward(std::get<0>(tile_bounds), std::get<1>(tile_bounds), (unsigned)w, (unsigned)h, c,
+                                        ip(gids), ip(tile_bins), (int)tile_bins.size(0), fp(xys), fp(conics), fp(colors),
+                                        fp(opacities), fp(background),
+                                        num_intersects_dev ? ip(*num_intersects_dev) : nullptr,
+                                        final_Ts.data_ptr<float>(), final_idx.data_ptr<int32_t>(),
+                                        out_img.data_ptr<float>(), stream_of(xys)),
+          "nd_rasterize_sum_forward");
+    return std::make_tuple(out_img, final_Ts, final_idx);
+}
+// bindings.cu:852-930 -> (v_xy, v_conic, v_colors[N,C], v_opacity[N,1]); background, final_Ts, final_idx and
+// v_output_alpha are accepted and ignored (the forward writes final_idx = end - 1: the reference's gate excludes nothing)
+std::tuple<Tensor, Tensor, Tensor, Tensor> nd_rasterize_sum_backward(
+    unsigned img_height, unsigned img_width, unsigned block_h, unsigned block_w, Tensor &gids, Tensor &tile_bins,
+    Tensor &xys, Tensor &conics, Tensor &colors, Tensor &opacities, const c10::optional<Tensor> &background,
+    const c10::optional<Tensor> &final_Ts, const c10::optional<Tensor> &final_idx, Tensor &v_output,
+    const c10::optional<Tensor> &v_output_alpha) {
+    GI2D_CHECK_F32(xys);
+    GI2D_CHECK_F32(colors);
+    TORCH_CHECK(xys.dim() == 2 && xys.size(1) == 2, "xys must have dimensions (num_points, 2)");  // bindings.cu:873
+    const int c = nd_channels(colors);
+    check_block(dim3_t((int)block_w, (int)block_h, 1));
+    GI2D_CHECK_I32(gids);
+    GI2D_CHECK_I32(tile_bins);
+    GI2D_CHECK_F32(conics);
+    GI2D_CHECK_F32(opacities);
+    GI2D_CHECK_F32(v_output);
+    TORCH_CHECK(v_output.numel() == (int64_t)img_height * img_width * c, "v_output must have dimensions (", img_height,
+                ", ", img_width, ", ", c, ")");
+    const int n = (int)xys.size(0), m = (int)gids.numel();
+    Tensor v_xy = f32(xys, {n, 2}), v_conic = f32(xys, {n, 3}), v_colors = f32(xys, {n, c}), v_opacity = f32(xys, {n, 1});
+    const size_t nbytes = gi2d_nd_rasterize_backward_workspace_bytes(n, m, c);
+    Tensor ws = torch::empty({(int64_t)(nbytes > 256 ? nbytes : 256)}, xys.options().dtype(torch::kUInt8));
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(xys.device());
+    check(gi2d_nd_rasterize_sum_backward(n, m, img_height, img_width, c, ip(gids), ip(tile_bins), (int)tile_bins.size(0),
+                                         fp(xys), fp(conics), fp(colors), fp(opacities), fp(v_output),
+                                         v_xy.data_ptr<float>(), v_conic.data_ptr<float>(), v_colors.data_ptr<float>(),
+                                         v_opacity.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), stream_of(xys)),
+          "nd_rasterize_sum_backward");
+    return std::make_tuple(v_xy, v_conic, v_colors, v_opacity);
+}
+
 // ------------------------------------------------------------------------------------------ fused fast path
 int64_t fast_workspace_bytes(int num_points, int tiles_x, int tiles_y) {
     return (int64_t)gi2d_fast_workspace_bytes(num_points, tiles_x, tiles_y);
@@ -456,6 +523,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("conics"), py::arg("colors"), py::arg("opacities"), py::arg("background"), py::arg("final_Ts"),
           py::arg("final_idx"), py::arg("v_output"), py::arg("v_output_alpha") = py::none(),
           py::arg("cum_tiles_hit") = py::none(), py::arg("inv_perm") = py::none());
+    m.def("nd_rasterize_sum_forward", &nd_rasterize_sum_forward, py::arg("tile_bounds"), py::arg("block"),
+          py::arg("img_size"), py::arg("gaussian_ids_sorted"), py::arg("tile_bins"), py::arg("xys"), py::arg("conics"),
+          py::arg("colors"), py::arg("opacities"), py::arg("background"), py::arg("num_intersects_dev") = py::none());
+    m.def("nd_rasterize_sum_backward", &nd_rasterize_sum_backward, py::arg("img_height"), py::arg("img_width"),
+          py::arg("BLOCK_H"), py::arg("BLOCK_W"), py::arg("gaussian_ids_sorted"), py::arg("tile_bins"), py::arg("xys"),
+          py::arg("conics"), py::arg("colors"), py::arg("opacities"), py::arg("background"), py::arg("final_Ts"),
+          py::arg("final_idx"), py::arg("v_output"), py::arg("v_output_alpha") = py::none());
     // the fused fast path the autograd wrappers run on
     m.def("fast_workspace_bytes", &fast_workspace_bytes);
     m.def("fast_workspace_init", &fast_workspace_init);

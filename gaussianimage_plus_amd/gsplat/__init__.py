@@ -1,7 +1,8 @@
 """Drop-in `gsplat` operator surface for GaussianImage++ on MI355X (gfx950).
 
-Exposes the 2D-path names of the reference's gsplat/gsplat/__init__.py:3-52; the 3D / SH / N-channel
-entries exist but raise NotImplementedError (outside this build).
+Exposes the 2D-path names of the reference's gsplat/gsplat/__init__.py:3-52.  rasterize_gaussians_sum takes 1 to 12
+colour channels (three: the RGB kernels; any other count: the N-channel sum rasterizer, rasterize_sum.py:170-210); the
+3D / SH entries exist but raise NotImplementedError (outside this build).
 """
 from typing import Any
 import warnings

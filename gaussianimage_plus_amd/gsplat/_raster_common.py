@@ -1,4 +1,6 @@
-"""Core of the two additive-rasterizer autograd Functions (rasterize_sum.py / rasterize_sum_plus.py).
+"""Core of the two additive-rasterizer autograd Functions (rasterize_sum.py / rasterize_sum_plus.py).  What follows is
+the RGB route (forward_impl / backward_impl); rasterize_gaussians_sum sends any other channel count to the N-channel route
+at the end of this file (nd_forward_impl / nd_backward_impl) before it gets here.
 
 Reference orchestration (rasterize_sum_plus.py:98-172): cumsum -> `.item()` (host sync in the middle of
 the forward) -> map -> torch.sort -> gather -> bin edges -> rasterize.  Here one forward is two native calls
@@ -179,8 +181,6 @@ def forward_impl(ctx, plus: bool, xys, depths, radii, conics, num_tiles_hit, col
     tile_bounds = tile_bounds_of(img_height, img_width, BLOCK_H, BLOCK_W)
     block = (BLOCK_W, BLOCK_H, 1)
     img_size = (img_width, img_height, 1)
-    if not plus and colors.shape[-1] != 3:  # rasterize_sum.py:170-171 would pick nd_rasterize_sum_forward
-        raise NotImplementedError("N-channel rasterization is outside this build (RGB only)")
     radii = radii if radii.dtype == torch.int32 else radii.to(torch.int32)
 
     lease = _acquire(xys, num_points, tile_bounds)
@@ -280,3 +280,59 @@ def backward_impl(ctx, plus: bool, v_out_img):
         v_xy, v_conic, v_colors, v_opacity, v_abs = _C.fast_backward(
             ctx.lease.ws, xys, radii, v_out_img, ctx.img_height, ctx.img_width, ctx.radius_clip, with_abs=not plus)
     return v_xy, v_conic, v_colors, v_opacity.view_as(opacity), v_abs
+
+
+# ------------------------------------------------------------------------------- N-channel route (rasterize_sum.py:170-210)
+def check_nd_arguments(colors, background) -> None:
+    """What the N-channel route refuses, before any device work: a channel count outside 1..12 (the reference's
+    MAX_REGISTER_CHANNELS, config.h:10: above it its kernels overrun their LDS colour rows) and a background that is
+    not one value per channel."""
+    c = colors.shape[-1]
+    if not 1 <= c <= _C.ND_MAX_CHANNELS:
+        raise NotImplementedError(f"rasterize_gaussians_sum: {c} colour channels; the N-channel rasterizer takes "
+                                  f"1..{_C.ND_MAX_CHANNELS}")
+    if background.numel() != c:
+        raise ValueError(f"background must have {c} elements (one per colour channel), got {background.numel()}")
+
+
+def nd_forward_impl(ctx, xys, radii, conics, colors, opacity, img_height, img_width, BLOCK_H, BLOCK_W, background,
+                    radius_clip):
+    """colors[N,C], C != 3: the capacity-free ops -- gi2d_bin_gaussians (capacity grown as in _exact_forward) +
+    gi2d_nd_rasterize_sum_forward.  The host reads the binning status ONCE per forward (the sync-free workspace route
+    is RGB only).  No intersection at all: the device writes the background image (the reference falls into an
+    undefined name there) and the backward returns zeros.  -> (out_img[H,W,C], final_Ts[H,W])"""
+    if BLOCK_H != BLOCK or BLOCK_W != BLOCK:
+        raise RuntimeError(f"only {BLOCK}x{BLOCK} tiles are supported (csrc/config.h BLOCK_X/BLOCK_Y)")
+    num_points = xys.size(0)
+    tile_bounds = tile_bounds_of(img_height, img_width, BLOCK_H, BLOCK_W)
+    num_tiles = tile_bounds[0] * tile_bounds[1]
+    radii = radii if radii.dtype == torch.int32 else radii.to(torch.int32)
+    key = (xys.device.index, num_points, img_height, img_width)
+    capacity = _capacity.get(key) or max(4 * num_points, num_tiles, 1024)
+    while True:
+        gids, bins, status = _C.bin_gaussians(xys, radii, tile_bounds, radius_clip, capacity)
+        out_img, final_Ts, _ = _C.nd_rasterize_sum_forward(tile_bounds, (BLOCK_W, BLOCK_H, 1), (img_width, img_height, 1),
+                                                           gids, bins, xys, conics, colors, opacity, background,
+                                                           num_intersects_dev=status)
+        num_intersects, overflow = status[:2].tolist()
+        capacity = _capacity[key] = max(int(1.25 * num_intersects) + 1024, num_tiles)
+        if not overflow:
+            break
+    ctx.set_materialize_grads(False)
+    ctx.img_width, ctx.img_height = img_width, img_height
+    ctx.BLOCK_H, ctx.BLOCK_W = BLOCK_H, BLOCK_W
+    ctx.num_intersects = num_intersects
+    # (the list beyond its M entries is unwritten memory: the backward's index must not see it)
+    ctx.save_for_backward(gids[:max(num_intersects, 0)], bins, xys, conics, colors, opacity)
+    return out_img, final_Ts
+
+
+def nd_backward_impl(ctx, v_out_img):
+    """-> (v_xy, v_conic, v_colors[N,C], v_opacity) on the lists kept from the forward (rasterize_sum.py:267-307)."""
+    gids, bins, xys, conics, colors, opacity = ctx.saved_tensors
+    if ctx.num_intersects < 1 or v_out_img is None:  # rasterize_sum.py:261-265; or the image took no part in the loss
+        return torch.zeros_like(xys), torch.zeros_like(conics), torch.zeros_like(colors), torch.zeros_like(opacity)
+    v_xy, v_conic, v_colors, v_opacity = _C.nd_rasterize_sum_backward(
+        ctx.img_height, ctx.img_width, ctx.BLOCK_H, ctx.BLOCK_W, gids, bins, xys, conics, colors, opacity, None, None,
+        None, v_out_img.contiguous())
+    return v_xy, v_conic, v_colors, v_opacity.view_as(opacity)

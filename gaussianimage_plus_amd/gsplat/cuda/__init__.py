@@ -9,6 +9,10 @@ HBM allocations and the current HIP stream.  Inputs must be device tensors and c
 Where the reference's Python wrappers and its C++ bindings disagree the op
 follows the WRAPPER's intent: rasterize_sum_forward returns 4 tensors (with the never-filled
 cnt_gs_counts, bindings.cu:506-508) and rasterize_sum_backward returns 5 (with v_abs_xys).
+
+nd_rasterize_sum_forward / nd_rasterize_sum_backward (bindings.cu:776-930: what rasterize_sum.py picks for other than
+three colour channels) are ops of this table, 1 to 12 channels; nd_rasterize_forward / _backward, nd_rasterize_gs_sum_*
+and the 3D / SH names exist and raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -482,17 +486,83 @@ def rasterize_sum_plus_backward(img_height, img_width, BLOCK_H, BLOCK_W, gaussia
                        cum_tiles_hit, inv_perm)[:4]
 
 
+# ------------------------------------------------------------------------------- N-channel sum rasterizer
+ND_MAX_CHANNELS = 12  # include/gi2d.h GI2D_ND_MAX_CHANNELS (config.h:10 MAX_REGISTER_CHANNELS)
+
+
+def _nd_channels(colors):
+    if colors.dim() != 2:
+        raise RuntimeError("colors must have 2 dimensions")  # bindings.cu:877-879
+    c = int(colors.size(1))
+    if not 1 <= c <= ND_MAX_CHANNELS:
+        raise RuntimeError(f"colors has {c} channels; supported are 1..{ND_MAX_CHANNELS} (GI2D_ND_MAX_CHANNELS)")
+    return c
+
+
+def nd_rasterize_sum_forward(tile_bounds, block, img_size, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+                             opacities, background, num_intersects_dev=None):
+    """bindings.cu:776-842 -> (out_img[H,W,C], final_Ts, final_idx), 1 <= C <= 12.  Every entry of a tile's list counts
+    (no 256-entry rule), alpha is clamped at 0.999, the background is not added; with `num_intersects_dev` (device
+    int32) below 1 the image is the background, as for rasterize_sum_forward."""
+    for t, nm in ((gaussian_ids_sorted, "gaussian_ids_sorted"), (tile_bins, "tile_bins")):
+        _chk(t, nm, torch.int32)
+    for t, nm in ((xys, "xys"), (conics, "conics"), (colors, "colors"), (opacities, "opacities"),
+                  (background, "background")):
+        _chk(t, nm, torch.float32)
+    _check_block(block)
+    c = _nd_channels(colors)
+    if background.numel() != c:
+        raise RuntimeError(f"background must have {c} elements, got {background.numel()}")
+    w, h = int(img_size[0]), int(img_size[1])
+    out_img, final_Ts, final_idx = _f32(h, w, c, like=xys), _f32(h, w, like=xys), _i32(h, w, like=xys)
+    with torch.cuda.device(xys.device):
+        _lib.call("gi2d_nd_rasterize_sum_forward", int(tile_bounds[0]), int(tile_bounds[1]), w, h, c,
+                  gaussian_ids_sorted.data_ptr(), tile_bins.data_ptr(), tile_bins.size(0), xys.data_ptr(),
+                  conics.data_ptr(), colors.data_ptr(), opacities.data_ptr(), background.data_ptr(),
+                  _ptr(num_intersects_dev), final_Ts.data_ptr(), final_idx.data_ptr(), out_img.data_ptr(), _stream(xys))
+    return out_img, final_Ts, final_idx
+
+
+def nd_rasterize_sum_backward(img_height, img_width, BLOCK_H, BLOCK_W, gaussian_ids_sorted, tile_bins, xys, conics,
+                              colors, opacities, background, final_Ts, final_idx, v_output, v_output_alpha=None):
+    """bindings.cu:852-930 -> (v_xy, v_conic, v_colors[N,C], v_opacity[N,1]).  `background`, `final_Ts`, `final_idx`
+    and `v_output_alpha` are accepted and ignored: the N-channel forward writes final_idx = end - 1, so the reference's
+    gate excludes nothing, and its kernel never reads v_output_alpha (backward.cu:1606)."""
+    _chk(xys, "xys", torch.float32)
+    _chk(colors, "colors", torch.float32)
+    if xys.dim() != 2 or xys.size(1) != 2:
+        raise RuntimeError("xys must have dimensions (num_points, 2)")  # bindings.cu:873-875
+    c = _nd_channels(colors)
+    _check_block((BLOCK_W, BLOCK_H))
+    for t, nm in ((gaussian_ids_sorted, "gaussian_ids_sorted"), (tile_bins, "tile_bins")):
+        _chk(t, nm, torch.int32)
+    for t, nm in ((conics, "conics"), (opacities, "opacities"), (v_output, "v_output")):
+        _chk(t, nm, torch.float32)
+    n, m = xys.size(0), gaussian_ids_sorted.numel()
+    h, w = int(img_height), int(img_width)
+    if v_output.numel() != h * w * c:
+        raise RuntimeError(f"v_output must have dimensions ({h}, {w}, {c})")
+    v_xy, v_conic = _f32(n, 2, like=xys), _f32(n, 3, like=xys)
+    v_colors, v_opacity = _f32(n, c, like=xys), _f32(n, 1, like=xys)
+    ws = _workspace(_lib.load().gi2d_nd_rasterize_backward_workspace_bytes(n, m, c), xys)
+    with torch.cuda.device(xys.device):
+        _lib.call("gi2d_nd_rasterize_sum_backward", n, m, h, w, c, gaussian_ids_sorted.data_ptr(),
+                  tile_bins.data_ptr(), tile_bins.size(0), xys.data_ptr(), conics.data_ptr(), colors.data_ptr(),
+                  opacities.data_ptr(), v_output.data_ptr(), v_xy.data_ptr(), v_conic.data_ptr(), v_colors.data_ptr(),
+                  v_opacity.data_ptr(), ws.data_ptr(), ws.numel(), _stream(xys))
+    return v_xy, v_conic, v_colors, v_opacity
+
+
 # ------------------------------------------------------------------------------- out of scope
 def _unsupported(name):
     def f(*a, **k):
-        raise NotImplementedError(f"gsplat.cuda.{name}: the 3D / N-channel paths are outside this build "
-                                  "(SURVEY.md section 2, items 16-17)")
+        raise NotImplementedError(f"gsplat.cuda.{name}: the 3D paths and the other N-channel variants are outside this "
+                                  "build (SURVEY.md section 2, items 16-17)")
     f.__name__ = name
     return f
 
 
-for _n in ("nd_rasterize_forward", "nd_rasterize_backward", "nd_rasterize_sum_forward",
-           "nd_rasterize_sum_backward", "nd_rasterize_gs_sum_forward", "nd_rasterize_gs_sum_backward",
+for _n in ("nd_rasterize_forward", "nd_rasterize_backward", "nd_rasterize_gs_sum_forward", "nd_rasterize_gs_sum_backward",
            "rasterize_forward", "rasterize_backward", "project_gaussians_forward",
            "project_gaussians_backward", "compute_sh_forward", "compute_sh_backward"):
     globals()[_n] = _unsupported(_n)
@@ -504,7 +574,7 @@ _COMPILED_NAMES = ("project_gaussians_2d_forward", "project_gaussians_2d_backwar
                    "project_gaussians_2d_scale_rot_forward", "project_gaussians_2d_scale_rot_backward",
                    "compute_cov2d_bounds", "compute_cov2d_bounds_xy", "map_gaussian_to_intersects", "get_tile_bin_edges",
                    "rasterize_sum_forward", "rasterize_sum_backward", "rasterize_sum_plus_forward",
-                   "rasterize_sum_plus_backward")
+                   "rasterize_sum_plus_backward", "nd_rasterize_sum_forward", "nd_rasterize_sum_backward")
 CTYPES_TABLE = {n: globals()[n] for n in _COMPILED_NAMES}  # kept reachable: tests hold the two bindings to each other
 if _ext is not None:
     for _n in _COMPILED_NAMES:

@@ -187,6 +187,44 @@ int gi2d_rasterize_sum_plus_backward(int num_points, int num_intersects, unsigne
                                      float *v_rgb, float *v_opacity, void *workspace,
                                      size_t workspace_bytes, gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ N-channel rasterizer
+ * bindings.cu:776-842 nd_rasterize_sum_forward_tensor / :852-930 nd_rasterize_sum_backward_tensor
+ * (kernels forward.cu:777-895, backward.cu:1555-1738): what rasterize_sum.py picks when colors has
+ * other than three channels.  colors f32[N,C], out_img / v_output f32[H,W,C], 1 <= C <=
+ * GI2D_ND_MAX_CHANNELS (config.h:10 MAX_REGISTER_CHANNELS; C == 3 is legal here too); any other
+ * channel count returns GI2D_ERR_UNSUPPORTED before anything is launched.
+ * Unlike the RGB ops EVERY entry of a tile's list is consumed, in list order (no GI2D_TILE_LIST_CAP).
+ * forward : alpha = min(0.999, opac * exp(-sigma)); a pair is skipped iff sigma < 0 || alpha < 1/255;
+ *           out_img[pix][ch] = sum colors[g][ch] * alpha.  Pixels of a tile with a non-empty list get
+ *           final_Ts = 1, final_idx = end - 1; pixels of an empty tile get zeros in all three outputs.
+ *           `background` (f32[C]) / num_intersects_dev as for gi2d_rasterize_sum_forward; the kernel
+ *           itself never adds the background.
+ * backward: the same pairs, tested with alpha_b = min(1, opac * exp(-sigma)) (the reference's own
+ *           inconsistency, kept); v_colors += alpha_b * v_output, v_sigma = -opac * vis * v_alpha ignores
+ *           the clamp; the reference's final_index gate never excludes anything (the forward writes
+ *           end - 1), so no final_idx is taken.  v_xy f32[N,2], v_conic f32[N,3], v_colors f32[N,C],
+ *           v_opacity f32[N]: every row is written.  No float atomics: one partial row per sorted list
+ *           position, summed per gaussian in ascending position (= tile) order; bitwise reproducible.
+ *           The gaussian-major index is rebuilt from gaussian_ids_sorted (the generic form above).
+ *           num_points == 0 or num_intersects == 0: outputs are zero-filled, GI2D_OK.
+ *           workspace >= gi2d_nd_rasterize_backward_workspace_bytes(N, M, C). */
+#define GI2D_ND_MAX_CHANNELS 12
+int gi2d_nd_rasterize_sum_forward(int tiles_x, int tiles_y, unsigned img_width, unsigned img_height,
+                                  int channels, const int32_t *gaussian_ids_sorted,
+                                  const int32_t *tile_bins, int tile_bins_rows, const float *xys,
+                                  const float *conics, const float *colors, const float *opacities,
+                                  const float *background, const int32_t *num_intersects_dev,
+                                  float *final_Ts, int32_t *final_idx, float *out_img,
+                                  gi2d_stream_t stream);
+size_t gi2d_nd_rasterize_backward_workspace_bytes(int num_points, int num_intersects, int channels);
+int gi2d_nd_rasterize_sum_backward(int num_points, int num_intersects, unsigned img_height,
+                                   unsigned img_width, int channels,
+                                   const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                                   int tile_bins_rows, const float *xys, const float *conics,
+                                   const float *colors, const float *opacities, const float *v_output,
+                                   float *v_xy, float *v_conic, float *v_colors, float *v_opacity,
+                                   void *workspace, size_t workspace_bytes, gi2d_stream_t stream);
+
 /* ------------------------------------------------------------------ sync-free fast path
  * The same results as the ops above, with the host round trip of the reference orchestration
  * (rasterize_sum_plus.py:108 -> utils.py:249 `.item()`) removed: buffers are sized by a
