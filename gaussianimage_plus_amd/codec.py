@@ -25,11 +25,13 @@
 
 Decoding needs no fitter, no target image and no optimizer state: this module imports neither `trainer` nor `quantize`.
 A decode is three native launches on buffers the Decoder owns -- gi2d_fast_workspace_init, gi2d_codec_decode_bin
-(record -> dequantise -> project -> bin, csrc/gi2d_codec.hip) and gi2d_fast_rasterize_forward -- plus the clamp to
-[0, 1] that NativeFitter.decompress_wo_ec applies; the picture is bit-identical to that method's.  The tile-overflow
-status is looked at ONCE, after the image has been enqueued; an overflowing stream (more than 1024 candidate gaussians in
-one 16x16 tile) is rendered again through the capacity-free ops, so a valid stream always decodes.  Every decode call
-(decode, decode_many, decode_views, decode_geometry) is one host driver, Decoder._run, on a list of pictures.
+(record -> dequantise -> project -> bin, csrc/gi2d_codec.hip) and gi2d_codec_draw (csrc/gi2d_codec_draw.hip), the decode's
+own tile pass, which ends in the clamp to [0, 1] that NativeFitter.decompress_wo_ec applies; the picture is bit-identical
+to that method's.  The tile-overflow status is looked at ONCE, after the image has been enqueued; an overflowing stream
+(more than 1024 candidate gaussians in one 16x16 tile) is rendered again through the capacity-free ops, so a valid stream
+always decodes.  Every decode call is one host driver on a list of pictures: Decoder._begin (stage, grow the buffers,
+expand each rANS payload once), the draw, Decoder._finish (the one host wait, the redraws).  Only the draw differs:
+decode, decode_many, decode_views and decode_geometry (Decoder._run) give every picture launches of its own, and
 decode_batch draws its pictures together: gi2d_codec_decode_batch (csrc/gi2d_codec_batch.hip) makes the reset, the
 decode/bin and the draw launch once for up to 64 pictures, each with a decode workspace and a status row of its own.
 
@@ -43,18 +45,18 @@ An overview (codec.Overview) is the same argument for scale < 1. 
 gaussian, so the low-pass a reduced picture needs is closed-form: every gaussian gets the filter's variance added to its
 covariance and its colour rescaled so that its mass stays (overview_parameters states the arithmetic).  A reduced tile
 holds far more than 256 gaussians, so an overview has launches of its own -- gi2d_codec_decode_overview (record ->
-transformed gaussian -> covariance projection), the capacity-free gi2d_bin_gaussians, and gi2d_rasterize_forward_long, which
-walks every tile list to its end (csrc/gi2d_codec_overview.hip) -- on buffers the Decoder keeps; the binning status joins
+transformed gaussian -> covariance projection), the capacity-free gi2d_bin_gaussians, and gi2d_rasterize_forward_long_as,
+which walks every tile list to its end (csrc/gi2d_codec_overview.hip) -- on buffers the Decoder keeps; the binning status joins
 the picture's status row, and a picture whose lists did not fit their buffer is drawn again with room for all of them.
 
 A picture FORMAT (DESIGN.md 3.8 "Picture formats") is a decoder argument too: dtype float32, float16 or uint8 times layout
 "hwc" [H, W, 3], "chw" [3, H, W] or "hwc4" [H, W, 4] (channel 3 = the element of 1.0).  `convert` states the arithmetic:
-clamp to [0, 1], then as it is / rounded to nearest even / rint(c * 255) with NaN -> 0.  With dtype and layout both None a
-call makes exactly the launches above.  With either given (the other defaults to float32 / "hwc") the picture is drawn by
-the decode's own tile pass, gi2d_codec_draw (csrc/gi2d_codec_draw.hip) -- the forward without the packed records and
-gradient rows that only a fit reads, ending in the clamp, the conversion and the layout -- or, for an overview, by
-gi2d_rasterize_forward_long_as; there is no clamp launch, and the values are `convert` of the default call's, bit for bit.
-The fallbacks draw in float32 and end in gi2d_codec_convert.
+clamp to [0, 1], then as it is / rounded to nearest even / rint(c * 255) with NaN -> 0.  A half that is not given defaults
+to float32 / "hwc", so a call that names neither is a float32 "hwc" call and there is one draw path: the format is an
+argument of the launches above.  gi2d_codec_draw is the fitting forward without the packed records and gradient rows that
+only a fit reads, and its epilogue -- like that of gi2d_rasterize_forward_long_as for an overview -- is the clamp, the
+conversion and the layout; its float32 "hwc" picture is the fitting forward's followed by a clamp, bit for bit, and every
+other format is `convert` of that.  The fallbacks draw in float32 and end in a clamp or in gi2d_codec_convert.
 
 Format version 1 (little-endian; INTEGRATION.md "Packed stream" has the record layout):
 
@@ -876,30 +878,27 @@ class _Format(NamedTuple):
     """A picture format, checked (_format)."""
     dtype: torch.dtype
     layout: str
-
-    @property
-    def ids(self):  # (dtype, layout) as the C ABI numbers them
-        return PIXEL_DTYPES[self.dtype], LAYOUTS[self.layout]
+    ids: Tuple[int, int]  # (dtype, layout) as the C ABI numbers them
 
     def shape(self, height: int, width: int):
-        return {"hwc": (height, width, 3), "chw": (3, height, width), "hwc4": (height, width, 4)}[self.layout]
+        return (3, height, width) if self.layout == "chw" else (height, width, 4 if self.layout == "hwc4" else 3)
 
 
-_DEFAULT_FORMAT = _Format(torch.float32, "hwc")
+_DEFAULT_FORMAT = _Format(torch.float32, "hwc", (PIXEL_DTYPES[torch.float32], LAYOUTS["hwc"]))
 
 
-def _format(dtype, layout) -> Optional[_Format]:
-    """(dtype, layout) of a decode call -> None for (None, None): the picture and the launches there were before there
-    were formats; else the format, a missing half defaulting to float32 / "hwc".  ValueError for anything else."""
+def _format(dtype, layout) -> _Format:
+    """(dtype, layout) of a decode call -> the format, a missing half (None) defaulting to float32 / "hwc": a call that
+    names neither is a float32 "hwc" call (_DEFAULT_FORMAT).  ValueError for anything else."""
     if dtype is None and layout is None:
-        return None
+        return _DEFAULT_FORMAT
     dtype = torch.float32 if dtype is None else dtype
     layout = "hwc" if layout is None else layout
     if not isinstance(dtype, torch.dtype) or dtype not in PIXEL_DTYPES:
         raise ValueError(f"dtype {dtype!r}: torch.float32, torch.float16 or torch.uint8")
     if not isinstance(layout, str) or layout not in LAYOUTS:
         raise ValueError(f"layout {layout!r}: 'hwc' [H, W, 3], 'chw' [3, H, W] or 'hwc4' [H, W, 4]")
-    return _Format(dtype, layout)
+    return _Format(dtype, layout, (PIXEL_DTYPES[dtype], LAYOUTS[layout]))
 
 
 def _check_out(out, shape, dtype: torch.dtype, dev: Optional[torch.device] = None) -> None:
@@ -918,7 +917,7 @@ def convert(img: torch.Tensor, dtype=None, layout=None) -> torch.Tensor:
         torch.uint8     (c * 255).round().to(torch.uint8)        (one float32 multiply, round half to even); NaN -> 0
     and layout "hwc": [H, W, 3], "chw": [3, H, W], "hwc4": [H, W, 4] with channel 3 the element of 1.0 (1.0, 1.0, 255).
     A new contiguous tensor.  The kernels do this in gi2d_pixel_format.h::pixel_convert."""
-    fmt = _format(dtype, layout) or _DEFAULT_FORMAT
+    fmt = _format(dtype, layout)
     if not isinstance(img, torch.Tensor) or img.dtype != torch.float32 or img.dim() != 3 or img.shape[2] != 3:
         raise ValueError("convert: a float32 [H, W, 3] tensor")
     c = img.clamp(0, 1)
@@ -1005,6 +1004,10 @@ class DeviceStream:
 
     def __init__(self, header: Dict[str, object], payload: torch.Tensor):
         self.header, self.payload = header, payload
+
+
+def _headers(streams) -> List[Dict[str, object]]:
+    return [s.header if isinstance(s, DeviceStream) else _parse(s) for s in streams]
 
 
 class Decoder:
@@ -1141,14 +1144,13 @@ class Decoder:
         return fixed
 
     # ---------------------------------------------------------------------------------------------- launches
-    def _launch(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, aux=None,
-                fmt: Optional[_Format] = None) -> None:
-        """Workspace reset + decode/bin + forward + clamp of a coding-0 payload on the current stream, at the picture's
-        size, with the status row at `status`; no host sync and no allocation.  With a format: workspace reset +
-        decode/bin + gi2d_codec_draw, whose epilogue is the clamp, the conversion and the layout."""
+    def _launch(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, fmt: _Format, aux=None) -> None:
+        """Workspace reset + decode/bin + gi2d_codec_draw (whose epilogue is the clamp, the conversion and the layout) of
+        a coding-0 payload on the current stream, at the picture's size, with the status row at `status`; no host sync
+        and no allocation.  aux: five tensors that take the decode kernel's per-gaussian outputs."""
         h, view, w, hh, tx, ty = pic
         if isinstance(view, Overview):
-            return self._launch_overview(pic, payload, status, out, aux, fmt=fmt)
+            return self._launch_overview(pic, payload, status, out, fmt, aux)
         n = h["num_points"]
         b = h["bits"]
         side = (C.c_float * 16)(*h["side"])
@@ -1165,21 +1167,16 @@ class Decoder:
                       C.c_void_p(payload.data_ptr()), h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"],
                       view.x0, view.y0, view.scale, hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3], a[4], ws, nws,
                       status, st)
-        if fmt is not None:
-            _lib.call("gi2d_codec_draw", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws, status,
-                      *fmt.ids, C.c_void_p(out.data_ptr()), st)
-            return
-        _lib.call("gi2d_fast_rasterize_forward", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws,
-                  status, None, None, C.c_void_p(out.data_ptr()), st)
-        out.clamp_(0, 1)
+        _lib.call("gi2d_codec_draw", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws, status,
+                  *fmt.ids, C.c_void_p(out.data_ptr()), st)
 
-    def _launch_overview(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, aux=None,
-                         capacity: Optional[int] = None, fmt: Optional[_Format] = None) -> None:
+    def _launch_overview(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, fmt: _Format,
+                         aux=None, capacity: Optional[int] = None) -> None:
         """An overview of a coding-0 payload on the current stream: gi2d_codec_decode_overview (record -> transformed,
         prefiltered gaussian -> covariance projection), gi2d_bin_gaussians into lists of `capacity` entries (its status
-        {count, overflow} goes to words 0 and 1 of the row at `status`), gi2d_rasterize_forward_long (whole lists, clamp
-        fused, ones if the count is 0; with a format gi2d_rasterize_forward_long_as, the same kernel ending in the
-        format's stores); no host sync and no allocation (_reserve_overview has been called)."""
+        {count, overflow} goes to words 0 and 1 of the row at `status`), gi2d_rasterize_forward_long_as (whole lists,
+        ones if the count is 0, ending in the clamp and the format's stores); no host sync and no allocation
+        (_reserve_overview has been called)."""
         h, ov, w, hh, tx, ty = pic
         n = h["num_points"]
         b = h["bits"]
@@ -1196,15 +1193,10 @@ class Decoder:
                   hh, w, tx, ty, h["radius_clip"], geo[0], geo[1], geo[2], geo[3], geo[4], st)
         _lib.call("gi2d_bin_gaussians", n, cap, geo[0], geo[1], tx, ty, ov.radius_clip(h), ids, bins, status,
                   C.c_void_p(o["binws"].data_ptr()), o["binws"].numel(), st)
-        if fmt is not None:
-            _lib.call("gi2d_rasterize_forward_long_as", n, cap, tx, ty, w, hh, ids, bins, tx * ty, geo[0], geo[2], geo[4],
-                      None, status, *fmt.ids, C.c_void_p(out.data_ptr()), st)
-            return
-        _lib.call("gi2d_rasterize_forward_long", n, cap, tx, ty, w, hh, ids, bins, tx * ty, geo[0], geo[2], geo[4], None,
-                  status, C.c_void_p(out.data_ptr()), st)
+        _lib.call("gi2d_rasterize_forward_long_as", n, cap, tx, ty, w, hh, ids, bins, tx * ty, geo[0], geo[2], geo[4],
+                  None, status, *fmt.ids, C.c_void_p(out.data_ptr()), st)
 
-    def _out(self, pic: _Picture, out: Optional[torch.Tensor], fmt: Optional[_Format] = None) -> torch.Tensor:
-        fmt = fmt or _DEFAULT_FORMAT
+    def _out(self, pic: _Picture, out: Optional[torch.Tensor], fmt: _Format) -> torch.Tensor:
         shape = fmt.shape(pic.height, pic.width)
         if out is None:
             return torch.empty(shape, dtype=fmt.dtype, device=self.dev)
@@ -1216,83 +1208,103 @@ class Decoder:
         i = lambda *s: torch.empty(s, dtype=torch.int32, device=self.dev)
         return [f(n, 2), i(n), f(n, 3), i(n), f(n, 3)]
 
-    def _exact(self, pic: _Picture, fixed: torch.Tensor, out: torch.Tensor, fmt: Optional[_Format] = None) -> None:
+    def _exact(self, pic: _Picture, fixed: torch.Tensor, out: torch.Tensor, fmt: _Format) -> None:
         """A tile row overflowed: the same picture through the capacity-free ops (gi2d_bin_gaussians + the plain
         rasterizer), fed with the decode kernel's per-gaussian outputs for the coding-0 payload `fixed` (for a view: the
-        transformed geometry, at the view's size and with its radius_clip).  With a format the float32 picture is
-        converted into `out` by gi2d_codec_convert."""
+        transformed geometry, at the view's size and with its radius_clip).  The float32 picture is clamped into `out`,
+        or converted into it by gi2d_codec_convert for any other format."""
         from .gsplat import _raster_common as rc
         h, w, hh = pic.header, pic.width, pic.height
         n = h["num_points"]
         aux = self._aux(n)
-        self._launch(pic, fixed, self._status.data_ptr(), torch.empty(hh, w, 3, dtype=torch.float32, device=self.dev), aux)
+        self._reserve_workspace([pic])  # a no-op behind _run; decode_batch draws on workspaces of another kind
+        self._launch(pic, fixed, self._status.data_ptr(), torch.empty(hh, w, 3, dtype=torch.float32, device=self.dev),
+                     _DEFAULT_FORMAT, aux)
         xys, radii, conics, _, colors = aux
         tb = rc.tile_bounds_of(hh, w, _TILE, _TILE)
         opacity = torch.ones(n, 1, dtype=torch.float32, device=self.dev)
         img = rc._exact_forward(h["kind"] == KIND_COVARIANCE, xys, radii, conics, colors, opacity, hh, w, tb,
                                 (_TILE, _TILE, 1), (w, hh, 1), self._background, pic.radius_clip, False)[0]
-        if fmt is None:
+        if fmt == _DEFAULT_FORMAT:
             torch.clamp(img, 0, 1, out=out)
         else:
             img = img.contiguous()
             _lib.call("gi2d_codec_convert", *fmt.ids, hh, w, C.c_void_p(img.data_ptr()), C.c_void_p(out.data_ptr()),
                       _stream(self.dev))
 
-    def _run(self, groups, outs: Optional[Sequence[torch.Tensor]] = None, views_only: bool = False,
-             geometry: bool = False, fmt: Optional[_Format] = None):
-        """The host driver of every decode call -> (images, aux).  groups: [(stream, [view or None, ...])], a picture per
-        entry; `outs`: a tensor per picture, in call order.  Everything is parsed and checked before anything touches
-        the device; a rANS payload is expanded once per group, into its slice of `_expanded` (valid until the next call);
-        every picture has its own status row, and the rows are read in ONE host wait behind the last picture; a picture
-        whose tile row overflowed is then drawn again (_exact), an overview whose tile lists outgrew their buffer likewise
-        (_launch_overview with the count the status row reports).  geometry (one group, one picture): the per-gaussian
-        outputs of the decode kernel are kept, and the picture stays the fast path's own.  fmt: the pictures' format
-        (None: float32 [H, W, 3] through the launches there were before there were formats)."""
-        who, what = ("decode_views", "view") if views_only else ("decode_many", "stream")
-        streams = [s for s, _ in groups]
-        headers = [s.header if isinstance(s, DeviceStream) else _parse(s) for s in streams]
-        pictures = [_picture(h, _checked_view(v, h, views_only)) for h, (_, views) in zip(headers, groups) for v in views]
+    # ---------------------------------------------------------------------------------------------- the host driver
+    def _begin(self, streams, headers, pictures: Sequence[_Picture], counts: Sequence[int]):
+        """What every decode call does before it draws, on parsed and checked input (stream k has the next counts[k]
+        pictures; a row is a picture) -> (fixed, coded, row0): per row the coding-0 payload it is drawn from, the rows
+        whose status word 4 an expansion may raise, the device address of status row 0.  Payloads are staged, the status
+        rows, the expansion buffer and the overview buffers grown to the call's needs, the token advanced, and every
+        rANS payload expanded ONCE, into its slice of `_expanded` (valid until the next call), with the status row of its
+        stream's first picture."""
+        payloads = self._stage(streams, headers)
+        if self._status.shape[0] < len(pictures):
+            self._status = torch.zeros(len(pictures), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
+        self._reserve_overview(pictures)
+        total = 0
+        for h in headers:
+            if h["coding"] != CODING_FIXED:
+                total += (h["fixed_payload_bytes"] + 255) & ~255
+        if self._expanded.numel() < total:
+            self._expanded = torch.empty(total, dtype=torch.uint8, device=self.dev)
+        self._next_token()
+        row0 = self._status.data_ptr()
+        fixed, coded, at = [], [], 0
+        for h, payload, count in zip(headers, payloads, counts):
+            if h["coding"] != CODING_FIXED:
+                nb = h["fixed_payload_bytes"]
+                coded.append(len(fixed))
+                payload = self._expand(h, payload, row0 + _STATUS_ROW * len(fixed), self._expanded[at:at + nb])
+                at += (nb + 255) & ~255
+            fixed += [payload] * count
+        return fixed, coded, row0
+
+    def _finish(self, pictures, fixed, coded, row0: int, images, fmt: _Format, aux=None, geometry: bool = False) -> List[int]:
+        """What every decode call does behind its last draw -> the rows drawn again.  The status rows are read in the ONE
+        host wait of a call; a picture whose tile row overflowed is drawn again through the capacity-free ops (_exact;
+        not for `geometry`, whose picture stays the fast path's own), an overview whose tile lists outgrew their buffer
+        with room for the count its row reports.  images[row] takes picture `row`."""
+        status = self._status[:len(pictures), 0:5].tolist()  # M, overflow, .., .., rANS
+        for row in coded:
+            self._check_expanded(status[row][4])
+        redrawn = []
+        for row, (m, overflow, _, _, _) in enumerate(status):
+            pic = pictures[row]
+            if isinstance(pic.view, Overview):
+                self._overview_m = max(self._overview_m, m)
+                if overflow:  # the lists were cut at the capacity: the same picture again with room for all m
+                    self._reserve_overview([pic], m)
+                    self._launch_overview(pic, fixed[row], row0 + _STATUS_ROW * row, images[row], fmt, aux, m)
+                    redrawn.append(row)
+            elif overflow and not geometry:
+                self._exact(pic, fixed[row], images[row], fmt)
+                redrawn.append(row)
+        return redrawn
+
+    def _run(self, streams, views, fmt: _Format, outs: Optional[Sequence[torch.Tensor]] = None, views_only: bool = False,
+             geometry: bool = False):
+        """decode, decode_many, decode_views and decode_geometry -> (images, aux).  views[k]: the views (or None) of
+        streams[k], a picture per entry, each drawn by launches of its own (_launch); `outs`: a tensor per picture, in
+        call order.  Everything is parsed and checked before anything touches the device.  geometry (one stream, one
+        picture): the per-gaussian outputs of the decode kernel are kept."""
+        headers = _headers(streams)
+        pictures = [_picture(h, _checked_view(v, h, views_only)) for h, vs in zip(headers, views) for v in vs]
         if outs is not None and len(outs) != len(pictures):
-            raise ValueError(f"{who}: one output tensor per {what}")
+            raise ValueError("decode_views: one output tensor per view" if views_only else
+                             "decode_many: one output tensor per stream")
         if not pictures:
             return [], None
         with torch.cuda.device(self.dev):
-            payloads = self._stage(streams, headers)
-            if self._status.shape[0] < len(pictures):
-                self._status = torch.zeros(len(pictures), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
-            self._reserve_workspace(pictures)
-            self._reserve_overview(pictures)
-            slices, total = [], 0
-            for h in headers:
-                slices.append(total)
-                total += (h["fixed_payload_bytes"] + 255) & ~255 if h["coding"] != CODING_FIXED else 0
-            if self._expanded.numel() < total:
-                self._expanded = torch.empty(total, dtype=torch.uint8, device=self.dev)
             images = [self._out(p, None if outs is None else outs[i], fmt) for i, p in enumerate(pictures)]
             aux = self._aux(headers[0]["num_points"]) if geometry else None
-            self._next_token()
-            row0 = self._status.data_ptr()
-            coded, fixed = [], []  # rows that carry an expansion's status word; the coding-0 payload of every picture
-            for h, payload, s, (_, views) in zip(headers, payloads, slices, groups):
-                if h["coding"] != CODING_FIXED:
-                    coded.append(len(fixed))  # the row of the group's first picture
-                    payload = self._expand(h, payload, row0 + _STATUS_ROW * len(fixed),
-                                           self._expanded[s:s + h["fixed_payload_bytes"]])
-                for _ in views:
-                    row = len(fixed)
-                    self._launch(pictures[row], payload, row0 + _STATUS_ROW * row, images[row], aux, fmt)
-                    fixed.append(payload)
-            status = self._status[:len(pictures), 0:5].tolist()  # the one host wait of a call: M, overflow, .., .., rANS
-            for row in coded:
-                self._check_expanded(status[row][4])
-            for row, (m, overflow, _, _, _) in enumerate(status):
-                if isinstance(pictures[row].view, Overview):
-                    self._overview_m = max(self._overview_m, m)
-                    if overflow:  # the lists were cut at the capacity: the same picture again with room for all m
-                        self._reserve_overview([pictures[row]], m)
-                        self._launch_overview(pictures[row], fixed[row], row0 + _STATUS_ROW * row, images[row], aux, m, fmt)
-                elif overflow and not geometry:
-                    self._exact(pictures[row], fixed[row], images[row], fmt)
+            self._reserve_workspace(pictures)
+            fixed, coded, row0 = self._begin(streams, headers, pictures, list(map(len, views)))
+            for row, pic in enumerate(pictures):
+                self._launch(pic, fixed[row], row0 + _STATUS_ROW * row, images[row], fmt, aux)
+            self._finish(pictures, fixed, coded, row0, images, fmt, aux, geometry)
         return images, aux
 
     # ---------------------------------------------------------------------------------------------- batches
@@ -1342,61 +1354,31 @@ class Decoder:
         status rows are read in one host wait behind the last launch; a picture whose tile row overflowed is drawn again
         into its slice (batch_redrawn lists them), its neighbours are left alone."""
         streams = list(streams)
-        headers = [s.header if isinstance(s, DeviceStream) else _parse(s) for s in streams]
+        headers = _headers(streams)
         views = [None] * len(headers) if views is None else list(views)
         height, width = batch_shape(headers, views)
         pictures = [_picture(h, v) for h, v in zip(headers, views)]
-        fmt = _format(dtype, layout) or _DEFAULT_FORMAT
+        fmt = _format(dtype, layout)
         shape = (len(pictures),) + tuple(fmt.shape(height, width))
         if out is not None:
             _check_out(out, shape, fmt.dtype, self.dev)
         groups = self._batch_groups(pictures)
         with torch.cuda.device(self.dev):
-            payloads = self._stage(streams, headers)
-            if self._status.shape[0] < len(pictures):
-                self._status = torch.zeros(len(pictures), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
-            self._reserve_overview(pictures)
             need = max([sum(sizes) for _, sizes in groups], default=0)
             if self._batch_ws.numel() < need:
                 self._batch_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
             need = int(_lib.load().gi2d_codec_batch_bytes(max([len(rows) for rows, _ in groups], default=1)))
             if self._batch_table.numel() < need:
                 self._batch_table = torch.empty(need, dtype=torch.uint8, device=self.dev)
-            slices, total = [], 0
-            for h in headers:
-                slices.append(total)
-                total += (h["fixed_payload_bytes"] + 255) & ~255 if h["coding"] != CODING_FIXED else 0
-            if self._expanded.numel() < total:
-                self._expanded = torch.empty(total, dtype=torch.uint8, device=self.dev)
             if out is None:
                 out = torch.empty(shape, dtype=fmt.dtype, device=self.dev)
-            self._next_token()
-            row0 = self._status.data_ptr()
-            fixed = []  # the coding-0 payload of every picture
-            for row, (h, payload, s) in enumerate(zip(headers, payloads, slices)):
-                if h["coding"] != CODING_FIXED:
-                    payload = self._expand(h, payload, row0 + _STATUS_ROW * row, self._expanded[s:s + h["fixed_payload_bytes"]])
-                fixed.append(payload)
-            for row, p in enumerate(pictures):
-                if isinstance(p.view, Overview):
-                    self._launch_overview(p, fixed[row], row0 + _STATUS_ROW * row, out[row], fmt=fmt)
+            fixed, coded, row0 = self._begin(streams, headers, pictures, [1] * len(pictures))
+            for row, pic in enumerate(pictures):
+                if isinstance(pic.view, Overview):
+                    self._launch_overview(pic, fixed[row], row0 + _STATUS_ROW * row, out[row], fmt)
             for rows, sizes in groups:
                 self._launch_batch(rows, sizes, pictures, fixed, row0, out, fmt)
-            status = self._status[:len(pictures), 0:5].tolist()  # the one host wait of a call
-            self.batch_redrawn = []
-            for row, (h, (m, overflow, _, _, word)) in enumerate(zip(headers, status)):
-                if h["coding"] != CODING_FIXED:
-                    self._check_expanded(word)
-                if isinstance(pictures[row].view, Overview):
-                    self._overview_m = max(self._overview_m, m)
-                    if overflow:
-                        self._reserve_overview([pictures[row]], m)
-                        self._launch_overview(pictures[row], fixed[row], row0 + _STATUS_ROW * row, out[row], None, m, fmt)
-                        self.batch_redrawn.append(row)
-                elif overflow:
-                    self._reserve_workspace([pictures[row]])
-                    self._exact(pictures[row], fixed[row], out[row], fmt)
-                    self.batch_redrawn.append(row)
+            self.batch_redrawn = self._finish(pictures, fixed, coded, row0, out, fmt)
         return out
 
     # ---------------------------------------------------------------------------------------------- public
@@ -1416,23 +1398,34 @@ class Decoder:
         """Several views of ONE stream back to back on the current stream of the device: the payload is staged once, a
         rANS payload expanded once, the workspace reserved for the largest view, and the statuses are read once, at the
         end.  Views and Overviews may be mixed.  dtype, layout: the format of every picture (decode)."""
-        return self._run([(stream, list(views))], outs, views_only=True, fmt=_format(dtype, layout))[0]
+        return self._run([stream], [list(views)], _format(dtype, layout), outs, views_only=True)[0]
 
     def decode_many(self, streams, outs: Optional[Sequence[torch.Tensor]] = None, dtype=None, layout=None) -> List[torch.Tensor]:
         """Streams decoded back to back on the current stream of the device; the overflow statuses are read once, at the
         end.  dtype, layout: the format of every picture (decode)."""
-        return self._run([(s, (None,)) for s in streams], outs, fmt=_format(dtype, layout))[0]
+        streams = list(streams)
+        return self._run(streams, [(None,)] * len(streams), _format(dtype, layout), outs)[0]
 
     def decode_geometry(self, stream, view: Optional[View] = None) -> Dict[str, torch.Tensor]:
         """What the decode kernel makes of every gaussian: xys, radii, conics, num_tiles_hit, colors (tests, tools); with
         a view, the transformed geometry in the view's pixel grid.  `image` is the fast path's own picture: a crowded
         tile is not drawn again.  With an Overview: the covariance projection of the transformed, prefiltered gaussians,
         `colors` rescaled, and `image` the overview itself (drawn again if its lists outgrew their buffer)."""
-        images, aux = self._run([(stream, (view,))], geometry=True)
+        images, aux = self._run([stream], [(view,)], _DEFAULT_FORMAT, geometry=True)
         return dict(zip(("xys", "radii", "conics", "num_tiles_hit", "colors"), aux), image=images[0])
 
 
 _decoders: Dict[torch.device, Decoder] = {}
+
+
+def _decoder(device: Union[str, torch.device]) -> Decoder:
+    """The Decoder kept for a device (the current one for a bare "cuda"), made at its first use."""
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if dev not in _decoders:
+        _decoders[dev] = Decoder(dev)
+    return _decoders[dev]
 
 
 def decode(blob, device: Union[str, torch.device] = "cuda:0", out: Optional[torch.Tensor] = None,
@@ -1444,13 +1437,8 @@ def decode(blob, device: Union[str, torch.device] = "cuda:0", out: Optional[torc
     fmt = _format(dtype, layout)
     if out is not None:
         pic = _picture(h, view)
-        _check_out(out, (fmt or _DEFAULT_FORMAT).shape(pic.height, pic.width), (fmt or _DEFAULT_FORMAT).dtype)
-    dev = torch.device(device)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if dev not in _decoders:
-        _decoders[dev] = Decoder(dev)
-    return _decoders[dev].decode(blob, out=out, view=view, dtype=dtype, layout=layout)
+        _check_out(out, fmt.shape(pic.height, pic.width), fmt.dtype)
+    return _decoder(device).decode(blob, out=out, view=view, dtype=dtype, layout=layout)
 
 
 def decode_batch(blobs, device: Union[str, torch.device] = "cuda:0", views=None, out: Optional[torch.Tensor] = None,
@@ -1458,13 +1446,8 @@ def decode_batch(blobs, device: Union[str, torch.device] = "cuda:0", views=None,
     """One-shot Decoder.decode_batch (the Decoder kept per device): K streams -> one [K, *format shape] tensor."""
     blobs, views = list(blobs), None if views is None else list(views)
     # malformed streams, views, sizes, formats and `out` are refused before a device is even touched
-    height, width = batch_shape([b.header if isinstance(b, DeviceStream) else _parse(b) for b in blobs], views)
-    fmt = _format(dtype, layout) or _DEFAULT_FORMAT
+    height, width = batch_shape(_headers(blobs), views)
+    fmt = _format(dtype, layout)
     if out is not None:
         _check_out(out, (len(blobs),) + tuple(fmt.shape(height, width)), fmt.dtype)
-    dev = torch.device(device)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if dev not in _decoders:
-        _decoders[dev] = Decoder(dev)
-    return _decoders[dev].decode_batch(blobs, views=views, out=out, dtype=dtype, layout=layout)
+    return _decoder(device).decode_batch(blobs, views=views, out=out, dtype=dtype, layout=layout)

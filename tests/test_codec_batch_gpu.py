@@ -174,6 +174,37 @@ def test_a_crowded_picture_in_the_middle_is_redrawn_alone():
         assert torch.equal(dec.decode(small), reference().decode(small))
 
 
+def test_both_drivers_redraw_the_same_two_pictures():
+    """Every branch of what follows the draw -- the one status read, the expansion's word, an overflowed tile row, an
+    overview whose lists overflowed -- through both host drivers, on the same four pictures: a coding-0 stream, a rANS
+    stream, the crowded stream, and an Overview whose lists start with ONE entry.  decode_many takes whole pictures only,
+    so on that side the Overview is a decode(view=) call of the same Decoder behind the one decode_many call."""
+    from gaussianimage_plus_amd import codec
+    fmt = (torch.uint8, "hwc")
+    ov = codec.Overview(1.0, 1.0, 100, 72, 0.55)
+    blobs = [stream("cov"), codec.recode(stream("rs"), "rans", device=DEV), crowded_stream(), stream("cov200")]
+    views = [None, None, None, ov]
+    want = [codec.Decoder(DEV).decode(b, view=v, dtype=fmt[0], layout=fmt[1]) for b, v in zip(blobs, views)]
+    assert not torch.equal(want[2], want[0]) and float(want[3].float().mean()) < 255.0
+    one = codec.Decoder(DEV)
+    one.overview_capacity = 1
+    before = one.expansions
+    many = one.decode_many(blobs[:3], dtype=fmt[0], layout=fmt[1])
+    assert one.expansions == before + 1
+    assert one._status[2, 1].item() != 0 and one._status[1, 1].item() == 0, "only the crowded picture's tile row overflowed"
+    many.append(one.decode(blobs[3], view=ov, dtype=fmt[0], layout=fmt[1]))
+    assert one._overview_m > 1 and one.expansions == before + 1
+    dec = codec.Decoder(DEV)
+    dec.overview_capacity = 1
+    before = dec.expansions
+    got = dec.decode_batch(blobs, views, dtype=fmt[0], layout=fmt[1])
+    assert dec.expansions == before + 1
+    assert dec.batch_redrawn == [2, 3] and dec._overview_m == one._overview_m
+    for k in range(4):
+        assert torch.equal(many[k], want[k]), ("decode_many / decode", k, int((many[k] != want[k]).sum()))
+        assert torch.equal(got[k], want[k]), ("decode_batch", k, int((got[k] != want[k]).sum()))
+
+
 # ------------------------------------------------------------------------------------------ 8. nothing outside `out`
 SENTINEL = 0xA5
 PAD = 64

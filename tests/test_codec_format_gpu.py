@@ -11,6 +11,7 @@ import torch
 
 from helpers_codec_format import (COV_BITS, FORMATS, ORIGINAL_COLOUR, RS_BITS, STREAMS, as_picture, format_id, random_stream,
                                   rounding_inputs, shape_of, stream)
+from helpers_codec_chain import unfused_chain, unfused_view_chain
 from oracle import codec_oracle as CO
 
 pytestmark = pytest.mark.gpu
@@ -72,17 +73,28 @@ def test_coded_streams_in_two_formats(coding, order):
     assert dec.expansions == before + 2
 
 
-# ------------------------------------------------------------------ 2. float32 "hwc" is the default picture, bit for bit
+# ------------------------------------- 2. float32 "hwc" is the fitting forward followed by a clamp, bit for bit
 @pytest.mark.parametrize("name", ALL)
 def test_float32_hwc_equals_the_default_decode_bit_for_bit(name):
+    """A call without a format IS a float32 "hwc" call, so the anchor is outside the codec: the unfused chain of
+    helpers_codec_chain.py, which ends in gi2d_fast_rasterize_forward (the fitting forward) and a clamp in torch.  The
+    chains assert that no tile row overflowed (status[1] == 0) and so serve uncrowded pictures only: that is every
+    stream of STREAMS under every view of views_of -- at most 1 200 gaussians, spread over the whole picture.  For the
+    two Overviews both sides are one C function; test_codec_overview_gpu.py anchors that one."""
     from gaussianimage_plus_amd import codec
     blob = stream(name)
     dec = codec.Decoder(DEV)
     for view in views_of(name):
-        ref = dec.decode(blob, view=view).clone()
         got = dec.decode(blob, view=view, dtype=torch.float32, layout="hwc")
+        if view is None:
+            ref = unfused_chain(blob)["image"]
+        elif isinstance(view, codec.View):
+            ref = unfused_view_chain(blob, view)["image"]
+        else:
+            ref = dec.decode(blob, view=view).clone()
         assert got.dtype == torch.float32 and got.shape == ref.shape
         assert torch.equal(got.view(torch.int32), ref.view(torch.int32)), (name, view)
+        assert torch.equal(dec.decode(blob, view=view).view(torch.int32), ref.view(torch.int32)), (name, view, "no format given")
         assert float(ref.min()) >= 0.0 and float(ref.max()) <= 1.0 and float(ref.min()) < 1.0
 
 

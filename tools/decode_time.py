@@ -1,7 +1,7 @@
 """Decode time of a packed stream (gaussianimage_plus_amd/codec.py) on one 768x512 picture: one JSON line.
 
 For N = 5 000 and N = 50 000 (covariance model, 12 / 10 / 6 bits), microseconds per decode
-    device  payload already on the device (Decoder.upload): workspace reset + decode/bin + forward + clamp
+    device  payload already on the device (Decoder.upload): workspace reset + decode/bin + draw (gi2d_codec_draw)
     bytes   from host bytes: header parse, CRC, one host-to-device copy, the same launches
     legacy  the same encoding through NativeFitter.decompress_wo_ec (quantiser decompress launches, the projection and
             rasterize operators with their allocations)
@@ -31,11 +31,10 @@ to the only route there is without overviews (`route_us`): the full decode follo
 
 --format DTYPE,LAYOUT (repeatable; float32 | float16 | uint8, hwc | chw | hwc4) adds, per fit and format, with the payload
 on the device: `format_us`, Decoder.decode(stream, dtype=, layout=) -- workspace reset + decode/bin + the decode's own
-draw kernel, which ends in the clamp, the conversion and the layout -- next to `route_us`, the only other route: today's
-float32 decode followed by codec.convert in torch.  For float32,hwc the row also holds `default_us`, today's default
-decode (fitting forward + clamp launch), timed in the same run: the draw kernel against it is the number that decides
-which of the two the default should be.  With --trace the formats are decoded too, so that the kernel trace holds the
-draw kernel next to fast_fwd_kernel and the clamp.  Same regions, same discipline (profiles/decode_format_time.json).
+draw kernel, which ends in the clamp, the conversion and the layout -- next to `route_us`, the only other route: the
+float32 decode followed by codec.convert in torch.  With --trace the formats are decoded too, so that the kernel trace
+holds every instantiation of the draw kernel.  Same regions, same discipline (profiles/decode_format_time.json; its
+`default_us` is the default decode of the time, the fitting forward and a clamp launch, which that file retired).
 
 --batch adds, per fit, `batches`: Decoder.decode_batch of K = 1, 8 and 64 uploaded streams in float16 "chw" (`batch_us`) next
 to Decoder.decode_many of the same streams in the same format (`many_us`), and K = 64 with a 224x224 codec.View per
@@ -195,8 +194,6 @@ def format_rows(a, dec, up, full):
         r = {"dtype": str(dtype).replace("torch.", ""), "layout": layout, "bytes_per_picture": fout.numel() * fout.element_size()}
         timed(r, "format", lambda: dec.decode(up, out=fout, dtype=dtype, layout=layout), a.reps)
         timed(r, "route", lambda: codec.convert(dec.decode(up, out=full), dtype, layout), a.reps)
-        if (dtype, layout) == (torch.float32, "hwc"):
-            timed(r, "default", lambda: dec.decode(up, out=full), a.reps)
         rows.append(r)
     return rows
 
