@@ -89,6 +89,14 @@ SIGNATURES.update({
     "gi2d_codec_convert": [_i, _i, _u, _u, _p, _p, _p],
     # several pictures per decode launch: host array of struct gi2d_codec_picture (gaussianimage_plus_amd/codec.py::_CPicture)
     "gi2d_codec_decode_batch": [_i, _p, _p, _sz, _u, _u, _i, _i, _p, _i, _i, _p, _p],
+    # affine views: the view launch with an affine map, its whole-row draw, the capacity-free route's per-gaussian kernel,
+    # and the batched call with a parallel array of struct gi2d_codec_affine (codec.py::_CAffine)
+    "gi2d_codec_decode_bin_affine": [_i, _i, _i, _i, _i, _i, _p, _p, _sz, _f, _u, _u, _f, _f, _f, _f, _f, _f, _f, _f, _f,
+                                     _u, _u, _i, _i, _f, _p, _p, _p, _p, _p, _p, _sz, _p, _p],
+    "gi2d_codec_decode_affine": [_i, _i, _i, _i, _i, _i, _p, _p, _sz, _f, _u, _u, _f, _f, _f, _f, _f, _f, _f, _f, _f, _u, _u,
+                                 _i, _i, _f, _p, _p, _p, _p, _p, _p],
+    "gi2d_codec_draw_rows": [_i, _i, _i, _u, _u, _p, _p, _sz, _p, _i, _i, _p, _p],
+    "gi2d_codec_decode_batch_affine": [_i, _p, _p, _p, _sz, _u, _u, _i, _i, _p, _i, _i, _p, _p],
     # rANS payload (payload coding 1)
     "gi2d_codec_histogram": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p],
     "gi2d_codec_rans_encode": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _sz, _p, _sz, _p, _p],

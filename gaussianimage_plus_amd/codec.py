@@ -22,6 +22,8 @@
     crops = [codec.View(x0, y0, 224, 224) for x0, y0 in origins]                  # one window per stream, all at one size
     batch = dec.decode_batch(blobs, crops, dtype=torch.float16, layout="chw")     # f16 [K, 3, 224, 224]: a network's batch,
                                                  # three launches per 64 pictures, picture k bit for bit decode(blobs[k], view=crops[k], ...)
+    aug  = codec.Affine.resized_crop(x0, y0, src_w, src_h, 224, 224, hflip=True)  # a scale per axis, a flip; Affine.rotated(...)
+    batch = dec.decode_batch(blobs, [aug, ...], dtype=torch.float16, layout="chw")  # affine views share the three launches
 
 Decoding needs no fitter, no target image and no optimizer state: this module imports neither `trainer` nor `quantize`.
 A decode is three native launches on buffers the Decoder owns -- gi2d_fast_workspace_init, gi2d_codec_decode_bin
@@ -48,6 +50,16 @@ holds far more than 256 gaussians, so an overview has launches of its own -- gi2
 transformed gaussian -> covariance projection), the capacity-free gi2d_bin_gaussians, and gi2d_rasterize_forward_long_as,
 which walks every tile list to its end (csrc/gi2d_codec_overview.hip) -- on buffers the Decoder keeps; the binning status joins
 the picture's status row, and a picture whose lists did not fit their buffer is drawn again with room for all of them.
+
+An affine view (codec.Affine, DESIGN.md 3.8 "Affine views") is the same argument for a general affine map of the pixel grid:
+a scale of its own per axis, a negative scale (a flip), a rotation, a shear -- an input pipeline's random resized crop.  A
+gaussian under an affine map is a gaussian, so the map is carried out exactly, on the parameters (affine_parameters states
+the arithmetic: centre B (c - origin), covariance B S B^T + P with B the inverse map and P the low-pass an axis that
+reduces needs, colour rescaled so that the mass stays), in the decode/bin kernel (gi2d_codec_decode_bin_affine), and the
+picture is drawn by the fast path with every tile consuming its WHOLE row, 256 staged entries at a time
+(gi2d_codec_draw_rows), so it shares decode_batch's three launches.  A row holds 1024 candidates; a picture with a fuller
+tile is drawn again through the launches an overview has (gi2d_codec_decode_affine in place of the overview kernel), which
+walk the same ascending lists with the same arithmetic: the two routes give the same bits (Decoder.affine_route pins one).
 
 A picture FORMAT (DESIGN.md 3.8 "Picture formats") is a decoder argument too: dtype float32, float16 or uint8 times layout
 "hwc" [H, W, 3], "chw" [3, H, W] or "hwc4" [H, W, 4] (channel 3 = the element of 1.0).  `convert` states the arithmetic:
@@ -774,13 +786,193 @@ class Overview:
         return float(np.float32(header["radius_clip"]) * np.float32(self.scale))
 
 
-def _checked_view(view, h, required: bool = False) -> Optional[Union[View, Overview]]:
+MIN_AFFINE_SINGULAR, MAX_AFFINE_SINGULAR = 1.0 / 64.0, 64.0
+MAX_AFFINE_PREFILTER = 4.0
+
+
+def _singular_values(b00: float, b01: float, b10: float, b11: float) -> Tuple[float, float]:
+    """(largest, smallest) singular value of a 2x2 matrix, closed form in double (what the C entries evaluate)."""
+    t = b00 * b00 + b01 * b01 + b10 * b10 + b11 * b11
+    d = b00 * b11 - b01 * b10
+    disc = math.sqrt(max(t * t - 4.0 * d * d, 0.0))
+    smax = math.sqrt((t + disc) / 2.0)
+    return smax, (abs(d) / smax if smax > 0.0 else 0.0)
+
+
+def _finite_numbers(who: str, **values) -> None:
+    """ValueError unless every keyword is a finite number (no bool, no string)."""
+    for name, v in values.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{who}: {name} must be a number, not {type(v).__name__}")
+        if not math.isfinite(float(v)):
+            raise ValueError(f"{who}: {name} = {float(v)} is not finite")
+
+
+@dataclasses.dataclass(frozen=True)
+class Affine:
+    """An AFFINE view of the fitted function (DESIGN.md 3.8 "Affine views"): output pixel (row i, column j) of a `height` x
+    `width` picture samples the function, low-passed, at source position (x0 + m00 j + m01 i, y0 + m10 j + m11 i) -- a
+    resized crop with a scale of its own per axis (reducing on one, magnifying on the other), a flip (a negative scale),
+    a rotation, a shear: what an input pipeline's augmentation asks for.  The six numbers are kept as the float32 values
+    they round to.  Derived once, here:
+        inverse     (b00, b01, b10, b11) = M^-1, computed in float64 from the float32 values and rounded to float32: what
+                    the kernel receives
+        prefilter   (pxx, pxy, pyy), the VARIANCE of the low-pass in output pixels^2.  None: P = (I - B B^T) / 12 in
+                    float64 on the float32 B, its eigenvalues clipped at 0, rounded to float32 (for B = s I that is
+                    Overview's default below s = 1 and zero from there on: an axis that magnifies is not filtered); a
+                    number v: (v, 0, v); a triple: as given
+    ValueError unless everything is finite, both singular values of B lie in 1/64 .. 64, P is positive semi-definite with
+    pxx, pyy <= 4, the size is at least 1 x 1 and ceil(width / 16) * ceil(height / 16) <= 16384 tiles.  Whether its corner
+    pixels sample positions inside a picture is checked against the stream's header by the decoder (`check`)."""
+    x0: float
+    y0: float
+    m00: float
+    m01: float
+    m10: float
+    m11: float
+    width: int
+    height: int
+    prefilter: Optional[Union[float, Tuple[float, float, float]]] = None
+    inverse: Tuple[float, float, float, float] = dataclasses.field(init=False, repr=False, compare=False, default=())
+
+    def __post_init__(self):
+        number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+        for name in ("x0", "y0", "m00", "m01", "m10", "m11"):
+            v = getattr(self, name)
+            if not number(v):
+                raise ValueError(f"Affine: {name} must be a number, not {type(v).__name__}")
+            if not math.isfinite(float(v)):
+                raise ValueError(f"Affine: {name} = {float(v)} is not finite")
+            with np.errstate(over="ignore"):
+                v32 = float(np.float32(v))
+            if not math.isfinite(v32):
+                raise ValueError(f"Affine: {name} = {float(v)} is not a finite float32")
+            object.__setattr__(self, name, v32)
+        for name in ("width", "height"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"Affine: {name} must be an integer, not {type(v).__name__}")
+            object.__setattr__(self, name, int(v))
+        det = self.m00 * self.m11 - self.m01 * self.m10  # (double, on the float32 values)
+        if det == 0.0 or not math.isfinite(1.0 / det):
+            raise ValueError("Affine: the map is singular")
+        with np.errstate(over="ignore"):
+            b = tuple(float(np.float32(v)) for v in (self.m11 / det, -self.m01 / det, -self.m10 / det, self.m00 / det))
+        if not all(math.isfinite(v) for v in b):
+            raise ValueError("Affine: the inverse of the map is not finite in float32")
+        smax, smin = _singular_values(*b)
+        if not (smin >= MIN_AFFINE_SINGULAR and smax <= MAX_AFFINE_SINGULAR):
+            raise ValueError(f"Affine: the singular values {smin:.6g}, {smax:.6g} of the inverse map do not lie in 1/64 .. 64")
+        object.__setattr__(self, "inverse", b)
+        p = self.prefilter
+        if p is None:
+            p = self._default_prefilter(b)
+        elif number(p):
+            p = (float(p), 0.0, float(p))
+        else:
+            try:
+                p = tuple(p)
+            except TypeError:
+                raise ValueError(f"Affine: prefilter {p!r}: None, a variance, or a triple (pxx, pxy, pyy)") from None
+            if len(p) != 3 or not all(number(v) for v in p):
+                raise ValueError(f"Affine: prefilter {p!r}: None, a variance, or a triple (pxx, pxy, pyy)")
+        if not all(math.isfinite(float(v)) for v in p):
+            raise ValueError(f"Affine: prefilter {p} is not finite")
+        with np.errstate(over="ignore"):
+            p = tuple(float(np.float32(v)) for v in p)
+        pxx, pxy, pyy = p
+        if not all(math.isfinite(v) for v in p) or pxx < 0.0 or pyy < 0.0 or pxx * pyy - pxy * pxy < 0.0:
+            raise ValueError(f"Affine: prefilter {p} is not a positive semi-definite variance")
+        if pxx > MAX_AFFINE_PREFILTER or pyy > MAX_AFFINE_PREFILTER:
+            raise ValueError(f"Affine: prefilter variances {pxx}, {pyy} above {MAX_AFFINE_PREFILTER:g} output pixels^2")
+        object.__setattr__(self, "prefilter", p)
+        if self.width < 1 or self.height < 1:
+            raise ValueError(f"Affine: empty output {self.width}x{self.height}")
+        if self.tiles[0] * self.tiles[1] > MAX_VIEW_TILES:
+            raise ValueError(f"Affine: {self.width}x{self.height} is more than {MAX_VIEW_TILES} tiles of 16x16 (compose a "
+                             "larger output from several views)")
+
+    @staticmethod
+    def _default_prefilter(b) -> Tuple[float, float, float]:
+        """(I - B B^T) / 12 in float64, eigenvalues clipped at 0, rounded to float32.  Rounding may leave the determinant
+        of a clipped (rank one) matrix a few ulp below 0: pxy then moves towards 0, one float32 at a time, until it is
+        not -- the products of two float32 are exact in double, so the sign is."""
+        b00, b01, b10, b11 = b
+        q = np.array([[1.0 - (b00 * b00 + b01 * b01), -(b00 * b10 + b01 * b11)],
+                      [-(b00 * b10 + b01 * b11), 1.0 - (b10 * b10 + b11 * b11)]], np.float64) / 12.0
+        lam, vec = np.linalg.eigh(q)
+        q = (vec * np.maximum(lam, 0.0)) @ vec.T
+        pxx, pxy, pyy = np.float32(max(q[0, 0], 0.0)), np.float32(q[0, 1]), np.float32(max(q[1, 1], 0.0))
+        while float(pxx) * float(pyy) - float(pxy) * float(pxy) < 0.0:
+            pxy = np.nextafter(pxy, np.float32(0))
+        return float(pxx), float(pxy), float(pyy)
+
+    @property
+    def tiles(self):
+        return _tiles(self.width), _tiles(self.height)
+
+    @classmethod
+    def resized_crop(cls, x0, y0, src_w, src_h, width: int, height: int, hflip: bool = False, vflip: bool = False,
+                     prefilter=None) -> "Affine":
+        """The src_w x src_h source pixels whose first one is (x0, y0), resampled to width x height with the pixel-centre
+        convention of Overview.thumbnail: sx = src_w / width, output column j samples x0 + (sx - 1) / 2 + sx j; flipped,
+        x0 + src_w - 0.5 - sx / 2 - sx j.  The same for y."""
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"Affine.resized_crop: {name} {v!r} is not an integer >= 1")
+        _finite_numbers("Affine.resized_crop", x0=x0, y0=y0, src_w=src_w, src_h=src_h)
+        sx, sy = float(src_w) / width, float(src_h) / height
+        ox, mx = (x0 + src_w - 0.5 - sx / 2, -sx) if hflip else (x0 + (sx - 1) / 2, sx)
+        oy, my = (y0 + src_h - 0.5 - sy / 2, -sy) if vflip else (y0 + (sy - 1) / 2, sy)
+        return cls(ox, oy, mx, 0.0, 0.0, my, width, height, prefilter)
+
+    @classmethod
+    def rotated(cls, cx, cy, degrees, scale, width: int, height: int, prefilter=None) -> "Affine":
+        """M = R(degrees) / scale, R = [[cos, -sin], [sin, cos]] (scale > 1 magnifies), with the output's centre
+        ((width - 1) / 2, (height - 1) / 2) on source position (cx, cy)."""
+        _finite_numbers("Affine.rotated", cx=cx, cy=cy, degrees=degrees, scale=scale)
+        if float(scale) == 0.0:
+            raise ValueError("Affine.rotated: scale 0")
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"Affine.rotated: {name} must be an integer, not {type(v).__name__}")
+        t = math.radians(float(degrees))
+        c, s = math.cos(t) / float(scale), math.sin(t) / float(scale)
+        m00, m01, m10, m11 = (float(np.float32(v)) for v in (c, -s, s, c))
+        jc, ic = (width - 1) / 2, (height - 1) / 2
+        return cls(cx - (m00 * jc + m01 * ic), cy - (m10 * jc + m11 * ic), m00, m01, m10, m11, width, height, prefilter)
+
+    def source(self, j: float, i: float) -> Tuple[float, float]:
+        """Source position of output pixel (row i, column j), in double on the float32 values."""
+        return self.x0 + self.m00 * j + self.m01 * i, self.y0 + self.m10 * j + self.m11 * i
+
+    def check(self, header) -> "Affine":
+        """ValueError unless the four corner pixel centres sample positions inside [0, W - 1] x [0, H - 1], in double on
+        the float32 values."""
+        for j in (0, self.width - 1):
+            for i in (0, self.height - 1):
+                x, y = self.source(j, i)
+                if not (0.0 <= x <= header["width"] - 1.0 and 0.0 <= y <= header["height"] - 1.0):
+                    raise ValueError(f"Affine: output pixel (row {i}, column {j}) samples ({x:.6g}, {y:.6g}), outside the "
+                                     f"sample grid of the {header['width']}x{header['height']} picture")
+        return self
+
+    def radius_clip(self, header) -> float:
+        """The stream's radius_clip * sqrt(|det B|) (float32 product of two float32): View's rule with the map's mean scale."""
+        b00, b01, b10, b11 = self.inverse
+        return float(np.float32(header["radius_clip"]) * np.float32(math.sqrt(abs(b00 * b11 - b01 * b10))))
+
+
+_VIEW_TYPES = (View, Overview, Affine)
+
+
+def _checked_view(view, h, required: bool = False) -> Optional[Union[View, Overview, Affine]]:
     if view is None:
         if required:
-            raise ValueError("decode_views: every entry is a codec.View or a codec.Overview")
+            raise ValueError("decode_views: every entry is a codec.View, a codec.Overview or a codec.Affine")
         return None
-    if not isinstance(view, (View, Overview)):
-        raise ValueError("view: a codec.View or codec.Overview (or None for the whole picture at its own size)")
+    if not isinstance(view, _VIEW_TYPES):
+        raise ValueError("view: a codec.View, codec.Overview or codec.Affine (or None for the whole picture at its own size)")
     return view.check(h)
 
 
@@ -870,6 +1062,64 @@ def overview_parameters(kind: int, values, ov: Overview):
     return out
 
 
+def affine_parameters(kind: int, values, affine: Affine):
+    """The specification of an affine view on the dequantised gaussians.  values: float32 [N, 8] in record order (numpy
+    array or torch tensor; the log channels already through exp) -> float32 [N, 8] of the same kind of array IN THE
+    COVARIANCE MODEL'S LAYOUT for either kind: x', y', cxx', cxy', cyy', r', g', b'.  With (b00, b01, b10, b11) =
+    affine.inverse and (pxx, pxy, pyy) = affine.prefilter, separate float32 operations, in this order:
+        dx = x - x0, dy = y - y0
+        x' = b00 * dx + b01 * dy,  y' = b10 * dx + b11 * dy                 (two products, one sum each)
+        (a, b, c) = the covariance; scale-rot model: formed as overview_parameters forms it, with scale 1
+        n00 = b00 * a + b01 * b,  n01 = b00 * b + b01 * c,  n10 = b10 * a + b11 * b,  n11 = b10 * b + b11 * c
+        cxx = n00 * b00 + n01 * b01,  cxy = n00 * b10 + n01 * b11,  cyy = n10 * b10 + n11 * b11       (B S B^T)
+        det0 = cxx * cyy - cxy * cxy
+        cxx' = cxx + pxx, cxy' = cxy + pxy, cyy' = cyy + pyy
+        det1 = cxx' * cyy' - cxy' * cxy'
+        g = sqrt(max(det0, 0) / det1);  colour' = colour * g             (the mass is kept, the opacity stays 1)
+    The view is the picture the operators draw for these gaussians AS COVARIANCE-MODEL GAUSSIANS at affine.height x
+    affine.width with the header's clip_coe and radius_clip = affine.radius_clip(header), every tile consuming its whole
+    list in ascending id order, clamped to [0, 1]; all ones if no gaussian reaches the window.  A host tensor takes the
+    numpy form (overview_parameters says why)."""
+    if kind not in _KIND_NAMES:
+        raise ValueError(f"affine_parameters: model kind {kind} (1 covariance, 2 scale-rot)")
+    if tuple(values.shape[1:]) != (8,) or "float32" not in str(values.dtype):
+        raise ValueError("affine_parameters: a float32 [N, 8] array")
+    is_torch = isinstance(values, torch.Tensor)
+    if is_torch and values.device.type == "cpu":
+        return torch.from_numpy(affine_parameters(kind, values.detach().numpy(), affine))
+    num = float if is_torch else np.float32  # a tensor takes a Python scalar at its own precision
+    x0, y0 = num(affine.x0), num(affine.y0)
+    b00, b01, b10, b11 = (num(v) for v in affine.inverse)
+    pxx, pxy, pyy = (num(v) for v in affine.prefilter)
+    out = values.clone() if is_torch else np.array(values, np.float32)
+    dx, dy = values[:, 0] - x0, values[:, 1] - y0
+    out[:, 0] = dx * b00 + dy * b01
+    out[:, 1] = dx * b10 + dy * b11
+    if kind == KIND_COVARIANCE:
+        a, b, c = values[:, 2], values[:, 3], values[:, 4]
+    else:
+        sx, sy = values[:, 2], values[:, 3]
+        cs, sn = (torch.cos(values[:, 4]), torch.sin(values[:, 4])) if is_torch else (np.cos(values[:, 4]), np.sin(values[:, 4]))
+        zero = num(0.0)
+        m00, m10 = cs * sx + sn * zero, -sn * sx + cs * zero
+        m01, m11 = cs * zero + sn * sy, -sn * zero + cs * sy
+        a, b, c = m00 * m00 + m01 * m01, m10 * m00 + m11 * m01, m10 * m10 + m11 * m11
+    n00, n01 = a * b00 + b * b01, b * b00 + c * b01
+    n10, n11 = a * b10 + b * b11, b * b10 + c * b11
+    cxx, cxy, cyy = n00 * b00 + n01 * b01, n00 * b10 + n01 * b11, n10 * b10 + n11 * b11
+    det0 = cxx * cyy - cxy * cxy
+    cxx, cxy, cyy = cxx + pxx, cxy + pxy, cyy + pyy
+    det1 = cxx * cyy - cxy * cxy
+    if is_torch:
+        g = torch.sqrt(torch.clamp(det0, min=0.0) / det1)
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            g = np.sqrt(np.maximum(det0, np.float32(0)) / det1)
+    out[:, 2], out[:, 3], out[:, 4] = cxx, cxy, cyy
+    out[:, 5:8] = values[:, 5:8] * g[:, None]
+    return out
+
+
 PIXEL_DTYPES = {torch.float32: 0, torch.float16: 1, torch.uint8: 2}  # GI2D_PIXEL_* of the C ABI
 LAYOUTS = {"hwc": 0, "chw": 1, "hwc4": 2}                            # GI2D_LAYOUT_*
 
@@ -936,7 +1186,7 @@ def convert(img: torch.Tensor, dtype=None, layout=None) -> torch.Tensor:
 class _Picture(NamedTuple):
     """What one launch sequence draws, derived once (_picture) from (header, view or None)."""
     header: Dict[str, object]
-    view: Optional[Union[View, Overview]]  # None: the whole picture at its own size, through the full decode's entry
+    view: Optional[Union[View, Overview, Affine]]  # None: the whole picture at its own size, through the full decode's entry
     width: int
     height: int
     tx: int
@@ -957,7 +1207,7 @@ BATCH_MAX = 64  # GI2D_BATCH_MAX: pictures per gi2d_codec_decode_batch call
 
 def batch_shape(headers, views=None) -> Tuple[int, int]:
     """(height, width) of the pictures of a decode_batch call, on the host: headers are parsed streams (codec.info, or
-    a DeviceStream's header), views None or one entry per header (None, a codec.View or a codec.Overview, each checked
+    a DeviceStream's header), views None or one entry per header (None, a codec.View, Overview or Affine, each checked
     against its header).  ValueError for an empty batch, a views list of another length, an entry that is no view, and
     for the first picture whose size is not picture 0's."""
     headers = list(headers)
@@ -984,6 +1234,11 @@ class _CPicture(C.Structure):
                 ("payload_bytes", C.c_size_t), ("clip_coe", C.c_float), ("img_height", C.c_uint), ("img_width", C.c_uint),
                 ("view", C.c_int), ("x0", C.c_float), ("y0", C.c_float), ("scale", C.c_float), ("radius_clip", C.c_float),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("status", C.c_void_p)]
+
+
+class _CAffine(C.Structure):
+    """struct gi2d_codec_affine of include/gi2d.h: the map of a picture whose descriptor says view = 2."""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("b", C.c_float * 4), ("prefilter", C.c_float * 3)]
 
 
 _STATUS_WORDS = 8
@@ -1039,12 +1294,32 @@ class Decoder:
         self._batch_ws = torch.empty(0, dtype=torch.uint8, device=self.dev)
         self._batch_table = torch.empty(0, dtype=torch.uint8, device=self.dev)
         self.batch_redrawn: List[int] = []  # pictures of the last decode_batch call that were drawn again (overflow)
+        # affine views: None = the fast path's whole-row draw, drawn again through the tile lists of the capacity-free ops
+        # where a row overflowed; "rows" / "lists" pin one of the two (tests, tools/decode_time.py): "rows" raises
+        # RuntimeError instead of drawing again, "lists" never touches the fast path
+        self._lists_types: Tuple[type, ...] = (Overview,)  # views first drawn through tile lists (affine_route's setter)
+        self.affine_route = None
+        self.overflowed: List[int] = []  # rows of the last call whose status word 1 was set at the call's host wait
+        self.redrawn: List[int] = []     # rows of the last call that were drawn again
 
     # ---------------------------------------------------------------------------------------------- buffers
+    @property
+    def affine_route(self) -> Optional[str]:
+        return self._affine_route
+
+    @affine_route.setter
+    def affine_route(self, route: Optional[str]) -> None:
+        if route not in (None, "rows", "lists"):
+            raise ValueError(f"affine_route {route!r}: None, 'rows' or 'lists'")
+        self._affine_route = route
+        # the views whose pictures are first drawn through tile lists of any length (launches of their own,
+        # _launch_overview): what the per-picture loops of the host driver test a view against
+        self._lists_types = (Overview, Affine) if route == "lists" else (Overview,)
+
     def _reserve_workspace(self, pictures: Sequence[_Picture]) -> None:
         size = _lib.load().gi2d_fast_workspace_bytes
-        need = max([int(size(p.header["num_points"], p.tx, p.ty)) for p in pictures if not isinstance(p.view, Overview)],
-                   default=0)
+        need = max([int(size(p.header["num_points"], p.tx, p.ty)) for p in pictures
+                    if not isinstance(p.view, self._lists_types)], default=0)
         if self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
 
@@ -1053,9 +1328,11 @@ class Decoder:
         max(4 n, the largest count seen); a picture that needs more is drawn again with exactly what it needs."""
         return max(1, int(self.overview_capacity)) if self.overview_capacity is not None else max(4 * n, self._overview_m)
 
-    def _reserve_overview(self, pictures: Sequence[_Picture], capacity: Optional[int] = None) -> None:
-        """The buffers of the overviews among `pictures`, each at least as large as the largest of them needs."""
-        ovs = [p for p in pictures if isinstance(p.view, Overview)]
+    def _reserve_overview(self, pictures: Sequence[_Picture], capacity: Optional[int] = None, every: bool = False) -> None:
+        """The buffers of the pictures among `pictures` that are drawn through tile lists (_lists_types; every: all of
+        them), each at least as large as the largest of them needs."""
+        lists_types = self._lists_types
+        ovs = [p for p in pictures if every or isinstance(p.view, lists_types)]
         if not ovs:
             return
         n = max(p.header["num_points"] for p in ovs)
@@ -1149,7 +1426,7 @@ class Decoder:
         a coding-0 payload on the current stream, at the picture's size, with the status row at `status`; no host sync
         and no allocation.  aux: five tensors that take the decode kernel's per-gaussian outputs."""
         h, view, w, hh, tx, ty = pic
-        if isinstance(view, Overview):
+        if isinstance(view, self._lists_types):
             return self._launch_overview(pic, payload, status, out, fmt, aux)
         n = h["num_points"]
         b = h["bits"]
@@ -1158,6 +1435,14 @@ class Decoder:
         st = _stream(self.dev)
         a = [C.c_void_p(t.data_ptr()) for t in aux] if aux is not None else [None] * 5
         _lib.call("gi2d_fast_workspace_init", ws, nws, n, tx, ty, st)
+        if isinstance(view, Affine):
+            _lib.call("gi2d_codec_decode_bin_affine", h["kind"], n, b[0], b[1], b[2], b[3], side,
+                      C.c_void_p(payload.data_ptr()), h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"],
+                      view.x0, view.y0, *view.inverse, *view.prefilter, hh, w, tx, ty, view.radius_clip(h), a[0], a[1],
+                      a[2], a[3], a[4], ws, nws, status, st)
+            _lib.call("gi2d_codec_draw_rows", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws, status,
+                      *fmt.ids, C.c_void_p(out.data_ptr()), st)
+            return
         if view is None:
             _lib.call("gi2d_codec_decode_bin", h["kind"], n, b[0], b[1], b[2], b[3], side, C.c_void_p(payload.data_ptr()),
                       h["fixed_payload_bytes"], h["clip_coe"], hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3],
@@ -1172,7 +1457,8 @@ class Decoder:
 
     def _launch_overview(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, fmt: _Format,
                          aux=None, capacity: Optional[int] = None) -> None:
-        """An overview of a coding-0 payload on the current stream: gi2d_codec_decode_overview (record -> transformed,
+        """An overview -- or an affine view on its capacity-free route, with gi2d_codec_decode_affine as the first of the
+        three -- of a coding-0 payload on the current stream: gi2d_codec_decode_overview (record -> transformed,
         prefiltered gaussian -> covariance projection), gi2d_bin_gaussians into lists of `capacity` entries (its status
         {count, overflow} goes to words 0 and 1 of the row at `status`), gi2d_rasterize_forward_long_as (whole lists,
         ones if the count is 0, ending in the clamp and the format's stores); no host sync and no allocation
@@ -1188,9 +1474,15 @@ class Decoder:
                (aux if aux is not None else [o[k] for k in ("xys", "radii", "conics", "num_tiles_hit", "colors")])]
         ids, bins = C.c_void_p(o["ids"].data_ptr()), C.c_void_p(o["bins"].data_ptr())
         assert o["ids"].numel() >= cap and o["bins"].numel() >= 2 * tx * ty
-        _lib.call("gi2d_codec_decode_overview", h["kind"], n, b[0], b[1], b[2], b[3], side, C.c_void_p(payload.data_ptr()),
-                  h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"], ov.x0, ov.y0, ov.scale, ov.prefilter,
-                  hh, w, tx, ty, h["radius_clip"], geo[0], geo[1], geo[2], geo[3], geo[4], st)
+        if isinstance(ov, Affine):
+            _lib.call("gi2d_codec_decode_affine", h["kind"], n, b[0], b[1], b[2], b[3], side, C.c_void_p(payload.data_ptr()),
+                      h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"], ov.x0, ov.y0, *ov.inverse,
+                      *ov.prefilter, hh, w, tx, ty, ov.radius_clip(h), geo[0], geo[1], geo[2], geo[3], geo[4], st)
+        else:
+            _lib.call("gi2d_codec_decode_overview", h["kind"], n, b[0], b[1], b[2], b[3], side,
+                      C.c_void_p(payload.data_ptr()), h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"], ov.x0,
+                      ov.y0, ov.scale, ov.prefilter, hh, w, tx, ty, h["radius_clip"], geo[0], geo[1], geo[2], geo[3], geo[4],
+                      st)
         _lib.call("gi2d_bin_gaussians", n, cap, geo[0], geo[1], tx, ty, ov.radius_clip(h), ids, bins, status,
                   C.c_void_p(o["binws"].data_ptr()), o["binws"].numel(), st)
         _lib.call("gi2d_rasterize_forward_long_as", n, cap, tx, ty, w, hh, ids, bins, tx * ty, geo[0], geo[2], geo[4],
@@ -1270,19 +1562,42 @@ class Decoder:
         status = self._status[:len(pictures), 0:5].tolist()  # M, overflow, .., .., rANS
         for row in coded:
             self._check_expanded(status[row][4])
-        redrawn = []
+        redrawn, overflowed, lists_types = [], [], self._lists_types
         for row, (m, overflow, _, _, _) in enumerate(status):
             pic = pictures[row]
-            if isinstance(pic.view, Overview):
+            if isinstance(pic.view, lists_types):
                 self._overview_m = max(self._overview_m, m)
                 if overflow:  # the lists were cut at the capacity: the same picture again with room for all m
-                    self._reserve_overview([pic], m)
+                    overflowed.append(row)
+                    self._reserve_overview([pic], m, every=True)
                     self._launch_overview(pic, fixed[row], row0 + _STATUS_ROW * row, images[row], fmt, aux, m)
                     redrawn.append(row)
-            elif overflow and not geometry:
-                self._exact(pic, fixed[row], images[row], fmt)
-                redrawn.append(row)
+            elif overflow:
+                overflowed.append(row)
+                if isinstance(pic.view, Affine):  # a tile row lost candidates: whole lists give the same sums
+                    if self.affine_route == "rows":
+                        raise RuntimeError("affine_route = 'rows': a tile row of the affine view overflowed (more than 1024 "
+                                           "candidates in one tile); the default route draws such a picture again")
+                    self._affine_lists(pic, fixed[row], row0 + _STATUS_ROW * row, row, images[row], fmt, aux)
+                    redrawn.append(row)
+                elif not geometry:
+                    self._exact(pic, fixed[row], images[row], fmt)
+                    redrawn.append(row)
+        self.overflowed, self.redrawn = overflowed, redrawn
         return redrawn
+
+    def _affine_lists(self, pic: _Picture, fixed: torch.Tensor, status: int, row: int, out: torch.Tensor, fmt: _Format,
+                      aux=None) -> None:
+        """An affine view whose fast-path draw overflowed, through the capacity-free route (_launch_overview): its lists
+        start at the capacity an overview's would, and a picture that needs more is drawn once more with room for the
+        count its status row then reports -- a host wait per attempt: this is the rare path."""
+        self._reserve_overview([pic], every=True)
+        self._launch_overview(pic, fixed, status, out, fmt, aux)
+        m, overflow = self._status[row, 0:2].tolist()
+        self._overview_m = max(self._overview_m, m)
+        if overflow:
+            self._reserve_overview([pic], m, every=True)
+            self._launch_overview(pic, fixed, status, out, fmt, aux, m)
 
     def _run(self, streams, views, fmt: _Format, outs: Optional[Sequence[torch.Tensor]] = None, views_only: bool = False,
              geometry: bool = False):
@@ -1309,12 +1624,13 @@ class Decoder:
 
     # ---------------------------------------------------------------------------------------------- batches
     def _batch_groups(self, pictures: Sequence[_Picture]):
-        """The rows gi2d_codec_decode_batch draws together: runs of consecutive pictures that are no overviews (a call
-        writes its pictures one behind the other), at most BATCH_MAX each -> [(rows, [workspace bytes of each])]."""
+        """The rows gi2d_codec_decode_batch draws together: runs of consecutive pictures that have no launches of their own
+        (_lists_types: overviews; a call writes its pictures one behind the other), at most BATCH_MAX each -> [(rows,
+        [workspace bytes of each])].  Affine pictures share the launches."""
         size = _lib.load().gi2d_codec_decode_workspace_bytes
-        groups = []
+        groups, lists_types = [], self._lists_types
         for row, p in enumerate(pictures):
-            if isinstance(p.view, Overview):
+            if isinstance(p.view, lists_types):
                 continue
             if not groups or groups[-1][0][-1] != row - 1 or len(groups[-1][0]) == BATCH_MAX:
                 groups.append(([], []))
@@ -1326,6 +1642,7 @@ class Decoder:
         """gi2d_codec_decode_batch for pictures `rows` (consecutive) of a call: table writers, workspace reset, decode/bin
         and draw, each once for all of them; no host sync and no allocation."""
         arr = (_CPicture * len(rows))()
+        maps = None  # struct gi2d_codec_affine per picture, made when the first Affine is met
         ws = self._batch_ws.data_ptr()
         for d, row, nws in zip(arr, rows, sizes):
             h, view, _, _, _, _ = pictures[row]
@@ -1335,14 +1652,21 @@ class Decoder:
             d.payload, d.payload_bytes = fixed[row].data_ptr(), h["fixed_payload_bytes"]
             d.clip_coe, d.img_height, d.img_width = h["clip_coe"], h["height"], h["width"]
             if view is not None:
-                d.view, d.x0, d.y0, d.scale = 1, view.x0, view.y0, view.scale
+                if view.__class__ is View:
+                    d.view, d.x0, d.y0, d.scale = 1, view.x0, view.y0, view.scale
+                else:
+                    maps = (_CAffine * len(rows))() if maps is None else maps
+                    a = maps[row - rows[0]]
+                    d.view, a.x0, a.y0 = 2, view.x0, view.y0
+                    a.b, a.prefilter = (C.c_float * 4)(*view.inverse), (C.c_float * 3)(*view.prefilter)
             d.radius_clip = pictures[row].radius_clip
             d.workspace, d.workspace_bytes, d.status = ws, nws, row0 + _STATUS_ROW * row
             ws += nws
         p = pictures[rows[0]]
-        _lib.call("gi2d_codec_decode_batch", len(rows), arr, C.c_void_p(self._batch_table.data_ptr()),
-                  self._batch_table.numel(), p.height, p.width, p.tx, p.ty, C.c_void_p(self._background.data_ptr()),
-                  *fmt.ids, C.c_void_p(out[rows[0]].data_ptr()), _stream(self.dev))
+        entry = ("gi2d_codec_decode_batch", len(rows), arr) if maps is None else ("gi2d_codec_decode_batch_affine", len(rows),
+                                                                                     arr, maps)
+        _lib.call(*entry, C.c_void_p(self._batch_table.data_ptr()), self._batch_table.numel(), p.height, p.width, p.tx, p.ty,
+                  C.c_void_p(self._background.data_ptr()), *fmt.ids, C.c_void_p(out[rows[0]].data_ptr()), _stream(self.dev))
 
     def decode_batch(self, streams, views=None, out: Optional[torch.Tensor] = None, dtype=None, layout=None) -> torch.Tensor:
         """K streams (bytes or uploaded DeviceStreams, any coding) -> ONE tensor [K, *format shape]: picture k is, bit for
@@ -1373,8 +1697,9 @@ class Decoder:
             if out is None:
                 out = torch.empty(shape, dtype=fmt.dtype, device=self.dev)
             fixed, coded, row0 = self._begin(streams, headers, pictures, [1] * len(pictures))
+            lists_types = self._lists_types
             for row, pic in enumerate(pictures):
-                if isinstance(pic.view, Overview):
+                if isinstance(pic.view, lists_types):
                     self._launch_overview(pic, fixed[row], row0 + _STATUS_ROW * row, out[row], fmt)
             for rows, sizes in groups:
                 self._launch_batch(rows, sizes, pictures, fixed, row0, out, fmt)

@@ -12,6 +12,9 @@
 //               projection every gaussian is moved and scaled into the window's pixel grid (view_transform), and the
 //               projection, the binning step and the tile pass run at the WINDOW's size.  A template flag of the
 //               same kernel: the full decode's instantiations keep their instructions.
+//   affine      the same launch again with an affine view (DESIGN.md 3.8 "Affine views"): affine_transform in place of
+//               view_transform, the covariance projection for either kind; gi2d_codec_draw_rows draws it.  And the
+//               per-gaussian kernel without a workspace, for the capacity-free route (gi2d_codec_decode_affine).
 //
 // Nothing here is read through a pointer computed from stream CONTENT: record positions follow from (N, R) alone, and
 // every load index is clamped to the dwords the entry has checked the payload to hold.
@@ -63,22 +66,44 @@ __global__ __launch_bounds__(GI2D_CODEC_PACK_BLOCK) void codec_pack_kernel(
 // (CodecOut, CodecView, view_transform and the per-gaussian body: gi2d_codec_core.h, shared with the batched decode)
 // img_w / img_h / tiles / radius_clip: those of the picture that is drawn (for a view: the window's size and the
 // header's radius_clip * scale, so that what the full decode drops as too small stays dropped).  VIEW = false never reads
-// `vw`: the full decode's instantiations have the instructions they had before there were views.
-template <int KIND, bool VIEW>
+// `vw`: the full decode's instantiations have the instructions they had before there were views.  FORM: GI2D_CODEC_FORM_*.
+template <int KIND, int FORM>
 __global__ __launch_bounds__(256) void codec_decode_bin_kernel(
     int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
-    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, CodecOut out, BinTarget bt, CodecView vw) {
-    codec_decode_bin_one<KIND, VIEW>(blockIdx.x * blockDim.x + threadIdx.x, n, lay, side, payload, last_dword, clip_coe, img_w,
-                                     img_h, tiles_x, tiles_y, radius_clip, out, bt, vw);
+    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, CodecOut out, BinTarget bt, CodecView vw,
+    CodecAffine af) {
+    codec_decode_bin_one<KIND, FORM>(blockIdx.x * blockDim.x + threadIdx.x, n, lay, side, payload, last_dword, clip_coe, img_w,
+                                     img_h, tiles_x, tiles_y, radius_clip, out, bt, vw, af);
+}
+
+// The affine view's per-gaussian kernel of the capacity-free route: what codec_decode_bin_one<KIND, AFFINE> computes of a
+// gaussian, written to the five arrays gi2d_bin_gaussians and gi2d_rasterize_forward_long_as consume; no workspace.
+template <int KIND>
+__global__ __launch_bounds__(256) void codec_decode_affine_kernel(
+    int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
+    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, CodecOut out, CodecAffine af) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    float v[GI2D_CODEC_FIELDS];
+    codec_values<KIND>(g, lay, side, payload, last_dword, v);
+    affine_transform<KIND>(v, af);
+    const ProjOut o = project_values<kCovariance>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h,
+                                                  tiles_x, tiles_y, radius_clip);
+    out.xys[g] = o.xy;
+    out.radii[g] = o.radius;
+    out.conics[3 * g] = o.k0, out.conics[3 * g + 1] = o.k1, out.conics[3 * g + 2] = o.k2;
+    out.num_tiles_hit[g] = o.tiles_hit;
+    out.colors[3 * g] = v[5], out.colors[3 * g + 1] = v[6], out.colors[3 * g + 2] = v[7];
 }
 
 }  // namespace gi2d
 
 using namespace gi2d;
 
-// Checks and launch shared by the two decode entries.  h, w_, tiles, radius_clip: those of the picture that is drawn;
-// view: the window of gi2d_codec_decode_bin_view (already checked), NULL for the full decode.
-static int codec_decode_launch(const char *what, const CodecView *view, int kind, int n, int xy_bits, int p0_bits,
+// Checks and launch shared by the three decode entries.  h, w_, tiles, radius_clip: those of the picture that is drawn;
+// view: the window of gi2d_codec_decode_bin_view (already checked), affine: the map of gi2d_codec_decode_bin_affine
+// (already checked); both NULL for the full decode.
+static int codec_decode_launch(const char *what, const CodecView *view, const CodecAffine *affine, int kind, int n, int xy_bits, int p0_bits,
                                int p1_bits, int color_bits, const float *side_host, const void *payload,
                                size_t payload_bytes, float clip_coe, unsigned h, unsigned w_, int tiles_x, int tiles_y,
                                float radius_clip, float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit,
@@ -116,16 +141,20 @@ static int codec_decode_launch(const char *what, const CodecView *view, int kind
     const dim3 grid((n + bs - 1) / bs > 0 ? (n + bs - 1) / bs : 1), block(bs);
     const long long last = need > 0 ? need - 1 : 0;
     const CodecView vw = view ? *view : CodecView{0.f, 0.f, 1.f};
-#define GI2D_CODEC_DECODE(KIND, VIEW)                                                                                  \
-    hipLaunchKernelGGL((codec_decode_bin_kernel<KIND, VIEW>), grid, block, 0, (hipStream_t)st, n, lay, side,            \
+    const CodecAffine af = affine ? *affine : CodecAffine{0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+#define GI2D_CODEC_DECODE(KIND, FORM)                                                                                  \
+    hipLaunchKernelGGL((codec_decode_bin_kernel<KIND, FORM>), grid, block, 0, (hipStream_t)st, n, lay, side,            \
                        (const uint32_t *)payload, last, clip_coe, (float)w_, (float)h, tiles_x, tiles_y, radius_clip,  \
-                       out, bt, vw)
-    if (view) {
-        if (kind == kCovariance) GI2D_CODEC_DECODE(kCovariance, true);
-        else GI2D_CODEC_DECODE(kScaleRot, true);
+                       out, bt, vw, af)
+    if (affine) {
+        if (kind == kCovariance) GI2D_CODEC_DECODE(kCovariance, GI2D_CODEC_FORM_AFFINE);
+        else GI2D_CODEC_DECODE(kScaleRot, GI2D_CODEC_FORM_AFFINE);
+    } else if (view) {
+        if (kind == kCovariance) GI2D_CODEC_DECODE(kCovariance, GI2D_CODEC_FORM_VIEW);
+        else GI2D_CODEC_DECODE(kScaleRot, GI2D_CODEC_FORM_VIEW);
     } else {
-        if (kind == kCovariance) GI2D_CODEC_DECODE(kCovariance, false);
-        else GI2D_CODEC_DECODE(kScaleRot, false);
+        if (kind == kCovariance) GI2D_CODEC_DECODE(kCovariance, GI2D_CODEC_FORM_FULL);
+        else GI2D_CODEC_DECODE(kScaleRot, GI2D_CODEC_FORM_FULL);
     }
 #undef GI2D_CODEC_DECODE
     return check_launch(what);
@@ -173,7 +202,7 @@ int gi2d_codec_decode_bin(int kind, int n, int xy_bits, int p0_bits, int p1_bits
                           unsigned h, unsigned w_, int tiles_x, int tiles_y, float radius_clip, float *xys,
                           int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors, void *ws,
                           size_t ws_bytes, int32_t *status, gi2d_stream_t st) {
-    return codec_decode_launch("codec decode", nullptr, kind, n, xy_bits, p0_bits, p1_bits, color_bits, side_host,
+    return codec_decode_launch("codec decode", nullptr, nullptr, kind, n, xy_bits, p0_bits, p1_bits, color_bits, side_host,
                                payload, payload_bytes, clip_coe, h, w_, tiles_x, tiles_y, radius_clip, xys, radii,
                                conics, num_tiles_hit, colors, ws, ws_bytes, status, st);
 }
@@ -189,9 +218,68 @@ int gi2d_codec_decode_bin_view(int kind, int n, int xy_bits, int p0_bits, int p1
         return GI2D_ERR_INVALID_ARGUMENT;
     }
     const CodecView vw{x0, y0, scale};
-    return codec_decode_launch("codec decode view", &vw, kind, n, xy_bits, p0_bits, p1_bits, color_bits, side_host,
+    return codec_decode_launch("codec decode view", &vw, nullptr, kind, n, xy_bits, p0_bits, p1_bits, color_bits, side_host,
                                payload, payload_bytes, clip_coe, out_h, out_w, tiles_x, tiles_y, radius_clip * scale, xys,
                                radii, conics, num_tiles_hit, colors, ws, ws_bytes, status, st);
+}
+
+int gi2d_codec_decode_bin_affine(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                                 const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
+                                 unsigned h, unsigned w_, float x0, float y0, float b00, float b01, float b10, float b11,
+                                 float pxx, float pxy, float pyy, unsigned out_h, unsigned out_w, int tiles_x, int tiles_y,
+                                 float radius_clip, float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit,
+                                 float *colors, void *ws, size_t ws_bytes, int32_t *status, gi2d_stream_t st) {
+    const CodecAffine af{x0, y0, b00, b01, b10, b11, pxx, pxy, pyy};
+    if (const char *why = codec_affine_refused(af, out_h, out_w, h, w_)) {
+        set_error((std::string("codec decode affine: ") + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    if (!std::isfinite(radius_clip)) {
+        set_error("codec decode affine: radius_clip must be finite");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    return codec_decode_launch("codec decode affine", nullptr, &af, kind, n, xy_bits, p0_bits, p1_bits, color_bits,
+                               side_host, payload, payload_bytes, clip_coe, out_h, out_w, tiles_x, tiles_y, radius_clip, xys,
+                               radii, conics, num_tiles_hit, colors, ws, ws_bytes, status, st);
+}
+
+int gi2d_codec_decode_affine(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                             const float *side_host, const void *payload, size_t payload_bytes, float clip_coe, unsigned h,
+                             unsigned w_, float x0, float y0, float b00, float b01, float b10, float b11, float pxx,
+                             float pxy, float pyy, unsigned out_h, unsigned out_w, int tiles_x, int tiles_y,
+                             float radius_clip, float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit,
+                             float *colors, gi2d_stream_t st) {
+    const char *what = "codec decode affine (lists)";
+    const auto fail = [&](const char *why) {
+        set_error((std::string(what) + ": " + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    };
+    const CodecAffine af{x0, y0, b00, b01, b10, b11, pxx, pxy, pyy};
+    if (const char *why = codec_affine_refused(af, out_h, out_w, h, w_)) return fail(why);
+    if (!std::isfinite(radius_clip)) return fail("radius_clip must be finite");
+    CodecLayout lay;
+    if (!codec_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 0 || tiles_x < 0 || tiles_y < 0) return fail("negative size");
+    const long long need = codec_dwords(n, lay.record_bits);
+    if (payload_bytes < (size_t)need * 4) return fail("payload shorter than 4 * ceil(N * R / 32) bytes");
+    if (!side_host || (n > 0 && (!payload || ((uintptr_t)payload & 3) || !xys || !radii || !conics || !num_tiles_hit || !colors)))
+        return fail("null or misaligned pointer");
+    if ((long long)tiles_x * GI2D_TILE < (long long)out_w || (long long)tiles_y * GI2D_TILE < (long long)out_h)
+        return fail("tile grid does not cover the image");
+    if (n == 0) return GI2D_OK;
+    CodecSide side;
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) side.scale[k] = side_host[2 * k], side.beta[k] = side_host[2 * k + 1];
+    const CodecOut out{(float2 *)xys, radii, conics, num_tiles_hit, colors};
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (kind == kCovariance)
+        hipLaunchKernelGGL(codec_decode_affine_kernel<kCovariance>, grid, block, 0, (hipStream_t)st, n, lay, side,
+                           (const uint32_t *)payload, need - 1, clip_coe, (float)out_w, (float)out_h, tiles_x, tiles_y,
+                           radius_clip, out, af);
+    else
+        hipLaunchKernelGGL(codec_decode_affine_kernel<kScaleRot>, grid, block, 0, (hipStream_t)st, n, lay, side,
+                           (const uint32_t *)payload, need - 1, clip_coe, (float)out_w, (float)out_h, tiles_x, tiles_y,
+                           radius_clip, out, af);
+    return check_launch(what);
 }
 
 }  // extern "C"

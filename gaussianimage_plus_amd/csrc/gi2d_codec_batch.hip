@@ -9,6 +9,10 @@
 //   decode    gi2d_codec_core.h::codec_decode_bin_one, 256 gaussians per workgroup; kind and view are per picture: a
 //             workgroup-uniform switch over the four instantiations the single-picture launch chooses from on the host
 //   draw      gi2d_codec_core.h::codec_draw_tile on the picture's own lists, records, status row and slice of `out`
+//   affine    a call with an affine picture among its K (gi2d_codec_decode_batch_affine) launches the second form of the
+//             two kernels: the decode switch has the two affine instantiations as well, and the draw picks per picture
+//             between codec_draw_tile and codec_draw_tile_rows (one LDS block serves either).  The maps travel in a table
+//             of their own behind the argument blocks, so a call without one runs exactly the launches it ran before.
 //
 // A workgroup finds its picture with batch_find and touches that picture's workspace and status row only, so every
 // access rule of gi2d_fast_internal.h holds per workspace exactly as in the single-picture launches, and nothing is
@@ -26,7 +30,7 @@ struct CodecBatchPicture {
     CodecSide side;
     const uint32_t *payload;
     long long last_dword;
-    int n, form;  // form: (kind == scale-rot) * 2 + view
+    int n, form;  // form: (kind == scale-rot) * 2 + view; affine: 4 + (kind == scale-rot), its map in the affine table
     float clip_coe, radius_clip;
     CodecView vw;
     BinTarget bt;  // prev_box, lists, record sets and the status row (colour comes from the record, opacity is 1)
@@ -40,13 +44,16 @@ struct CodecBatchHead {
 struct CodecBatchTable {
     CodecBatchHead *head;
     CodecBatchPicture *pic;
+    CodecAffine *affine;  // [k]: entry i is read by the workgroups of picture i when its form is an affine one
     size_t bytes;
 };
 static inline CodecBatchTable carve_codec_batch(void *base, int k) {
     CodecBatchTable b;
+    const size_t kk = (size_t)(k > 0 ? k : 1);
     b.head = (CodecBatchHead *)base;
     b.pic = (CodecBatchPicture *)((char *)base + align_up(sizeof(CodecBatchHead)));
-    b.bytes = align_up(sizeof(CodecBatchHead)) + align_up((size_t)(k > 0 ? k : 1) * sizeof(CodecBatchPicture));
+    b.affine = (CodecAffine *)((char *)b.pic + align_up(kk * sizeof(CodecBatchPicture)));
+    b.bytes = align_up(sizeof(CodecBatchHead)) + align_up(kk * sizeof(CodecBatchPicture)) + align_up(kk * sizeof(CodecAffine));
     return b;
 }
 
@@ -54,7 +61,11 @@ static inline CodecBatchTable carve_codec_batch(void *base, int k) {
 struct CodecBatchPack {
     CodecBatchPicture pic[GI2D_CODEC_BATCH_PACK];
 };
-static_assert(sizeof(CodecBatchPack) <= 3840 && sizeof(CodecBatchHead) <= 3840, "a writer's block must fit the kernel-argument segment");
+struct CodecBatchAffines {
+    CodecAffine af[GI2D_BATCH_MAX];
+};
+static_assert(sizeof(CodecBatchPack) <= 3840 && sizeof(CodecBatchHead) <= 3840 && sizeof(CodecBatchAffines) <= 3840,
+              "a writer's block must fit the kernel-argument segment");
 template <class T>
 __global__ __launch_bounds__(256) void codec_batch_write_kernel(T v, int words, int *__restrict__ dst) {
     static_assert(sizeof(T) % sizeof(int) == 0, "copied word by word");
@@ -89,12 +100,34 @@ __global__ __launch_bounds__(256) void codec_decode_bin_batched_kernel(const Cod
     const CodecOut none{nullptr, nullptr, nullptr, nullptr, nullptr};
 #define GI2D_DECODE_ONE(KIND, VIEW)                                                                                     \
     codec_decode_bin_one<KIND, VIEW>(g, p.n, p.lay, p.side, p.payload, p.last_dword, p.clip_coe, img_w, img_h, tiles_x, \
-                                     tiles_y, p.radius_clip, none, p.bt, p.vw)
+                                     tiles_y, p.radius_clip, none, p.bt, p.vw, af)
+    const CodecAffine af{};
     switch (p.form) {  // workgroup-uniform
-        case 0: GI2D_DECODE_ONE(kCovariance, false); break;
-        case 1: GI2D_DECODE_ONE(kCovariance, true); break;
-        case 2: GI2D_DECODE_ONE(kScaleRot, false); break;
-        default: GI2D_DECODE_ONE(kScaleRot, true); break;
+        case 0: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_FULL); break;
+        case 1: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_VIEW); break;
+        case 2: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_FULL); break;
+        default: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_VIEW); break;
+    }
+}
+
+// ... of a call with affine pictures: two more forms
+__global__ __launch_bounds__(256) void codec_decode_bin_batched_affine_kernel(const CodecBatchHead *__restrict__ head,
+                                                                              const CodecBatchPicture *__restrict__ pics,
+                                                                              const CodecAffine *__restrict__ affines,
+                                                                              int k_pictures, float img_w, float img_h,
+                                                                              int tiles_x, int tiles_y) {
+    const int k = batch_find(head->pg_start, k_pictures, (int)blockIdx.x);
+    const CodecBatchPicture &p = pics[k];
+    const int g = ((int)blockIdx.x - head->pg_start[k]) * 256 + (int)threadIdx.x;
+    const CodecOut none{nullptr, nullptr, nullptr, nullptr, nullptr};
+    const CodecAffine af = affines[k];
+    switch (p.form) {  // workgroup-uniform
+        case 0: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_FULL); break;
+        case 1: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_VIEW); break;
+        case 2: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_FULL); break;
+        case 3: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_VIEW); break;
+        case 4: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_AFFINE); break;
+        default: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_AFFINE); break;
     }
 #undef GI2D_DECODE_ONE
 }
@@ -111,6 +144,26 @@ __global__ __launch_bounds__(256) void codec_draw_batched_kernel(const CodecBatc
     const int tile = (int)blockIdx.x - head->tile_start[k];
     codec_draw_tile<DTYPE, LAYOUT>(sm, grp, tile, tile == 0, tiles_x, tiles_y, img_w, img_h, p.bt.recs, background,
                                    p.bt.lists, p.tile_bins, nullptr, nullptr, p.bt.status, p.out);
+}
+
+// ... of a call with affine pictures: the draw routine is the picture's (workgroup-uniform); one LDS block serves either
+template <int DTYPE, int LAYOUT>
+__global__ __launch_bounds__(256) void codec_draw_batched_affine_kernel(const CodecBatchHead *__restrict__ head,
+                                                                        const CodecBatchPicture *__restrict__ pics,
+                                                                        int k_pictures, int tiles_x, int tiles_y, int img_w,
+                                                                        int img_h, const float *__restrict__ background) {
+    constexpr size_t LDS = sizeof(FwdLds) > sizeof(RowsLds) ? sizeof(FwdLds) : sizeof(RowsLds);
+    __shared__ __align__(16) unsigned char lds[LDS];
+    __shared__ int grp[32];
+    const int k = batch_find(head->tile_start, k_pictures, (int)blockIdx.x);
+    const CodecBatchPicture &p = pics[k];
+    const int tile = (int)blockIdx.x - head->tile_start[k];
+    if (p.form >= 4)
+        codec_draw_tile_rows<DTYPE, LAYOUT>(*reinterpret_cast<RowsLds *>(lds), grp, tile, tile == 0, tiles_x, tiles_y, img_w,
+                                            img_h, p.bt.recs, background, p.bt.lists, p.tile_bins, p.bt.status, p.out);
+    else
+        codec_draw_tile<DTYPE, LAYOUT>(*reinterpret_cast<FwdLds *>(lds), grp, tile, tile == 0, tiles_x, tiles_y, img_w, img_h,
+                                       p.bt.recs, background, p.bt.lists, p.tile_bins, nullptr, nullptr, p.bt.status, p.out);
 }
 
 static inline size_t pixel_plane_bytes(int dtype, int layout, size_t h, size_t w_) {
@@ -134,6 +187,14 @@ size_t gi2d_codec_decode_workspace_bytes(int n, int tiles_x, int tiles_y) {
 int gi2d_codec_decode_batch(int num_pictures, const gi2d_codec_picture *pictures, void *batch, size_t batch_bytes,
                             unsigned out_h, unsigned out_w, int tiles_x, int tiles_y, const float *background, int dtype,
                             int layout, void *out, gi2d_stream_t st) {
+    return gi2d_codec_decode_batch_affine(num_pictures, pictures, nullptr, batch, batch_bytes, out_h, out_w, tiles_x, tiles_y,
+                                          background, dtype, layout, out, st);
+}
+
+int gi2d_codec_decode_batch_affine(int num_pictures, const gi2d_codec_picture *pictures, const gi2d_codec_affine *affines,
+                                   void *batch, size_t batch_bytes, unsigned out_h, unsigned out_w, int tiles_x,
+                                   int tiles_y, const float *background, int dtype, int layout, void *out,
+                                   gi2d_stream_t st) {
     const auto fail = [&](const std::string &why) {
         set_error(("codec decode batch: " + why).c_str());
         return GI2D_ERR_INVALID_ARGUMENT;
@@ -154,6 +215,8 @@ int gi2d_codec_decode_batch(int num_pictures, const gi2d_codec_picture *pictures
     const int tiles = tiles_x * tiles_y;
     const size_t plane = pixel_plane_bytes(dtype, layout, out_h, out_w);
     std::vector<CodecBatchPicture> pics((size_t)num_pictures);
+    CodecBatchAffines maps = {};
+    bool any_affine = false;
     CodecBatchHead head = {};
     int max_n = 0;
     long long pg_total = 0;
@@ -170,7 +233,15 @@ int gi2d_codec_decode_batch(int num_pictures, const gi2d_codec_picture *pictures
         if (d.payload_bytes < (size_t)need * 4) return fail(who + ": payload shorter than 4 * ceil(N * R / 32) bytes");
         if (!d.status || !d.workspace || (n > 0 && (!d.payload || ((uintptr_t)d.payload & 3))))
             return fail(who + ": null or misaligned pointer");
-        if (d.view) {
+        if (d.view == 2) {
+            if (!affines) return fail(who + ": an affine view (view = 2) needs gi2d_codec_decode_batch_affine and its maps");
+            const gi2d_codec_affine &a = affines[k];
+            maps.af[k] = CodecAffine{a.x0, a.y0, a.b[0], a.b[1], a.b[2], a.b[3], a.prefilter[0], a.prefilter[1], a.prefilter[2]};
+            if (const char *why = codec_affine_refused(maps.af[k], out_h, out_w, d.img_height, d.img_width))
+                return fail(who + ": affine view: " + why);
+            if (!std::isfinite(d.radius_clip)) return fail(who + ": affine view: radius_clip must be finite");
+            any_affine = true;
+        } else if (d.view) {
             if (const char *why = codec_view_refused(d.x0, d.y0, d.scale, out_h, out_w, d.img_height, d.img_width))
                 return fail(who + ": view: " + why);
         } else if (d.img_height != out_h || d.img_width != out_w) {
@@ -188,10 +259,10 @@ int gi2d_codec_decode_batch(int num_pictures, const gi2d_codec_picture *pictures
         p.payload = (const uint32_t *)d.payload;
         p.last_dword = need > 0 ? need - 1 : 0;
         p.n = n;
-        p.form = (d.kind == kScaleRot ? 2 : 0) + (d.view ? 1 : 0);
+        p.form = d.view == 2 ? 4 + (d.kind == kScaleRot ? 1 : 0) : (d.kind == kScaleRot ? 2 : 0) + (d.view ? 1 : 0);
         p.clip_coe = d.clip_coe;
         p.radius_clip = d.radius_clip;
-        p.vw = d.view ? CodecView{d.x0, d.y0, d.scale} : CodecView{0.f, 0.f, 1.f};
+        p.vw = d.view == 1 ? CodecView{d.x0, d.y0, d.scale} : CodecView{0.f, 0.f, 1.f};
         p.bt.colors = p.bt.opacities = nullptr;
         p.bt.prev_box = w.prev_box;
         p.bt.lists = w.lists;
@@ -218,19 +289,36 @@ int gi2d_codec_decode_batch(int num_pictures, const gi2d_codec_picture *pictures
     }
     hipLaunchKernelGGL(codec_batch_write_kernel<CodecBatchHead>, dim3(1), dim3(256), 0, s, head,
                        (int)(sizeof(CodecBatchHead) / sizeof(int)), (int *)table.head);
+    if (any_affine)
+        hipLaunchKernelGGL(codec_batch_write_kernel<CodecBatchAffines>, dim3(1), dim3(256), 0, s, maps,
+                           num_pictures * (int)(sizeof(CodecAffine) / sizeof(int)), (int *)table.affine);
     // ---- the three launches
     const int work = tiles > max_n ? tiles : max_n;
     const int reset_blocks = (work + 255) / 256;
     hipLaunchKernelGGL(codec_reset_batched_kernel, dim3((unsigned)(reset_blocks * num_pictures)), dim3(256), 0, s,
                        (const CodecBatchPicture *)table.pic, reset_blocks, tiles);
-    hipLaunchKernelGGL(codec_decode_bin_batched_kernel, dim3((unsigned)pg_total), dim3(256), 0, s,
-                       (const CodecBatchHead *)table.head, (const CodecBatchPicture *)table.pic, num_pictures, (float)out_w,
-                       (float)out_h, tiles_x, tiles_y);
+    if (any_affine)
+        hipLaunchKernelGGL(codec_decode_bin_batched_affine_kernel, dim3((unsigned)pg_total), dim3(256), 0, s,
+                           (const CodecBatchHead *)table.head, (const CodecBatchPicture *)table.pic,
+                           (const CodecAffine *)table.affine, num_pictures, (float)out_w, (float)out_h, tiles_x, tiles_y);
+    else
+        hipLaunchKernelGGL(codec_decode_bin_batched_kernel, dim3((unsigned)pg_total), dim3(256), 0, s,
+                           (const CodecBatchHead *)table.head, (const CodecBatchPicture *)table.pic, num_pictures,
+                           (float)out_w, (float)out_h, tiles_x, tiles_y);
 #define GI2D_DRAW_BATCH(D, L)                                                                                            \
     hipLaunchKernelGGL((codec_draw_batched_kernel<D, L>), dim3((unsigned)(num_pictures * tiles)), dim3(256), 0, s,        \
                        (const CodecBatchHead *)table.head, (const CodecBatchPicture *)table.pic, num_pictures, tiles_x,   \
                        tiles_y, (int)out_w, (int)out_h, background)
-    GI2D_FOR_FORMAT(dtype, layout, GI2D_DRAW_BATCH)
+#define GI2D_DRAW_BATCH_AFFINE(D, L)                                                                                      \
+    hipLaunchKernelGGL((codec_draw_batched_affine_kernel<D, L>), dim3((unsigned)(num_pictures * tiles)), dim3(256), 0, s, \
+                       (const CodecBatchHead *)table.head, (const CodecBatchPicture *)table.pic, num_pictures, tiles_x,   \
+                       tiles_y, (int)out_w, (int)out_h, background)
+    if (any_affine) {
+        GI2D_FOR_FORMAT(dtype, layout, GI2D_DRAW_BATCH_AFFINE)
+    } else {
+        GI2D_FOR_FORMAT(dtype, layout, GI2D_DRAW_BATCH)
+    }
+#undef GI2D_DRAW_BATCH_AFFINE
 #undef GI2D_DRAW_BATCH
     return check_launch("codec decode batch");
 }

@@ -7,6 +7,7 @@
 
 #include "gi2d_codec_layout.h"
 #include "gi2d_fast_internal.h"
+#include "gi2d_long_core.h"
 #include "gi2d_pixel_format.h"
 #include "gi2d_quant_core.h"
 
@@ -59,22 +60,132 @@ static inline const char *codec_view_refused(float x0, float y0, float scale, un
     return nullptr;
 }
 
+// An AFFINE view (DESIGN.md 3.8 "Affine views"): output pixel (row i, column j) samples the fitted function, low-passed,
+// at source position (x0, y0) + M (j, i).  The kernel gets B = M^-1 and the low-pass's variance P (output pixels^2), and
+// carries the map out on the gaussians -- a gaussian under an affine map is a gaussian -- in separate fp32 operations
+// (codec.affine_parameters restates them): centre B (c - origin), covariance B S B^T + P for EITHER model kind, colour
+// times sqrt(det(B S B^T) / det(B S B^T + P)) so that the mass stays.  The result is a covariance-model gaussian.
+struct CodecAffine {
+    float x0, y0;
+    float b00, b01, b10, b11;
+    float pxx, pxy, pyy;
+};
+template <int KIND>
+__device__ __forceinline__ void affine_transform(float (&v)[GI2D_CODEC_FIELDS], const CodecAffine af) {
+#pragma clang fp contract(off)
+    const float dx = v[0] - af.x0, dy = v[1] - af.y0;
+    v[0] = af.b00 * dx + af.b01 * dy;
+    v[1] = af.b10 * dx + af.b11 * dy;
+    float a, b, c;
+    if (KIND == kCovariance) {
+        a = v[2], b = v[3], c = v[4];
+    } else {  // project_values<kScaleRot>: R = [[cos, sin], [-sin, cos]], M = R S, M M^T (overview_transform at scale 1)
+        const float cs = cosf(v[4]), sn = sinf(v[4]);
+        const M2 R{{cs, -sn, sn, cs}};
+        const M2 S{{v[2], 0.f, 0.f, v[3]}};
+        const M2 M = mul(R, S);
+        const M2 T = mul(M, tr(M));
+        a = T.v[0], b = T.v[1], c = T.v[3];
+    }
+    const float n00 = af.b00 * a + af.b01 * b, n01 = af.b00 * b + af.b01 * c;
+    const float n10 = af.b10 * a + af.b11 * b, n11 = af.b10 * b + af.b11 * c;
+    float cxx = n00 * af.b00 + n01 * af.b01, cxy = n00 * af.b10 + n01 * af.b11, cyy = n10 * af.b10 + n11 * af.b11;
+    const float det0 = cxx * cyy - cxy * cxy;
+    cxx = cxx + af.pxx;
+    cxy = cxy + af.pxy;
+    cyy = cyy + af.pyy;
+    const float det1 = cxx * cyy - cxy * cxy;
+    const float g = sqrtf(fmaxf(det0, 0.f) / det1);
+    v[2] = cxx, v[3] = cxy, v[4] = cyy;
+    v[5] = v[5] * g, v[6] = v[6] * g, v[7] = v[7] * g;
+}
+
+#define GI2D_CODEC_AFFINE_MAX_PREFILTER 4.0f
+// The conditions on an affine view, in double on the fp32 values the kernel receives: what is wrong with
+// it, or nullptr.  h, w_: the source picture's size.  The corner test needs M, which the entry does not receive: it is
+// B^-1 in double, i.e. the caller's fp32 M to within fp32 rounding, and the picture's bounds are widened by that much
+// (2^-20 of the terms' magnitudes), so that a map whose corner lies ON the last sample is not refused here.
+static inline const char *codec_affine_refused(const CodecAffine &a, unsigned out_h, unsigned out_w, unsigned h,
+                                               unsigned w_) {
+#pragma clang fp contract(off)
+    const float all[9] = {a.x0, a.y0, a.b00, a.b01, a.b10, a.b11, a.pxx, a.pxy, a.pyy};
+    for (float f : all)
+        if (!std::isfinite(f)) return "origin, inverse map and prefilter must be finite";
+    const double b00 = a.b00, b01 = a.b01, b10 = a.b10, b11 = a.b11;
+    const double t = b00 * b00 + b01 * b01 + b10 * b10 + b11 * b11, d = b00 * b11 - b01 * b10;
+    const double disc = std::sqrt(std::fmax(t * t - 4.0 * d * d, 0.0));
+    const double smax = std::sqrt((t + disc) / 2.0), smin = smax > 0.0 ? std::fabs(d) / smax : 0.0;
+    if (!(smin >= 1.0 / 64.0) || !(smax <= 64.0)) return "both singular values of the inverse map must lie in 1/64 .. 64";
+    const double pxx = a.pxx, pxy = a.pxy, pyy = a.pyy;
+    if (pxx < 0.0 || pyy < 0.0 || pxx * pyy - pxy * pxy < 0.0 || a.pxx > GI2D_CODEC_AFFINE_MAX_PREFILTER ||
+        a.pyy > GI2D_CODEC_AFFINE_MAX_PREFILTER)
+        return "the prefilter must be positive semi-definite with variances in 0 .. 4 output pixels^2";
+    if (out_w < 1 || out_h < 1) return "empty output";
+    if (((unsigned long long)out_w + GI2D_TILE - 1) / GI2D_TILE * (((unsigned long long)out_h + GI2D_TILE - 1) / GI2D_TILE) >
+        (unsigned long long)GI2D_CODEC_VIEW_MAX_TILES)
+        return "more than 16384 tiles in one view (compose larger outputs from several views)";
+    const double m00 = b11 / d, m01 = -b01 / d, m10 = -b10 / d, m11 = b00 / d;
+    const double slack = 1.0 / 1048576.0;
+    for (int corner = 0; corner < 4; ++corner) {
+        const double j = (corner & 1) ? (double)(out_w - 1) : 0.0, i = (corner & 2) ? (double)(out_h - 1) : 0.0;
+        const double sx = (double)a.x0 + m00 * j + m01 * i, sy = (double)a.y0 + m10 * j + m11 * i;
+        const double ex = slack * (std::fabs((double)a.x0) + std::fabs(m00) * j + std::fabs(m01) * i + 1.0);
+        const double ey = slack * (std::fabs((double)a.y0) + std::fabs(m10) * j + std::fabs(m11) * i + 1.0);
+        if (sx < -ex || sx > (double)w_ - 1.0 + ex || sy < -ey || sy > (double)h - 1.0 + ey)
+            return "a corner pixel samples a position outside the picture's sample grid";
+    }
+    return nullptr;
+}
+
+// Record g of a payload -> the 8 dequantised values: dwords first, first + 1, ... (all requested before the first use;
+// `loads` is the same for every lane, every index clamped to the payload), fields peeled off with funnel shifts.
+template <int KIND>
+__device__ __forceinline__ void codec_values(int g, const CodecLayout lay, const CodecSide side,
+                                             const uint32_t *__restrict__ payload, long long last_dword,
+                                             float (&v)[GI2D_CODEC_FIELDS]) {
+    const long long bit0 = (long long)g * lay.record_bits;
+    const long long first = bit0 >> 5;
+    uint32_t w[GI2D_CODEC_MAX_LOADS];
+#pragma unroll
+    for (int j = 0; j < GI2D_CODEC_MAX_LOADS; ++j) {
+        const long long d = first + j;
+        w[j] = j < lay.loads ? payload[d < last_dword ? d : last_dword] : 0u;
+    }
+    const uint32_t s0 = (uint32_t)bit0 & 31u;
+    uint32_t r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], s0);
+#pragma unroll
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
+        const float code = (float)((int)codec_take(r, lay.width[k]) + lay.qmin[k]);
+        // the variances of a covariance row are log-quantised (HybirdQuant), everything else is LSQ
+        v[k] = (KIND == kCovariance && (k == 2 || k == 4)) ? quant_dequant<GI2D_QUANT_LOG>(code, side.scale[k], side.beta[k])
+                                                          : quant_dequant<GI2D_QUANT_LSQ>(code, side.scale[k], side.beta[k]);
+    }
+}
+
 // Gaussian g of a picture of n: record -> codes -> values -> (view) -> projection -> binning step.  Called by every lane
 // of the picture's launch share, g >= n included (lane 0 resets the status words and advances the record sets).
 // img_w / img_h / tiles / radius_clip: those of the picture that is drawn (for a view: the window's size and the
-// header's radius_clip * scale, so that what the full decode drops as too small stays dropped).  VIEW = false never reads
-// `vw`.
-template <int KIND, bool VIEW>
+// header's radius_clip * scale, so that what the full decode drops as too small stays dropped).  FORM: GI2D_CODEC_FORM_FULL
+// never reads `vw` or `af`, _VIEW reads `vw`, _AFFINE reads `af` and projects a covariance-model gaussian whichever KIND
+// the record has (radius_clip: the header's * sqrt(|det B|), formed by the caller).
+#define GI2D_CODEC_FORM_FULL 0
+#define GI2D_CODEC_FORM_VIEW 1
+#define GI2D_CODEC_FORM_AFFINE 2
+template <int KIND, int FORM>
 __device__ __forceinline__ void codec_decode_bin_one(int g, int n, const CodecLayout lay, const CodecSide side,
                                                      const uint32_t *__restrict__ payload, long long last_dword,
                                                      float clip_coe, float img_w, float img_h, int tiles_x, int tiles_y,
                                                      float radius_clip, const CodecOut out, const BinTarget bt,
-                                                     const CodecView vw) {
+                                                     const CodecView vw, const CodecAffine af) {
     begin_binning(g, bt.status);
     const BinRecs recs = recs_for_binning(bt.recs, g == 0);
     if (g >= n) return;
     const PrevBox old_box = bt.prev_box[g];
-    // the record: dwords first, first + 1, ... (all requested before the first use; `loads` is the same for every lane)
+    // the record: dwords first, first + 1, ... (all requested before the first use; `loads` is the same for every lane).
+    // Spelled out here, not through codec_values: the full decode's and the view's instantiations keep the instructions
+    // they had before there were affine views
     const long long bit0 = (long long)g * lay.record_bits;
     const long long first = bit0 >> 5;
     uint32_t w[GI2D_CODEC_MAX_LOADS];
@@ -95,8 +206,10 @@ __device__ __forceinline__ void codec_decode_bin_one(int g, int n, const CodecLa
         v[k] = (KIND == kCovariance && (k == 2 || k == 4)) ? quant_dequant<GI2D_QUANT_LOG>(code, side.scale[k], side.beta[k])
                                                           : quant_dequant<GI2D_QUANT_LSQ>(code, side.scale[k], side.beta[k]);
     }
-    if (VIEW) view_transform<KIND>(v, vw);
-    const ProjOut o = project_values<KIND>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h, tiles_x,
+    if (FORM == GI2D_CODEC_FORM_VIEW) view_transform<KIND>(v, vw);
+    if (FORM == GI2D_CODEC_FORM_AFFINE) affine_transform<KIND>(v, af);
+    constexpr int PROJ = FORM == GI2D_CODEC_FORM_AFFINE ? (int)kCovariance : KIND;
+    const ProjOut o = project_values<PROJ>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h, tiles_x,
                                            tiles_y, radius_clip);
     if (out.xys) out.xys[g] = o.xy;
     if (out.radii) out.radii[g] = o.radius;
@@ -180,6 +293,78 @@ __device__ __forceinline__ void codec_draw_tile(FwdLds &sm, int *grp, int tile, 
     // "no intersection at all" (image = background): what the binning step noted (fast_fwd_kernel has the reasoning)
     const bool nothing = background != nullptr && !tile_pass_has_members(rs);
     draw_rasterize_staged<DTYPE, LAYOUT>(sm, len, tx, ty, img_w, img_h, nothing, background, out);
+    if (tid == 0 && L > 0) status[0] = 1;
+}
+
+// ------------------------------------------------------------------------------------------- draw, the whole row
+// The draw of an AFFINE picture: a reduced or sheared view puts more than the 256 entries of the rule above into a tile,
+// and its specification (codec.affine_parameters) consumes every tile list to its end.  Same list head, but every survivor
+// of the row -- up to GI2D_FAST_C -- is kept: its id goes to `sorted` at its rank, and the walk is that of
+// gi2d_codec_overview.hip::raster_fwd_long_kernel, 256 entries staged at a time with the per-wave skip, the pixel sums
+// carried across the rounds (gi2d_long_core.h).  Round 0 is staged by the head's `put` straight from the records it has
+// loaded; later rounds load their entries' records again by id.  The ids must outlive the head, so they have an array of
+// their own instead of overlaying the staging arrays.  A row that lost candidates (more than GI2D_FAST_C) raises
+// status[1] as in every tile pass, and the caller draws the picture again through the capacity-free ops, which walk the
+// same ascending lists with the same arithmetic: the two routes give the same bits.
+struct RowsLds {
+    LongLds l;
+    int ids[GI2D_FAST_C];     // the head's candidate buffer
+    int sorted[GI2D_FAST_C];  // the survivors' ids by rank
+};
+// one entry of a row staged for long_consume, from its record -> whether it can exceed alpha = 1
+__device__ __forceinline__ bool rows_stage_entry(LongLds &sm, int k, const BinRec &br) {
+    const GaussRec &r = br.r;
+    const AlphaRule ar = alpha_rule(r.gx, r.gy, r.a, r.b, r.c, r.opac);
+    const ConicS s = scale_conic(r.a, r.b, r.c);
+    sm.a[k] = make_float4(r.gx, r.gy, s.ha, s.hb);
+    sm.b[k] = make_float4(s.hc, r.opac, r.cr, r.cg);
+    sm.c[k] = make_float2(r.cb, __int_as_float((int)ar.lim));
+    sm.reach[k] = make_float2(br.hx, br.hy);  // cull_extent of the same values, formed once by the binning step
+    return ar.clamp;
+}
+// Arguments as codec_draw_tile's (no gradient rows: an affine picture's workspace is a decode's).
+template <int DTYPE, int LAYOUT>
+__device__ __forceinline__ void codec_draw_tile_rows(RowsLds &sm, int *grp, int tile, bool first, int tiles_x, int tiles_y,
+                                                     int img_w, int img_h, const RecSets rs,
+                                                     const float *__restrict__ background, int32_t *__restrict__ lists,
+                                                     int2 *__restrict__ tile_bins, int32_t *__restrict__ status,
+                                                     void *__restrict__ out) {
+    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float4 *recs = recs_for_tile_pass(rs, first && tid == 0);
+    bool clamp = false;  // an entry this lane staged for round 0 can exceed alpha = 1
+    const int L = tile_list_head<false>(
+        sm.ids, grp, tile, tx, ty, recs, lists, tile_bins, status, [&](int, const BinRec &br) { return br; },
+        [&](int rank, int g, const BinRec &br) {  // (rank < GI2D_FAST_C: it counts other candidates of the row)
+            sm.sorted[rank] = g;
+            if (rank < GI2D_LONG_BATCH) clamp = rows_stage_entry(sm.l, rank, br) || clamp;
+        }, Inbox{nullptr}, head_row_load(lists, tile, false));
+    const int len = L > GI2D_FAST_C ? GI2D_FAST_C : L;
+    const int j = tx * GI2D_TILE + (lane & 15), i = ty * GI2D_TILE + wv * 4 + (lane >> 4);
+    const float px = (float)j, py = (float)i;
+    const LongStrip strip = long_strip(tx, ty, wv, img_w, img_h);
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+    for (int base = 0; base < len; base += GI2D_LONG_BATCH) {  // (tile-uniform trip count)
+        const int m = min(GI2D_LONG_BATCH, len - base);
+        if (base > 0) {  // (sorted: complete since the first round's barriers)
+            clamp = false;
+            if (tid < m) {
+                const int g = min(max(sm.sorted[base + tid], 0), (int)(rs.stride / 4) - 1);
+                clamp = rows_stage_entry(sm.l, tid, load_record(recs, g));
+            }
+        }
+        long_consume<true>(sm.l, m, clamp, strip, px, py, o0, o1, o2);  // (opens and ends with a workgroup barrier)
+    }
+    // "no intersection at all" (image = background): what the binning step noted (codec_draw_tile)
+    if (background != nullptr && !tile_pass_has_members(rs)) {
+        o0 = background[0];
+        o1 = background[1];
+        o2 = background[2];
+    }
+    // (every round is consumed behind a workgroup barrier, and with no round nothing was staged: the arrays are free)
+    pixel_store_strip<DTYPE, LAYOUT>(o0, o1, o2, lane & 15, lane >> 4, tx, ty * GI2D_TILE + wv * 4, img_w, img_h,
+                                     (tx + 1) * GI2D_TILE <= img_w && (ty + 1) * GI2D_TILE <= img_h,
+                                     reinterpret_cast<char *>(sm.l.a) + wv * GI2D_PIXEL_STAGE_BYTES, out);
     if (tid == 0 && L > 0) status[0] = 1;
 }
 

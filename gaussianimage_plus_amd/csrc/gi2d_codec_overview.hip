@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "gi2d_codec_layout.h"
+#include "gi2d_long_core.h"
 #include "gi2d_pixel_format.h"
 #include "gi2d_quant_core.h"
 
@@ -102,39 +103,8 @@ __global__ __launch_bounds__(256) void codec_decode_overview_kernel(
 }
 
 // ------------------------------------------------------------------------------------------- forward, any list length
-#define GI2D_LONG_BATCH 256
-struct LongLds {
-    float4 a[GI2D_LONG_BATCH];               // gx, gy, ha, hb   (conic pre-scaled: scale_conic)
-    float4 b[GI2D_LONG_BATCH];               // hc, opacity, cr, cg
-    float2 c[GI2D_LONG_BATCH];               // cb, AlphaRule::lim
-    float2 reach[GI2D_LONG_BATCH];           // half extents of the alpha >= 1/255 box (cull_extent)
-    unsigned char keep[4][GI2D_LONG_BATCH];  // per wave: the batch entries its strip keeps, ascending
-};
-
-// one staged entry on this lane's pixel: the arithmetic of gi2d_raster_core.h::fwd_trips, one pixel per lane
-template <bool CLAMP>
-__device__ __forceinline__ void long_pair(const LongLds &sm, int k, float px, float py, float &o0, float &o1, float &o2) {
-    const float4 A = sm.a[k], B = sm.b[k];
-    const float2 Cc = sm.c[k];
-    const unsigned lim = (unsigned)__float_as_int(Cc.y);
-    const float dy = A.y - py;
-    const float bdy = A.w * dy, cdy2 = __builtin_fmaf(B.x * dy, dy, 0.f);
-    const float dx = A.x - px;
-    const float sig = __builtin_fmaf(dx, __builtin_fmaf(A.z, dx, bdy), cdy2);
-    const float tt = B.y * pair_vis(sig);
-    const bool ok = CLAMP ? pair_lands_odd(sig, tt, lim) : pair_lands(sig, lim);
-    float am = ok ? tt : 0.f;
-    if (CLAMP) am = fminf(1.f, am);
-    o0 = __builtin_fmaf(B.z, am, o0);
-    o1 = __builtin_fmaf(B.w, am, o1);
-    o2 = __builtin_fmaf(Cc.x, am, o2);
-}
-
-// torch.clamp(x, 0, 1): a NaN stays a NaN
-__device__ __forceinline__ float clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
-
-static_assert(sizeof(float4) * GI2D_LONG_BATCH >= 4 * GI2D_PIXEL_STAGE_BYTES, "LongLds::a holds the four waves' staged strips");
-
+// (LongLds, long_pair, clamp01 and the consumption of a staged batch, long_consume: gi2d_long_core.h, shared with the
+// whole-row draw of the decoder's fast path)
 // DTYPE, LAYOUT: the picture format (gi2d_pixel_format.h).  float32 "hwc" is the kernel as it was before there were formats:
 // its epilogue is spelled out below, clamp01 and three dword stores per lane.
 template <bool SKIP, int DTYPE = GI2D_PIXEL_F32, int LAYOUT = GI2D_LAYOUT_HWC>
@@ -167,9 +137,7 @@ __global__ __launch_bounds__(256) void raster_fwd_long_kernel(
     const int start = min(max(range.x, 0), capacity);
     const int end = min(max(range.y, start), capacity);
     const float px = (float)j, py = (float)i;
-    // what this wave's strip and the tile's columns span (clipped to the picture)
-    const float sy0 = (float)(ty * GI2D_TILE + wv * 4), sy1 = fminf(sy0 + 3.f, (float)(img_h - 1));
-    const float sx0 = (float)(tx * GI2D_TILE), sx1 = fminf(sx0 + 15.f, (float)(img_w - 1));
+    const LongStrip strip = long_strip(tx, ty, wv, img_w, img_h);
     float o0 = 0.f, o1 = 0.f, o2 = 0.f;
     for (int base = start; base < end; base += GI2D_LONG_BATCH) {
         const int m = min(GI2D_LONG_BATCH, end - base);
@@ -191,41 +159,7 @@ __global__ __launch_bounds__(256) void raster_fwd_long_kernel(
                 sm.reach[tid] = make_float2(hx, hy);
             }
         }
-        const bool clamp_any = __syncthreads_or(clamp) != 0;  // (also the barrier behind the staging stores)
-        if (SKIP) {
-            int kept = 0;
-            for (int c0 = 0; c0 < m; c0 += 64) {
-                const int k = c0 + lane;
-                bool keep = false;
-                if (k < m) {
-                    const float2 h = sm.reach[k];
-                    const float4 A = sm.a[k];
-                    // hx < 0: can never land; GI2D_CULL_FULL: no finite box, every pixel is evaluated
-                    keep = h.x >= 0.f && (h.x >= GI2D_CULL_FULL || (A.y - h.y <= sy1 && A.y + h.y >= sy0 &&
-                                                                    A.x - h.x <= sx1 && A.x + h.x >= sx0));
-                }
-                const unsigned long long mask = __ballot(keep);
-                if (keep) sm.keep[wv][kept + __popcll(mask & lanemask_lt())] = (unsigned char)k;
-                kept += __popcll(mask);
-            }
-            __builtin_amdgcn_wave_barrier();  // wave-private list: DS ops of one wave complete in order
-            if (clamp_any) {
-#pragma unroll 4
-                for (int t = 0; t < kept; ++t) long_pair<true>(sm, sm.keep[wv][t], px, py, o0, o1, o2);
-            } else {
-#pragma unroll 4
-                for (int t = 0; t < kept; ++t) long_pair<false>(sm, sm.keep[wv][t], px, py, o0, o1, o2);
-            }
-        } else {
-            if (clamp_any) {
-#pragma unroll 4
-                for (int k = 0; k < m; ++k) long_pair<true>(sm, k, px, py, o0, o1, o2);
-            } else {
-#pragma unroll 4
-                for (int k = 0; k < m; ++k) long_pair<false>(sm, k, px, py, o0, o1, o2);
-            }
-        }
-        __syncthreads();  // the batch is consumed: the next one may be staged
+        long_consume<SKIP>(sm, m, clamp, strip, px, py, o0, o1, o2);  // (opens and ends with a workgroup barrier)
     }
     if constexpr (PLAIN) {
         if (inside) {

@@ -673,6 +673,48 @@ int gi2d_codec_decode_bin_view(int kind, int num_points, int xy_bits, int p0_bit
                                float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors,
                                void *workspace, size_t workspace_bytes, int32_t *status, gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ affine views of a packed stream
+ * An AFFINE VIEW samples the fitted function, low-passed, through an affine map: output pixel (row i, column j) of an
+ * out_height x out_width picture is the function at source position (x0 + m00 j + m01 i, y0 + m10 j + m11 i) -- a resized
+ * crop with a scale per axis, a flip (negative scale), a rotation, a shear.  The entries receive B = M^-1 (b00, b01, b10,
+ * b11, fp32) and the low-pass's variance P = (pxx, pxy, pyy) in output pixels^2, and carry the map out on the gaussians
+ * in separate fp32 operations (codec.affine_parameters restates them):
+ *     dx = x - x0, dy = y - y0;  x' = b00 dx + b01 dy,  y' = b10 dx + b11 dy
+ *     (a, b, c) = the covariance (kind 2: as the scale-rot projection builds it)
+ *     n00 = b00 a + b01 b, n01 = b00 b + b01 c, n10 = b10 a + b11 b, n11 = b10 b + b11 c
+ *     cxx = n00 b00 + n01 b01, cxy = n00 b10 + n01 b11, cyy = n10 b10 + n11 b11
+ *     det0 = cxx cyy - cxy cxy;  cxx += pxx, cxy += pxy, cyy += pyy;  det1 likewise;  colour *= sqrt(max(det0, 0) / det1)
+ * The result is projected as a COVARIANCE-model gaussian (gi2d_project_gaussians_2d_covariance_forward) for either kind,
+ * at out_height x out_width with radius_clip AS GIVEN (the caller passes the stream's value * sqrt(|det B|)), and every
+ * tile consumes its whole list in ascending id order: there is no 256-entry rule.
+ *   gi2d_codec_decode_bin_affine  gi2d_codec_decode_bin_view's launch with this map: fills a fast-path workspace.
+ *   gi2d_codec_draw_rows          gi2d_codec_draw for such a workspace: the same list head, then the WHOLE row (up to 1024
+ *                                 candidates) walked 256 staged entries at a time with the arithmetic and the per-wave skip
+ *                                 of gi2d_rasterize_forward_long.  A row that lost candidates raises status[1]; the picture
+ *                                 is then drawn by the route below, which gives the same bits whenever both are complete.
+ *   gi2d_codec_decode_affine      the capacity-free route's per-gaussian kernel, the sibling of gi2d_codec_decode_overview:
+ *                                 the five arrays (all required) for gi2d_bin_gaussians + gi2d_rasterize_forward_long_as.
+ * Refused (-1) before any HIP call, in double on the fp32 values: a value that is not finite; a singular value of B outside
+ * 1/64 .. 64; P not positive semi-definite or pxx, pyy > 4; an empty output; more than 16384 tiles; a corner pixel centre
+ * whose source position (through M = B^-1, bounds widened by 2^-20 of the terms) lies outside [0, img_width - 1] x
+ * [0, img_height - 1]; and what gi2d_codec_decode_bin / gi2d_codec_draw refuse. */
+int gi2d_codec_decode_bin_affine(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                                 const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
+                                 unsigned img_height, unsigned img_width, float x0, float y0, float b00, float b01,
+                                 float b10, float b11, float pxx, float pxy, float pyy, unsigned out_height,
+                                 unsigned out_width, int tiles_x, int tiles_y, float radius_clip, float *xys,
+                                 int32_t *radii, float *conics, int32_t *num_tiles_hit, float *colors, void *workspace,
+                                 size_t workspace_bytes, int32_t *status, gi2d_stream_t stream);
+int gi2d_codec_decode_affine(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                             const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
+                             unsigned img_height, unsigned img_width, float x0, float y0, float b00, float b01, float b10,
+                             float b11, float pxx, float pxy, float pyy, unsigned out_height, unsigned out_width,
+                             int tiles_x, int tiles_y, float radius_clip, float *xys, int32_t *radii, float *conics,
+                             int32_t *num_tiles_hit, float *colors, gi2d_stream_t stream);
+int gi2d_codec_draw_rows(int num_points, int tiles_x, int tiles_y, unsigned img_width, unsigned img_height,
+                         const float *background, void *workspace, size_t workspace_bytes, int32_t *status, int dtype,
+                         int layout, void *out, gi2d_stream_t stream);
+
 /* ------------------------------------------------------------------ reduced views of a packed stream
  * An OVERVIEW samples the fitted function, low-passed with an isotropic gaussian, on a grid coarser than the picture's:
  * output pixel (row i, column j) is the prefiltered function at (x0 + j / scale, y0 + i / scale), 1/64 <= scale < 1.
@@ -775,7 +817,19 @@ int gi2d_codec_convert(int dtype, int layout, unsigned img_height, unsigned img_
  *                        tiles_y workgroups; no host synchronisation, capturable in a graph.  Refuses (-1,
  *                        gi2d_last_error_string set) before any HIP call: K out of range, a NULL pointer, an unknown format,
  *                        a tile grid that does not cover the picture, a table or workspace that is too small, a stream or a
- *                        view the single-picture calls refuse, two pictures that share a workspace or a status row. */
+ *                        view the single-picture calls refuse, two pictures that share a workspace or a status row.
+ *   gi2d_codec_decode_batch_affine   the same call with AFFINE pictures among its K: view = 2 in a picture's descriptor
+ *                        selects gi2d_codec_decode_bin_affine + gi2d_codec_draw_rows for it (x0, y0, scale of the descriptor
+ *                        are then not read; radius_clip is the stream's value * sqrt(|det B|)), and its map is affines[k]
+ *                        -- a parallel array of K entries, read only where view = 2, so struct gi2d_codec_picture keeps its
+ *                        size and a caller of gi2d_codec_decode_batch is untouched (that entry is this one with affines =
+ *                        NULL, and refuses view = 2).  Still three launches for all K; a call with an affine picture runs
+ *                        the second form of the decode and draw kernels and one more table writer. */
+typedef struct gi2d_codec_affine {
+    float x0, y0;       /* source position of output pixel (0, 0) */
+    float b[4];         /* b00, b01, b10, b11: the inverse of the map */
+    float prefilter[3]; /* pxx, pxy, pyy: variance of the low-pass, output pixels^2 */
+} gi2d_codec_affine;
 typedef struct gi2d_codec_picture {
     int kind, num_points, xy_bits, p0_bits, p1_bits, color_bits;
     float side[16];
@@ -795,6 +849,10 @@ size_t gi2d_codec_decode_workspace_bytes(int num_points, int tiles_x, int tiles_
 int gi2d_codec_decode_batch(int num_pictures, const gi2d_codec_picture *pictures, void *batch, size_t batch_bytes,
                             unsigned out_height, unsigned out_width, int tiles_x, int tiles_y, const float *background,
                             int dtype, int layout, void *out, gi2d_stream_t stream);
+int gi2d_codec_decode_batch_affine(int num_pictures, const gi2d_codec_picture *pictures, const gi2d_codec_affine *affines,
+                                   void *batch, size_t batch_bytes, unsigned out_height, unsigned out_width, int tiles_x,
+                                   int tiles_y, const float *background, int dtype, int layout, void *out,
+                                   gi2d_stream_t stream);
 
 /* ------------------------------------------------------------------ rANS payload (payload codings 1 and 2 of format 1)
  * The records of coding 0, entropy coded: gaussianimage_plus_amd/codec.py owns the container (tag "rANS", model section,

@@ -42,17 +42,28 @@ picture at distinct origins, scale 1, next to Decoder.decode_views of the same v
 (a region is `reps` calls of K pictures).  Same regions, same discipline (profiles/decode_batch_time.json).  With --trace
 the K = 64 batch and the 64 single decodes are run a few times, for the per-kernel split.
 
+--affine adds, per fit, `affine`: 64 pictures per call in float16 "chw" at 224x224, microseconds PER PICTURE, for seeded
+random resized crops (area 8-100 % of the picture, aspect 3/4-4/3 log-uniform, half of them flipped; redrawn until the
+crop fits): (a) `affine_us`, Decoder.decode_batch with one codec.Affine.resized_crop per picture -- the three shared
+launches, plus the redraw of any picture whose tile row overflowed (`redrawn_share`); (b) `isotropic_us`, the same crops
+without aspect jitter or flip -- the square of the same area at the same centre, as a codec.View (scale >= 1) or a
+codec.Overview (scale < 1) through decode_batch: what a caller has without affine views; (c) `grid_sample_us`, a full-size
+decode_batch followed by torch.nn.functional.affine_grid + grid_sample (bilinear) with the same matrices.  Same regions,
+same discipline (profiles/decode_affine_time.json).
+
     python tools/decode_time.py [--reps 200] [--coding fixed|rans|rans-delta] [--order fit position]
                                 [--chunk-log2 10 8 12] [--trace]
                                 [--view 256,128,256,256,1 --view 256,128,1024,1024,4 --view 0,0,1536,1024,2]
                                 [--overview] [--out-json profiles/decode_overview_time.json]
-                                [--format uint8,hwc4 --format float16,chw --format float32,hwc] [--batch]
+                                [--format uint8,hwc4 --format float16,chw --format float32,hwc] [--batch] [--affine]
 --trace decodes a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for
 the per-kernel split (profiles/decode_kernel_stats.csv).
 """
 import argparse
 import json
+import math
 import os
+import random
 import statistics
 import sys
 import time
@@ -227,6 +238,78 @@ def batch_rows(a, dec, up):
     return rows
 
 
+def random_crops(k, seed, side=224):
+    """k seeded random resized crops of the W x H picture -> (affines, isotropic views, theta [k, 2, 3] for affine_grid)."""
+    rng = random.Random(seed)
+    header = dict(width=W, height=H)
+    affines, plain, theta = [], [], []
+    for _ in range(k):
+        while True:
+            area = rng.uniform(0.08, 1.0) * W * H
+            ratio = math.exp(rng.uniform(math.log(3 / 4), math.log(4 / 3)))
+            cw, ch = math.sqrt(area * ratio), math.sqrt(area / ratio)
+            if cw <= W and ch <= H:
+                break
+        x0, y0, flip = rng.uniform(0, W - cw), rng.uniform(0, H - ch), rng.random() < 0.5
+        af = codec.Affine.resized_crop(x0, y0, cw, ch, side, side, hflip=flip).check(header)
+        affines.append(af)
+        # the square of the same area at the same centre, no flip: a View where it magnifies, an Overview where it reduces
+        sq = min(math.sqrt(cw * ch), float(H))
+        sx0, sy0 = min(max(x0 + (cw - sq) / 2, 0.0), W - sq), min(max(y0 + (ch - sq) / 2, 0.0), H - sq)
+        scale = side / sq
+        if scale >= 1.0:
+            v = codec.View(sx0, sy0, side, side, scale)
+            while v.x0 + side / v.scale > W or v.y0 + side / v.scale > H:  # (float32 rounding of the three numbers)
+                v = codec.View(max(v.x0 - 1e-3, 0.0), max(v.y0 - 1e-3, 0.0), side, side, v.scale * (1 + 1e-6))
+        else:
+            m = (1 / scale - 1) / 2
+            v = codec.Overview(sx0 + m, sy0 + m, side, side, scale)
+            while True:
+                mm = (1.0 / v.scale - 1.0) / 2.0
+                if v.x0 - mm >= 0 and v.y0 - mm >= 0 and v.x0 + (side - 1) / v.scale + mm <= W - 1 and \
+                        v.y0 + (side - 1) / v.scale + mm <= H - 1:
+                    break
+                v = codec.Overview(min(max(v.x0, mm + 1e-3), W - 1 - (side - 1) / v.scale - mm - 1e-3),
+                                   min(max(v.y0, mm + 1e-3), H - 1 - (side - 1) / v.scale - mm - 1e-3), side, side,
+                                   min(v.scale * (1 + 1e-5), 0.99999))
+        plain.append(v.check(header))
+        # source pixel x = x0 + m00 j + m01 i with j = (jn + 1) side / 2 - 0.5, normalised as grid_sample does (align_corners=False)
+        row = lambda o, a, b, size: [a * side / size, b * side / size,
+                                     2 * (o + (a + b) * (side / 2 - 0.5) + 0.5) / size - 1]
+        theta.append([row(af.x0, af.m00, af.m01, W), row(af.y0, af.m10, af.m11, H)])
+    return affines, plain, torch.tensor(theta, dtype=torch.float32, device="cuda:0")
+
+
+def affine_rows(a, dec, up, k=64, side=224):
+    affines, plain, theta = random_crops(k, 20241019, side)
+    streams = [up] * k
+    out = torch.empty(k, 3, side, side, dtype=torch.float16, device="cuda:0")
+    full = torch.empty(k, 3, H, W, dtype=torch.float16, device="cuda:0")
+
+    def grid_route():
+        dec.decode_batch(streams, None, out=full, **BATCH_FORMAT)
+        grid = torch.nn.functional.affine_grid(theta, (k, 3, side, side), align_corners=False).half()
+        return torch.nn.functional.grid_sample(full, grid, mode="bilinear", padding_mode="border", align_corners=False)
+
+    got = dec.decode_batch(streams, affines, **BATCH_FORMAT).float()
+    redrawn = list(dec.batch_redrawn)
+    ref = grid_route().float()
+    mse = torch.mean((got - ref) ** 2, dim=(1, 2, 3))
+    r = {"pictures": k, "size": [side, side], "format": ["float16", "chw"], "seed": 20241019,
+         "crops_reducing_on_an_axis": sum(abs(af.m00) > 1 or abs(af.m11) > 1 for af in affines),
+         "isotropic_overviews": sum(isinstance(v, codec.Overview) for v in plain),
+         "redrawn_share": round(len(redrawn) / k, 4),
+         "median_psnr_db_against_grid_sample": round(float(torch.median(10 * torch.log10(1.0 / mse))), 2)}
+    for key, fn in (("affine", lambda: dec.decode_batch(streams, affines, out=out, **BATCH_FORMAT)),
+                    ("isotropic", lambda: dec.decode_batch(streams, plain, out=out, **BATCH_FORMAT)),
+                    ("grid_sample", grid_route)):
+        med, lo, hi, regions = median_us(fn, a.reps)
+        r[key + "_us"] = round(med / k, 2)  # per picture
+        r[key + "_us_range"] = [round(lo / k, 2), round(hi / k, 2)]
+        r[key + "_us_regions"] = [round(x / k, 2) for x in regions]
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
@@ -240,6 +323,7 @@ def main():
     ap.add_argument("--overview", action="store_true")
     ap.add_argument("--format", type=parse_format, action="append", default=[], metavar="DTYPE,LAYOUT")
     ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--affine", action="store_true")
     ap.add_argument("--out-json", default=None, metavar="PATH")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_time.py needs the GPU"
@@ -323,6 +407,8 @@ def main():
             row["formats"] = format_rows(a, dec, up, out)
         if a.batch:
             row["batches"] = batch_rows(a, dec, up)
+        if a.affine:
+            row["affine"] = affine_rows(a, dec, up)
         res["sizes"][str(n)] = row
     if not a.trace:
         print(json.dumps(res))
