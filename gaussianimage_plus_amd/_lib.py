@@ -105,6 +105,8 @@ SIGNATURES.update({
     "gi2d_codec_histogram_delta": [_i, _i, _i, _i, _i, _i, _i, _u, _p, _sz, _p, _p],
     "gi2d_codec_rans_encode_delta": [_i, _i, _i, _i, _i, _i, _i, _u, _u, _p, _sz, _p, _sz, _p, _sz, _p, _p],
     "gi2d_codec_rans_expand_delta": [_i, _i, _i, _i, _i, _i, _i, _u, _u, _p, _sz, _p, _p, _sz, _sz, _p, _sz, _p, _i, _p],
+    # several streams per expansion launch: host array of struct gi2d_codec_rans_stream (codec.py::_CRansStream)
+    "gi2d_codec_rans_expand_batch": [_i, _p, _p, _sz, _i, _p],
     "gi2d_codec_position_keys": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p],
     "gi2d_codec_gather": [_i, _i, _i, _i, _i, _i, _p, _sz, _p, _p, _sz, _p],
     # SSIM / MS-SSIM (gaussianimage_plus_amd/metrics.py; the batched entries take struct gi2d_ssim_pair[])
@@ -130,6 +132,7 @@ SIZE_FUNCS = {
     "gi2d_codec_batch_bytes": [_i],
     "gi2d_codec_decode_workspace_bytes": [_i, _i, _i],
     "gi2d_codec_rans_scratch_bytes": [_i, _i, _i, _i, _i, _i, _i, _u],
+    "gi2d_codec_rans_batch_bytes": [_i],
     "gi2d_ssim_workspace_bytes": [_i, _i, _i, _i],
     "gi2d_ssim_batch_workspace_bytes": [_i, _p, _i, _i],
 }

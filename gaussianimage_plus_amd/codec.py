@@ -81,7 +81,8 @@ Payload coding 1 carries the integers of coding 0 entropy coded (INTEGRATION.md 
 width w is split into hi = v >> max(0, w - 8), a symbol of a 12-bit rANS model stored in the stream, and raw low bits; a
 chunk of 2^k records (k = 8..12) is one wave's work, one coder state per lane over a shared stream of 16-bit words.
 gi2d_codec_rans_expand (csrc/gi2d_rans.hip) turns the chunks back into the coding-0 payload in a buffer the Decoder owns,
-and the launches above run on it unchanged: the picture is that of the coding-0 stream with the same codes.
+and the launches above run on it unchanged: the picture is that of the coding-0 stream with the same codes.  A call that
+holds two or more coded streams expands them in one launch per 64 (gi2d_codec_rans_expand_batch; expansion_groups is the plan).
 
 Payload coding 2 ("rans-delta") is that container under the tag "rANd", and the byte of a table header that coding 1
 keeps 0 names the field's transform: 1 = the symbol of record g is (hi(g) - hi(g - 1)) mod 2^hb, except for the first
@@ -1241,6 +1242,24 @@ class _CAffine(C.Structure):
     _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("b", C.c_float * 4), ("prefilter", C.c_float * 3)]
 
 
+class _CRansStream(C.Structure):
+    """struct gi2d_codec_rans_stream of include/gi2d.h."""
+    _fields_ = [("kind", C.c_int), ("num_points", C.c_int), ("xy_bits", C.c_int), ("p0_bits", C.c_int),
+                ("p1_bits", C.c_int), ("color_bits", C.c_int), ("chunk_log2", C.c_int), ("coded_mask", C.c_uint),
+                ("delta_mask", C.c_uint), ("tables", C.c_void_p), ("tables_bytes", C.c_size_t),
+                ("directory", C.c_void_p), ("chunk_data", C.c_void_p), ("chunk_data_bytes", C.c_size_t),
+                ("max_chunk_bytes", C.c_size_t), ("payload", C.c_void_p), ("payload_bytes", C.c_size_t),
+                ("status", C.c_void_p)]
+
+
+def expansion_groups(headers) -> List[List[int]]:
+    """The plan of a decode call's expansions, on the host: headers are parsed streams in call order -> the groups of
+    stream indices that are expanded together, one launch each.  Fixed streams are left out, a group holds at most
+    BATCH_MAX streams, call order is kept.  (A call whose plan is one group of one makes the single-stream call.)"""
+    coded = [k for k, h in enumerate(headers) if h["coding"] != CODING_FIXED]
+    return [coded[i:i + BATCH_MAX] for i in range(0, len(coded), BATCH_MAX)]
+
+
 _STATUS_WORDS = 8
 _STATUS_ROW = 4 * _STATUS_WORDS  # bytes; a launch is given the device address of its row, a plain integer
 
@@ -1284,7 +1303,9 @@ class Decoder:
         # per picture: words 0..3 belong to the binning step and the tile pass (1 = overflow), word 4 to the rANS expansion
         self._status = torch.zeros(1, _STATUS_WORDS, dtype=torch.int32, device=self.dev)
         self._token = 0  # the expansion raises word 4 to the token of its decode: no reset launch between decodes
-        self.expansions = 0  # rANS payloads expanded so far (gi2d_codec_rans_expand launches)
+        self.expansions = 0  # rANS payloads expanded so far
+        self.expansion_launches = 0  # expansion kernel launches so far: 1 per single expansion, 1 per group of up to 64
+        self._rans_table = torch.empty(0, dtype=torch.uint8, device=self.dev)  # gi2d_codec_rans_expand_batch's table
         self._background = torch.ones(3, dtype=torch.float32, device=self.dev)  # the rasterize wrappers' default
         # overviews: per-gaussian arrays, tile lists and the binning workspace (_reserve_overview), regrown when needed
         self._ov: Dict[str, torch.Tensor] = {}
@@ -1393,7 +1414,37 @@ class Decoder:
                   h["data_bytes"], h["max_chunk_bytes"], C.c_void_p(fixed.data_ptr()), fixed.numel(),
                   status + 16, self._token, _stream(self.dev))
         self.expansions += 1
+        self.expansion_launches += 1
         return fixed
+
+    def _expand_all(self, items) -> None:
+        """Every expansion of a call: items = [(header, payload, status row address, fixed)] in call order, as _expand
+        takes them.  One item: _expand, the single-stream launch.  More: gi2d_codec_rans_expand_batch per group of at most
+        BATCH_MAX (expansion_groups) -- the table's writer launches and ONE expansion launch per group."""
+        if len(items) < 2:
+            for item in items:
+                self._expand(*item)
+            return
+        lib = _lib.load()
+        for i in range(0, len(items), BATCH_MAX):
+            group = items[i:i + BATCH_MAX]
+            need = int(lib.gi2d_codec_rans_batch_bytes(len(group)))
+            if self._rans_table.numel() < need:
+                self._rans_table = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            descs = (_CRansStream * len(group))()
+            for d, (h, payload, status, fixed) in zip(descs, group):
+                nb, at = h["payload_bytes"], payload.data_ptr()
+                d.kind, d.num_points, d.chunk_log2 = h["kind"], h["num_points"], h["chunk_log2"]
+                d.xy_bits, d.p0_bits, d.p1_bits, d.color_bits = h["bits"]
+                d.coded_mask, d.delta_mask = h["coded_mask"], h["delta_mask"] if h["coding"] == CODING_RANS_DELTA else 0
+                d.tables, d.tables_bytes = at + nb, payload.numel() - nb
+                d.directory, d.chunk_data = at + h["directory_offset"], at + h["data_offset"]
+                d.chunk_data_bytes, d.max_chunk_bytes = h["data_bytes"], h["max_chunk_bytes"]
+                d.payload, d.payload_bytes, d.status = fixed.data_ptr(), fixed.numel(), status + 16
+            _lib.call("gi2d_codec_rans_expand_batch", len(group), descs, C.c_void_p(self._rans_table.data_ptr()),
+                      self._rans_table.numel(), self._token, _stream(self.dev))
+            self.expansions += len(group)
+            self.expansion_launches += 1
 
     def _next_token(self) -> None:
         self._token += 1
@@ -1401,9 +1452,9 @@ class Decoder:
             self._status.zero_()
             self._token = 1
 
-    def _check_expanded(self, word: int) -> None:
+    def _check_expanded(self, word: int, which: str = "") -> None:
         if word == self._token:
-            raise ValueError("GI2D stream: rANS payload: a coder state did not return to its start value (the chunk data "
+            raise ValueError(f"GI2D stream{which}: rANS payload: a coder state did not return to its start value (the chunk data "
                              "is not what an encoder wrote)")
 
     def fixed_payload(self, stream) -> torch.Tensor:
@@ -1419,6 +1470,26 @@ class Decoder:
                                  torch.empty(h["fixed_payload_bytes"], dtype=torch.uint8, device=self.dev))
             self._check_expanded(int(self._status[0, 4]))
         return fixed
+
+    def fixed_payloads(self, streams) -> List[torch.Tensor]:
+        """fixed_payload of every stream of a list -> the coding-0 payloads, tensors of their own (a fixed stream: a
+        clone).  The coded streams are expanded together (_expand_all: one launch per 64, the single-stream call for
+        one) and their status words read in ONE host wait; ValueError names the first stream, by its index in `streams`,
+        whose coder states did not return."""
+        dss = [s if isinstance(s, DeviceStream) else self.upload(s) for s in streams]
+        with torch.cuda.device(self.dev):
+            coded = [k for k, ds in enumerate(dss) if ds.header["coding"] != CODING_FIXED]
+            if self._status.shape[0] < len(coded):
+                self._status = torch.zeros(len(coded), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
+            self._next_token()
+            row0 = self._status.data_ptr()
+            out = [ds.payload.clone() if ds.header["coding"] == CODING_FIXED else
+                   torch.empty(ds.header["fixed_payload_bytes"], dtype=torch.uint8, device=self.dev) for ds in dss]
+            self._expand_all([(dss[k].header, dss[k].payload, row0 + _STATUS_ROW * row, out[k]) for row, k in enumerate(coded)])
+            if coded:
+                for k, word in zip(coded, self._status[:len(coded), 4].tolist()):
+                    self._check_expanded(word, f" {k}")
+        return out
 
     # ---------------------------------------------------------------------------------------------- launches
     def _launch(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, fmt: _Format, aux=None) -> None:
@@ -1531,7 +1602,8 @@ class Decoder:
         whose status word 4 an expansion may raise, the device address of status row 0.  Payloads are staged, the status
         rows, the expansion buffer and the overview buffers grown to the call's needs, the token advanced, and every
         rANS payload expanded ONCE, into its slice of `_expanded` (valid until the next call), with the status row of its
-        stream's first picture."""
+        stream's first picture -- all of the call's coded streams together (_expand_all: one launch per 64, the
+        single-stream launch for one)."""
         payloads = self._stage(streams, headers)
         if self._status.shape[0] < len(pictures):
             self._status = torch.zeros(len(pictures), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
@@ -1544,14 +1616,16 @@ class Decoder:
             self._expanded = torch.empty(total, dtype=torch.uint8, device=self.dev)
         self._next_token()
         row0 = self._status.data_ptr()
-        fixed, coded, at = [], [], 0
+        fixed, coded, at, items = [], [], 0, []
         for h, payload, count in zip(headers, payloads, counts):
             if h["coding"] != CODING_FIXED:
                 nb = h["fixed_payload_bytes"]
                 coded.append(len(fixed))
-                payload = self._expand(h, payload, row0 + _STATUS_ROW * len(fixed), self._expanded[at:at + nb])
+                items.append((h, payload, row0 + _STATUS_ROW * len(fixed), self._expanded[at:at + nb]))
+                payload = items[-1][3]
                 at += (nb + 255) & ~255
             fixed += [payload] * count
+        self._expand_all(items)
         return fixed, coded, row0
 
     def _finish(self, pictures, fixed, coded, row0: int, images, fmt: _Format, aux=None, geometry: bool = False) -> List[int]:

@@ -172,6 +172,15 @@ __device__ __forceinline__ int batch_find(const int *__restrict__ starts, int k_
     return __builtin_amdgcn_readfirstlane(__popcll(m) - 1);
 }
 
+// The writer of the codec's batch tables (gi2d_codec_batch.hip, gi2d_rans.hip): `words` ints of the block `v`, which
+// travels as the kernel argument, to `dst`.  A block is at most 3840 bytes (the kernel-argument segment is 4 KB).
+template <class T>
+__global__ __launch_bounds__(256) void codec_batch_write_kernel(T v, int words, int *__restrict__ dst) {
+    static_assert(sizeof(T) % sizeof(int) == 0, "copied word by word");
+    const int *src = reinterpret_cast<const int *>(&v);
+    for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
+}
+
 // gi2d_train.hip: write `imgs` (host) and `head` into the table with kernels that carry them as kernel arguments --
 // stream-ordered, no host buffer whose lifetime anybody has to think about, capturable in a graph.
 void write_batch_table(const BatchTable &table, const BatchImage *imgs, int k_images, const BatchHead &head,

@@ -65,13 +65,7 @@ struct CodecBatchAffines {
     CodecAffine af[GI2D_BATCH_MAX];
 };
 static_assert(sizeof(CodecBatchPack) <= 3840 && sizeof(CodecBatchHead) <= 3840 && sizeof(CodecBatchAffines) <= 3840,
-              "a writer's block must fit the kernel-argument segment");
-template <class T>
-__global__ __launch_bounds__(256) void codec_batch_write_kernel(T v, int words, int *__restrict__ dst) {
-    static_assert(sizeof(T) % sizeof(int) == 0, "copied word by word");
-    const int *src = reinterpret_cast<const int *>(&v);
-    for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-}
+              "a writer's block must fit the kernel-argument segment");  // (gi2d_batch.h::codec_batch_write_kernel)
 
 // What gi2d_fast.hip::fast_ws_init_kernel resets of the regions a decode workspace has (carve_decode): the version words,
 // the pool cursor, every row header, every previous box.  blocks_per_picture * 256 lanes per picture.

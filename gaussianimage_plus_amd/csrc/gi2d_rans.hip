@@ -28,6 +28,9 @@
 // Every index that comes from stream content is masked or clamped: the slot to 12 bits, the symbol is a byte and indexes
 // 258 entries, a word position to the wave's staging area, a chunk's offset and length to the chunk data and the staging
 // area.  A stream with nonsense inside decodes to nonsense records inside its own buffers.
+#include <vector>
+
+#include "gi2d_batch.h"
 #include "gi2d_codec_layout.h"
 
 namespace gi2d {
@@ -268,16 +271,18 @@ struct RansExpandArgs {
     unsigned dmask;          // DELTA only: the differenced fields
 };
 
+// The work of one workgroup of the expansion: the tables of the stream `a` into LDS, then wave w expands chunk
+// block * waves + w of that stream (a wave past the stream's last chunk idles).  Called by every thread of the workgroup
+// (it holds the workgroup's one barrier); `lds`: a.L.ncoded tables + waves * (a.in_cap + 2 R) dwords.
 template <bool DELTA>
-__global__ __launch_bounds__(256) void rans_expand_kernel(RansExpandArgs a) {
-    extern __shared__ __align__(16) uint32_t lds[];
+__device__ __forceinline__ void rans_expand_block(const RansExpandArgs &a, uint32_t *lds, int block) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
     const int table_dw = a.L.ncoded * GI2D_RANS_TABLE_DWORDS;
     for (int i = tid; i < table_dw; i += blockDim.x) lds[i] = a.tables[i];
     const int R = a.L.rec.record_bits, group_dw = 2 * R;  // 64 records: dword aligned
     uint32_t *in = lds + table_dw + wave * (a.in_cap + group_dw);
     uint32_t *grp = in + a.in_cap;
-    const int c = blockIdx.x * waves + wave;
+    const int c = block * waves + wave;
     if (c < a.chunks) {
         // the chunk: states | raw section | words, as it lies in the stream
         const uint32_t o0 = min(a.dir[c] >> 2, a.data_dwords), o1 = min(a.dir[c + 1] >> 2, a.data_dwords);
@@ -375,6 +380,54 @@ __global__ __launch_bounds__(256) void rans_expand_kernel(RansExpandArgs a) {
     }
     const bool bad = lane < records && x != GI2D_RANS_LOW;
     if (__ballot(bad) != 0ull && lane == 0) atomicMax(a.status, a.token);
+}
+
+template <bool DELTA>
+__global__ __launch_bounds__(256) void rans_expand_kernel(RansExpandArgs a) {
+    extern __shared__ __align__(16) uint32_t lds[];
+    rans_expand_block<DELTA>(a, lds, (int)blockIdx.x);
+}
+
+// Several streams per expansion launch (include/gi2d.h gi2d_codec_rans_expand_batch; DESIGN.md 3.8 "Batched expansion"):
+// the device table is a head -- the workgroup at which stream s starts -- and one argument block per stream, written as
+// gi2d_codec_batch.hip writes its table.  A workgroup finds its stream with batch_find and does that stream's work only:
+// its tables, its chunks, its output range and its status word; the last workgroup of a stream leaves its surplus waves
+// idle.  DELTA is a workgroup-uniform branch here.
+struct RansBatchHead {
+    int wg_start[96];  // GI2D_BATCH_MAX + 1 used; entry K = number of workgroups
+};
+struct RansBatchTable {
+    RansBatchHead *head;
+    RansExpandArgs *args;
+    size_t bytes;
+};
+static inline size_t rans_batch_bytes(int k) {
+    return align_up(sizeof(RansBatchHead)) + (size_t)(k > 0 ? k : 1) * sizeof(RansExpandArgs);
+}
+static inline RansBatchTable carve_rans_batch(void *base, int k) {  // base: not null
+    RansBatchTable b;
+    b.head = (RansBatchHead *)base;
+    b.args = (RansExpandArgs *)((char *)base + align_up(sizeof(RansBatchHead)));
+    b.bytes = rans_batch_bytes(k);
+    return b;
+}
+#define GI2D_RANS_BATCH_PACK 16 /* argument blocks per writer launch (kernel arguments are limited to 4 KB) */
+struct RansBatchPack {
+    RansExpandArgs args[GI2D_RANS_BATCH_PACK];
+};
+static_assert(sizeof(RansBatchPack) <= 3840 && sizeof(RansBatchHead) <= 3840,
+              "a writer's block must fit the kernel-argument segment");
+
+__global__ __launch_bounds__(256) void rans_expand_batched_kernel(const RansBatchHead *__restrict__ head,
+                                                                  const RansExpandArgs *__restrict__ args, int k_streams) {
+    extern __shared__ __align__(16) uint32_t lds[];
+    const int s = batch_find(head->wg_start, k_streams, (int)blockIdx.x);
+    const RansExpandArgs a = args[s];
+    const int block = (int)blockIdx.x - head->wg_start[s];
+    if (a.dmask)  // workgroup-uniform
+        rans_expand_block<true>(a, lds, block);
+    else
+        rans_expand_block<false>(a, lds, block);
 }
 
 // ------------------------------------------------------------------------------------------------- position order
@@ -507,10 +560,13 @@ static int rans_encode(const char *what, int kind, int n, int xy_bits, int p0_bi
     return check_launch(what);
 }
 
-static int rans_expand(const char *what, int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
-                       int chunk_log2, unsigned coded_mask, unsigned delta_mask, const void *tables, size_t tables_bytes,
-                       const void *directory, const void *chunk_data, size_t chunk_data_bytes, size_t max_chunk_bytes,
-                       void *payload, size_t payload_bytes, int32_t *status, int token, gi2d_stream_t st) {
+// The checks of one stream's expansion, shared by the single entries and the batched one -> its argument block and the
+// two LDS footprints a launch is sized by: the tables' bytes and one wave's (staging area + the group of 64 records).
+static int rans_expand_args(const char *what, int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                            int chunk_log2, unsigned coded_mask, unsigned delta_mask, const void *tables,
+                            size_t tables_bytes, const void *directory, const void *chunk_data, size_t chunk_data_bytes,
+                            size_t max_chunk_bytes, void *payload, size_t payload_bytes, int32_t *status, int token,
+                            RansExpandArgs &a, size_t &table_b, size_t &wave_b) {
     RansLayout L;
     if (!rans_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask, L))
         return GI2D_ERR_INVALID_ARGUMENT;
@@ -531,15 +587,33 @@ static int rans_expand(const char *what, int kind, int n, int xy_bits, int p0_bi
     if (!directory || !chunk_data || !payload || !status || (L.ncoded && !tables) ||
         (((uintptr_t)directory | (uintptr_t)chunk_data | (uintptr_t)payload | (uintptr_t)status | (uintptr_t)tables) & 3))
         return rans_fail(what, "null or misaligned pointer", GI2D_ERR_INVALID_ARGUMENT);
-    RansExpandArgs a;
     a.L = L, a.n = n, a.chunks = chunks, a.tables = (const uint32_t *)tables, a.dir = (const uint32_t *)directory;
     a.data = (const uint32_t *)chunk_data, a.data_dwords = (uint32_t)(chunk_data_bytes / 4);
     a.in_cap = (int)(max_chunk_bytes / 4), a.out = (uint32_t *)payload, a.out_dwords = need;
     a.status = status, a.token = token, a.dmask = delta_mask;
-    const size_t table_b = (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES;
-    const size_t wave_b = ((size_t)a.in_cap + 2 * L.rec.record_bits) * 4;
+    table_b = (size_t)L.ncoded * GI2D_RANS_TABLE_BYTES;
+    wave_b = ((size_t)a.in_cap + 2 * L.rec.record_bits) * 4;
+    return GI2D_OK;
+}
+// Waves per workgroup of an expansion launch: as many of 4 as share the tables within the LDS a launch gets without
+// asking, and no more than the launch has chunks for (`chunks`: of its stream, or of its largest stream).
+static int rans_expand_waves(size_t table_b, size_t wave_b, int chunks) {
     int waves = 4;
     while (waves > 1 && (table_b + waves * wave_b > GI2D_RANS_STATIC_LDS || waves > chunks)) waves >>= 1;
+    return waves;
+}
+
+static int rans_expand(const char *what, int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                       int chunk_log2, unsigned coded_mask, unsigned delta_mask, const void *tables, size_t tables_bytes,
+                       const void *directory, const void *chunk_data, size_t chunk_data_bytes, size_t max_chunk_bytes,
+                       void *payload, size_t payload_bytes, int32_t *status, int token, gi2d_stream_t st) {
+    RansExpandArgs a;
+    size_t table_b, wave_b;
+    const int rc = rans_expand_args(what, kind, n, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask, delta_mask,
+                                    tables, tables_bytes, directory, chunk_data, chunk_data_bytes, max_chunk_bytes, payload,
+                                    payload_bytes, status, token, a, table_b, wave_b);
+    if (rc != GI2D_OK) return rc;
+    const int chunks = a.chunks, waves = rans_expand_waves(table_b, wave_b, chunks);
     const size_t lds = table_b + waves * wave_b;
     const dim3 grid((chunks + waves - 1) / waves), block(64 * waves);
     if (delta_mask) {
@@ -613,6 +687,61 @@ int gi2d_codec_rans_expand_delta(int kind, int n, int xy_bits, int p0_bits, int 
     return rans_expand("codec rans expand delta", kind, n, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2, coded_mask,
                        delta_mask, tables, tables_bytes, directory, chunk_data, chunk_data_bytes, max_chunk_bytes,
                        payload, payload_bytes, status, token, st);
+}
+
+size_t gi2d_codec_rans_batch_bytes(int num_streams) { return rans_batch_bytes(num_streams); }
+
+int gi2d_codec_rans_expand_batch(int num_streams, const struct gi2d_codec_rans_stream *streams, void *batch,
+                                 size_t batch_bytes, int token, gi2d_stream_t st) {
+    const char *what = "codec rans expand batch";
+    // ---- everything is checked before anything is launched (and before any device call at all)
+    if (num_streams < 1 || num_streams > GI2D_BATCH_MAX)
+        return rans_fail(what, "1 .. 64 streams per call", GI2D_ERR_INVALID_ARGUMENT);
+    if (!streams || !batch) return rans_fail(what, "null pointer", GI2D_ERR_INVALID_ARGUMENT);
+    const RansBatchTable table = carve_rans_batch(batch, num_streams);
+    if (batch_bytes < table.bytes || ((uintptr_t)batch & 15))
+        return rans_fail(what, "batch table too small (gi2d_codec_rans_batch_bytes) or misaligned", GI2D_ERR_INVALID_ARGUMENT);
+    std::vector<RansExpandArgs> args((size_t)num_streams);
+    size_t table_b = 0, wave_b = 0;  // the launch's LDS is sized for the most demanding stream of each kind of footprint
+    int most_chunks = 0;
+    for (int s = 0; s < num_streams; ++s) {
+        const gi2d_codec_rans_stream &d = streams[s];
+        const std::string who = std::string(what) + ": stream " + std::to_string(s);
+        size_t tb, wb;
+        const int rc = rans_expand_args(who.c_str(), d.kind, d.num_points, d.xy_bits, d.p0_bits, d.p1_bits, d.color_bits,
+                                        d.chunk_log2, d.coded_mask, d.delta_mask, d.tables, d.tables_bytes, d.directory,
+                                        d.chunk_data, d.chunk_data_bytes, d.max_chunk_bytes, d.payload, d.payload_bytes,
+                                        d.status, token, args[(size_t)s], tb, wb);
+        if (rc != GI2D_OK) return rc;
+        table_b = tb > table_b ? tb : table_b;
+        wave_b = wb > wave_b ? wb : wave_b;
+        most_chunks = args[(size_t)s].chunks > most_chunks ? args[(size_t)s].chunks : most_chunks;
+    }
+    const int waves = rans_expand_waves(table_b, wave_b, most_chunks);
+    const size_t lds = table_b + waves * wave_b;
+    if (!rans_reserve_lds(what, rans_expand_batched_kernel, lds)) return GI2D_ERR_UNSUPPORTED;
+    RansBatchHead head = {};
+    long long total = 0;
+    for (int s = 0; s < num_streams; ++s) {
+        head.wg_start[s] = (int)total;
+        total += (args[(size_t)s].chunks + waves - 1) / waves;
+    }
+    if (total > 0x7fffffffLL) return rans_fail(what, "too many chunks for one launch", GI2D_ERR_INVALID_ARGUMENT);
+    head.wg_start[num_streams] = (int)total;
+    // ---- the table, stream-ordered, then the one expansion launch
+    const hipStream_t q = (hipStream_t)st;
+    RansBatchPack pack = {};
+    for (int s0 = 0; s0 < num_streams; s0 += GI2D_RANS_BATCH_PACK) {
+        const int cnt = num_streams - s0 < GI2D_RANS_BATCH_PACK ? num_streams - s0 : GI2D_RANS_BATCH_PACK;
+        for (int i = 0; i < cnt; ++i) pack.args[i] = args[(size_t)(s0 + i)];
+        hipLaunchKernelGGL(codec_batch_write_kernel<RansBatchPack>, dim3(1), dim3(256), 0, q, pack,
+                           cnt * (int)(sizeof(RansExpandArgs) / sizeof(int)), (int *)(table.args + s0));
+    }
+    hipLaunchKernelGGL(codec_batch_write_kernel<RansBatchHead>, dim3(1), dim3(256), 0, q, head,
+                       (int)(sizeof(RansBatchHead) / sizeof(int)), (int *)table.head);
+    hipLaunchKernelGGL(rans_expand_batched_kernel, dim3((unsigned)total), dim3(64 * waves), lds, q,
+                       (const RansBatchHead *)table.head, (const RansExpandArgs *)table.args, num_streams);
+    return check_launch(what);
 }
 
 int gi2d_codec_position_keys(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, const void *payload,

@@ -889,6 +889,20 @@ int gi2d_codec_decode_batch_affine(int num_pictures, const gi2d_codec_picture *p
  *   gi2d_codec_gather         coding-0 payload + perm i32[N] (device) -> out, the coding-0 payload whose record g is the
  *                             source's record perm[g] (entries clamped to [0, N)); every dword of out written once, the
  *                             padding included; out must not be the input, out_bytes >= 4 * ceil(N * R / 32).
+ *
+ * Several streams per expansion launch: the chunks of different streams are independent waves, so a call that holds K
+ * coded streams (K = 1 .. GI2D_BATCH_MAX = 64) expands them in ONE grid.
+ *   gi2d_codec_rans_stream        the arguments of gi2d_codec_rans_expand_delta, one stream's worth (delta_mask 0: a
+ *                                 coding-1 stream); entries of one call may differ in kind, widths, masks, chunk size, N.
+ *   gi2d_codec_rans_batch_bytes   the device table of a call of `num_streams` (16-byte aligned), rewritten by every call
+ *                                 with stream-ordered writer launches (no host-to-device copy, no pinned buffer).
+ *   gi2d_codec_rans_expand_batch  every stream checked as the single entries check theirs, all before the first launch (an
+ *                                 invalid stream fails the whole call, the message names its index); then the table and one
+ *                                 expansion launch, whose workgroups each serve one stream: its tables, its chunks, its
+ *                                 output and its own status word (raised to `token` as above), under the same clamps.  LDS
+ *                                 and waves per workgroup are those of the call's most demanding stream
+ *                                 (GI2D_ERR_UNSUPPORTED if one wave of it does not fit).  Every output equals the single
+ *                                 entry's byte for byte.
  * Every entry checks its arguments before it launches anything. */
 size_t gi2d_codec_rans_scratch_bytes(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
                                      int chunk_log2, unsigned coded_mask);
@@ -915,6 +929,21 @@ int gi2d_codec_rans_expand_delta(int kind, int num_points, int xy_bits, int p0_b
                                  size_t tables_bytes, const void *directory, const void *chunk_data,
                                  size_t chunk_data_bytes, size_t max_chunk_bytes, void *payload, size_t payload_bytes,
                                  int32_t *status, int token, gi2d_stream_t stream);
+struct gi2d_codec_rans_stream {
+    /* the arguments of gi2d_codec_rans_expand_delta, one stream's worth */
+    int kind, num_points, xy_bits, p0_bits, p1_bits, color_bits, chunk_log2;
+    unsigned coded_mask, delta_mask; /* delta_mask 0: a coding-1 stream */
+    const void *tables;
+    size_t tables_bytes;
+    const void *directory, *chunk_data;
+    size_t chunk_data_bytes, max_chunk_bytes;
+    void *payload;
+    size_t payload_bytes;
+    int32_t *status; /* this stream's own word */
+};
+size_t gi2d_codec_rans_batch_bytes(int num_streams);
+int gi2d_codec_rans_expand_batch(int num_streams, const struct gi2d_codec_rans_stream *streams, void *batch,
+                                 size_t batch_bytes, int token, gi2d_stream_t stream);
 int gi2d_codec_position_keys(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
                              const void *payload, size_t payload_bytes, int32_t *keys, gi2d_stream_t stream);
 int gi2d_codec_gather(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,

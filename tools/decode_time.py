@@ -40,7 +40,10 @@ holds every instantiation of the draw kernel.  Same regions, same discipline (pr
 to Decoder.decode_many of the same streams in the same format (`many_us`), and K = 64 with a 224x224 codec.View per
 picture at distinct origins, scale 1, next to Decoder.decode_views of the same views -- all as microseconds PER PICTURE
 (a region is `reps` calls of K pictures).  Same regions, same discipline (profiles/decode_batch_time.json).  With --trace
-the K = 64 batch and the 64 single decodes are run a few times, for the per-kernel split.
+the K = 64 batch and the 64 single decodes are run a few times, for the per-kernel split.  With --coding rans or
+rans-delta, `batches_coded` holds the same rows for K copies of the coded, uploaded stream, per --order and coding
+(rans-delta: both codings) -- a call's coded streams are expanded in one launch per 64 (profiles/decode_batch_rans_time.json);
+with --trace the K = 64 batch of every coded stream is run too.
 
 --affine adds, per fit, `affine`: 64 pictures per call in float16 "chw" at 224x224, microseconds PER PICTURE, for seeded
 random resized crops (area 8-100 % of the picture, aspect 3/4-4/3 log-uniform, half of them flipped; redrawn until the
@@ -238,6 +241,26 @@ def batch_rows(a, dec, up):
     return rows
 
 
+def coded_batch_block(a, dec, blob):
+    """--batch with --coding rans | rans-delta: the rows of batch_rows for K copies of the coded, uploaded stream, per
+    --order and coding (rans-delta: both codings), at the first --chunk-log2; with what sizes the expansion launch
+    (coded fields, largest chunk) and how many expansion launches one K = 64 call makes."""
+    block = {}
+    for order in a.order:
+        for coding in (("rans",) if a.coding == "rans" else ("rans", "rans-delta")):
+            c = codec.recode(blob, coding, chunk_log2=a.chunk_log2[0], order=None if order == "fit" else order)
+            ci, cup = codec.info(c), dec.upload(c)
+            before = getattr(dec, "expansion_launches", None)
+            dec.decode_batch([cup] * 64, **BATCH_FORMAT)
+            entry = {"stream_bytes": len(c), "ratio_to_fixed": round(len(c) / len(blob), 4), "chunks": ci["chunks"],
+                     "chunk_log2": ci["chunk_log2"], "coded_fields": bin(ci["coded_mask"]).count("1"),
+                     "max_chunk_bytes": ci["max_chunk_bytes"],
+                     "expansion_launches_k64": None if before is None else dec.expansion_launches - before,
+                     "rows": batch_rows(a, dec, cup)}
+            block[f"{coding}/{order}"] = entry
+    return block
+
+
 def random_crops(k, seed, side=224):
     """k seeded random resized crops of the W x H picture -> (affines, isotropic views, theta [k, 2, 3] for affine_grid)."""
     rng = random.Random(seed)
@@ -348,6 +371,8 @@ def main():
             for k in a.chunk_log2:
                 for order in a.order:
                     coded[(k, order)] = codec.recode(blob, "rans-delta", chunk_log2=k, order=None if order == "fit" else order)
+                    if a.batch:  # the coding-1 stream in the same order: the batched expansion serves both
+                        coded[(k, order, "rans")] = codec.recode(blob, "rans", chunk_log2=k, order=None if order == "fit" else order)
         if a.trace:
             ups = [up] + [dec.upload(c) for c in coded.values()]
             for u in ups:
@@ -360,6 +385,9 @@ def main():
                 for _ in range(10):
                     dec.decode_batch([up] * 64, **BATCH_FORMAT)
                     dec.decode_many([up] * 64, **BATCH_FORMAT)
+                for u in ups[1:]:  # coded streams: the expansion of 64 of them in one call, next to the 50 single ones above
+                    for _ in range(10):
+                        dec.decode_batch([u] * 64, **BATCH_FORMAT)
             torch.cuda.synchronize()
             continue
         info = codec.info(blob)
@@ -407,6 +435,8 @@ def main():
             row["formats"] = format_rows(a, dec, up, out)
         if a.batch:
             row["batches"] = batch_rows(a, dec, up)
+            if a.coding != "fixed":
+                row["batches_coded"] = coded_batch_block(a, dec, blob)
         if a.affine:
             row["affine"] = affine_rows(a, dec, up)
         res["sizes"][str(n)] = row
