@@ -1185,22 +1185,32 @@ def convert(img: torch.Tensor, dtype=None, layout=None) -> torch.Tensor:
 
 
 class _Picture(NamedTuple):
-    """What one launch sequence draws, derived once (_picture) from (header, view or None)."""
+    """What one launch sequence draws, derived once (_picture) from (header, view or None, the Decoder's affine_route)."""
     header: Dict[str, object]
     view: Optional[Union[View, Overview, Affine]]  # None: the whole picture at its own size, through the full decode's entry
     width: int
     height: int
     tx: int
     ty: int
+    route: str  # how it is first drawn: _FAST, _ROWS or _LISTS (_picture)
 
     @property
     def radius_clip(self) -> float:  # what the capacity-free ops of the fallback are given
         return self.header["radius_clip"] if self.view is None else self.view.radius_clip(self.header)
 
+_FAST, _ROWS, _LISTS = "fast", "rows", "lists"
 
-def _picture(h, view: Optional[View]) -> _Picture:
+
+def _picture(h, view, affine_route: Optional[str]) -> _Picture:
+    """The picture a Decoder whose affine_route is `affine_route` draws of (header, view or None).  How it is first drawn
+    is decided here and nowhere else: _LISTS (tile lists of any length, launches of its own: Decoder._launch_lists), _ROWS
+    (the fast path's whole-row draw of an affine view) or _FAST (the fast-path draw)."""
     w, hh = (h["width"], h["height"]) if view is None else (view.width, view.height)
-    return _Picture(h, view, w, hh, _tiles(w), _tiles(hh))
+    if isinstance(view, Affine):
+        route = _LISTS if affine_route == "lists" else _ROWS
+    else:
+        route = _LISTS if isinstance(view, Overview) else _FAST
+    return _Picture(h, view, w, hh, _tiles(w), _tiles(hh), route)
 
 
 BATCH_MAX = 64  # GI2D_BATCH_MAX: pictures per gi2d_codec_decode_batch call
@@ -1219,11 +1229,12 @@ def batch_shape(headers, views=None) -> Tuple[int, int]:
         raise ValueError(f"decode_batch: {len(views)} views for {len(headers)} streams (one entry per stream, or views=None)")
     size = None
     for k, (h, v) in enumerate(zip(headers, views)):
-        p = _picture(h, _checked_view(v, h))
+        v = _checked_view(v, h)
+        w, hh = (h["width"], h["height"]) if v is None else (v.width, v.height)
         if size is None:
-            size = (p.height, p.width)
-        elif (p.height, p.width) != size:
-            raise ValueError(f"decode_batch: picture {k} is {p.width}x{p.height}, picture 0 is {size[1]}x{size[0]}: every "
+            size = (hh, w)
+        elif (hh, w) != size:
+            raise ValueError(f"decode_batch: picture {k} is {w}x{hh}, picture 0 is {size[1]}x{size[0]}: every "
                              "picture of a batch has one size (give the others a codec.View)")
     return size
 
@@ -1284,6 +1295,16 @@ def _headers(streams) -> List[Dict[str, object]]:
     return [s.header if isinstance(s, DeviceStream) else _parse(s) for s in streams]
 
 
+_CSide = C.c_float * 16  # scale and beta of the eight fields, as the C entries take them
+
+
+def _stream_args(h, payload: torch.Tensor) -> tuple:
+    """The ten arguments every decode entry begins with: kind, N, the four field widths, the side information, the
+    coding-0 payload with its length, clip_coe."""
+    return (h["kind"], h["num_points"], *h["bits"], _CSide(*h["side"]), C.c_void_p(payload.data_ptr()),
+            h["fixed_payload_bytes"], h["clip_coe"])
+
+
 class Decoder:
     """Decodes streams on one device.  Payload staging, the fast-path workspace and the status words are kept between
     calls and regrown only when a stream needs more; nothing of one stream survives into the next (the workspace is
@@ -1318,7 +1339,6 @@ class Decoder:
         # affine views: None = the fast path's whole-row draw, drawn again through the tile lists of the capacity-free ops
         # where a row overflowed; "rows" / "lists" pin one of the two (tests, tools/decode_time.py): "rows" raises
         # RuntimeError instead of drawing again, "lists" never touches the fast path
-        self._lists_types: Tuple[type, ...] = (Overview,)  # views first drawn through tile lists (affine_route's setter)
         self.affine_route = None
         self.overflowed: List[int] = []  # rows of the last call whose status word 1 was set at the call's host wait
         self.redrawn: List[int] = []     # rows of the last call that were drawn again
@@ -1333,14 +1353,11 @@ class Decoder:
         if route not in (None, "rows", "lists"):
             raise ValueError(f"affine_route {route!r}: None, 'rows' or 'lists'")
         self._affine_route = route
-        # the views whose pictures are first drawn through tile lists of any length (launches of their own,
-        # _launch_overview): what the per-picture loops of the host driver test a view against
-        self._lists_types = (Overview, Affine) if route == "lists" else (Overview,)
 
     def _reserve_workspace(self, pictures: Sequence[_Picture]) -> None:
         size = _lib.load().gi2d_fast_workspace_bytes
         need = max([int(size(p.header["num_points"], p.tx, p.ty)) for p in pictures
-                    if not isinstance(p.view, self._lists_types)], default=0)
+                    if p.route != _LISTS], default=0)
         if self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
 
@@ -1350,10 +1367,9 @@ class Decoder:
         return max(1, int(self.overview_capacity)) if self.overview_capacity is not None else max(4 * n, self._overview_m)
 
     def _reserve_overview(self, pictures: Sequence[_Picture], capacity: Optional[int] = None, every: bool = False) -> None:
-        """The buffers of the pictures among `pictures` that are drawn through tile lists (_lists_types; every: all of
-        them), each at least as large as the largest of them needs."""
-        lists_types = self._lists_types
-        ovs = [p for p in pictures if every or isinstance(p.view, lists_types)]
+        """The buffers of the pictures among `pictures` that are drawn through tile lists (_LISTS; every: all of them),
+        each at least as large as the largest of them needs."""
+        ovs = [p for p in pictures if every or p.route == _LISTS]
         if not ovs:
             return
         n = max(p.header["num_points"] for p in ovs)
@@ -1496,49 +1512,37 @@ class Decoder:
         """Workspace reset + decode/bin + gi2d_codec_draw (whose epilogue is the clamp, the conversion and the layout) of
         a coding-0 payload on the current stream, at the picture's size, with the status row at `status`; no host sync
         and no allocation.  aux: five tensors that take the decode kernel's per-gaussian outputs."""
-        h, view, w, hh, tx, ty = pic
-        if isinstance(view, self._lists_types):
-            return self._launch_overview(pic, payload, status, out, fmt, aux)
+        h, view, w, hh, tx, ty, route = pic
+        if route == _LISTS:
+            return self._launch_lists(pic, payload, status, out, fmt, aux)
         n = h["num_points"]
-        b = h["bits"]
-        side = (C.c_float * 16)(*h["side"])
         ws, nws = C.c_void_p(self._ws.data_ptr()), self._ws.numel()
         st = _stream(self.dev)
         a = [C.c_void_p(t.data_ptr()) for t in aux] if aux is not None else [None] * 5
         _lib.call("gi2d_fast_workspace_init", ws, nws, n, tx, ty, st)
-        if isinstance(view, Affine):
-            _lib.call("gi2d_codec_decode_bin_affine", h["kind"], n, b[0], b[1], b[2], b[3], side,
-                      C.c_void_p(payload.data_ptr()), h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"],
-                      view.x0, view.y0, *view.inverse, *view.prefilter, hh, w, tx, ty, view.radius_clip(h), a[0], a[1],
-                      a[2], a[3], a[4], ws, nws, status, st)
-            _lib.call("gi2d_codec_draw_rows", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws, status,
-                      *fmt.ids, C.c_void_p(out.data_ptr()), st)
-            return
-        if view is None:
-            _lib.call("gi2d_codec_decode_bin", h["kind"], n, b[0], b[1], b[2], b[3], side, C.c_void_p(payload.data_ptr()),
-                      h["fixed_payload_bytes"], h["clip_coe"], hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3],
-                      a[4], ws, nws, status, st)
-        else:
-            _lib.call("gi2d_codec_decode_bin_view", h["kind"], n, b[0], b[1], b[2], b[3], side,
-                      C.c_void_p(payload.data_ptr()), h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"],
-                      view.x0, view.y0, view.scale, hh, w, tx, ty, h["radius_clip"], a[0], a[1], a[2], a[3], a[4], ws, nws,
+        if route == _ROWS:
+            _lib.call("gi2d_codec_decode_bin_affine", *_stream_args(h, payload), h["height"], h["width"], view.x0, view.y0,
+                      *view.inverse, *view.prefilter, hh, w, tx, ty, pic.radius_clip, *a, ws, nws, status, st)
+        elif view is None:
+            _lib.call("gi2d_codec_decode_bin", *_stream_args(h, payload), hh, w, tx, ty, h["radius_clip"], *a, ws, nws,
                       status, st)
-        _lib.call("gi2d_codec_draw", n, tx, ty, w, hh, C.c_void_p(self._background.data_ptr()), ws, nws, status,
-                  *fmt.ids, C.c_void_p(out.data_ptr()), st)
+        else:
+            _lib.call("gi2d_codec_decode_bin_view", *_stream_args(h, payload), h["height"], h["width"], view.x0, view.y0,
+                      view.scale, hh, w, tx, ty, h["radius_clip"], *a, ws, nws, status, st)
+        _lib.call("gi2d_codec_draw_rows" if route == _ROWS else "gi2d_codec_draw", n, tx, ty, w, hh,
+                  C.c_void_p(self._background.data_ptr()), ws, nws, status, *fmt.ids, C.c_void_p(out.data_ptr()), st)
 
-    def _launch_overview(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, fmt: _Format,
-                         aux=None, capacity: Optional[int] = None) -> None:
-        """An overview -- or an affine view on its capacity-free route, with gi2d_codec_decode_affine as the first of the
-        three -- of a coding-0 payload on the current stream: gi2d_codec_decode_overview (record -> transformed,
-        prefiltered gaussian -> covariance projection), gi2d_bin_gaussians into lists of `capacity` entries (its status
-        {count, overflow} goes to words 0 and 1 of the row at `status`), gi2d_rasterize_forward_long_as (whole lists,
-        ones if the count is 0, ending in the clamp and the format's stores); no host sync and no allocation
-        (_reserve_overview has been called)."""
-        h, ov, w, hh, tx, ty = pic
+    def _launch_lists(self, pic: _Picture, payload: torch.Tensor, status: int, out: torch.Tensor, fmt: _Format,
+                      aux=None, capacity: Optional[int] = None) -> None:
+        """The lists route: an overview -- or an affine view, with gi2d_codec_decode_affine as the first of the three --
+        of a coding-0 payload on the current stream: gi2d_codec_decode_overview (record -> transformed, prefiltered
+        gaussian -> covariance projection), gi2d_bin_gaussians into lists of `capacity` entries (its status {count,
+        overflow} goes to words 0 and 1 of the row at `status`), gi2d_rasterize_forward_long_as (whole lists, ones if the
+        count is 0, ending in the clamp and the format's stores); no host sync and no allocation (_reserve_overview has
+        been called)."""
+        h, ov, w, hh, tx, ty, _ = pic
         n = h["num_points"]
-        b = h["bits"]
         cap = capacity if capacity is not None else self._overview_list_capacity(n)
-        side = (C.c_float * 16)(*h["side"])
         st = _stream(self.dev)
         o = self._ov
         geo = [C.c_void_p(t.data_ptr()) for t in
@@ -1546,18 +1550,25 @@ class Decoder:
         ids, bins = C.c_void_p(o["ids"].data_ptr()), C.c_void_p(o["bins"].data_ptr())
         assert o["ids"].numel() >= cap and o["bins"].numel() >= 2 * tx * ty
         if isinstance(ov, Affine):
-            _lib.call("gi2d_codec_decode_affine", h["kind"], n, b[0], b[1], b[2], b[3], side, C.c_void_p(payload.data_ptr()),
-                      h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"], ov.x0, ov.y0, *ov.inverse,
-                      *ov.prefilter, hh, w, tx, ty, ov.radius_clip(h), geo[0], geo[1], geo[2], geo[3], geo[4], st)
+            _lib.call("gi2d_codec_decode_affine", *_stream_args(h, payload), h["height"], h["width"], ov.x0, ov.y0,
+                      *ov.inverse, *ov.prefilter, hh, w, tx, ty, ov.radius_clip(h), *geo, st)
         else:
-            _lib.call("gi2d_codec_decode_overview", h["kind"], n, b[0], b[1], b[2], b[3], side,
-                      C.c_void_p(payload.data_ptr()), h["fixed_payload_bytes"], h["clip_coe"], h["height"], h["width"], ov.x0,
-                      ov.y0, ov.scale, ov.prefilter, hh, w, tx, ty, h["radius_clip"], geo[0], geo[1], geo[2], geo[3], geo[4],
-                      st)
+            _lib.call("gi2d_codec_decode_overview", *_stream_args(h, payload), h["height"], h["width"], ov.x0, ov.y0,
+                      ov.scale, ov.prefilter, hh, w, tx, ty, h["radius_clip"], *geo, st)
         _lib.call("gi2d_bin_gaussians", n, cap, geo[0], geo[1], tx, ty, ov.radius_clip(h), ids, bins, status,
                   C.c_void_p(o["binws"].data_ptr()), o["binws"].numel(), st)
         _lib.call("gi2d_rasterize_forward_long_as", n, cap, tx, ty, w, hh, ids, bins, tx * ty, geo[0], geo[2], geo[4],
                   None, status, *fmt.ids, C.c_void_p(out.data_ptr()), st)
+
+    def _lists_again(self, pic: _Picture, payload: torch.Tensor, status: int, m: int, overflow: int, out: torch.Tensor,
+                     fmt: _Format, aux=None) -> bool:
+        """What follows a _launch_lists once its status row (m, overflow) is on the host: the count is remembered, and
+        lists that were cut at the capacity are drawn again with room for all m -> whether they were."""
+        self._overview_m = max(self._overview_m, m)
+        if overflow:
+            self._reserve_overview([pic], m, every=True)
+            self._launch_lists(pic, payload, status, out, fmt, aux, m)
+        return bool(overflow)
 
     def _out(self, pic: _Picture, out: Optional[torch.Tensor], fmt: _Format) -> torch.Tensor:
         shape = fmt.shape(pic.height, pic.width)
@@ -1636,42 +1647,32 @@ class Decoder:
         status = self._status[:len(pictures), 0:5].tolist()  # M, overflow, .., .., rANS
         for row in coded:
             self._check_expanded(status[row][4])
-        redrawn, overflowed, lists_types = [], [], self._lists_types
+        redrawn, overflowed = [], []
         for row, (m, overflow, _, _, _) in enumerate(status):
             pic = pictures[row]
-            if isinstance(pic.view, lists_types):
-                self._overview_m = max(self._overview_m, m)
-                if overflow:  # the lists were cut at the capacity: the same picture again with room for all m
+            if pic.route != _LISTS and not overflow:
+                continue  # (nearly every picture of nearly every call)
+            lists = (pic, fixed[row], row0 + _STATUS_ROW * row)
+            if pic.route == _LISTS:
+                if self._lists_again(*lists, m, overflow, images[row], fmt, aux):
                     overflowed.append(row)
-                    self._reserve_overview([pic], m, every=True)
-                    self._launch_overview(pic, fixed[row], row0 + _STATUS_ROW * row, images[row], fmt, aux, m)
                     redrawn.append(row)
             elif overflow:
                 overflowed.append(row)
-                if isinstance(pic.view, Affine):  # a tile row lost candidates: whole lists give the same sums
+                if pic.route == _ROWS:  # a tile row lost candidates: whole lists give the same sums.  They start at the
+                    # capacity an overview's would; a host wait of its own per attempt: this is the rare path
                     if self.affine_route == "rows":
                         raise RuntimeError("affine_route = 'rows': a tile row of the affine view overflowed (more than 1024 "
                                            "candidates in one tile); the default route draws such a picture again")
-                    self._affine_lists(pic, fixed[row], row0 + _STATUS_ROW * row, row, images[row], fmt, aux)
+                    self._reserve_overview([pic], every=True)
+                    self._launch_lists(*lists, images[row], fmt, aux)
+                    self._lists_again(*lists, *self._status[row, 0:2].tolist(), images[row], fmt, aux)
                     redrawn.append(row)
                 elif not geometry:
                     self._exact(pic, fixed[row], images[row], fmt)
                     redrawn.append(row)
         self.overflowed, self.redrawn = overflowed, redrawn
         return redrawn
-
-    def _affine_lists(self, pic: _Picture, fixed: torch.Tensor, status: int, row: int, out: torch.Tensor, fmt: _Format,
-                      aux=None) -> None:
-        """An affine view whose fast-path draw overflowed, through the capacity-free route (_launch_overview): its lists
-        start at the capacity an overview's would, and a picture that needs more is drawn once more with room for the
-        count its status row then reports -- a host wait per attempt: this is the rare path."""
-        self._reserve_overview([pic], every=True)
-        self._launch_overview(pic, fixed, status, out, fmt, aux)
-        m, overflow = self._status[row, 0:2].tolist()
-        self._overview_m = max(self._overview_m, m)
-        if overflow:
-            self._reserve_overview([pic], m, every=True)
-            self._launch_overview(pic, fixed, status, out, fmt, aux, m)
 
     def _run(self, streams, views, fmt: _Format, outs: Optional[Sequence[torch.Tensor]] = None, views_only: bool = False,
              geometry: bool = False):
@@ -1680,7 +1681,8 @@ class Decoder:
         call order.  Everything is parsed and checked before anything touches the device.  geometry (one stream, one
         picture): the per-gaussian outputs of the decode kernel are kept."""
         headers = _headers(streams)
-        pictures = [_picture(h, _checked_view(v, h, views_only)) for h, vs in zip(headers, views) for v in vs]
+        pictures = [_picture(h, _checked_view(v, h, views_only), self._affine_route)
+                    for h, vs in zip(headers, views) for v in vs]
         if outs is not None and len(outs) != len(pictures):
             raise ValueError("decode_views: one output tensor per view" if views_only else
                              "decode_many: one output tensor per stream")
@@ -1699,12 +1701,12 @@ class Decoder:
     # ---------------------------------------------------------------------------------------------- batches
     def _batch_groups(self, pictures: Sequence[_Picture]):
         """The rows gi2d_codec_decode_batch draws together: runs of consecutive pictures that have no launches of their own
-        (_lists_types: overviews; a call writes its pictures one behind the other), at most BATCH_MAX each -> [(rows,
+        (the lists route: overviews; a call writes its pictures one behind the other), at most BATCH_MAX each -> [(rows,
         [workspace bytes of each])].  Affine pictures share the launches."""
         size = _lib.load().gi2d_codec_decode_workspace_bytes
-        groups, lists_types = [], self._lists_types
+        groups = []
         for row, p in enumerate(pictures):
-            if isinstance(p.view, lists_types):
+            if p.route == _LISTS:
                 continue
             if not groups or groups[-1][0][-1] != row - 1 or len(groups[-1][0]) == BATCH_MAX:
                 groups.append(([], []))
@@ -1719,20 +1721,18 @@ class Decoder:
         maps = None  # struct gi2d_codec_affine per picture, made when the first Affine is met
         ws = self._batch_ws.data_ptr()
         for d, row, nws in zip(arr, rows, sizes):
-            h, view, _, _, _, _ = pictures[row]
-            b = h["bits"]
-            d.kind, d.num_points, d.xy_bits, d.p0_bits, d.p1_bits, d.color_bits = h["kind"], h["num_points"], *b
-            d.side = (C.c_float * 16)(*h["side"])
+            h, view, _, _, _, _, route = pictures[row]
+            d.kind, d.num_points, d.xy_bits, d.p0_bits, d.p1_bits, d.color_bits = h["kind"], h["num_points"], *h["bits"]
+            d.side = _CSide(*h["side"])
             d.payload, d.payload_bytes = fixed[row].data_ptr(), h["fixed_payload_bytes"]
             d.clip_coe, d.img_height, d.img_width = h["clip_coe"], h["height"], h["width"]
-            if view is not None:
-                if view.__class__ is View:
-                    d.view, d.x0, d.y0, d.scale = 1, view.x0, view.y0, view.scale
-                else:
-                    maps = (_CAffine * len(rows))() if maps is None else maps
-                    a = maps[row - rows[0]]
-                    d.view, a.x0, a.y0 = 2, view.x0, view.y0
-                    a.b, a.prefilter = (C.c_float * 4)(*view.inverse), (C.c_float * 3)(*view.prefilter)
+            if route == _ROWS:
+                maps = (_CAffine * len(rows))() if maps is None else maps
+                a = maps[row - rows[0]]
+                d.view, a.x0, a.y0 = 2, view.x0, view.y0
+                a.b, a.prefilter = (C.c_float * 4)(*view.inverse), (C.c_float * 3)(*view.prefilter)
+            elif view is not None:
+                d.view, d.x0, d.y0, d.scale = 1, view.x0, view.y0, view.scale
             d.radius_clip = pictures[row].radius_clip
             d.workspace, d.workspace_bytes, d.status = ws, nws, row0 + _STATUS_ROW * row
             ws += nws
@@ -1755,7 +1755,7 @@ class Decoder:
         headers = _headers(streams)
         views = [None] * len(headers) if views is None else list(views)
         height, width = batch_shape(headers, views)
-        pictures = [_picture(h, v) for h, v in zip(headers, views)]
+        pictures = [_picture(h, v, self._affine_route) for h, v in zip(headers, views)]
         fmt = _format(dtype, layout)
         shape = (len(pictures),) + tuple(fmt.shape(height, width))
         if out is not None:
@@ -1771,10 +1771,9 @@ class Decoder:
             if out is None:
                 out = torch.empty(shape, dtype=fmt.dtype, device=self.dev)
             fixed, coded, row0 = self._begin(streams, headers, pictures, [1] * len(pictures))
-            lists_types = self._lists_types
             for row, pic in enumerate(pictures):
-                if isinstance(pic.view, lists_types):
-                    self._launch_overview(pic, fixed[row], row0 + _STATUS_ROW * row, out[row], fmt)
+                if pic.route == _LISTS:
+                    self._launch_lists(pic, fixed[row], row0 + _STATUS_ROW * row, out[row], fmt)
             for rows, sizes in groups:
                 self._launch_batch(rows, sizes, pictures, fixed, row0, out, fmt)
             self.batch_redrawn = self._finish(pictures, fixed, coded, row0, out, fmt)
@@ -1835,8 +1834,8 @@ def decode(blob, device: Union[str, torch.device] = "cuda:0", out: Optional[torc
     view = _checked_view(view, h)  # a malformed stream, view, format or `out` is refused before a device is even touched
     fmt = _format(dtype, layout)
     if out is not None:
-        pic = _picture(h, view)
-        _check_out(out, fmt.shape(pic.height, pic.width), fmt.dtype)
+        w, hh = (h["width"], h["height"]) if view is None else (view.width, view.height)
+        _check_out(out, fmt.shape(hh, w), fmt.dtype)
     return _decoder(device).decode(blob, out=out, view=view, dtype=dtype, layout=layout)
 
 

@@ -11,10 +11,11 @@
 //   view        the same launch with a window on the fitted function: between dequantisation and
 //               projection every gaussian is moved and scaled into the window's pixel grid (view_transform), and the
 //               projection, the binning step and the tile pass run at the WINDOW's size.  A template flag of the
-//               same kernel: the full decode's instantiations keep their instructions.
+//               same kernel.
 //   affine      the same launch again with an affine view (DESIGN.md 3.8 "Affine views"): affine_transform in place of
-//               view_transform, the covariance projection for either kind; gi2d_codec_draw_rows draws it.  And the
-//               per-gaussian kernel without a workspace, for the capacity-free route (gi2d_codec_decode_affine).
+//               view_transform, the covariance projection for either kind; gi2d_codec_draw_rows draws it.  Its
+//               capacity-free route (gi2d_codec_decode_affine) launches the per-gaussian kernel the overviews use
+//               (gi2d_codec_core.h::codec_decode_lists_kernel).
 //
 // Nothing here is read through a pointer computed from stream CONTENT: record positions follow from (N, R) alone, and
 // every load index is clamped to the dwords the entry has checked the payload to hold.
@@ -65,8 +66,7 @@ __global__ __launch_bounds__(GI2D_CODEC_PACK_BLOCK) void codec_pack_kernel(
 // ---------------------------------------------------------------------------------------------------- decode + bin
 // (CodecOut, CodecView, view_transform and the per-gaussian body: gi2d_codec_core.h, shared with the batched decode)
 // img_w / img_h / tiles / radius_clip: those of the picture that is drawn (for a view: the window's size and the
-// header's radius_clip * scale, so that what the full decode drops as too small stays dropped).  VIEW = false never reads
-// `vw`: the full decode's instantiations have the instructions they had before there were views.  FORM: GI2D_CODEC_FORM_*.
+// header's radius_clip * scale, so that what the full decode drops as too small stays dropped).  FORM: GI2D_CODEC_FORM_*.
 template <int KIND, int FORM>
 __global__ __launch_bounds__(256) void codec_decode_bin_kernel(
     int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
@@ -74,26 +74,6 @@ __global__ __launch_bounds__(256) void codec_decode_bin_kernel(
     CodecAffine af) {
     codec_decode_bin_one<KIND, FORM>(blockIdx.x * blockDim.x + threadIdx.x, n, lay, side, payload, last_dword, clip_coe, img_w,
                                      img_h, tiles_x, tiles_y, radius_clip, out, bt, vw, af);
-}
-
-// The affine view's per-gaussian kernel of the capacity-free route: what codec_decode_bin_one<KIND, AFFINE> computes of a
-// gaussian, written to the five arrays gi2d_bin_gaussians and gi2d_rasterize_forward_long_as consume; no workspace.
-template <int KIND>
-__global__ __launch_bounds__(256) void codec_decode_affine_kernel(
-    int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
-    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, CodecOut out, CodecAffine af) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    float v[GI2D_CODEC_FIELDS];
-    codec_values<KIND>(g, lay, side, payload, last_dword, v);
-    affine_transform<KIND>(v, af);
-    const ProjOut o = project_values<kCovariance>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h,
-                                                  tiles_x, tiles_y, radius_clip);
-    out.xys[g] = o.xy;
-    out.radii[g] = o.radius;
-    out.conics[3 * g] = o.k0, out.conics[3 * g + 1] = o.k1, out.conics[3 * g + 2] = o.k2;
-    out.num_tiles_hit[g] = o.tiles_hit;
-    out.colors[3 * g] = v[5], out.colors[3 * g + 1] = v[6], out.colors[3 * g + 2] = v[7];
 }
 
 }  // namespace gi2d
@@ -113,13 +93,13 @@ static int codec_decode_launch(const char *what, const CodecView *view, const Co
         return rc;
     };
     CodecLayout lay;
-    if (!codec_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
-    if (n < 0 || tiles_x < 0 || tiles_y < 0) return fail("negative size", GI2D_ERR_INVALID_ARGUMENT);
-    const long long need = codec_dwords(n, lay.record_bits);
-    if (payload_bytes < (size_t)need * 4)
-        return fail("payload shorter than 4 * ceil(N * R / 32) bytes", GI2D_ERR_INVALID_ARGUMENT);
-    if (!side_host || !status || !ws || (n > 0 && (!payload || ((uintptr_t)payload & 3))))
-        return fail("null or misaligned pointer", GI2D_ERR_INVALID_ARGUMENT);
+    CodecSide side;
+    long long last;
+    if (const int rc = codec_stream_checked(what, kind, n, xy_bits, p0_bits, p1_bits, color_bits, side_host, payload,
+                                            payload_bytes, lay, side, last))
+        return rc;
+    if (tiles_x < 0 || tiles_y < 0) return fail("negative size", GI2D_ERR_INVALID_ARGUMENT);
+    if (!status || !ws) return fail("null or misaligned pointer", GI2D_ERR_INVALID_ARGUMENT);
     if ((long long)tiles_x * GI2D_TILE < (long long)w_ || (long long)tiles_y * GI2D_TILE < (long long)h)
         return fail("tile grid does not cover the image", GI2D_ERR_INVALID_ARGUMENT);
     if ((long long)tiles_x * tiles_y * GI2D_FAST_LROW > 0x7fffffffLL || (long long)n * GI2D_FAST_S > 0x7fffffffLL ||
@@ -127,8 +107,6 @@ static int codec_decode_launch(const char *what, const CodecView *view, const Co
         return fail("problem too large for 32-bit slot indices", GI2D_ERR_UNSUPPORTED);
     if (ws_bytes < carve_fast(nullptr, n, tiles_x * tiles_y).bytes)
         return fail("workspace too small", GI2D_ERR_WORKSPACE_TOO_SMALL);
-    CodecSide side;
-    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) side.scale[k] = side_host[2 * k], side.beta[k] = side_host[2 * k + 1];
     FastWs w = carve_fast(ws, n, tiles_x * tiles_y);
     BinTarget bt;
     bt.colors = bt.opacities = nullptr;  // colour comes from the record, opacity is 1
@@ -139,24 +117,17 @@ static int codec_decode_launch(const char *what, const CodecView *view, const Co
     const CodecOut out{(float2 *)xys, radii, conics, num_tiles_hit, colors};
     const int bs = per_gaussian_block(n);
     const dim3 grid((n + bs - 1) / bs > 0 ? (n + bs - 1) / bs : 1), block(bs);
-    const long long last = need > 0 ? need - 1 : 0;
     const CodecView vw = view ? *view : CodecView{0.f, 0.f, 1.f};
     const CodecAffine af = affine ? *affine : CodecAffine{0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
-#define GI2D_CODEC_DECODE(KIND, FORM)                                                                                  \
-    hipLaunchKernelGGL((codec_decode_bin_kernel<KIND, FORM>), grid, block, 0, (hipStream_t)st, n, lay, side,            \
-                       (const uint32_t *)payload, last, clip_coe, (float)w_, (float)h, tiles_x, tiles_y, radius_clip,  \
-                       out, bt, vw, af)
-    if (affine) {
-        if (kind == kCovariance) GI2D_CODEC_DECODE(kCovariance, GI2D_CODEC_FORM_AFFINE);
-        else GI2D_CODEC_DECODE(kScaleRot, GI2D_CODEC_FORM_AFFINE);
-    } else if (view) {
-        if (kind == kCovariance) GI2D_CODEC_DECODE(kCovariance, GI2D_CODEC_FORM_VIEW);
-        else GI2D_CODEC_DECODE(kScaleRot, GI2D_CODEC_FORM_VIEW);
-    } else {
-        if (kind == kCovariance) GI2D_CODEC_DECODE(kCovariance, GI2D_CODEC_FORM_FULL);
-        else GI2D_CODEC_DECODE(kScaleRot, GI2D_CODEC_FORM_FULL);
-    }
-#undef GI2D_CODEC_DECODE
+    static const decltype(&codec_decode_bin_kernel<kCovariance, GI2D_CODEC_FORM_FULL>) kernels[2][3] = {
+        {codec_decode_bin_kernel<kCovariance, GI2D_CODEC_FORM_FULL>, codec_decode_bin_kernel<kCovariance, GI2D_CODEC_FORM_VIEW>,
+         codec_decode_bin_kernel<kCovariance, GI2D_CODEC_FORM_AFFINE>},
+        {codec_decode_bin_kernel<kScaleRot, GI2D_CODEC_FORM_FULL>, codec_decode_bin_kernel<kScaleRot, GI2D_CODEC_FORM_VIEW>,
+         codec_decode_bin_kernel<kScaleRot, GI2D_CODEC_FORM_AFFINE>}};
+    const int form = affine ? GI2D_CODEC_FORM_AFFINE : view ? GI2D_CODEC_FORM_VIEW : GI2D_CODEC_FORM_FULL;
+    hipLaunchKernelGGL(kernels[kind == kScaleRot][form], grid, block, 0, (hipStream_t)st, n, lay, side,
+                       (const uint32_t *)payload, last, clip_coe, (float)w_, (float)h, tiles_x, tiles_y, radius_clip, out, bt,
+                       vw, af);
     return check_launch(what);
 }
 
@@ -257,29 +228,9 @@ int gi2d_codec_decode_affine(int kind, int n, int xy_bits, int p0_bits, int p1_b
     const CodecAffine af{x0, y0, b00, b01, b10, b11, pxx, pxy, pyy};
     if (const char *why = codec_affine_refused(af, out_h, out_w, h, w_)) return fail(why);
     if (!std::isfinite(radius_clip)) return fail("radius_clip must be finite");
-    CodecLayout lay;
-    if (!codec_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
-    if (n < 0 || tiles_x < 0 || tiles_y < 0) return fail("negative size");
-    const long long need = codec_dwords(n, lay.record_bits);
-    if (payload_bytes < (size_t)need * 4) return fail("payload shorter than 4 * ceil(N * R / 32) bytes");
-    if (!side_host || (n > 0 && (!payload || ((uintptr_t)payload & 3) || !xys || !radii || !conics || !num_tiles_hit || !colors)))
-        return fail("null or misaligned pointer");
-    if ((long long)tiles_x * GI2D_TILE < (long long)out_w || (long long)tiles_y * GI2D_TILE < (long long)out_h)
-        return fail("tile grid does not cover the image");
-    if (n == 0) return GI2D_OK;
-    CodecSide side;
-    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) side.scale[k] = side_host[2 * k], side.beta[k] = side_host[2 * k + 1];
-    const CodecOut out{(float2 *)xys, radii, conics, num_tiles_hit, colors};
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (kind == kCovariance)
-        hipLaunchKernelGGL(codec_decode_affine_kernel<kCovariance>, grid, block, 0, (hipStream_t)st, n, lay, side,
-                           (const uint32_t *)payload, need - 1, clip_coe, (float)out_w, (float)out_h, tiles_x, tiles_y,
-                           radius_clip, out, af);
-    else
-        hipLaunchKernelGGL(codec_decode_affine_kernel<kScaleRot>, grid, block, 0, (hipStream_t)st, n, lay, side,
-                           (const uint32_t *)payload, need - 1, clip_coe, (float)out_w, (float)out_h, tiles_x, tiles_y,
-                           radius_clip, out, af);
-    return check_launch(what);
+    return codec_decode_lists_launch(what, af, kind, n, xy_bits, p0_bits, p1_bits, color_bits, side_host, payload,
+                                     payload_bytes, clip_coe, out_h, out_w, tiles_x, tiles_y, radius_clip, xys, radii,
+                                     conics, num_tiles_hit, colors, st);
 }
 
 }  // extern "C"

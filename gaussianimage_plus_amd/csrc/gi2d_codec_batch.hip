@@ -9,10 +9,11 @@
 //   decode    gi2d_codec_core.h::codec_decode_bin_one, 256 gaussians per workgroup; kind and view are per picture: a
 //             workgroup-uniform switch over the four instantiations the single-picture launch chooses from on the host
 //   draw      gi2d_codec_core.h::codec_draw_tile on the picture's own lists, records, status row and slice of `out`
-//   affine    a call with an affine picture among its K (gi2d_codec_decode_batch_affine) launches the second form of the
-//             two kernels: the decode switch has the two affine instantiations as well, and the draw picks per picture
-//             between codec_draw_tile and codec_draw_tile_rows (one LDS block serves either).  The maps travel in a table
-//             of their own behind the argument blocks, so a call without one runs exactly the launches it ran before.
+//   affine    a call with an affine picture among its K (gi2d_codec_decode_batch_affine) launches the AFFINE = true
+//             instantiation of the two kernels: the decode switch has the two affine forms as well, and the draw picks per
+//             picture between codec_draw_tile and codec_draw_tile_rows (one LDS block serves either).  The maps travel in
+//             a table of their own behind the argument blocks; the AFFINE = false instantiations, which a call without an
+//             affine picture launches, neither read that table nor reserve the whole-row draw's LDS.
 //
 // A workgroup finds its picture with batch_find and touches that picture's workspace and status row only, so every
 // access rule of gi2d_fast_internal.h holds per workspace exactly as in the single-picture launches, and nothing is
@@ -84,80 +85,63 @@ __global__ __launch_bounds__(256) void codec_reset_batched_kernel(const CodecBat
     if (i < p.n) p.bt.prev_box[i] = no_box();
 }
 
+template <bool AFFINE>
 __global__ __launch_bounds__(256) void codec_decode_bin_batched_kernel(const CodecBatchHead *__restrict__ head,
                                                                        const CodecBatchPicture *__restrict__ pics,
+                                                                       const CodecAffine *__restrict__ affines,
                                                                        int k_pictures, float img_w, float img_h,
                                                                        int tiles_x, int tiles_y) {
     const int k = batch_find(head->pg_start, k_pictures, (int)blockIdx.x);
     const CodecBatchPicture &p = pics[k];
     const int g = ((int)blockIdx.x - head->pg_start[k]) * 256 + (int)threadIdx.x;
     const CodecOut none{nullptr, nullptr, nullptr, nullptr, nullptr};
-#define GI2D_DECODE_ONE(KIND, VIEW)                                                                                     \
-    codec_decode_bin_one<KIND, VIEW>(g, p.n, p.lay, p.side, p.payload, p.last_dword, p.clip_coe, img_w, img_h, tiles_x, \
+#define GI2D_DECODE_ONE(KIND, FORM)                                                                                     \
+    codec_decode_bin_one<KIND, FORM>(g, p.n, p.lay, p.side, p.payload, p.last_dword, p.clip_coe, img_w, img_h, tiles_x, \
                                      tiles_y, p.radius_clip, none, p.bt, p.vw, af)
-    const CodecAffine af{};
-    switch (p.form) {  // workgroup-uniform
-        case 0: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_FULL); break;
-        case 1: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_VIEW); break;
-        case 2: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_FULL); break;
-        default: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_VIEW); break;
-    }
-}
-
-// ... of a call with affine pictures: two more forms
-__global__ __launch_bounds__(256) void codec_decode_bin_batched_affine_kernel(const CodecBatchHead *__restrict__ head,
-                                                                              const CodecBatchPicture *__restrict__ pics,
-                                                                              const CodecAffine *__restrict__ affines,
-                                                                              int k_pictures, float img_w, float img_h,
-                                                                              int tiles_x, int tiles_y) {
-    const int k = batch_find(head->pg_start, k_pictures, (int)blockIdx.x);
-    const CodecBatchPicture &p = pics[k];
-    const int g = ((int)blockIdx.x - head->pg_start[k]) * 256 + (int)threadIdx.x;
-    const CodecOut none{nullptr, nullptr, nullptr, nullptr, nullptr};
-    const CodecAffine af = affines[k];
-    switch (p.form) {  // workgroup-uniform
-        case 0: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_FULL); break;
-        case 1: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_VIEW); break;
-        case 2: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_FULL); break;
-        case 3: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_VIEW); break;
-        case 4: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_AFFINE); break;
-        default: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_AFFINE); break;
+    CodecAffine af{};
+    if constexpr (AFFINE) af = affines[k];
+    if constexpr (AFFINE) {  // (a case label cannot stand inside an `if constexpr` of its switch: two switches)
+        switch (p.form) {    // workgroup-uniform
+            case 0: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_FULL); break;
+            case 1: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_VIEW); break;
+            case 2: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_FULL); break;
+            case 3: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_VIEW); break;
+            case 4: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_AFFINE); break;
+            default: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_AFFINE); break;
+        }
+    } else {
+        switch (p.form) {
+            case 0: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_FULL); break;
+            case 1: GI2D_DECODE_ONE(kCovariance, GI2D_CODEC_FORM_VIEW); break;
+            case 2: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_FULL); break;
+            default: GI2D_DECODE_ONE(kScaleRot, GI2D_CODEC_FORM_VIEW); break;
+        }
     }
 #undef GI2D_DECODE_ONE
 }
 
-template <int DTYPE, int LAYOUT>
+// AFFINE: the draw routine is the picture's (workgroup-uniform), and the LDS block is large enough for either
+template <bool AFFINE, int DTYPE, int LAYOUT>
 __global__ __launch_bounds__(256) void codec_draw_batched_kernel(const CodecBatchHead *__restrict__ head,
                                                                  const CodecBatchPicture *__restrict__ pics,
                                                                  int k_pictures, int tiles_x, int tiles_y, int img_w,
                                                                  int img_h, const float *__restrict__ background) {
-    __shared__ FwdLds sm;
-    __shared__ int grp[32];
-    const int k = batch_find(head->tile_start, k_pictures, (int)blockIdx.x);
-    const CodecBatchPicture &p = pics[k];
-    const int tile = (int)blockIdx.x - head->tile_start[k];
-    codec_draw_tile<DTYPE, LAYOUT>(sm, grp, tile, tile == 0, tiles_x, tiles_y, img_w, img_h, p.bt.recs, background,
-                                   p.bt.lists, p.tile_bins, nullptr, nullptr, p.bt.status, p.out);
-}
-
-// ... of a call with affine pictures: the draw routine is the picture's (workgroup-uniform); one LDS block serves either
-template <int DTYPE, int LAYOUT>
-__global__ __launch_bounds__(256) void codec_draw_batched_affine_kernel(const CodecBatchHead *__restrict__ head,
-                                                                        const CodecBatchPicture *__restrict__ pics,
-                                                                        int k_pictures, int tiles_x, int tiles_y, int img_w,
-                                                                        int img_h, const float *__restrict__ background) {
-    constexpr size_t LDS = sizeof(FwdLds) > sizeof(RowsLds) ? sizeof(FwdLds) : sizeof(RowsLds);
+    constexpr size_t LDS = AFFINE && sizeof(RowsLds) > sizeof(FwdLds) ? sizeof(RowsLds) : sizeof(FwdLds);
     __shared__ __align__(16) unsigned char lds[LDS];
     __shared__ int grp[32];
     const int k = batch_find(head->tile_start, k_pictures, (int)blockIdx.x);
     const CodecBatchPicture &p = pics[k];
     const int tile = (int)blockIdx.x - head->tile_start[k];
-    if (p.form >= 4)
-        codec_draw_tile_rows<DTYPE, LAYOUT>(*reinterpret_cast<RowsLds *>(lds), grp, tile, tile == 0, tiles_x, tiles_y, img_w,
-                                            img_h, p.bt.recs, background, p.bt.lists, p.tile_bins, p.bt.status, p.out);
-    else
-        codec_draw_tile<DTYPE, LAYOUT>(*reinterpret_cast<FwdLds *>(lds), grp, tile, tile == 0, tiles_x, tiles_y, img_w, img_h,
-                                       p.bt.recs, background, p.bt.lists, p.tile_bins, nullptr, nullptr, p.bt.status, p.out);
+    if constexpr (AFFINE) {
+        if (p.form >= 4) {
+            codec_draw_tile_rows<DTYPE, LAYOUT>(*reinterpret_cast<RowsLds *>(lds), grp, tile, tile == 0, tiles_x, tiles_y,
+                                                img_w, img_h, p.bt.recs, background, p.bt.lists, p.tile_bins, p.bt.status,
+                                                p.out);
+            return;
+        }
+    }
+    codec_draw_tile<DTYPE, LAYOUT>(*reinterpret_cast<FwdLds *>(lds), grp, tile, tile == 0, tiles_x, tiles_y, img_w, img_h,
+                                   p.bt.recs, background, p.bt.lists, p.tile_bins, nullptr, nullptr, p.bt.status, p.out);
 }
 
 static inline size_t pixel_plane_bytes(int dtype, int layout, size_t h, size_t w_) {
@@ -218,15 +202,12 @@ int gi2d_codec_decode_batch_affine(int num_pictures, const gi2d_codec_picture *p
         const gi2d_codec_picture &d = pictures[k];
         const std::string who = "picture " + std::to_string(k);
         CodecBatchPicture &p = pics[(size_t)k];
-        if (!codec_layout(("codec decode batch: " + who).c_str(), d.kind, d.xy_bits, d.p0_bits,
-                          d.p1_bits, d.color_bits, p.lay))
-            return GI2D_ERR_INVALID_ARGUMENT;
         const int n = d.num_points;
         if (n < 0 || (long long)n * GI2D_FAST_S > 0x7fffffffLL) return fail(who + ": population negative or too large");
-        const long long need = codec_dwords(n, p.lay.record_bits);
-        if (d.payload_bytes < (size_t)need * 4) return fail(who + ": payload shorter than 4 * ceil(N * R / 32) bytes");
-        if (!d.status || !d.workspace || (n > 0 && (!d.payload || ((uintptr_t)d.payload & 3))))
-            return fail(who + ": null or misaligned pointer");
+        if (const int rc = codec_stream_checked("codec decode batch: " + who, d.kind, n, d.xy_bits, d.p0_bits, d.p1_bits,
+                                                d.color_bits, d.side, d.payload, d.payload_bytes, p.lay, p.side, p.last_dword))
+            return rc;
+        if (!d.status || !d.workspace) return fail(who + ": null or misaligned pointer");
         if (d.view == 2) {
             if (!affines) return fail(who + ": an affine view (view = 2) needs gi2d_codec_decode_batch_affine and its maps");
             const gi2d_codec_affine &a = affines[k];
@@ -249,9 +230,7 @@ int gi2d_codec_decode_batch_affine(int num_pictures, const gi2d_codec_picture *p
             if ((a < b + w.bytes && b < a + pictures[j].workspace_bytes) || pictures[j].status == d.status)
                 return fail(who + ": shares its workspace or status row with picture " + std::to_string(j));
         }
-        for (int f = 0; f < GI2D_CODEC_FIELDS; ++f) p.side.scale[f] = d.side[2 * f], p.side.beta[f] = d.side[2 * f + 1];
         p.payload = (const uint32_t *)d.payload;
-        p.last_dword = need > 0 ? need - 1 : 0;
         p.n = n;
         p.form = d.view == 2 ? 4 + (d.kind == kScaleRot ? 1 : 0) : (d.kind == kScaleRot ? 2 : 0) + (d.view ? 1 : 0);
         p.clip_coe = d.clip_coe;
@@ -291,28 +270,16 @@ int gi2d_codec_decode_batch_affine(int num_pictures, const gi2d_codec_picture *p
     const int reset_blocks = (work + 255) / 256;
     hipLaunchKernelGGL(codec_reset_batched_kernel, dim3((unsigned)(reset_blocks * num_pictures)), dim3(256), 0, s,
                        (const CodecBatchPicture *)table.pic, reset_blocks, tiles);
-    if (any_affine)
-        hipLaunchKernelGGL(codec_decode_bin_batched_affine_kernel, dim3((unsigned)pg_total), dim3(256), 0, s,
-                           (const CodecBatchHead *)table.head, (const CodecBatchPicture *)table.pic,
-                           (const CodecAffine *)table.affine, num_pictures, (float)out_w, (float)out_h, tiles_x, tiles_y);
-    else
-        hipLaunchKernelGGL(codec_decode_bin_batched_kernel, dim3((unsigned)pg_total), dim3(256), 0, s,
-                           (const CodecBatchHead *)table.head, (const CodecBatchPicture *)table.pic, num_pictures,
-                           (float)out_w, (float)out_h, tiles_x, tiles_y);
-#define GI2D_DRAW_BATCH(D, L)                                                                                            \
-    hipLaunchKernelGGL((codec_draw_batched_kernel<D, L>), dim3((unsigned)(num_pictures * tiles)), dim3(256), 0, s,        \
-                       (const CodecBatchHead *)table.head, (const CodecBatchPicture *)table.pic, num_pictures, tiles_x,   \
-                       tiles_y, (int)out_w, (int)out_h, background)
-#define GI2D_DRAW_BATCH_AFFINE(D, L)                                                                                      \
-    hipLaunchKernelGGL((codec_draw_batched_affine_kernel<D, L>), dim3((unsigned)(num_pictures * tiles)), dim3(256), 0, s, \
-                       (const CodecBatchHead *)table.head, (const CodecBatchPicture *)table.pic, num_pictures, tiles_x,   \
-                       tiles_y, (int)out_w, (int)out_h, background)
-    if (any_affine) {
-        GI2D_FOR_FORMAT(dtype, layout, GI2D_DRAW_BATCH_AFFINE)
-    } else {
-        GI2D_FOR_FORMAT(dtype, layout, GI2D_DRAW_BATCH)
-    }
-#undef GI2D_DRAW_BATCH_AFFINE
+    const auto decode = any_affine ? codec_decode_bin_batched_kernel<true> : codec_decode_bin_batched_kernel<false>;
+    hipLaunchKernelGGL(decode, dim3((unsigned)pg_total), dim3(256), 0, s, (const CodecBatchHead *)table.head,
+                       (const CodecBatchPicture *)table.pic, (const CodecAffine *)table.affine, num_pictures, (float)out_w,
+                       (float)out_h, tiles_x, tiles_y);
+#define GI2D_DRAW_BATCH(D, L)                                                                                             \
+    hipLaunchKernelGGL((any_affine ? codec_draw_batched_kernel<true, D, L> : codec_draw_batched_kernel<false, D, L>),     \
+                       dim3((unsigned)(num_pictures * tiles)), dim3(256), 0, s, (const CodecBatchHead *)table.head,       \
+                       (const CodecBatchPicture *)table.pic, num_pictures, tiles_x, tiles_y, (int)out_w, (int)out_h,      \
+                       background)
+    GI2D_FOR_FORMAT(dtype, layout, GI2D_DRAW_BATCH)
 #undef GI2D_DRAW_BATCH
     return check_launch("codec decode batch");
 }

@@ -1,9 +1,13 @@
 // Device routines of the decoder that more than one kernel is made of: the decode/bin step of one
 // gaussian and the decode's tile pass of one tile.  The single-picture kernels (gi2d_codec.hip, gi2d_codec_draw.hip) take
 // their arguments from the launch, the batched ones (gi2d_codec_batch.hip) from a per-picture table; both call the
-// routines below, so a picture's bits do not depend on which of the two drew it.
+// routines below, so a picture's bits do not depend on which of the two drew it.  Also here, because more than one entry
+// needs them: the three view transforms, the per-gaussian kernel of the capacity-free route and the host checks of a
+// stream.
 #pragma once
 #include <cmath>
+#include <string>
+#include <type_traits>
 
 #include "gi2d_codec_layout.h"
 #include "gi2d_fast_internal.h"
@@ -44,6 +48,11 @@ __device__ __forceinline__ void view_transform(float (&v)[GI2D_CODEC_FIELDS], co
 
 #define GI2D_CODEC_VIEW_MAX_SCALE 64
 #define GI2D_CODEC_VIEW_MAX_TILES 16384
+// a view, an overview or an affine view of more tiles than that is refused (the workspace grows with the tiles)
+static inline bool codec_too_many_tiles(unsigned out_h, unsigned out_w) {
+    return ((unsigned long long)out_w + GI2D_TILE - 1) / GI2D_TILE * (((unsigned long long)out_h + GI2D_TILE - 1) / GI2D_TILE) >
+           (unsigned long long)GI2D_CODEC_VIEW_MAX_TILES;
+}
 // The conditions on a view, in double on the fp32 values the kernel receives: what is wrong with it, or
 // nullptr.  h, w_: the source picture's size.
 static inline const char *codec_view_refused(float x0, float y0, float scale, unsigned out_h, unsigned out_w, unsigned h,
@@ -54,10 +63,19 @@ static inline const char *codec_view_refused(float x0, float y0, float scale, un
     if (out_w < 1 || out_h < 1) return "empty output";
     if ((double)x0 + (double)out_w / (double)scale > (double)w_ || (double)y0 + (double)out_h / (double)scale > (double)h)
         return "the window reaches beyond the picture";
-    if (((unsigned long long)out_w + GI2D_TILE - 1) / GI2D_TILE * (((unsigned long long)out_h + GI2D_TILE - 1) / GI2D_TILE) >
-        (unsigned long long)GI2D_CODEC_VIEW_MAX_TILES)
-        return "more than 16384 tiles in one view (compose larger outputs from several views)";
+    if (codec_too_many_tiles(out_h, out_w)) return "more than 16384 tiles in one view (compose larger outputs from several views)";
     return nullptr;
+}
+
+// The covariance of a scale-rot gaussian, as project_values<kScaleRot> builds it (the same operations in the same order):
+// R = [[cos, sin], [-sin, cos]], M = R S, M M^T.
+__device__ __forceinline__ void scale_rot_covariance(float sx, float sy, float rot, float &cxx, float &cxy, float &cyy) {
+    const float c = cosf(rot), s = sinf(rot);
+    const M2 R{{c, -s, s, c}};
+    const M2 S{{sx, 0.f, 0.f, sy}};
+    const M2 M = mul(R, S);
+    const M2 T = mul(M, tr(M));
+    cxx = T.v[0], cxy = T.v[1], cyy = T.v[3];
 }
 
 // An AFFINE view (DESIGN.md 3.8 "Affine views"): output pixel (row i, column j) samples the fitted function, low-passed,
@@ -77,16 +95,10 @@ __device__ __forceinline__ void affine_transform(float (&v)[GI2D_CODEC_FIELDS], 
     v[0] = af.b00 * dx + af.b01 * dy;
     v[1] = af.b10 * dx + af.b11 * dy;
     float a, b, c;
-    if (KIND == kCovariance) {
+    if (KIND == kCovariance)
         a = v[2], b = v[3], c = v[4];
-    } else {  // project_values<kScaleRot>: R = [[cos, sin], [-sin, cos]], M = R S, M M^T (overview_transform at scale 1)
-        const float cs = cosf(v[4]), sn = sinf(v[4]);
-        const M2 R{{cs, -sn, sn, cs}};
-        const M2 S{{v[2], 0.f, 0.f, v[3]}};
-        const M2 M = mul(R, S);
-        const M2 T = mul(M, tr(M));
-        a = T.v[0], b = T.v[1], c = T.v[3];
-    }
+    else
+        scale_rot_covariance(v[2], v[3], v[4], a, b, c);
     const float n00 = af.b00 * a + af.b01 * b, n01 = af.b00 * b + af.b01 * c;
     const float n10 = af.b10 * a + af.b11 * b, n11 = af.b10 * b + af.b11 * c;
     float cxx = n00 * af.b00 + n01 * af.b01, cxy = n00 * af.b10 + n01 * af.b11, cyy = n10 * af.b10 + n11 * af.b11;
@@ -121,9 +133,7 @@ static inline const char *codec_affine_refused(const CodecAffine &a, unsigned ou
         a.pyy > GI2D_CODEC_AFFINE_MAX_PREFILTER)
         return "the prefilter must be positive semi-definite with variances in 0 .. 4 output pixels^2";
     if (out_w < 1 || out_h < 1) return "empty output";
-    if (((unsigned long long)out_w + GI2D_TILE - 1) / GI2D_TILE * (((unsigned long long)out_h + GI2D_TILE - 1) / GI2D_TILE) >
-        (unsigned long long)GI2D_CODEC_VIEW_MAX_TILES)
-        return "more than 16384 tiles in one view (compose larger outputs from several views)";
+    if (codec_too_many_tiles(out_h, out_w)) return "more than 16384 tiles in one view (compose larger outputs from several views)";
     const double m00 = b11 / d, m01 = -b01 / d, m10 = -b10 / d, m11 = b00 / d;
     const double slack = 1.0 / 1048576.0;
     for (int corner = 0; corner < 4; ++corner) {
@@ -135,6 +145,34 @@ static inline const char *codec_affine_refused(const CodecAffine &a, unsigned ou
             return "a corner pixel samples a position outside the picture's sample grid";
     }
     return nullptr;
+}
+
+// An OVERVIEW (DESIGN.md 3.8 "Reduced views"): the window of a view at a scale below 1, low-passed with an isotropic
+// gaussian of variance `prefilter` (output pixels^2).  v: the dequantised record -> centre, covariance and colour of the
+// gaussian in the overview's pixel grid, every step a separate fp32 operation in the order codec.overview_parameters
+// states.  The result is a covariance-model gaussian.  (Its conditions: gi2d_codec_overview.hip.)
+struct CodecOverview {
+    float x0, y0, scale, prefilter;
+};
+template <int KIND>
+__device__ __forceinline__ void overview_transform(float (&v)[GI2D_CODEC_FIELDS], const CodecOverview ov) {
+#pragma clang fp contract(off)
+    v[0] = (v[0] - ov.x0) * ov.scale;
+    v[1] = (v[1] - ov.y0) * ov.scale;
+    float cxx, cxy, cyy;
+    if (KIND == kCovariance) {
+        const float s2 = ov.scale * ov.scale;
+        cxx = v[2] * s2, cxy = v[3] * s2, cyy = v[4] * s2;
+    } else {
+        scale_rot_covariance(v[2] * ov.scale, v[3] * ov.scale, v[4], cxx, cxy, cyy);
+    }
+    const float det0 = cxx * cyy - cxy * cxy;
+    cxx = cxx + ov.prefilter;
+    cyy = cyy + ov.prefilter;
+    const float det1 = cxx * cyy - cxy * cxy;
+    const float g = sqrtf(fmaxf(det0, 0.f) / det1);
+    v[2] = cxx, v[3] = cxy, v[4] = cyy;
+    v[5] = v[5] * g, v[6] = v[6] * g, v[7] = v[7] * g;
 }
 
 // Record g of a payload -> the 8 dequantised values: dwords first, first + 1, ... (all requested before the first use;
@@ -183,29 +221,8 @@ __device__ __forceinline__ void codec_decode_bin_one(int g, int n, const CodecLa
     const BinRecs recs = recs_for_binning(bt.recs, g == 0);
     if (g >= n) return;
     const PrevBox old_box = bt.prev_box[g];
-    // the record: dwords first, first + 1, ... (all requested before the first use; `loads` is the same for every lane).
-    // Spelled out here, not through codec_values: the full decode's and the view's instantiations keep the instructions
-    // they had before there were affine views
-    const long long bit0 = (long long)g * lay.record_bits;
-    const long long first = bit0 >> 5;
-    uint32_t w[GI2D_CODEC_MAX_LOADS];
-#pragma unroll
-    for (int j = 0; j < GI2D_CODEC_MAX_LOADS; ++j) {
-        const long long d = first + j;
-        w[j] = j < lay.loads ? payload[d < last_dword ? d : last_dword] : 0u;
-    }
-    const uint32_t s0 = (uint32_t)bit0 & 31u;
-    uint32_t r[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], s0);
     float v[GI2D_CODEC_FIELDS];
-#pragma unroll
-    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
-        const float code = (float)((int)codec_take(r, lay.width[k]) + lay.qmin[k]);
-        // the variances of a covariance row are log-quantised (HybirdQuant), everything else is LSQ
-        v[k] = (KIND == kCovariance && (k == 2 || k == 4)) ? quant_dequant<GI2D_QUANT_LOG>(code, side.scale[k], side.beta[k])
-                                                          : quant_dequant<GI2D_QUANT_LSQ>(code, side.scale[k], side.beta[k]);
-    }
+    codec_values<KIND>(g, lay, side, payload, last_dword, v);
     if (FORM == GI2D_CODEC_FORM_VIEW) view_transform<KIND>(v, vw);
     if (FORM == GI2D_CODEC_FORM_AFFINE) affine_transform<KIND>(v, af);
     constexpr int PROJ = FORM == GI2D_CODEC_FORM_AFFINE ? (int)kCovariance : KIND;
@@ -217,6 +234,82 @@ __device__ __forceinline__ void codec_decode_bin_one(int g, int n, const CodecLa
     if (out.num_tiles_hit) out.num_tiles_hit[g] = o.tiles_hit;
     if (out.colors) out.colors[3 * g] = v[5], out.colors[3 * g + 1] = v[6], out.colors[3 * g + 2] = v[7];
     bin_projected(g, o, 1.f, v[5], v[6], v[7], tiles_x, tiles_y, radius_clip, old_box, bt.prev_box, bt.lists, recs);
+}
+
+// The per-gaussian kernel of the capacity-free route, for an overview or an affine view (VIEW: CodecOverview or
+// CodecAffine): record -> values -> the view's transform -> the COVARIANCE projection for either model kind, written to
+// the five arrays gi2d_bin_gaussians and gi2d_rasterize_forward_long_as consume; no workspace.  For an affine view that
+// is what codec_decode_bin_one<KIND, AFFINE> computes of a gaussian.
+template <int KIND, class VIEW>
+__global__ __launch_bounds__(256) void codec_decode_lists_kernel(
+    int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
+    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, CodecOut out, VIEW view) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    float v[GI2D_CODEC_FIELDS];
+    codec_values<KIND>(g, lay, side, payload, last_dword, v);
+    if constexpr (std::is_same<VIEW, CodecOverview>::value)
+        overview_transform<KIND>(v, view);
+    else
+        affine_transform<KIND>(v, view);
+    const ProjOut o = project_values<kCovariance>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h,
+                                                  tiles_x, tiles_y, radius_clip);
+    out.xys[g] = o.xy;
+    out.radii[g] = o.radius;
+    out.conics[3 * g] = o.k0, out.conics[3 * g + 1] = o.k1, out.conics[3 * g + 2] = o.k2;
+    out.num_tiles_hit[g] = o.tiles_hit;
+    out.colors[3 * g] = v[5], out.colors[3 * g + 1] = v[6], out.colors[3 * g + 2] = v[7];
+}
+
+// ------------------------------------------------------------------------------------------------- host checks
+// The stream of a decode entry, checked before any device call -> its record layout, the side information as a kernel
+// argument and the last payload dword a record's loads may touch; or the error ("<what>: ...") set and its code.
+static int codec_stream_checked(const std::string &what, int kind, int n, int xy_bits, int p0_bits, int p1_bits,
+                                int color_bits, const float *side_host, const void *payload, size_t payload_bytes,
+                                CodecLayout &lay, CodecSide &side, long long &last_dword) {
+    const auto fail = [&](const char *why) {
+        set_error((what + ": " + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    };
+    if (!codec_layout(what.c_str(), kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
+    if (n < 0) return fail("negative size");
+    const long long need = codec_dwords(n, lay.record_bits);
+    if (payload_bytes < (size_t)need * 4) return fail("payload shorter than 4 * ceil(N * R / 32) bytes");
+    if (!side_host || (n > 0 && (!payload || ((uintptr_t)payload & 3)))) return fail("null or misaligned pointer");
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) side.scale[k] = side_host[2 * k], side.beta[k] = side_host[2 * k + 1];
+    last_dword = need > 0 ? need - 1 : 0;
+    return GI2D_OK;
+}
+
+// What the two capacity-free entries (gi2d_codec_decode_overview, gi2d_codec_decode_affine) do once the conditions on
+// their view hold: the checks of the full decode, then codec_decode_lists_kernel.  All five arrays are required.
+template <class VIEW>
+static int codec_decode_lists_launch(const char *what, const VIEW &view, int kind, int n, int xy_bits, int p0_bits, int p1_bits,
+                                     int color_bits, const float *side_host, const void *payload, size_t payload_bytes,
+                                     float clip_coe, unsigned out_h, unsigned out_w, int tiles_x, int tiles_y,
+                                     float radius_clip, float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit,
+                                     float *colors, gi2d_stream_t st) {
+    const auto fail = [&](const char *why) {
+        set_error((std::string(what) + ": " + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    };
+    CodecLayout lay;
+    CodecSide side;
+    long long last;
+    if (const int rc = codec_stream_checked(what, kind, n, xy_bits, p0_bits, p1_bits, color_bits, side_host, payload,
+                                            payload_bytes, lay, side, last))
+        return rc;
+    if (tiles_x < 0 || tiles_y < 0) return fail("negative size");
+    if (n > 0 && (!xys || !radii || !conics || !num_tiles_hit || !colors)) return fail("null or misaligned pointer");
+    if ((long long)tiles_x * GI2D_TILE < (long long)out_w || (long long)tiles_y * GI2D_TILE < (long long)out_h)
+        return fail("tile grid does not cover the image");
+    if (n == 0) return GI2D_OK;
+    const CodecOut out{(float2 *)xys, radii, conics, num_tiles_hit, colors};
+    const auto kernel = kind == kCovariance ? codec_decode_lists_kernel<kCovariance, VIEW> : codec_decode_lists_kernel<kScaleRot, VIEW>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)st, n, lay, side,
+                       (const uint32_t *)payload, last, clip_coe, (float)out_w, (float)out_h, tiles_x, tiles_y, radius_clip,
+                       out, view);
+    return check_launch(what);
 }
 
 // ------------------------------------------------------------------------------------------------------------ draw

@@ -1,10 +1,11 @@
 // Reduced views ("overviews") of a packed stream (include/gi2d.h "reduced views"):
 //
-//   decode      one lane per gaussian: record -> dequantised values exactly as the full decode forms them -> the overview
-//               transform (move and scale into the output grid, add the low-pass's variance to the covariance, fold the
-//               lost peak height into the colour: codec.overview_parameters restates the arithmetic) -> the COVARIANCE
-//               projection for either model kind.  Writes the five per-gaussian arrays gi2d_bin_gaussians and the forward
-//               below consume; no fast-path workspace.
+//   decode      gi2d_codec_core.h::codec_decode_lists_kernel with overview_transform, one lane per gaussian: record ->
+//               dequantised values (codec_values, the one record reader) -> the overview transform (move and scale into
+//               the output grid, add the low-pass's variance to the covariance, fold the lost peak height into the
+//               colour: codec.overview_parameters restates the arithmetic) -> the COVARIANCE projection for either model
+//               kind.  Writes the five per-gaussian arrays gi2d_bin_gaussians and the forward below consume; no
+//               fast-path workspace.  This file has the conditions on an overview and the entry.
 //   forward     one workgroup per 16x16 tile, one pixel per lane, the tile's WHOLE list walked in batches of 256 entries
 //               staged through LDS (a reduced view puts a thousand and more entries into a tile; every other forward in
 //               the tree stops at GI2D_TILE_LIST_CAP).  Each wave owns a 16x4 strip and, per staged batch, keeps only the
@@ -19,88 +20,9 @@
 // are clamped to the capacity of the id buffer and ids to [0, N).
 #include <cmath>
 
-#include "gi2d_codec_layout.h"
-#include "gi2d_long_core.h"
-#include "gi2d_pixel_format.h"
-#include "gi2d_quant_core.h"
+#include "gi2d_codec_core.h"
 
 namespace gi2d {
-
-struct CodecOverview {
-    float x0, y0, scale, prefilter;
-};
-struct OverviewOut {
-    float2 *xys;
-    int32_t *radii;
-    float *conics;
-    int32_t *num_tiles_hit;
-    float *colors;
-};
-
-// v: the dequantised record.  -> centre, covariance and colour of the gaussian in the overview's pixel grid, every step a
-// separate fp32 operation in the order codec.overview_parameters states.
-template <int KIND>
-__device__ __forceinline__ void overview_transform(float (&v)[GI2D_CODEC_FIELDS], const CodecOverview ov) {
-#pragma clang fp contract(off)
-    v[0] = (v[0] - ov.x0) * ov.scale;
-    v[1] = (v[1] - ov.y0) * ov.scale;
-    float cxx, cxy, cyy;
-    if (KIND == kCovariance) {
-        const float s2 = ov.scale * ov.scale;
-        cxx = v[2] * s2, cxy = v[3] * s2, cyy = v[4] * s2;
-    } else {  // project_values<kScaleRot>: R = [[cos, sin], [-sin, cos]], M = R S, M M^T
-        const float sx = v[2] * ov.scale, sy = v[3] * ov.scale;
-        const float c = cosf(v[4]), s = sinf(v[4]);
-        const M2 R{{c, -s, s, c}};
-        const M2 S{{sx, 0.f, 0.f, sy}};
-        const M2 M = mul(R, S);
-        const M2 T = mul(M, tr(M));
-        cxx = T.v[0], cxy = T.v[1], cyy = T.v[3];
-    }
-    const float det0 = cxx * cyy - cxy * cxy;
-    cxx = cxx + ov.prefilter;
-    cyy = cyy + ov.prefilter;
-    const float det1 = cxx * cyy - cxy * cxy;
-    const float g = sqrtf(fmaxf(det0, 0.f) / det1);
-    v[2] = cxx, v[3] = cxy, v[4] = cyy;
-    v[5] = v[5] * g, v[6] = v[6] * g, v[7] = v[7] * g;
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void codec_decode_overview_kernel(
-    int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
-    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, OverviewOut out, CodecOverview ov) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    // the record, as the full decode reads it: dwords first, first + 1, ..., every index clamped to the payload
-    const long long bit0 = (long long)g * lay.record_bits;
-    const long long first = bit0 >> 5;
-    uint32_t w[GI2D_CODEC_MAX_LOADS];
-#pragma unroll
-    for (int j = 0; j < GI2D_CODEC_MAX_LOADS; ++j) {
-        const long long d = first + j;
-        w[j] = j < lay.loads ? payload[d < last_dword ? d : last_dword] : 0u;
-    }
-    const uint32_t s0 = (uint32_t)bit0 & 31u;
-    uint32_t r[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], s0);
-    float v[GI2D_CODEC_FIELDS];
-#pragma unroll
-    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) {
-        const float code = (float)((int)codec_take(r, lay.width[k]) + lay.qmin[k]);
-        v[k] = (KIND == kCovariance && (k == 2 || k == 4)) ? quant_dequant<GI2D_QUANT_LOG>(code, side.scale[k], side.beta[k])
-                                                          : quant_dequant<GI2D_QUANT_LSQ>(code, side.scale[k], side.beta[k]);
-    }
-    overview_transform<KIND>(v, ov);
-    const ProjOut o = project_values<kCovariance>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h,
-                                                  tiles_x, tiles_y, radius_clip);
-    out.xys[g] = o.xy;
-    out.radii[g] = o.radius;
-    out.conics[3 * g] = o.k0, out.conics[3 * g + 1] = o.k1, out.conics[3 * g + 2] = o.k2;
-    out.num_tiles_hit[g] = o.tiles_hit;
-    out.colors[3 * g] = v[5], out.colors[3 * g + 1] = v[6], out.colors[3 * g + 2] = v[7];
-}
 
 // ------------------------------------------------------------------------------------------- forward, any list length
 // (LongLds, long_pair, clamp01 and the consumption of a staged batch, long_consume: gi2d_long_core.h, shared with the
@@ -180,7 +102,6 @@ using namespace gi2d;
 
 #define GI2D_CODEC_OVERVIEW_MIN_SCALE (1.0f / 64.0f)
 #define GI2D_CODEC_OVERVIEW_MAX_PREFILTER 4.0f
-#define GI2D_CODEC_OVERVIEW_MAX_TILES 16384
 
 extern "C" {
 
@@ -201,38 +122,16 @@ int gi2d_codec_decode_overview(int kind, int n, int xy_bits, int p0_bits, int p1
         return fail("the prefilter variance must be finite and in 0 .. 4 output pixels^2");
     if (!std::isfinite(x0) || !std::isfinite(y0)) return fail("the origin must be finite");
     if (out_w < 1 || out_h < 1) return fail("empty output");
-    if (((unsigned long long)out_w + GI2D_TILE - 1) / GI2D_TILE * (((unsigned long long)out_h + GI2D_TILE - 1) / GI2D_TILE) >
-        (unsigned long long)GI2D_CODEC_OVERVIEW_MAX_TILES)
+    if (codec_too_many_tiles(out_h, out_w))
         return fail("more than 16384 tiles in one overview (compose larger outputs from several)");
     const double sc = (double)scale, m = (1.0 / sc - 1.0) / 2.0;
     if ((double)x0 - m < 0.0 || (double)x0 + (double)(out_w - 1) / sc + m > (double)w_ - 1.0 ||
         (double)y0 - m < 0.0 || (double)y0 + (double)(out_h - 1) / sc + m > (double)h - 1.0)
         return fail("the footprint of an output pixel reaches beyond the picture's sample grid");
     // ... and those of the full decode
-    CodecLayout lay;
-    if (!codec_layout(what, kind, xy_bits, p0_bits, p1_bits, color_bits, lay)) return GI2D_ERR_INVALID_ARGUMENT;
-    if (n < 0 || tiles_x < 0 || tiles_y < 0) return fail("negative size");
-    const long long need = codec_dwords(n, lay.record_bits);
-    if (payload_bytes < (size_t)need * 4) return fail("payload shorter than 4 * ceil(N * R / 32) bytes");
-    if (!side_host || (n > 0 && (!payload || ((uintptr_t)payload & 3) || !xys || !radii || !conics || !num_tiles_hit || !colors)))
-        return fail("null or misaligned pointer");
-    if ((long long)tiles_x * GI2D_TILE < (long long)out_w || (long long)tiles_y * GI2D_TILE < (long long)out_h)
-        return fail("tile grid does not cover the image");
-    if (n == 0) return GI2D_OK;
-    CodecSide side;
-    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) side.scale[k] = side_host[2 * k], side.beta[k] = side_host[2 * k + 1];
-    const OverviewOut out{(float2 *)xys, radii, conics, num_tiles_hit, colors};
-    const CodecOverview ov{x0, y0, scale, prefilter};
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (kind == kCovariance)
-        hipLaunchKernelGGL(codec_decode_overview_kernel<kCovariance>, grid, block, 0, (hipStream_t)st, n, lay, side,
-                           (const uint32_t *)payload, need - 1, clip_coe, (float)out_w, (float)out_h, tiles_x, tiles_y,
-                           radius_clip * scale, out, ov);
-    else
-        hipLaunchKernelGGL(codec_decode_overview_kernel<kScaleRot>, grid, block, 0, (hipStream_t)st, n, lay, side,
-                           (const uint32_t *)payload, need - 1, clip_coe, (float)out_w, (float)out_h, tiles_x, tiles_y,
-                           radius_clip * scale, out, ov);
-    return check_launch(what);
+    return codec_decode_lists_launch(what, CodecOverview{x0, y0, scale, prefilter}, kind, n, xy_bits, p0_bits, p1_bits,
+                                     color_bits, side_host, payload, payload_bytes, clip_coe, out_h, out_w, tiles_x, tiles_y,
+                                     radius_clip * scale, xys, radii, conics, num_tiles_hit, colors, st);
 }
 
 int gi2d_rasterize_forward_long_as(int n, int capacity, int tiles_x, int tiles_y, unsigned w, unsigned h,

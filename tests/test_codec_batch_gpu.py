@@ -152,6 +152,35 @@ def test_an_overview_inside_a_batch():
         check_batch(got, blobs, views, fmt, "overview redrawn in a batch")
 
 
+def test_every_route_in_one_batch_under_both_affine_routes():
+    """Four 100 x 72 pictures -- a plain decode, a View, an Overview and an Affine -- so that one call walks every route a
+    picture can take (the fast-path draw, the whole-row draw, the tile lists) through both host drivers, with the affine
+    picture on either of its routes.  Every picture is the single decode's, and the two Decoders report the same
+    overflows and redraws except for the affine picture, whose route is what differs."""
+    from gaussianimage_plus_amd import codec
+    fmt = (torch.float32, "hwc")
+    wide = random_stream(CO.KIND_SCALE_ROT, RS_BITS, 1500, 256, 192, 23)
+    blobs = [stream("cov"), stream("cov200"), wide, stream("cov200")]
+    views = [None, codec.View(50.25, 30.5, 100, 72, 1.0), codec.Overview(0.5, 0.5, 100, 72, 0.5),
+             codec.Affine.resized_crop(20, 10, 150, 108, 100, 72, hflip=True)]
+    want = [single(b, v, fmt) for b, v in zip(blobs, views)]
+    for capacity, redrawn in [(None, {None: [], "lists": []}), (64, {None: [2], "lists": [2, 3]})]:
+        for route in (None, "lists"):
+            dec = codec.Decoder(DEV)
+            dec.affine_route, dec.overview_capacity = route, capacity
+            got = dec.decode_batch(blobs, views)
+            assert tuple(got.shape) == (4, 72, 100, 3)
+            for k in range(4):
+                assert torch.equal(got[k], want[k]), (route, capacity, "picture", k, int((got[k] != want[k]).sum()))
+            # lists of 64 entries are outgrown by every picture that is drawn through lists, and by no other
+            assert dec.overflowed == dec.redrawn == dec.batch_redrawn == redrawn[route], (route, capacity, dec.overflowed)
+            for k in range(4):  # ... and the other driver, picture by picture, agrees
+                one = codec.Decoder(DEV)
+                one.affine_route, one.overview_capacity = route, capacity
+                assert torch.equal(one.decode(blobs[k], view=views[k]), want[k]), (route, capacity, "single", k)
+                assert one.overflowed == one.redrawn == ([0] if k in redrawn[route] else []), (route, capacity, k)
+
+
 # ------------------------------------------------------------------------------- 7. a crowded picture in the middle
 def crowded_stream():
     """test_codec_format_gpu.py::crowded_stream (all centres in tile (0, 0): capacity + 500 candidates in one row), its
