@@ -220,15 +220,19 @@ __global__ __launch_bounds__(256) void ssim_finish_kernel(const SsimPlane *__res
             val = cut ? 0.f : v;
             d_ssim[0] = cut ? 0.f : 1.f;
         } else {  // prod_s relu(v_s)^w_s, v_s = cs below the last scale and ssim on it
+            // a weight of exactly 0 turns its scale off: the factor is 1 whatever v_s is, the derivative is 0 (not
+            // w val / v, which is 0 / 0 at v = 0) and the scale takes no part in the cut
             bool cut = false;
             val = 1.f;
             for (int s = 0; s < levels; ++s) {
+                if (wts.w[s] == 0.f) continue;
                 const float v = mean[s == levels - 1 ? 0 : 1][s][c];
                 cut = cut || !(v > 0.f);
                 val *= powf(fmaxf(v, 0.f), wts.w[s]);
             }
             if (cut) val = 0.f;
             for (int s = 0; s < levels && !cut; ++s) {
+                if (wts.w[s] == 0.f) continue;
                 const float v = mean[s == levels - 1 ? 0 : 1][s][c];
                 (s == levels - 1 ? d_ssim : d_cs)[s] = wts.w[s] * val / v;
             }

@@ -9,6 +9,7 @@
                                           device); .ms_ssim_many / .ssim_many take lists of images of any sizes
     install_as_pytorch_msssim()           `from pytorch_msssim import ms_ssim, ssim` resolves to the two functions
 
+A zero in `weights` turns that scale of ms_ssim off: its factor is 1 and it gets no gradient, whatever its mean is.
 There is no CPU path: CPU tensors raise NotImplementedError.  Differences from the package: a side shorter than the
 window is an error (the package skips the filter along it with a warning), only three-channel 2-D images are served,
 and win_size stops at 11.

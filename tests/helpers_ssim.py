@@ -172,6 +172,11 @@ def picture(kind, h, w, seed=0):
     elif kind == "anti":  # anti-correlated noise: negative cs on the coarse scales, the relu cuts
         t = torch.rand(3, h, w, generator=g)
         p = 1 - t
+    elif kind == "fine_anti":  # fine noise anti-correlated between the images on a shared smooth base: cs is clearly
+        # negative at scale 0 and near 1 on the coarse scales (a generator of its own: the base draws from g)
+        base = 0.6 * picture("smooth", h, w, seed)[1] + 0.2
+        n = torch.rand(3, h, w, generator=torch.Generator().manual_seed(seed)) - 0.5
+        p, t = base + 0.2 * n, base - 0.2 * n
     else:
         raise ValueError(kind)
     return p.float().contiguous(), t.float().contiguous()

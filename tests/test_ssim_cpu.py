@@ -1,5 +1,6 @@
 """CPU: the float64 specification of SSIM / MS-SSIM (tests/helpers_ssim.py) pinned against itself and against closed
-forms, the argument checks of gaussianimage_plus_amd.metrics, the `pytorch_msssim` stand-in and the new ABI symbols."""
+forms, the argument checks of gaussianimage_plus_amd.metrics, the `pytorch_msssim` stand-in and the new ABI symbols; and
+the specification at every case that tests/test_ssim_edges_gpu.py compares the device with (its lists are read here)."""
 import ctypes as C
 import os
 import subprocess
@@ -10,6 +11,7 @@ import pytest
 import torch
 
 import helpers_ssim as S
+import test_ssim_edges_gpu as E  # the case lists and the cached specification; nothing in it touches a device on import
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -29,6 +31,81 @@ def test_the_two_restatements_agree(kind, h, w):
         assert float(a[0]) == 0.0 and float(a[3].min()) < 0
         loss, grad = S.loss_value_and_grad("ms_ssim", p, t)
         assert loss == 1.0 and torch.isfinite(grad).all() and float(grad.abs().max()) == 0.0
+
+
+def test_the_fine_anti_picture():
+    """p, t = base +- 0.2 n on 0.6 smooth + 0.2, n from a generator of its own; the other kinds draw what they drew."""
+    before = [S.picture(kind, 20, 31, 5) for kind in ("smooth", "noise", "flat", "anti")]
+    p, t = S.picture("fine_anti", 65, 80, 5)
+    assert p.dtype == t.dtype == torch.float32 and p.is_contiguous() and t.is_contiguous() and p.shape == (3, 65, 80)
+    base = 0.6 * S.picture("smooth", 65, 80, 5)[1] + 0.2
+    n = torch.rand(3, 65, 80, generator=torch.Generator().manual_seed(5)) - 0.5
+    assert torch.equal(p, base + 0.2 * n) and torch.equal(t, base - 0.2 * n)
+    assert float(p.min()) >= 0 and float(p.max()) <= 1 and float(t.min()) >= 0 and float(t.max()) <= 1
+    for (a, b), kind in zip(before, ("smooth", "noise", "flat", "anti")):
+        again = S.picture(kind, 20, 31, 5)
+        assert torch.equal(a, again[0]) and torch.equal(b, again[1])
+    want = S.ms_ssim_torch(p, t, win=5)
+    assert float(want[3][0].max()) < -0.55 and float(want[3][0].min()) > -0.78 and float(want[2][4].min()) >= 0.998
+
+
+def test_the_two_restatements_agree_on_every_edge_case():
+    assert len(E.ALL_CASES) == len(set(E.ALL_CASES)) and len(E.SSIM_CASES) == 4 * 17 and len(E.MS_CASES) == 3 * 8
+    for case in E.ALL_CASES:
+        name, kind, h, w, seed, kw = case
+        kw = dict(kw)
+        p, t = E.images(kind, h, w, seed, kw.get("data_range", 1.0))
+        a = E.spec(case)[0]
+        b = (S.ssim_scipy if name == "ssim" else S.ms_ssim_scipy)(p.numpy(), t.numpy(), **kw)
+        assert len(a) == len(b) == (3 if name == "ssim" else 4)
+        for u, v in zip(a, b):
+            assert np.abs(u.numpy() - v).max() < 1e-12, case
+
+
+def _on_means(case):
+    """the [5, 3] numbers that enter the product and the weights of a five-scale case"""
+    out = E.spec(case)[0]
+    weights = torch.tensor(dict(case[5]).get("weights", S.WEIGHTS), dtype=torch.float64)
+    return torch.cat([out[3][:4], out[2][4:]]), weights
+
+
+def test_zero_weights_turn_a_scale_off_in_the_specification():
+    case = E.ZERO_WEIGHT_CASES[0]
+    assert case[1:5] == ("fine_anti", 65, 80, 5) and dict(case[5]) == {"win": 5, "weights": (0.0, 0.0, 0.4, 0.4, 0.2)}
+    out, grad = E.spec(case)
+    v, w = _on_means(case)
+    assert float(v[0].max()) < -0.55 and float(v[1].min()) < 0  # the turned-off scales are negative
+    assert float(v[2:].min()) > 0.5
+    want = (v[2:] ** w[2:, None]).prod(0)  # the product over scales 2 .. 4 alone
+    assert float((out[1] - want).abs().max()) < 1e-15 and abs(float(out[0]) - 0.891348) < 5e-7
+    p, t = E.images(*case[1:5])
+    assert abs(S.ms_ssim_scipy(p.numpy(), t.numpy(), **dict(case[5]))[0] - 0.891348) < 5e-7
+    assert torch.isfinite(grad).all() and float(grad.abs().max()) > 0
+    assert abs(float(E.spec(E.ZERO_WEIGHT_CASES[1])[0][0]) - 0.619327) < 5e-7
+    out, grad = E.spec(E.ALL_OFF_CASE)  # every scale off: exactly 1, no gradient
+    assert float(out[0]) == 1.0 and torch.equal(out[1], torch.ones(3, dtype=torch.float64))
+    assert torch.isfinite(grad).all() and float(grad.abs().max()) == 0.0
+    out, grad = E.spec(E.CUT_CASES[0])  # the default weights: scale 0 cuts
+    assert E.CUT_CASES[0][1:5] == case[1:5] and float(out[0]) == 0.0 and float(out[1].abs().max()) == 0.0
+    assert torch.isfinite(grad).all() and float(grad.abs().max()) == 0.0
+
+
+def test_every_compared_ms_ssim_case_is_away_from_the_relu():
+    """fp32 and float64 must fall on the same side of every relu that counts, or the comparison on the device means
+    nothing: no mean that enters a product with a non-zero weight lies within 0.02 of zero.  (The "noise" kind cannot
+    meet this at small sides -- its coarse cs means are about +-0.01 -- and is not among the five-scale cases.)"""
+    count = 0
+    for case in E.ALL_CASES:
+        if case[0] == "ms_ssim":
+            assert case[1] != "noise"
+            v, w = _on_means(case)
+            on = v[w != 0]
+            assert on.numel() == 0 or float(on.abs().min()) > 0.02, (case, v)
+            count += 1
+    assert count == len(E.MS_CASES) + 10 + 3 + 1 + 3
+    out = E.spec(E.NONNEGATIVE_CASE)[0]  # the single-scale relu: its raw means are as far from zero
+    raw = S.ssim_torch(*E.images("anti1", 40, 50, 9), win=5)[1]
+    assert float(raw.abs().min()) > 0.02 and float(raw[0]) < -0.3 and float(out[1][0]) == 0.0
 
 
 def test_closed_forms():
