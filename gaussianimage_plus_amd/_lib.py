@@ -64,6 +64,10 @@ SIGNATURES.update({
     "gi2d_train_steps_batched": [_i, _p, _p, _sz, _p, C.c_double, C.c_double, _f, _i, _i, _p],
     "gi2d_fast_rasterize_forward_backward_batched": [_i, _p, _p, _sz, _p],
     "gi2d_batch_tile_pass_form": [_p],
+    # the reference's loss types on launches of their own: struct gi2d_train_state*, struct gi2d_train_loss*
+    # (gaussianimage_plus_amd/trainer.py::_TrainLoss)
+    "gi2d_loss_gradient": [_p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p],
+    "gi2d_train_steps_loss": [_p, _p, _p, C.c_double, C.c_double, _f, _i, _i, _p],
     "gi2d_train_prune": [_p, _p, _sz, _p, _p],
     "gi2d_train_grow": [_p, _i, _i, _p, _i, _p, _sz, _p, _p],
     # quantisers: struct gi2d_quant_spec* (gaussianimage_plus_amd/quantize.py::_QuantSpec)
@@ -128,6 +132,7 @@ SIZE_FUNCS = {
     "gi2d_densify_scratch_bytes": [_p, _i],
     "gi2d_batch_bytes": [_i],
     "gi2d_train_inbox_bytes": [_i, _i],
+    "gi2d_train_loss_workspace_bytes": [_i, _i, _i],
     "gi2d_codec_payload_bytes": [_i, _i, _i, _i, _i, _i],
     "gi2d_codec_batch_bytes": [_i],
     "gi2d_codec_decode_workspace_bytes": [_i, _i, _i],

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "gi2d_batch.h"
+#include "gi2d_loss.h"
 #include "gi2d_quant_core.h"
 
 namespace gi2d {
@@ -1697,6 +1698,80 @@ int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, 
 int gi2d_train_step(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps, int step,
                     gi2d_stream_t st) {
     return gi2d_train_steps(s, lr, beta1, beta2, eps, step, 1, st);
+}
+
+// The same iterations under any of the reference's loss types (include/gi2d.h; csrc/gi2d_loss.hip), the loss on
+// launches of its own between the two halves of the tile pass.  Per iteration: [the quantisers' projection kernel,] the
+// forward tile pass (out_img stored every time: the loss reads it), the loss launches, the backward tile kernel on the
+// records and lists the forward left, and the update kernel(s) as gi2d_train_steps launches them without inbox delivery.
+// The backward is gi2d_fast_rasterize_backward_tiles, not the one-launch forward+backward with v_output: that call's
+// contract is to leave the gradient rows "exactly as gi2d_fast_rasterize_forward + _backward_tiles(with_abs=0) would for
+// the reduce calls", i.e. this pair IS what the update kernel's inputs are defined by, it runs one binning call per tile
+// pass head as the workspace's contract asks, and it renders once per iteration instead of twice.
+int gi2d_train_steps_loss(const gi2d_train_state *s, const gi2d_train_loss *loss, const double *lr, double beta1,
+                          double beta2, float eps, int first_step, int count, gi2d_stream_t st_) {
+    const bool idle = count <= 0 || (s && s->num_points == 0);
+    int rc = train_check(s, idle ? kStateOnly : kSteps);
+    if (rc != GI2D_OK || idle) return rc;
+    if (!lr || first_step < 1) return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT, "bad lr/step");
+    LossTerms terms;
+    if (!loss || !loss_terms(loss->type, (double)loss->lambda, terms))
+        return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT,
+                            "unknown loss type (0 L2 .. 7 Fusion_hinerv) or lambda outside [0, 1]");
+    const LossWs lw = carve_loss(loss->workspace, s->img_height, s->img_width, terms);
+    if (lw.bytes == 0) return GI2D_ERR_INVALID_ARGUMENT;  // (the message is set: a size the type cannot take)
+    if (!loss->loss_value) return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT, "null loss_value");
+    if (!loss->workspace || ((uintptr_t)loss->workspace & 255) || loss->workspace_bytes < lw.bytes)
+        return train_refuse(kSteps, GI2D_ERR_WORKSPACE_TOO_SMALL,
+                            "loss workspace too small (gi2d_train_loss_workspace_bytes) or not 256-byte aligned");
+    ImagePlan p;
+    rc = image_plan(s, p);
+    if (rc != GI2D_OK) return rc;
+    hipStream_t st = (hipStream_t)st_;
+    const bool quantised = s->quant != nullptr;
+    const dim3 gg(p.blocks + (quantised ? 0 : 1)), bb(p.bs);  // + 1: the workgroup that orders the tiles (plain fits)
+    if (!quantised)
+        train_launch_project_fill(s->kind, p, st);
+    else if (s->kind != 2)
+        train_launch_quant_range(p, st);
+    for (int it = 0; it < count; ++it) {
+        const int step = first_step + it;
+        const bool last = it + 1 == count;
+        if (quantised) train_launch_project_fill_quant(s->kind, p, st, last);
+        rc = gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, (unsigned)s->img_width, (unsigned)s->img_height,
+                                         nullptr, s->workspace, s->workspace_bytes, s->status, nullptr, nullptr,
+                                         s->out_img, st_);
+        if (rc != GI2D_OK) return rc;
+        rc = loss_launch(s->out_img, s->gt, s->img_height, s->img_width, terms, lw, lw.v, s->tile_sse, loss->loss_value, st);
+        if (rc != GI2D_OK) return rc;
+        rc = gi2d_fast_rasterize_backward_tiles(s->num_points, p.tx, p.ty, (unsigned)s->img_width,
+                                                (unsigned)s->img_height, nullptr, lw.v, 0, s->workspace,
+                                                s->workspace_bytes, st_);
+        if (rc != GI2D_OK) return rc;
+        const IterSteps t = iter_steps(s, lr, beta1, beta2, eps, first_step, it);
+        const AdamStep *a = t.a, *aq = t.aq;
+        if (quantised) {
+#define GI2D_LAUNCH_QUANT(M)                                                                                          \
+    hipLaunchKernelGGL(train_reduce_update_quant_kernel<M>, gg, bb, 0, st, p.u, p.q, a[0], a[1], a[2], step);         \
+    hipLaunchKernelGGL(train_quant_finish_kernel<M>, dim3(1), dim3(256), 0, st, p.blocks * (p.bs / 64), p.u, p.q, a[1], \
+                       aq[0], aq[1], aq[2], step)
+            GI2D_DISPATCH_QUANT(s->kind);
+#undef GI2D_LAUNCH_QUANT
+            continue;
+        }
+        const bool more = it + 1 < count;
+        const int store_proj = it + 2 == count ? 1 : 0;
+#define GI2D_LAUNCH_RU(K, F, A) \
+    hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step, store_proj)
+        GI2D_DISPATCH_RU(s->kind, more, s->optimizer == 1);
+#undef GI2D_LAUNCH_RU
+    }
+    if (loss->v_output) {  // the last iteration's gradient image, for tests
+        const hipError_t e = hipMemcpyAsync(loss->v_output, lw.v, (size_t)s->img_height * s->img_width * 3 * sizeof(float),
+                                            hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return train_refuse(kSteps, (int)e, "copy of v_output failed");
+    }
+    return check_launch("train steps (loss)");
 }
 
 // ---------------------------------------------------------------------------------------------- several images per launch

@@ -91,7 +91,8 @@ def fit_images_native(gts: Sequence[torch.Tensor], num_points: int, iterations: 
                       seed: int = 3047, eval_renders: int = 10, kind: str = "cholesky", max_points: int = 0,
                       prune_iter: int = 100, grow_iter: int = 5000, eps: float = 1e-8,
                       chunk: int = 16, optimizer: str = "adam", quantize: bool = False, warmup_iter: int = 6000,
-                      bits=(12, 10, 6), threaded: bool = False, batched=False) -> List[Dict[str, float]]:
+                      bits=(12, 10, 6), threaded: bool = False, batched=False, loss_type: str = "L2",
+                      lambda_value: float = 0.7) -> List[Dict[str, float]]:
     """Fit the images of `gts` CONCURRENTLY on one GPU on the fused training iteration (trainer.NativeFitter ->
     gi2d_train_step: one C-ABI call, three kernel launches, no host synchronisation per iteration).  With `batched`
     the images run in lockstep and every kernel of an iteration is launched ONCE
@@ -106,8 +107,14 @@ def fit_images_native(gts: Sequence[torch.Tensor], num_points: int, iterations: 
     the best model on the device and evaluate that one.  `train_s` is the wall time of the whole group.
     With `quantize` (covariance model) the loop is train_quantize.py's: plain fitting up to `warmup_iter`, then
     quantisation-aware iterations with `bits` = (xy, covariance, colour) bit depths; the result rows then also carry
-    the size of the encoding in bits per pixel (analysis_wo_ec) and the PSNR of the decoded image."""
+    the size of the encoding in bits per pixel (analysis_wo_ec) and the PSNR of the decoded image.
+    `loss_type` / `lambda_value` (models/utils.py:60-80; trainer.LOSS_TYPES): any type but "L2" fits on
+    gi2d_train_steps_loss, which serves one image per call -- such a run is unbatched (one image, or one stream each)."""
     from .trainer import BatchFitter, NativeFitter
+
+    if loss_type != "L2" and len(gts) > 1 and batched:
+        raise ValueError(f"loss_type {loss_type!r} with batched launches: a batch runs the fused L2 iteration only "
+                         "(batched loss launches do not exist yet); pass batched=False for one stream per image")
 
     dev = gts[0].device
     adaptive = kind == "covariance" and max_points > num_points
@@ -116,7 +123,7 @@ def fit_images_native(gts: Sequence[torch.Tensor], num_points: int, iterations: 
                          "rotation-scale model (models/gaussianimage_rs.py:131-163)")
     fitters = [NativeFitter(gt, num_points, kind=kind, lr=lr, seed=seed, eps=eps, optimizer=optimizer,
                             max_points=max_points if adaptive else None, track_best=adaptive or quantize,
-                            device_resident=adaptive)
+                            device_resident=adaptive, loss_type=loss_type, lambda_value=lambda_value)
                for gt in gts]
     # batched: True = one batch, an int G > 1 = G batches of every G-th image, each on its own HIP stream and host thread
     groups = (1 if batched else 0) if isinstance(batched, bool) else max(int(batched), 0)
@@ -414,6 +421,12 @@ def main(argv=None):
                     help="covariance model: HybirdQuant bits (default 10); scale_rot: bits of the scaling quantiser "
                          "(default 6, models/gaussianimage_rs.py:142)")
     ap.add_argument("--color_bit", type=int, default=6)
+    ap.add_argument("--loss_type", default="L2",
+                    choices=["L2", "L1", "SSIM", "Fusion1", "Fusion2", "Fusion3", "Fusion4", "Fusion_hinerv"],
+                    help="train.py's --loss_type (models/utils.py:60-80), native loop: anything but L2 puts the loss on "
+                         "launches of its own between a forward and a backward tile pass (gi2d_train_steps_loss); "
+                         "one image at a time, or --streams")
+    ap.add_argument("--lambda_value", type=float, default=0.7, help="weight of the pixel term in the Fusion losses")
     ap.add_argument("--loop", choices=["native", "autograd"], default="native",
                     help="native: fused training iteration (gi2d_train_step); autograd: gsplat wrappers + torch Adam")
     ap.add_argument("--graph", action="store_true",
@@ -450,7 +463,13 @@ def main(argv=None):
     native_kw = dict(lr=args.lr, seed=args.seed, kind=args.model, max_points=args.max_num_points,
                      prune_iter=args.prune_iter, grow_iter=args.grow_iter, eps=eps, optimizer=args.opt_type,
                      quantize=args.quantize, warmup_iter=args.warmup_iter,
-                     bits=(args.xy_bit, args.cov_bit, args.color_bit))
+                     bits=(args.xy_bit, args.cov_bit, args.color_bit), loss_type=args.loss_type,
+                     lambda_value=args.lambda_value)
+    if args.loss_type != "L2" and args.loop != "native":
+        raise SystemExit("--loss_type selects the native loop's loss; the autograd loop is L2")
+    if args.loss_type != "L2" and args.images_per_gpu > 1 and not args.streams:
+        raise SystemExit("--loss_type other than L2 with --images_per_gpu > 1 needs --streams: a batch runs the fused L2 "
+                         "iteration only (batched loss launches do not exist yet)")
     if args.quantize and (args.model == "cholesky" or args.loop != "native"):
         raise SystemExit("--quantize needs --model covariance or scale_rot and the native loop")
 

@@ -30,6 +30,40 @@ from . import _lib
 
 _KINDS = {"cholesky": 0, "covariance": 1, "scale_rot": 2}
 
+# models/utils.py:60-80 loss_fn: the loss types in the order of gi2d_train_loss::type (include/gi2d.h)
+LOSS_TYPES = ("L2", "L1", "SSIM", "Fusion1", "Fusion2", "Fusion3", "Fusion4", "Fusion_hinerv")
+
+
+def loss_terms(loss_type: str, lambda_value: float = 0.7) -> Tuple[float, float, float, int, int]:
+    """-> (w2, w1, ws, levels, win): the weights of (mean d^2, mean |d|, 1 - structural value) in the loss and the
+    structural term's form -- levels 0 (none), 1 (ssim) or 5 (ms_ssim), window `win`.  Pure: no device, no library."""
+    if loss_type not in LOSS_TYPES:
+        raise ValueError(f"unknown loss_type {loss_type!r}: one of {', '.join(LOSS_TYPES)}")
+    lam = float(lambda_value)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda_value must lie in [0, 1], got {lambda_value!r}")
+    return {"L2": (1.0, 0.0, 0.0, 0, 11), "L1": (0.0, 1.0, 0.0, 0, 11), "SSIM": (0.0, 0.0, 1.0, 1, 11),
+            "Fusion1": (lam, 0.0, 1.0 - lam, 1, 11), "Fusion2": (0.0, lam, 1.0 - lam, 1, 11),
+            "Fusion3": (lam, 1.0 - lam, 0.0, 0, 11), "Fusion4": (0.0, lam, 1.0 - lam, 5, 11),
+            "Fusion_hinerv": (0.0, lam, 1.0 - lam, 5, 5)}[loss_type]
+
+
+def check_loss_size(loss_type: str, h: int, w: int) -> None:
+    """ValueError for an image the loss type's structural term cannot take: a side below the window for the one-scale
+    types, min(H, W) <= (win - 1) * 16 for the five-scale ones (160 for Fusion4, 64 for Fusion_hinerv)."""
+    _, _, _, levels, win = loss_terms(loss_type)
+    if levels >= 1 and min(h, w) < win:
+        raise ValueError(f"loss_type {loss_type}: image {h}x{w} has a side below the SSIM window ({win})")
+    if levels > 1 and min(h, w) <= (win - 1) * 16:
+        raise ValueError(f"loss_type {loss_type}: five scales with window {win} need min(H, W) > {(win - 1) * 16}, "
+                         f"got {h}x{w}")
+
+
+class _TrainLoss(C.Structure):
+    """struct gi2d_train_loss (include/gi2d.h), field for field."""
+    _fields_ = [("type", C.c_int), ("lambda_", C.c_float), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("loss_value", C.c_void_p), ("v_output", C.c_void_p)]
+
 
 class _TrainState(C.Structure):
     """struct gi2d_train_state (include/gi2d.h), field for field."""
@@ -180,9 +214,19 @@ class NativeFitter:
                  betas=None, eps: float = 1e-8, lr_step: int = 20000, lr_gamma: float = 0.5,
                  seed: int = 3047, clip_coe: float = 3.0, radius_clip: float = 1.0,
                  init: Optional[dict] = None, debug_grads: bool = False, max_points: Optional[int] = None,
-                 track_best: bool = False, optimizer: str = "adam", device_resident: bool = False):
+                 track_best: bool = False, optimizer: str = "adam", device_resident: bool = False,
+                 loss_type: str = "L2", lambda_value: float = 0.7):
         """optimizer: "adam" (torch.optim.Adam, betas (0.9, 0.999)) or "adan" (the reference's optimizer.py::Adan,
-        betas (0.98, 0.92, 0.99) -- what train.py picks for the Cholesky and RS models, with lr 1e-3, eps 1e-15)."""
+        betas (0.98, 0.92, 0.99) -- what train.py picks for the Cholesky and RS models, with lr 1e-3, eps 1e-15).
+        loss_type / lambda_value: models/utils.py:60-80 (LOSS_TYPES).  "L2" is the fused iteration (gi2d_train_steps);
+        any other type runs gi2d_train_steps_loss, the loss on launches of its own between a forward and a backward tile
+        pass (csrc/gi2d_loss.hip), and gives the fitter last_step_loss().  PSNR, the best-model snapshot, schedules,
+        checkpoints and encode are the same under every type."""
+        # refused before anything is allocated or launched (ValueError: these are user arguments)
+        loss_terms(loss_type, lambda_value)
+        if gt_hwc.dim() == 3:
+            check_loss_size(loss_type, int(gt_hwc.shape[0]), int(gt_hwc.shape[1]))
+        self.loss_type, self.lambda_value = loss_type, float(lambda_value)
         assert kind in _KINDS and gt_hwc.is_cuda and gt_hwc.dim() == 3 and gt_hwc.size(2) == 3
         assert optimizer in ("adam", "adan")
         assert not device_resident or kind == "covariance", "prune / grow are the covariance model's"
@@ -281,6 +325,22 @@ class NativeFitter:
         self._render_fn = self.lib.gi2d_train_render
         self._render_fn.argtypes = [C.c_void_p, C.c_void_p]
         self._render_fn.restype = C.c_int
+        self.loss = None  # _TrainLoss of a fitter under another loss than L2: its workspace, the loss word
+        if loss_type != "L2":
+            nbytes = int(self.lib.gi2d_train_loss_workspace_bytes(h, w, LOSS_TYPES.index(loss_type)))
+            if nbytes == 0:
+                raise _lib.Gi2dError("gi2d_train_loss_workspace_bytes: " + self.lib.gi2d_last_error_string().decode())
+            self.loss_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.loss_value = f32(1)
+            self.dbg_v_output = f32(h, w, 3) if debug_grads else None  # the last iteration's gradient image (tests)
+            self.loss = _TrainLoss(LOSS_TYPES.index(loss_type), self.lambda_value, p(self.loss_ws), nbytes,
+                                   p(self.loss_value), p(self.dbg_v_output) if debug_grads else None)
+            self._loss_ref = C.byref(self.loss)
+            self._inbox_looked = True  # (the loss route delivers through the row headers: no inbox is ever allocated)
+            self._steps_loss_fn = self.lib.gi2d_train_steps_loss
+            self._steps_loss_fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_int,
+                                            C.c_int, C.c_void_p]
+            self._steps_loss_fn.restype = C.c_int
 
     # ------------------------------------------------------------------ views of the live rows
     xyz = property(lambda self: self._xyz[:self.n])
@@ -364,9 +424,13 @@ class NativeFitter:
         with torch.cuda.device(self.dev):
             while left > 0:
                 first_step, count = self._plan_call(left, self._lr3, self.max_call, fitters)
-                rc = self._steps_fn(self._state_ref, self._lr3, b1, b2, self.eps, first_step, count, st)
+                if self.loss is None:
+                    rc = self._steps_fn(self._state_ref, self._lr3, b1, b2, self.eps, first_step, count, st)
+                else:
+                    rc = self._steps_loss_fn(self._state_ref, self._loss_ref, self._lr3, b1, b2, self.eps, first_step,
+                                             count, st)
                 if rc != 0:
-                    self._check(rc, "gi2d_train_steps")
+                    self._check(rc, "gi2d_train_steps" if self.loss is None else "gi2d_train_steps_loss")
                 self.iteration += count
                 left -= count
 
@@ -382,8 +446,16 @@ class NativeFitter:
         mse = float(self.tile_sse.sum().item()) / (3.0 * self.h * self.w)
         return 10 * math.log10(1.0 / max(mse, 1e-12))
 
+    def last_step_loss(self) -> float:
+        """The loss of the render made inside the last training step, under this fitter's loss type (one host read, like
+        last_step_psnr).  Fitters under another loss than "L2" only: the fused iteration forms no loss value."""
+        if self.loss is None:
+            raise AttributeError('last_step_loss() belongs to fitters with a loss_type other than "L2"; '
+                                 "an L2 fitter's loss is the mean squared error behind last_step_psnr()")
+        return float(self.loss_value.item())
+
     def psnr(self) -> float:
-        mse = torch.nn.functional.mse_loss(self.render(), self.gt).item()
+        mse =torch.nn.functional.mse_loss(self.render(), self.gt).item()
         return 10 * math.log10(1.0 / max(mse, 1e-12))
 
     def ssim(self, **kw) -> float:
@@ -876,6 +948,10 @@ class BatchFitter:
         f0 = fitters[0]
         # (ValueError, not assert: under `python -O` a mismatch would otherwise train every image with fitter 0's schedule)
         for i, f in enumerate(fitters):
+            if f.loss_type != "L2":
+                raise ValueError(f"fitter {i} of a batch fits under loss_type {f.loss_type!r}: a batch runs the fused L2 "
+                                 "iteration only -- batched loss launches do not exist yet; fit such an image with its "
+                                 "own NativeFitter")
             mine = (f.kind, f.optimizer, f.lr, f.betas, f.eps, f.lr_step, f.lr_gamma, f.iteration, f.opt_start)
             first = (f0.kind, f0.optimizer, f0.lr, f0.betas, f0.eps, f0.lr_step, f0.lr_gamma, f0.iteration, f0.opt_start)
             if mine != first:

@@ -551,6 +551,69 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
                              const double *lr_host, double beta1, double beta2, float eps, int first_step, int count,
                              gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ fitting under the reference's loss types
+ * models/utils.py:60-80 loss_fn(image, gt, loss_type, lambda_value = 0.7), which train.py / train_quantize.py select
+ * with --loss_type and the models call in train_iter and train_iter_quantize.  csrc/gi2d_loss.hip; DESIGN.md 3.11.
+ * With X = clamp(out_img, 0, 1), d = X - gt, P = 3 H W, lambda = lambda_value:
+ *     type 0 L2             mean d^2
+ *          1 L1             mean |d|
+ *          2 SSIM           1 - ssim(X, gt)
+ *          3 Fusion1        lambda L2 + (1 - lambda) (1 - ssim)
+ *          4 Fusion2        lambda L1 + (1 - lambda) (1 - ssim)
+ *          5 Fusion3        lambda L2 + (1 - lambda) L1
+ *          6 Fusion4        lambda L1 + (1 - lambda) (1 - ms_ssim)
+ *          7 Fusion_hinerv  lambda L1 + (1 - lambda) (1 - ms_ssim, window 5)
+ * ssim / ms_ssim as the section on structural similarity below states them: data_range 1, size_average, window 11
+ * unless said, sigma 1.5, K (0.01, 0.03), the five default scale weights, no nonnegative_ssim.  With the weights
+ * (w2, w1, ws) of (mean d^2, mean |d|, 1 - structural value) read off that table,
+ *     v_output = [out_img == X] ((2 w2 / P) d + (w1 / P) sign(d) + g_s),      sign(0) = 0,
+ * where g_s, the gradient of ws (1 - value) with respect to X, is what gi2d_ssim_backward writes for grad_result =
+ * -ws / 3 per channel, and the bracket is the clamp's gradient, inclusive at 0 and 1.  tile_sse keeps its meaning under
+ * every type: the squared error of X per tile over the pixels inside the image, so PSNR and the best-model snapshot
+ * stay PSNR-based (train.py:133-139).  All fp32, every sum in a fixed order, no atomics: a call repeats bit for bit.
+ *
+ * The loss runs on launches of its own (an SSIM value is not local to a pixel: it cannot live inside the tile pass):
+ *     prepare   X to a scratch plane, tile_sse, per-tile sums of |d|                 1 launch
+ *     SSIM      gi2d_ssim_forward + gi2d_ssim_backward on X; g_s lands in v_output   their own launches
+ *     combine   pixel terms and mask, in place                                       1 launch
+ *     finish    the scalar loss from the tile sums and the SSIM result               1 launch
+ * Types 0, 1 and 5 make no SSIM call and run prepare + combine as one launch: 2 launches.  Types 2, 3, 4: 3 + the SSIM
+ * entries' 5 (table, scale, finish; table, backward) = 8.  Types 6, 7: 3 + 17 (table, 5 scales, 4 pools, finish; table,
+ * 5 backward scales) = 20.
+ *   workspace  gi2d_train_loss_workspace_bytes(h, w, type) bytes, 256-byte aligned, uninitialised.  The query needs no
+ *              GPU; it returns 0 and sets the error string for an unknown type or a size the type cannot take (a side
+ *              below 11 for types 2-4, min(H, W) <= 160 for type 6, <= 64 for type 7).
+ *   gi2d_loss_gradient  the loss launches alone: out_img, gt f32[H,W,3] -> v_output f32[H,W,3], tile_sse f32[tiles],
+ *              loss_value f32[1].
+ *   gi2d_train_steps_loss  `count` iterations like gi2d_train_steps (same remaining arguments, same state, all three
+ *              model kinds, Adam and Adan, num_points_dev, the best-model snapshot, `quant` fits), each one
+ *                  [the quantisers' projection kernel]  forward tile pass  loss launches  backward tile kernel
+ *                  update kernel(s)
+ *              i.e. 1 + 3 count + (loss launches) count launches of a plain fit.  The forward is
+ *              gi2d_fast_rasterize_forward and stores out_img every iteration; the backward is
+ *              gi2d_fast_rasterize_backward_tiles on the records and lists that forward left -- the pair by which
+ *              gi2d_fast_rasterize_forward_backward defines what it leaves "for the reduce calls", so the update kernel
+ *              reads what it reads in gi2d_train_steps; the one-launch forward+backward with v_output would render a
+ *              second time and run a second list head behind one binning step.  The update kernels are launched exactly
+ *              as gi2d_train_steps launches them without inbox delivery (state->inbox is not looked at), the route
+ *              documented above as bit-identical.  Type 0 is accepted so that this route can be held against the fused
+ *              one.  loss_value holds the LAST iteration's loss once the call's work is complete; v_output (optional)
+ *              receives a copy of that iteration's gradient image. */
+typedef struct gi2d_train_loss {
+    int type;     /* 0 L2 ... 7 Fusion_hinerv */
+    float lambda; /* lambda_value, 0 .. 1 (unused by types 0-2) */
+    void *workspace;
+    size_t workspace_bytes;
+    float *loss_value; /* device f32[1] */
+    float *v_output;   /* device f32[H,W,3] or NULL: a copy for tests */
+} gi2d_train_loss;
+size_t gi2d_train_loss_workspace_bytes(int h, int w, int type);
+int gi2d_loss_gradient(const float *out_img, const float *gt, int h, int w, int type, float lambda, float *v_output,
+                       float *tile_sse, float *loss_value, void *workspace, size_t workspace_bytes,
+                       gi2d_stream_t stream);
+int gi2d_train_steps_loss(const gi2d_train_state *state, const gi2d_train_loss *loss, const double *lr_host,
+                          double beta1, double beta2, float eps, int first_step, int count, gi2d_stream_t stream);
+
 /* Population changes of a fit on the device (covariance model; state->num_points_dev required):
  *   gi2d_train_prune  non_semi_definite_prune (models/gaussianimage_covariance.py:352-382): rows whose covariance +
  *                     bound is not positive definite are dropped, all per-gaussian arrays of the state (parameters,
