@@ -1601,40 +1601,41 @@ static void train_launch_project_fill_quant(int kind, const ImagePlan &p, hipStr
 #undef GI2D_LAUNCH_QUANT
 }
 
-extern "C" {
-
-// Forward only (render): activations + projection + fill + rasterize into state->out_img.
-int gi2d_train_render(const gi2d_train_state *s, gi2d_stream_t st_) {
-    int rc = train_check(s, kStateOnly);
-    if (rc != GI2D_OK || s->num_points == 0) return rc;
-    ImagePlan p;
-    rc = image_plan(s, p);
-    if (rc != GI2D_OK) return rc;
-    hipStream_t st = (hipStream_t)st_;
-    if (s->quant) {  // forward_quantize (models/gaussianimage_covariance.py:384-410, models/gaussianimage_rs.py:443-471)
-        if (s->kind != 2) train_launch_quant_range(p, st);  // (the RS model's ranges are learned values)
-        train_launch_project_fill_quant(s->kind, p, st, true);
-    } else {
-        train_launch_project_fill(s->kind, p, st);
-    }
-    return gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, (unsigned)s->img_width, (unsigned)s->img_height,
-                                       nullptr, s->workspace, s->workspace_bytes, s->status, nullptr, nullptr, s->out_img,
-                                       st_);
-}
-
-// `count` full iterations: render, L2 loss gradient + backward, optimizer update.  lr[3] / first_step are host values:
-// learning rates of the xyz / cholesky / colour groups (constant over the call) and the 1-based Adam step count of
-// the first iteration.  Launches of a plain fit: project+fill once, then per iteration the tile pass and the update
-// kernel, which also projects and bins the updated gaussians for the following iteration (all but the last) --
-// 2*count + 1.  Of a quantisation-aware one (train_iter_quantize): the log range once (covariance model), then per
-// iteration project+fill behind the quantisers, tile pass, update kernel and its closing step.
-// gi2d_train_steps_batched issues the same sequence for K images per launch.
-int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps,
-                     int first_step, int count, gi2d_stream_t st_) {
+// gi2d_train_steps, and with `loss_route` gi2d_train_steps_loss: `count` fitting iterations on one image
+// (gi2d_train_steps_batched issues the same sequence for K images per launch).  A plain fit: project+fill once, then per
+// iteration the tile pass and the update kernel, which also projects and bins the updated gaussians for the following
+// iteration (all but the last) -- 2*count + 1 launches.  A quantisation-aware one (train_iter_quantize): the log range
+// once (covariance model), then per iteration project+fill behind the quantisers, tile pass, update kernel and its
+// closing step.  lr[3] / first_step are host values: learning rates of the xyz / cholesky / colour groups (constant over
+// the call) and the 1-based Adam step count of the first iteration.
+// The fused tile pass: render, L2 gradient and backward in one pass.  The update kernel of a plain fit delivers through
+// the tiles' inboxes, if the caller brought them, when another iteration follows, and the tile pass of that iteration --
+// never the first of a call, which follows the projection kernel -- is the one built to take entrants in.
+// The loss route's: the forward tile pass (out_img stored every time: the loss reads it), the loss launches
+// (csrc/gi2d_loss.hip), the backward tile kernel on the records and lists the forward left; no inbox delivery, no
+// single-pass bracket.  The backward is gi2d_fast_rasterize_backward_tiles, not the one-launch forward+backward with
+// v_output: that call's contract is to leave the gradient rows "exactly as gi2d_fast_rasterize_forward +
+// _backward_tiles(with_abs=0) would for the reduce calls", i.e. this pair IS what the update kernel's inputs are defined
+// by, it runs one binning call per tile pass head as the workspace's contract asks, and it renders once per iteration.
+static int single_steps(const gi2d_train_state *s, const gi2d_train_loss *loss, bool loss_route, const double *lr,
+                        double beta1, double beta2, float eps, int first_step, int count, gi2d_stream_t st_) {
     const bool idle = count <= 0 || (s && s->num_points == 0);  // nothing to launch: only the state itself is looked at
     int rc = train_check(s, idle ? kStateOnly : kSteps);
     if (rc != GI2D_OK || idle) return rc;
     if (!lr || first_step < 1) return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT, "bad lr/step");
+    LossTerms terms;
+    LossWs lw = {};
+    if (loss_route) {
+        if (!loss || !loss_terms(loss->type, (double)loss->lambda, terms))
+            return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT,
+                                "unknown loss type (0 L2 .. 7 Fusion_hinerv) or lambda outside [0, 1]");
+        lw = carve_loss(loss->workspace, s->img_height, s->img_width, terms);
+        if (lw.bytes == 0) return GI2D_ERR_INVALID_ARGUMENT;  // (the message is set: a size the type cannot take)
+        if (!loss->loss_value) return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT, "null loss_value");
+        if (!loss->workspace || ((uintptr_t)loss->workspace & 255) || loss->workspace_bytes < lw.bytes)
+            return train_refuse(kSteps, GI2D_ERR_WORKSPACE_TOO_SMALL,
+                                "loss workspace too small (gi2d_train_loss_workspace_bytes) or not 256-byte aligned");
+    }
     ImagePlan p;
     rc = image_plan(s, p);
     if (rc != GI2D_OK) return rc;
@@ -1643,12 +1644,10 @@ int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, 
     // a large image's tile passes run as two launches while the previous call on this workspace saw at most one row in
     // sixteen above the small form's capacity (gi2d_fast.hip: pass_form_begin)
     const long long tiles = (long long)p.tx * p.ty;
-    const int form = single_pass_begin(s->workspace, tiles, st);
+    const int form = loss_route ? 0 : single_pass_begin(s->workspace, tiles, st);
     // The inboxes: one image of at most GI2D_INBOX_MAX_TILES tiles, i.e. a tile pass of the general form throughout,
-    // whose caller brought the inboxes' buffer (gi2d_train_state::inbox), in a plain fit.  The update kernel delivers
-    // through them when another iteration follows, and the tile pass of that iteration -- never the first of a call,
-    // which follows the projection kernel -- is the one built to take entrants in.
-    float4 *const inbox = quantised ? nullptr : p.u.next.inbox;
+    // whose caller brought the inboxes' buffer (gi2d_train_state::inbox), in a plain fit.
+    float4 *const inbox = quantised || loss_route ? nullptr : p.u.next.inbox;
     const dim3 gg(p.blocks + (quantised ? 0 : 1)), bb(p.bs);  // + 1: the workgroup that orders the tiles (plain fits)
     if (!quantised)
         train_launch_project_fill(s->kind, p, st);
@@ -1661,9 +1660,21 @@ int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, 
         // opening projection kernel when count == 1), in a quantised fit the last iteration's own projection kernel.
         const bool last = it + 1 == count;
         if (quantised) train_launch_project_fill_quant(s->kind, p, st, last);
-        rc = fast_forward_backward_form(s->num_points, p.tx, p.ty, (unsigned)s->img_width, (unsigned)s->img_height, nullptr,
-                                        nullptr, s->gt, p.grad_scale, s->tile_sse, s->workspace, s->workspace_bytes,
-                                        s->status, s->out_img, st_, form, it > 0 ? inbox : nullptr, !last);
+        const unsigned w = (unsigned)s->img_width, h = (unsigned)s->img_height;
+        if (!loss_route) {
+            rc = fast_forward_backward_form(s->num_points, p.tx, p.ty, w, h, nullptr, nullptr, s->gt, p.grad_scale,
+                                            s->tile_sse, s->workspace, s->workspace_bytes, s->status, s->out_img, st_, form,
+                                            it > 0 ? inbox : nullptr, !last);
+        } else {
+            rc = gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, w, h, nullptr, s->workspace, s->workspace_bytes,
+                                             s->status, nullptr, nullptr, s->out_img, st_);
+            if (rc == GI2D_OK)
+                rc = loss_launch(s->out_img, s->gt, s->img_height, s->img_width, terms, lw, lw.v, s->tile_sse,
+                                 loss->loss_value, st);
+            if (rc == GI2D_OK)
+                rc = gi2d_fast_rasterize_backward_tiles(s->num_points, p.tx, p.ty, w, h, nullptr, lw.v, 0, s->workspace,
+                                                        s->workspace_bytes, st_);
+        }
         if (rc != GI2D_OK) return rc;
         const IterSteps t = iter_steps(s, lr, beta1, beta2, eps, first_step, it);
         const AdamStep *a = t.a, *aq = t.aq;
@@ -1691,80 +1702,9 @@ int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, 
         GI2D_DISPATCH_RU(s->kind, more, s->optimizer == 1);
 #undef GI2D_LAUNCH_RU
     }
-    single_pass_end(s->workspace, p.w, tiles, st);
-    return check_launch("train steps");
-}
-
-int gi2d_train_step(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps, int step,
-                    gi2d_stream_t st) {
-    return gi2d_train_steps(s, lr, beta1, beta2, eps, step, 1, st);
-}
-
-// The same iterations under any of the reference's loss types (include/gi2d.h; csrc/gi2d_loss.hip), the loss on
-// launches of its own between the two halves of the tile pass.  Per iteration: [the quantisers' projection kernel,] the
-// forward tile pass (out_img stored every time: the loss reads it), the loss launches, the backward tile kernel on the
-// records and lists the forward left, and the update kernel(s) as gi2d_train_steps launches them without inbox delivery.
-// The backward is gi2d_fast_rasterize_backward_tiles, not the one-launch forward+backward with v_output: that call's
-// contract is to leave the gradient rows "exactly as gi2d_fast_rasterize_forward + _backward_tiles(with_abs=0) would for
-// the reduce calls", i.e. this pair IS what the update kernel's inputs are defined by, it runs one binning call per tile
-// pass head as the workspace's contract asks, and it renders once per iteration instead of twice.
-int gi2d_train_steps_loss(const gi2d_train_state *s, const gi2d_train_loss *loss, const double *lr, double beta1,
-                          double beta2, float eps, int first_step, int count, gi2d_stream_t st_) {
-    const bool idle = count <= 0 || (s && s->num_points == 0);
-    int rc = train_check(s, idle ? kStateOnly : kSteps);
-    if (rc != GI2D_OK || idle) return rc;
-    if (!lr || first_step < 1) return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT, "bad lr/step");
-    LossTerms terms;
-    if (!loss || !loss_terms(loss->type, (double)loss->lambda, terms))
-        return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT,
-                            "unknown loss type (0 L2 .. 7 Fusion_hinerv) or lambda outside [0, 1]");
-    const LossWs lw = carve_loss(loss->workspace, s->img_height, s->img_width, terms);
-    if (lw.bytes == 0) return GI2D_ERR_INVALID_ARGUMENT;  // (the message is set: a size the type cannot take)
-    if (!loss->loss_value) return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT, "null loss_value");
-    if (!loss->workspace || ((uintptr_t)loss->workspace & 255) || loss->workspace_bytes < lw.bytes)
-        return train_refuse(kSteps, GI2D_ERR_WORKSPACE_TOO_SMALL,
-                            "loss workspace too small (gi2d_train_loss_workspace_bytes) or not 256-byte aligned");
-    ImagePlan p;
-    rc = image_plan(s, p);
-    if (rc != GI2D_OK) return rc;
-    hipStream_t st = (hipStream_t)st_;
-    const bool quantised = s->quant != nullptr;
-    const dim3 gg(p.blocks + (quantised ? 0 : 1)), bb(p.bs);  // + 1: the workgroup that orders the tiles (plain fits)
-    if (!quantised)
-        train_launch_project_fill(s->kind, p, st);
-    else if (s->kind != 2)
-        train_launch_quant_range(p, st);
-    for (int it = 0; it < count; ++it) {
-        const int step = first_step + it;
-        const bool last = it + 1 == count;
-        if (quantised) train_launch_project_fill_quant(s->kind, p, st, last);
-        rc = gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, (unsigned)s->img_width, (unsigned)s->img_height,
-                                         nullptr, s->workspace, s->workspace_bytes, s->status, nullptr, nullptr,
-                                         s->out_img, st_);
-        if (rc != GI2D_OK) return rc;
-        rc = loss_launch(s->out_img, s->gt, s->img_height, s->img_width, terms, lw, lw.v, s->tile_sse, loss->loss_value, st);
-        if (rc != GI2D_OK) return rc;
-        rc = gi2d_fast_rasterize_backward_tiles(s->num_points, p.tx, p.ty, (unsigned)s->img_width,
-                                                (unsigned)s->img_height, nullptr, lw.v, 0, s->workspace,
-                                                s->workspace_bytes, st_);
-        if (rc != GI2D_OK) return rc;
-        const IterSteps t = iter_steps(s, lr, beta1, beta2, eps, first_step, it);
-        const AdamStep *a = t.a, *aq = t.aq;
-        if (quantised) {
-#define GI2D_LAUNCH_QUANT(M)                                                                                          \
-    hipLaunchKernelGGL(train_reduce_update_quant_kernel<M>, gg, bb, 0, st, p.u, p.q, a[0], a[1], a[2], step);         \
-    hipLaunchKernelGGL(train_quant_finish_kernel<M>, dim3(1), dim3(256), 0, st, p.blocks * (p.bs / 64), p.u, p.q, a[1], \
-                       aq[0], aq[1], aq[2], step)
-            GI2D_DISPATCH_QUANT(s->kind);
-#undef GI2D_LAUNCH_QUANT
-            continue;
-        }
-        const bool more = it + 1 < count;
-        const int store_proj = it + 2 == count ? 1 : 0;
-#define GI2D_LAUNCH_RU(K, F, A) \
-    hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step, store_proj)
-        GI2D_DISPATCH_RU(s->kind, more, s->optimizer == 1);
-#undef GI2D_LAUNCH_RU
+    if (!loss_route) {
+        single_pass_end(s->workspace, p.w, tiles, st);
+        return check_launch("train steps");
     }
     if (loss->v_output) {  // the last iteration's gradient image, for tests
         const hipError_t e = hipMemcpyAsync(loss->v_output, lw.v, (size_t)s->img_height * s->img_width * 3 * sizeof(float),
@@ -1772,6 +1712,44 @@ int gi2d_train_steps_loss(const gi2d_train_state *s, const gi2d_train_loss *loss
         if (e != hipSuccess) return train_refuse(kSteps, (int)e, "copy of v_output failed");
     }
     return check_launch("train steps (loss)");
+}
+
+extern "C" {
+
+// Forward only (render): activations + projection + fill + rasterize into state->out_img.
+int gi2d_train_render(const gi2d_train_state *s, gi2d_stream_t st_) {
+    int rc = train_check(s, kStateOnly);
+    if (rc != GI2D_OK || s->num_points == 0) return rc;
+    ImagePlan p;
+    rc = image_plan(s, p);
+    if (rc != GI2D_OK) return rc;
+    hipStream_t st = (hipStream_t)st_;
+    if (s->quant) {  // forward_quantize (models/gaussianimage_covariance.py:384-410, models/gaussianimage_rs.py:443-471)
+        if (s->kind != 2) train_launch_quant_range(p, st);  // (the RS model's ranges are learned values)
+        train_launch_project_fill_quant(s->kind, p, st, true);
+    } else {
+        train_launch_project_fill(s->kind, p, st);
+    }
+    return gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, (unsigned)s->img_width, (unsigned)s->img_height,
+                                       nullptr, s->workspace, s->workspace_bytes, s->status, nullptr, nullptr, s->out_img,
+                                       st_);
+}
+
+int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps,
+                     int first_step, int count, gi2d_stream_t st) {
+    return single_steps(s, nullptr, false, lr, beta1, beta2, eps, first_step, count, st);
+}
+
+int gi2d_train_step(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps, int step,
+                    gi2d_stream_t st) {
+    return gi2d_train_steps(s, lr, beta1, beta2, eps, step, 1, st);
+}
+
+// The same iterations under any of the reference's loss types (include/gi2d.h), the loss on launches of its own between
+// the two halves of the tile pass.
+int gi2d_train_steps_loss(const gi2d_train_state *s, const gi2d_train_loss *loss, const double *lr, double beta1,
+                          double beta2, float eps, int first_step, int count, gi2d_stream_t st) {
+    return single_steps(s, loss, true, lr, beta1, beta2, eps, first_step, count, st);
 }
 
 // ---------------------------------------------------------------------------------------------- several images per launch
@@ -1840,7 +1818,7 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
     head.pg_start[num_images] = pg_blocks;
     const BatchTable b = carve_batch(batch, num_images);
     write_batch_table(b, host_imgs.data(), num_images, head, st);
-    // the same sequence as gi2d_train_steps; the kernels find their image's argument blocks in the table
+    // the same sequence as single_steps; the kernels find their image's argument blocks in the table
     const int form = batch_pass_begin(batch, tile_blocks, st);
     const bool quantised = s0->quant != nullptr;
     const BatchImage *imgs = b.img;
@@ -1861,7 +1839,7 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
     }
     for (int it = 0; it < count; ++it) {
         const int step = first_step + it;
-        const bool last = it + 1 == count;  // (what the call's last render alone stores: see gi2d_train_steps)
+        const bool last = it + 1 == count;  // (what the call's last render alone stores: see single_steps)
         if (quantised) {
 #define GI2D_LAUNCH_QUANT(M)                                                                                   \
     hipLaunchKernelGGL(train_project_fill_quant_batched_kernel<M>, gg, bb, 0, st, imgs, pg_start, num_images, \

@@ -209,6 +209,26 @@ def _fit_quantize_schedule(fitters, train, tagged: bool, iterations: int, warmup
         f.sync_population()
 
 
+def _train_calls(fitters, fn_name: str, head: tuple, lr3, max_call: int, iterations: int) -> None:
+    """NativeFitter.train / BatchFitter.train: `iterations` iterations of `fitters` (one fitter, or a batch in lockstep)
+    as C-ABI calls of `fn_name`, whose arguments in front of the learning rates are `head` -- one call per stretch
+    fitters[0]._plan_call plans."""
+    f0 = fitters[0]
+    fn = getattr(f0.lib, fn_name)
+    st = torch.cuda.current_stream(f0.dev).cuda_stream
+    b1, b2 = f0.betas[0], f0.betas[1]
+    left = int(iterations)
+    with torch.cuda.device(f0.dev):
+        while left > 0:
+            first_step, count = f0._plan_call(left, lr3, max_call, fitters)
+            rc = fn(*head, lr3, b1, b2, f0.eps, first_step, count, st)
+            if rc != 0:
+                f0._check(rc, fn_name)
+            for f in fitters:
+                f.iteration += count
+            left -= count
+
+
 class NativeFitter:
     def __init__(self, gt_hwc: torch.Tensor, num_points: int, kind: str = "cholesky", lr: float = 1e-3,
                  betas=None, eps: float = 1e-8, lr_step: int = 20000, lr_gamma: float = 0.5,
@@ -319,9 +339,8 @@ class NativeFitter:
         self.opt_start = 0       # iteration at which the optimizer / StepLR of the gaussians was (re)created
         self._state_ref = C.byref(self.state)
         self._lr3 = (C.c_double * 3)()
-        self._steps_fn = self.lib.gi2d_train_steps
-        self._steps_fn.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_int, C.c_int, C.c_void_p]
-        self._steps_fn.restype = C.c_int
+        # train()'s C call (signatures: _lib.SIGNATURES) and its leading arguments: the fused L2 iteration, or below ...
+        self._steps = ("gi2d_train_steps", (self._state_ref,))
         self._render_fn = self.lib.gi2d_train_render
         self._render_fn.argtypes = [C.c_void_p, C.c_void_p]
         self._render_fn.restype = C.c_int
@@ -335,12 +354,8 @@ class NativeFitter:
             self.dbg_v_output = f32(h, w, 3) if debug_grads else None  # the last iteration's gradient image (tests)
             self.loss = _TrainLoss(LOSS_TYPES.index(loss_type), self.lambda_value, p(self.loss_ws), nbytes,
                                    p(self.loss_value), p(self.dbg_v_output) if debug_grads else None)
-            self._loss_ref = C.byref(self.loss)
             self._inbox_looked = True  # (the loss route delivers through the row headers: no inbox is ever allocated)
-            self._steps_loss_fn = self.lib.gi2d_train_steps_loss
-            self._steps_loss_fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_int,
-                                            C.c_int, C.c_void_p]
-            self._steps_loss_fn.restype = C.c_int
+            self._steps = ("gi2d_train_steps_loss", (self._state_ref, C.byref(self.loss)))  # ... the loss route
 
     # ------------------------------------------------------------------ views of the live rows
     xyz = property(lambda self: self._xyz[:self.n])
@@ -408,10 +423,7 @@ class NativeFitter:
     def train(self, iterations: int) -> None:
         """Run `iterations` training iterations (asynchronous: only kernel launches).  One C-ABI call per stretch
         of constant learning rate (StepLR changes it every `lr_step` iterations), at most `max_call` iterations each."""
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-        b1, b2 = self.betas[0], self.betas[1]
-        left = int(iterations)
-        if self.inbox is None and not self._inbox_looked and left > 1 and self.quant is None:
+        if self.inbox is None and not self._inbox_looked and int(iterations) > 1 and self.quant is None:
             # Only a single-image call of more than one iteration delivers through the inboxes (csrc/gi2d_fast_internal.h::
             # Inbox), so only such a fitter owns the buffer -- members of a BatchFitter, quantised fits and evaluation
             # renders never allocate its 128 KB per tile (192 MiB at 768x512).  Uninitialised scratch.
@@ -420,19 +432,7 @@ class NativeFitter:
             if nbytes:  # (0: an image of more than 1 536 tiles does without)
                 self.inbox = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
                 self.state.inbox, self.state.inbox_bytes = self.inbox.data_ptr(), nbytes
-        fitters = (self,)
-        with torch.cuda.device(self.dev):
-            while left > 0:
-                first_step, count = self._plan_call(left, self._lr3, self.max_call, fitters)
-                if self.loss is None:
-                    rc = self._steps_fn(self._state_ref, self._lr3, b1, b2, self.eps, first_step, count, st)
-                else:
-                    rc = self._steps_loss_fn(self._state_ref, self._loss_ref, self._lr3, b1, b2, self.eps, first_step,
-                                             count, st)
-                if rc != 0:
-                    self._check(rc, "gi2d_train_steps" if self.loss is None else "gi2d_train_steps_loss")
-                self.iteration += count
-                left -= count
+        _train_calls((self,), *self._steps, self._lr3, self.max_call, iterations)
 
     def render(self) -> torch.Tensor:
         """Rasterize the current parameters; returns clamp(out_img, 0, 1) as [H, W, 3]."""
@@ -971,7 +971,6 @@ class BatchFitter:
         self.table = torch.empty(int(self.lib.gi2d_batch_bytes(k)), dtype=torch.uint8, device=self.dev)
         self._states = (C.c_void_p * k)(*[C.addressof(f.state) for f in self.fitters])
         self._lr3 = (C.c_double * 3)()
-        self._fn = self.lib.gi2d_train_steps_batched
         self.max_call = 256
 
     iteration = property(lambda self: self.fitters[0].iteration)
@@ -991,20 +990,8 @@ class BatchFitter:
 
     def train(self, iterations: int) -> None:
         """`iterations` training iterations of every image (asynchronous: only kernel launches)."""
-        f0 = self.fitters[0]
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-        b1, b2 = f0.betas[0], f0.betas[1]
-        left = int(iterations)
-        with torch.cuda.device(self.dev):
-            while left > 0:
-                first_step, count = f0._plan_call(left, self._lr3, self.max_call, self.fitters)
-                rc = self._fn(len(self.fitters), self._states, self.table.data_ptr(), self.table.numel(), self._lr3,
-                              b1, b2, f0.eps, first_step, count, st)
-                if rc != 0:
-                    f0._check(rc, "gi2d_train_steps_batched")
-                for f in self.fitters:
-                    f.iteration += count
-                left -= count
+        head = (len(self.fitters), self._states, self.table.data_ptr(), self.table.numel())
+        _train_calls(self.fitters, "gi2d_train_steps_batched", head, self._lr3, self.max_call, iterations)
 
     def fit_schedule(self, iterations: int, prune_iter: int = 100, grow_iter: int = 5000, adaptive_add: bool = True,
                      max_points: Optional[int] = None, log=None, chunk: Optional[int] = None,

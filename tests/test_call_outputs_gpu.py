@@ -1,8 +1,8 @@
 """What a fitting call leaves for its caller: out_img, xys and num_tiles_hit are stored by the call's LAST render only
-(csrc/gi2d_train.hip: gi2d_train_steps / gi2d_train_steps_batched; include/gi2d.h, train state).  A call of one
-iteration stores everything, so a fitter stepped by `count` calls of one iteration is the yardstick: a twin stepped by
-ONE call of `count` iterations must end with the same bits in every output and in the whole optimizer state.  Every
-comparison here is torch.equal."""
+(csrc/gi2d_train.hip: single_steps behind gi2d_train_steps / _loss, gi2d_train_steps_batched; include/gi2d.h).  A
+call of one iteration stores everything, so a fitter stepped by `count` calls of one iteration is the yardstick: a twin
+stepped by ONE call of `count` iterations must end with the same bits in every output and in the whole optimizer
+state.  Every comparison here is torch.equal."""
 import ctypes as C
 
 import numpy as np
@@ -129,6 +129,64 @@ def test_quantised_call_of_many_iterations_equals_calls_of_one(batched, kind, co
         _one_by_one(tb, count)
         for i, (fa, fb) in enumerate(zip(a, b)):
             _assert_same(fa, fb, STATE + QUANT_STATE, (kind, count, "image", i, "call", rnd))
+
+
+@pytest.mark.parametrize("count", COUNTS)
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("loss_type", ["L1", "Fusion2"])
+def test_loss_route_call_of_many_iterations_equals_calls_of_one(loss_type, kind, count):
+    """gi2d_train_steps_loss: every tile pass stores out_img (the loss reads it), the projections store as in the fused
+    route.  70x90: partial tiles, still at least the SSIM window."""
+    a, b = _fitter(kind, 70, 90, 1500, loss_type=loss_type), _fitter(kind, 70, 90, 1500, loss_type=loss_type)
+    for rnd in range(2):
+        a.train(count)
+        _one_by_one(b, count)
+        _assert_same(a, b, STATE + ("loss_value",), (loss_type, kind, count, "call", rnd))
+    assert a.inbox is None and b.inbox is None
+
+
+@pytest.mark.parametrize("count", COUNTS)
+def test_quantised_loss_route_call_of_many_iterations_equals_calls_of_one(count):
+    a, b = _fitter("covariance", 70, 90, 900, loss_type="Fusion2"), _fitter("covariance", 70, 90, 900, loss_type="Fusion2")
+    for f in (a, b):
+        f.train(1)  # (colours leave zero: the quantisers are initialised from the data)
+        f.enable_quantize()
+    for rnd in range(2):
+        a.train(count)
+        _one_by_one(b, count)
+        _assert_same(a, b, STATE + QUANT_STATE + ("loss_value",), (count, "call", rnd))
+
+
+def test_what_the_single_image_entries_test_first():
+    """gi2d_train_steps and gi2d_train_steps_loss open alike: an idle call (count <= 0, or no gaussians) looks at the
+    state alone and launches nothing; any other is refused for a null lr or a step count below 1 before it launches.
+    gi2d_train_steps_batched returns from count <= 0 before it looks at any state.  No call here launches a kernel."""
+    from gaussianimage_plus_amd.trainer import _TrainState
+    OK, INVALID = 0, -1  # include/gi2d.h: GI2D_OK, GI2D_ERR_INVALID_ARGUMENT
+    st = torch.cuda.current_stream().cuda_stream
+    lr3 = (C.c_double * 3)(1e-3, 1e-3, 1e-3)
+    plain, lossy = _fitter("cholesky", 32, 48, 64), _fitter("cholesky", 32, 48, 64, loss_type="L1")
+    entries = ((plain, "gi2d_train_steps", ()), (lossy, "gi2d_train_steps_loss", (C.byref(lossy.loss),)))
+    for f, name, head in entries:  # head: the arguments between the state and lr
+        fn, error = getattr(f.lib, name), lambda: f.lib.gi2d_last_error_string().decode()
+        before = [t.clone() for t in (f._xyz, f._chol, f._feat, f._m_xyz, f._v_xyz, f.out_img, f.status)]
+        no_xyz, empty = _TrainState.from_buffer_copy(f.state), _TrainState.from_buffer_copy(f.state)
+        no_xyz.xyz, empty.num_points = None, 0
+        call = lambda state, lr, first_step, count: fn(C.byref(state), *head, lr, 0.9, 0.999, 1e-8, first_step, count, st)
+        assert call(f.state, None, 1, 3) == INVALID and error() == "train steps: bad lr/step", name
+        assert call(f.state, lr3, 0, 3) == INVALID and error() == "train steps: bad lr/step", name
+        assert call(f.state, lr3, 1, 0) == OK, name
+        assert call(f.state, None, 0, 0) == OK, name  # (an idle call does not get as far as lr / first_step)
+        assert call(no_xyz, lr3, 1, 0) == INVALID and error() == "train: null pointer in state", name
+        assert call(empty, lr3, 1, 3) == OK and call(empty, None, 0, 3) == OK, name
+        torch.cuda.synchronize()
+        after = (f._xyz, f._chol, f._feat, f._m_xyz, f._v_xyz, f.out_img, f.status)
+        assert all(torch.equal(x, y) for x, y in zip(before, after)), name
+    # batched: count <= 0 is OK before any state is looked at -- a null entry among them included
+    states = (C.c_void_p * 2)(C.addressof(plain.state), None)
+    table = torch.empty(int(plain.lib.gi2d_batch_bytes(2)), dtype=torch.uint8, device=DEV)
+    rc = plain.lib.gi2d_train_steps_batched(2, states, table.data_ptr(), table.numel(), lr3, 0.9, 0.999, 1e-8, 1, 0, st)
+    assert rc == OK
 
 
 @pytest.mark.parametrize("count", [1, 3])
