@@ -68,6 +68,10 @@ SIGNATURES.update({
     # (gaussianimage_plus_amd/trainer.py::_TrainLoss)
     "gi2d_loss_gradient": [_p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p],
     "gi2d_train_steps_loss": [_p, _p, _p, C.c_double, C.c_double, _f, _i, _i, _p],
+    # ... for several images per launch: host arrays of struct gi2d_loss_image (trainer.py::_LossImage) / of
+    # struct gi2d_train_state* and struct gi2d_train_loss*
+    "gi2d_loss_gradient_batched": [_i, _p, _i, _f, _p, _sz, _p, _sz, _p],
+    "gi2d_train_steps_loss_batched": [_i, _p, _p, _p, _sz, _p, _sz, _p, C.c_double, C.c_double, _f, _i, _i, _p],
     "gi2d_train_prune": [_p, _p, _sz, _p, _p],
     "gi2d_train_grow": [_p, _i, _i, _p, _i, _p, _sz, _p, _p],
     # quantisers: struct gi2d_quant_spec* (gaussianimage_plus_amd/quantize.py::_QuantSpec)
@@ -133,6 +137,7 @@ SIZE_FUNCS = {
     "gi2d_batch_bytes": [_i],
     "gi2d_train_inbox_bytes": [_i, _i],
     "gi2d_train_loss_workspace_bytes": [_i, _i, _i],
+    "gi2d_train_loss_batch_workspace_bytes": [_i, _p, _p, _i],
     "gi2d_codec_payload_bytes": [_i, _i, _i, _i, _i, _i],
     "gi2d_codec_batch_bytes": [_i],
     "gi2d_codec_decode_workspace_bytes": [_i, _i, _i],

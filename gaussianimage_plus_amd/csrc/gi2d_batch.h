@@ -8,6 +8,7 @@
 // are K residency rounds whose workgroups overlap each other's phases.
 #pragma once
 #include "gi2d_fast_internal.h"
+#include "gi2d_loss.h"
 
 namespace gi2d {
 
@@ -132,10 +133,23 @@ struct QuantTrain {
 };
 #define GI2D_QT_ROW 24  // 12 LSQ sums, 2 log sums, next range (min, #min, max, #max), padding
 
+// The loss route of a batch (gi2d_train_steps_loss_batched, gi2d_loss_gradient_batched): what its separate forward /
+// loss / backward launches need of one image beyond `t` (out_img, vsrc = the target, tile_sse, the lists and rows).  A
+// block of its own: TilePassArgs and UpdateArgs are kernel arguments of the fused kernels and stay as they are.
+struct LossImage {
+    GaussRec *packed;               // the records the forward tile kernel leaves for the backward one (FastWs::packed)
+    float *x_plane, *v, *tile_abs;  // of the image's own gi2d_train_loss workspace (LossWs); x_plane: structural types
+    float *loss_value;
+    LossPixel k;
+    LossScalar s;
+    int pad;
+};
+
 struct BatchImage {
     TilePassArgs t;
     UpdateArgs u;
     QuantTrain q;  // quantisation-aware batches only
+    LossImage l;   // loss-route batches only
 };
 
 #define GI2D_BATCH_MAX 64 /* images per launch: one ballot finds a workgroup's image */
@@ -207,6 +221,19 @@ int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned img_w, 
                                size_t ws_bytes, int32_t *status, float *out_img, gi2d_stream_t st, int form,
                                float4 *inbox, bool leave_image);
 int batch_pass_begin(const void *batch, int total_blocks, hipStream_t st);
+// gi2d_fast.hip: the two halves of the loss route's tile pass over the batch -- fast_fwd_kernel's / fast_bwd_kernel's code
+// on image k's tile `local` (workgroups dealt to images as in launch_tile_pass_batched).  The forward stores every
+// image's out_img; the backward reads each image's own gradient plane (LossImage::v).
+int launch_fwd_tiles_batched(const BatchTable &b, int k_images, int total_blocks, int uniform_tiles, hipStream_t st);
+int launch_bwd_tiles_batched(const BatchTable &b, int k_images, int total_blocks, int uniform_tiles, hipStream_t st);
+// gi2d_loss.hip: the loss launches for the K images of the table (t.out_img, t.vsrc, t.tile_sse and `l` filled in):
+// loss_launch K at a time.  pairs: the K (X plane, target, v plane) triples of a structural type, or null.
+// ... and one image's share of both: `l` (packed left null) and its SSIM pair from its own carved workspace; v: where the
+// gradient image goes
+void loss_batch_image(const LossWs &lw, float *v, float *loss_value, const float *gt, int h, int w, const LossTerms &t,
+                      LossImage &l, gi2d_ssim_pair &pair);
+int loss_launch_batched(const BatchTable &b, int k_images, int total_blocks, const LossTerms &t,
+                        const gi2d_ssim_pair *pairs, const LossBatchWs &bw, hipStream_t st);
 void batch_pass_end(const void *batch, const BatchTable &b, int k_images, int total_blocks, hipStream_t st);
 
 }  // namespace gi2d

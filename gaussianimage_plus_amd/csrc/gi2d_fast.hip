@@ -99,20 +99,21 @@ static_assert(sizeof(float4) * GI2D_FWD_PAIRBUF >= sizeof(int) * GI2D_FAST_C, "t
 
 // WT: packed records and image leave as write-through stores (gi2d_raster_core.h::store16): launches of at most one
 // residency round of the chip, whose dirty lines the next kernel of the stream would otherwise wait for.
+// The kernel's body as a function of the image's tile (`first`: the image's first workgroup): fast_fwd_kernel passes
+// blockIdx.x and its kernel arguments, fast_fwd_batched_kernel the tile and the words of its image's entry of the table.
 template <bool WT>
-__global__ __launch_bounds__(256) void fast_fwd_kernel(
-    int tiles_x, int tiles_y, int img_w, int img_h, RecSets rs, const float *__restrict__ background,
-    int32_t *__restrict__ lists, int2 *__restrict__ tile_bins,
+__device__ __forceinline__ void fast_fwd_tile(
+    int tile, bool first, int tiles_x, int tiles_y, int img_w, int img_h, const RecSets &rs,
+    const float *__restrict__ background, int32_t *__restrict__ lists, int2 *__restrict__ tile_bins,
     GaussRec *__restrict__ packed, float4 *__restrict__ partial_g, float4 *__restrict__ partial_big,
     int32_t *__restrict__ status, float *__restrict__ final_Ts, int32_t *__restrict__ final_idx,
     float *__restrict__ out_img) {
     __shared__ FastFwdLds sm;
     __shared__ int grp[32];
     int *ids = reinterpret_cast<int *>(sm.f.pairbuf);  // id buffer of the head: dead before the pair buffers are first written
-    const int tile = blockIdx.x;
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int tid = threadIdx.x;
-    const float4 *recs = recs_for_tile_pass(rs, blockIdx.x == 0 && tid == 0);
+    const float4 *recs = recs_for_tile_pass(rs, first && tid == 0);
     if (tid == 0) fwd_stage_dummy(sm.f);
     const float tx0 = (float)(tx * GI2D_TILE), ty0 = (float)(ty * GI2D_TILE);
     const int L = tile_list_head<false>(
@@ -156,6 +157,16 @@ __global__ __launch_bounds__(256) void fast_fwd_kernel(
                                         final_Ts, final_idx, out_img);
     if (tid == 0 && L > 0) status[0] = 1;
 }
+template <bool WT>
+__global__ __launch_bounds__(256) void fast_fwd_kernel(
+    int tiles_x, int tiles_y, int img_w, int img_h, RecSets rs, const float *__restrict__ background,
+    int32_t *__restrict__ lists, int2 *__restrict__ tile_bins,
+    GaussRec *__restrict__ packed, float4 *__restrict__ partial_g, float4 *__restrict__ partial_big,
+    int32_t *__restrict__ status, float *__restrict__ final_Ts, int32_t *__restrict__ final_idx,
+    float *__restrict__ out_img) {
+    fast_fwd_tile<WT>((int)blockIdx.x, blockIdx.x == 0, tiles_x, tiles_y, img_w, img_h, rs, background, lists, tile_bins,
+                      packed, partial_g, partial_big, status, final_Ts, final_idx, out_img);
+}
 
 // rasterize_sum_plus.py:110-118: if there is not a single intersection the image is the background.
 __global__ __launch_bounds__(256) void fast_background_kernel(int img_w, int img_h,
@@ -173,12 +184,11 @@ __global__ __launch_bounds__(256) void fast_background_kernel(int img_w, int img
 
 // ------------------------------------------------------------------------------------- backward
 template <bool WITH_ABS, bool WT>
-__global__ __launch_bounds__(256, WITH_ABS ? 4 : GI2D_BWD_OCC) void fast_bwd_kernel(
-    int tiles_x, int tiles_y, int img_w, int img_h, const int2 *__restrict__ tile_bins,
+__device__ __forceinline__ void fast_bwd_tile(
+    int tile, int tiles_x, int tiles_y, int img_w, int img_h, const int2 *__restrict__ tile_bins,
     const GaussRec *__restrict__ packed, const int32_t *__restrict__ final_idx,
     const float *__restrict__ v_output, float4 *__restrict__ partial_g, float4 *__restrict__ partial_big) {
     __shared__ BwdLds<WITH_ABS, false> sm;
-    const int tile = blockIdx.x;
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int tid = threadIdx.x;
     const int2 range = tile_bins[tile];
@@ -204,6 +214,14 @@ __global__ __launch_bounds__(256, WITH_ABS ? 4 : GI2D_BWD_OCC) void fast_bwd_ker
         dst = slot >= 0 ? partial_g + GI2D_FAST_ROW * (size_t)slot : partial_big + GI2D_FAST_ROW * (size_t)(-slot - 1);
     bwd_run_tile<WITH_ABS, false, false, WT>(sm, len, mask, range.x, (float)(tx * GI2D_TILE), (float)(ty * GI2D_TILE), dst, 0ull,
                                              nullptr, partial_g);
+}
+template <bool WITH_ABS, bool WT>
+__global__ __launch_bounds__(256, WITH_ABS ? 4 : GI2D_BWD_OCC) void fast_bwd_kernel(
+    int tiles_x, int tiles_y, int img_w, int img_h, const int2 *__restrict__ tile_bins,
+    const GaussRec *__restrict__ packed, const int32_t *__restrict__ final_idx,
+    const float *__restrict__ v_output, float4 *__restrict__ partial_g, float4 *__restrict__ partial_big) {
+    fast_bwd_tile<WITH_ABS, WT>((int)blockIdx.x, tiles_x, tiles_y, img_w, img_h, tile_bins, packed, final_idx, v_output,
+                                partial_g, partial_big);
 }
 
 // Empty state of a workspace: every tile row empty, no gaussian binned, identity tile order.
@@ -419,6 +437,30 @@ __global__ __launch_bounds__(256, GI2D_PHASE_OCC(PHASE)) void fast_fwdbwd_batche
     }
 }
 
+// The loss route's two halves of the tile pass over a batch (gi2d_train_steps_loss_batched): fast_fwd_kernel's and
+// fast_bwd_kernel<false, false>'s code on tile `local` of image k, in index order like the single-image kernels (no tile
+// order, no second phase); workgroups are dealt to images as above.  Plain stores, as in every batched launch.  The
+// forward stores out_img every time (the loss launches read it) and takes no background and no final_Ts / final_idx.
+__global__ __launch_bounds__(256) void fast_fwd_batched_kernel(const BatchImage *__restrict__ imgs,
+                                                               const BatchHead *__restrict__ head, int k_images,
+                                                               int uniform_tiles, int xcd_map) {
+    int k, local;
+    batched_slot((int)blockIdx.x, head->tile_start, k_images, uniform_tiles, xcd_map, k, local);
+    const TilePassArgs &t = imgs[k].t;
+    fast_fwd_tile<false>(local, local == 0, t.tiles_x, t.tiles_y, t.img_w, t.img_h, t.rs, nullptr, t.lists, t.tile_bins,
+                         imgs[k].l.packed, t.partial_g, t.partial_big, t.status, nullptr, nullptr, t.out_img);
+}
+__global__ __launch_bounds__(256, GI2D_BWD_OCC) void fast_bwd_batched_kernel(const BatchImage *__restrict__ imgs,
+                                                                             const BatchHead *__restrict__ head,
+                                                                             int k_images, int uniform_tiles,
+                                                                             int xcd_map) {
+    int k, local;
+    batched_slot((int)blockIdx.x, head->tile_start, k_images, uniform_tiles, xcd_map, k, local);
+    const TilePassArgs &t = imgs[k].t;
+    fast_bwd_tile<false, false>(local, t.tiles_x, t.tiles_y, t.img_w, t.img_h, t.tile_bins, imgs[k].l.packed, nullptr,
+                                imgs[k].l.v, t.partial_g, t.partial_big);
+}
+
 // How many tiles of the batch the last tile pass marked as too full for the small form: one number per call, read back
 // behind the call's kernels (batch_pass_end).  head->big_seen is zero when the call starts (write_batch_table).
 __global__ __launch_bounds__(256) void batch_count_big_kernel(const BatchImage *__restrict__ imgs,
@@ -623,6 +665,27 @@ int launch_tile_pass_batched(int mode, const BatchTable &b, int k_images, int to
                           xcd_map, leave);
     }
     return check_launch("batched tile pass");
+}
+
+static int launch_loss_tiles_batched(bool forward, const BatchTable &b, int k_images, int total_blocks, int uniform_tiles,
+                                     hipStream_t st) {
+    if (total_blocks <= 0) return GI2D_OK;
+    const int xcd_map = uniform_tiles > 0 ? k_images & ~7 : 0;  // (as launch_tile_pass_batched)
+    const dim3 grid((unsigned)total_blocks), block(256);
+    const BatchImage *imgs = (const BatchImage *)b.img;
+    if (forward)
+        hipLaunchKernelGGL(fast_fwd_batched_kernel, grid, block, 0, st, imgs, (const BatchHead *)b.head, k_images,
+                           uniform_tiles, xcd_map);
+    else
+        hipLaunchKernelGGL(fast_bwd_batched_kernel, grid, block, 0, st, imgs, (const BatchHead *)b.head, k_images,
+                           uniform_tiles, xcd_map);
+    return check_launch(forward ? "batched forward tiles" : "batched backward tiles");
+}
+int launch_fwd_tiles_batched(const BatchTable &b, int k_images, int total_blocks, int uniform_tiles, hipStream_t st) {
+    return launch_loss_tiles_batched(true, b, k_images, total_blocks, uniform_tiles, st);
+}
+int launch_bwd_tiles_batched(const BatchTable &b, int k_images, int total_blocks, int uniform_tiles, hipStream_t st) {
+    return launch_loss_tiles_batched(false, b, k_images, total_blocks, uniform_tiles, st);
 }
 
 // ---- which form the next call's tile passes take

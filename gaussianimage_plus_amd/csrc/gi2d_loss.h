@@ -1,4 +1,5 @@
-// The loss launches of gi2d_train_steps_loss (gi2d_loss.hip), as gi2d_train.hip's driver calls them.
+// The loss launches of gi2d_train_steps_loss / gi2d_train_steps_loss_batched (gi2d_loss.hip), as gi2d_train.hip's driver
+// calls them.
 #pragma once
 #include "gi2d_common.h"
 
@@ -25,8 +26,31 @@ struct LossWs {
 // bytes == 0: the type cannot take this size (the message is set)
 LossWs carve_loss(void *base, int h, int w, const LossTerms &t);
 
+// The constants of the per-pixel terms: they depend on the image's size through P = 3 H W.
+struct LossPixel {
+    float c2, c1;  // 2 w2 / P, w1 / P
+    float gres;    // -ws / 3: the upstream gradient of every channel's structural value
+};
+// ... and of the scalar loss: w2 / P, w1 / P (ws is the same for every image of a call)
+struct LossScalar {
+    float w2_over_p, w1_over_p;
+};
+LossPixel loss_pixel(int h, int w, const LossTerms &t);
+LossScalar loss_scalar(int h, int w, const LossTerms &t);
+
 // out_img, gt -> v (the gradient image), tile_sse, loss_value; only enqueues.
 int loss_launch(const float *out_img, const float *gt, int h, int w, const LossTerms &t, const LossWs &ws, float *v,
                 float *tile_sse, float *loss_value, hipStream_t st);
+
+// What a batch of loss launches owns beside its images' own workspaces (gi2d_train_loss_batch_workspace_bytes): the
+// contiguous results and upstream gradients the batched SSIM entries ask for, and their batch workspace.
+struct LossBatchWs {
+    float *results;       // [K][GI2D_SSIM_RESULT_FLOATS]
+    float *grad_results;  // [K][3]
+    void *ssim;
+    size_t ssim_bytes, bytes;
+};
+// heights / widths: K host ints.  bytes == 0: a size the type cannot take (the message is set)
+LossBatchWs carve_loss_batch(void *base, int k, const int *heights, const int *widths, const LossTerms &t);
 
 }  // namespace gi2d

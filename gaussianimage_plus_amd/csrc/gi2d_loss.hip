@@ -16,7 +16,9 @@
 // bit for bit.
 #include <cmath>
 #include <cstring>
+#include <vector>
 
+#include "gi2d_batch.h"
 #include "gi2d_loss.h"
 
 namespace gi2d {
@@ -73,10 +75,52 @@ LossWs carve_loss(void *base, int h, int w, const LossTerms &t) {
     return ws;
 }
 
-struct LossPixel {
-    float c2, c1;  // 2 w2 / P, w1 / P
-    float gres;    // -ws / 3: the upstream gradient of every channel's structural value
-};
+LossBatchWs carve_loss_batch(void *base, int k, const int *heights, const int *widths, const LossTerms &t) {
+    LossBatchWs ws;
+    std::memset(&ws, 0, sizeof(ws));
+    if (k < 1 || k > GI2D_SSIM_MAX_BATCH || !heights || !widths) {
+        set_error("loss batch workspace: 1 .. 64 images and their sizes");
+        return ws;
+    }
+    gi2d_ssim_pair pairs[GI2D_SSIM_MAX_BATCH];
+    std::memset(pairs, 0, sizeof(pairs));
+    for (int i = 0; i < k; ++i) {
+        if (heights[i] <= 0 || widths[i] <= 0 || (long long)heights[i] * widths[i] > 0x7fffffffLL / 3) {
+            set_error("loss batch workspace: bad image size");
+            return ws;
+        }
+        pairs[i].width = widths[i], pairs[i].height = heights[i];
+    }
+    size_t ssim_bytes = 0;
+    if (t.levels > 0) {
+        ssim_bytes = gi2d_ssim_batch_workspace_bytes(k, pairs, t.levels, t.win);  // (sets the message for a size it cannot take)
+        if (ssim_bytes == 0) return ws;
+    }
+    char *b = (char *)base;
+    size_t off = 0;
+    ws.results = (float *)(b + off);
+    off += loss_align((size_t)k * GI2D_SSIM_RESULT_FLOATS * sizeof(float));
+    ws.grad_results = (float *)(b + off);
+    off += loss_align((size_t)k * 3 * sizeof(float));
+    ws.ssim = b + off;
+    ws.ssim_bytes = ssim_bytes;
+    off += loss_align(ssim_bytes);
+    ws.bytes = off;
+    return ws;
+}
+
+LossPixel loss_pixel(int h, int w, const LossTerms &t) {
+    const double P = 3.0 * (double)h * (double)w;
+    LossPixel k;
+    k.c2 = (float)(2.0 * t.w2 / P), k.c1 = (float)(t.w1 / P), k.gres = (float)(-t.ws / 3.0);
+    return k;
+}
+LossScalar loss_scalar(int h, int w, const LossTerms &t) {
+    const double P = 3.0 * (double)h * (double)w;
+    LossScalar s;
+    s.w2_over_p = (float)(t.w2 / P), s.w1_over_p = (float)(t.w1 / P);
+    return s;
+}
 
 // What one lane knows of its pixel: X, d and the clamp's mask per channel (zeros outside the image).
 struct PixelTerms {
@@ -112,16 +156,17 @@ __device__ __forceinline__ float tile_sum(float x, float *lds4) {
 }
 
 // FUSED: a type without a structural term -- the gradient image is formed here and nothing else is launched per pixel.
+// (the kernels' bodies as functions of the image's tile: the single-image kernels pass blockIdx.x and their kernel
+// arguments, the batched ones the tile and the words of their image's entry of the batch table)
 template <bool FUSED>
-__global__ __launch_bounds__(256) void loss_prepare_kernel(int tiles_x, int img_w, int img_h,
-                                                           const float *__restrict__ out_img,
-                                                           const float *__restrict__ gt, LossPixel k,
-                                                           float *__restrict__ x_plane, float *__restrict__ v,
-                                                           float *__restrict__ tile_sse, float *__restrict__ tile_abs,
-                                                           float *__restrict__ grad_result) {
+__device__ __forceinline__ void loss_prepare_tile(int tile, int tiles_x, int img_w, int img_h,
+                                                  const float *__restrict__ out_img, const float *__restrict__ gt,
+                                                  const LossPixel &k, float *__restrict__ x_plane,
+                                                  float *__restrict__ v, float *__restrict__ tile_sse,
+                                                  float *__restrict__ tile_abs, float *__restrict__ grad_result) {
 #pragma clang fp contract(off)
     __shared__ float lds4[4];
-    const int tile = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int j = tx * GI2D_TILE + (tid & 15), i = ty * GI2D_TILE + (tid >> 4);
     const bool inside = i < img_h && j < img_w;
@@ -145,13 +190,35 @@ __global__ __launch_bounds__(256) void loss_prepare_kernel(int tiles_x, int img_
     }
     if (!FUSED && tile == 0 && tid < 3) grad_result[tid] = k.gres;
 }
-
-// v holds g_s on entry.
-__global__ __launch_bounds__(256) void loss_combine_kernel(int tiles_x, int img_w, int img_h,
+template <bool FUSED>
+__global__ __launch_bounds__(256) void loss_prepare_kernel(int tiles_x, int img_w, int img_h,
                                                            const float *__restrict__ out_img,
                                                            const float *__restrict__ gt, LossPixel k,
-                                                           float *__restrict__ v) {
-    const int tile = blockIdx.x, tid = threadIdx.x;
+                                                           float *__restrict__ x_plane, float *__restrict__ v,
+                                                           float *__restrict__ tile_sse, float *__restrict__ tile_abs,
+                                                           float *__restrict__ grad_result) {
+    loss_prepare_tile<FUSED>((int)blockIdx.x, tiles_x, img_w, img_h, out_img, gt, k, x_plane, v, tile_sse, tile_abs,
+                             grad_result);
+}
+// K images in one launch (gi2d_batch.h): workgroup b is tile b - tile_start[k] of image k; an image's upstream gradient
+// is row k of the batch's [K][3].
+template <bool FUSED>
+__global__ __launch_bounds__(256) void loss_prepare_batched_kernel(const BatchImage *__restrict__ imgs,
+                                                                   const BatchHead *__restrict__ head, int k_images,
+                                                                   float *__restrict__ grad_results) {
+    const int k = batch_find(head->tile_start, k_images, (int)blockIdx.x);
+    const int local = __builtin_amdgcn_readfirstlane((int)blockIdx.x - head->tile_start[k]);
+    const TilePassArgs &t = imgs[k].t;
+    const LossImage &l = imgs[k].l;
+    loss_prepare_tile<FUSED>(local, t.tiles_x, t.img_w, t.img_h, t.out_img, t.vsrc, l.k, l.x_plane, l.v, t.tile_sse,
+                             l.tile_abs, FUSED ? nullptr : grad_results + 3 * k);
+}
+
+// v holds g_s on entry.
+__device__ __forceinline__ void loss_combine_tile(int tile, int tiles_x, int img_w, int img_h,
+                                                  const float *__restrict__ out_img, const float *__restrict__ gt,
+                                                  const LossPixel &k, float *__restrict__ v) {
+    const int tid = threadIdx.x;
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int j = tx * GI2D_TILE + (tid & 15), i = ty * GI2D_TILE + (tid >> 4);
     if (i >= img_h || j >= img_w) return;
@@ -160,13 +227,26 @@ __global__ __launch_bounds__(256) void loss_combine_kernel(int tiles_x, int img_
 #pragma unroll
     for (int c = 0; c < 3; ++c) v[3 * pix + c] = pixel_gradient(k, p.d[c], v[3 * pix + c], p.open[c]);
 }
+__global__ __launch_bounds__(256) void loss_combine_kernel(int tiles_x, int img_w, int img_h,
+                                                           const float *__restrict__ out_img,
+                                                           const float *__restrict__ gt, LossPixel k,
+                                                           float *__restrict__ v) {
+    loss_combine_tile((int)blockIdx.x, tiles_x, img_w, img_h, out_img, gt, k, v);
+}
+__global__ __launch_bounds__(256) void loss_combine_batched_kernel(const BatchImage *__restrict__ imgs,
+                                                                   const BatchHead *__restrict__ head, int k_images) {
+    const int k = batch_find(head->tile_start, k_images, (int)blockIdx.x);
+    const int local = __builtin_amdgcn_readfirstlane((int)blockIdx.x - head->tile_start[k]);
+    const TilePassArgs &t = imgs[k].t;
+    loss_combine_tile(local, t.tiles_x, t.img_w, t.img_h, t.out_img, t.vsrc, imgs[k].l.k, imgs[k].l.v);
+}
 
 // One workgroup: loss = w2 sum(tile_sse) / P + w1 sum(tile_abs) / P + ws (1 - result[0]).  Lane t sums tiles t, t + 256,
 // ... in ascending order; lanes and waves as tile_sum.
-__global__ __launch_bounds__(256) void loss_finish_kernel(int tiles, const float *__restrict__ tile_sse,
-                                                          const float *__restrict__ tile_abs,
-                                                          const float *__restrict__ ssim_result, float w2_over_p,
-                                                          float w1_over_p, float ws, float *__restrict__ loss_value) {
+__device__ __forceinline__ void loss_finish_image(int tiles, const float *__restrict__ tile_sse,
+                                                  const float *__restrict__ tile_abs,
+                                                  const float *__restrict__ ssim_result, float w2_over_p,
+                                                  float w1_over_p, float ws, float *__restrict__ loss_value) {
 #pragma clang fp contract(off)
     __shared__ float lds4[4];
     float a = 0.f, b = 0.f;
@@ -178,8 +258,25 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(int tiles, const float
         loss_value[0] = loss;
     }
 }
+__global__ __launch_bounds__(256) void loss_finish_kernel(int tiles, const float *__restrict__ tile_sse,
+                                                          const float *__restrict__ tile_abs,
+                                                          const float *__restrict__ ssim_result, float w2_over_p,
+                                                          float w1_over_p, float ws, float *__restrict__ loss_value) {
+    loss_finish_image(tiles, tile_sse, tile_abs, ssim_result, w2_over_p, w1_over_p, ws, loss_value);
+}
+// one workgroup per image; ssim_results: the batch's [K][GI2D_SSIM_RESULT_FLOATS], or null
+__global__ __launch_bounds__(256) void loss_finish_batched_kernel(const BatchImage *__restrict__ imgs,
+                                                                  const float *__restrict__ ssim_results, float ws) {
+    const int k = (int)blockIdx.x;
+    const TilePassArgs &t = imgs[k].t;
+    const LossImage &l = imgs[k].l;
+    loss_finish_image(t.tiles_x * t.tiles_y, t.tile_sse, l.tile_abs,
+                      ssim_results ? ssim_results + (size_t)GI2D_SSIM_RESULT_FLOATS * k : nullptr, l.s.w2_over_p,
+                      l.s.w1_over_p, ws, l.loss_value);
+}
 
 // g[i] = exp(-(i - win / 2)^2 / (2 sigma^2)) normalised to sum 1, in fp32, sigma = 1.5
+static const float kLossScaleWeights[GI2D_SSIM_MAX_LEVELS] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
 static void loss_taps(int win, float *g) {
     float sum = 0.f;
     for (int i = 0; i < win; ++i) {
@@ -194,9 +291,8 @@ int loss_launch(const float *out_img, const float *gt, int h, int w, const LossT
                 float *tile_sse, float *loss_value, hipStream_t st) {
     const int tiles_x = (w + GI2D_TILE - 1) / GI2D_TILE, tiles_y = (h + GI2D_TILE - 1) / GI2D_TILE;
     const int tiles = tiles_x * tiles_y;
-    const double P = 3.0 * (double)h * (double)w;
-    LossPixel k;
-    k.c2 = (float)(2.0 * t.w2 / P), k.c1 = (float)(t.w1 / P), k.gres = (float)(-t.ws / 3.0);
+    const LossPixel k = loss_pixel(h, w, t);
+    const LossScalar sc = loss_scalar(h, w, t);
     float *grad_result = ws.result + GI2D_SSIM_RESULT_FLOATS;
     const dim3 grid((unsigned)tiles), block(256);
     if (t.levels == 0) {
@@ -207,20 +303,56 @@ int loss_launch(const float *out_img, const float *gt, int h, int w, const LossT
                            ws.tile_abs, grad_result);
         float taps[11];
         loss_taps(t.win, taps);
-        static const float weights[GI2D_SSIM_MAX_LEVELS] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
         const int64_t hwc[3] = {3, 1, 3 * (int64_t)w};  // [H, W, 3] read in place: (pixel, channel, row) strides
-        int rc = gi2d_ssim_forward(ws.x, hwc, gt, hwc, w, h, t.win, taps, 1.f, 0.01f, 0.03f, t.levels, weights, 0, ws.result,
+        int rc = gi2d_ssim_forward(ws.x, hwc, gt, hwc, w, h, t.win, taps, 1.f, 0.01f, 0.03f, t.levels, kLossScaleWeights, 0, ws.result,
                                    ws.ssim, ws.ssim_bytes, (gi2d_stream_t)st);
         if (rc != GI2D_OK) return rc;
-        rc = gi2d_ssim_backward(ws.x, hwc, gt, hwc, w, h, t.win, taps, 1.f, 0.01f, 0.03f, t.levels, weights, 0, ws.result,
+        rc = gi2d_ssim_backward(ws.x, hwc, gt, hwc, w, h, t.win, taps, 1.f, 0.01f, 0.03f, t.levels, kLossScaleWeights, 0, ws.result,
                                 grad_result, v, hwc, ws.ssim, ws.ssim_bytes, (gi2d_stream_t)st);
         if (rc != GI2D_OK) return rc;
         hipLaunchKernelGGL(loss_combine_kernel, grid, block, 0, st, tiles_x, w, h, out_img, gt, k, v);
     }
     hipLaunchKernelGGL(loss_finish_kernel, dim3(1), block, 0, st, tiles, (const float *)tile_sse,
                        (const float *)ws.tile_abs, t.levels ? (const float *)ws.result : (const float *)nullptr,
-                       (float)(t.w2 / P), (float)(t.w1 / P), (float)t.ws, loss_value);
+                       sc.w2_over_p, sc.w1_over_p, (float)t.ws, loss_value);
     return check_launch("loss launches");
+}
+
+void loss_batch_image(const LossWs &lw, float *v, float *loss_value, const float *gt, int h, int w, const LossTerms &t,
+                      LossImage &l, gi2d_ssim_pair &pair) {
+    std::memset(&l, 0, sizeof(l));
+    l.x_plane = lw.x, l.v = v, l.tile_abs = lw.tile_abs, l.loss_value = loss_value;
+    l.k = loss_pixel(h, w, t);
+    l.s = loss_scalar(h, w, t);
+    std::memset(&pair, 0, sizeof(pair));
+    pair.x = lw.x, pair.y = gt, pair.grad_x = v, pair.width = w, pair.height = h;
+    const int64_t hwc[3] = {3, 1, 3 * (int64_t)w};  // [H, W, 3] read in place: (pixel, channel, row) strides
+    for (int i = 0; i < 3; ++i) pair.x_stride[i] = pair.y_stride[i] = pair.grad_stride[i] = hwc[i];
+}
+
+int loss_launch_batched(const BatchTable &b, int k_images, int total_blocks, const LossTerms &t,
+                        const gi2d_ssim_pair *pairs, const LossBatchWs &bw, hipStream_t st) {
+    const BatchImage *imgs = b.img;
+    const dim3 grid((unsigned)total_blocks), block(256);
+    if (t.levels == 0) {
+        hipLaunchKernelGGL(loss_prepare_batched_kernel<true>, grid, block, 0, st, imgs, (const BatchHead *)b.head, k_images,
+                           (float *)nullptr);
+    } else {
+        hipLaunchKernelGGL(loss_prepare_batched_kernel<false>, grid, block, 0, st, imgs, (const BatchHead *)b.head, k_images,
+                           bw.grad_results);
+        float taps[11];
+        loss_taps(t.win, taps);
+        int rc = gi2d_ssim_forward_batched(k_images, pairs, t.win, taps, 1.f, 0.01f, 0.03f, t.levels, kLossScaleWeights, 0,
+                                           bw.results, bw.ssim, bw.ssim_bytes, (gi2d_stream_t)st);
+        if (rc != GI2D_OK) return rc;
+        rc = gi2d_ssim_backward_batched(k_images, pairs, t.win, taps, 1.f, 0.01f, 0.03f, t.levels, kLossScaleWeights, 0,
+                                        bw.results, bw.grad_results, bw.ssim, bw.ssim_bytes, (gi2d_stream_t)st);
+        if (rc != GI2D_OK) return rc;
+        hipLaunchKernelGGL(loss_combine_batched_kernel, grid, block, 0, st, imgs, (const BatchHead *)b.head, k_images);
+    }
+    hipLaunchKernelGGL(loss_finish_batched_kernel, dim3((unsigned)k_images), block, 0, st, imgs,
+                       t.levels ? (const float *)bw.results : (const float *)nullptr, (float)t.ws);
+    return check_launch("loss launches (batched)");
 }
 
 }  // namespace gi2d
@@ -236,6 +368,75 @@ size_t gi2d_train_loss_workspace_bytes(int h, int w, int type) {
         return 0;
     }
     return carve_loss(nullptr, h, w, t).bytes;
+}
+
+size_t gi2d_train_loss_batch_workspace_bytes(int num_images, const int *heights, const int *widths, int type) {
+    LossTerms t;
+    if (!loss_terms(type, 0.5, t)) {
+        set_error("loss batch workspace: unknown loss type (0 L2 .. 7 Fusion_hinerv)");
+        return 0;
+    }
+    return carve_loss_batch(nullptr, num_images, heights, widths, t).bytes;
+}
+
+int gi2d_loss_gradient_batched(int num_images, const gi2d_loss_image *images, int type, float lambda, void *batch,
+                               size_t batch_bytes, void *loss_batch_ws, size_t loss_batch_ws_bytes,
+                               gi2d_stream_t stream) {
+    if (num_images < 1 || num_images > GI2D_BATCH_MAX || !images) {
+        set_error("loss gradient (batched): 1 .. 64 images per launch");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    if (!batch || batch_bytes < gi2d_batch_bytes(num_images) || ((uintptr_t)batch & 15)) {
+        set_error("loss gradient (batched): batch table too small (gi2d_batch_bytes) or not 16-byte aligned");
+        return GI2D_ERR_WORKSPACE_TOO_SMALL;
+    }
+    LossTerms t;
+    if (!loss_terms(type, (double)lambda, t)) {
+        set_error("loss gradient (batched): unknown loss type (0 L2 .. 7 Fusion_hinerv) or lambda outside [0, 1]");
+        return GI2D_ERR_INVALID_ARGUMENT;
+    }
+    std::vector<BatchImage> host_imgs((size_t)num_images);
+    std::vector<gi2d_ssim_pair> pairs((size_t)num_images);
+    int heights[GI2D_BATCH_MAX], widths[GI2D_BATCH_MAX];
+    BatchHead head;
+    std::memset(&head, 0, sizeof(head));
+    int tile_blocks = 0;
+    for (int k = 0; k < num_images; ++k) {
+        const gi2d_loss_image &im = images[k];
+        const LossWs lw = carve_loss(im.workspace, im.h, im.w, t);
+        if (lw.bytes == 0) return GI2D_ERR_INVALID_ARGUMENT;  // (the message is set)
+        if (!im.out_img || !im.gt || !im.v_output || !im.tile_sse || !im.loss_value) {
+            set_error("loss gradient (batched): null pointer");
+            return GI2D_ERR_INVALID_ARGUMENT;
+        }
+        if (!im.workspace || ((uintptr_t)im.workspace & 255) || im.workspace_bytes < lw.bytes) {
+            set_error("loss gradient (batched): an image's workspace too small (gi2d_train_loss_workspace_bytes) or not "
+                      "256-byte aligned");
+            return GI2D_ERR_WORKSPACE_TOO_SMALL;
+        }
+        BatchImage &bi = host_imgs[k];
+        std::memset(&bi, 0, sizeof(bi));
+        bi.t.tiles_x = (im.w + GI2D_TILE - 1) / GI2D_TILE, bi.t.tiles_y = (im.h + GI2D_TILE - 1) / GI2D_TILE;
+        bi.t.img_w = im.w, bi.t.img_h = im.h;
+        bi.t.out_img = (float *)im.out_img;  // (read only by the loss launches)
+        bi.t.vsrc = im.gt;
+        bi.t.tile_sse = im.tile_sse;
+        loss_batch_image(lw, im.v_output, im.loss_value, im.gt, im.h, im.w, t, bi.l, pairs[k]);
+        heights[k] = im.h, widths[k] = im.w;
+        head.tile_start[k] = tile_blocks;
+        tile_blocks += bi.t.tiles_x * bi.t.tiles_y;
+    }
+    head.tile_start[num_images] = tile_blocks;
+    const LossBatchWs bw = carve_loss_batch(loss_batch_ws, num_images, heights, widths, t);
+    if (bw.bytes == 0) return GI2D_ERR_INVALID_ARGUMENT;  // (the message is set)
+    if (!loss_batch_ws || ((uintptr_t)loss_batch_ws & 255) || loss_batch_ws_bytes < bw.bytes) {
+        set_error("loss gradient (batched): batch loss workspace too small (gi2d_train_loss_batch_workspace_bytes) or not "
+                  "256-byte aligned");
+        return GI2D_ERR_WORKSPACE_TOO_SMALL;
+    }
+    const BatchTable b = carve_batch(batch, num_images);
+    write_batch_table(b, host_imgs.data(), num_images, head, (hipStream_t)stream);
+    return loss_launch_batched(b, num_images, tile_blocks, t, pairs.data(), bw, (hipStream_t)stream);
 }
 
 int gi2d_loss_gradient(const float *out_img, const float *gt, int h, int w, int type, float lambda, float *v_output,

@@ -1307,7 +1307,7 @@ __global__ __launch_bounds__(256) void train_quant_finish_batched_kernel(const B
 
 // The batch table is written by kernels that carry the argument blocks as kernel arguments: stream-ordered, no host
 // buffer whose lifetime anybody has to think about, capturable in a graph.
-#define GI2D_BATCH_PACK 6 /* argument blocks per writer launch (kernel arguments are limited to 4 KB) */
+#define GI2D_BATCH_PACK 5 /* argument blocks per writer launch (kernel arguments are limited to 4 KB) */
 struct BatchPack {
     BatchImage img[GI2D_BATCH_PACK];
 };
@@ -1617,6 +1617,29 @@ static void train_launch_project_fill_quant(int kind, const ImagePlan &p, hipStr
 // v_output: that call's contract is to leave the gradient rows "exactly as gi2d_fast_rasterize_forward +
 // _backward_tiles(with_abs=0) would for the reduce calls", i.e. this pair IS what the update kernel's inputs are defined
 // by, it runs one binning call per tile pass head as the workspace's contract asks, and it renders once per iteration.
+// One image's gi2d_train_loss on the loss route: its terms and the regions of its workspace.
+static int loss_check(const gi2d_train_state *s, const gi2d_train_loss *loss, TrainEntry entry, LossTerms &terms,
+                      LossWs &lw) {
+    if (!loss || !loss_terms(loss->type, (double)loss->lambda, terms))
+        return train_refuse(entry, GI2D_ERR_INVALID_ARGUMENT,
+                            "unknown loss type (0 L2 .. 7 Fusion_hinerv) or lambda outside [0, 1]");
+    lw = carve_loss(loss->workspace, s->img_height, s->img_width, terms);
+    if (lw.bytes == 0) return GI2D_ERR_INVALID_ARGUMENT;  // (the message is set: a size the type cannot take)
+    if (!loss->loss_value) return train_refuse(entry, GI2D_ERR_INVALID_ARGUMENT, "null loss_value");
+    if (!loss->workspace || ((uintptr_t)loss->workspace & 255) || loss->workspace_bytes < lw.bytes)
+        return train_refuse(entry, GI2D_ERR_WORKSPACE_TOO_SMALL,
+                            "loss workspace too small (gi2d_train_loss_workspace_bytes) or not 256-byte aligned");
+    return GI2D_OK;
+}
+// The last iteration's gradient image, for tests (gi2d_train_loss::v_output).
+static int loss_copy_v(const gi2d_train_state *s, const gi2d_train_loss *loss, const LossWs &lw, TrainEntry entry,
+                       hipStream_t st) {
+    if (!loss->v_output) return GI2D_OK;
+    const hipError_t e = hipMemcpyAsync(loss->v_output, lw.v, (size_t)s->img_height * s->img_width * 3 * sizeof(float),
+                                        hipMemcpyDeviceToDevice, st);
+    return e == hipSuccess ? GI2D_OK : train_refuse(entry, (int)e, "copy of v_output failed");
+}
+
 static int single_steps(const gi2d_train_state *s, const gi2d_train_loss *loss, bool loss_route, const double *lr,
                         double beta1, double beta2, float eps, int first_step, int count, gi2d_stream_t st_) {
     const bool idle = count <= 0 || (s && s->num_points == 0);  // nothing to launch: only the state itself is looked at
@@ -1626,15 +1649,8 @@ static int single_steps(const gi2d_train_state *s, const gi2d_train_loss *loss, 
     LossTerms terms;
     LossWs lw = {};
     if (loss_route) {
-        if (!loss || !loss_terms(loss->type, (double)loss->lambda, terms))
-            return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT,
-                                "unknown loss type (0 L2 .. 7 Fusion_hinerv) or lambda outside [0, 1]");
-        lw = carve_loss(loss->workspace, s->img_height, s->img_width, terms);
-        if (lw.bytes == 0) return GI2D_ERR_INVALID_ARGUMENT;  // (the message is set: a size the type cannot take)
-        if (!loss->loss_value) return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT, "null loss_value");
-        if (!loss->workspace || ((uintptr_t)loss->workspace & 255) || loss->workspace_bytes < lw.bytes)
-            return train_refuse(kSteps, GI2D_ERR_WORKSPACE_TOO_SMALL,
-                                "loss workspace too small (gi2d_train_loss_workspace_bytes) or not 256-byte aligned");
+        rc = loss_check(s, loss, kSteps, terms, lw);
+        if (rc != GI2D_OK) return rc;
     }
     ImagePlan p;
     rc = image_plan(s, p);
@@ -1706,11 +1722,8 @@ static int single_steps(const gi2d_train_state *s, const gi2d_train_loss *loss, 
         single_pass_end(s->workspace, p.w, tiles, st);
         return check_launch("train steps");
     }
-    if (loss->v_output) {  // the last iteration's gradient image, for tests
-        const hipError_t e = hipMemcpyAsync(loss->v_output, lw.v, (size_t)s->img_height * s->img_width * 3 * sizeof(float),
-                                            hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return train_refuse(kSteps, (int)e, "copy of v_output failed");
-    }
+    rc = loss_copy_v(s, loss, lw, kSteps, st);
+    if (rc != GI2D_OK) return rc;
     return check_launch("train steps (loss)");
 }
 
@@ -1756,15 +1769,25 @@ int gi2d_train_steps_loss(const gi2d_train_state *s, const gi2d_train_loss *loss
 size_t gi2d_batch_bytes(int num_images) { return carve_batch(nullptr, num_images).bytes; }
 size_t gi2d_train_inbox_bytes(int tiles_x, int tiles_y) { return inbox_bytes((long long)tiles_x * tiles_y); }
 
-int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *states, void *batch, size_t batch_bytes,
-                             const double *lr, double beta1, double beta2, float eps, int first_step, int count,
-                             gi2d_stream_t st_) {
+}  // extern "C"
+
+// gi2d_train_steps_batched, and with `loss_route` gi2d_train_steps_loss_batched: single_steps' sequence for K images, every
+// kernel launched once.  The loss route's tile pass is the batched forward tile kernel, the batched loss launches and
+// the batched backward tile kernel (gi2d_fast.hip, gi2d_loss.hip) in place of the fused one -- as on the single loss
+// route without the tile-pass-form bracket; everything in front of and behind the tile pass is the same launch either way.
+static int batched_steps(int num_images, const gi2d_train_state *const *states, const gi2d_train_loss *const *losses,
+                         bool loss_route, void *batch, size_t batch_bytes, void *loss_batch_ws,
+                         size_t loss_batch_ws_bytes, const double *lr, double beta1, double beta2, float eps,
+                         int first_step, int count, gi2d_stream_t st_) {
     hipStream_t st = (hipStream_t)st_;
-    if (num_images < 1 || num_images > GI2D_BATCH_MAX || !states)
+    if (num_images < 1 || num_images > GI2D_BATCH_MAX || !states || (loss_route && !losses))
         return train_refuse(kStepsBatched, GI2D_ERR_INVALID_ARGUMENT, "1 .. 64 images per launch");
     if (!batch || batch_bytes < gi2d_batch_bytes(num_images) || ((uintptr_t)batch & 15))
         return train_refuse(kStepsBatched, GI2D_ERR_WORKSPACE_TOO_SMALL,
                             "batch table too small (gi2d_batch_bytes) or not 16-byte aligned");
+    if (loss_route && (!loss_batch_ws || ((uintptr_t)loss_batch_ws & 255)))
+        return train_refuse(kStepsBatched, GI2D_ERR_WORKSPACE_TOO_SMALL,
+                            "batch loss workspace null or not 256-byte aligned");
     if (count <= 0) return GI2D_OK;
     if (!lr || first_step < 1) return train_refuse(kStepsBatched, GI2D_ERR_INVALID_ARGUMENT, "bad lr/step");
     const gi2d_train_state *s0 = states[0];
@@ -1772,6 +1795,11 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
     std::memset(&head, 0, sizeof(head));
     // the table: tile-pass and per-gaussian workgroup ranges, one argument block per image
     std::vector<BatchImage> host_imgs((size_t)num_images);
+    // the loss route's: one type and one lambda for the batch, every image's own workspace, the SSIM pairs
+    LossTerms terms = {};
+    std::vector<LossWs> lws(loss_route ? (size_t)num_images : 0);
+    std::vector<gi2d_ssim_pair> pairs(loss_route ? (size_t)num_images : 0);
+    int heights[GI2D_BATCH_MAX], widths[GI2D_BATCH_MAX];
     long long total_n = 0;
     bool uniform = true;
     int tile_blocks = 0, tiles0 = 0;
@@ -1801,6 +1829,20 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
                                         s->out_img, s->gt, p.grad_scale, s->tile_sse);
         host_imgs[k].u = p.u;
         host_imgs[k].q = p.q;
+        std::memset(&host_imgs[k].l, 0, sizeof(LossImage));
+        if (loss_route) {
+            const gi2d_train_loss *loss = losses[k];
+            LossTerms mine;
+            rc = loss_check(s, loss, kStepsBatched, mine, lws[k]);
+            if (rc != GI2D_OK) return rc;
+            if (loss->type != losses[0]->type || loss->lambda != losses[0]->lambda)
+                return train_refuse(kStepsBatched, GI2D_ERR_UNSUPPORTED, "the images of a batch share loss type and lambda");
+            terms = mine;
+            loss_batch_image(lws[k], lws[k].v, loss->loss_value, s->gt, s->img_height, s->img_width, terms,
+                             host_imgs[k].l, pairs[k]);
+            host_imgs[k].l.packed = p.w.packed;
+            heights[k] = s->img_height, widths[k] = s->img_width;
+        }
         head.tile_start[k] = tile_blocks;
         tile_blocks += p.tx * p.ty;
         if (k == 0) tiles0 = p.tx * p.ty;
@@ -1816,10 +1858,18 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
         pg_blocks += (states[k]->num_points + bs - 1) / bs + (s0->quant ? 0 : 1);
     }
     head.pg_start[num_images] = pg_blocks;
+    LossBatchWs bw = {};
+    if (loss_route) {
+        bw = carve_loss_batch(loss_batch_ws, num_images, heights, widths, terms);
+        if (bw.bytes == 0) return GI2D_ERR_INVALID_ARGUMENT;  // (the message is set)
+        if (loss_batch_ws_bytes < bw.bytes)
+            return train_refuse(kStepsBatched, GI2D_ERR_WORKSPACE_TOO_SMALL,
+                                "batch loss workspace too small (gi2d_train_loss_batch_workspace_bytes)");
+    }
     const BatchTable b = carve_batch(batch, num_images);
     write_batch_table(b, host_imgs.data(), num_images, head, st);
     // the same sequence as single_steps; the kernels find their image's argument blocks in the table
-    const int form = batch_pass_begin(batch, tile_blocks, st);
+    const int form = loss_route ? 0 : batch_pass_begin(batch, tile_blocks, st);
     const bool quantised = s0->quant != nullptr;
     const BatchImage *imgs = b.img;
     const int *pg_start = b.head->pg_start;
@@ -1847,7 +1897,15 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
             GI2D_DISPATCH_QUANT(s0->kind);
 #undef GI2D_LAUNCH_QUANT
         }
-        int rc = launch_tile_pass_batched(1, b, num_images, tile_blocks, uniform ? tiles0 : 0, form, st, !last);
+        const int uniform_tiles = uniform ? tiles0 : 0;
+        int rc;
+        if (!loss_route) {
+            rc = launch_tile_pass_batched(1, b, num_images, tile_blocks, uniform_tiles, form, st, !last);
+        } else {
+            rc = launch_fwd_tiles_batched(b, num_images, tile_blocks, uniform_tiles, st);
+            if (rc == GI2D_OK) rc = loss_launch_batched(b, num_images, tile_blocks, terms, pairs.data(), bw, st);
+            if (rc == GI2D_OK) rc = launch_bwd_tiles_batched(b, num_images, tile_blocks, uniform_tiles, st);
+        }
         if (rc != GI2D_OK) return rc;
         const IterSteps t = iter_steps(s0, lr, beta1, beta2, eps, first_step, it);
         const AdamStep *a = t.a, *aq = t.aq;
@@ -1869,8 +1927,33 @@ int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *stat
         GI2D_DISPATCH_RU(s0->kind, more, s0->optimizer == 1);
 #undef GI2D_LAUNCH_RU
     }
-    batch_pass_end(batch, b, num_images, tile_blocks, st);
-    return check_launch("train steps (batched)");
+    if (!loss_route) {
+        batch_pass_end(batch, b, num_images, tile_blocks, st);
+        return check_launch("train steps (batched)");
+    }
+    for (int k = 0; k < num_images; ++k) {
+        const int rc = loss_copy_v(states[k], losses[k], lws[k], kStepsBatched, st);
+        if (rc != GI2D_OK) return rc;
+    }
+    return check_launch("train steps (loss, batched)");
+}
+
+extern "C" {
+
+int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *states, void *batch, size_t batch_bytes,
+                             const double *lr, double beta1, double beta2, float eps, int first_step, int count,
+                             gi2d_stream_t st) {
+    return batched_steps(num_images, states, nullptr, false, batch, batch_bytes, nullptr, 0, lr, beta1, beta2, eps,
+                         first_step, count, st);
+}
+
+// The same under any of the reference's loss types: gi2d_train_steps_loss for K images, every kernel launched once.
+int gi2d_train_steps_loss_batched(int num_images, const gi2d_train_state *const *states,
+                                  const gi2d_train_loss *const *losses, void *batch, size_t batch_bytes,
+                                  void *loss_batch_ws, size_t loss_batch_ws_bytes, const double *lr, double beta1,
+                                  double beta2, float eps, int first_step, int count, gi2d_stream_t st) {
+    return batched_steps(num_images, states, losses, true, batch, batch_bytes, loss_batch_ws, loss_batch_ws_bytes, lr,
+                         beta1, beta2, eps, first_step, count, st);
 }
 
 }  // extern "C"

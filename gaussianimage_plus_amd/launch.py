@@ -92,7 +92,7 @@ def fit_images_native(gts: Sequence[torch.Tensor], num_points: int, iterations: 
                       prune_iter: int = 100, grow_iter: int = 5000, eps: float = 1e-8,
                       chunk: int = 16, optimizer: str = "adam", quantize: bool = False, warmup_iter: int = 6000,
                       bits=(12, 10, 6), threaded: bool = False, batched=False, loss_type: str = "L2",
-                      lambda_value: float = 0.7) -> List[Dict[str, float]]:
+                      lambda_value: float = 0.7, batched_losses: bool = False) -> List[Dict[str, float]]:
     """Fit the images of `gts` CONCURRENTLY on one GPU on the fused training iteration (trainer.NativeFitter ->
     gi2d_train_step: one C-ABI call, three kernel launches, no host synchronisation per iteration).  With `batched`
     the images run in lockstep and every kernel of an iteration is launched ONCE
@@ -109,12 +109,16 @@ def fit_images_native(gts: Sequence[torch.Tensor], num_points: int, iterations: 
     quantisation-aware iterations with `bits` = (xy, covariance, colour) bit depths; the result rows then also carry
     the size of the encoding in bits per pixel (analysis_wo_ec) and the PSNR of the decoded image.
     `loss_type` / `lambda_value` (models/utils.py:60-80; trainer.LOSS_TYPES): any type but "L2" fits on
-    gi2d_train_steps_loss, which serves one image per call -- such a run is unbatched (one image, or one stream each)."""
-    from .trainer import BatchFitter, NativeFitter
+    gi2d_train_steps_loss, one image per call (one image, or one stream each), or, with `batched` AND `batched_losses`, on
+    gi2d_train_steps_loss_batched (trainer.LossBatchFitter where a plain fit builds a BatchFitter: every kernel of an
+    iteration, the loss launches included, launched once per batch).  `batched` alone is refused for such a type."""
+    from .trainer import BatchFitter, LossBatchFitter, NativeFitter
 
-    if loss_type != "L2" and len(gts) > 1 and batched:
-        raise ValueError(f"loss_type {loss_type!r} with batched launches: a batch runs the fused L2 iteration only "
-                         "(batched loss launches do not exist yet); pass batched=False for one stream per image")
+    if loss_type != "L2" and len(gts) > 1 and batched and not batched_losses:
+        raise ValueError(f"loss_type {loss_type!r} with batched launches: a BatchFitter runs the fused L2 iteration only; "
+                         "pass batched_losses=True for batched loss launches (trainer.LossBatchFitter), or batched=False "
+                         "for one stream per image")
+    batch_class = BatchFitter if loss_type == "L2" else LossBatchFitter
 
     dev = gts[0].device
     adaptive = kind == "covariance" and max_points > num_points
@@ -148,7 +152,7 @@ def fit_images_native(gts: Sequence[torch.Tensor], num_points: int, iterations: 
         def fit_batch(part):
             # (a batch of ONE image -- the three-image shard of an 8-GPU Kodak run is three of them -- takes the
             # single-image calls: same results bit for bit, no table lookups)
-            runner = BatchFitter(part) if len(part) > 1 else part[0]
+            runner = batch_class(part) if len(part) > 1 else part[0]
             if quantize:  # train_quantize.py's loop for the whole batch
                 for _ in runner.fit_quantize_schedule(iterations, warmup_iter, bits=bits, **sched_kw):
                     pass
@@ -425,7 +429,11 @@ def main(argv=None):
                     choices=["L2", "L1", "SSIM", "Fusion1", "Fusion2", "Fusion3", "Fusion4", "Fusion_hinerv"],
                     help="train.py's --loss_type (models/utils.py:60-80), native loop: anything but L2 puts the loss on "
                          "launches of its own between a forward and a backward tile pass (gi2d_train_steps_loss); "
-                         "one image at a time, or --streams")
+                         "one image at a time, --streams, or --batched_losses")
+    ap.add_argument("--batched_losses", action="store_true",
+                    help="with --loss_type other than L2 and --images_per_gpu > 1: the concurrent images run as batches "
+                         "with every kernel of an iteration, the loss launches included, launched once per batch "
+                         "(gi2d_train_steps_loss_batched), as plain fits do")
     ap.add_argument("--lambda_value", type=float, default=0.7, help="weight of the pixel term in the Fusion losses")
     ap.add_argument("--loop", choices=["native", "autograd"], default="native",
                     help="native: fused training iteration (gi2d_train_step); autograd: gsplat wrappers + torch Adam")
@@ -464,12 +472,12 @@ def main(argv=None):
                      prune_iter=args.prune_iter, grow_iter=args.grow_iter, eps=eps, optimizer=args.opt_type,
                      quantize=args.quantize, warmup_iter=args.warmup_iter,
                      bits=(args.xy_bit, args.cov_bit, args.color_bit), loss_type=args.loss_type,
-                     lambda_value=args.lambda_value)
+                     lambda_value=args.lambda_value, batched_losses=args.batched_losses)
     if args.loss_type != "L2" and args.loop != "native":
         raise SystemExit("--loss_type selects the native loop's loss; the autograd loop is L2")
-    if args.loss_type != "L2" and args.images_per_gpu > 1 and not args.streams:
-        raise SystemExit("--loss_type other than L2 with --images_per_gpu > 1 needs --streams: a batch runs the fused L2 "
-                         "iteration only (batched loss launches do not exist yet)")
+    if args.loss_type != "L2" and args.images_per_gpu > 1 and not args.streams and not args.batched_losses:
+        raise SystemExit("--loss_type other than L2 with --images_per_gpu > 1 needs --streams or --batched_losses: a plain "
+                         "batch runs the fused L2 iteration only (batched loss launches: --batched_losses)")
     if args.quantize and (args.model == "cholesky" or args.loop != "native"):
         raise SystemExit("--quantize needs --model covariance or scale_rot and the native loop")
 

@@ -65,6 +65,13 @@ class _TrainLoss(C.Structure):
                 ("loss_value", C.c_void_p), ("v_output", C.c_void_p)]
 
 
+class _LossImage(C.Structure):
+    """struct gi2d_loss_image (include/gi2d.h), field for field."""
+    _fields_ = [("out_img", C.c_void_p), ("gt", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("v_output", C.c_void_p),
+                ("tile_sse", C.c_void_p), ("loss_value", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
+
 class _TrainState(C.Structure):
     """struct gi2d_train_state (include/gi2d.h), field for field."""
     _fields_ = [
@@ -942,16 +949,22 @@ class BatchFitter:
     per-image calls between the batched stretches.  The fitters share model kind, optimizer, learning-rate schedule and
     iteration count; image sizes and populations may differ."""
 
+    @staticmethod
+    def _check_losses(fitters) -> None:
+        """The loss types the members may have, looked at before anything else (LossBatchFitter has its own rule)."""
+        for i, f in enumerate(fitters):
+            if f.loss_type != "L2":
+                raise ValueError(f"fitter {i} of a batch fits under loss_type {f.loss_type!r}: a BatchFitter runs the fused "
+                                 "L2 iteration only -- batched loss launches are LossBatchFitter's "
+                                 "(launch.fit_images_native: batched_losses=True)")
+
     def __init__(self, fitters):
         if not 1 <= len(fitters) <= 64:
             raise ValueError(f"a batch holds 1 .. 64 images, got {len(fitters)}")
         f0 = fitters[0]
+        self._check_losses(fitters)
         # (ValueError, not assert: under `python -O` a mismatch would otherwise train every image with fitter 0's schedule)
         for i, f in enumerate(fitters):
-            if f.loss_type != "L2":
-                raise ValueError(f"fitter {i} of a batch fits under loss_type {f.loss_type!r}: a batch runs the fused L2 "
-                                 "iteration only -- batched loss launches do not exist yet; fit such an image with its "
-                                 "own NativeFitter")
             mine = (f.kind, f.optimizer, f.lr, f.betas, f.eps, f.lr_step, f.lr_gamma, f.iteration, f.opt_start)
             first = (f0.kind, f0.optimizer, f0.lr, f0.betas, f0.eps, f0.lr_step, f0.lr_gamma, f0.iteration, f0.opt_start)
             if mine != first:
@@ -1009,3 +1022,44 @@ class BatchFitter:
         switch per image (best warm-up model, prune, quantisers initialised from its own data), then quantisation-aware
         iterations in lockstep -- four launches per iteration for all images (gi2d_train_steps_batched)."""
         return _fit_quantize_schedule(self.fitters, self.train, True, iterations, warmup_iter, bits, chunk, log, **kw)
+
+
+class LossBatchFitter(BatchFitter):
+    """BatchFitter for NativeFitters under one common loss type other than "L2" and one lambda_value
+    (gi2d_train_steps_loss_batched): per iteration the batched forward tile kernel, the batched loss launches
+    (csrc/gi2d_loss.hip; one batched SSIM forward and backward for the structural types), the batched backward tile kernel
+    and the batched update kernel(s) -- as many launches as for one image.  Every fitter's results are those of fitting
+    it alone, bit for bit.  Schedules, metrics, prune and grow are BatchFitter's."""
+
+    @staticmethod
+    def _check_losses(fitters) -> None:
+        f0 = fitters[0]
+        for i, f in enumerate(fitters):
+            if f.loss_type == "L2":
+                raise ValueError(f"fitter {i} of a loss batch fits under loss_type 'L2', the fused iteration: use BatchFitter")
+            if (f.loss_type, f.lambda_value) != (f0.loss_type, f0.lambda_value):
+                raise ValueError(f"fitter {i} of a loss batch differs from fitter 0 in (loss_type, lambda_value): "
+                                 f"{(f.loss_type, f.lambda_value)} != {(f0.loss_type, f0.lambda_value)}")
+        for f in fitters:
+            check_loss_size(f.loss_type, f.h, f.w)  # (ValueError for a size the type cannot take)
+
+    def __init__(self, fitters):
+        super().__init__(fitters)
+        k = len(self.fitters)
+        hs = (C.c_int * k)(*[f.h for f in self.fitters])
+        ws = (C.c_int * k)(*[f.w for f in self.fitters])
+        nbytes = int(self.lib.gi2d_train_loss_batch_workspace_bytes(k, hs, ws, LOSS_TYPES.index(self.fitters[0].loss_type)))
+        if nbytes == 0:
+            raise _lib.Gi2dError("gi2d_train_loss_batch_workspace_bytes: " + self.lib.gi2d_last_error_string().decode())
+        self.loss_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)  # what the batch itself owns
+        self._losses = (C.c_void_p * k)(*[C.addressof(f.loss) for f in self.fitters])
+
+    def train(self, iterations: int) -> None:
+        """`iterations` training iterations of every image (asynchronous: only kernel launches)."""
+        head = (len(self.fitters), self._states, self._losses, self.table.data_ptr(), self.table.numel(),
+                self.loss_ws.data_ptr(), self.loss_ws.numel())
+        _train_calls(self.fitters, "gi2d_train_steps_loss_batched", head, self._lr3, self.max_call, iterations)
+
+    def last_step_loss(self):
+        """Every fitter's NativeFitter.last_step_loss(), as a list."""
+        return [f.last_step_loss() for f in self.fitters]

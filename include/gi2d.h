@@ -614,6 +614,44 @@ int gi2d_loss_gradient(const float *out_img, const float *gt, int h, int w, int 
 int gi2d_train_steps_loss(const gi2d_train_state *state, const gi2d_train_loss *loss, const double *lr_host,
                           double beta1, double beta2, float eps, int first_step, int count, gi2d_stream_t stream);
 
+/* The same for `num_images` (1 .. 64) independent images in lockstep, every kernel launched ONCE for the whole batch:
+ * what gi2d_train_steps_batched is to gi2d_train_steps.  Per iteration
+ *     [the quantisers' batched projection kernel]  batched forward tile kernel  batched loss launches
+ *     batched backward tile kernel  batched update kernel(s)
+ * with the batched loss launches being prepare, [one gi2d_ssim_forward_batched, one gi2d_ssim_backward_batched, combine,]
+ * finish -- the launch counts of the single route (2 / 8 / 20 per iteration), whatever num_images is (the table writes of
+ * the call and of the SSIM entries aside).  The images share kind, optimizer, quantiser configuration, loss type and
+ * lambda (losses[k]->type / ->lambda); sizes and populations may differ.
+ * CONTRACT: every image's parameters, moments, quantiser state, out_img, tile_sse, loss_value, best-model snapshot and
+ * device population are those of gi2d_train_steps_loss on that image alone, bit for bit (v_output copies included).
+ *   losses[k]      image k's gi2d_train_loss with its OWN workspace (gi2d_train_loss_workspace_bytes): the X plane, the
+ *                  gradient plane and the per-tile |d| sums stay there.
+ *   batch          gi2d_batch_bytes(num_images) bytes, 16-byte aligned, rewritten by every call.
+ *   loss_batch_ws  gi2d_train_loss_batch_workspace_bytes(num_images, heights, widths, type) bytes, 256-byte aligned,
+ *                  uninitialised: what the batch itself owns -- the contiguous [K][GI2D_SSIM_RESULT_FLOATS] results and
+ *                  [K][3] upstream gradients the batched SSIM entries ask for, and their batch workspace
+ *                  (gi2d_ssim_batch_workspace_bytes).  The query needs no GPU; heights / widths are HOST int[K]; it
+ *                  returns 0 and sets the error string for an unknown type, a bad count or a size the type cannot take.
+ * Every argument check runs before the first launch.
+ *   gi2d_loss_gradient_batched  the loss launches alone for K image pairs: gi2d_loss_gradient K at a time (images[k]:
+ *                  that call's arguments for image k, the workspace being image k's own), one type and one lambda per
+ *                  call; results per image are those of gi2d_loss_gradient, bit for bit. */
+typedef struct gi2d_loss_image {
+    const float *out_img, *gt; /* device f32[H,W,3] */
+    int h, w;
+    float *v_output, *tile_sse, *loss_value; /* device f32[H,W,3], f32[tiles], f32[1] */
+    void *workspace;                         /* gi2d_train_loss_workspace_bytes(h, w, type), 256-byte aligned */
+    size_t workspace_bytes;
+} gi2d_loss_image;
+size_t gi2d_train_loss_batch_workspace_bytes(int num_images, const int *heights_host, const int *widths_host, int type);
+int gi2d_loss_gradient_batched(int num_images, const gi2d_loss_image *images_host, int type, float lambda, void *batch,
+                               size_t batch_bytes, void *loss_batch_ws, size_t loss_batch_ws_bytes,
+                               gi2d_stream_t stream);
+int gi2d_train_steps_loss_batched(int num_images, const gi2d_train_state *const *states,
+                                  const gi2d_train_loss *const *losses, void *batch, size_t batch_bytes,
+                                  void *loss_batch_ws, size_t loss_batch_ws_bytes, const double *lr_host, double beta1,
+                                  double beta2, float eps, int first_step, int count, gi2d_stream_t stream);
+
 /* Population changes of a fit on the device (covariance model; state->num_points_dev required):
  *   gi2d_train_prune  non_semi_definite_prune (models/gaussianimage_covariance.py:352-382): rows whose covariance +
  *                     bound is not positive definite are dropped, all per-gaussian arrays of the state (parameters,

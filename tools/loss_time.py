@@ -13,6 +13,14 @@ table.  --trace LOSS runs 60 native iterations of that type and nothing else, fo
 `rocprofv3 --kernel-trace --stats -- python tools/loss_time.py --trace Fusion2`.
 
     python tools/loss_time.py [--iters 200] [--dropin-iters 20] [--out profiles/loss_time.json]
+
+--batch K [K ...] measures the batched loss route instead (trainer.LossBatchFitter: gi2d_train_steps_loss_batched), in
+microseconds per IMAGE-iteration, for K images of the bench scene under --types (default L1 Fusion2 Fusion4), in
+alternation with what a caller had before -- the same K fitters one after the other, and the same K fitters on one HIP
+stream and host thread each -- and writes every region to profiles/loss_batch_time.json.  With --trace LOSS it runs 60
+batched iterations of that type for the first K and nothing else.
+
+    python tools/loss_time.py --batch 1 8 24 [--iters 50] [--types L1 Fusion2 Fusion4] [--out profiles/loss_batch_time.json]
 """
 import argparse
 import json
@@ -75,6 +83,62 @@ class DropIn:
             self.opt.step()
 
 
+def batch_mode(a, dev):
+    """The batched loss route against the two forms a caller had before it, K images at a time."""
+    import threading
+
+    from gaussianimage_plus_amd.trainer import LossBatchFitter
+    out = {"scene": f"Cholesky model, N={N}, {W}x{H}, Adam 1e-3, K images (targets synthetic_image(seed 1 + i))",
+           "iters_per_region": a.iters, "regions": 5, "lib": _lib.version(), "device": torch.cuda.get_device_name(0),
+           "unit": "us per image-iteration", "us_per_image_iteration": {}}
+    for loss_type in a.types:
+        for k in a.batch:
+            fits = [native_fitter(synthetic_image(H, W, 1 + i).to(dev), loss_type=loss_type) for i in range(k)]
+            batch = LossBatchFitter(fits)
+            if a.trace:
+                batch.train(60)
+                torch.cuda.synchronize()
+                return None
+            streams = [torch.cuda.Stream(device=dev) for _ in fits]
+
+            def one_after_the_other(count):
+                for f in fits:
+                    f.train(count)
+
+            def drive(i, count):
+                with torch.cuda.device(dev), torch.cuda.stream(streams[i]):
+                    fits[i].train(count)
+
+            def one_stream_each(count):
+                ts = [threading.Thread(target=drive, args=(i, count)) for i in range(k)]
+                for t in ts:
+                    t.start()
+                for t in ts:
+                    t.join()
+
+            ways = (("batched", batch.train), ("one_after_the_other", one_after_the_other), ("one_stream_each", one_stream_each))
+            for _, train in ways:
+                # warm-up, each way to its end before the next begins: the third way's streams do not wait for the
+                # default stream, and two iterations of ONE image must never run side by side (its tile rows take
+                # atomics from the binning launches and plain stores from the tile pass: csrc/gi2d_fast_internal.h)
+                region_us(train, 10)
+            rows = {name: [] for name, _ in ways}
+            for _ in range(5):  # in alternation
+                for name, train in ways:
+                    rows[name].append(region_us(train, a.iters) / k)
+            for f in fits:
+                f.check_status()
+            out["us_per_image_iteration"][f"{loss_type} K={k}"] = {
+                name: {"median": statistics.median(v), "min": min(v), "max": max(v), "regions": v} for name, v in rows.items()}
+            print(f"{loss_type} K={k}: " + ", ".join(f"{name} {statistics.median(v):.1f}" for name, v in rows.items()),
+                  flush=True)
+            del batch, fits, streams
+            torch.cuda.empty_cache()
+            torch.cuda.synchronize()
+            time.sleep(0.5)  # (returning gigabytes to the driver stalls the queue: keep it out of the next timing)
+    return out
+
+
 def region_us(train, iters):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -89,9 +153,31 @@ def main():
     ap.add_argument("--dropin-iters", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss_time.json"))
     ap.add_argument("--trace", default=None, choices=LOSS_TYPES)
+    ap.add_argument("--batch", type=int, nargs="+", default=None, help="K images per launch: the batched loss route")
+    ap.add_argument("--types", nargs="+", default=["L1", "Fusion2", "Fusion4"], choices=LOSS_TYPES[1:])
     a = ap.parse_args()
     assert torch.cuda.is_available(), "loss_time.py measures on the GPU"
     dev = torch.device("cuda:0")
+    if a.batch:
+        if a.trace:
+            a.types, a.batch = [a.trace], a.batch[:1]
+        if a.iters == 200:
+            a.iters = 50  # (a region of K images: the default of the single-image table would take K times as long)
+        if a.out == os.path.join(ROOT, "profiles", "loss_time.json"):
+            a.out = os.path.join(ROOT, "profiles", "loss_batch_time.json")
+        out = batch_mode(a, dev)
+        if out is None:
+            return
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print("| loss_type | K | batched | one after the other | one stream each |")
+        print("|---|---|---|---|---|")
+        for key, r in out["us_per_image_iteration"].items():
+            cell = lambda w: f"{r[w]['median']:.1f} ({r[w]['min']:.1f} .. {r[w]['max']:.1f})"
+            print(f"| {key.split()[0]} | {key.split('=')[1]} | {cell('batched')} | {cell('one_after_the_other')} | "
+                  f"{cell('one_stream_each')} |")
+        return
     gt = synthetic_image(H, W, 1).to(dev)
     if a.trace:
         fit = native_fitter(gt, loss_type=a.trace)
