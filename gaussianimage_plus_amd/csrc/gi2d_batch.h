@@ -72,8 +72,9 @@ struct TilePassArgs {
     int32_t *big_tile;  // two-phase tile pass: which tiles the small form left to the general one (FastWs::big_tile)
     float4 *inbox;      // the tiles' inboxes (gi2d_train_state::inbox; nullptr: none)
     int write_through;  // single-image launches of one residency round: rows and image leave as sc1 stores (store16)
-    int leave_image;    // single-image launches: this pass does not store out_img (fused_tile; a batched launch says so
-                        // in a kernel argument: its table is written once per call)
+    int leave_image;    // single-image launches: bit 0 this pass does not store out_img, bit 1 nor sum and store tile_sse
+                        // (fused_tile: leave_image / leave_sse; a batched launch says the former in a kernel argument:
+                        // its table is written once per call)
 };
 
 // One image's arguments of the per-gaussian fitting kernels (project+fill, reduce+update).
@@ -216,10 +217,12 @@ void single_pass_end(const void *ws, const FastWs &w, long long tiles, hipStream
 // gi2d_fast_rasterize_forward_backward with the form given: 1 / 2 two launches, 0 one, -1 the C entry's own rule
 // inbox: the tiles' inboxes to take entrants out of (fast_fwdbwd_kernel), or null
 // leave_image: out_img is not written (neither by the tiles nor as the background image): the caller's last pass stores it
+// leave_sse (with `target`): tile_sse is neither summed nor stored -- a pass that is not the caller's last, of a fit that
+// tracks no best model (nothing on the device reads the sums then: gi2d_train.hip::best_decision is their only reader)
 int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned img_w, unsigned img_h, const float *background,
                                const float *v_output, const float *target, float grad_scale, float *tile_sse, void *ws,
                                size_t ws_bytes, int32_t *status, float *out_img, gi2d_stream_t st, int form,
-                               float4 *inbox, bool leave_image);
+                               float4 *inbox, bool leave_image, bool leave_sse);
 int batch_pass_begin(const void *batch, int total_blocks, hipStream_t st);
 // gi2d_fast.hip: the two halves of the loss route's tile pass over the batch -- fast_fwd_kernel's / fast_bwd_kernel's code
 // on image k's tile `local` (workgroups dealt to images as in launch_tile_pass_batched).  The forward stores every

@@ -45,6 +45,18 @@ static std::string dev_switches() {
 #ifdef GI2D_INBOX_STATS
     add("GI2D_INBOX_STATS", "");
 #endif
+#ifdef GI2D_KNOCK_BOX_FILL
+    add("GI2D_KNOCK_BOX_FILL", "");
+#endif
+#ifdef GI2D_KEEP_SSE
+    add("GI2D_KEEP_SSE", "");
+#endif
+#ifdef GI2D_KEEP_VOPAC
+    add("GI2D_KEEP_VOPAC", "");
+#endif
+#ifdef GI2D_HEAD_BALLOT_IDS /* (only when given on the command line: the default lives in gi2d_fast_internal.h) */
+    add("GI2D_HEAD_BALLOT_IDS", GI2D_STR(GI2D_HEAD_BALLOT_IDS));
+#endif
 #ifdef GI2D_DEV_VARIANT /* any other experiment: -DGI2D_DEV_VARIANT=name next to its own macros */
     add("GI2D_DEV_VARIANT", GI2D_STR(GI2D_DEV_VARIANT));
 #endif

@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256) void fast_ws_init_kernel(int num_tiles, int n,
 // single image: the launch code knows the tile count).
 template <int MODE, int PHASE, bool INBOX = false, int WTMODE = 0>
 __device__ __forceinline__ void tile_pass_workgroup(const TilePassArgs &a, int slot, bool first, bool leave_image,
-                                                    bool mark_big = false, bool wt = false) {
+                                                    bool mark_big = false, bool wt = false, bool leave_sse = false) {
     constexpr int CAP = PHASE == 1 ? GI2D_SMALL_CAP : GI2D_TILE_LIST_CAP;
     __shared__ FusedLdsT<CAP> sm;
     int tile;
@@ -287,11 +287,11 @@ __device__ __forceinline__ void tile_pass_workgroup(const TilePassArgs &a, int s
     if (WTMODE == 1 || (WTMODE == 2 && wt))  // workgroup-uniform (launch-uniform)
         fused_tile<MODE, CAP, PHASE == 2 ? 1 : GI2D_FWD_UNROLL, INBOX, WTMODE != 0>(
             sm, tile, a.tiles_x, a.tiles_y, a.img_w, a.img_h, recs, a.lists, a.tile_bins, a.partial_g, a.partial_big, a.status,
-            a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib, leave_image);
+            a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib, leave_image, leave_sse);
     else
         fused_tile<MODE, CAP, PHASE == 2 ? 1 : GI2D_FWD_UNROLL, INBOX, false>(
             sm, tile, a.tiles_x, a.tiles_y, a.img_w, a.img_h, recs, a.lists, a.tile_bins, a.partial_g, a.partial_big, a.status,
-            a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib, leave_image);
+            a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib, leave_image, leave_sse);
 }
 
 // Phase 2 finds nothing to do on the scenes the two-phase form is for (large images: sparse rows), and ten thousand
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(256, GI2D_PHASE_OCC(PHASE)) void fast_fwdbwd_kernel
         while (todo) {  // workgroup-uniform: every wave computed the same mask
             const int slot = s0 + __builtin_ctzll(todo) * stride;
             todo &= todo - 1;
-            tile_pass_workgroup<MODE, PHASE>(a, slot, false, a.leave_image != 0);
+            tile_pass_workgroup<MODE, PHASE>(a, slot, false, (a.leave_image & 1) != 0, false, false, (a.leave_image & 2) != 0);
             __syncthreads();  // the next tile stages into the same LDS
         }
     } else {
@@ -348,7 +348,8 @@ __global__ __launch_bounds__(256, GI2D_PHASE_OCC(PHASE)) void fast_fwdbwd_kernel
         // (the small form of a single LARGE image -- phase 1 of two launches at 2040x1356 -- measured with write-through
         // rows, image and both: 54.97 -> 55.6-55.7 us; seven residency rounds overlap their stores already)
         tile_pass_workgroup<MODE, PHASE, INBOX, INBOX ? 1 : (PHASE == 0 ? 2 : 0)>(
-            a, (int)blockIdx.x, blockIdx.x == 0, a.leave_image != 0, tiles > GI2D_TWO_PHASE_TILES, a.write_through != 0);
+            a, (int)blockIdx.x, blockIdx.x == 0, (a.leave_image & 1) != 0, tiles > GI2D_TWO_PHASE_TILES, a.write_through != 0,
+            (a.leave_image & 2) != 0);
     }
 }
 
@@ -999,7 +1000,7 @@ int gi2d_fast_rasterize_forward_backward(int n, int tiles_x, int tiles_y, unsign
                                          float grad_scale, float *tile_sse, void *ws, size_t ws_bytes,
                                          int32_t *status, float *out_img, gi2d_stream_t st) {
     return gi2d::fast_forward_backward_form(n, tiles_x, tiles_y, w_, h, background, v_output, target, grad_scale, tile_sse,
-                                            ws, ws_bytes, status, out_img, st, -1, nullptr, false);
+                                            ws, ws_bytes, status, out_img, st, -1, nullptr, false, false);
 }
 }  // extern "C"
 
@@ -1010,7 +1011,7 @@ namespace gi2d {
 int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned w_, unsigned h, const float *background,
                                const float *v_output, const float *target, float grad_scale, float *tile_sse, void *ws,
                                size_t ws_bytes, int32_t *status, float *out_img, gi2d_stream_t st, int form,
-                               float4 *inbox, bool leave_image) {
+                               float4 *inbox, bool leave_image, bool leave_sse) {
     int rc = check_ws("fast rasterize forward+backward: workspace too small", ws, ws_bytes, n, tiles_x, tiles_y);
     if (rc != GI2D_OK) return rc;
     const long long t = (long long)tiles_x * tiles_y;
@@ -1032,7 +1033,7 @@ int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned w_, uns
                                     v_output ? v_output : target, v_output ? 0.f : grad_scale,
                                     v_output ? nullptr : tile_sse);
     a.write_through = wt ? 1 : 0;
-    a.leave_image = leave_image ? 1 : 0;
+    a.leave_image = (leave_image ? 1 : 0) | (leave_sse && target ? 2 : 0);
     const dim3 grid((unsigned)t), block(256);
     if (form < 0) form = pass_form_override() >= 0 ? pass_form_override() : 1;
     if (two_phase_tile_pass(t) && form >= 1) {

@@ -393,6 +393,9 @@ __device__ __forceinline__ FillPending fill_diff_begin(int g, bool member, int m
     }
     prev_box[g] = make_int4(nw.x, nw.y, f.pool, cap);
     if (!member) return f;  // its old entries are dropped by the tile pass (they fail the membership test)
+#ifdef GI2D_KNOCK_BOX_FILL /* development aid, WRONG RESULTS (a changed box enters no tile): the bound of what the walks cost */
+    if constexpr (INBOX) return f;
+#endif
     f.omnx = old.x & 0xffff, f.omxx = (int)((unsigned)old.x >> 16), f.omny = old.y & 0xffff,
     f.omxy = (int)((unsigned)old.y >> 16);
     f.mnx = mnx, f.mny = mny;
@@ -706,6 +709,42 @@ __device__ __forceinline__ HeadRow head_row_for(const int32_t *__restrict__ list
     if (tile != slot) h = head_row_load(lists, tile, inbox);  // workgroup-uniform
     return h;
 }
+// Rank of an id among ALL candidates ids[0 .. count_all) -- what an appended entry or an entrant needs (whole waves;
+// `has`: this lane holds such an id `g`, whose rank it receives).  A lane used to walk the candidates itself, one LDS
+// read per trip (75 on the bench scene) with the other 63 lanes of its wave in tow, and the tile's workgroup waited for
+// that wave at the barrier behind the head.  A wave usually holds one to three such ids: it takes them in turn,
+// wave-uniform, reads the candidates lane-parallel (ids[lane + 64 k]; dropped entries read as -1 = 0xffffffff) and counts
+// the smaller ones with ballots -- one round of LDS reads per id.  Where most of a wave's entries are appended ones (a
+// row's first pass after gi2d_fast_workspace_init) the lanes' own walks, all side by side, are the shorter way.  The
+// ranks are the same integers either way.
+#ifndef GI2D_HEAD_BALLOT_IDS /* (development aid: 0 leaves every id to its lane's walk) */
+#define GI2D_HEAD_BALLOT_IDS 8 /* ids per wave up to which they are ranked in turn: an id costs ceil(count_all / 64)
+                                  LDS rounds, the lanes' walks count_all trips for all of them together */
+#endif
+__device__ __forceinline__ void wave_rank_all(const int *ids, int count_all, bool has, int g, int &rank) {
+    unsigned long long m = __ballot(has);
+    if (m == 0ull) return;
+    const int lane = threadIdx.x & 63;
+    if (__popcll(m) > GI2D_HEAD_BALLOT_IDS) {
+        if (has) {
+            int r = 0;
+            for (int q = 0; q < count_all; ++q) r += ((unsigned)ids[q] < (unsigned)g) ? 1 : 0;
+            rank = r;
+        }
+        return;
+    }
+    do {
+        const int src = __builtin_ctzll(m);
+        m &= m - 1ull;
+        const unsigned x = (unsigned)wave_read_lane(g, src);
+        int r = 0;
+        for (int b = 0; b < count_all; b += 64) {
+            const unsigned v = b + lane < count_all ? (unsigned)ids[b + lane] : 0xffffffffu;
+            r += __popcll(__ballot(v < x));
+        }
+        if (lane == src) rank = r;
+    } while (m != 0ull);
+}
 // The general form of the head for a row of more than 64 candidates: EPT = list entries per lane.  A row of at most 256
 // candidates -- every tile of the bench scene, nearly every tile of a trained one -- is served by the EPT = 1
 // instantiation, whose per-lane state is scalars and which has none of the `u < rounds` bookkeeping of the four-entry
@@ -836,6 +875,14 @@ __device__ __forceinline__ int tile_list_head_rows(int *ids, int *grp, int tile,
 #pragma unroll
     for (int u = 0; u < EPT; ++u) before[u] = wave_read_lane(incl - cnt, wv_u + 4 * u);
     const bool clean = len == count && sorted == count && !any_in;  // nothing dropped, nothing appended: rank == position
+#ifdef GI2D_INBOX_STATS /* development aid: tiles that leave the clean path / with an entrant / with a dropped entry */
+    if (tid == 0 && !clean) {
+        int32_t *row0 = row - (size_t)tile * GI2D_FAST_LROW;
+        atomicAdd(&row0[2], 1);
+        if (any_in) atomicAdd(&row0[3], 1);
+        if (len - (count_all - count) != count) atomicAdd(&row0[4], 1);  // (survivors of the row's own entries)
+    }
+#endif
     if (tid == 0) {
         // an overflowed row keeps its count: it has lost entries, so every pass flags it until the workspace is emptied
         if (hdr_count <= GI2D_FAST_C && (hdr_count != len || hdr_sorted != len)) {
@@ -853,25 +900,30 @@ __device__ __forceinline__ int tile_list_head_rows(int *ids, int *grp, int tile,
         return len;
     }
     // (the optimistic staging was complete at the barrier above: what follows overwrites it in program order)
+    // ids are unique within a row, so "smaller" needs no tie rule; dropped entries read as -1 = 0xffffffff
 #pragma unroll
     for (int u = 0; u < EPT; ++u) {
-        if (u >= rounds || !keep[u]) continue;
+        if (u >= rounds) continue;  // tile-uniform
         const int e = tid + 256 * u, g = my_id[u];
-        // ids are unique within a row, so "smaller" needs no tie rule; dropped entries read as -1 = 0xffffffff
-        int rank, lo, hi;
-        if (e < sorted)
-            rank = before[u] + pos[u], lo = sorted, hi = count_all;
-        else
-            rank = 0, lo = 0, hi = count_all;
-        for (int q = lo; q < hi; ++q) rank += ((unsigned)ids[q] < (unsigned)g) ? 1 : 0;
-        const bool in_place = e < sorted && rank == e;  // an entry of the ascending part that nothing in front of it moved
-        if (!in_place) row[GI2D_FAST_HDR + rank] = g;
-        // ... and whose optimistic staging at rank = position (before the barrier) therefore already is the final one
-        if (!(OPTIMISTIC && u == 0 && in_place)) put(rank, g, u == 0 ? st0 : prep(g, load_record(recs, g)));
+        // an entry of the ascending part: the survivors in front of it plus the smaller APPENDED ids (a tile-uniform
+        // walk over the few of them; lanes without such an entry run along and drop the number)
+        int rank = before[u] + pos[u];
+        if (__ballot(keep[u] && e < sorted) != 0ull)
+            for (int q = sorted; q < count_all; ++q) rank += ((unsigned)ids[q] < (unsigned)g) ? 1 : 0;
+        // an appended entry: against everything, by its wave
+        wave_rank_all(ids, count_all, keep[u] && e >= sorted, g, rank);
+        if (keep[u]) {
+            const bool in_place = e < sorted && rank == e;  // an entry of the ascending part that nothing in front of it moved
+            if (!in_place) row[GI2D_FAST_HDR + rank] = g;
+            // ... and whose optimistic staging at rank = position (before the barrier) therefore already is the final one
+            if (!(OPTIMISTIC && u == 0 && in_place)) put(rank, g, u == 0 ? st0 : prep(g, load_record(recs, g)));
+        }
     }
-    if (ent_id >= 0 && ent_at < GI2D_FAST_C) {  // the entrants: ranked against everything
-        int rank = 0;
-        for (int q = 0; q < count_all; ++q) rank += ((unsigned)ids[q] < (unsigned)ent_id) ? 1 : 0;
+    const bool has_ent = ent_id >= 0 && ent_at < GI2D_FAST_C;
+    int ent_rank = 0;
+    if (any_in) wave_rank_all(ids, count_all, has_ent, ent_id, ent_rank);  // the entrants: ranked against everything
+    if (has_ent) {
+        int rank = ent_rank;
         row[GI2D_FAST_HDR + rank] = ent_id;
         put(rank, ent_id, st_in);
         int at = ent_at + 1;
@@ -927,10 +979,21 @@ __device__ __forceinline__ int tile_list_head(int *ids, int *grp, int tile, int 
             const int len = __popcll(km);
             int rank = lane;
             if (!(len == count && sorted == count)) {  // something was dropped or appended: rank = smaller survivors
-                ids[lane] = keep ? g : -1;             // (ids are unique; dropped entries read as 0xffffffff)
-                __builtin_amdgcn_wave_barrier();
-                rank = 0;
-                for (int q = 0; q < count; ++q) rank += ((unsigned)ids[q] < (unsigned)g) ? 1 : 0;
+                // (ids are unique; dropped entries read as 0xffffffff.)  Register to register: a survivor of the
+                // ascending part has the survivors of that part in front of it, plus the smaller appended ones; the
+                // appended survivors -- a few -- are taken in turn, each ranked against the whole wave by one ballot.
+                const unsigned gk = keep ? (unsigned)g : 0xffffffffu;
+                const unsigned long long asc = sorted >= 64 ? ~0ull : (1ull << sorted) - 1ull;
+                rank = __popcll(km & asc & lanemask_lt());
+                for (unsigned long long m = km & ~asc; m != 0ull; m &= m - 1ull) {
+                    const int src = __builtin_ctzll(m);
+                    const unsigned x = (unsigned)wave_read_lane((int)gk, src);
+                    const int r = __popcll(__ballot(gk < x));
+                    if (lane < sorted)
+                        rank += x < gk ? 1 : 0;
+                    else if (lane == src)
+                        rank = r;
+                }
                 const bool in_place = lane < sorted && rank == lane;
                 if (keep && !in_place) row[GI2D_FAST_HDR + rank] = g;
             }

@@ -131,15 +131,21 @@ static_assert(offsetof(FusedLdsSmall, slot) >= offsetof(FusedLdsSmall, part) &&
 // and squared error come from the pixel in registers, so every other result is that of the storing pass, from the same
 // instructions (a run-time switch on purpose: ONE body serves the iterations that store and those that do not, so a call
 // of K iterations stays bitwise equal to K calls of one).
+// leave_sse (MODE 1; workgroup-uniform like leave_image): tile_sse[tile] is neither summed nor stored -- a lane exchange,
+// a wave sum, an LDS round and a store per tile that only the best-model decision of the update kernel reads on the
+// device.  A fit that tracks no best model asks for the sums in its call's last pass only, which is what its caller sees.
 template <int MODE, int CAP = GI2D_TILE_LIST_CAP, int FWD_UNROLL = GI2D_FWD_UNROLL, bool INBOX = false, bool WT = false>
 __device__ __forceinline__ void fused_tile(
     FusedLdsT<CAP> &sm, int tile, int tiles_x, int tiles_y, int img_w, int img_h, const float4 *__restrict__ recs,
     int32_t *__restrict__ lists, int2 *__restrict__ tile_bins,
     float4 *__restrict__ partial_g, float4 *__restrict__ partial_big, int32_t *__restrict__ status,
     float *__restrict__ out_img, const float *__restrict__ vsrc, float grad_scale, float *__restrict__ tile_sse,
-    const HeadRow head_row, const Inbox &ib, bool leave_image = false) {
+    const HeadRow head_row, const Inbox &ib, bool leave_image = false, bool leave_sse = false) {
 #ifdef GI2D_KNOCK_CALL_STORES /* development aid: what the stores a fitting call can leave out cost at most (no image at all) */
     leave_image = true;
+#endif
+#ifdef GI2D_KEEP_SSE /* development aid: every pass sums and stores its tile's squared error */
+    leave_sse = false;
 #endif
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int pool_rows = tiles_x * tiles_y * GI2D_TILE_LIST_CAP;  // rows of `partial_big`, the row pool (PrevBox)
@@ -263,9 +269,11 @@ __device__ __forceinline__ void fused_tile(
         }
         // summed in COLUMN order within each pixel row, as every round has (the per-tile squared errors decide the
         // best-model snapshot: a fit stays bit-identical to round 5's): lane r of a row fetches column r's term
-        sse = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * ((tid & 48) | fwd_col_lane(tid & 15)), __float_as_int(sse)));
-        sse = wave_sum_dpp(sse);
-        if (lane == 0) sm.sse_w[wv] = sse;
+        if (!leave_sse) {
+            sse = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * ((tid & 48) | fwd_col_lane(tid & 15)), __float_as_int(sse)));
+            sse = wave_sum_dpp(sse);
+            if (lane == 0) sm.sse_w[wv] = sse;
+        }
     }
     // the backward's item scan starts here, ahead of the barrier that is needed anyway
     const unsigned cull = tid < len ? sm.cullw[tid] : 0u;
@@ -283,12 +291,19 @@ __device__ __forceinline__ void fused_tile(
     bwd_publish_pixel(sm, lx, ly, v0, v1, v2, 0.f);
     float4 *dst = nullptr;
     if (tid < len) dst = partial_row(sm.slot[tid], partial_g, partial_big, pool_rows, status);
-    bwd_run_tile<false, false, true, WT>(sm, len, cull, 0, tx0, ty0, dst, scan_incl, sm.scan_w, partial_g);
+    // (INBOX: the pass that only gi2d_train_steps issues, between two update kernels of a fit -- its rows' v_opacity word
+    // has no reader, so the hand-off's division is left out; every other instantiation serves the reduce calls as well)
+#ifdef GI2D_KEEP_VOPAC /* development aid: the division in every instantiation */
+    constexpr bool NO_VOPAC = false;
+#else
+    constexpr bool NO_VOPAC = INBOX;
+#endif
+    bwd_run_tile<false, false, true, WT, NO_VOPAC>(sm, len, cull, 0, tx0, ty0, dst, scan_incl, sm.scan_w, partial_g);
     GI2D_TRACE(10);
     GI2D_TRACE_VALUE(14, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4));   // HW_REG_HW_ID
     GI2D_TRACE_VALUE(15, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20));  // HW_REG_XCC_ID
     GI2D_TRACE_VALUE(4, (unsigned long long)L);
-    if (MODE == 1 && tid == 0) tile_sse[tile] = (sm.sse_w[0] + sm.sse_w[1]) + (sm.sse_w[2] + sm.sse_w[3]);
+    if (MODE == 1 && tid == 0 && !leave_sse) tile_sse[tile] = (sm.sse_w[0] + sm.sse_w[1]) + (sm.sse_w[2] + sm.sse_w[3]);
     // "No intersection at all" is a global property: see fast_fwd_kernel
     if (tid == 0 && L > 0) status[0] = 1;
 }

@@ -636,7 +636,10 @@ __device__ __forceinline__ void bwd_item_columns(const BwdItemIn &in, BwdItemAcc
     } while (rec <= in.rec_end);
 }
 
-template <bool WITH_ABS, bool USE_FIDX = true, bool PRESCANNED = false, bool WT = false, class Lds = BwdLds<WITH_ABS, USE_FIDX>>
+// NO_VOPAC: the rows' v_opacity word is left as the moment T0 (no division by the opacity) -- for a caller whose rows
+// only ever reach a fitting update kernel, none of which reads that word (the opacity is not a fitted parameter).
+template <bool WITH_ABS, bool USE_FIDX = true, bool PRESCANNED = false, bool WT = false, bool NO_VOPAC = false,
+          class Lds = BwdLds<WITH_ABS, USE_FIDX>>
 __device__ __forceinline__ void bwd_run_tile(Lds &sm, int len, unsigned cull, int list_base, float tx0, float ty0,
                                              float4 *__restrict__ dst, unsigned long long prescan_incl = 0ull,
                                              const int *prescan_wsum = nullptr, const void *wt_base = nullptr) {
@@ -818,7 +821,7 @@ __device__ __forceinline__ void bwd_run_tile(Lds &sm, int len, unsigned cull, in
                 acc[2] *= -0.5f;                                          // sum 0.5 v_sigma dx dx
                 acc[3] *= -0.5f;                                          // sum 0.5 v_sigma dx dy
                 acc[4] *= -0.5f;                                          // sum 0.5 v_sigma dy dy
-                acc[8] = (acc[8] != 0.f) ? acc[8] / opac : 0.f;           // v_opacity = sum vis*v_alpha (backward.cu:961)
+                if (!NO_VOPAC) acc[8] = (acc[8] != 0.f) ? acc[8] / opac : 0.f;  // v_opacity = sum vis*v_alpha (backward.cu:961)
             }
             if (my_lo < round0) {  // an earlier round already stored part of this row
                 wt_drain<WT>();

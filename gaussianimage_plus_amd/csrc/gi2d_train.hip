@@ -1674,13 +1674,14 @@ static int single_steps(const gi2d_train_state *s, const gi2d_train_loss *loss, 
         // Outputs the caller reads behind the call are stored by the call's LAST render only: out_img by the last tile
         // pass, xys / num_tiles_hit by the last projection -- the last binning update kernel (iteration count - 2; the
         // opening projection kernel when count == 1), in a quantised fit the last iteration's own projection kernel.
+        // The per-tile squared errors likewise, unless the update kernel reads them (a tracked best model).
         const bool last = it + 1 == count;
         if (quantised) train_launch_project_fill_quant(s->kind, p, st, last);
         const unsigned w = (unsigned)s->img_width, h = (unsigned)s->img_height;
         if (!loss_route) {
             rc = fast_forward_backward_form(s->num_points, p.tx, p.ty, w, h, nullptr, nullptr, s->gt, p.grad_scale,
                                             s->tile_sse, s->workspace, s->workspace_bytes, s->status, s->out_img, st_, form,
-                                            it > 0 ? inbox : nullptr, !last);
+                                            it > 0 ? inbox : nullptr, !last, !last && p.u.best.sse == nullptr);
         } else {
             rc = gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, w, h, nullptr, s->workspace, s->workspace_bytes,
                                              s->status, nullptr, nullptr, s->out_img, st_);

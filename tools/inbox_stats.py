@@ -51,3 +51,5 @@ print(f"  entered tiles via the inbox    {d[9] / steps:9.1f}")
 print(f"  entered tiles via the header   {d[10] / steps:9.1f}   (not a neighbour {d[11] / steps:.1f}, neighbour without rank {d[12] / steps:.1f})")
 print(f"  waves waiting for an atomic    {d[7] / steps:9.1f}")
 print(f"  entrants taken in by the tiles {(d[5] + d[6]) / steps:9.1f}   (second and later ones of a lane's eight slots: {d[6] / steps:.1f})")
+print(f"  tiles off the head's clean path {d[2] / steps:8.1f}   (of {fit.tx * fit.ty}: an entrant in the inbox {d[3] / steps:.1f}, "
+      f"an entry dropped {d[4] / steps:.1f}; the rest: appended through the header only)")
