@@ -1239,28 +1239,10 @@ def batch_shape(headers, views=None) -> Tuple[int, int]:
     return size
 
 
-class _CPicture(C.Structure):
-    """struct gi2d_codec_picture of include/gi2d.h."""
-    _fields_ = [("kind", C.c_int), ("num_points", C.c_int), ("xy_bits", C.c_int), ("p0_bits", C.c_int),
-                ("p1_bits", C.c_int), ("color_bits", C.c_int), ("side", C.c_float * 16), ("payload", C.c_void_p),
-                ("payload_bytes", C.c_size_t), ("clip_coe", C.c_float), ("img_height", C.c_uint), ("img_width", C.c_uint),
-                ("view", C.c_int), ("x0", C.c_float), ("y0", C.c_float), ("scale", C.c_float), ("radius_clip", C.c_float),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("status", C.c_void_p)]
-
-
-class _CAffine(C.Structure):
-    """struct gi2d_codec_affine of include/gi2d.h: the map of a picture whose descriptor says view = 2."""
-    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("b", C.c_float * 4), ("prefilter", C.c_float * 3)]
-
-
-class _CRansStream(C.Structure):
-    """struct gi2d_codec_rans_stream of include/gi2d.h."""
-    _fields_ = [("kind", C.c_int), ("num_points", C.c_int), ("xy_bits", C.c_int), ("p0_bits", C.c_int),
-                ("p1_bits", C.c_int), ("color_bits", C.c_int), ("chunk_log2", C.c_int), ("coded_mask", C.c_uint),
-                ("delta_mask", C.c_uint), ("tables", C.c_void_p), ("tables_bytes", C.c_size_t),
-                ("directory", C.c_void_p), ("chunk_data", C.c_void_p), ("chunk_data_bytes", C.c_size_t),
-                ("max_chunk_bytes", C.c_size_t), ("payload", C.c_void_p), ("payload_bytes", C.c_size_t),
-                ("status", C.c_void_p)]
+# the structures of include/gi2d.h, generated from it (_abi.py)
+_CPicture = _lib.struct("gi2d_codec_picture")
+_CAffine = _lib.struct("gi2d_codec_affine")  # the map of a picture whose descriptor says view = 2
+_CRansStream = _lib.struct("gi2d_codec_rans_stream")
 
 
 def expansion_groups(headers) -> List[List[int]]:

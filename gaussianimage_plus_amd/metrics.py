@@ -34,10 +34,7 @@ MAX_BATCH = 64  # GI2D_SSIM_MAX_BATCH
 RESULT_FLOATS = 64  # GI2D_SSIM_RESULT_FLOATS: value, 3 channel values, [5][3] ssim, cs, d/d ssim, d/d cs
 
 
-class _Pair(C.Structure):  # struct gi2d_ssim_pair
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("grad_x", C.c_void_p),
-                ("x_stride", C.c_int64 * 3), ("y_stride", C.c_int64 * 3), ("grad_stride", C.c_int64 * 3),
-                ("width", C.c_int32), ("height", C.c_int32)]
+_Pair = _lib.struct("gi2d_ssim_pair")  # generated from include/gi2d.h (_abi.py)
 
 
 def gaussian_taps(win_size: int, win_sigma: float) -> torch.Tensor:

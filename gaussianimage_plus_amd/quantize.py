@@ -54,9 +54,7 @@ def ste(x):
     return x + (torch.round(x) - x).detach()
 
 
-class _QuantSpec(C.Structure):
-    """struct gi2d_quant_spec (include/gi2d.h)."""
-    _fields_ = [("channels", C.c_int32), ("kind", C.c_int32 * 4), ("qmin", C.c_float * 4), ("qmax", C.c_float * 4)]
+_QuantSpec = _lib.struct("gi2d_quant_spec")  # generated from include/gi2d.h (_abi.py)
 
 
 def make_spec(kinds, qmins, qmaxs) -> _QuantSpec:

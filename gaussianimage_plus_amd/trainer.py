@@ -59,56 +59,11 @@ def check_loss_size(loss_type: str, h: int, w: int) -> None:
                          f"got {h}x{w}")
 
 
-class _TrainLoss(C.Structure):
-    """struct gi2d_train_loss (include/gi2d.h), field for field."""
-    _fields_ = [("type", C.c_int), ("lambda_", C.c_float), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-                ("loss_value", C.c_void_p), ("v_output", C.c_void_p)]
-
-
-class _LossImage(C.Structure):
-    """struct gi2d_loss_image (include/gi2d.h), field for field."""
-    _fields_ = [("out_img", C.c_void_p), ("gt", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("v_output", C.c_void_p),
-                ("tile_sse", C.c_void_p), ("loss_value", C.c_void_p), ("workspace", C.c_void_p),
-                ("workspace_bytes", C.c_size_t)]
-
-
-class _TrainState(C.Structure):
-    """struct gi2d_train_state (include/gi2d.h), field for field."""
-    _fields_ = [
-        ("kind", C.c_int), ("num_points", C.c_int), ("img_height", C.c_int), ("img_width", C.c_int),
-        ("clip_coe", C.c_float), ("radius_clip", C.c_float),
-        ("xyz", C.c_void_p), ("chol", C.c_void_p), ("feat", C.c_void_p),
-        ("opacity", C.c_void_p), ("bound", C.c_void_p),
-        ("bound_stride", C.c_int), ("pad0", C.c_int),
-        ("m_xyz", C.c_void_p), ("v_xyz", C.c_void_p), ("m_chol", C.c_void_p), ("v_chol", C.c_void_p),
-        ("m_feat", C.c_void_p), ("v_feat", C.c_void_p),
-        ("gt", C.c_void_p),
-        ("xys", C.c_void_p), ("conics", C.c_void_p),
-        ("radii", C.c_void_p), ("num_tiles_hit", C.c_void_p),
-        ("out_img", C.c_void_p), ("tile_sse", C.c_void_p),
-        ("status", C.c_void_p),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-        ("dbg_grads", C.c_void_p),
-        ("best_xyz", C.c_void_p), ("best_chol", C.c_void_p), ("best_feat", C.c_void_p), ("best_bound", C.c_void_p),
-        ("best_sse", C.c_void_p), ("best_info", C.c_void_p),
-        ("optimizer", C.c_int), ("pad1", C.c_int), ("beta3", C.c_double),
-        ("d_xyz", C.c_void_p), ("d_chol", C.c_void_p), ("d_feat", C.c_void_p),
-        ("pg_xyz", C.c_void_p), ("pg_chol", C.c_void_p), ("pg_feat", C.c_void_p),
-        ("quant", C.c_void_p), ("num_points_dev", C.c_void_p),
-        ("inbox", C.c_void_p), ("inbox_bytes", C.c_size_t),
-    ]
-
-
-class _TrainQuant(C.Structure):
-    """struct gi2d_train_quant (include/gi2d.h), field for field."""
-    _fields_ = [
-        ("xy_bits", C.c_int), ("cov_bits", C.c_int), ("color_bits", C.c_int), ("defer_capacity", C.c_int),
-        ("qparams", C.c_void_p), ("qm", C.c_void_p), ("qv", C.c_void_p), ("range", C.c_void_p),
-        ("qfeat", C.c_void_p), ("partial", C.c_void_p), ("defer", C.c_void_p),
-        ("best_qparams", C.c_void_p), ("dbg_qgrads", C.c_void_p),
-        ("lr", C.c_double * 3), ("eps", C.c_float * 3), ("pad1", C.c_int), ("beta1", C.c_double), ("beta2", C.c_double),
-        ("first_step", C.c_int), ("rot_bits", C.c_int),
-    ]
+# the structures of include/gi2d.h, generated from it (_abi.py): fields by their C names, `lambda` as `lambda_`
+_TrainLoss = _lib.struct("gi2d_train_loss")
+_LossImage = _lib.struct("gi2d_loss_image")
+_TrainState = _lib.struct("gi2d_train_state")
+_TrainQuant = _lib.struct("gi2d_train_quant")
 
 
 # ------------------------------------------------------------------ host-side pieces of densify / prune (any device)
@@ -321,19 +276,24 @@ class NativeFitter:
             _lib.call("gi2d_fast_workspace_init", self.ws.data_ptr(), nbytes, cap, self.tx, self.ty,
                       torch.cuda.current_stream(dev).cuda_stream)
         p = lambda t: t.data_ptr()
-        bp = (lambda t: p(t)) if track_best else (lambda t: None)
-        self.state = _TrainState(
-            _KINDS[kind], n, h, w, float(clip_coe), float(radius_clip), p(self._xyz), p(self._chol), p(self._feat),
-            p(self._opacity), p(self._bound), 3 if self.per_point_bound else 0, 0,
-            p(self._m_xyz), p(self._v_xyz), p(self._m_chol), p(self._v_chol), p(self._m_feat), p(self._v_feat),
-            p(self.gt), p(self.xys), p(self.conics), p(self.radii), p(self.nth), p(self.out_img), p(self.tile_sse),
-            p(self.status), p(self.ws), nbytes, p(self.dbg_grads) if debug_grads else None,
-            bp(getattr(self, "best_xyz", None)), bp(getattr(self, "best_chol", None)),
-            bp(getattr(self, "best_feat", None)), bp(getattr(self, "best_bound", None)),
-            bp(getattr(self, "best_sse", None)), bp(getattr(self, "best_info", None)),
-            1 if optimizer == "adan" else 0, 0, self.betas[2] if optimizer == "adan" else 0.0,
-            *[(p(getattr(self, nm)) if optimizer == "adan" else None)
-              for nm in ("_d_xyz", "_d_chol", "_d_feat", "_pg_xyz", "_pg_chol", "_pg_feat")], None, None, None, 0)
+        # fields by name; one that is not named stays 0 / NULL (pads, quant, num_points_dev, inbox, the options below)
+        state = dict(
+            kind=_KINDS[kind], num_points=n, img_height=h, img_width=w, clip_coe=float(clip_coe),
+            radius_clip=float(radius_clip), xyz=p(self._xyz), chol=p(self._chol), feat=p(self._feat),
+            opacity=p(self._opacity), bound=p(self._bound), bound_stride=3 if self.per_point_bound else 0,
+            m_xyz=p(self._m_xyz), v_xyz=p(self._v_xyz), m_chol=p(self._m_chol), v_chol=p(self._v_chol),
+            m_feat=p(self._m_feat), v_feat=p(self._v_feat), gt=p(self.gt), xys=p(self.xys), conics=p(self.conics),
+            radii=p(self.radii), num_tiles_hit=p(self.nth), out_img=p(self.out_img), tile_sse=p(self.tile_sse),
+            status=p(self.status), workspace=p(self.ws), workspace_bytes=nbytes)
+        if debug_grads:
+            state.update(dbg_grads=p(self.dbg_grads))
+        if track_best:
+            state.update({nm: p(getattr(self, nm)) for nm in ("best_xyz", "best_chol", "best_feat", "best_bound",
+                                                              "best_sse", "best_info")})
+        if optimizer == "adan":
+            state.update({nm: p(getattr(self, "_" + nm)) for nm in ("d_xyz", "d_chol", "d_feat", "pg_xyz", "pg_chol",
+                                                                    "pg_feat")}, optimizer=1, beta3=self.betas[2])
+        self.state = _TrainState(**state)
         self.inbox = None  # the tiles' inboxes (gi2d_train_state::inbox): this fitter's own, from its first multi-iteration call
         self._inbox_looked = False
         if self.device_resident:
@@ -346,11 +306,9 @@ class NativeFitter:
         self.opt_start = 0       # iteration at which the optimizer / StepLR of the gaussians was (re)created
         self._state_ref = C.byref(self.state)
         self._lr3 = (C.c_double * 3)()
-        # train()'s C call (signatures: _lib.SIGNATURES) and its leading arguments: the fused L2 iteration, or below ...
+        # train()'s C call (signatures: include/gi2d.h, through _lib) and its leading arguments: the fused L2 iteration, or below ...
         self._steps = ("gi2d_train_steps", (self._state_ref,))
         self._render_fn = self.lib.gi2d_train_render
-        self._render_fn.argtypes = [C.c_void_p, C.c_void_p]
-        self._render_fn.restype = C.c_int
         self.loss = None  # _TrainLoss of a fitter under another loss than L2: its workspace, the loss word
         if loss_type != "L2":
             nbytes = int(self.lib.gi2d_train_loss_workspace_bytes(h, w, LOSS_TYPES.index(loss_type)))

@@ -214,14 +214,6 @@ def test_batches_on_streams_equal_one_batch(groups):
         assert ra["final_num_gaussians"] == rb["final_num_gaussians"]
 
 
-class _FastImage(C.Structure):
-    """struct gi2d_fast_image (include/gi2d.h), field for field."""
-    _fields_ = [("num_points", C.c_int), ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("img_width", C.c_uint),
-                ("img_height", C.c_uint), ("grad_scale", C.c_float), ("v_output", C.c_void_p), ("target", C.c_void_p),
-                ("tile_sse", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-                ("status", C.c_void_p), ("out_img", C.c_void_p)]
-
-
 @pytest.mark.parametrize("given", [True, False])
 def test_batched_tile_pass_equals_single_image_passes(given):
     """gi2d_fast_rasterize_forward_backward_batched on three scenes == three gi2d_fast_rasterize_forward_backward calls:
@@ -234,6 +226,7 @@ def test_batched_tile_pass_equals_single_image_passes(given):
     import gaussianimage_plus_amd.gsplat.cuda as _C
     from gaussianimage_plus_amd import _lib
     lib = _lib.load()
+    _FastImage = _lib.struct("gi2d_fast_image")
     st = torch.cuda.current_stream().cuda_stream
     scenes = []
     for i, (h, w, n) in enumerate([(96, 160, 3000), (70, 50, 500), (128, 144, 6000)]):
