@@ -174,10 +174,27 @@ struct BatchTable {
 static inline BatchTable carve_batch(void *base, int k) {
     BatchTable b;
     b.head = (BatchHead *)base;
-    b.img = (BatchImage *)((char *)base + align_up(sizeof(BatchHead)));
+    b.img = (BatchImage *)((uintptr_t)base + align_up(sizeof(BatchHead)));  // (an integer sum: a size query's base is null)
     b.bytes = align_up(sizeof(BatchHead)) + align_up((size_t)(k > 0 ? k : 1) * sizeof(BatchImage));
     return b;
 }
+// The tile-pass side of a batch, accumulated image by image on the host: head.tile_start[], the total number of tile
+// workgroups, whether every image has as many tiles as the first, and the images' sizes (the loss route's batch
+// workspace is carved from them; zeros beyond the images added).
+struct BatchLayout {
+    int images = 0, total = 0, tiles0 = 0;
+    bool uniform = true;
+    int heights[GI2D_BATCH_MAX] = {}, widths[GI2D_BATCH_MAX] = {};
+    void add(BatchHead &head, int tiles, int img_h, int img_w) {
+        if (images == 0) tiles0 = tiles;
+        uniform = uniform && tiles == tiles0;
+        heights[images] = img_h, widths[images] = img_w;
+        head.tile_start[images] = total;
+        total += tiles;
+        head.tile_start[++images] = total;  // (entry K = total)
+    }
+    int uniform_tiles() const { return uniform ? tiles0 : 0; }  // the launches' argument: 0 = the images differ
+};
 // Which image does workgroup `block` belong to?  starts[0..K]: ascending, starts[K] = number of workgroups.
 // Wave-uniform result; every wave of the workgroup computes it for itself (one 65-word load, one ballot).
 __device__ __forceinline__ int batch_find(const int *__restrict__ starts, int k_images, int block) {

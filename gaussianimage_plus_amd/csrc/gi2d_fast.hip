@@ -612,15 +612,6 @@ static KernelTimer *next_timer() {
     }
     return t;
 }
-#define GI2D_LAUNCH_TIMED(kernel, grid, block, stream, ...)                                               \
-    do {                                                                                                  \
-        if (KernelTimer *gi2d_t = next_timer()) {                                                         \
-            hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, gi2d_t->begin, gi2d_t->end, 0,          \
-                                  __VA_ARGS__);                                                           \
-        } else {                                                                                          \
-            hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);                              \
-        }                                                                                                 \
-    } while (0)
 
 namespace gi2d {
 // A single-image launch of more tiles than the chip holds at once (six general-form workgroups per CU x 256 CUs) runs in
@@ -636,35 +627,36 @@ static void launch_between(K kernel, dim3 grid, dim3 block, hipStream_t st, hipE
     else
         hipLaunchKernelGGL(kernel, grid, block, 0, st, args...);
 }
+// One tile pass as its launches: `two` -- the small form on `grid`, then the general form on `grid2`, one half of the
+// pass's timer each -- or the one-launch form on `grid`, timed whole.  Either way the pass takes ONE timer (bench.py arms
+// them per tile pass).
+template <class K, class... A>
+static void launch_pass_forms(bool two, K one, K small, K general, dim3 grid, dim3 grid2, hipStream_t st, A... args) {
+    KernelTimer *tm = next_timer();
+    hipEvent_t begin = tm ? tm->begin : nullptr, end = tm ? tm->end : nullptr;
+    if (two) {
+        launch_between(small, grid, dim3(256), st, begin, nullptr, args...);
+        launch_between(general, grid2, dim3(256), st, nullptr, end, args...);
+    } else {
+        launch_between(one, grid, dim3(256), st, begin, end, args...);
+    }
+}
 int launch_tile_pass_batched(int mode, const BatchTable &b, int k_images, int total_blocks, int uniform_tiles,
                              int form, hipStream_t st, bool leave_image) {
     const int leave = leave_image ? 1 : 0;
     if (total_blocks <= 0) return GI2D_OK;
     int xcd_map = 0;  // images placed on the XCDs whole (see the kernel): a multiple of 8
     if (uniform_tiles > 0) xcd_map = k_images & ~7;
-    const dim3 grid((unsigned)total_blocks), block(256);
+    const dim3 grid((unsigned)total_blocks), grid2(phase2_blocks(total_blocks, form == 2));
     const BatchImage *imgs = (const BatchImage *)b.img;
-    if (form != 0) {
-        KernelTimer *tm = next_timer();
-        const dim3 grid2(phase2_blocks(total_blocks, form == 2));
-        if (mode == 0) {
-            launch_between((fast_fwdbwd_batched_kernel<0, 1>), grid, block, st, tm ? tm->begin : nullptr, nullptr, imgs,
-                           b.head, k_images, uniform_tiles, xcd_map, leave);
-            launch_between((fast_fwdbwd_batched_kernel<0, 2>), grid2, block, st, nullptr, tm ? tm->end : nullptr, imgs,
-                           b.head, k_images, uniform_tiles, xcd_map, leave);
-        } else {
-            launch_between((fast_fwdbwd_batched_kernel<1, 1>), grid, block, st, tm ? tm->begin : nullptr, nullptr, imgs,
-                           b.head, k_images, uniform_tiles, xcd_map, leave);
-            launch_between((fast_fwdbwd_batched_kernel<1, 2>), grid2, block, st, nullptr, tm ? tm->end : nullptr, imgs,
-                           b.head, k_images, uniform_tiles, xcd_map, leave);
-        }
-    } else if (mode == 0) {
-        GI2D_LAUNCH_TIMED((fast_fwdbwd_batched_kernel<0, 0>), grid, block, st, imgs, b.head, k_images, uniform_tiles,
-                          xcd_map, leave);
-    } else {
-        GI2D_LAUNCH_TIMED((fast_fwdbwd_batched_kernel<1, 0>), grid, block, st, imgs, b.head, k_images, uniform_tiles,
-                          xcd_map, leave);
-    }
+    if (mode == 0)
+        launch_pass_forms(form != 0, fast_fwdbwd_batched_kernel<0, 0>, fast_fwdbwd_batched_kernel<0, 1>,
+                          fast_fwdbwd_batched_kernel<0, 2>, grid, grid2, st, imgs, b.head, k_images, uniform_tiles, xcd_map,
+                          leave);
+    else
+        launch_pass_forms(form != 0, fast_fwdbwd_batched_kernel<1, 0>, fast_fwdbwd_batched_kernel<1, 1>,
+                          fast_fwdbwd_batched_kernel<1, 2>, grid, grid2, st, imgs, b.head, k_images, uniform_tiles, xcd_map,
+                          leave);
     return check_launch("batched tile pass");
 }
 
@@ -1034,27 +1026,16 @@ int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned w_, uns
                                     v_output ? nullptr : tile_sse);
     a.write_through = wt ? 1 : 0;
     a.leave_image = (leave_image ? 1 : 0) | (leave_sse && target ? 2 : 0);
-    const dim3 grid((unsigned)t), block(256);
     if (form < 0) form = pass_form_override() >= 0 ? pass_form_override() : 1;
-    if (two_phase_tile_pass(t) && form >= 1) {
-        KernelTimer *tm = next_timer();
-        const dim3 grid2(phase2_blocks(t, form == 2));
-        if (v_output) {
-            launch_between(fast_fwdbwd_kernel<0, 1>, grid, block, (hipStream_t)st, tm ? tm->begin : nullptr, nullptr, a);
-            launch_between(fast_fwdbwd_kernel<0, 2>, grid2, block, (hipStream_t)st, nullptr,
-                           tm ? tm->end : nullptr, a);
-        } else {
-            launch_between(fast_fwdbwd_kernel<1, 1>, grid, block, (hipStream_t)st, tm ? tm->begin : nullptr, nullptr, a);
-            launch_between(fast_fwdbwd_kernel<1, 2>, grid2, block, (hipStream_t)st, nullptr,
-                           tm ? tm->end : nullptr, a);
-        }
-    } else if (v_output) {
-        GI2D_LAUNCH_TIMED((fast_fwdbwd_kernel<0, 0>), grid, block, (hipStream_t)st, a);
-    } else if (inbox != nullptr && t <= GI2D_INBOX_MAX_TILES) {
-        GI2D_LAUNCH_TIMED((fast_fwdbwd_kernel<1, 0, true>), grid, block, (hipStream_t)st, a);
-    } else {
-        GI2D_LAUNCH_TIMED((fast_fwdbwd_kernel<1, 0>), grid, block, (hipStream_t)st, a);
-    }
+    const bool two = two_phase_tile_pass(t) && form >= 1;
+    const dim3 grid((unsigned)t), grid2(phase2_blocks(t, form == 2));
+    if (v_output)
+        launch_pass_forms(two, fast_fwdbwd_kernel<0, 0>, fast_fwdbwd_kernel<0, 1>, fast_fwdbwd_kernel<0, 2>, grid, grid2,
+                          (hipStream_t)st, a);
+    else  // (the one-launch form alone takes entrants out of the inboxes)
+        launch_pass_forms(two, inbox != nullptr && t <= GI2D_INBOX_MAX_TILES ? fast_fwdbwd_kernel<1, 0, true>
+                                                                              : fast_fwdbwd_kernel<1, 0>,
+                          fast_fwdbwd_kernel<1, 1>, fast_fwdbwd_kernel<1, 2>, grid, grid2, (hipStream_t)st, a);
     if (background && !leave_image)
         hipLaunchKernelGGL(fast_background_kernel, dim3(256), dim3(256), 0, (hipStream_t)st, (int)w_, (int)h,
                            status, background, out_img);
@@ -1087,8 +1068,7 @@ int gi2d_fast_rasterize_forward_backward_batched(int num_images, const gi2d_fast
     std::memset(&head, 0, sizeof(head));
     std::vector<BatchImage> host_imgs((size_t)num_images);
     std::memset(host_imgs.data(), 0, host_imgs.size() * sizeof(BatchImage));
-    int blocks = 0, tiles0 = 0;
-    bool uniform = true;
+    BatchLayout tiles;
     const bool given = images[0].v_output != nullptr;
     for (int k = 0; k < num_images; ++k) {
         const gi2d_fast_image &im = images[k];
@@ -1111,18 +1091,14 @@ int gi2d_fast_rasterize_forward_backward_batched(int num_images, const gi2d_fast
         host_imgs[k].t = tile_pass_args(w, im.num_points, im.tiles_x, im.tiles_y, (int)im.img_width, (int)im.img_height,
                                         im.status, im.out_img, given ? im.v_output : im.target,
                                         given ? 0.f : im.grad_scale, given ? nullptr : im.tile_sse);
-        head.tile_start[k] = blocks;
-        blocks += (int)t;
-        if (k == 0) tiles0 = (int)t;
-        uniform = uniform && (int)t == tiles0;
+        tiles.add(head, (int)t, (int)im.img_height, (int)im.img_width);
     }
-    head.tile_start[num_images] = blocks;
     BatchTable b = carve_batch(batch, num_images);
     write_batch_table(b, host_imgs.data(), num_images, head, (hipStream_t)st);
-    const int two_phase = batch_pass_begin(batch, blocks, (hipStream_t)st);
-    const int rc = launch_tile_pass_batched(given ? 0 : 1, b, num_images, blocks, uniform ? tiles0 : 0, two_phase,
+    const int two_phase = batch_pass_begin(batch, tiles.total, (hipStream_t)st);
+    const int rc = launch_tile_pass_batched(given ? 0 : 1, b, num_images, tiles.total, tiles.uniform_tiles(), two_phase,
                                             (hipStream_t)st, false);
-    batch_pass_end(batch, b, num_images, blocks, (hipStream_t)st);
+    batch_pass_end(batch, b, num_images, tiles.total, (hipStream_t)st);
     return rc;
 }
 

@@ -176,7 +176,7 @@ struct FastWs {
 };
 static FastWs carve_fast(void *base, int n, int num_tiles) {
     FastWs w;
-    char *b = (char *)base;
+    const uintptr_t b = (uintptr_t)base;  // (an integer: a size query carves from a null base)
     size_t off = 0;
     const size_t t = (size_t)(num_tiles > 0 ? num_tiles : 1), nn = (size_t)(n > 0 ? n : 1);
     // (the inboxes' records -- 128 KB of sparsely used address space per tile -- were part of every workspace in round 5:

@@ -54,7 +54,7 @@ LossWs carve_loss(void *base, int h, int w, const LossTerms &t) {
         ssim_bytes = gi2d_ssim_workspace_bytes(w, h, t.levels, t.win);  // (sets the message for a size it cannot take)
         if (ssim_bytes == 0) return ws;
     }
-    char *b = (char *)base;
+    const uintptr_t b = (uintptr_t)base;  // (an integer: a size query carves from a null base)
     size_t off = 0;
     const size_t plane = loss_align((size_t)h * w * 3 * sizeof(float));
     const size_t tiles = (size_t)((w + GI2D_TILE - 1) / GI2D_TILE) * ((h + GI2D_TILE - 1) / GI2D_TILE);
@@ -68,7 +68,7 @@ LossWs carve_loss(void *base, int h, int w, const LossTerms &t) {
     off += loss_align((GI2D_SSIM_RESULT_FLOATS + 4) * sizeof(float));
     ws.tile_abs = (float *)(b + off);
     off += loss_align(tiles * sizeof(float));
-    ws.ssim = b + off;
+    ws.ssim = (void *)(b + off);
     ws.ssim_bytes = ssim_bytes;
     off += loss_align(ssim_bytes);
     ws.bytes = off;
@@ -96,13 +96,13 @@ LossBatchWs carve_loss_batch(void *base, int k, const int *heights, const int *w
         ssim_bytes = gi2d_ssim_batch_workspace_bytes(k, pairs, t.levels, t.win);  // (sets the message for a size it cannot take)
         if (ssim_bytes == 0) return ws;
     }
-    char *b = (char *)base;
+    const uintptr_t b = (uintptr_t)base;  // (as in carve_loss)
     size_t off = 0;
     ws.results = (float *)(b + off);
     off += loss_align((size_t)k * GI2D_SSIM_RESULT_FLOATS * sizeof(float));
     ws.grad_results = (float *)(b + off);
     off += loss_align((size_t)k * 3 * sizeof(float));
-    ws.ssim = b + off;
+    ws.ssim = (void *)(b + off);
     ws.ssim_bytes = ssim_bytes;
     off += loss_align(ssim_bytes);
     ws.bytes = off;

@@ -15,6 +15,7 @@
 // (models/gaussianimage_cholesky.py:302-317) is folded into the kernels either side of the rasterizer.
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "gi2d_batch.h"
@@ -1341,40 +1342,41 @@ void write_batch_table(const BatchTable &table, const BatchImage *imgs, int k_im
 
 using namespace gi2d;
 
-// kind x (more iterations follow: the update kernel also starts the next one) x optimizer -> GI2D_LAUNCH_RU(K, F, A)
-#define GI2D_DISPATCH_RU2(K, more, adan) \
-    do {                                  \
-        if (more) {                       \
-            if (adan)                     \
-                GI2D_LAUNCH_RU(K, true, true);   \
-            else                          \
-                GI2D_LAUNCH_RU(K, true, false);  \
-        } else {                          \
-            if (adan)                     \
-                GI2D_LAUNCH_RU(K, false, true);  \
-            else                          \
-                GI2D_LAUNCH_RU(K, false, false); \
-        }                                 \
-    } while (0)
-#define GI2D_DISPATCH_RU(kind, more, adan)           \
-    do {                                             \
-        if ((kind) == 2)                             \
-            GI2D_DISPATCH_RU2(kScaleRot, more, adan);   \
-        else if ((kind) == 0)                        \
-            GI2D_DISPATCH_RU2(kCholesky, more, adan);   \
-        else                                         \
-            GI2D_DISPATCH_RU2(kCovariance, more, adan); \
-    } while (0)
+// A run-time choice as a compile-time value: what the three dispatch functions hand to their callback, which names the
+// kernel instantiation with decltype(k)::value.
+template <int V>
+using Int = std::integral_constant<int, V>;
 
-// model of the quantised kernels (1 covariance, 2 rotation-scale) -> GI2D_LAUNCH_QUANT(M)
-#define GI2D_DISPATCH_QUANT(kind)  \
-    do {                           \
-        if ((kind) == 2) {         \
-            GI2D_LAUNCH_QUANT(2);  \
-        } else {                   \
-            GI2D_LAUNCH_QUANT(1);  \
-        }                          \
-    } while (0)
+// model kind -> f(Int<KIND>)
+template <class F>
+static void for_kind(int kind, F f) {
+    if (kind == 2)
+        f(Int<kScaleRot>{});
+    else if (kind == 0)
+        f(Int<kCholesky>{});
+    else
+        f(Int<kCovariance>{});
+}
+template <class F>
+static void for_bool(bool b, F f) {
+    if (b)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+// kind x (more iterations follow: the update kernel also starts the next one) x optimizer -> f(KIND, FILL_NEXT, ADAN)
+template <class F>
+static void for_update_kernel(int kind, bool more, bool adan, F f) {
+    for_kind(kind, [&](auto k) { for_bool(more, [&](auto m) { for_bool(adan, [&](auto a) { f(k, m, a); }); }); });
+}
+// model of the quantised kernels (1 covariance, 2 rotation-scale) -> f(Int<MODEL>)
+template <class F>
+static void for_quant_model(int kind, F f) {
+    if (kind == 2)
+        f(Int<2>{});
+    else
+        f(Int<1>{});
+}
 
 static TrainParams params_of(const gi2d_train_state *s) {
     TrainParams P;
@@ -1555,68 +1557,6 @@ static int quant_of(const gi2d_train_state *s, QuantTrain &Q) {
     return GI2D_OK;
 }
 
-// What the launches on one image need, worked out once per call from a state that passed train_check.
-struct ImagePlan {
-    int tx, ty;
-    FastWs w;
-    float grad_scale;  // of the L2 loss: 2 / (3 H W)
-    UpdateArgs u;
-    QuantTrain q;    // zeros unless the state is quantisation-aware
-    int bs, blocks;  // launch shape of the per-gaussian kernels on this image alone (a batch has one for all its images)
-};
-static int image_plan(const gi2d_train_state *s, ImagePlan &p) {
-    p.tx = (s->img_width + GI2D_TILE - 1) / GI2D_TILE, p.ty = (s->img_height + GI2D_TILE - 1) / GI2D_TILE;
-    p.w = carve_fast(s->workspace, s->num_points, p.tx * p.ty);
-    p.grad_scale = 2.f / (3.f * (float)s->img_height * (float)s->img_width);
-    p.u = update_args_of(s, p.w, p.tx, p.ty);
-    p.bs = per_gaussian_block(s->num_points);
-    p.blocks = (s->num_points + p.bs - 1) / p.bs;
-    std::memset(&p.q, 0, sizeof(QuantTrain));
-    return s->quant ? quant_of(s, p.q) : GI2D_OK;
-}
-
-// activations + projection + fill
-static void train_launch_project_fill(int kind, const ImagePlan &p, hipStream_t st) {
-    const dim3 gg(p.blocks), bb(p.bs);
-    if (kind == 2)
-        hipLaunchKernelGGL(train_project_fill_kernel<kScaleRot>, gg, bb, 0, st, p.u);
-    else if (kind == 0)
-        hipLaunchKernelGGL(train_project_fill_kernel<kCholesky>, gg, bb, 0, st, p.u);
-    else
-        hipLaunchKernelGGL(train_project_fill_kernel<kCovariance>, gg, bb, 0, st, p.u);
-}
-// log range of the current variances (covariance model, start of a call); the closing step (one workgroup) reads the
-// partial rows -- one per wave -- the per-gaussian launch left
-static void train_launch_quant_range(const ImagePlan &p, hipStream_t st) {
-    const AdamStep z = idle_adam_step();
-    hipLaunchKernelGGL(train_quant_range_kernel, dim3(p.blocks), dim3(p.bs), 0, st, p.u, p.q);
-    hipLaunchKernelGGL(train_quant_finish_kernel<0>, dim3(1), dim3(256), 0, st, p.blocks * (p.bs / 64), p.u, p.q, z, z, z,
-                       z, 0);
-}
-// activations / quantisers + projection + fill
-static void train_launch_project_fill_quant(int kind, const ImagePlan &p, hipStream_t st, bool store_proj) {
-#define GI2D_LAUNCH_QUANT(M) \
-    hipLaunchKernelGGL(train_project_fill_quant_kernel<M>, dim3(p.blocks), dim3(p.bs), 0, st, p.u, p.q, store_proj ? 1 : 0)
-    GI2D_DISPATCH_QUANT(kind);
-#undef GI2D_LAUNCH_QUANT
-}
-
-// gi2d_train_steps, and with `loss_route` gi2d_train_steps_loss: `count` fitting iterations on one image
-// (gi2d_train_steps_batched issues the same sequence for K images per launch).  A plain fit: project+fill once, then per
-// iteration the tile pass and the update kernel, which also projects and bins the updated gaussians for the following
-// iteration (all but the last) -- 2*count + 1 launches.  A quantisation-aware one (train_iter_quantize): the log range
-// once (covariance model), then per iteration project+fill behind the quantisers, tile pass, update kernel and its
-// closing step.  lr[3] / first_step are host values: learning rates of the xyz / cholesky / colour groups (constant over
-// the call) and the 1-based Adam step count of the first iteration.
-// The fused tile pass: render, L2 gradient and backward in one pass.  The update kernel of a plain fit delivers through
-// the tiles' inboxes, if the caller brought them, when another iteration follows, and the tile pass of that iteration --
-// never the first of a call, which follows the projection kernel -- is the one built to take entrants in.
-// The loss route's: the forward tile pass (out_img stored every time: the loss reads it), the loss launches
-// (csrc/gi2d_loss.hip), the backward tile kernel on the records and lists the forward left; no inbox delivery, no
-// single-pass bracket.  The backward is gi2d_fast_rasterize_backward_tiles, not the one-launch forward+backward with
-// v_output: that call's contract is to leave the gradient rows "exactly as gi2d_fast_rasterize_forward +
-// _backward_tiles(with_abs=0) would for the reduce calls", i.e. this pair IS what the update kernel's inputs are defined
-// by, it runs one binning call per tile pass head as the workspace's contract asks, and it renders once per iteration.
 // One image's gi2d_train_loss on the loss route: its terms and the regions of its workspace.
 static int loss_check(const gi2d_train_state *s, const gi2d_train_loss *loss, TrainEntry entry, LossTerms &terms,
                       LossWs &lw) {
@@ -1640,143 +1580,264 @@ static int loss_copy_v(const gi2d_train_state *s, const gi2d_train_loss *loss, c
     return e == hipSuccess ? GI2D_OK : train_refuse(entry, (int)e, "copy of v_output failed");
 }
 
-static int single_steps(const gi2d_train_state *s, const gi2d_train_loss *loss, bool loss_route, const double *lr,
-                        double beta1, double beta2, float eps, int first_step, int count, gi2d_stream_t st_) {
+// What the launches on one image need, worked out once per call from a state that passed train_check -- every entry's
+// preparation of an image (what an entry tests between train_check and this is its own: lr / first_step, what the images
+// of a batch share).  `loss` is looked at on the loss route alone.
+struct ImagePlan {
+    int tx, ty;
+    FastWs w;
+    float grad_scale;  // of the L2 loss: 2 / (3 H W)
+    UpdateArgs u;
+    QuantTrain q;    // zeros unless the state is quantisation-aware
+    int bs, blocks;  // launch shape of the per-gaussian kernels on this image alone (a batch has one for all its images)
+    LossTerms terms;  // the loss route's: the loss's terms and the regions of its workspace; zeros on the fused route
+    LossWs lw;
+};
+static int image_plan(const gi2d_train_state *s, const gi2d_train_loss *loss, bool loss_route, TrainEntry entry,
+                      ImagePlan &p) {
+    p.terms = LossTerms{}, p.lw = LossWs{};
+    // (a bad loss AND bad quantiser fields: the single-image entries report the former, the batched ones the latter --
+    // as found)
+    const bool loss_first = entry == kSteps;
+    if (loss_route && loss_first)
+        if (const int rc = loss_check(s, loss, entry, p.terms, p.lw)) return rc;
+    p.tx = (s->img_width + GI2D_TILE - 1) / GI2D_TILE, p.ty = (s->img_height + GI2D_TILE - 1) / GI2D_TILE;
+    p.w = carve_fast(s->workspace, s->num_points, p.tx * p.ty);
+    p.grad_scale = 2.f / (3.f * (float)s->img_height * (float)s->img_width);
+    p.u = update_args_of(s, p.w, p.tx, p.ty);
+    p.bs = per_gaussian_block(s->num_points);
+    p.blocks = (s->num_points + p.bs - 1) / p.bs;
+    std::memset(&p.q, 0, sizeof(QuantTrain));
+    if (s->quant)
+        if (const int rc = quant_of(s, p.q)) return rc;
+    return loss_route && !loss_first ? loss_check(s, loss, entry, p.terms, p.lw) : GI2D_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the iteration sequence
+// `count` fitting iterations, written once for the five entries: gi2d_train_steps / gi2d_train_step / gi2d_train_steps_loss
+// drive it with the launch target of one image (OneImage), gi2d_train_steps_batched / gi2d_train_steps_loss_batched with
+// that of K images per launch (ImageBatch); `s` is the state whose kind, optimizer and quantisers speak for the call (a
+// batch's images share them).  A plain fit: project+fill once, then per iteration the tile pass and the update kernel,
+// which also projects and bins the updated gaussians for the following iteration (all but the last) -- 2*count + 1
+// launches.  A quantisation-aware one (train_iter_quantize): the log range once (covariance model), then per iteration
+// project+fill behind the quantisers, tile pass, update kernel and its closing step.  lr[3] / first_step are host values:
+// learning rates of the xyz / cholesky / colour groups (constant over the call) and the 1-based Adam step count of the
+// first iteration.
+// Outputs the caller reads behind the call are stored by the call's LAST render only: out_img by the last tile pass
+// (`last`), xys / num_tiles_hit by the last projection (`store_proj`) -- the last binning update kernel (iteration
+// count - 2; the opening projection kernel, which always stores, when count == 1), in a quantised fit the last iteration's
+// own projection kernel.
+// A target's tile pass is one of two routes.  The fused tile pass: render, L2 gradient and backward in one pass.  The
+// loss route's (a target with a `loss`): the forward tile pass (out_img stored every time: the loss reads it), the loss
+// launches (csrc/gi2d_loss.hip), the backward tile kernel on the records and lists the forward left; no inbox delivery,
+// no tile-pass-form bracket; everything in front of and behind the tile pass is the same launch either way.  The backward
+// is gi2d_fast_rasterize_backward_tiles, not the one-launch forward+backward with v_output: that call's contract is to
+// leave the gradient rows "exactly as gi2d_fast_rasterize_forward + _backward_tiles(with_abs=0) would for the reduce
+// calls", i.e. this pair IS what the update kernel's inputs are defined by, it runs one binning call per tile pass head
+// as the workspace's contract asks, and it renders once per iteration.
+template <class Target>
+static int fit_sequence(const Target &t, const gi2d_train_state *s, const double *lr, double beta1, double beta2,
+                        float eps, int first_step, int count) {
+    const bool quantised = s->quant != nullptr;
+    t.open();
+    for (int it = 0; it < count; ++it) {
+        const bool last = it + 1 == count, more = !last;  // more: the update kernel also starts the next iteration
+        const bool store_proj = quantised ? last : it + 2 == count;
+        if (quantised) t.project_fill_quant(store_proj);
+        const int rc = t.tile_pass(it, last);
+        if (rc != GI2D_OK) return rc;
+        const IterSteps c = iter_steps(s, lr, beta1, beta2, eps, first_step, it);
+        const int step = first_step + it;
+        if (quantised)
+            for_quant_model(s->kind, [&](auto m) { t.template update_quant<decltype(m)::value>(c, step); });
+        else
+            for_update_kernel(s->kind, more, s->optimizer == 1, [&](auto k, auto fill_next, auto adan) {
+                t.template update<decltype(k)::value, decltype(fill_next)::value, decltype(adan)::value>(c.a, step,
+                                                                                                         store_proj);
+            });
+    }
+    return t.close();
+}
+
+// The launch target of ONE image: its argument blocks (UpdateArgs, QuantTrain) travel as kernel arguments.
+struct OneImage {
+    const gi2d_train_state *s;
+    const ImagePlan &p;
+    const gi2d_train_loss *loss;  // the loss route's; null: the fused tile pass
+    hipStream_t st;
+    // a large image's tile passes run as two launches while the previous call on this workspace saw at most one row in
+    // sixteen above the small form's capacity (gi2d_fast.hip: pass_form_begin)
+    int form;
+    // The inboxes: one image of at most GI2D_INBOX_MAX_TILES tiles, i.e. a tile pass of the general form throughout,
+    // whose caller brought the inboxes' buffer (gi2d_train_state::inbox), in a plain fit on the fused route; else null.
+    float4 *inbox;
+
+    // plain: activations + projection + fill, on the gaussians' workgroups alone (the tile-ordering one belongs to the
+    // update kernel); quantised: the log range of the current variances (covariance model; the RS model's ranges are
+    // learned values) -- the closing step (one workgroup) reads the partial rows -- one per wave -- the per-gaussian
+    // launch left
+    void open() const {
+        const dim3 gg(p.blocks), bb(p.bs);
+        if (!s->quant) {
+            for_kind(s->kind, [&](auto k) {
+                hipLaunchKernelGGL(train_project_fill_kernel<decltype(k)::value>, gg, bb, 0, st, p.u);
+            });
+        } else if (s->kind != 2) {
+            const AdamStep z = idle_adam_step();
+            hipLaunchKernelGGL(train_quant_range_kernel, gg, bb, 0, st, p.u, p.q);
+            hipLaunchKernelGGL(train_quant_finish_kernel<0>, dim3(1), dim3(256), 0, st, p.blocks * (p.bs / 64), p.u, p.q, z,
+                               z, z, z, 0);
+        }
+    }
+    // activations / quantisers + projection + fill
+    void project_fill_quant(bool store_proj) const {
+        for_quant_model(s->kind, [&](auto m) {
+            hipLaunchKernelGGL(train_project_fill_quant_kernel<decltype(m)::value>, dim3(p.blocks), dim3(p.bs), 0, st, p.u,
+                               p.q, store_proj ? 1 : 0);
+        });
+    }
+    // The fused pass takes entrants out of the inboxes from the call's second iteration on (the first follows the
+    // projection kernel, which delivers nothing), and is the one built to take them in.  The per-tile squared errors are
+    // left out of passes nobody reads: all but the last, unless the update kernel reads them (a tracked best model).
+    int tile_pass(int it, bool last) const {
+        const unsigned w = (unsigned)s->img_width, h = (unsigned)s->img_height;
+        if (!loss)
+            return fast_forward_backward_form(s->num_points, p.tx, p.ty, w, h, nullptr, nullptr, s->gt, p.grad_scale,
+                                              s->tile_sse, s->workspace, s->workspace_bytes, s->status, s->out_img, st, form,
+                                              it > 0 ? inbox : nullptr, !last, !last && p.u.best.sse == nullptr);
+        int rc = gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, w, h, nullptr, s->workspace, s->workspace_bytes,
+                                             s->status, nullptr, nullptr, s->out_img, st);
+        if (rc == GI2D_OK)
+            rc = loss_launch(s->out_img, s->gt, s->img_height, s->img_width, p.terms, p.lw, p.lw.v, s->tile_sse,
+                             loss->loss_value, st);
+        if (rc == GI2D_OK)
+            rc = gi2d_fast_rasterize_backward_tiles(s->num_points, p.tx, p.ty, w, h, nullptr, p.lw.v, 0, s->workspace,
+                                                    s->workspace_bytes, st);
+        return rc;
+    }
+    // + 1: the workgroup that orders the tiles.  An update kernel that starts the next iteration delivers through the
+    // tiles' inboxes, if the call has them (the INBOX instantiation).
+    template <int K, bool FILL_NEXT, bool ADAN>
+    void update(const AdamStep *a, int step, bool store_proj) const {
+        const dim3 gg(p.blocks + 1), bb(p.bs);
+        if (FILL_NEXT && inbox != nullptr)
+            hipLaunchKernelGGL((train_reduce_update_kernel<K, FILL_NEXT, ADAN, FILL_NEXT>), gg, bb, 0, st, p.u, a[0], a[1],
+                               a[2], step, store_proj ? 1 : 0);
+        else
+            hipLaunchKernelGGL((train_reduce_update_kernel<K, FILL_NEXT, ADAN>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step,
+                               store_proj ? 1 : 0);
+    }
+    // the quantised update kernel (no tile-ordering workgroup) and its closing step
+    template <int M>
+    void update_quant(const IterSteps &c, int step) const {
+        hipLaunchKernelGGL(train_reduce_update_quant_kernel<M>, dim3(p.blocks), dim3(p.bs), 0, st, p.u, p.q, c.a[0], c.a[1],
+                           c.a[2], step);
+        hipLaunchKernelGGL(train_quant_finish_kernel<M>, dim3(1), dim3(256), 0, st, p.blocks * (p.bs / 64), p.u, p.q,
+                           c.a[1], c.aq[0], c.aq[1], c.aq[2], step);
+    }
+    int close() const {
+        if (!loss) {
+            single_pass_end(s->workspace, p.w, (long long)p.tx * p.ty, st);
+            return check_launch("train steps");
+        }
+        const int rc = loss_copy_v(s, loss, p.lw, kSteps, st);
+        return rc != GI2D_OK ? rc : check_launch("train steps (loss)");
+    }
+};
+
+// The launch target of K images per launch: the `_batched_kernel` forms, which find their image's argument blocks in the
+// table by workgroup index.  Every per-gaussian launch runs on the table's one grid `gg`: each image's workgroups and,
+// in a plain fit, its tile-ordering one (idle in project+fill); `gi`: the closing steps, one workgroup per image.  No
+// inbox delivery, and no pass leaves the per-tile squared errors out.
+struct ImageBatch {
+    const gi2d_train_state *const *states;  // states[0] speaks for what the images share
+    const gi2d_train_loss *const *losses;   // the loss route's; null: the fused tile pass
+    const ImagePlan *plans;
+    void *batch;
+    BatchTable b;
+    const BatchImage *imgs;  // = b.img, b.head->pg_start: what every per-gaussian kernel is given
+    const int *pg_start;
+    int k_images, tile_blocks, uniform_tiles;
+    dim3 gg, bb, gi;
+    int form;  // of the fused tile pass (gi2d_fast.hip: batch_pass_begin)
+    const gi2d_ssim_pair *pairs;
+    LossBatchWs bw;
+    hipStream_t st;
+
+    void open() const {
+        const int kind = states[0]->kind;
+        if (!states[0]->quant) {
+            for_kind(kind, [&](auto k) {
+                hipLaunchKernelGGL(train_project_fill_batched_kernel<decltype(k)::value>, gg, bb, 0, st, imgs, pg_start,
+                                   k_images);
+            });
+        } else if (kind != 2) {
+            const AdamStep z = idle_adam_step();
+            hipLaunchKernelGGL(train_quant_range_batched_kernel, gg, bb, 0, st, imgs, pg_start, k_images);
+            hipLaunchKernelGGL(train_quant_finish_batched_kernel<0>, gi, dim3(256), 0, st, imgs, pg_start, (int)bb.x / 64, z,
+                               z, z, z, 0);
+        }
+    }
+    void project_fill_quant(bool store_proj) const {
+        for_quant_model(states[0]->kind, [&](auto m) {
+            hipLaunchKernelGGL(train_project_fill_quant_batched_kernel<decltype(m)::value>, gg, bb, 0, st, imgs, pg_start,
+                               k_images, store_proj ? 1 : 0);
+        });
+    }
+    // the fused batched tile pass, or the batched forward tile kernel, the batched loss launches and the batched backward
+    // tile kernel (gi2d_fast.hip, gi2d_loss.hip)
+    int tile_pass(int, bool last) const {
+        if (!losses) return launch_tile_pass_batched(1, b, k_images, tile_blocks, uniform_tiles, form, st, !last);
+        int rc = launch_fwd_tiles_batched(b, k_images, tile_blocks, uniform_tiles, st);
+        if (rc == GI2D_OK) rc = loss_launch_batched(b, k_images, tile_blocks, plans[0].terms, pairs, bw, st);
+        if (rc == GI2D_OK) rc = launch_bwd_tiles_batched(b, k_images, tile_blocks, uniform_tiles, st);
+        return rc;
+    }
+    template <int K, bool FILL_NEXT, bool ADAN>
+    void update(const AdamStep *a, int step, bool store_proj) const {
+        hipLaunchKernelGGL((train_reduce_update_batched_kernel<K, FILL_NEXT, ADAN>), gg, bb, 0, st, imgs, pg_start, k_images,
+                           a[0], a[1], a[2], step, store_proj ? 1 : 0);
+    }
+    template <int M>
+    void update_quant(const IterSteps &c, int step) const {
+        hipLaunchKernelGGL(train_reduce_update_quant_batched_kernel<M>, gg, bb, 0, st, imgs, pg_start, k_images, c.a[0],
+                           c.a[1], c.a[2], step);
+        hipLaunchKernelGGL(train_quant_finish_batched_kernel<M>, gi, dim3(256), 0, st, imgs, pg_start, (int)bb.x / 64,
+                           c.a[1], c.aq[0], c.aq[1], c.aq[2], step);
+    }
+    int close() const {
+        if (!losses) {
+            batch_pass_end(batch, b, k_images, tile_blocks, st);
+            return check_launch("train steps (batched)");
+        }
+        for (int k = 0; k < k_images; ++k) {
+            const int rc = loss_copy_v(states[k], losses[k], plans[k].lw, kStepsBatched, st);
+            if (rc != GI2D_OK) return rc;
+        }
+        return check_launch("train steps (loss, batched)");
+    }
+};
+
+// gi2d_train_steps, and with `loss_route` gi2d_train_steps_loss: the sequence on one image.
+static int steps_one_image(const gi2d_train_state *s, const gi2d_train_loss *loss, bool loss_route, const double *lr,
+                           double beta1, double beta2, float eps, int first_step, int count, gi2d_stream_t st_) {
     const bool idle = count <= 0 || (s && s->num_points == 0);  // nothing to launch: only the state itself is looked at
     int rc = train_check(s, idle ? kStateOnly : kSteps);
     if (rc != GI2D_OK || idle) return rc;
     if (!lr || first_step < 1) return train_refuse(kSteps, GI2D_ERR_INVALID_ARGUMENT, "bad lr/step");
-    LossTerms terms;
-    LossWs lw = {};
-    if (loss_route) {
-        rc = loss_check(s, loss, kSteps, terms, lw);
-        if (rc != GI2D_OK) return rc;
-    }
     ImagePlan p;
-    rc = image_plan(s, p);
+    rc = image_plan(s, loss, loss_route, kSteps, p);
     if (rc != GI2D_OK) return rc;
     hipStream_t st = (hipStream_t)st_;
-    const bool quantised = s->quant != nullptr;
-    // a large image's tile passes run as two launches while the previous call on this workspace saw at most one row in
-    // sixteen above the small form's capacity (gi2d_fast.hip: pass_form_begin)
-    const long long tiles = (long long)p.tx * p.ty;
-    const int form = loss_route ? 0 : single_pass_begin(s->workspace, tiles, st);
-    // The inboxes: one image of at most GI2D_INBOX_MAX_TILES tiles, i.e. a tile pass of the general form throughout,
-    // whose caller brought the inboxes' buffer (gi2d_train_state::inbox), in a plain fit.
-    float4 *const inbox = quantised || loss_route ? nullptr : p.u.next.inbox;
-    const dim3 gg(p.blocks + (quantised ? 0 : 1)), bb(p.bs);  // + 1: the workgroup that orders the tiles (plain fits)
-    if (!quantised)
-        train_launch_project_fill(s->kind, p, st);
-    else if (s->kind != 2)
-        train_launch_quant_range(p, st);
-    for (int it = 0; it < count; ++it) {
-        const int step = first_step + it;
-        // Outputs the caller reads behind the call are stored by the call's LAST render only: out_img by the last tile
-        // pass, xys / num_tiles_hit by the last projection -- the last binning update kernel (iteration count - 2; the
-        // opening projection kernel when count == 1), in a quantised fit the last iteration's own projection kernel.
-        // The per-tile squared errors likewise, unless the update kernel reads them (a tracked best model).
-        const bool last = it + 1 == count;
-        if (quantised) train_launch_project_fill_quant(s->kind, p, st, last);
-        const unsigned w = (unsigned)s->img_width, h = (unsigned)s->img_height;
-        if (!loss_route) {
-            rc = fast_forward_backward_form(s->num_points, p.tx, p.ty, w, h, nullptr, nullptr, s->gt, p.grad_scale,
-                                            s->tile_sse, s->workspace, s->workspace_bytes, s->status, s->out_img, st_, form,
-                                            it > 0 ? inbox : nullptr, !last, !last && p.u.best.sse == nullptr);
-        } else {
-            rc = gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, w, h, nullptr, s->workspace, s->workspace_bytes,
-                                             s->status, nullptr, nullptr, s->out_img, st_);
-            if (rc == GI2D_OK)
-                rc = loss_launch(s->out_img, s->gt, s->img_height, s->img_width, terms, lw, lw.v, s->tile_sse,
-                                 loss->loss_value, st);
-            if (rc == GI2D_OK)
-                rc = gi2d_fast_rasterize_backward_tiles(s->num_points, p.tx, p.ty, w, h, nullptr, lw.v, 0, s->workspace,
-                                                        s->workspace_bytes, st_);
-        }
-        if (rc != GI2D_OK) return rc;
-        const IterSteps t = iter_steps(s, lr, beta1, beta2, eps, first_step, it);
-        const AdamStep *a = t.a, *aq = t.aq;
-        if (quantised) {
-#define GI2D_LAUNCH_QUANT(M)                                                                                          \
-    hipLaunchKernelGGL(train_reduce_update_quant_kernel<M>, gg, bb, 0, st, p.u, p.q, a[0], a[1], a[2], step);         \
-    hipLaunchKernelGGL(train_quant_finish_kernel<M>, dim3(1), dim3(256), 0, st, p.blocks * (p.bs / 64), p.u, p.q, a[1], \
-                       aq[0], aq[1], aq[2], step)
-            GI2D_DISPATCH_QUANT(s->kind);
-#undef GI2D_LAUNCH_QUANT
-            continue;
-        }
-        const bool more = it + 1 < count;
-        const bool deliver = more && inbox != nullptr;
-        const int store_proj = it + 2 == count ? 1 : 0;
-#define GI2D_LAUNCH_RU(K, F, A)                                                                                       \
-    do {                                                                                                              \
-        if (F && deliver)                                                                                             \
-            hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A, F>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step,  \
-                               store_proj);                                                                           \
-        else                                                                                                          \
-            hipLaunchKernelGGL((train_reduce_update_kernel<K, F, A>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step,     \
-                               store_proj);                                                                           \
-    } while (0)
-        GI2D_DISPATCH_RU(s->kind, more, s->optimizer == 1);
-#undef GI2D_LAUNCH_RU
-    }
-    if (!loss_route) {
-        single_pass_end(s->workspace, p.w, tiles, st);
-        return check_launch("train steps");
-    }
-    rc = loss_copy_v(s, loss, lw, kSteps, st);
-    if (rc != GI2D_OK) return rc;
-    return check_launch("train steps (loss)");
+    const int form = loss_route ? 0 : single_pass_begin(s->workspace, (long long)p.tx * p.ty, st);
+    float4 *const inbox = s->quant || loss_route ? nullptr : p.u.next.inbox;
+    const OneImage t = {s, p, loss_route ? loss : nullptr, st, form, inbox};
+    return fit_sequence(t, s, lr, beta1, beta2, eps, first_step, count);
 }
 
-extern "C" {
-
-// Forward only (render): activations + projection + fill + rasterize into state->out_img.
-int gi2d_train_render(const gi2d_train_state *s, gi2d_stream_t st_) {
-    int rc = train_check(s, kStateOnly);
-    if (rc != GI2D_OK || s->num_points == 0) return rc;
-    ImagePlan p;
-    rc = image_plan(s, p);
-    if (rc != GI2D_OK) return rc;
-    hipStream_t st = (hipStream_t)st_;
-    if (s->quant) {  // forward_quantize (models/gaussianimage_covariance.py:384-410, models/gaussianimage_rs.py:443-471)
-        if (s->kind != 2) train_launch_quant_range(p, st);  // (the RS model's ranges are learned values)
-        train_launch_project_fill_quant(s->kind, p, st, true);
-    } else {
-        train_launch_project_fill(s->kind, p, st);
-    }
-    return gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, (unsigned)s->img_width, (unsigned)s->img_height,
-                                       nullptr, s->workspace, s->workspace_bytes, s->status, nullptr, nullptr, s->out_img,
-                                       st_);
-}
-
-int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps,
-                     int first_step, int count, gi2d_stream_t st) {
-    return single_steps(s, nullptr, false, lr, beta1, beta2, eps, first_step, count, st);
-}
-
-int gi2d_train_step(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps, int step,
-                    gi2d_stream_t st) {
-    return gi2d_train_steps(s, lr, beta1, beta2, eps, step, 1, st);
-}
-
-// The same iterations under any of the reference's loss types (include/gi2d.h), the loss on launches of its own between
-// the two halves of the tile pass.
-int gi2d_train_steps_loss(const gi2d_train_state *s, const gi2d_train_loss *loss, const double *lr, double beta1,
-                          double beta2, float eps, int first_step, int count, gi2d_stream_t st) {
-    return single_steps(s, loss, true, lr, beta1, beta2, eps, first_step, count, st);
-}
-
-// ---------------------------------------------------------------------------------------------- several images per launch
-size_t gi2d_batch_bytes(int num_images) { return carve_batch(nullptr, num_images).bytes; }
-size_t gi2d_train_inbox_bytes(int tiles_x, int tiles_y) { return inbox_bytes((long long)tiles_x * tiles_y); }
-
-}  // extern "C"
-
-// gi2d_train_steps_batched, and with `loss_route` gi2d_train_steps_loss_batched: single_steps' sequence for K images, every
-// kernel launched once.  The loss route's tile pass is the batched forward tile kernel, the batched loss launches and
-// the batched backward tile kernel (gi2d_fast.hip, gi2d_loss.hip) in place of the fused one -- as on the single loss
-// route without the tile-pass-form bracket; everything in front of and behind the tile pass is the same launch either way.
-static int batched_steps(int num_images, const gi2d_train_state *const *states, const gi2d_train_loss *const *losses,
+// gi2d_train_steps_batched, and with `loss_route` gi2d_train_steps_loss_batched: the sequence on K images, every kernel
+// launched once.
+static int steps_batched(int num_images, const gi2d_train_state *const *states, const gi2d_train_loss *const *losses,
                          bool loss_route, void *batch, size_t batch_bytes, void *loss_batch_ws,
                          size_t loss_batch_ws_bytes, const double *lr, double beta1, double beta2, float eps,
                          int first_step, int count, gi2d_stream_t st_) {
@@ -1796,14 +1857,11 @@ static int batched_steps(int num_images, const gi2d_train_state *const *states, 
     std::memset(&head, 0, sizeof(head));
     // the table: tile-pass and per-gaussian workgroup ranges, one argument block per image
     std::vector<BatchImage> host_imgs((size_t)num_images);
-    // the loss route's: one type and one lambda for the batch, every image's own workspace, the SSIM pairs
-    LossTerms terms = {};
-    std::vector<LossWs> lws(loss_route ? (size_t)num_images : 0);
+    std::vector<ImagePlan> plans((size_t)num_images);
+    // the loss route's SSIM pairs (one type and one lambda for the batch, every image's own workspace)
     std::vector<gi2d_ssim_pair> pairs(loss_route ? (size_t)num_images : 0);
-    int heights[GI2D_BATCH_MAX], widths[GI2D_BATCH_MAX];
+    BatchLayout tiles;
     long long total_n = 0;
-    bool uniform = true;
-    int tile_blocks = 0, tiles0 = 0;
     for (int k = 0; k < num_images; ++k) {
         const gi2d_train_state *s = states[k];
         int rc = train_check(s, kStepsBatched);
@@ -1823,34 +1881,25 @@ static int batched_steps(int num_images, const gi2d_train_state *const *states, 
                 return train_refuse(kStepsBatched, GI2D_ERR_UNSUPPORTED,
                                     "the quantisers of a batch share bit depths, learning rates, eps, betas and step count");
         }
-        ImagePlan p;
-        rc = image_plan(s, p);
+        const gi2d_train_loss *loss = loss_route ? losses[k] : nullptr;
+        ImagePlan &p = plans[k];
+        rc = image_plan(s, loss, loss_route, kStepsBatched, p);
         if (rc != GI2D_OK) return rc;
+        if (loss_route && (loss->type != losses[0]->type || loss->lambda != losses[0]->lambda))
+            return train_refuse(kStepsBatched, GI2D_ERR_UNSUPPORTED, "the images of a batch share loss type and lambda");
         host_imgs[k].t = tile_pass_args(p.w, s->num_points, p.tx, p.ty, s->img_width, s->img_height, s->status,
                                         s->out_img, s->gt, p.grad_scale, s->tile_sse);
         host_imgs[k].u = p.u;
         host_imgs[k].q = p.q;
         std::memset(&host_imgs[k].l, 0, sizeof(LossImage));
         if (loss_route) {
-            const gi2d_train_loss *loss = losses[k];
-            LossTerms mine;
-            rc = loss_check(s, loss, kStepsBatched, mine, lws[k]);
-            if (rc != GI2D_OK) return rc;
-            if (loss->type != losses[0]->type || loss->lambda != losses[0]->lambda)
-                return train_refuse(kStepsBatched, GI2D_ERR_UNSUPPORTED, "the images of a batch share loss type and lambda");
-            terms = mine;
-            loss_batch_image(lws[k], lws[k].v, loss->loss_value, s->gt, s->img_height, s->img_width, terms,
-                             host_imgs[k].l, pairs[k]);
+            loss_batch_image(p.lw, p.lw.v, loss->loss_value, s->gt, s->img_height, s->img_width, p.terms, host_imgs[k].l,
+                             pairs[k]);
             host_imgs[k].l.packed = p.w.packed;
-            heights[k] = s->img_height, widths[k] = s->img_width;
         }
-        head.tile_start[k] = tile_blocks;
-        tile_blocks += p.tx * p.ty;
-        if (k == 0) tiles0 = p.tx * p.ty;
-        uniform = uniform && p.tx * p.ty == tiles0;
+        tiles.add(head, p.tx * p.ty, s->img_height, s->img_width);
         total_n += s->num_points;
     }
-    head.tile_start[num_images] = tile_blocks;
     const int bs = per_gaussian_block((int)(total_n > 0x7fffffff ? 0x7fffffff : total_n));
     int pg_blocks = 0;
     for (int k = 0; k < num_images; ++k) {
@@ -1861,7 +1910,7 @@ static int batched_steps(int num_images, const gi2d_train_state *const *states, 
     head.pg_start[num_images] = pg_blocks;
     LossBatchWs bw = {};
     if (loss_route) {
-        bw = carve_loss_batch(loss_batch_ws, num_images, heights, widths, terms);
+        bw = carve_loss_batch(loss_batch_ws, num_images, tiles.heights, tiles.widths, plans[0].terms);
         if (bw.bytes == 0) return GI2D_ERR_INVALID_ARGUMENT;  // (the message is set)
         if (loss_batch_ws_bytes < bw.bytes)
             return train_refuse(kStepsBatched, GI2D_ERR_WORKSPACE_TOO_SMALL,
@@ -1869,82 +1918,57 @@ static int batched_steps(int num_images, const gi2d_train_state *const *states, 
     }
     const BatchTable b = carve_batch(batch, num_images);
     write_batch_table(b, host_imgs.data(), num_images, head, st);
-    // the same sequence as single_steps; the kernels find their image's argument blocks in the table
-    const int form = loss_route ? 0 : batch_pass_begin(batch, tile_blocks, st);
-    const bool quantised = s0->quant != nullptr;
-    const BatchImage *imgs = b.img;
-    const int *pg_start = b.head->pg_start;
-    const dim3 gg((unsigned)pg_blocks), bb(bs), gi((unsigned)num_images), b256(256);  // gi: closing steps, one workgroup per image
-    const int wpb = bs / 64;
-    if (!quantised) {
-        if (s0->kind == 2)
-            hipLaunchKernelGGL(train_project_fill_batched_kernel<kScaleRot>, gg, bb, 0, st, imgs, pg_start, num_images);
-        else if (s0->kind == 0)
-            hipLaunchKernelGGL(train_project_fill_batched_kernel<kCholesky>, gg, bb, 0, st, imgs, pg_start, num_images);
-        else
-            hipLaunchKernelGGL(train_project_fill_batched_kernel<kCovariance>, gg, bb, 0, st, imgs, pg_start, num_images);
-    } else if (s0->kind != 2) {
-        const AdamStep z = idle_adam_step();
-        hipLaunchKernelGGL(train_quant_range_batched_kernel, gg, bb, 0, st, imgs, pg_start, num_images);
-        hipLaunchKernelGGL(train_quant_finish_batched_kernel<0>, gi, b256, 0, st, imgs, pg_start, wpb, z, z, z, z, 0);
-    }
-    for (int it = 0; it < count; ++it) {
-        const int step = first_step + it;
-        const bool last = it + 1 == count;  // (what the call's last render alone stores: see single_steps)
-        if (quantised) {
-#define GI2D_LAUNCH_QUANT(M)                                                                                   \
-    hipLaunchKernelGGL(train_project_fill_quant_batched_kernel<M>, gg, bb, 0, st, imgs, pg_start, num_images, \
-                       last ? 1 : 0)
-            GI2D_DISPATCH_QUANT(s0->kind);
-#undef GI2D_LAUNCH_QUANT
-        }
-        const int uniform_tiles = uniform ? tiles0 : 0;
-        int rc;
-        if (!loss_route) {
-            rc = launch_tile_pass_batched(1, b, num_images, tile_blocks, uniform_tiles, form, st, !last);
-        } else {
-            rc = launch_fwd_tiles_batched(b, num_images, tile_blocks, uniform_tiles, st);
-            if (rc == GI2D_OK) rc = loss_launch_batched(b, num_images, tile_blocks, terms, pairs.data(), bw, st);
-            if (rc == GI2D_OK) rc = launch_bwd_tiles_batched(b, num_images, tile_blocks, uniform_tiles, st);
-        }
-        if (rc != GI2D_OK) return rc;
-        const IterSteps t = iter_steps(s0, lr, beta1, beta2, eps, first_step, it);
-        const AdamStep *a = t.a, *aq = t.aq;
-        if (quantised) {
-#define GI2D_LAUNCH_QUANT(M)                                                                                           \
-    hipLaunchKernelGGL(train_reduce_update_quant_batched_kernel<M>, gg, bb, 0, st, imgs, pg_start, num_images, a[0],   \
-                       a[1], a[2], step);                                                                              \
-    hipLaunchKernelGGL(train_quant_finish_batched_kernel<M>, gi, b256, 0, st, imgs, pg_start, wpb, a[1], aq[0], aq[1], \
-                       aq[2], step)
-            GI2D_DISPATCH_QUANT(s0->kind);
-#undef GI2D_LAUNCH_QUANT
-            continue;
-        }
-        const bool more = it + 1 < count;
-        const int store_proj = it + 2 == count ? 1 : 0;
-#define GI2D_LAUNCH_RU(K, F, A)                                                                                       \
-    hipLaunchKernelGGL((train_reduce_update_batched_kernel<K, F, A>), gg, bb, 0, st, imgs, pg_start, num_images, a[0], \
-                       a[1], a[2], step, store_proj)
-        GI2D_DISPATCH_RU(s0->kind, more, s0->optimizer == 1);
-#undef GI2D_LAUNCH_RU
-    }
-    if (!loss_route) {
-        batch_pass_end(batch, b, num_images, tile_blocks, st);
-        return check_launch("train steps (batched)");
-    }
-    for (int k = 0; k < num_images; ++k) {
-        const int rc = loss_copy_v(states[k], losses[k], lws[k], kStepsBatched, st);
-        if (rc != GI2D_OK) return rc;
-    }
-    return check_launch("train steps (loss, batched)");
+    const int form = loss_route ? 0 : batch_pass_begin(batch, tiles.total, st);
+    const ImageBatch t = {states, loss_route ? losses : nullptr, plans.data(), batch, b, b.img, b.head->pg_start,
+                          num_images, tiles.total, tiles.uniform_tiles(), dim3((unsigned)pg_blocks), dim3(bs),
+                          dim3((unsigned)num_images), form, pairs.data(), bw, st};
+    return fit_sequence(t, s0, lr, beta1, beta2, eps, first_step, count);
 }
 
 extern "C" {
 
+// Forward only (render): activations + projection + fill + rasterize into state->out_img.
+int gi2d_train_render(const gi2d_train_state *s, gi2d_stream_t st_) {
+    int rc = train_check(s, kStateOnly);
+    if (rc != GI2D_OK || s->num_points == 0) return rc;
+    ImagePlan p;
+    rc = image_plan(s, nullptr, false, kStateOnly, p);
+    if (rc != GI2D_OK) return rc;
+    // a fit's opening launches; a quantised state renders behind its quantisers: forward_quantize
+    // (models/gaussianimage_covariance.py:384-410, models/gaussianimage_rs.py:443-471)
+    const OneImage t = {s, p, nullptr, (hipStream_t)st_, 0, nullptr};
+    t.open();
+    if (s->quant) t.project_fill_quant(true);
+    return gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, (unsigned)s->img_width, (unsigned)s->img_height,
+                                       nullptr, s->workspace, s->workspace_bytes, s->status, nullptr, nullptr, s->out_img,
+                                       st_);
+}
+
+int gi2d_train_steps(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps,
+                     int first_step, int count, gi2d_stream_t st) {
+    return steps_one_image(s, nullptr, false, lr, beta1, beta2, eps, first_step, count, st);
+}
+
+int gi2d_train_step(const gi2d_train_state *s, const double *lr, double beta1, double beta2, float eps, int step,
+                    gi2d_stream_t st) {
+    return gi2d_train_steps(s, lr, beta1, beta2, eps, step, 1, st);
+}
+
+// The same iterations under any of the reference's loss types (include/gi2d.h), the loss on launches of its own between
+// the two halves of the tile pass.
+int gi2d_train_steps_loss(const gi2d_train_state *s, const gi2d_train_loss *loss, const double *lr, double beta1,
+                          double beta2, float eps, int first_step, int count, gi2d_stream_t st) {
+    return steps_one_image(s, loss, true, lr, beta1, beta2, eps, first_step, count, st);
+}
+
+// ---------------------------------------------------------------------------------------------- several images per launch
+size_t gi2d_batch_bytes(int num_images) { return carve_batch(nullptr, num_images).bytes; }
+size_t gi2d_train_inbox_bytes(int tiles_x, int tiles_y) { return inbox_bytes((long long)tiles_x * tiles_y); }
+
 int gi2d_train_steps_batched(int num_images, const gi2d_train_state *const *states, void *batch, size_t batch_bytes,
                              const double *lr, double beta1, double beta2, float eps, int first_step, int count,
                              gi2d_stream_t st) {
-    return batched_steps(num_images, states, nullptr, false, batch, batch_bytes, nullptr, 0, lr, beta1, beta2, eps,
+    return steps_batched(num_images, states, nullptr, false, batch, batch_bytes, nullptr, 0, lr, beta1, beta2, eps,
                          first_step, count, st);
 }
 
@@ -1953,7 +1977,7 @@ int gi2d_train_steps_loss_batched(int num_images, const gi2d_train_state *const 
                                   const gi2d_train_loss *const *losses, void *batch, size_t batch_bytes,
                                   void *loss_batch_ws, size_t loss_batch_ws_bytes, const double *lr, double beta1,
                                   double beta2, float eps, int first_step, int count, gi2d_stream_t st) {
-    return batched_steps(num_images, states, losses, true, batch, batch_bytes, loss_batch_ws, loss_batch_ws_bytes, lr,
+    return steps_batched(num_images, states, losses, true, batch, batch_bytes, loss_batch_ws, loss_batch_ws_bytes, lr,
                          beta1, beta2, eps, first_step, count, st);
 }
 

@@ -1,5 +1,5 @@
 """What a fitting call leaves for its caller: out_img, xys and num_tiles_hit are stored by the call's LAST render only
-(csrc/gi2d_train.hip: single_steps behind gi2d_train_steps / _loss, gi2d_train_steps_batched; include/gi2d.h).  A
+(csrc/gi2d_train.hip: fit_sequence behind gi2d_train_steps / _loss and their _batched forms; include/gi2d.h).  A
 call of one iteration stores everything, so a fitter stepped by `count` calls of one iteration is the yardstick: a twin
 stepped by ONE call of `count` iterations must end with the same bits in every output and in the whole optimizer
 state.  Every comparison here is torch.equal."""
