@@ -75,6 +75,7 @@ struct TilePassArgs {
     int leave_image;    // single-image launches: bit 0 this pass does not store out_img, bit 1 nor sum and store tile_sse
                         // (fused_tile: leave_image / leave_sse; a batched launch says the former in a kernel argument:
                         // its table is written once per call)
+    unsigned rank_off;  // compact gradient rows (gi2d_raster_core.h::FitRows): their rank array, in bytes from partial_g
 };
 
 // One image's arguments of the per-gaussian fitting kernels (project+fill, reduce+update).
@@ -105,6 +106,7 @@ static inline TilePassArgs tile_pass_args(const FastWs &w, int n, int tiles_x, i
     a.inbox = w.inbox_recs;
     a.write_through = 0;
     a.leave_image = 0;
+    a.rank_off = 0u;
     a.tile_bins = (int2 *)w.tile_bins;
     a.partial_g = w.partial_g;
     a.partial_big = w.partial_big;
@@ -236,10 +238,12 @@ void single_pass_end(const void *ws, const FastWs &w, long long tiles, hipStream
 // leave_image: out_img is not written (neither by the tiles nor as the background image): the caller's last pass stores it
 // leave_sse (with `target`): tile_sse is neither summed nor stored -- a pass that is not the caller's last, of a fit that
 // tracks no best model (nothing on the device reads the sums then: gi2d_train.hip::best_decision is their only reader)
+// fit_rows: the pass leaves its gradient rows in the format of a fitting call on one image (gi2d_raster_core.h::
+// FitCallRows) -- every pass of a call whose update kernels read that format; the caller has looked at wt_fits<FitCallRows>
 int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned img_w, unsigned img_h, const float *background,
                                const float *v_output, const float *target, float grad_scale, float *tile_sse, void *ws,
                                size_t ws_bytes, int32_t *status, float *out_img, gi2d_stream_t st, int form,
-                               float4 *inbox, bool leave_image, bool leave_sse);
+                               float4 *inbox, bool leave_image, bool leave_sse, bool fit_rows = false);
 int batch_pass_begin(const void *batch, int total_blocks, hipStream_t st);
 // gi2d_fast.hip: the two halves of the loss route's tile pass over the batch -- fast_fwd_kernel's / fast_bwd_kernel's code
 // on image k's tile `local` (workgroups dealt to images as in launch_tile_pass_batched).  The forward stores every

@@ -260,10 +260,12 @@ __global__ __launch_bounds__(256) void fast_ws_init_kernel(int num_tiles, int n,
 // images: their stores overlap other tiles' work and compete for the memory system's slots: +28 % at K = 24), 1 always
 // (the INBOX instantiation: one image of at most one residency round), 2 when `wt` says so (the general-form kernel of a
 // single image: the launch code knows the tile count).
-template <int MODE, int PHASE, bool INBOX = false, int WTMODE = 0>
+// Fmt: the format of the gradient rows (gi2d_raster_core.h); compact rows are always written through.
+template <int MODE, int PHASE, bool INBOX = false, int WTMODE = 0, class Fmt = WideRows>
 __device__ __forceinline__ void tile_pass_workgroup(const TilePassArgs &a, int slot, bool first, bool leave_image,
                                                     bool mark_big = false, bool wt = false, bool leave_sse = false) {
     constexpr int CAP = PHASE == 1 ? GI2D_SMALL_CAP : GI2D_TILE_LIST_CAP;
+    static_assert(!Fmt::COMPACT || WTMODE == 1, "compact rows leave as write-through stores");
     __shared__ FusedLdsT<CAP> sm;
     int tile;
     HeadRow hr;
@@ -285,10 +287,10 @@ __device__ __forceinline__ void tile_pass_workgroup(const TilePassArgs &a, int s
     }
     // (phase 2 loops over tiles: its loop keeps the lane's invariants alive, so the forward's trips are not unrolled there)
     if (WTMODE == 1 || (WTMODE == 2 && wt))  // workgroup-uniform (launch-uniform)
-        fused_tile<MODE, CAP, PHASE == 2 ? 1 : GI2D_FWD_UNROLL, INBOX, WTMODE != 0>(
+        fused_tile<MODE, CAP, PHASE == 2 ? 1 : GI2D_FWD_UNROLL, INBOX, WTMODE != 0, Fmt>(
             sm, tile, a.tiles_x, a.tiles_y, a.img_w, a.img_h, recs, a.lists, a.tile_bins, a.partial_g, a.partial_big, a.status,
-            a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib, leave_image, leave_sse);
-    else
+            a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib, leave_image, leave_sse, a.rank_off);
+    else if constexpr (!Fmt::COMPACT)
         fused_tile<MODE, CAP, PHASE == 2 ? 1 : GI2D_FWD_UNROLL, INBOX, false>(
             sm, tile, a.tiles_x, a.tiles_y, a.img_w, a.img_h, recs, a.lists, a.tile_bins, a.partial_g, a.partial_big, a.status,
             a.out_img, a.vsrc, a.grad_scale, a.tile_sse, hr, ib, leave_image, leave_sse);
@@ -323,9 +325,12 @@ __device__ __forceinline__ int phase2_strip(int slots) { return (slots + (int)gr
 
 // INBOX: the launch right behind an update kernel that delivers through the inboxes (gi2d_train_steps, iterations 2 ...
 // of a call on one image of at most GI2D_INBOX_MAX_TILES tiles); every other launch runs the kernel built without.
-template <int MODE, int PHASE, bool INBOX = false>
+// Fmt: the format of the gradient rows (gi2d_raster_core.h) -- FitRows in every pass of a fitting call on one image whose
+// update kernels read that format (its first pass, behind the projection kernel, is the instantiation without INBOX).
+template <int MODE, int PHASE, bool INBOX = false, class Fmt = WideRows>
 __global__ __launch_bounds__(256, GI2D_PHASE_OCC(PHASE)) void fast_fwdbwd_kernel(TilePassArgs a) {
     static_assert(PHASE == 0 || !INBOX, "the small form has no room for the entrants' bookkeeping");
+    static_assert(PHASE == 0 || !Fmt::COMPACT, "compact rows: launches of one residency round, the general form");
     if (PHASE == 2) {
         // which slots of the strip were passed over: lane i looks at slot i (ONE round of two dependent loads for the
         // whole strip -- slot by slot it was sixteen), a ballot makes the answer scalar
@@ -347,7 +352,7 @@ __global__ __launch_bounds__(256, GI2D_PHASE_OCC(PHASE)) void fast_fwdbwd_kernel
         const int tiles = a.tiles_x * a.tiles_y;
         // (the small form of a single LARGE image -- phase 1 of two launches at 2040x1356 -- measured with write-through
         // rows, image and both: 54.97 -> 55.6-55.7 us; seven residency rounds overlap their stores already)
-        tile_pass_workgroup<MODE, PHASE, INBOX, INBOX ? 1 : (PHASE == 0 ? 2 : 0)>(
+        tile_pass_workgroup<MODE, PHASE, INBOX, INBOX || Fmt::COMPACT ? 1 : (PHASE == 0 ? 2 : 0), Fmt>(
             a, (int)blockIdx.x, blockIdx.x == 0, (a.leave_image & 1) != 0, tiles > GI2D_TWO_PHASE_TILES, a.write_through != 0,
             (a.leave_image & 2) != 0);
     }
@@ -1003,7 +1008,7 @@ namespace gi2d {
 int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned w_, unsigned h, const float *background,
                                const float *v_output, const float *target, float grad_scale, float *tile_sse, void *ws,
                                size_t ws_bytes, int32_t *status, float *out_img, gi2d_stream_t st, int form,
-                               float4 *inbox, bool leave_image, bool leave_sse) {
+                               float4 *inbox, bool leave_image, bool leave_sse, bool fit_rows) {
     int rc = check_ws("fast rasterize forward+backward: workspace too small", ws, ws_bytes, n, tiles_x, tiles_y);
     if (rc != GI2D_OK) return rc;
     const long long t = (long long)tiles_x * tiles_y;
@@ -1018,13 +1023,16 @@ int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned w_, uns
     }
     FastWs w = carve_fast(ws, n, (int)t);
     // (the inbox instantiation always stores write-through: it is only picked where that is possible)
-    const bool wt = t <= GI2D_TWO_PHASE_TILES && wt_fits(w, (int)t, (size_t)w_ * h * 12);
+    // (fit_rows: the caller picked the format where its extents can be written through; the wide extents may be larger)
+    fit_rows = fit_rows && target && t <= GI2D_INBOX_MAX_TILES && wt_fits<FitCallRows>(w, (int)t, (size_t)w_ * h * 12);
+    const bool wt = fit_rows || (t <= GI2D_TWO_PHASE_TILES && wt_fits(w, (int)t, (size_t)w_ * h * 12));
     w.inbox_recs = wt ? inbox : nullptr;
     inbox = w.inbox_recs;
     TilePassArgs a = tile_pass_args(w, n, tiles_x, tiles_y, (int)w_, (int)h, status, out_img,
                                     v_output ? v_output : target, v_output ? 0.f : grad_scale,
                                     v_output ? nullptr : tile_sse);
     a.write_through = wt ? 1 : 0;
+    if (fit_rows) a.rank_off = rank_offset_of<FitCallRows>(n);
     a.leave_image = (leave_image ? 1 : 0) | (leave_sse && target ? 2 : 0);
     if (form < 0) form = pass_form_override() >= 0 ? pass_form_override() : 1;
     const bool two = two_phase_tile_pass(t) && form >= 1;
@@ -1032,6 +1040,10 @@ int fast_forward_backward_form(int n, int tiles_x, int tiles_y, unsigned w_, uns
     if (v_output)
         launch_pass_forms(two, fast_fwdbwd_kernel<0, 0>, fast_fwdbwd_kernel<0, 1>, fast_fwdbwd_kernel<0, 2>, grid, grid2,
                           (hipStream_t)st, a);
+    else if (fit_rows)  // (one residency round: never two launches)
+        launch_pass_forms(false, inbox != nullptr ? fast_fwdbwd_kernel<1, 0, true, FitCallRows>
+                                                  : fast_fwdbwd_kernel<1, 0, false, FitCallRows>,
+                          fast_fwdbwd_kernel<1, 1>, fast_fwdbwd_kernel<1, 2>, grid, grid2, (hipStream_t)st, a);
     else  // (the one-launch form alone takes entrants out of the inboxes)
         launch_pass_forms(two, inbox != nullptr && t <= GI2D_INBOX_MAX_TILES ? fast_fwdbwd_kernel<1, 0, true>
                                                                               : fast_fwdbwd_kernel<1, 0>,

@@ -46,10 +46,13 @@ namespace gi2d {
 #define GI2D_REDUCE_BATCH 8                          /* partial rows a lane loads before it starts adding */
 #endif
 #define GI2D_BIG_TILES_F 32
-#ifndef GI2D_UPDATE_ROWS_AHEAD
-#define GI2D_UPDATE_ROWS_AHEAD 2                     /* gradient rows the update kernel requests before it knows the box (reduce_one) */
-#endif
-#define GI2D_FAST_ROW 4 /* float4 per partial row: 48 bytes of data padded to one 64-byte line */
+/* (gradient rows the single-image update kernel requests before it knows the box: Fmt::AHEAD, gi2d_raster_core.h) */
+#define GI2D_FAST_ROW 4 /* float4 per partial row as the workspace is carved: 48 bytes of data padded to one 64-byte line */
+static_assert(WideRows::STRIDE == GI2D_FAST_ROW, "the wide rows fill the carve");
+// (FitRows: 32 x 32 bytes of rows and 32 x 2 bytes of ranks per gaussian in the 32 x 64 bytes carved for it; the pool's
+// rows in the front half of the pool)
+static_assert(FitRows::STRIDE * sizeof(float4) + sizeof(unsigned short) <= GI2D_FAST_ROW * sizeof(float4),
+              "compact rows and their ranks live in the bytes carved for the wide rows");
 
 // What the binning step remembers per gaussian: (x, y) the packed tile box it is binned with (pack_box; 0/0 = none),
 // z = first row of its run in the row pool (-1: none), w = rows of that run.  Only a gaussian on more than GI2D_FAST_S
@@ -145,6 +148,37 @@ struct InboxSrc {
         return v;
     }
 };
+// The same for compact rows (FitRows): the ranks are not in the rows the lane has summed -- `at`: the gaussian's entries
+// of the rank array.  Every lane requests its first eight (ONE 16-byte load: whoever uses them looks at boxes of at most
+// eight tiles) when the kernel's first round of loads is back, and only the few lanes whose box changed ever look at the
+// answer, a thousand instructions later.  Measured (profiles/fit_rows_ab_measurements.txt): left to those lanes as a
+// dependent load in the kernel's tail -- one wave in five holds such a lane, and a launch ends with its slowest wave --
+// the update kernel takes 9.22-9.24 us instead of 8.71; requested with the first round of loads 8.96.
+#ifndef GI2D_FIT_RANKS_EARLY
+#define GI2D_FIT_RANKS_EARLY 2 /* tuning build: 0 a dependent load of the lanes that look, 1 with the first round of loads */
+#endif
+struct InboxSrcAt {
+    const unsigned short *at;
+    uint4 first8;  // (unless GI2D_FIT_RANKS_EARLY == 0)
+    bool on;
+    __device__ __forceinline__ void load_first8() { first8 = *reinterpret_cast<const uint4 *>(at); }
+    __device__ __forceinline__ unsigned get(int k) const {
+#if GI2D_FIT_RANKS_EARLY
+        unsigned a0 = first8.x, a1 = first8.y, a2 = first8.z, a3 = first8.w;
+        asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));  // (values, not loads: see InboxSrc::get)
+        const int w = k >> 1;
+        unsigned v = a0;
+        v = w == 1 ? a1 : v;
+        v = w == 2 ? a2 : v;
+        v = w == 3 ? a3 : v;
+        return (v >> (16 * (k & 1))) & 0xffffu;
+#else
+        return at[k];
+#endif
+    }
+};
+template <class Fmt>
+using InboxSrcOf = std::conditional_t<Fmt::COMPACT, InboxSrcAt, InboxSrc>;
 // Workgroup size of the one-lane-per-gaussian kernels (project+fill, reduce+project backward, optimizer update):
 // single waves spread a small population over many CUs and shorten the dependent load chains
 // (N=2500: project+fill 10.9 -> 5.5 us, reduce 7.4 -> 4.7 us; neutral to slightly worse beyond ~30k gaussians).
@@ -212,11 +246,22 @@ static FastWs carve_fast(void *base, int n, int num_tiles) {
 // May a launch on this workspace store write-through (gi2d_raster_core.h::store16)?  Its buffer stores address the
 // gradient rows -- gaussian-major rows and the row pool behind them -- by a 32-bit offset from `partial_g`, the image and
 // the packed records from their own bases: every one of those spans must stay below 4 GB (2 million gaussians' rows).
+// Fmt: the rows' format (gi2d_raster_core.h) -- the extent of the pool's rows is the format's.
+template <class Fmt = WideRows>
 static inline bool wt_fits(const FastWs &w, int num_tiles, size_t image_bytes) {
     const size_t rows_span = (size_t)((const char *)w.partial_big - (const char *)w.partial_g) +
-                             (size_t)(num_tiles > 0 ? num_tiles : 1) * GI2D_TILE_LIST_CAP * GI2D_FAST_ROW * sizeof(float4);
+                             (size_t)(num_tiles > 0 ? num_tiles : 1) * GI2D_TILE_LIST_CAP * Fmt::STRIDE * sizeof(float4);
     const size_t packed_span = (size_t)(num_tiles > 0 ? num_tiles : 1) * GI2D_TILE_LIST_CAP * sizeof(GaussRec);
     return rows_span < 0xffff0000ull && packed_span < 0xffff0000ull && image_bytes < 0xffff0000ull;
+}
+// Where the ranks of a workspace's compact rows live, in bytes from `partial_g`: behind the gaussian-major rows of the
+// `n` gaussians the workspace is carved for (carve_fast), in the half of that region the 32-byte rows leave free.
+template <class Fmt>
+__host__ __device__ __forceinline__ unsigned rank_offset_of(int n) {
+    if constexpr (Fmt::COMPACT)
+        return (unsigned)Fmt::rank_offset((size_t)(n > 0 ? n : 1) * GI2D_FAST_S);
+    else
+        return 0u;  // (in the rows)
 }
 // What every C entry on a fast-path workspace checks first (`what`: its message for a workspace that is too small).
 static inline int check_ws(const char *what, void *ws, size_t ws_bytes, int n, int tiles_x, int tiles_y) {
@@ -272,14 +317,17 @@ struct FillPending {
     do {                      \
     } while (0)
 #endif
-struct InboxFill {
+template <class Src>
+struct InboxFillT {
     Inbox ib;
-    InboxSrc src;
+    Src src;
     float4 q[4];
 };
+typedef InboxFillT<InboxSrc> InboxFill;
 // Tile (ti, tj) has been entered by a gaussian whose old box is f.o*: through the inbox if the nearest tile of the old
 // box is a neighbour that handed a rank on (true), through the row's header otherwise.
-__device__ __forceinline__ bool inbox_enter(const FillPending &f, const InboxFill &in, int ti, int tj, int tiles_x,
+template <class In>
+__device__ __forceinline__ bool inbox_enter(const FillPending &f, const In &in, int ti, int tj, int tiles_x,
                                             int32_t *__restrict__ lists) {
     const int sj = min(max(tj, f.omnx), f.omxx - 1), si = min(max(ti, f.omny), f.omxy - 1);
     const int ddx = sj - tj, ddy = si - ti;  // not both zero: the tile is outside the old box
@@ -302,9 +350,9 @@ __device__ __forceinline__ bool inbox_enter(const FillPending &f, const InboxFil
     atomicOr(reinterpret_cast<unsigned *>(inbox_bits_of(lists, tile)) + (slot >> 5), 1u << (slot & 31));  // no answer needed
     return true;
 }
-template <bool INBOX>
+template <bool INBOX, class In = InboxFill>
 __device__ __forceinline__ void fill_trip_issue(FillPending &f, int base, int tiles_x, int32_t *__restrict__ lists,
-                                                const InboxFill *in = nullptr) {
+                                                const In *in = nullptr) {
     // the entered tiles that take the gaussian through their inbox (a ROLLED loop over the trip's tiles: one copy of the
     // record's stores, no indexing of register arrays; a lane has one or two entered tiles, rarely more)
     unsigned handled = 0u;
@@ -371,10 +419,10 @@ __device__ __forceinline__ void fill_trip_store(const FillPending &f, int g, int
     for (int q = 0; q < GI2D_FILL_BATCH; ++q)
         if (f.p[q] < GI2D_FAST_C) lists[f.c[q] + GI2D_FAST_HDR + f.p[q]] = g;  // a fuller row is flagged by the tile pass
 }
-template <bool INBOX = false>
+template <bool INBOX = false, class In = InboxFill>
 __device__ __forceinline__ FillPending fill_diff_begin(int g, bool member, int mnx, int mny, int mxx, int mxy,
                                                        int tiles_x, PrevBox old, PrevBox *__restrict__ prev_box,
-                                                       int32_t *__restrict__ lists, InboxFill *in = nullptr) {
+                                                       int32_t *__restrict__ lists, In *in = nullptr) {
     FillPending f;
     f.nt = 0;
     f.pool = old.z;
@@ -405,9 +453,9 @@ __device__ __forceinline__ FillPending fill_diff_begin(int g, bool member, int m
     fill_trip_issue<INBOX>(f, 0, tiles_x, lists, in);
     return f;
 }
-template <bool INBOX = false>
+template <bool INBOX = false, class In = InboxFill>
 __device__ __forceinline__ void fill_diff_end(int g, FillPending &f, int tiles_x, int32_t *__restrict__ lists,
-                                              const InboxFill *in = nullptr) {
+                                              const In *in = nullptr) {
     if (f.nt == 0) return;
     fill_trip_store(f, g, lists);
     for (int base = GI2D_FILL_BATCH; base < f.nt; base += GI2D_FILL_BATCH) {
@@ -586,12 +634,12 @@ __device__ __forceinline__ void unpack_box(int2 box, int &mnx, int &mny, int &mx
 // (fill_diff_begin / _end above).
 // INBOX (the update kernel of a fit): `in` = the inboxes and what the gaussian knows of its old tiles (InboxFill; its
 // record words are filled in here).
-template <bool INBOX = false, class Between>
+template <bool INBOX = false, class Between, class In = InboxFill>
 __device__ __forceinline__ void bin_one(int g, float2 xy, int radius, bool has_tiles, float ka, float kb, float kc,
                                         float opac, float cr, float cg, float cb, int tiles_x, int tiles_y,
                                         float radius_clip, PrevBox old_box, PrevBox *__restrict__ prev_box,
                                         int32_t *__restrict__ lists, const BinRecs &br, Between between,
-                                        InboxFill *in = nullptr) {
+                                        In *in = nullptr) {
     int mnx, mny, mxx, mxy;
     const bool member = bin_box(xy, radius, radius_clip, tiles_x, tiles_y, mnx, mny, mxx, mxy) && has_tiles;
     {  // one store per wave that holds a member (by its first such lane)
@@ -622,11 +670,11 @@ __device__ __forceinline__ void bin_one(int g, float2 xy, int radius, bool has_t
     bin_one(g, xy, radius, has_tiles, ka, kb, kc, opac, cr, cg, cb, tiles_x, tiles_y, radius_clip, old_box, prev_box, lists,
             recs, [] {});
 }
-template <bool INBOX = false, class Between>
+template <bool INBOX = false, class Between, class In = InboxFill>
 __device__ __forceinline__ void bin_projected(int g, const ProjOut &o, float opac, float cr, float cg, float cb,
                                               int tiles_x, int tiles_y, float radius_clip, PrevBox old_box,
                                               PrevBox *__restrict__ prev_box, int32_t *__restrict__ lists,
-                                              const BinRecs &recs, Between between, InboxFill *in = nullptr) {
+                                              const BinRecs &recs, Between between, In *in = nullptr) {
     bin_one<INBOX>(g, o.xy, o.radius, o.tiles_hit > 0, o.k0, o.k1, o.k2, opac, cr, cg, cb, tiles_x, tiles_y, radius_clip,
                    old_box, prev_box, lists, recs, between, in);
 }
@@ -647,16 +695,18 @@ __device__ __forceinline__ int partial_slot(int g, int2 box, int tx, int ty, int
     return -(pool + at) - 1;
 }
 // Where the partial row with that code lives; nullptr (and the overflow status raised) for a pool row past the pool's end.
+// Fmt: the rows' format (gi2d_raster_core.h) -- row k of either buffer starts Fmt::STRIDE * k float4 behind its base.
+template <class Fmt = WideRows>
 __device__ __forceinline__ float4 *partial_row(int slot, float4 *__restrict__ partial_g, float4 *__restrict__ partial_big,
                                                int pool_rows, int32_t *__restrict__ status) {
-    if (slot >= 0) return partial_g + GI2D_FAST_ROW * (size_t)slot;
+    if (slot >= 0) return partial_g + Fmt::STRIDE * (size_t)slot;
     const int row = -slot - 1;
     if (row < 0 || row >= pool_rows) {  // the pool ran out (PrevBox): the caller falls back as for a tile row that
         atomicOr(&status[1], GI2D_STATUS_POOL);  // overflowed, but is told which of the two it was
         atomicOr(&status[2], GI2D_STATUS_POOL);
         return nullptr;
     }
-    return partial_big + GI2D_FAST_ROW * (size_t)row;
+    return partial_big + Fmt::STRIDE * (size_t)row;
 }
 
 #ifndef GI2D_HEAD_TRACE /* gi2d_fused_core.h defines it for its phase trace (development aid) */
@@ -1115,29 +1165,29 @@ static_assert(GI2D_REDUCE_BATCH >= 8 && GI2D_TILE_LIST_CAP == 256, "reduce_one r
 // first round of loads -- their addresses depend on g alone, so they need not wait for the box that says how many of
 // them count (the bench scene's gaussians lie on 1, 2 or 4 tiles: the box -> rows round trip disappears for every wave
 // without a larger one).  What is added, and in which order, is the same with or without.
-template <int AHEAD>
+template <int AHEAD, class Fmt = WideRows>
 struct RowsAhead {
-    float4 r[AHEAD > 0 ? AHEAD : 1][3];
+    float4 r[AHEAD > 0 ? AHEAD : 1][Fmt::PIECES];
 };
-template <int AHEAD>
-__device__ __forceinline__ RowsAhead<AHEAD> rows_ahead(const float4 *__restrict__ partial_g, int g_in_rows) {
+// (FitRows with AHEAD = 4: eight 16-byte loads of ONE 128-byte line per lane)
+template <int AHEAD, class Fmt = WideRows>
+__device__ __forceinline__ RowsAhead<AHEAD, Fmt> rows_ahead(const float4 *__restrict__ partial_g, int g_in_rows) {
     static_assert(AHEAD <= GI2D_REDUCE_BATCH && AHEAD <= GI2D_FAST_S, "rows of the first trip only");
-    RowsAhead<AHEAD> a;
-    const float4 *rows = partial_g + GI2D_FAST_ROW * ((size_t)g_in_rows * GI2D_FAST_S);
+    RowsAhead<AHEAD, Fmt> a;
 #pragma unroll
-    for (int q = 0; q < AHEAD; ++q) {
-        a.r[q][0] = rows[GI2D_FAST_ROW * q];
-        a.r[q][1] = rows[GI2D_FAST_ROW * q + 1];
-        a.r[q][2] = rows[GI2D_FAST_ROW * q + 2];
-    }
+    for (int q = 0; q < AHEAD; ++q)
+        load_partial_row<Fmt::STRIDE, Fmt::PIECES>(a.r[q], partial_g, (size_t)g_in_rows * GI2D_FAST_S + q);
     return a;
 }
-template <int AHEAD = 0>
+// Fmt: the rows' format (gi2d_raster_core.h).  Compact rows hold the eight words a fit reads -- acc[8..10] stay zero -- and
+// no ranks: `src` is not looked at (the caller points its InboxSrcAt at the rank array itself).
+template <int AHEAD = 0, class Fmt = WideRows>
 __device__ __forceinline__ void reduce_one(int g, int2 box, int pool, int pool_rows, const float4 *__restrict__ partial_g,
                                            const float4 *__restrict__ partial_big, float (&acc)[11],
-                                           InboxSrc *src = nullptr, const RowsAhead<AHEAD> *ahead = nullptr) {
+                                           InboxSrcOf<Fmt> *src = nullptr, const RowsAhead<AHEAD, Fmt> *ahead = nullptr) {
     const int lane = threadIdx.x & 63;
-    if (src) src->clear();
+    if constexpr (!Fmt::COMPACT)
+        if (src) src->clear();
 #pragma unroll
     for (int q = 0; q < 11; ++q) acc[q] = 0.f;
     int mnx, mny, mxx, mxy;
@@ -1147,28 +1197,29 @@ __device__ __forceinline__ void reduce_one(int g, int2 box, int pool, int pool_r
     if (mapped && ntiles <= GI2D_FAST_S) {
         // GI2D_REDUCE_BATCH rows per trip: their loads are in flight together, the additions stay in ascending
         // tile order
-        const float4 *rows = partial_g + GI2D_FAST_ROW * ((size_t)g * GI2D_FAST_S);
+        const size_t row0 = (size_t)g * GI2D_FAST_S;
         // (the first trip is written out: rows [0, AHEAD) are in registers already)
         const auto trip = [&](int k0, auto have) {
             constexpr int HAVE = decltype(have)::value;
-            float4 r[GI2D_REDUCE_BATCH][3];
+            float4 r[GI2D_REDUCE_BATCH][Fmt::PIECES];
 #pragma unroll
             for (int q = 0; q < GI2D_REDUCE_BATCH; ++q) {
                 if (q < HAVE) {
-                    r[q][0] = ahead->r[q][0], r[q][1] = ahead->r[q][1], r[q][2] = ahead->r[q][2];
+#pragma unroll
+                    for (int c = 0; c < Fmt::PIECES; ++c) r[q][c] = ahead->r[q][c];
                 } else if (k0 + q < ntiles) {
-                    r[q][0] = rows[GI2D_FAST_ROW * (k0 + q)];
-                    r[q][1] = rows[GI2D_FAST_ROW * (k0 + q) + 1];
-                    r[q][2] = rows[GI2D_FAST_ROW * (k0 + q) + 2];
+                    load_partial_row<Fmt::STRIDE, Fmt::PIECES>(r[q], partial_g, row0 + k0 + q);
                 }
             }
 #pragma unroll
             for (int q = 0; q < GI2D_REDUCE_BATCH; ++q)
-                if (k0 + q < ntiles) add_partial_row(acc, r[q][0], r[q][1], r[q][2]);
-            if (src && k0 == 0) {  // (the first eight tiles' tags; whoever uses them looks at boxes of <= 8 tiles only)
+                if (k0 + q < ntiles) add_partial_row<Fmt::PIECES>(acc, r[q]);
+            if constexpr (!Fmt::COMPACT) {
+                if (src && k0 == 0) {  // (the first eight tiles' tags; whoever uses them looks at boxes of <= 8 tiles only)
 #pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    if (q < ntiles) src->set(q, (unsigned)__float_as_int(r[q][2].w));
+                    for (int q = 0; q < 8; ++q)
+                        if (q < ntiles) src->set(q, (unsigned)__float_as_int(r[q][2].w));
+                }
             }
         };
         trip(0, std::integral_constant<int, AHEAD>());
@@ -1183,9 +1234,9 @@ __device__ __forceinline__ void reduce_one(int g, int2 box, int pool, int pool_r
         float part[11];
 #pragma unroll
         for (int q = 0; q < 11; ++q) part[q] = 0.f;
-        for (int t = lane; t < bn; t += 64) add_partial<GI2D_FAST_ROW>(part, partial_big, (size_t)bpool + t);
+        for (int t = lane; t < bn; t += 64) add_partial<Fmt::STRIDE, Fmt::PIECES>(part, partial_big, (size_t)bpool + t);
 #pragma unroll
-        for (int q = 0; q < 11; ++q) {
+        for (int q = 0; q < (Fmt::COMPACT ? 8 : 11); ++q) {
             float v = part[q];
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);

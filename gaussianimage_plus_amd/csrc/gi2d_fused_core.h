@@ -134,13 +134,16 @@ static_assert(offsetof(FusedLdsSmall, slot) >= offsetof(FusedLdsSmall, part) &&
 // leave_sse (MODE 1; workgroup-uniform like leave_image): tile_sse[tile] is neither summed nor stored -- a lane exchange,
 // a wave sum, an LDS round and a store per tile that only the best-model decision of the update kernel reads on the
 // device.  A fit that tracks no best model asks for the sums in its call's last pass only, which is what its caller sees.
-template <int MODE, int CAP = GI2D_TILE_LIST_CAP, int FWD_UNROLL = GI2D_FWD_UNROLL, bool INBOX = false, bool WT = false>
+// Fmt: the format of the gradient rows this pass leaves (gi2d_raster_core.h; FitRows: every pass of a fitting call on one
+// image whose caller brought the inboxes), rank_off: where that format keeps the ranks (rank_offset_of).
+template <int MODE, int CAP = GI2D_TILE_LIST_CAP, int FWD_UNROLL = GI2D_FWD_UNROLL, bool INBOX = false, bool WT = false,
+          class Fmt = WideRows>
 __device__ __forceinline__ void fused_tile(
     FusedLdsT<CAP> &sm, int tile, int tiles_x, int tiles_y, int img_w, int img_h, const float4 *__restrict__ recs,
     int32_t *__restrict__ lists, int2 *__restrict__ tile_bins,
     float4 *__restrict__ partial_g, float4 *__restrict__ partial_big, int32_t *__restrict__ status,
     float *__restrict__ out_img, const float *__restrict__ vsrc, float grad_scale, float *__restrict__ tile_sse,
-    const HeadRow head_row, const Inbox &ib, bool leave_image = false, bool leave_sse = false) {
+    const HeadRow head_row, const Inbox &ib, bool leave_image = false, bool leave_sse = false, unsigned rank_off = 0u) {
 #ifdef GI2D_KNOCK_CALL_STORES /* development aid: what the stores a fitting call can leave out cost at most (no image at all) */
     leave_image = true;
 #endif
@@ -202,12 +205,11 @@ __device__ __forceinline__ void fused_tile(
                 sm.gC[rank] = s.C;
                 sm.cullw[rank] = s.cull;
                 sm.slot[rank] = s.slot;
-            } else if (float4 *row = partial_row(s.slot, partial_g, partial_big, pool_rows, status)) {
-                // beyond the 256-entry cap: never rasterized, its gradient row must read as zero
-                const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-                store16<WT>(row, z, partial_g);  // (the row pool lies behind the gaussian-major rows: carve_fast)
-                store16<WT>(row + 1, z, partial_g);
-                store16<WT>(row + 2, z, partial_g);
+            } else if (float4 *row = partial_row<Fmt>(s.slot, partial_g, partial_big, pool_rows, status)) {
+                // beyond the 256-entry cap: never rasterized, its gradient row must read as zero -- rank 0 = none
+                // (the row pool lies behind the gaussian-major rows: carve_fast)
+                const float z[Fmt::PSTR] = {};
+                store_partial_row<Fmt, Fmt::PSTR, WT>(row, z, 0, partial_g, rank_off);
             }
         }, ib, head_row);
     GI2D_TRACE(2);
@@ -290,15 +292,17 @@ __device__ __forceinline__ void fused_tile(
     // ---- backward on the same staged records
     bwd_publish_pixel(sm, lx, ly, v0, v1, v2, 0.f);
     float4 *dst = nullptr;
-    if (tid < len) dst = partial_row(sm.slot[tid], partial_g, partial_big, pool_rows, status);
+    if (tid < len) dst = partial_row<Fmt>(sm.slot[tid], partial_g, partial_big, pool_rows, status);
     // (INBOX: the pass that only gi2d_train_steps issues, between two update kernels of a fit -- its rows' v_opacity word
-    // has no reader, so the hand-off's division is left out; every other instantiation serves the reduce calls as well)
+    // has no reader, so the hand-off's division is left out; every other instantiation serves the reduce calls as well.
+    // Compact rows have no such word.)
 #ifdef GI2D_KEEP_VOPAC /* development aid: the division in every instantiation */
     constexpr bool NO_VOPAC = false;
 #else
     constexpr bool NO_VOPAC = INBOX;
 #endif
-    bwd_run_tile<false, false, true, WT, NO_VOPAC>(sm, len, cull, 0, tx0, ty0, dst, scan_incl, sm.scan_w, partial_g);
+    bwd_run_tile<false, false, true, WT, NO_VOPAC, FusedLdsT<CAP>, Fmt>(sm, len, cull, 0, tx0, ty0, dst, scan_incl, sm.scan_w,
+                                                                        partial_g, rank_off);
     GI2D_TRACE(10);
     GI2D_TRACE_VALUE(14, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4));   // HW_REG_HW_ID
     GI2D_TRACE_VALUE(15, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20));  // HW_REG_XCC_ID

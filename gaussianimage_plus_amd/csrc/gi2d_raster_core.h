@@ -435,9 +435,48 @@ static_assert(GI2D_BWD_ITEMS == 256, "an item's row in the hand-off buffer is it
 #define GI2D_BWD_OCC 5 /* waves per SIMD the register allocator must leave room for; measured: 5 (96 VGPRs) beats 6 (80) */
 #endif
 
-template <int PSTR, bool WT = false>
+// THE TWO FORMATS OF A GRADIENT ROW (the partial a tile pass leaves per (gaussian, tile) for the per-gaussian sum).
+// WideRows: (v_x, v_y, v_conic[3], v_rgb[3]) (v_opacity, sum|v_x|, sum|v_y|, rank) -- three 16-byte pieces in a 64-byte
+//   slot; what the reduce calls behind the autograd wrappers, the batched, quantised and loss-route kernels read.
+// FitRows: the first two pieces alone, 32 bytes, rows back to back -- a gaussian's rows 0..3 are ONE naturally aligned
+//   128-byte line, which the update kernel of a single-image fit requests whole before it knows the gaussian's box
+//   (AHEAD; gi2d_fast_internal.h::rows_ahead).  No fit reads v_opacity (the opacity is not a fitted parameter), and the
+//   rank is read by the few lanes whose box changed: it lives in a uint16 array of its own, one entry per
+//   gaussian-major row, behind those rows (`rank_offset`: bytes from the rows' base; `rows` = gaussian-major rows).
+//   Rows of the pool (boxes of more than 32 tiles) carry no rank: ranks are read for boxes of at most eight tiles.
+// PIECES: float4 stored / loaded per row; STRIDE: float4 from one row to the next; PSTR: moments an item hands over in
+// the tile pass (bwd_run_tile; + 2 with the |v_xy| sums); AHEAD: rows the single-image update kernel requests up front
+// (-DGI2D_UPDATE_ROWS_AHEAD=k: a tuning build, both formats).
+struct WideRows {
+    static constexpr bool COMPACT = false;
+    static constexpr int PIECES = 3, STRIDE = 4, PSTR = 9;
+#ifdef GI2D_UPDATE_ROWS_AHEAD
+    static constexpr int AHEAD = GI2D_UPDATE_ROWS_AHEAD;
+#else
+    static constexpr int AHEAD = 2;
+#endif
+};
+struct FitRows {
+    static constexpr bool COMPACT = true;
+    static constexpr int PIECES = 2, STRIDE = 2, PSTR = 8;
+#ifdef GI2D_UPDATE_ROWS_AHEAD
+    static constexpr int AHEAD = GI2D_UPDATE_ROWS_AHEAD;
+#else
+    static constexpr int AHEAD = 4;
+#endif
+    __host__ __device__ static constexpr size_t rank_offset(size_t rows) { return rows * STRIDE * sizeof(float4); }
+};
+// what a fitting call on one image uses where its tile pass can store write-through (gi2d_train.hip::OneImage);
+// -DGI2D_WIDE_FIT_ROWS: the wide rows there too (the A/B build)
+#ifdef GI2D_WIDE_FIT_ROWS
+typedef WideRows FitCallRows;
+#else
+typedef FitRows FitCallRows;
+#endif
+
+template <class Fmt, int PSTR, bool WT = false>
 __device__ __forceinline__ void store_partial_row(float4 *__restrict__ dst, const float (&acc)[PSTR], int tag,
-                                                  const void *wt_base = nullptr);
+                                                  const void *wt_base = nullptr, unsigned rank_off = 0u);
 
 // Pixel gradients in LDS: one 32-byte record per (row pair p, column c) at pix[2 * (16 p + c)]:
 //   (vox_A, vox_B, voy_A, voy_B) (voz_A, voz_B, fidx_A, fidx_B)        A = row 2p, B = row 2p + 1
@@ -638,12 +677,17 @@ __device__ __forceinline__ void bwd_item_columns(const BwdItemIn &in, BwdItemAcc
 
 // NO_VOPAC: the rows' v_opacity word is left as the moment T0 (no division by the opacity) -- for a caller whose rows
 // only ever reach a fitting update kernel, none of which reads that word (the opacity is not a fitted parameter).
+// Fmt: the rows' format (above); FitRows: eight moments per item (T0 is not handed over: S0 is still summed, U0 and V0
+// need it), two pieces per row, the rank to the array `rank_off` bytes behind `wt_base`.
 template <bool WITH_ABS, bool USE_FIDX = true, bool PRESCANNED = false, bool WT = false, bool NO_VOPAC = false,
-          class Lds = BwdLds<WITH_ABS, USE_FIDX>>
+          class Lds = BwdLds<WITH_ABS, USE_FIDX>, class Fmt = WideRows>
 __device__ __forceinline__ void bwd_run_tile(Lds &sm, int len, unsigned cull, int list_base, float tx0, float ty0,
                                              float4 *__restrict__ dst, unsigned long long prescan_incl = 0ull,
-                                             const int *prescan_wsum = nullptr, const void *wt_base = nullptr) {
-    constexpr int PSTR = Lds::PSTR;
+                                             const int *prescan_wsum = nullptr, const void *wt_base = nullptr,
+                                             unsigned rank_off = 0u) {
+    constexpr int PSTR = Fmt::COMPACT ? Fmt::PSTR : Lds::PSTR;
+    static_assert(PSTR <= Lds::PSTR && (!Fmt::COMPACT || (WT && !WITH_ABS)),
+                  "the hand-off buffer holds Lds::PSTR words per item; compact rows are written through and carry no |v_xy| sums");
     static_assert(!USE_FIDX || Lds::HAS_FIDX, "final_idx is not staged in this LDS layout");
     static_assert(!WITH_ABS || Lds::HAS_RAW, "the |v_xy| sums need the conic as given");
     const int tid = threadIdx.x, wv = tid >> 6;
@@ -761,7 +805,7 @@ __device__ __forceinline__ void bwd_run_tile(Lds &sm, int len, unsigned cull, in
             res[5] = gr.x + gr.y;
             res[6] = gg.x + gg.y;
             res[7] = gb.x + gb.y;
-            res[8] = S0.x + S0.y;                              // T0 = sum w = sum opac*vis*v_alpha
+            if constexpr (PSTR > 8) res[8] = S0.x + S0.y;      // T0 = sum w = sum opac*vis*v_alpha
             if (WITH_ABS) {
                 res[PSTR - 2] = ax.x + ax.y;
                 res[PSTR - 1] = ay.x + ay.y;
@@ -815,23 +859,27 @@ __device__ __forceinline__ void bwd_run_tile(Lds &sm, int len, unsigned cull, in
                 // The conic staged in LDS is the pre-scaled one (a log2e / 2, b log2e, c log2e / 2).
                 const float4 A = sm.gA[tid], B = sm.gB[tid];
                 const float ln2 = 0.6931471805599453f;
-                const float T1 = acc[0], U0 = acc[1], opac = B.y;
+                const float T1 = acc[0], U0 = acc[1];
                 acc[0] = -ln2 * __builtin_fmaf(2.f * A.z, T1, A.w * U0);  // -(a T1 + b U0) = sum v_sigma (a dx + b dy)
                 acc[1] = -ln2 * __builtin_fmaf(A.w, T1, 2.f * B.x * U0);  // -(b T1 + c U0) = sum v_sigma (b dx + c dy)
                 acc[2] *= -0.5f;                                          // sum 0.5 v_sigma dx dx
                 acc[3] *= -0.5f;                                          // sum 0.5 v_sigma dx dy
                 acc[4] *= -0.5f;                                          // sum 0.5 v_sigma dy dy
-                if (!NO_VOPAC) acc[8] = (acc[8] != 0.f) ? acc[8] / opac : 0.f;  // v_opacity = sum vis*v_alpha (backward.cu:961)
+                if constexpr (PSTR > 8 && !NO_VOPAC)  // v_opacity = sum vis*v_alpha (backward.cu:961); B.y: the opacity
+                    acc[8] = (acc[8] != 0.f) ? acc[8] / B.y : 0.f;
             }
             if (my_lo < round0) {  // an earlier round already stored part of this row
                 wt_drain<WT>();
-                const float4 d0 = dst[0], d1 = dst[1], d2 = dst[2];
+                const float4 d0 = dst[0], d1 = dst[1];
                 acc[0] += d0.x, acc[1] += d0.y, acc[2] += d0.z, acc[3] += d0.w;
                 acc[4] += d1.x, acc[5] += d1.y, acc[6] += d1.z, acc[7] += d1.w;
-                acc[8] += d2.x;
-                if (PSTR > 9) acc[PSTR - 2] += d2.y, acc[PSTR - 1] += d2.z;
+                if constexpr (PSTR > 8) {
+                    const float4 d2 = dst[2];
+                    acc[8] += d2.x;
+                    if constexpr (PSTR > 9) acc[PSTR - 2] += d2.y, acc[PSTR - 1] += d2.z;
+                }
             }
-            store_partial_row<PSTR, WT>(dst, acc, tid + 1, wt_base);
+            store_partial_row<Fmt, PSTR, WT>(dst, acc, tid + 1, wt_base, rank_off);
         }
         round0 += GI2D_BWD_ITEMS;
     } while (round0 < n_items);
@@ -839,34 +887,55 @@ __device__ __forceinline__ void bwd_run_tile(Lds &sm, int len, unsigned cull, in
 
 // `tag`: the entry's rank in its tile's staged list, plus one -- the spare word of the row hands it to the gaussian's
 // lane of the update kernel, which needs it to enter a neighbouring tile through that tile's inbox
-// (gi2d_fast_internal.h::Inbox); rows written as zeros elsewhere carry 0 = no rank.
-template <int PSTR, bool WT>
+// (gi2d_fast_internal.h::Inbox); rows written as zeros elsewhere carry 0 = no rank.  FitRows: the rank of a
+// gaussian-major row goes to the rank array (2 bytes at rank_off + 2 * row index: the row's own offset / 16), by the same
+// lane, written through like the row (the format is only picked where that is possible); a row of the pool has none.
+template <class Fmt, int PSTR, bool WT>
 __device__ __forceinline__ void store_partial_row(float4 *__restrict__ dst, const float (&acc)[PSTR], int tag,
-                                                  const void *wt_base) {
+                                                  const void *wt_base, unsigned rank_off) {
     store16<WT>(dst, make_float4(acc[0], acc[1], acc[2], acc[3]), wt_base);
     store16<WT>(dst + 1, make_float4(acc[4], acc[5], acc[6], acc[7]), wt_base);
-    store16<WT>(dst + 2, make_float4(acc[8], PSTR > 9 ? acc[PSTR - 2] : 0.f, PSTR > 9 ? acc[PSTR - 1] : 0.f, __int_as_float(tag)),
-                wt_base);
+    if constexpr (Fmt::COMPACT) {
+        static_assert(WT && PSTR == Fmt::PSTR, "compact rows leave as write-through stores");
+        const unsigned off = wt_offset(dst, wt_base);
+        if (off < rank_off)  // (the gaussian-major rows end where their ranks begin)
+            __builtin_amdgcn_raw_buffer_store_b16((unsigned short)tag, wt_resource(wt_base), (int)(rank_off + (off >> 4)), 0,
+                                                  GI2D_WT_AUX);
+    } else {
+        store16<WT>(dst + 2,
+                    make_float4(acc[8], PSTR > 9 ? acc[PSTR - 2] : 0.f, PSTR > 9 ? acc[PSTR - 1] : 0.f, __int_as_float(tag)),
+                    wt_base);
+    }
 }
 
-__device__ __forceinline__ void add_partial_row(float acc[11], const float4 &p0, const float4 &p1, const float4 &p2);
-// STRIDE = float4 per row: 3 (packed 48-byte rows) or 4 (rows padded to one 64-byte line each)
-template <int STRIDE = 3>
-__device__ __forceinline__ void add_partial(float acc[11], const float4 *__restrict__ partials, size_t row) {
-    add_partial_row(acc, partials[STRIDE * row], partials[STRIDE * row + 1], partials[STRIDE * row + 2]);
+// acc += one row, given as its PIECES float4 (3: the wide row's eleven words; 2: the eight words every row starts with)
+template <int PIECES = 3>
+__device__ __forceinline__ void add_partial_row(float acc[11], const float4 (&p)[PIECES]) {
+    acc[0] += p[0].x;
+    acc[1] += p[0].y;
+    acc[2] += p[0].z;
+    acc[3] += p[0].w;
+    acc[4] += p[1].x;
+    acc[5] += p[1].y;
+    acc[6] += p[1].z;
+    acc[7] += p[1].w;
+    if constexpr (PIECES > 2) {
+        acc[8] += p[2].x;
+        acc[9] += p[2].y;
+        acc[10] += p[2].z;
+    }
 }
-__device__ __forceinline__ void add_partial_row(float acc[11], const float4 &p0, const float4 &p1, const float4 &p2) {
-    acc[0] += p0.x;
-    acc[1] += p0.y;
-    acc[2] += p0.z;
-    acc[3] += p0.w;
-    acc[4] += p1.x;
-    acc[5] += p1.y;
-    acc[6] += p1.z;
-    acc[7] += p1.w;
-    acc[8] += p2.x;
-    acc[9] += p2.y;
-    acc[10] += p2.z;
+// STRIDE = float4 per row: 3 (packed 48-byte rows), 4 (rows padded to one 64-byte line each) or 2 (FitRows)
+template <int STRIDE = 3, int PIECES = 3>
+__device__ __forceinline__ void load_partial_row(float4 (&p)[PIECES], const float4 *__restrict__ partials, size_t row) {
+#pragma unroll
+    for (int q = 0; q < PIECES; ++q) p[q] = partials[STRIDE * row + q];
+}
+template <int STRIDE = 3, int PIECES = 3>
+__device__ __forceinline__ void add_partial(float acc[11], const float4 *__restrict__ partials, size_t row) {
+    float4 p[PIECES];
+    load_partial_row<STRIDE, PIECES>(p, partials, row);
+    add_partial_row<PIECES>(acc, p);
 }
 __device__ __forceinline__ void store_grads(int g, const float acc[11], float2 *v_xy, float *v_conic,
                                             float *v_rgb, float *v_opacity, float4 *v_abs_xy) {

@@ -336,7 +336,9 @@ __device__ __forceinline__ bool best_decision(const BestSnap &best, const SseLoa
 // store_proj (FILL_NEXT; launch-uniform, a kernel argument): the projection's `xys` and `num_tiles_hit` are stored -- the
 // last binning update kernel of a call.  No kernel of a fit reads the two (the tile pass works from the records, the
 // next update kernel reads radii and conics): they are outputs for the caller, who looks once the call is complete.
-template <int KIND, bool FILL_NEXT, bool ADAN, bool INBOX = false, bool ALONE = INBOX>
+// Fmt: the format of the gradient rows the tile pass left (gi2d_raster_core.h): FitRows in every update kernel of a call on
+// one image whose tile passes write that format (OneImage), the call's last one (FILL_NEXT = false) included.
+template <int KIND, bool FILL_NEXT, bool ADAN, bool INBOX = false, bool ALONE = INBOX, class Fmt = WideRows>
 __device__ __forceinline__ void train_reduce_update_body(int block, bool order_block, const UpdateArgs &u,
                                                          const AdamStep &a_xyz, const AdamStep &a_chol,
                                                          const AdamStep &a_feat, int step, bool store_proj) {
@@ -381,8 +383,18 @@ __device__ __forceinline__ void train_reduce_update_body(int block, bool order_b
     // ... and the gaussian's first gradient rows, whose addresses need no box (reduce_one)
     // (a single image's kernels only: 9.05 -> 8.65 us at 768x512, 11.5 -> 11.05 at 2040x1356; a batch's launch is short
     // of memory slots, not of things to wait for -- 15.1 -> 15.9 us per image-iteration at K = 24 with four rows ahead)
-    constexpr int AHEAD = ALONE ? GI2D_UPDATE_ROWS_AHEAD : 0;
-    const RowsAhead<AHEAD> ahead = rows_ahead<AHEAD>(u.partial_g, in_rows ? g : 0);
+    // (two 64-byte rows, or the four 32-byte rows of a fitting call's format: one 128-byte line either way)
+    constexpr int AHEAD = ALONE ? Fmt::AHEAD : 0;
+    const RowsAhead<AHEAD, Fmt> ahead = rows_ahead<AHEAD, Fmt>(u.partial_g, in_rows ? g : 0);
+    // (compact rows: the ranks are an array of their own, requested below, once this round is back -- InboxSrcAt)
+    InboxFillT<InboxSrcOf<Fmt>> inbox;
+    if constexpr (Fmt::COMPACT && FILL_NEXT && INBOX) {
+        inbox.src.at = reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(u.partial_g) +
+                                                                rank_offset_of<Fmt>(u.n)) + (size_t)(in_rows ? g : 0) * GI2D_FAST_S;
+#if GI2D_FIT_RANKS_EARLY == 1
+        inbox.src.load_first8();
+#endif
+    }
     // the additive bound of this gaussian (one row for all when bound_stride == 0): used by both activations and the snapshot
     const Row3 bound_row = in_rows ? load_row3(P.bound, P.bound_stride ? g : 0) : Row3{0.f, 0.f, 0.f};
     const float bound3[3] = {bound_row.a, bound_row.b, bound_row.c};
@@ -394,9 +406,11 @@ __device__ __forceinline__ void train_reduce_update_body(int block, bool order_b
     float acc[11];
     // (FILL_NEXT: with the sums come the ranks the tile pass staged this gaussian at -- what it needs to enter a
     // neighbouring tile through that tile's inbox instead of waiting for an atomic's answer: gi2d_fast_internal.h::Inbox)
-    InboxFill inbox;
-    reduce_one<AHEAD>(g, box, pbox.z, tiles_x * u.tiles_y * GI2D_TILE_LIST_CAP, u.partial_g, u.partial_big,
-                                       acc, FILL_NEXT && INBOX ? &inbox.src : nullptr, &ahead);
+#if GI2D_FIT_RANKS_EARLY == 2
+    if constexpr (Fmt::COMPACT && FILL_NEXT && INBOX) inbox.src.load_first8();
+#endif
+    reduce_one<AHEAD, Fmt>(g, box, pbox.z, tiles_x * u.tiles_y * GI2D_TILE_LIST_CAP, u.partial_g, u.partial_big, acc,
+                           FILL_NEXT && INBOX ? &inbox.src : nullptr, &ahead);
     if (g >= n) return;
 #if defined(GI2D_UPDATE_STOP) && GI2D_UPDATE_STOP == 1 /* development aid: the kernel's time up to the end of its two load rounds */
     {
@@ -552,11 +566,11 @@ __device__ __forceinline__ void train_reduce_update_body(int block, bool order_b
 // INBOX: an image of at most GI2D_INBOX_MAX_TILES tiles with another iteration to follow (the launch code picks: a
 // kernel of its own, not a run-time switch -- with the switch the box-changing lanes of a large image walked their
 // tiles twice, +0.6 us at 2040x1356)
-template <int KIND, bool FILL_NEXT, bool ADAN, bool INBOX = false>
+template <int KIND, bool FILL_NEXT, bool ADAN, bool INBOX = false, class Fmt = WideRows>
 __global__ __launch_bounds__(256) void train_reduce_update_kernel(UpdateArgs u, AdamStep a_xyz, AdamStep a_chol,
                                                                   AdamStep a_feat, int step, int store_proj) {
     static_assert(FILL_NEXT || !INBOX, "only a binning update kernel has entrants to deliver");
-    train_reduce_update_body<KIND, FILL_NEXT, ADAN, INBOX, true>((int)blockIdx.x, blockIdx.x == gridDim.x - 1, u, a_xyz, a_chol,
+    train_reduce_update_body<KIND, FILL_NEXT, ADAN, INBOX, true, Fmt>((int)blockIdx.x, blockIdx.x == gridDim.x - 1, u, a_xyz, a_chol,
                                                            a_feat, step, store_proj != 0);
 }
 // K images in one launch (gi2d_batch.h): image k owns workgroups [pg_start[k], pg_start[k + 1]), the last of them its
@@ -888,7 +902,7 @@ __device__ __forceinline__ void reduce_update_quant_body(int block, const Update
     const int g = block * blockDim.x + threadIdx.x;
     int32_t *status = u.next.status;
     // (one image alone: its first gradient rows are asked for before the box says how many count -- reduce_one)
-    constexpr int AHEAD = ALONE ? GI2D_UPDATE_ROWS_AHEAD : 0;
+    constexpr int AHEAD = ALONE ? WideRows::AHEAD : 0;
     const RowsAhead<AHEAD> ahead = rows_ahead<AHEAD>(partial_g, g < u.n ? g : 0);
     const PrevBox box_ld = g < u.n ? prev_box[g] : no_box();
     const bool snapshot = best_decision(best, best_sse_loads(best), n, g);
@@ -1095,7 +1109,7 @@ __device__ __forceinline__ void reduce_update_quant_rs_body(int block, const Upd
     // alone also asks for its first gradient rows before the box says how many count (reduce_one)
     AdamRows rows;
     if (g < u.n) rows = adam_load_rows(P, g);
-    constexpr int AHEAD = ALONE ? GI2D_UPDATE_ROWS_AHEAD : 0;
+    constexpr int AHEAD = ALONE ? WideRows::AHEAD : 0;
     const RowsAhead<AHEAD> ahead = rows_ahead<AHEAD>(partial_g, g < u.n ? g : 0);
     const PrevBox box_ld = g < u.n ? prev_box[g] : no_box();
     const bool snapshot = best_decision(best, best_sse_loads(best), n, g);
@@ -1477,7 +1491,7 @@ static UpdateArgs update_args_of(const gi2d_train_state *s, const FastWs &w, int
     // the tiles' inboxes: the caller's own buffer, for an image small enough to use them (single-image calls only look)
     // (... and whose tile pass can store write-through, which the inbox instantiation always does: wt_fits)
     u.next.inbox = (s->inbox != nullptr && inbox_bytes((long long)tx * ty) > 0 && s->inbox_bytes >= inbox_bytes((long long)tx * ty) &&
-                    wt_fits(w, tx * ty, (size_t)s->img_width * s->img_height * 12))
+                    wt_fits<FitCallRows>(w, tx * ty, (size_t)s->img_width * s->img_height * 12))
                        ? (float4 *)s->inbox
                        : nullptr;
     u.next.prev_box = w.prev_box;
@@ -1670,6 +1684,8 @@ struct OneImage {
     int form;
     // The inboxes: one image of at most GI2D_INBOX_MAX_TILES tiles, i.e. a tile pass of the general form throughout,
     // whose caller brought the inboxes' buffer (gi2d_train_state::inbox), in a plain fit on the fused route; else null.
+    // Such a call also keeps its gradient rows in the fitting format (gi2d_raster_core.h::FitCallRows) in EVERY kernel it
+    // launches, from its first tile pass to its last update kernel: a call never mixes formats.
     float4 *inbox;
 
     // plain: activations + projection + fill, on the gaussians' workgroups alone (the tile-ordering one belongs to the
@@ -1704,7 +1720,8 @@ struct OneImage {
         if (!loss)
             return fast_forward_backward_form(s->num_points, p.tx, p.ty, w, h, nullptr, nullptr, s->gt, p.grad_scale,
                                               s->tile_sse, s->workspace, s->workspace_bytes, s->status, s->out_img, st, form,
-                                              it > 0 ? inbox : nullptr, !last, !last && p.u.best.sse == nullptr);
+                                              it > 0 ? inbox : nullptr, !last, !last && p.u.best.sse == nullptr,
+                                              inbox != nullptr);
         int rc = gi2d_fast_rasterize_forward(s->num_points, p.tx, p.ty, w, h, nullptr, s->workspace, s->workspace_bytes,
                                              s->status, nullptr, nullptr, s->out_img, st);
         if (rc == GI2D_OK)
@@ -1716,13 +1733,14 @@ struct OneImage {
         return rc;
     }
     // + 1: the workgroup that orders the tiles.  An update kernel that starts the next iteration delivers through the
-    // tiles' inboxes, if the call has them (the INBOX instantiation).
+    // tiles' inboxes, if the call has them (the INBOX instantiation).  Every update kernel of such a call, its last one
+    // included, reads the rows in the call's format (FitCallRows: what its tile passes wrote).
     template <int K, bool FILL_NEXT, bool ADAN>
     void update(const AdamStep *a, int step, bool store_proj) const {
         const dim3 gg(p.blocks + 1), bb(p.bs);
-        if (FILL_NEXT && inbox != nullptr)
-            hipLaunchKernelGGL((train_reduce_update_kernel<K, FILL_NEXT, ADAN, FILL_NEXT>), gg, bb, 0, st, p.u, a[0], a[1],
-                               a[2], step, store_proj ? 1 : 0);
+        if (inbox != nullptr)
+            hipLaunchKernelGGL((train_reduce_update_kernel<K, FILL_NEXT, ADAN, FILL_NEXT, FitCallRows>), gg, bb, 0, st, p.u,
+                               a[0], a[1], a[2], step, store_proj ? 1 : 0);
         else
             hipLaunchKernelGGL((train_reduce_update_kernel<K, FILL_NEXT, ADAN>), gg, bb, 0, st, p.u, a[0], a[1], a[2], step,
                                store_proj ? 1 : 0);
