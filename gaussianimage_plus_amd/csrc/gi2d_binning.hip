@@ -10,7 +10,7 @@
 //                   position) order -- an LDS rank sort for short lists, an LDS bitmap sweep for
 //                   long ones -- which is exactly what a stable sort of the whole key array gives.
 // All integer work; HBM traffic per pair: 8+4 B read three times, 8+4+4(+4) B written: ~60 B.
-#include "gi2d_common.h"
+#include "gi2d_tile_order.h"
 
 namespace gi2d {
 
@@ -27,25 +27,16 @@ __global__ __launch_bounds__(1024) void scan_kernel(int n, const int32_t *__rest
                                                     int32_t *__restrict__ total,
                                                     int32_t *__restrict__ bins,
                                                     int32_t *__restrict__ cursor) {
-    __shared__ int wave_sums[16];
-    __shared__ int carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
+    __shared__ int wsum[16];
+    const int tid = threadIdx.x;
+    int carry = 0;  // sum of the steps before this one, the same in every lane
     for (int base = 0; base < n; base += 4096) {
         const int i0 = base + tid * 4;
         int v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = (i0 + k < n) ? in[i0 + k] : 0;
-        const int local = v[0] + v[1] + v[2] + v[3];
-        const int incl = wave_inclusive_scan(local);
-        if (lane == 63) wave_sums[wv] = incl;
-        __syncthreads();
-        int wave_off = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) wave_off += (k < wv) ? wave_sums[k] : 0;
-        const int carry = carry_s;
-        int run = carry + wave_off + incl - local;  // exclusive prefix of this lane's 4 elements
+        int step_total;
+        int run = carry + block_exclusive_scan(v[0] + v[1] + v[2] + v[3], wsum, step_total);  // exclusive prefix of v[0]
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (i0 + k < n) {
@@ -62,15 +53,13 @@ __global__ __launch_bounds__(1024) void scan_kernel(int n, const int32_t *__rest
             }
             run += v[k];
         }
-        __syncthreads();
-        if (tid == 1023) carry_s = run;
-        __syncthreads();
+        carry += step_total;
     }
     if (tid == 0) {
         if (MODE == 0) {
-            if (total) *total = carry_s;
+            if (total) *total = carry;
         } else {
-            out[n] = carry_s;
+            out[n] = carry;
         }
     }
 }
@@ -147,10 +136,7 @@ __global__ __launch_bounds__(256) void tile_scatter_kernel(int m, int num_tiles,
     slots[p] = i;
 }
 
-#define GI2D_RANK_MAX 1024   /* longest tile list ordered by the LDS rank sort */
-#define GI2D_BITMAP_WORDS 8192 /* 32 KiB LDS bitmap = 262144 input positions per sweep */
-
-// One workgroup per tile: order the tile's segment of `slots` and emit the sorted arrays.
+// One workgroup per tile: order the tile's segment of `slots` and emit the sorted arrays (gi2d_tile_order.h).
 __global__ __launch_bounds__(256) void tile_order_kernel(
     int m, const int64_t *__restrict__ isect_ids, const int32_t *__restrict__ gaussian_ids,
     const int32_t *__restrict__ start, const int32_t *__restrict__ slots,
@@ -161,70 +147,32 @@ __global__ __launch_bounds__(256) void tile_order_kernel(
         uint32_t bits[GI2D_BITMAP_WORDS];
     } sm;
     __shared__ int wsum[4];
-    const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tile = blockIdx.x;
     const int s0 = start[tile], len = start[tile + 1] - s0;
     if (len <= 0) return;
-    if (len <= GI2D_RANK_MAX) {
-        for (int e = tid; e < len; e += 256) {
-            const int slot = slots[s0 + e];
-            const uint32_t lo = (uint32_t)isect_ids[slot];
-            sm.keys[e] = ((unsigned long long)lo << 32) | (uint32_t)slot;
-        }
-        __syncthreads();
-        for (int e = tid; e < len; e += 256) {
-            const unsigned long long mine = sm.keys[e];
-            int rank = 0;
-            for (int j = 0; j < len; ++j) rank += (sm.keys[j] < mine) ? 1 : 0;
-            const int slot = (int)(uint32_t)mine;
-            const int pos = s0 + rank;
-            gids_sorted[pos] = gaussian_ids[slot];
-            if (isect_sorted) isect_sorted[pos] = isect_ids[slot];
-            if (perm) perm[pos] = slot;
-            if (inv_perm) inv_perm[slot] = pos;
-        }
+    auto emit = [&](int k, int slot) {  // input position `slot` is the k-th entry of the tile
+        const int pos = s0 + k;
+        gids_sorted[pos] = gaussian_ids[slot];
+        if (isect_sorted) isect_sorted[pos] = isect_ids[slot];
+        if (perm) perm[pos] = slot;
+        if (inv_perm) inv_perm[slot] = pos;
+    };
+    if (len <= GI2D_RANK_MAX) {  // keys: (depth bits, input position)
+        tile_rank_sort(
+            sm.keys, len,
+            [&](int e) {
+                const int slot = slots[s0 + e];
+                return ((unsigned long long)(uint32_t)isect_ids[slot] << 32) | (uint32_t)slot;
+            },
+            [&](int rank, unsigned long long key) { emit(rank, (int)(uint32_t)key); });
         return;
     }
     if (flags[0] != 0) {  // long list with real depth keys: not supported on the 2D path
-        if (tid == 0) atomicOr(&flags[2], 1);
+        if (threadIdx.x == 0) atomicOr(&flags[2], 1);
         return;
     }
-    // Long list, all depth bits zero: order == ascending input position.  Sweep the position
-    // space [0, m) in windows of 32*GI2D_BITMAP_WORDS, mark the tile's positions in an LDS bitmap
-    // and enumerate the set bits in order.
-    int emitted = 0;
-    for (int win = 0; win < m; win += 32 * GI2D_BITMAP_WORDS) {
-        for (int w = tid; w < GI2D_BITMAP_WORDS; w += 256) sm.bits[w] = 0u;
-        __syncthreads();
-        for (int e = tid; e < len; e += 256) {
-            const int rel = slots[s0 + e] - win;
-            if (rel >= 0 && rel < 32 * GI2D_BITMAP_WORDS) atomicOr(&sm.bits[rel >> 5], 1u << (rel & 31));
-        }
-        __syncthreads();
-        const int w0 = tid * (GI2D_BITMAP_WORDS / 256);
-        int cnt = 0;
-        for (int w = 0; w < GI2D_BITMAP_WORDS / 256; ++w) cnt += __popc(sm.bits[w0 + w]);
-        const int incl = wave_inclusive_scan(cnt);
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        int off = emitted + incl - cnt;
-        for (int k = 0; k < wv; ++k) off += wsum[k];
-        const int win_total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        for (int w = 0; w < GI2D_BITMAP_WORDS / 256; ++w) {
-            uint32_t b = sm.bits[w0 + w];
-            while (b) {
-                const int bit = __ffs(b) - 1;
-                b &= b - 1;
-                const int slot = win + ((w0 + w) << 5) + bit;
-                const int pos = s0 + off++;
-                gids_sorted[pos] = gaussian_ids[slot];
-                if (isect_sorted) isect_sorted[pos] = isect_ids[slot];
-                if (perm) perm[pos] = slot;
-                if (inv_perm) inv_perm[slot] = pos;
-            }
-        }
-        emitted += win_total;
-        __syncthreads();
-    }
+    // Long list, all depth bits zero: order == ascending input position, a sweep over [0, m).
+    tile_bitmap_sweep(sm.bits, wsum, len, m, [&](int e) { return slots[s0 + e]; }, emit);
 }
 
 // forward.cu:211-233 get_tile_bin_edges; rows indexed by tile id, zero-filled first.
@@ -244,27 +192,20 @@ __global__ __launch_bounds__(256) void bin_edges_kernel(int m, const int64_t *__
     }
 }
 
-static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct SortWs {
     int32_t *counts, *start, *cursor, *slots, *flags;
     size_t bytes;
 };
 static SortWs carve_sort_ws(void *base, int m, int num_tiles) {
     SortWs w;
-    size_t off = 0;
-    char *b = (char *)base;
-    w.flags = (int32_t *)(b + off);
-    off += align_up(4 * sizeof(int32_t));
-    w.counts = (int32_t *)(b + off);
-    off += align_up(sizeof(int32_t) * (size_t)(num_tiles > 0 ? num_tiles : 1));
-    w.start = (int32_t *)(b + off);
-    off += align_up(sizeof(int32_t) * ((size_t)(num_tiles > 0 ? num_tiles : 1) + 1));
-    w.cursor = (int32_t *)(b + off);
-    off += align_up(sizeof(int32_t) * (size_t)(num_tiles > 0 ? num_tiles : 1));
-    w.slots = (int32_t *)(b + off);
-    off += align_up(sizeof(int32_t) * (size_t)(m > 0 ? m : 1));
-    w.bytes = off;
+    Carver c{base};
+    const size_t t = (size_t)(num_tiles > 0 ? num_tiles : 1);
+    w.flags = c.take<int32_t>(4);
+    w.counts = c.take<int32_t>(t);
+    w.start = c.take<int32_t>(t + 1);
+    w.cursor = c.take<int32_t>(t);
+    w.slots = c.take<int32_t>((size_t)(m > 0 ? m : 1));
+    w.bytes = c.off;
     return w;
 }
 
@@ -307,16 +248,11 @@ int gi2d_map_gaussian_to_intersects(int n, int m, const float *xys, const float 
         return GI2D_ERR_INVALID_ARGUMENT;
     }
     if (n == 0 || m == 0) {
-        if (m > 0) {
-            hipError_t e = hipMemsetAsync(isect_ids, 0, sizeof(int64_t) * (size_t)m, (hipStream_t)st);
-            if (e == hipSuccess)
-                e = hipMemsetAsync(gaussian_ids, 0, sizeof(int32_t) * (size_t)m, (hipStream_t)st);
-            if (e != hipSuccess) {
-                set_error(hipGetErrorString(e));
-                return (int)e;
-            }
-        }
-        return GI2D_OK;
+        if (m == 0) return GI2D_OK;
+        const int rc = zero_async(isect_ids, sizeof(int64_t) * (size_t)m, (hipStream_t)st, "map_gaussian_to_intersects");
+        return rc != GI2D_OK ? rc
+                             : zero_async(gaussian_ids, sizeof(int32_t) * (size_t)m, (hipStream_t)st,
+                                          "map_gaussian_to_intersects");
     }
     if (!xys || !depths || !radii || !cum || !isect_ids || !gaussian_ids) {
         set_error("map_gaussian_to_intersects: null pointer");
@@ -352,11 +288,8 @@ int gi2d_sort_intersects(int m, int num_tiles, const int64_t *isect_ids,
     }
     SortWs w = carve_sort_ws(workspace, m, num_tiles);
     // flags + counts are adjacent at the head of the workspace: one memset node
-    hipError_t e = hipMemsetAsync(w.flags, 0, (size_t)((char *)w.start - (char *)w.flags), st);
-    if (e != hipSuccess) {
-        set_error(hipGetErrorString(e));
-        return (int)e;
-    }
+    const int rc = zero_async(w.flags, (size_t)((char *)w.start - (char *)w.flags), st, "sort_intersects");
+    if (rc != GI2D_OK) return rc;
     if (m > 0)
         hipLaunchKernelGGL(tile_hist_kernel, dim3((m + 255) / 256), dim3(256), 0, st, m, num_tiles,
                            isect_ids, w.counts, w.flags);
@@ -383,11 +316,8 @@ int gi2d_get_tile_bin_edges(int m, const int64_t *sorted, int rows, int32_t *bin
         set_error("get_tile_bin_edges: null pointer");
         return GI2D_ERR_INVALID_ARGUMENT;
     }
-    hipError_t e = hipMemsetAsync(bins, 0, sizeof(int32_t) * 2 * (size_t)rows, (hipStream_t)st);
-    if (e != hipSuccess) {
-        set_error(hipGetErrorString(e));
-        return (int)e;
-    }
+    const int rc = zero_async(bins, sizeof(int32_t) * 2 * (size_t)rows, (hipStream_t)st, "get_tile_bin_edges");
+    if (rc != GI2D_OK) return rc;
     if (m > 0)
         hipLaunchKernelGGL(bin_edges_kernel, dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)st, m,
                            sorted, rows, bins);

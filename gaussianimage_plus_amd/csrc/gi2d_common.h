@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "gi2d.h"
 
@@ -12,6 +13,33 @@ namespace gi2d {
 
 void set_error(const char *msg);
 int check_launch(const char *what);
+
+// ---- host side: workspace carving and clearing ---------------------------------------------
+// Every region of a caller-provided workspace starts on a 256-byte boundary.
+static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Hands out consecutive regions of a workspace; `off` ends up as its size.  A size query carves from a null base
+// (the addresses are integer sums, never dereferenced).
+struct Carver {
+    void *base;
+    size_t off = 0;
+    template <class T>
+    T *take(size_t count) {
+        T *p = (T *)((uintptr_t)base + off);
+        off += align_up(count * sizeof(T));
+        return p;
+    }
+};
+
+// hipMemsetAsync(ptr, 0, bytes) with the entries' error convention: the message is recorded, the HIP code returned
+static inline int zero_async(void *ptr, size_t bytes, hipStream_t st, const char *what) {
+    const hipError_t e = hipMemsetAsync(ptr, 0, bytes, st);
+    if (e == hipSuccess) return GI2D_OK;
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
+    set_error(msg);
+    return (int)e;
+}
 
 // float -> int with the semantics of CUDA's cvt.rzi.s32.f32 (truncate, saturate, NaN -> 0),
 // which get_bbox (helpers.cuh:26-29) relies on for huge / non-finite centres.
@@ -71,6 +99,20 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {
     GI2D_DPP_ADD(0x143, 0xc);  // row_bcast:31 -> rows 2 and 3
 #undef GI2D_DPP_ADD
     return v;
+}
+// Exclusive scan of one int per lane across the workgroup (whole waves, at most 16 of them); `total`, the workgroup's
+// sum, comes back in every lane, so a caller that walks an array in steps keeps its running total in a register.
+__device__ __forceinline__ int block_exclusive_scan(int v, int *wsum /* LDS, one word per wave */, int &total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, waves = (int)blockDim.x >> 6;
+    const int incl = wave_inclusive_scan(v);
+    __syncthreads();  // wsum may still be read from the previous use
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    // every wave scans the wave sums itself, one per lane: one LDS read instead of one per wave
+    const int s = lane < waves ? wsum[lane] : 0;
+    const int s_incl = wave_inclusive_scan(s);
+    total = __builtin_amdgcn_readlane(s_incl, 63);
+    return __builtin_amdgcn_readlane(s_incl - s, __builtin_amdgcn_readfirstlane(wv)) + incl - v;
 }
 // Sum of one float per lane over the wave, the same value in every lane (fixed order: the scan's).
 __device__ __forceinline__ float wave_sum_dpp(float x) {

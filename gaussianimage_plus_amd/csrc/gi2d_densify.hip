@@ -36,23 +36,6 @@ struct RowArrays {  // the per-gaussian arrays of a fit that move together; widt
     int offset[GI2D_DENSIFY_MAX_ARRAYS + 1];  // float offset of the array's row inside a scratch row
 };
 
-// block-wide exclusive scan of one int per lane (1024 lanes), returns the exclusive prefix and the block total
-__device__ __forceinline__ int block_exclusive_scan(int v, int *wsum /* [17] LDS */, int &total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, waves = (int)blockDim.x >> 6;
-    const int incl = wave_inclusive_scan(v);
-    __syncthreads();  // wsum may still be read from the previous use
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-    for (int k = 0; k < waves; ++k) {
-        const int s = wsum[k];
-        if (k < wv) base += s;
-        total += s;
-    }
-    return base + incl - v;
-}
-
 // models/gaussianimage_covariance.py:372-379
 __device__ __forceinline__ bool positive_definite(float a, float b, float c) {
 #pragma clang fp contract(off)

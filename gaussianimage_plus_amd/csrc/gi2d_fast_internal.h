@@ -71,7 +71,6 @@ typedef int4 PrevBox;
    (gi2d_train.hip), 4 the row pool ran out */
 #define GI2D_STATUS_POOL 4
 __host__ __device__ __forceinline__ PrevBox no_box() { return make_int4(0, 0, -1, 0); }
-static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 // THE INBOX OF A TILE -- how a gaussian enters a tile without waiting for an atomic's answer.  The update kernel of a
 // fit ends with the binning step of the next iteration, and a gaussian that has ENTERED a tile used to reserve its slot
 // in the tile's row with a returning atomic: a device-scope round trip at the very end of every lane's dependency

@@ -16,13 +16,11 @@
 //           sweep over the id space for lists longer than 1024).
 // Integer work, HBM-light: 12 B read per gaussian twice, 4 B written + 4 B read + 4 B written
 // per intersection.
-#include "gi2d_common.h"
+#include "gi2d_tile_order.h"
 
 namespace gi2d {
 
 #define GI2D_SUB 8
-#define GI2D_FB_RANK_MAX 1024
-#define GI2D_FB_BITMAP_WORDS 8192
 
 __device__ __forceinline__ bool mapped_bbox(int idx, const float2 *__restrict__ xys,
                                             const int32_t *__restrict__ radii, int tiles_x, int tiles_y,
@@ -57,12 +55,10 @@ __global__ __launch_bounds__(1024) void fb_scan_kernel(int num_tiles, int capaci
                                                        int32_t *__restrict__ cursor,
                                                        int32_t *__restrict__ bins,
                                                        int32_t *__restrict__ status) {
-    __shared__ int wave_sums[16];
-    __shared__ int carry_s;
+    __shared__ int wsum[16];
     const int n = num_tiles * GI2D_SUB;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
+    const int tid = threadIdx.x;
+    int total = 0;  // sum of the steps so far, the same in every lane
     for (int base = 0; base < n; base += 8192) {
         // 8 consecutive counters per lane = one tile's sub-counters
         const int i0 = base + tid * GI2D_SUB;
@@ -79,13 +75,9 @@ __global__ __launch_bounds__(1024) void fb_scan_kernel(int num_tiles, int capaci
 #pragma unroll
             for (int k = 0; k < GI2D_SUB; ++k) v[k] = 0;
         }
-        const int incl = wave_inclusive_scan(local);
-        if (lane == 63) wave_sums[wv] = incl;
-        __syncthreads();
-        int wave_off = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) wave_off += (k < wv) ? wave_sums[k] : 0;
-        int run = carry_s + wave_off + incl - local;
+        int step_total;
+        int run = total + block_exclusive_scan(local, wsum, step_total);
+        total += step_total;
         if (i0 < n) {
             const int tile = i0 / GI2D_SUB;
             bins[2 * tile] = local > 0 ? min(run, capacity) : 0;
@@ -102,12 +94,8 @@ __global__ __launch_bounds__(1024) void fb_scan_kernel(int num_tiles, int capaci
             *reinterpret_cast<int4 *>(cursor + i0) = z;
             *reinterpret_cast<int4 *>(cursor + i0 + 4) = z;
         }
-        __syncthreads();
-        if (tid == 1023) carry_s = run;
-        __syncthreads();
     }
     if (tid == 0) {
-        const int total = carry_s;
         start[n] = total;
         status[0] = total;
         status[1] = total > capacity ? 1 : 0;
@@ -140,75 +128,35 @@ __global__ __launch_bounds__(256) void fb_order_kernel(int n, int capacity, cons
                                                        const int32_t *__restrict__ unsorted,
                                                        int32_t *__restrict__ gids_sorted) {
     __shared__ union {
-        int ids[GI2D_FB_RANK_MAX];
-        uint32_t bits[GI2D_FB_BITMAP_WORDS];
+        int ids[GI2D_RANK_MAX];
+        uint32_t bits[GI2D_BITMAP_WORDS];
     } sm;
     __shared__ int wsum[4];
-    const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tile = blockIdx.x;
     const int s0 = min(start[tile * GI2D_SUB], capacity);
     const int len = min(start[(tile + 1) * GI2D_SUB], capacity) - s0;
     if (len <= 0) return;
-    if (len <= GI2D_FB_RANK_MAX) {
-        for (int e = tid; e < len; e += 256) sm.ids[e] = unsorted[s0 + e];
-        __syncthreads();
-        for (int e = tid; e < len; e += 256) {
-            const int mine = sm.ids[e];
-            int rank = 0;
-            for (int j = 0; j < len; ++j) rank += (sm.ids[j] < mine) ? 1 : 0;
-            gids_sorted[s0 + rank] = mine;
-        }
-        return;
-    }
-    int emitted = 0;
-    for (int win = 0; win < n; win += 32 * GI2D_FB_BITMAP_WORDS) {
-        for (int w = tid; w < GI2D_FB_BITMAP_WORDS; w += 256) sm.bits[w] = 0u;
-        __syncthreads();
-        for (int e = tid; e < len; e += 256) {
-            const int rel = unsorted[s0 + e] - win;
-            if (rel >= 0 && rel < 32 * GI2D_FB_BITMAP_WORDS) atomicOr(&sm.bits[rel >> 5], 1u << (rel & 31));
-        }
-        __syncthreads();
-        const int w0 = tid * (GI2D_FB_BITMAP_WORDS / 256);
-        int cnt = 0;
-        for (int w = 0; w < GI2D_FB_BITMAP_WORDS / 256; ++w) cnt += __popc(sm.bits[w0 + w]);
-        const int incl = wave_inclusive_scan(cnt);
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        int off = emitted + incl - cnt;
-        for (int k = 0; k < wv; ++k) off += wsum[k];
-        const int win_total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        for (int w = 0; w < GI2D_FB_BITMAP_WORDS / 256; ++w) {
-            uint32_t b = sm.bits[w0 + w];
-            while (b) {
-                const int bit = __ffs(b) - 1;
-                b &= b - 1;
-                gids_sorted[s0 + off++] = win + ((w0 + w) << 5) + bit;
-            }
-        }
-        emitted += win_total;
-        __syncthreads();
-    }
+    auto id_of = [&](int e) { return unsorted[s0 + e]; };
+    auto emit = [&](int k, int id) { gids_sorted[s0 + k] = id; };
+    if (len <= GI2D_RANK_MAX)
+        tile_rank_sort(sm.ids, len, id_of, emit);
+    else  // a sweep over the id space [0, n)
+        tile_bitmap_sweep(sm.bits, wsum, len, n, id_of, emit);
 }
 
-static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 struct FbWs {
     int32_t *counts, *start, *cursor, *unsorted;
     size_t bytes;
 };
 static FbWs carve_fb(void *base, int capacity, int num_tiles) {
     FbWs w;
-    char *b = (char *)base;
-    size_t off = 0;
-    const size_t c = (size_t)(num_tiles > 0 ? num_tiles : 1) * GI2D_SUB;
-    w.counts = (int32_t *)(b + off);
-    off += align_up(c * sizeof(int32_t));
-    w.start = (int32_t *)(b + off);
-    off += align_up((c + 1) * sizeof(int32_t));
-    w.cursor = (int32_t *)(b + off);
-    off += align_up(c * sizeof(int32_t));
-    w.unsorted = (int32_t *)(b + off);
-    off += align_up((size_t)(capacity > 0 ? capacity : 1) * sizeof(int32_t));
-    w.bytes = off;
+    Carver c{base};
+    const size_t counters = (size_t)(num_tiles > 0 ? num_tiles : 1) * GI2D_SUB;
+    w.counts = c.take<int32_t>(counters);
+    w.start = c.take<int32_t>(counters + 1);
+    w.cursor = c.take<int32_t>(counters);
+    w.unsorted = c.take<int32_t>((size_t)(capacity > 0 ? capacity : 1));
+    w.bytes = c.off;
     return w;
 }
 
@@ -245,11 +193,8 @@ int gi2d_bin_gaussians(int n, int capacity, const float *xys, const int32_t *rad
         return GI2D_ERR_WORKSPACE_TOO_SMALL;
     }
     FbWs w = carve_fb(workspace, capacity, (int)t);
-    hipError_t e = hipMemsetAsync(w.counts, 0, sizeof(int32_t) * (size_t)t * GI2D_SUB, st);
-    if (e != hipSuccess) {
-        set_error(hipGetErrorString(e));
-        return (int)e;
-    }
+    const int rc = zero_async(w.counts, sizeof(int32_t) * (size_t)t * GI2D_SUB, st, "bin_gaussians");
+    if (rc != GI2D_OK) return rc;
     if (n > 0)
         hipLaunchKernelGGL(fb_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, (const float2 *)xys,
                            radii, tiles_x, tiles_y, radius_clip, w.counts);

@@ -16,13 +16,21 @@
 //             part of the quadratic form hoisted, accumulating 7 sums in registers -- no
 //             cross-lane reduction at all.  Row partials go through LDS to the lane that owns
 //             the gaussian, which adds them in row order and stores ONE 48-byte partial per
-//             (tile, gaussian).  A second kernel sums each gaussian's partials in tile order.
+//             (tile, gaussian).  A second kernel sums each gaussian's partials in ascending tile
+//             order, in one of three forms that differ only in how a gaussian finds its rows:
+//             plan (cum_tiles_hit + inv_perm of the forward binning), box (the tile box re-derived
+//             from xys and radii) and generic (an index rebuilt from gaussian_ids_sorted and walked
+//             in ascending list position, gi2d_gidx.h).  The generic form keeps that order for ANY
+//             number of tiles per gaussian, so it and the plan form give the same bits (the box
+//             form too, up to the size at which it hands a gaussian to a whole wave).
 //             No float atomics anywhere: gradients are bitwise reproducible, and the 72 atomics
 //             per intersection of the reference become one coalesced 48-byte store.
 //
 // Roofline: algorithmic HBM bytes are 40*M + 20*H*W (fwd) and 40*M + 16*H*W + 36*N (bwd)
 // (SURVEY 8d); every staged gaussian is reused by up to 256 pixels, so the kernels are bound by
 // VALU issue (v_exp_f32 + ~25 fp32 ops per pixel-gaussian pair), not by HBM.
+#include <type_traits>
+
 #include "gi2d_gidx.h"
 #include "gi2d_raster_core.h"
 
@@ -182,12 +190,11 @@ __global__ __launch_bounds__(256) void gather_bbox_kernel(
     if (g < n) store_grads(g, acc, v_xy, v_conic, v_rgb, v_opacity, v_abs_xy);
 }
 
-// Generic form: rebuild the gaussian-major index from gaussian_ids_sorted (gi2d_gidx.h: gidx_count_kernel,
-// gidx_scatter_kernel -- shared with the N-channel backward).
-#define GI2D_ORDERED_MAX 64 /* gaussians on <= 64 tiles are summed in ascending position order */
+// Generic form: the gaussian-major index is rebuilt from gaussian_ids_sorted and walked in ascending list position
+// (gi2d_gidx.h, shared with the N-channel backward) -- the plan form's order, so the two forms agree bit for bit.
 __global__ __launch_bounds__(256) void gather_generic_kernel(int n, int m,
                                                              const int32_t *__restrict__ start,
-                                                             const int32_t *__restrict__ gslots,
+                                                             int32_t *__restrict__ gslots,
                                                              const float4 *__restrict__ partials,
                                                              float2 *__restrict__ v_xy,
                                                              float *__restrict__ v_conic,
@@ -199,48 +206,26 @@ __global__ __launch_bounds__(256) void gather_generic_kernel(int n, int m,
     float acc[11];
 #pragma unroll
     for (int q = 0; q < 11; ++q) acc[q] = 0.f;
-    const int s0 = start[g], s1 = start[g + 1];
-    const int cnt = s1 - s0;
-    if (cnt <= GI2D_ORDERED_MAX) {
-        int last = -1;
-        for (int r = 0; r < cnt; ++r) {  // selection by ascending sorted position (cnt is small)
-            int best = 0x7fffffff;
-            for (int s = s0; s < s1; ++s) {
-                const int p = gslots[s];
-                best = (p > last && p < best) ? p : best;
-            }
-            add_partial(acc, partials, best);
-            last = best;
-        }
-    } else {
-        for (int s = s0; s < s1; ++s) add_partial(acc, partials, gslots[s]);
-    }
+    gidx_for_each_ascending(gslots, start[g], start[g + 1], [&](int pos) { add_partial(acc, partials, pos); });
     store_grads(g, acc, v_xy, v_conic, v_rgb, v_opacity, v_abs_xy);
 }
 
-static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-struct BwdWs {
-    float4 *partials;
-    int32_t *counts, *start, *cursor, *gslots;
-    size_t bytes;
-};
-static BwdWs carve_bwd_ws(void *base, int n, int m) {
-    BwdWs w;
-    char *b = (char *)base;
-    size_t off = 0;
-    const size_t nn = (size_t)(n > 0 ? n : 1), mm = (size_t)(m > 0 ? m : 1);
-    w.partials = (float4 *)(b + off);
-    off += align_up(mm * 3 * sizeof(float4));
-    w.counts = (int32_t *)(b + off);
-    off += align_up(nn * sizeof(int32_t));
-    w.start = (int32_t *)(b + off);
-    off += align_up((nn + 1) * sizeof(int32_t));
-    w.cursor = (int32_t *)(b + off);
-    off += align_up(nn * sizeof(int32_t));
-    w.gslots = (int32_t *)(b + off);
-    off += align_up(mm * sizeof(int32_t));
-    w.bytes = off;
-    return w;
+#define GI2D_RGB_ROW 12 /* floats of one partial row: three float4 */
+
+// both instantiations of the tile kernel from one argument list
+static void launch_raster_bwd(bool with_abs, long long t, int tiles_x, int tiles_y, unsigned w, unsigned h,
+                              const int32_t *gids, const int32_t *bins, int rows, const float *xys,
+                              const float *conics, const float *colors, const float *opac, const int32_t *final_idx,
+                              const float *v_output, float4 *partials, hipStream_t st) {
+    auto launch = [&](auto abs) {
+        hipLaunchKernelGGL(raster_bwd_kernel<decltype(abs)::value>, dim3((unsigned)t), dim3(256), 0, st, tiles_x,
+                           tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows, (const float2 *)xys, conics,
+                           colors, opac, final_idx, v_output, partials);
+    };
+    if (with_abs)
+        launch(std::true_type{});
+    else
+        launch(std::false_type{});
 }
 
 static int raster_forward(int tiles_x, int tiles_y, unsigned w, unsigned h, const int32_t *gids,
@@ -294,7 +279,7 @@ static int raster_backward(int n, int m, unsigned h, unsigned w, const int32_t *
     }
     const int tiles_x = (int)((w + GI2D_TILE - 1) / GI2D_TILE), tiles_y = (int)((h + GI2D_TILE - 1) / GI2D_TILE);
     const long long t = (long long)tiles_x * tiles_y;
-    BwdWs wsp = carve_bwd_ws(ws, n, m);
+    BwdWs wsp = carve_bwd_ws(ws, n, m, GI2D_RGB_ROW);
     if (m > 0 && t > 0) {
         if (!gids || !bins || !xys || !conics || !colors || !opac || !final_idx || !v_output) {
             set_error("rasterize backward: null input");
@@ -302,22 +287,11 @@ static int raster_backward(int n, int m, unsigned h, unsigned w, const int32_t *
         }
         if ((long long)rows < t) {
             // bins do not cover the grid: positions no tile claims must still read as zero
-            hipError_t e = hipMemsetAsync(wsp.partials, 0, sizeof(float4) * 3 * (size_t)m, st);
-            if (e != hipSuccess) {
-                set_error(hipGetErrorString(e));
-                return (int)e;
-            }
+            const int rc = zero_async(wsp.partials, wsp.partial_bytes, st, "rasterize backward");
+            if (rc != GI2D_OK) return rc;
         }
-        if (v_abs_xy)
-            hipLaunchKernelGGL(raster_bwd_kernel<true>, dim3((unsigned)t), dim3(256), 0, st, tiles_x,
-                               tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows,
-                               (const float2 *)xys, conics, colors, opac, final_idx, v_output,
-                               wsp.partials);
-        else
-            hipLaunchKernelGGL(raster_bwd_kernel<false>, dim3((unsigned)t), dim3(256), 0, st, tiles_x,
-                               tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows,
-                               (const float2 *)xys, conics, colors, opac, final_idx, v_output,
-                               wsp.partials);
+        launch_raster_bwd(v_abs_xy != nullptr, t, tiles_x, tiles_y, w, h, gids, bins, rows, xys, conics, colors, opac,
+                          final_idx, v_output, wsp.partials, st);
     }
     const int mm = (t > 0) ? m : 0;
     if (cum) {
@@ -325,19 +299,8 @@ static int raster_backward(int n, int m, unsigned h, unsigned w, const int32_t *
                            inv_perm, wsp.partials, (float2 *)v_xy, v_conic, v_rgb, v_opacity,
                            (float4 *)v_abs_xy);
     } else {
-        hipError_t e = hipMemsetAsync(wsp.counts, 0, sizeof(int32_t) * (size_t)n, st);
-        if (e != hipSuccess) {
-            set_error(hipGetErrorString(e));
-            return (int)e;
-        }
-        if (mm > 0)
-            hipLaunchKernelGGL(gidx_count_kernel, dim3((mm + 255) / 256), dim3(256), 0, st, mm, n,
-                               gids, wsp.counts);
-        int rc = launch_exclusive_scan_with_cursor(n, wsp.counts, wsp.start, wsp.cursor, st);
+        const int rc = build_gaussian_index(mm, n, gids, wsp, st);
         if (rc != GI2D_OK) return rc;
-        if (mm > 0)
-            hipLaunchKernelGGL(gidx_scatter_kernel, dim3((mm + 255) / 256), dim3(256), 0, st, mm, n,
-                               gids, wsp.start, wsp.cursor, wsp.gslots);
         hipLaunchKernelGGL(gather_generic_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, mm,
                            wsp.start, wsp.gslots, wsp.partials, (float2 *)v_xy, v_conic, v_rgb,
                            v_opacity, (float4 *)v_abs_xy);
@@ -352,7 +315,7 @@ using namespace gi2d;
 extern "C" {
 
 size_t gi2d_rasterize_backward_workspace_bytes(int n, int m) {
-    return carve_bwd_ws(nullptr, n, m).bytes;
+    return carve_bwd_ws(nullptr, n, m, GI2D_RGB_ROW).bytes;
 }
 
 int gi2d_rasterize_backward_tiles(unsigned h, unsigned w, const int32_t *gids, const int32_t *bins,
@@ -366,14 +329,8 @@ int gi2d_rasterize_backward_tiles(unsigned h, unsigned w, const int32_t *gids, c
         set_error("rasterize backward tiles: null pointer");
         return GI2D_ERR_INVALID_ARGUMENT;
     }
-    if (with_abs)
-        hipLaunchKernelGGL(raster_bwd_kernel<true>, dim3((unsigned)t), dim3(256), 0, (hipStream_t)st, tiles_x,
-                           tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows, (const float2 *)xys, conics,
-                           colors, opac, final_idx, v_output, (float4 *)partials);
-    else
-        hipLaunchKernelGGL(raster_bwd_kernel<false>, dim3((unsigned)t), dim3(256), 0, (hipStream_t)st, tiles_x,
-                           tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows, (const float2 *)xys, conics,
-                           colors, opac, final_idx, v_output, (float4 *)partials);
+    launch_raster_bwd(with_abs != 0, t, tiles_x, tiles_y, w, h, gids, bins, rows, xys, conics, colors, opac, final_idx,
+                      v_output, (float4 *)partials, (hipStream_t)st);
     return check_launch("rasterize backward tiles");
 }
 

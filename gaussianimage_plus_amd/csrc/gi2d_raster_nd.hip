@@ -211,10 +211,7 @@ __global__ __launch_bounds__(256) void nd_bwd_kernel(
 }
 
 // Per-gaussian sum of the rows, in ascending list position -- the lists are tile-major, so that is ascending tile
-// order.  The index hands the positions over in the order its atomics ran: up to 64 of them are picked smallest first
-// as the RGB gather does; a longer run (a gaussian on more than 64 tiles) is put in order in place first -- the segment
-// belongs to this lane alone.
-#define GI2D_ND_ORDERED_MAX 64
+// order (gi2d_gidx.h: the walk the RGB generic gather uses).
 template <int C>
 __global__ __launch_bounds__(256) void nd_gather_kernel(int n, const int32_t *__restrict__ start,
                                                         int32_t *__restrict__ gslots,
@@ -227,37 +224,13 @@ __global__ __launch_bounds__(256) void nd_gather_kernel(int n, const int32_t *__
     float acc[KP];
 #pragma unroll
     for (int k = 0; k < KP; ++k) acc[k] = 0.f;
-    auto add_row = [&](int pos) {
+    gidx_for_each_ascending(gslots, start[g], start[g + 1], [&](int pos) {
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
             const float4 p = partials[(size_t)pos * Q + q];
             acc[4 * q] += p.x, acc[4 * q + 1] += p.y, acc[4 * q + 2] += p.z, acc[4 * q + 3] += p.w;
         }
-    };
-    const int s0 = start[g], s1 = start[g + 1];
-    if (s1 - s0 <= GI2D_ND_ORDERED_MAX) {
-        int last = -1;
-        for (int r = s0; r < s1; ++r) {
-            int best = 0x7fffffff;
-            for (int s = s0; s < s1; ++s) {
-                const int p = gslots[s];
-                best = (p > last && p < best) ? p : best;
-            }
-            add_row(best);
-            last = best;
-        }
-    } else {
-        for (int s = s0 + 1; s < s1; ++s) {  // insertion sort: the atomics mostly ran in position order already
-            const int p = gslots[s];
-            int q = s - 1;
-            while (q >= s0 && gslots[q] > p) {
-                gslots[q + 1] = gslots[q];
-                --q;
-            }
-            gslots[q + 1] = p;
-        }
-        for (int s = s0; s < s1; ++s) add_row(gslots[s]);
-    }
+    });
     v_xy[g] = make_float2(acc[0], acc[1]);
     v_conic[3 * (size_t)g] = acc[2];
     v_conic[3 * (size_t)g + 1] = acc[3];
@@ -268,32 +241,6 @@ __global__ __launch_bounds__(256) void nd_gather_kernel(int n, const int32_t *__
 }
 
 // ------------------------------------------------------------------------------------ host side
-static inline size_t nd_align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-struct NdBwdWs {
-    float4 *partials;
-    int32_t *counts, *start, *cursor, *gslots;
-    size_t partial_bytes, bytes;
-};
-static NdBwdWs nd_carve_ws(void *base, int n, int m, int channels) {
-    NdBwdWs w;
-    char *b = (char *)base;
-    size_t off = 0;
-    const size_t nn = (size_t)(n > 0 ? n : 1), mm = (size_t)(m > 0 ? m : 1);
-    w.partials = (float4 *)(b + off);
-    w.partial_bytes = mm * (size_t)GI2D_ND_ROW(channels) * sizeof(float);
-    off += nd_align_up(w.partial_bytes);
-    w.counts = (int32_t *)(b + off);
-    off += nd_align_up(nn * sizeof(int32_t));
-    w.start = (int32_t *)(b + off);
-    off += nd_align_up((nn + 1) * sizeof(int32_t));
-    w.cursor = (int32_t *)(b + off);
-    off += nd_align_up(nn * sizeof(int32_t));
-    w.gslots = (int32_t *)(b + off);
-    off += nd_align_up(mm * sizeof(int32_t));
-    w.bytes = off;
-    return w;
-}
-
 static bool nd_channels_ok(int channels, const char *what) {
     if (channels >= 1 && channels <= GI2D_ND_MAX_CHANNELS) return true;
     char msg[160];
@@ -306,15 +253,6 @@ static bool nd_channels_ok(int channels, const char *what) {
 // one instantiation per channel count: `X(C)` for C = 1..GI2D_ND_MAX_CHANNELS
 #define GI2D_ND_FOR_CHANNELS(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
 static_assert(GI2D_ND_MAX_CHANNELS == 12, "GI2D_ND_FOR_CHANNELS lists the channel counts");
-
-static int nd_zero(void *p, size_t bytes, hipStream_t st) {
-    const hipError_t e = hipMemsetAsync(p, 0, bytes, st);
-    if (e != hipSuccess) {
-        set_error(hipGetErrorString(e));
-        return (int)e;
-    }
-    return GI2D_OK;
-}
 
 }  // namespace gi2d
 
@@ -362,7 +300,7 @@ int gi2d_nd_rasterize_sum_forward(int tiles_x, int tiles_y, unsigned w, unsigned
 
 size_t gi2d_nd_rasterize_backward_workspace_bytes(int n, int m, int channels) {
     const int c = channels < 1 ? 1 : (channels > GI2D_ND_MAX_CHANNELS ? GI2D_ND_MAX_CHANNELS : channels);
-    return nd_carve_ws(nullptr, n, m, c).bytes;
+    return carve_bwd_ws(nullptr, n, m, GI2D_ND_ROW(c)).bytes;
 }
 
 int gi2d_nd_rasterize_sum_backward(int n, int m, unsigned h, unsigned w, int channels, const int32_t *gids,
@@ -388,10 +326,11 @@ int gi2d_nd_rasterize_sum_backward(int n, int m, unsigned h, unsigned w, int cha
         return GI2D_ERR_INVALID_ARGUMENT;
     }
     if (m == 0 || t == 0 || rows == 0) {  // nothing was rasterized: zero gradients
-        int rc = nd_zero(v_xy, sizeof(float) * 2 * (size_t)n, st);
-        if (rc == GI2D_OK) rc = nd_zero(v_conic, sizeof(float) * 3 * (size_t)n, st);
-        if (rc == GI2D_OK) rc = nd_zero(v_colors, sizeof(float) * (size_t)channels * (size_t)n, st);
-        if (rc == GI2D_OK) rc = nd_zero(v_opacity, sizeof(float) * (size_t)n, st);
+        const char *what = "nd rasterize backward";
+        int rc = zero_async(v_xy, sizeof(float) * 2 * (size_t)n, st, what);
+        if (rc == GI2D_OK) rc = zero_async(v_conic, sizeof(float) * 3 * (size_t)n, st, what);
+        if (rc == GI2D_OK) rc = zero_async(v_colors, sizeof(float) * (size_t)channels * (size_t)n, st, what);
+        if (rc == GI2D_OK) rc = zero_async(v_opacity, sizeof(float) * (size_t)n, st, what);
         return rc;
     }
     if (!ws || ws_bytes < gi2d_nd_rasterize_backward_workspace_bytes(n, m, channels)) {
@@ -402,12 +341,11 @@ int gi2d_nd_rasterize_sum_backward(int n, int m, unsigned h, unsigned w, int cha
         set_error("nd rasterize backward: null input");
         return GI2D_ERR_INVALID_ARGUMENT;
     }
-    const NdBwdWs wsp = nd_carve_ws(ws, n, m, channels);
+    const BwdWs wsp = carve_bwd_ws(ws, n, m, GI2D_ND_ROW(channels));
     // list positions that no tile claims (bins that do not cover [0, M)) must read as zero rows
-    int rc = nd_zero(wsp.partials, wsp.partial_bytes, st);
-    if (rc == GI2D_OK) rc = nd_zero(wsp.counts, sizeof(int32_t) * (size_t)n, st);
+    int rc = zero_async(wsp.partials, wsp.partial_bytes, st, "nd rasterize backward");
     if (rc != GI2D_OK) return rc;
-    const dim3 per_entry((unsigned)((m + 255) / 256)), per_gaussian((unsigned)((n + 255) / 256));
+    const dim3 per_gaussian((unsigned)((n + 255) / 256));
     switch (channels) {
 #define GI2D_ND_LAUNCH(C)                                                                                          \
     case C:                                                                                                        \
@@ -418,10 +356,8 @@ int gi2d_nd_rasterize_sum_backward(int n, int m, unsigned h, unsigned w, int cha
         GI2D_ND_FOR_CHANNELS(GI2D_ND_LAUNCH)
 #undef GI2D_ND_LAUNCH
     }
-    hipLaunchKernelGGL(gidx_count_kernel, per_entry, dim3(256), 0, st, m, n, gids, wsp.counts);
-    rc = launch_exclusive_scan_with_cursor(n, wsp.counts, wsp.start, wsp.cursor, st);
+    rc = build_gaussian_index(m, n, gids, wsp, st);
     if (rc != GI2D_OK) return rc;
-    hipLaunchKernelGGL(gidx_scatter_kernel, per_entry, dim3(256), 0, st, m, n, gids, wsp.start, wsp.cursor, wsp.gslots);
     switch (channels) {
 #define GI2D_ND_LAUNCH(C)                                                                                        \
     case C:                                                                                                      \

@@ -160,6 +160,19 @@ def test_size_queries_need_no_gpu():
     lib = _lib.load()
     assert lib.gi2d_sort_workspace_bytes(1000, 64) >= 4 * (1000 + 3 * 64)
     assert lib.gi2d_rasterize_backward_workspace_bytes(100, 1000) >= 1000 * 48
+    # The layouts are part of the ABI (callers size and reuse buffers by these numbers): every region on a 256-byte
+    # boundary, empty sizes counted as one element.
+    exact = {
+        "gi2d_sort_workspace_bytes": {(0, 0): 1280, (1000, 64): 5376, (63, 64): 1536, (123457, 1536): 513024},
+        "gi2d_bin_workspace_bytes": {(0, 0): 1024, (1000, 64): 10496, (511, 1025): 101120, (200000, 1536): 947712},
+        "gi2d_rasterize_backward_workspace_bytes": {(0, 0): 1280, (100, 1000): 53760, (64, 63): 4352,
+                                                    (50000, 231077): 12616704},
+        "gi2d_nd_rasterize_backward_workspace_bytes": {(0, 0, 1): 1280, (100, 1000, 2): 37632, (100, 1000, 3): 53760,
+                                                       (64, 63, 7): 5376, (50000, 231077, 12): 20011264},
+    }
+    for fn, rows in exact.items():
+        for args, want in rows.items():
+            assert getattr(lib, fn)(*args) == want, (fn, args)
 
 
 def test_quant_argument_checks_need_no_gpu():

@@ -198,6 +198,26 @@ def test_sort_long_tiles_and_depth_keys(C, oracle):
     assert n(srt["status"])[0] == 1
 
 
+def test_sort_across_the_scan_step_boundary(C, oracle):
+    """The tile scan of sort_intersects walks the tile counts 4096 at a time; with 4097 tiles the last one starts at
+    the total the first step hands on.  Tiles 4095 and 4096 -- either side of the step -- are populated."""
+    rng = np.random.default_rng(17)
+    num_tiles = 4097
+    some = rng.choice(np.arange(1, 4095), 40, replace=False)
+    tiles = np.concatenate([np.full(30, 0), np.full(45, 4095), np.full(25, 4096), rng.choice(some, 300)]).astype(np.int64)
+    rng.shuffle(tiles)
+    isect = tiles << 32
+    gids = rng.integers(0, 1000, len(tiles)).astype(np.int32)
+    srt = C.sort_intersects(t(isect), t(gids), num_tiles, want_bins=True)
+    so, go = oracle.sort_intersects(isect, gids)
+    assert np.array_equal(n(srt["isect_ids_sorted"]), so) and np.array_equal(n(srt["gaussian_ids_sorted"]), go)
+    counts = np.bincount(tiles, minlength=num_tiles)
+    start = np.cumsum(counts) - counts
+    want = np.where(counts[:, None] > 0, np.stack([start, start + counts], 1), 0).astype(np.int32)
+    assert want[4095].tolist() == [330, 375] and want[4096].tolist() == [375, 400]
+    assert np.array_equal(n(srt["tile_bins"]), want)
+
+
 # ------------------------------------------------------------------------------- rasterizer
 def _raster_inputs(g):
     return dict(gids=t(g["gids_sorted"]), bins=t(g["tile_bins"]), xys=t(g["xys"]), conics=t(g["conics"]),
@@ -417,6 +437,68 @@ def test_bin_gaussians_long_tiles(C, oracle):
     assert int(status[0]) == m
     assert (bins_o[:6, 1] - bins_o[:6, 0]).max() > 1024
     assert np.array_equal(n(gids)[:m], go) and np.array_equal(n(bins), bins_o[:tb[0] * tb[1]])
+
+
+def test_bin_gaussians_across_the_scan_step_boundary(C, oracle):
+    """The counter scan of bin_gaussians walks 1024 tiles at a time; a 33 x 32 grid has 1056, so tile 1024 starts at
+    the total the first step hands on.  Gaussians whose boxes straddle tiles 1023 / 1024 (the two leftmost of the last
+    tile row) and gaussians on the last tile; ids, tile_bins and status against the reference pipeline, bit for bit."""
+    rng = np.random.default_rng(23)
+    h, w, npts = 512, 528, 200
+    tb = oracle.tile_bounds(h, w)
+    assert tb[0] * tb[1] == 1056
+    xys = (rng.random((npts, 2)) * np.array([w, h])).astype(np.float32)
+    radii = rng.integers(0, 30, npts).astype(np.int32)
+    xys[:12] = np.array([16.0, 504.0]) + rng.uniform(-3, 3, (12, 2))    # on the edge between tiles 1023 and 1024
+    radii[:12] = rng.integers(5, 20, 12)
+    xys[12:20] = np.array([520.0, 505.0]) + rng.uniform(-4, 4, (8, 2))  # inside tile 1055, the last one
+    radii[12:20] = rng.integers(1, 40, 8)
+    m, cum = oracle.compute_cumulative_intersects(_num_tiles_hit(xys, radii, tb))
+    _, _, so, go, bins_o = oracle.bin_and_sort_gaussians(npts, m, xys, np.zeros(npts, np.float32), radii, cum, tb, 1.0)
+    bins_o = bins_o[:1056]
+    in_tile = lambda k: set(go[bins_o[k, 0]:bins_o[k, 1]].tolist())
+    assert len(in_tile(1023) & in_tile(1024)) >= 12 and len(in_tile(1055)) >= 8
+    assert bins_o[1024, 0] > 0  # the hand-over is not zero
+    gids, bins, status = C.bin_gaussians(t(xys), t(radii), tb, 1.0, m + 10)
+    assert n(status).tolist() == [m, 0, 0, 0]
+    assert np.array_equal(n(gids)[:m], go) and np.array_equal(n(bins), bins_o)
+
+
+def test_generic_gather_equals_plan_form_above_64_tiles(C, oracle):
+    """Three gaussians that cover all 90 tiles of a 160x144 picture (the scene of test_nd_raster_gpu.py::
+    test_gaussians_on_more_than_64_tiles, with three colours): the generic form -- index rebuilt from
+    gaussian_ids_sorted -- sums a gaussian's rows in ascending list position whatever their number, which is the plan
+    form's order: the two agree bit for bit, run after run, and with the oracle to the usual tolerance."""
+    h, w, npts = 144, 160, 3
+    tb = oracle.tile_bounds(h, w)
+    xys = np.array([[80.3, 70.6], [20.5, 130.2], [150.1, 10.7]], np.float32)
+    conics = np.array([[4e-4, 1e-4, 5e-4], [3e-4, -1e-4, 3e-4], [6e-4, 0.0, 2e-4]], np.float32)
+    op = np.array([[0.9], [0.6], [1.0]], np.float32)
+    radii = np.full(npts, 400, np.int32)
+    rng = np.random.default_rng(7)
+    col = (2 * rng.random((npts, 3)) - 1).astype(np.float32)
+    v_out = rng.normal(size=(h, w, 3)).astype(np.float32)
+    cum, total = C.cumsum_tiles_hit(t(np.full(npts, 90, np.int32)))
+    m = int(total.item())
+    assert m == 3 * 90
+    isect, gids = C.map_gaussian_to_intersects(npts, m, t(xys), torch.zeros(npts, device=DEV), t(radii), cum, tb, 1.0, False)
+    srt = C.sort_intersects(isect, gids, tb[0] * tb[1], want_inv_perm=True, want_bins=True)
+    go, bins = srt["gaussian_ids_sorted"], srt["tile_bins"]
+    assert (n(bins)[:, 1] - n(bins)[:, 0] == 3).all()
+    bg = torch.ones(3, device=DEV)
+    out, fT, fidx, _ = C.rasterize_sum_forward(tb, (16, 16, 1), (w, h, 1), go, bins, t(xys), t(conics), t(col), t(op), bg, False)
+    out_o, fT_o, fidx_o, amb, absimg = oracle.rasterize_sum_forward(tb, (16, 16, 1), (w, h, 1), n(go), n(bins), xys, conics,
+                                                                    col, op, with_aux=True)
+    _check_forward("wide", out, fT, fidx, out_o, fidx_o, amb, absimg)
+    want = oracle.rasterize_sum_backward(h, w, 16, 16, n(go), n(bins), xys, conics, col, op, None, fT_o, fidx_o, v_out,
+                                         with_aux=True)
+    args = (h, w, 16, 16, go, bins, t(xys), t(conics), t(col), t(op), bg, fT, t(fidx_o), t(v_out), None)
+    generic = C.rasterize_sum_backward(*args)
+    plan = C.rasterize_sum_plus_backward(*args, cum_tiles_hit=cum, inv_perm=srt["inv_perm"])
+    again = C.rasterize_sum_backward(*args)
+    for a, b, c in zip(generic[:4], plan, again[:4]):
+        assert torch.equal(a, b) and torch.equal(a, c)
+    _check_backward("wide generic", generic, want[:4], want[4], want[5])
 
 
 def test_backward_fast_path_matches_oracle_and_generic(C, oracle, golden_dir):
