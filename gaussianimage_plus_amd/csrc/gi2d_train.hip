@@ -603,49 +603,121 @@ __global__ __launch_bounds__(256) void train_reduce_update_batched_kernel(const 
 //     elements that attain the extremes receive sum-type gradients.  The update kernel cannot finish those elements
 //     (their gradient needs the global sums) in its main pass: it parks them in a short list for the closing step;
 //   * the log range of the NEXT iteration (min / max / tie counts of the updated variances).
+//
+// The rotation-scale model (BASELINE config 5): GaussianImage_RS.forward_quantize / train_iter_quantize
+// (models/gaussianimage_rs.py:443-485) with the quantiser set of training_setup (:131-163): four LSQ+
+// UniformQuantizers -- positions 12 bit unsigned (2 channels), the RAW `_scaling` 6 bit unsigned (2 channels; as
+// written, forward_quantize feeds the dequantised raw scaling to the projection without |. + bound|, :451-453),
+// rotation = sigmoid(_rotation) * 2 pi 6 bit SIGNED (1 channel), colours 6 bit unsigned (3 channels).  Every range is a
+// learned (scale, beta) pair, so there is no data-dependent range and nothing to park: the update kernel leaves 16
+// partial sums per wave and the closing kernel runs Adam on the 16 quantiser values
+//   qparams = xy scale[2], xy beta[2], scaling scale[2], scaling beta[2], rotation scale, beta, colour scale[3], beta[3]
+// (optimizer groups as the model file creates them: positions eps 1e-8; scaling + rotation together, eps 1e-15;
+// colours eps 1e-15 -- stepped every iteration like GaussianImage_Covariance.optimizer_step does, :235-247 there).
+//
+// How this section is laid out.  What the two models do alike is written once, as functions (templates on MODEL where
+// they touch a quantiser: 1 covariance, 2 rotation-scale) that read the model from QuantModel<MODEL>: the project + fill
+// body, the update kernel's opening (quant_update_open), projection backward (quant_project_grad), debug row and
+// snapshot stores, the per-wave partial row, the closing kernel's sums (quant_close_sums) and its Adam step on a
+// quantiser value (quant_value_step).  What they do differently stays in two plainly separate pieces per step: the
+// quantisers themselves (QuantModel<1> / <2>), the update bodies' quantiser backward (the covariance model parks its
+// extremes and keeps the next log range) and the closing steps (the covariance model finishes the parked entries).
 
-struct QuantVals {
-    float xs[2], xb[2], cs, cb, fs[3], fb[3];
-    float lbeta, lmax, lscale;
-};
-__device__ __forceinline__ QuantVals load_quant(const QuantTrain &Q) {
-    QuantVals v;
-    v.xs[0] = Q.qparams[0], v.xs[1] = Q.qparams[1], v.xb[0] = Q.qparams[2], v.xb[1] = Q.qparams[3];
-    v.cs = Q.qparams[4], v.cb = Q.qparams[5];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) v.fs[q] = Q.qparams[6 + q], v.fb[q] = Q.qparams[9 + q];
-    v.lbeta = Q.range[0];
-    v.lmax = Q.range[1];
-    v.lscale = quant_log_scale(v.lbeta, v.lmax, 0.f, Q.qmax_cov);
-    return v;
-}
+// What the shared functions need to know about a model.
+//   Vals   the learned quantiser values (and the log range) in registers; load(Q) fetches them
+//   Row    one gaussian's quantiser evaluations; quantise(..., xy, raw, col, row) fills it from the raw parameter rows
+//   KIND   the projection the dequantised values go through, par(row, .) its three inputs
+//   SUMS   partial sums a wave leaves for the closing kernel: a (v_scale, v_beta) pair per LSQ channel (+ the log pair)
+template <int MODEL>
+struct QuantModel;
 
-struct QuantRow {
-    QuantEval xy[2], cov[3], col[3];
-    float covx[3];  // _cov2d + bound: what the covariance quantiser sees
-};
-__device__ __forceinline__ void quantise_row(const TrainParams &P, const QuantTrain &Q, const QuantVals &v, int g,
-                                             QuantRow &r) {
-    const float *bd = P.bound + (size_t)P.bound_stride * g;
-    const float2 xy = load_row2(P.xyz, g);
-    r.xy[0] = quant_eval<GI2D_QUANT_LSQ>(xy.x, v.xs[0], v.xb[0], 0.f, Q.qmax_xy);
-    r.xy[1] = quant_eval<GI2D_QUANT_LSQ>(xy.y, v.xs[1], v.xb[1], 0.f, Q.qmax_xy);
-    const Row3 raw = load_row3(P.chol, g), col = load_row3(P.feat, g);
-    r.covx[0] = raw.a + bd[0], r.covx[1] = raw.b + bd[1], r.covx[2] = raw.c + bd[2];
-    r.cov[0] = quant_eval<GI2D_QUANT_LOG>(r.covx[0], v.lscale, v.lbeta, 0.f, Q.qmax_cov);
-    r.cov[1] = quant_eval<GI2D_QUANT_LSQ>(r.covx[1], v.cs, v.cb, 0.f, Q.qmax_cov);
-    r.cov[2] = quant_eval<GI2D_QUANT_LOG>(r.covx[2], v.lscale, v.lbeta, 0.f, Q.qmax_cov);
-    const float cin[3] = {col.a, col.b, col.c};
+template <>
+struct QuantModel<1> {
+    static constexpr int KIND = kCovariance, SUMS = 14;
+    struct Vals {
+        float xs[2], xb[2], cs, cb, fs[3], fb[3];
+        float lbeta, lmax, lscale;
+    };
+    struct Row {
+        QuantEval xy[2], cov[3], col[3];
+        float covx[3];  // _cov2d + bound: what the covariance quantiser sees
+    };
+    static __device__ __forceinline__ Vals load(const QuantTrain &Q) {
+        Vals v;
+        v.xs[0] = Q.qparams[0], v.xs[1] = Q.qparams[1], v.xb[0] = Q.qparams[2], v.xb[1] = Q.qparams[3];
+        v.cs = Q.qparams[4], v.cb = Q.qparams[5];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) r.col[q] = quant_eval<GI2D_QUANT_LSQ>(cin[q], v.fs[q], v.fb[q], 0.f, Q.qmax_col);
-}
+        for (int q = 0; q < 3; ++q) v.fs[q] = Q.qparams[6 + q], v.fb[q] = Q.qparams[9 + q];
+        v.lbeta = Q.range[0];
+        v.lmax = Q.range[1];
+        v.lscale = quant_log_scale(v.lbeta, v.lmax, 0.f, Q.qmax_cov);
+        return v;
+    }
+    static __device__ __forceinline__ void quantise(const TrainParams &P, const QuantTrain &Q, const Vals &v, int g,
+                                                    float2 xy, Row3 raw, Row3 col, Row &r) {
+        const float *bd = P.bound + (size_t)P.bound_stride * g;
+        r.xy[0] = quant_eval<GI2D_QUANT_LSQ>(xy.x, v.xs[0], v.xb[0], 0.f, Q.qmax_xy);
+        r.xy[1] = quant_eval<GI2D_QUANT_LSQ>(xy.y, v.xs[1], v.xb[1], 0.f, Q.qmax_xy);
+        r.covx[0] = raw.a + bd[0], r.covx[1] = raw.b + bd[1], r.covx[2] = raw.c + bd[2];
+        r.cov[0] = quant_eval<GI2D_QUANT_LOG>(r.covx[0], v.lscale, v.lbeta, 0.f, Q.qmax_cov);
+        r.cov[1] = quant_eval<GI2D_QUANT_LSQ>(r.covx[1], v.cs, v.cb, 0.f, Q.qmax_cov);
+        r.cov[2] = quant_eval<GI2D_QUANT_LOG>(r.covx[2], v.lscale, v.lbeta, 0.f, Q.qmax_cov);
+        const float cin[3] = {col.a, col.b, col.c};
+#pragma unroll
+        for (int q = 0; q < 3; ++q) r.col[q] = quant_eval<GI2D_QUANT_LSQ>(cin[q], v.fs[q], v.fb[q], 0.f, Q.qmax_col);
+    }
+    static __device__ __forceinline__ void par(const Row &r, float (&p)[3]) {
+        p[0] = r.cov[0].dequant, p[1] = r.cov[1].dequant, p[2] = r.cov[2].dequant;
+    }
+};
+
+template <>
+struct QuantModel<2> {
+    static constexpr int KIND = kScaleRot, SUMS = 16;
+    struct Vals {
+        float xs[2], xb[2], ss[2], sb[2], rs, rb, fs[3], fb[3];
+    };
+    struct Row {
+        QuantEval xy[2], sc[2], rot, col[3];
+        float sig;  // sigmoid(_rotation)
+    };
+    static __device__ __forceinline__ Vals load(const QuantTrain &Q) {
+        Vals v;
+        const float4 *q4 = reinterpret_cast<const float4 *>(Q.qparams);  // 64-byte aligned by contract
+        const float4 a = q4[0], b = q4[1], c = q4[2], d = q4[3];
+        v.xs[0] = a.x, v.xs[1] = a.y, v.xb[0] = a.z, v.xb[1] = a.w;
+        v.ss[0] = b.x, v.ss[1] = b.y, v.sb[0] = b.z, v.sb[1] = b.w;
+        v.rs = c.x, v.rb = c.y, v.fs[0] = c.z, v.fs[1] = c.w;
+        v.fs[2] = d.x, v.fb[0] = d.y, v.fb[1] = d.z, v.fb[2] = d.w;
+        return v;
+    }
+    // (P and g: the covariance model's bound; nothing here)
+    static __device__ __forceinline__ void quantise(const TrainParams &, const QuantTrain &Q, const Vals &v, int,
+                                                    float2 xy, Row3 raw, Row3 col, Row &r) {
+#pragma clang fp contract(off)
+        r.xy[0] = quant_eval<GI2D_QUANT_LSQ>(xy.x, v.xs[0], v.xb[0], 0.f, Q.qmax_xy);
+        r.xy[1] = quant_eval<GI2D_QUANT_LSQ>(xy.y, v.xs[1], v.xb[1], 0.f, Q.qmax_xy);
+        r.sc[0] = quant_eval<GI2D_QUANT_LSQ>(raw.a, v.ss[0], v.sb[0], 0.f, Q.qmax_cov);
+        r.sc[1] = quant_eval<GI2D_QUANT_LSQ>(raw.b, v.ss[1], v.sb[1], 0.f, Q.qmax_cov);
+        r.sig = 1.f / (1.f + expf(-raw.c));                                   // get_rotation: torch.sigmoid(_rotation)
+        r.rot = quant_eval<GI2D_QUANT_LSQ>(r.sig * 2.f * 3.14159265358979323846f, v.rs, v.rb, Q.qmin_rot, Q.qmax_rot);
+        const float cin[3] = {col.a, col.b, col.c};
+#pragma unroll
+        for (int q = 0; q < 3; ++q) r.col[q] = quant_eval<GI2D_QUANT_LSQ>(cin[q], v.fs[q], v.fb[q], 0.f, Q.qmax_col);
+    }
+    static __device__ __forceinline__ void par(const Row &r, float (&p)[3]) {
+        p[0] = r.sc[0].dequant, p[1] = r.sc[1].dequant, p[2] = r.rot.dequant;
+    }
+};
 
 // The kernels of a quantisation-aware iteration as functions of (workgroup index within the image, the image's argument
 // blocks): the single-image kernels pass blockIdx.x and their kernel arguments, the batched ones their image's entry of
 // the batch table (gi2d_batch.h).
 // store_proj: as train_reduce_update_body's -- the call's last projection (and every render) stores xys / num_tiles_hit
+template <int MODEL>
 __device__ __forceinline__ void project_fill_quant_body(int block, const UpdateArgs &u, const QuantTrain &Q,
                                                         bool store_proj) {
+    using M = QuantModel<MODEL>;
 #ifdef GI2D_KNOCK_CALL_STORES
     store_proj = false;
 #endif
@@ -664,15 +736,15 @@ __device__ __forceinline__ void project_fill_quant_body(int block, const UpdateA
     if (g >= n) return;
     const PrevBox old_box = prev_box[g];  // with the other inputs, ahead of the stores
     const float opac = P.opacity[g];
-    const QuantVals v = load_quant(Q);
-    QuantRow r;
-    quantise_row(P, Q, v, g, r);
+    const typename M::Vals v = M::load(Q);
+    typename M::Row r;
+    M::quantise(P, Q, v, g, load_row2(P.xyz, g), load_row3(P.chol, g), load_row3(P.feat, g), r);
     const float2 mean = make_float2(r.xy[0].dequant, r.xy[1].dequant);
-    const float par[3] = {r.cov[0].dequant, r.cov[1].dequant, r.cov[2].dequant};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) Q.qfeat[3 * g + q] = r.col[q].dequant;
-    const ProjOut o =
-        project_one<kCovariance>(0, clip_coe, &mean, par, nullptr, img_w, img_h, tiles_x, tiles_y, radius_clip);
+    float par[3];
+    M::par(r, par);
+    store_row3(Q.qfeat, g, r.col[0].dequant, r.col[1].dequant, r.col[2].dequant);
+    const ProjOut o = project_one<M::KIND>(0, clip_coe, &mean, par, rot_of<M::KIND>(par), img_w, img_h, tiles_x, tiles_y,
+                                           radius_clip);
     if (store_proj) xys[g] = o.xy;
     radii[g] = o.radius;
     conics[3 * g] = o.k0;
@@ -714,152 +786,214 @@ __device__ __forceinline__ void wave_range_reduce(float &mn, float &cmn, float &
 // wave's first lane.  Rows per wave, not per workgroup, so that the closing kernel's sums do not depend on the workgroup
 // size a launch happens to use -- single-image launches pick 64 or 256 lanes by population, a batch by its total.
 __device__ __forceinline__ int quant_wave_row(int block) { return block * ((int)blockDim.x >> 6) + ((int)threadIdx.x >> 6); }
-__device__ __forceinline__ void wave_partial_row(float (&sums)[14], float mn, float cmn, float mx, float cmx,
-                                                 float *row) {
+// Row layout: the SUMS sums, then (14 sums: the covariance model, the only one that passes them) the range words
+// min, #min, max, #max and two zeros -- 20 or 16 words of the row's GI2D_QT_ROW, whole float4s.
+template <int SUMS>
+constexpr int quant_row_words() {
+    static_assert(SUMS == 14 || SUMS == 16, "a partial row holds the covariance or the rotation-scale model's sums");
+    return SUMS == 14 ? 20 : 16;
+}
+template <int SUMS>
+__device__ __forceinline__ void wave_partial_row(const float (&sums)[SUMS], float *row, float mn = INFINITY,
+                                                 float cmn = 0.f, float mx = -INFINITY, float cmx = 0.f) {
+    constexpr int WORDS = quant_row_words<SUMS>();
+    float w[WORDS];
 #pragma unroll
-    for (int k = 0; k < 14; ++k) sums[k] = wave_sum(sums[k]);
-    wave_range_reduce(mn, cmn, mx, cmx);
+    for (int k = 0; k < SUMS; ++k) w[k] = wave_sum(sums[k]);
+    if constexpr (SUMS == 14) {
+        wave_range_reduce(mn, cmn, mx, cmx);
+        w[14] = mn, w[15] = cmn, w[16] = mx, w[17] = cmx, w[18] = 0.f, w[19] = 0.f;
+    }
     if ((threadIdx.x & 63) == 0) {
         float4 *r4 = reinterpret_cast<float4 *>(row);
-        r4[0] = make_float4(sums[0], sums[1], sums[2], sums[3]);
-        r4[1] = make_float4(sums[4], sums[5], sums[6], sums[7]);
-        r4[2] = make_float4(sums[8], sums[9], sums[10], sums[11]);
-        r4[3] = make_float4(sums[12], sums[13], mn, cmn);
-        r4[4] = make_float4(mx, cmx, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < WORDS / 4; ++k) r4[k] = make_float4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
     }
 }
 
-// Closes the reductions of an iteration (RANGE_ONLY: just the log range, start of a call); one workgroup of any size
-// that is a multiple of 64 up to 256.
-template <bool RANGE_ONLY>
-__device__ __forceinline__ void quant_finish(int blocks, const TrainParams &P, const QuantTrain &Q,
-                                             const AdamStep &a_chol, const AdamStep &a_qxy, const AdamStep &a_qcov,
-                                             const AdamStep &a_qcol, float *__restrict__ dbg_grads,
-                                             const BestSnap &best) {
+// ---- the closing kernel: one workgroup of kQuantCloseLanes lanes per image (a constant, not blockDim.x: read inside the
+// row loop the workgroup size becomes a vector load in front of the pass)
+constexpr int kQuantCloseLanes = 256;
+// The whole-array sums.  One pass over the partial rows, whole rows per lane (every 16-byte load of a row in flight),
+// sums in double; then across the lanes through LDS in two 16-way steps (fourteen 6-step double shuffle chains cost
+// 4 us here).  The order is fixed: a lane adds its rows in ascending order, 16 lanes are added in ascending order, the
+// 16-lane groups in ascending order.  tot (LDS) holds the totals when this returns; `tail(f)` sees every row's words,
+// for what lies behind its sums.
+template <int SUMS, class Tail>
+__device__ __forceinline__ void quant_close_sums(int rows, const float *partial, double (&tot)[SUMS], Tail tail) {
 #pragma clang fp contract(off)
-    __shared__ double lane_acc[RANGE_ONLY ? 1 : 256][15];  // 15: odd stride in 8-byte words
-    __shared__ double dred[16][16];
-    __shared__ double tot[14];
-    __shared__ float rred[4][4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, waves = (int)blockDim.x >> 6;
-    float mn = INFINITY, cmn = 0.f, mx = -INFINITY, cmx = 0.f;
-    // Everything that does not depend on the sums is fetched first, so the dependent load chains (parking list ->
-    // entry -> its parameter / moments / bound; quantiser values and their moments) overlap the partial-row pass.
-    int parked = 0, idx = 0, pg = 0, pq = 0;
-    float vt0 = 0.f, p_chol = 0.f, p_m = 0.f, p_v = 0.f, p_bd = 0.f;
-    float q_p = 0.f, q_m = 0.f, q_v = 0.f, lbeta = 0.f, lmax = 0.f, n_min = 0.f, n_max = 0.f;
-    bool snap = false;
-    if (!RANGE_ONLY) {
-        // the first round of parked entries is read before the count is known (slots past the count hold stale
-        // data that is never used), so count, entries, quantiser values and partial rows are ONE round of loads
-        if ((int)threadIdx.x < Q.defer_cap) {
-            const float4 *e = reinterpret_cast<const float4 *>(Q.defer + 8 + 8 * threadIdx.x);
-            const float4 e0 = e[0], e1 = e[1];
-            idx = __float_as_int(e0.x), vt0 = e0.y, p_chol = e0.z, p_m = e0.w, p_v = e1.x, p_bd = e1.y;
-        }
-        parked = min(Q.defer[0], Q.defer_cap);
-        if (threadIdx.x < 12) q_p = Q.qparams[threadIdx.x], q_m = Q.qm[threadIdx.x], q_v = Q.qv[threadIdx.x];
-        lbeta = Q.range[0], lmax = Q.range[1], n_min = Q.range[2], n_max = Q.range[3];
-        snap = best.sse != nullptr && best.info[1] == best.step;
-    }
-    // one pass over the partial rows, whole rows per lane (five 16-byte loads in flight), sums in double
-    double acc[14];
+    constexpr int WORDS = quant_row_words<SUMS>();
+    __shared__ double lane_acc[kQuantCloseLanes][SUMS + 1];  // odd stride in 8-byte words
+    __shared__ double dred[kQuantCloseLanes / 16][16];
+    double acc[SUMS];
 #pragma unroll
-    for (int k = 0; k < 14; ++k) acc[k] = 0.0;
-    for (int b = threadIdx.x; b < blocks; b += (int)blockDim.x) {
-        const float4 *row = reinterpret_cast<const float4 *>(Q.partial + (size_t)b * GI2D_QT_ROW);
-        float4 r[5];
+    for (int k = 0; k < SUMS; ++k) acc[k] = 0.0;
+    for (int b = threadIdx.x; b < rows; b += kQuantCloseLanes) {
+        const float4 *row = reinterpret_cast<const float4 *>(partial + (size_t)b * GI2D_QT_ROW);
+        float4 r[WORDS / 4];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) r[k] = row[k];
+        for (int k = 0; k < WORDS / 4; ++k) r[k] = row[k];
         const float *f = reinterpret_cast<const float *>(r);
-        if (!RANGE_ONLY) {
 #pragma unroll
-            for (int k = 0; k < 14; ++k) acc[k] += (double)f[k];
-        }
-        range_min_combine(mn, cmn, f[14], f[15]);
-        range_max_combine(mx, cmx, f[16], f[17]);
+        for (int k = 0; k < SUMS; ++k) acc[k] += (double)f[k];
+        tail(f);
     }
-    if (!RANGE_ONLY) {
-        // cross-lane sums through LDS in two 16-way steps (fourteen 6-step double shuffle chains cost 4 us here)
 #pragma unroll
-        for (int k = 0; k < 14; ++k) lane_acc[threadIdx.x][k] = acc[k];
-        __syncthreads();
-        const int k = threadIdx.x & 15, j = threadIdx.x >> 4, nj = (int)blockDim.x >> 4;
-        if (k < 14) {
-            double part = 0.0;
+    for (int k = 0; k < SUMS; ++k) lane_acc[threadIdx.x][k] = acc[k];
+    __syncthreads();
+    const int k = threadIdx.x & 15, j = threadIdx.x >> 4;
+    if (k < SUMS) {
+        double part = 0.0;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) part += lane_acc[j * 16 + i][k];
-            dred[j][k] = part;
-        }
-        __syncthreads();
-        if (threadIdx.x < 14) {
-            double t = dred[0][threadIdx.x];
-            for (int w = 1; w < nj; ++w) t += dred[w][threadIdx.x];
-            tot[threadIdx.x] = t;
-        }
-        __syncthreads();
-        // Adam on the twelve quantiser values: qparams = xs[2] xb[2] cs cb fs[3] fb[3]; tot = (s,b) pairs per channel
-        if (threadIdx.x < 12) {
-            const int k = threadIdx.x;
-            int ch, isb;  // channel and which of (scale, beta) this slot is
-            if (k < 4) ch = k & 1, isb = k >> 1;
-            else if (k < 6) ch = 2, isb = k - 4;
-            else ch = 3 + (k - 6) % 3, isb = (k - 6) / 3;
-            const float grad = (float)tot[2 * ch + isb];
-            const AdamStep &a = k < 4 ? a_qxy : (k < 6 ? a_qcov : a_qcol);
-            const float nv = adam(q_p, grad, q_m, q_v, a);
-            Q.qparams[k] = nv;
-            Q.qm[k] = q_m;
-            Q.qv[k] = q_v;
-            if (Q.dbg_q) Q.dbg_q[k] = grad;
-            if (snap && Q.best_q) Q.best_q[k] = nv;
-        }
-        // range gradient: scale = (max - beta)/Q is in the graph, so beta gets -v_scale/Q too and max +v_scale/Q,
-        // spread evenly over the elements that attain them
-        const double qrange = (double)Q.qmax_cov;
-        const float e_min = n_min > 0.f ? (float)((tot[13] - tot[12] / qrange) / (double)n_min) : 0.f;
-        const float e_max = n_max > 0.f ? (float)((tot[12] / qrange) / (double)n_max) : 0.f;
-        if (threadIdx.x == 0 && Q.dbg_q) {
-            Q.dbg_q[12] = (float)tot[12];
-            Q.dbg_q[13] = (float)tot[13];
-            Q.dbg_q[14] = e_min;
-            Q.dbg_q[15] = e_max;
-        }
-        for (int e = threadIdx.x; e < parked; e += (int)blockDim.x) {
-            if (e >= (int)blockDim.x) {  // beyond the prefetched first round (rare: more parked entries than lanes)
-                const float4 *en = reinterpret_cast<const float4 *>(Q.defer + 8 + 8 * e);
-                const float4 e0 = en[0], e1 = en[1];
-                idx = __float_as_int(e0.x), vt0 = e0.y, p_chol = e0.z, p_m = e0.w, p_v = e1.x, p_bd = e1.y;
-            }
-            pg = idx / 3, pq = idx - 3 * pg;
-            const float x = p_chol + p_bd, t = quant_log_of(x);
-            float vt = vt0;
-            if (t == lbeta) vt = vt + e_min;
-            if (t == lmax) vt = vt + e_max;
-            const float gxv = vt * quant_log_chain(x);
-            const float nv = adam(p_chol, gxv, p_m, p_v, a_chol);
-            P.chol[idx] = nv;
-            P.m_chol[idx] = p_m;
-            P.v_chol[idx] = p_v;
-            if (dbg_grads) dbg_grads[8 * (size_t)pg + 2 + pq] = gxv;
-            if (snap) best.chol[idx] = nv;
-            const float t2 = quant_log_of(nv + p_bd);
-            range_min_combine(mn, cmn, t2, 1.f);
-            range_max_combine(mx, cmx, t2, 1.f);
-        }
+        for (int i = 0; i < 16; ++i) part += lane_acc[j * 16 + i][k];
+        dred[j][k] = part;
     }
+    __syncthreads();
+    if (threadIdx.x < SUMS) {
+        double t = dred[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kQuantCloseLanes / 16; ++w) t += dred[w][threadIdx.x];
+        tot[threadIdx.x] = t;
+    }
+    __syncthreads();
+}
+
+// Adam on the learned quantiser values, one lane per slot of qparams.  A slot's gradient is tot[2 * ch + isb]: the sums
+// come as (v_scale, v_beta) pairs per channel, qparams holds each attribute's scales, then its betas.
+struct QuantSlot {
+    int ch, isb, group;  // channel; scale (0) or beta (1); optimizer: 0 positions, 1 covariance / scaling + rotation, 2 colours
+};
+// covariance: xs[2] xb[2] | cs cb | fs[3] fb[3]
+constexpr QuantSlot kQuantSlotsCov[12] = {{0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {1, 1, 0}, {2, 0, 1}, {2, 1, 1},
+                                          {3, 0, 2}, {4, 0, 2}, {5, 0, 2}, {3, 1, 2}, {4, 1, 2}, {5, 1, 2}};
+// rotation-scale: xs[2] xb[2] | ss[2] sb[2] rs rb | fs[3] fb[3]
+constexpr QuantSlot kQuantSlotsRS[16] = {{0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {1, 1, 0}, {2, 0, 1}, {3, 0, 1},
+                                         {2, 1, 1}, {3, 1, 1}, {4, 0, 1}, {4, 1, 1}, {5, 0, 2}, {6, 0, 2},
+                                         {7, 0, 2}, {5, 1, 2}, {6, 1, 2}, {7, 1, 2}};
+// A lane's slot, value and moments: fetched with the kernel's first loads, ahead of the sums they wait for.  (The table
+// is read by a chain of selects on its compile-time entries, not from memory: a load here would be one more round trip
+// in front of the row pass.)
+struct QuantValue {
+    QuantSlot slot;
+    float p, m, v;
+};
+template <int SLOTS>
+__device__ __forceinline__ QuantValue quant_value_load(const QuantSlot (&table)[SLOTS], const QuantTrain &Q) {
+    QuantValue q;
+    q.slot = table[0];
+#pragma unroll
+    for (int k = 1; k < SLOTS; ++k)
+        if ((int)threadIdx.x == k) q.slot = table[k];
+    q.p = q.m = q.v = 0.f;
+    if (threadIdx.x < SLOTS) q.p = Q.qparams[threadIdx.x], q.m = Q.qm[threadIdx.x], q.v = Q.qv[threadIdx.x];
+    return q;
+}
+// (slot: threadIdx.x < the model's slot count; snap: this step's model is the best so far)
+__device__ __forceinline__ void quant_value_step(int slot, QuantValue q, const double *tot, const QuantTrain &Q,
+                                                 const AdamStep &a_qxy, const AdamStep &a_qcov, const AdamStep &a_qcol,
+                                                 bool snap) {
+    const float grad = (float)tot[2 * q.slot.ch + q.slot.isb];
+    const AdamStep &a = q.slot.group == 0 ? a_qxy : (q.slot.group == 1 ? a_qcov : a_qcol);
+    const float nv = adam(q.p, grad, q.m, q.v, a);
+    Q.qparams[slot] = nv;
+    Q.qm[slot] = q.m;
+    Q.qv[slot] = q.v;
+    if (Q.dbg_q) Q.dbg_q[slot] = grad;
+    if (snap && Q.best_q) Q.best_q[slot] = nv;
+}
+
+// The log range (covariance model): every lane's (min, #min, max, #max) -> Q.range, and the parking list is emptied.
+__device__ __forceinline__ void quant_range_close(const QuantTrain &Q, float mn, float cmn, float mx, float cmx) {
+    __shared__ float rred[kQuantCloseLanes / 64][4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     wave_range_reduce(mn, cmn, mx, cmx);
     if (lane == 0) rred[wave][0] = mn, rred[wave][1] = cmn, rred[wave][2] = mx, rred[wave][3] = cmx;
     __syncthreads();
     if (threadIdx.x == 0) {
         float a = rred[0][0], ac = rred[0][1], b = rred[0][2], bc = rred[0][3];
-        for (int w = 1; w < waves; ++w) {
+        for (int w = 1; w < kQuantCloseLanes / 64; ++w) {
             range_min_combine(a, ac, rred[w][0], rred[w][1]);
             range_max_combine(b, bc, rred[w][2], rred[w][3]);
         }
         Q.range[0] = a, Q.range[1] = b, Q.range[2] = ac, Q.range[3] = bc;
         Q.defer[0] = 0;
     }
+}
+// Start of a call: just the log range of the rows quant_range_body left.
+__device__ __forceinline__ void quant_finish_range(int rows, const QuantTrain &Q) {
+    float mn = INFINITY, cmn = 0.f, mx = -INFINITY, cmx = 0.f;
+    for (int b = threadIdx.x; b < rows; b += kQuantCloseLanes) {
+        const float4 *row = reinterpret_cast<const float4 *>(Q.partial + (size_t)b * GI2D_QT_ROW);
+        const float4 lo = row[3], hi = row[4];
+        range_min_combine(mn, cmn, lo.z, lo.w);
+        range_max_combine(mx, cmx, hi.x, hi.y);
+    }
+    quant_range_close(Q, mn, cmn, mx, cmx);
+}
+
+// Covariance model: Adam on the twelve quantiser values, the parked variances (whose gradient needs the sums) and the
+// next iteration's log range.
+__device__ __forceinline__ void quant_finish_cov(int rows, const TrainParams &P, const QuantTrain &Q,
+                                                 const AdamStep &a_chol, const AdamStep &a_qxy, const AdamStep &a_qcov,
+                                                 const AdamStep &a_qcol, float *__restrict__ dbg_grads,
+                                                 const BestSnap &best) {
+#pragma clang fp contract(off)
+    __shared__ double tot[14];
+    float mn = INFINITY, cmn = 0.f, mx = -INFINITY, cmx = 0.f;
+    // Everything that does not depend on the sums is fetched first, so the dependent load chains (parking list ->
+    // entry -> its parameter / moments / bound; quantiser values and their moments) overlap the partial-row pass.
+    // The first round of parked entries is read before the count is known (slots past the count hold stale
+    // data that is never used), so count, entries, quantiser values and partial rows are ONE round of loads.
+    int idx = 0, pg = 0, pq = 0;
+    float vt0 = 0.f, p_chol = 0.f, p_m = 0.f, p_v = 0.f, p_bd = 0.f;
+    if ((int)threadIdx.x < Q.defer_cap) {
+        const float4 *e = reinterpret_cast<const float4 *>(Q.defer + 8 + 8 * threadIdx.x);
+        const float4 e0 = e[0], e1 = e[1];
+        idx = __float_as_int(e0.x), vt0 = e0.y, p_chol = e0.z, p_m = e0.w, p_v = e1.x, p_bd = e1.y;
+    }
+    const int parked = min(Q.defer[0], Q.defer_cap);
+    const QuantValue qv = quant_value_load(kQuantSlotsCov, Q);
+    const float lbeta = Q.range[0], lmax = Q.range[1], n_min = Q.range[2], n_max = Q.range[3];
+    const bool snap = best.sse != nullptr && best.info[1] == best.step;
+    quant_close_sums<14>(rows, Q.partial, tot, [&](const float *f) {
+        range_min_combine(mn, cmn, f[14], f[15]);
+        range_max_combine(mx, cmx, f[16], f[17]);
+    });
+    if (threadIdx.x < 12) quant_value_step(threadIdx.x, qv, tot, Q, a_qxy, a_qcov, a_qcol, snap);
+    // range gradient: scale = (max - beta)/Q is in the graph, so beta gets -v_scale/Q too and max +v_scale/Q,
+    // spread evenly over the elements that attain them
+    const double qrange = (double)Q.qmax_cov;
+    const float e_min = n_min > 0.f ? (float)((tot[13] - tot[12] / qrange) / (double)n_min) : 0.f;
+    const float e_max = n_max > 0.f ? (float)((tot[12] / qrange) / (double)n_max) : 0.f;
+    if (threadIdx.x == 0 && Q.dbg_q) {
+        Q.dbg_q[12] = (float)tot[12];
+        Q.dbg_q[13] = (float)tot[13];
+        Q.dbg_q[14] = e_min;
+        Q.dbg_q[15] = e_max;
+    }
+    for (int e = threadIdx.x; e < parked; e += kQuantCloseLanes) {
+        if (e >= kQuantCloseLanes) {  // beyond the prefetched first round (rare: more parked entries than lanes)
+            const float4 *en = reinterpret_cast<const float4 *>(Q.defer + 8 + 8 * e);
+            const float4 e0 = en[0], e1 = en[1];
+            idx = __float_as_int(e0.x), vt0 = e0.y, p_chol = e0.z, p_m = e0.w, p_v = e1.x, p_bd = e1.y;
+        }
+        pg = idx / 3, pq = idx - 3 * pg;
+        const float x = p_chol + p_bd, t = quant_log_of(x);
+        float vt = vt0;
+        if (t == lbeta) vt = vt + e_min;
+        if (t == lmax) vt = vt + e_max;
+        const float gxv = vt * quant_log_chain(x);
+        const float nv = adam(p_chol, gxv, p_m, p_v, a_chol);
+        P.chol[idx] = nv;
+        P.m_chol[idx] = p_m;
+        P.v_chol[idx] = p_v;
+        if (dbg_grads) dbg_grads[8 * (size_t)pg + 2 + pq] = gxv;
+        if (snap) best.chol[idx] = nv;
+        const float t2 = quant_log_of(nv + p_bd);
+        range_min_combine(mn, cmn, t2, 1.f);
+        range_max_combine(mx, cmx, t2, 1.f);
+    }
+    quant_range_close(Q, mn, cmn, mx, cmx);
 }
 
 // Range of the variance channels of the current parameters (start of a call, after the host touched them)
@@ -880,53 +1014,92 @@ __device__ __forceinline__ void quant_range_body(int block, const UpdateArgs &u,
             range_max_combine(mx, cmx, t, 1.f);
         }
     }
-    wave_partial_row(sums, mn, cmn, mx, cmx, Q.partial + (size_t)quant_wave_row(block) * GI2D_QT_ROW);
+    wave_partial_row(sums, Q.partial + (size_t)quant_wave_row(block) * GI2D_QT_ROW, mn, cmn, mx, cmx);
 }
 
+// ---- the update kernel
+// What both models' bodies do before anything model-specific: the best-model decision and this lane's gradient sums.
+struct QuantOpen {
+    int g, n;        // this lane's gaussian, the live population
+    float acc[11];   // its gradient sums (reduce_one); the bodies read [0, 8), and what nobody reads is not loaded
+    bool snapshot;   // this step's render is the best so far
+    BestSnap best;
+};
 template <bool ALONE>
-__device__ __forceinline__ void reduce_update_quant_body(int block, const UpdateArgs &u, const QuantTrain &Q,
-                                                         const AdamStep &a_xyz, const AdamStep &a_chol,
-                                                         const AdamStep &a_feat, int step) {
-#pragma clang fp contract(off)
-    const TrainParams &P = u.P;
-    const int n = live_n(P, u.n);
-    const float img_w = u.img_w, img_h = u.img_h;
-    const int tiles_x = u.tiles_x, tiles_y = u.tiles_y;
-    const int32_t *radii = u.radii;
-    const float *conics = u.conics;
-    const PrevBox *prev_box = u.next.prev_box;
-    const float4 *partial_g = u.partial_g, *partial_big = u.partial_big;
-    float *dbg_grads = u.dbg_grads;
-    BestSnap best = u.best;
-    best.step = step;
-    const int g = block * blockDim.x + threadIdx.x;
-    int32_t *status = u.next.status;
+__device__ __forceinline__ QuantOpen quant_update_open(int block, const UpdateArgs &u, int step) {
+    QuantOpen o;
+    o.n = live_n(u.P, u.n);
+    o.best = u.best;
+    o.best.step = step;
+    const int g = o.g = block * blockDim.x + threadIdx.x;
     // (one image alone: its first gradient rows are asked for before the box says how many count -- reduce_one)
     constexpr int AHEAD = ALONE ? WideRows::AHEAD : 0;
-    const RowsAhead<AHEAD> ahead = rows_ahead<AHEAD>(partial_g, g < u.n ? g : 0);
-    const PrevBox box_ld = g < u.n ? prev_box[g] : no_box();
-    const bool snapshot = best_decision(best, best_sse_loads(best), n, g);
-    float acc[11];
-    const PrevBox pbox = g < n ? box_ld : no_box();
-    reduce_one<AHEAD>(g, make_int2(pbox.x, pbox.y), pbox.z, tiles_x * tiles_y * GI2D_TILE_LIST_CAP, partial_g, partial_big,
-                      acc, nullptr, &ahead);
-    float sums[14];
+    const RowsAhead<AHEAD> ahead = rows_ahead<AHEAD>(u.partial_g, g < u.n ? g : 0);
+    const PrevBox box_ld = g < u.n ? u.next.prev_box[g] : no_box();
+    o.snapshot = best_decision(o.best, best_sse_loads(o.best), o.n, g);
+    const PrevBox pbox = g < o.n ? box_ld : no_box();
+    reduce_one<AHEAD>(g, make_int2(pbox.x, pbox.y), pbox.z, u.tiles_x * u.tiles_y * GI2D_TILE_LIST_CAP, u.partial_g,
+                      u.partial_big, o.acc, nullptr, &ahead);
+    return o;
+}
+// Projection backward of gaussian g from its dequantised projection inputs `par` and gradient sums `acc`.
+template <int MODEL>
+__device__ __forceinline__ ProjGrad quant_project_grad(const UpdateArgs &u, int g, const float (&par)[3],
+                                                       const float (&acc)[11]) {
+    constexpr int KIND = QuantModel<MODEL>::KIND;
+    ProjGrad r;
+    r.g11 = r.g12 = r.g22 = r.o0 = r.o1 = r.o2 = 0.f;
+    r.v_mean = make_float2(0.f, 0.f);
+    if (u.radii[g] > 0) {
+        const float conic[3] = {u.conics[3 * g], u.conics[3 * g + 1], u.conics[3 * g + 2]};
+        const float vc[3] = {acc[2], acc[3], acc[4]};
+        r = project_bwd_one<KIND>(0, par, rot_of<KIND>(par), u.img_w, u.img_h, conic, make_float2(acc[0], acc[1]), vc);
+    }
+    return r;
+}
+// [N,8]: gradients w.r.t. the raw parameters (tests)
+__device__ __forceinline__ void quant_dbg_row(float *dbg_grads, int g, float gx, float gy, const float (&gp)[3],
+                                              const float (&gf)[3]) {
+    if (dbg_grads) {
+        float *d = dbg_grads + 8 * (size_t)g;
+        d[0] = gx, d[1] = gy, d[2] = gp[0], d[3] = gp[1], d[4] = gp[2], d[5] = gf[0], d[6] = gf[1], d[7] = gf[2];
+    }
+}
+// The best-model snapshot of gaussian g: the rows the update left, from registers, not read back through memory.
+__device__ __forceinline__ void quant_snapshot_store(const BestSnap &best, const TrainParams &P, int g, float2 xy,
+                                                     const float (&chol)[3], const float (&feat)[3]) {
+    best.xyz[2 * g] = xy.x;
+    best.xyz[2 * g + 1] = xy.y;
 #pragma unroll
-    for (int k = 0; k < 14; ++k) sums[k] = 0.f;
+    for (int q = 0; q < 3; ++q) {
+        best.chol[3 * g + q] = chol[q];
+        best.feat[3 * g + q] = feat[q];
+        if (best.bound) best.bound[3 * g + q] = P.bound[(size_t)P.bound_stride * g + q];
+    }
+}
+
+// Covariance model (the overloads are picked by the model's description).
+template <bool ALONE>
+__device__ __forceinline__ void reduce_update_quant_body(QuantModel<1>, int block, const UpdateArgs &u,
+                                                         const QuantTrain &Q, const AdamStep &a_xyz,
+                                                         const AdamStep &a_chol, const AdamStep &a_feat, int step) {
+#pragma clang fp contract(off)
+    using M = QuantModel<1>;
+    const TrainParams &P = u.P;
+    const QuantOpen o = quant_update_open<ALONE>(block, u, step);
+    const int g = o.g;
+    const float(&acc)[11] = o.acc;
+    float sums[M::SUMS];
+#pragma unroll
+    for (int k = 0; k < M::SUMS; ++k) sums[k] = 0.f;
     float mn = INFINITY, cmn = 0.f, mx = -INFINITY, cmx = 0.f;
-    if (g < n) {
-        const QuantVals v = load_quant(Q);
-        QuantRow qr;
-        quantise_row(P, Q, v, g, qr);
-        const float par[3] = {qr.cov[0].dequant, qr.cov[1].dequant, qr.cov[2].dequant};
-        ProjGrad r;
-        r.g11 = r.g12 = r.g22 = r.o0 = r.o1 = r.o2 = 0.f;
-        r.v_mean = make_float2(0.f, 0.f);
-        if (radii[g] > 0) {
-            const float conic[3] = {conics[3 * g], conics[3 * g + 1], conics[3 * g + 2]};
-            const float vc[3] = {acc[2], acc[3], acc[4]};
-            r = project_bwd_one<kCovariance>(0, par, nullptr, img_w, img_h, conic, make_float2(acc[0], acc[1]), vc);
-        }
+    if (g < o.n) {
+        const M::Vals v = M::load(Q);
+        M::Row qr;
+        M::quantise(P, Q, v, g, load_row2(P.xyz, g), load_row3(P.chol, g), load_row3(P.feat, g), qr);
+        float par[3];
+        M::par(qr, par);
+        const ProjGrad r = quant_project_grad<1>(u, g, par, acc);
         // quantiser backward: sums[0..11] = (v_scale, v_beta) of xy.x, xy.y, cov, colour r, g, b; sums[12,13] = log
         const float gx = quant_grad<GI2D_QUANT_LSQ>(qr.xy[0], r.v_mean.x, v.xs[0], sums[0], sums[1]);
         const float gy = quant_grad<GI2D_QUANT_LSQ>(qr.xy[1], r.v_mean.y, v.xs[1], sums[2], sums[3]);
@@ -951,188 +1124,61 @@ __device__ __forceinline__ void reduce_update_quant_body(int block, const Update
                     e[0] = make_float4(__int_as_float(3 * g + q), vt, P.chol[3 * g + q], P.m_chol[3 * g + q]);
                     e[1] = make_float4(P.v_chol[3 * g + q], P.bound[(size_t)P.bound_stride * g + q], 0.f, 0.f);
                 } else {
-                    atomicOr(&status[2], 2);
+                    atomicOr(&u.next.status[2], 2);
                 }
             }
         }
-        if (dbg_grads) {
-            float *d = dbg_grads + 8 * (size_t)g;
-            d[0] = gx, d[1] = gy, d[2] = gp[0], d[3] = gp[1], d[4] = gp[2], d[5] = gf[0], d[6] = gf[1], d[7] = gf[2];
-        }
-        // Adam on whole rows; a parked variance keeps its value and moments (the finish kernel updates it)
+        quant_dbg_row(u.dbg_grads, g, gx, gy, gp, gf);
+        // Adam on whole rows (loaded here, behind the quantiser backward); a parked variance keeps its value and moments
+        // (the finish kernel updates it)
         const float *bd = P.bound + (size_t)P.bound_stride * g;
-        {
-            const float2 x = load_row2(P.xyz, g);
-            float2 m_xy = load_row2(P.m_xyz, g), v_xy = load_row2(P.v_xyz, g);
-            const Row3 c = load_row3(P.chol, g), f = load_row3(P.feat, g);
-            Row3 mc = load_row3(P.m_chol, g), vc = load_row3(P.v_chol, g), mf = load_row3(P.m_feat, g),
-                 vf = load_row3(P.v_feat, g);
-            const float nx = adam(x.x, gx, m_xy.x, v_xy.x, a_xyz), ny = adam(x.y, gy, m_xy.y, v_xy.y, a_xyz);
-            float cn[3] = {c.a, c.b, c.c}, cm[3] = {mc.a, mc.b, mc.c}, cv[3] = {vc.a, vc.b, vc.c};
+        AdamRows w = adam_load_rows(P, g);
+        w.x.x = adam(w.x.x, gx, w.mx.x, w.vx.x, a_xyz), w.x.y = adam(w.x.y, gy, w.mx.y, w.vx.y, a_xyz);
+        float cn[3] = {w.c.a, w.c.b, w.c.c}, cm[3] = {w.mc.a, w.mc.b, w.mc.c}, cv[3] = {w.vc.a, w.vc.b, w.vc.c};
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                if (parked[q]) continue;
-                cn[q] = adam(cn[q], gp[q], cm[q], cv[q], a_chol);
-                if (q != 1) {  // this variance's place in the NEXT iteration's log range
-                    const float t = quant_log_of(cn[q] + bd[q]);
-                    range_min_combine(mn, cmn, t, 1.f);
-                    range_max_combine(mx, cmx, t, 1.f);
-                }
-            }
-            const float f0 = adam(f.a, gf[0], mf.a, vf.a, a_feat), f1 = adam(f.b, gf[1], mf.b, vf.b, a_feat),
-                        f2 = adam(f.c, gf[2], mf.c, vf.c, a_feat);
-            store_row2(P.xyz, g, nx, ny);
-            store_row2(P.m_xyz, g, m_xy.x, m_xy.y);
-            store_row2(P.v_xyz, g, v_xy.x, v_xy.y);
-            store_row3(P.chol, g, cn[0], cn[1], cn[2]);
-            store_row3(P.m_chol, g, cm[0], cm[1], cm[2]);
-            store_row3(P.v_chol, g, cv[0], cv[1], cv[2]);
-            store_row3(P.feat, g, f0, f1, f2);
-            store_row3(P.m_feat, g, mf.a, mf.b, mf.c);
-            store_row3(P.v_feat, g, vf.a, vf.b, vf.c);
-            if (snapshot) {  // from registers, not read back through memory
-                best.xyz[2 * g] = nx;
-                best.xyz[2 * g + 1] = ny;
-                const float nf[3] = {f0, f1, f2};
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    best.chol[3 * g + q] = cn[q];  // parked entries are patched by the finish kernel
-                    best.feat[3 * g + q] = nf[q];
-                    if (best.bound) best.bound[3 * g + q] = bd[q];
-                }
+        for (int q = 0; q < 3; ++q) {
+            if (parked[q]) continue;
+            cn[q] = adam(cn[q], gp[q], cm[q], cv[q], a_chol);
+            if (q != 1) {  // this variance's place in the NEXT iteration's log range
+                const float t = quant_log_of(cn[q] + bd[q]);
+                range_min_combine(mn, cmn, t, 1.f);
+                range_max_combine(mx, cmx, t, 1.f);
             }
         }
+        w.c = Row3{cn[0], cn[1], cn[2]}, w.mc = Row3{cm[0], cm[1], cm[2]}, w.vc = Row3{cv[0], cv[1], cv[2]};
+        w.f.a = adam(w.f.a, gf[0], w.mf.a, w.vf.a, a_feat), w.f.b = adam(w.f.b, gf[1], w.mf.b, w.vf.b, a_feat),
+        w.f.c = adam(w.f.c, gf[2], w.mf.c, w.vf.c, a_feat);
+        adam_store_rows(P, g, w);
+        // (parked entries of the snapshot are patched by the finish kernel)
+        if (o.snapshot) quant_snapshot_store(o.best, P, g, w.x, cn, {w.f.a, w.f.b, w.f.c});
     }
-    wave_partial_row(sums, mn, cmn, mx, cmx, Q.partial + (size_t)quant_wave_row(block) * GI2D_QT_ROW);
+    wave_partial_row(sums, Q.partial + (size_t)quant_wave_row(block) * GI2D_QT_ROW, mn, cmn, mx, cmx);
 }
 
-
-// =====================================================================================================================
-// Quantisation-aware iteration of the rotation-scale model (BASELINE config 5): GaussianImage_RS.forward_quantize /
-// train_iter_quantize (models/gaussianimage_rs.py:443-485) with the quantiser set of training_setup (:131-163): four
-// LSQ+ UniformQuantizers -- positions 12 bit unsigned (2 channels), the RAW `_scaling` 6 bit unsigned (2 channels; as
-// written, forward_quantize feeds the dequantised raw scaling to the projection without |. + bound|, :451-453),
-// rotation = sigmoid(_rotation) * 2 pi 6 bit SIGNED (1 channel), colours 6 bit unsigned (3 channels).  Every range is a
-// learned (scale, beta) pair, so there is no data-dependent range and nothing to park: the update kernel leaves 16
-// partial sums per workgroup and a one-workgroup kernel closes them with Adam on the 16 quantiser values
-//   qparams = xy scale[2], xy beta[2], scaling scale[2], scaling beta[2], rotation scale, beta, colour scale[3], beta[3]
-// (optimizer groups as the model file creates them: positions eps 1e-8; scaling + rotation together, eps 1e-15;
-// colours eps 1e-15 -- stepped every iteration like GaussianImage_Covariance.optimizer_step does, :235-247 there).
-#define GI2D_QT_RS_SUMS 16
-struct QuantValsRS {
-    float xs[2], xb[2], ss[2], sb[2], rs, rb, fs[3], fb[3];
-};
-__device__ __forceinline__ QuantValsRS load_quant_rs(const QuantTrain &Q) {
-    QuantValsRS v;
-    const float4 *q4 = reinterpret_cast<const float4 *>(Q.qparams);  // 64-byte aligned by contract
-    const float4 a = q4[0], b = q4[1], c = q4[2], d = q4[3];
-    v.xs[0] = a.x, v.xs[1] = a.y, v.xb[0] = a.z, v.xb[1] = a.w;
-    v.ss[0] = b.x, v.ss[1] = b.y, v.sb[0] = b.z, v.sb[1] = b.w;
-    v.rs = c.x, v.rb = c.y, v.fs[0] = c.z, v.fs[1] = c.w;
-    v.fs[2] = d.x, v.fb[0] = d.y, v.fb[1] = d.z, v.fb[2] = d.w;
-    return v;
-}
-struct QuantRowRS {
-    QuantEval xy[2], sc[2], rot, col[3];
-    float sig;  // sigmoid(_rotation)
-};
-__device__ __forceinline__ void quantise_row_rs(const QuantTrain &Q, const QuantValsRS &v, float2 xy, Row3 raw,
-                                                Row3 col, QuantRowRS &r) {
-#pragma clang fp contract(off)
-    r.xy[0] = quant_eval<GI2D_QUANT_LSQ>(xy.x, v.xs[0], v.xb[0], 0.f, Q.qmax_xy);
-    r.xy[1] = quant_eval<GI2D_QUANT_LSQ>(xy.y, v.xs[1], v.xb[1], 0.f, Q.qmax_xy);
-    r.sc[0] = quant_eval<GI2D_QUANT_LSQ>(raw.a, v.ss[0], v.sb[0], 0.f, Q.qmax_cov);
-    r.sc[1] = quant_eval<GI2D_QUANT_LSQ>(raw.b, v.ss[1], v.sb[1], 0.f, Q.qmax_cov);
-    r.sig = 1.f / (1.f + expf(-raw.c));                                   // get_rotation: torch.sigmoid(_rotation)
-    r.rot = quant_eval<GI2D_QUANT_LSQ>(r.sig * 2.f * 3.14159265358979323846f, v.rs, v.rb, Q.qmin_rot, Q.qmax_rot);
-    const float cin[3] = {col.a, col.b, col.c};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) r.col[q] = quant_eval<GI2D_QUANT_LSQ>(cin[q], v.fs[q], v.fb[q], 0.f, Q.qmax_col);
-}
-
-__device__ __forceinline__ void project_fill_quant_rs_body(int block, const UpdateArgs &u, const QuantTrain &Q,
-                                                           bool store_proj) {
-#ifdef GI2D_KNOCK_CALL_STORES
-    store_proj = false;
-#endif
-    const TrainParams &P = u.P;
-    const int n = live_n(P, u.n);
-    const float clip_coe = u.next.clip_coe, img_w = u.img_w, img_h = u.img_h, radius_clip = u.radius_clip;
-    const int tiles_x = u.tiles_x, tiles_y = u.tiles_y;
-    float2 *xys = u.xys;
-    int32_t *radii = u.radii, *num_tiles_hit = u.next.num_tiles_hit, *lists = u.next.lists, *status = u.next.status;
-    float *conics = u.conics;
-    PrevBox *prev_box = u.next.prev_box;
-    const RecSets &rs = u.next.recs;
-    const int g = block * blockDim.x + threadIdx.x;
-    begin_binning(g, status);
-    const BinRecs recs = recs_for_binning(rs, g == 0);
-    if (g >= n) return;
-    const PrevBox old_box = prev_box[g];  // with the other inputs, ahead of the stores
-    const float opac = P.opacity[g];
-    const QuantValsRS v = load_quant_rs(Q);
-    QuantRowRS r;
-    quantise_row_rs(Q, v, load_row2(P.xyz, g), load_row3(P.chol, g), load_row3(P.feat, g), r);
-    const float2 mean = make_float2(r.xy[0].dequant, r.xy[1].dequant);
-    const float par[3] = {r.sc[0].dequant, r.sc[1].dequant, r.rot.dequant};
-    store_row3(Q.qfeat, g, r.col[0].dequant, r.col[1].dequant, r.col[2].dequant);
-    const ProjOut o =
-        project_one<kScaleRot>(0, clip_coe, &mean, par, &par[2], img_w, img_h, tiles_x, tiles_y, radius_clip);
-    if (store_proj) xys[g] = o.xy;
-    radii[g] = o.radius;
-    conics[3 * g] = o.k0;
-    conics[3 * g + 1] = o.k1;
-    conics[3 * g + 2] = o.k2;
-    if (store_proj) num_tiles_hit[g] = o.tiles_hit;
-    bin_projected(g, o, opac, r.col[0].dequant, r.col[1].dequant, r.col[2].dequant, tiles_x, tiles_y, radius_clip,
-                  old_box, prev_box, lists, recs);
-}
-
+// Rotation-scale model: every quantiser is an LSQ one with a learned range, so the rows are updated here, whole.
 template <bool ALONE>
-__device__ __forceinline__ void reduce_update_quant_rs_body(int block, const UpdateArgs &u, const QuantTrain &Q,
-                                                            const AdamStep &a_xyz, const AdamStep &a_chol,
-                                                            const AdamStep &a_feat, int step) {
+__device__ __forceinline__ void reduce_update_quant_body(QuantModel<2>, int block, const UpdateArgs &u,
+                                                         const QuantTrain &Q, const AdamStep &a_xyz,
+                                                         const AdamStep &a_chol, const AdamStep &a_feat, int step) {
 #pragma clang fp contract(off)
+    using M = QuantModel<2>;
     const TrainParams &P = u.P;
-    const int n = live_n(P, u.n);
-    const float img_w = u.img_w, img_h = u.img_h;
-    const int tiles_x = u.tiles_x, tiles_y = u.tiles_y;
-    const int32_t *radii = u.radii;
-    const float *conics = u.conics;
-    const PrevBox *prev_box = u.next.prev_box;
-    const float4 *partial_g = u.partial_g, *partial_big = u.partial_big;
-    float *dbg_grads = u.dbg_grads;
-    BestSnap best = u.best;
-    best.step = step;
+    // first round of loads: for every row below the host's bound (the live count is itself one of these loads)
     const int g = block * blockDim.x + threadIdx.x;
-    // first round of loads: for every row below the host's bound (the live count is itself one of these loads); one image
-    // alone also asks for its first gradient rows before the box says how many count (reduce_one)
     AdamRows rows;
     if (g < u.n) rows = adam_load_rows(P, g);
-    constexpr int AHEAD = ALONE ? WideRows::AHEAD : 0;
-    const RowsAhead<AHEAD> ahead = rows_ahead<AHEAD>(partial_g, g < u.n ? g : 0);
-    const PrevBox box_ld = g < u.n ? prev_box[g] : no_box();
-    const bool snapshot = best_decision(best, best_sse_loads(best), n, g);
-    float acc[11];
-    const PrevBox pbox = g < n ? box_ld : no_box();
-    reduce_one<AHEAD>(g, make_int2(pbox.x, pbox.y), pbox.z, tiles_x * tiles_y * GI2D_TILE_LIST_CAP, partial_g, partial_big,
-                      acc, nullptr, &ahead);
-    float sums[GI2D_QT_RS_SUMS];
+    const QuantOpen o = quant_update_open<ALONE>(block, u, step);  // (o.g is g)
+    const float(&acc)[11] = o.acc;
+    float sums[M::SUMS];
 #pragma unroll
-    for (int k = 0; k < GI2D_QT_RS_SUMS; ++k) sums[k] = 0.f;
-    if (g < n) {
-        const QuantValsRS v = load_quant_rs(Q);
-        QuantRowRS qr;
-        quantise_row_rs(Q, v, rows.x, rows.c, rows.f, qr);
-        const float par[3] = {qr.sc[0].dequant, qr.sc[1].dequant, qr.rot.dequant};
-        ProjGrad r;
-        r.g11 = r.g12 = r.g22 = r.o0 = r.o1 = r.o2 = 0.f;
-        r.v_mean = make_float2(0.f, 0.f);
-        if (radii[g] > 0) {
-            const float conic[3] = {conics[3 * g], conics[3 * g + 1], conics[3 * g + 2]};
-            const float vc[3] = {acc[2], acc[3], acc[4]};
-            r = project_bwd_one<kScaleRot>(0, par, &par[2], img_w, img_h, conic, make_float2(acc[0], acc[1]), vc);
-        }
+    for (int k = 0; k < M::SUMS; ++k) sums[k] = 0.f;
+    if (g < o.n) {
+        const M::Vals v = M::load(Q);
+        M::Row qr;
+        M::quantise(P, Q, v, g, rows.x, rows.c, rows.f, qr);
+        float par[3];
+        M::par(qr, par);
+        const ProjGrad r = quant_project_grad<2>(u, g, par, acc);
         // quantiser backward; sums = (v_scale, v_beta) of xy.x, xy.y, scaling.x, scaling.y, rotation, colour r, g, b
         const float gx = quant_grad<GI2D_QUANT_LSQ>(qr.xy[0], r.v_mean.x, v.xs[0], sums[0], sums[1]);
         const float gy = quant_grad<GI2D_QUANT_LSQ>(qr.xy[1], r.v_mean.y, v.xs[1], sums[2], sums[3]);
@@ -1145,123 +1191,55 @@ __device__ __forceinline__ void reduce_update_quant_rs_body(int block, const Upd
 #pragma unroll
         for (int q = 0; q < 3; ++q)
             gf[q] = quant_grad<GI2D_QUANT_LSQ>(qr.col[q], acc[5 + q], v.fs[q], sums[10 + 2 * q], sums[11 + 2 * q]);
-        if (dbg_grads) {
-            float *d = dbg_grads + 8 * (size_t)g;
-            d[0] = gx, d[1] = gy, d[2] = gp[0], d[3] = gp[1], d[4] = gp[2], d[5] = gf[0], d[6] = gf[1], d[7] = gf[2];
-        }
-        float2 new_xy;
-        Row3 new_chol, new_feat;
+        quant_dbg_row(u.dbg_grads, g, gx, gy, gp, gf);
         adam_update_rows(rows, gx, gy, gp, gf, a_xyz, a_chol, a_feat);
         adam_store_rows(P, g, rows);
-        new_xy = rows.x, new_chol = rows.c, new_feat = rows.f;
-        if (snapshot) {  // from registers, not read back through memory
-            best.xyz[2 * g] = new_xy.x;
-            best.xyz[2 * g + 1] = new_xy.y;
-            const float nc[3] = {new_chol.a, new_chol.b, new_chol.c}, nf[3] = {new_feat.a, new_feat.b, new_feat.c};
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                best.chol[3 * g + q] = nc[q];
-                best.feat[3 * g + q] = nf[q];
-                if (best.bound) best.bound[3 * g + q] = P.bound[(size_t)P.bound_stride * g + q];
-            }
-        }
+        if (o.snapshot)
+            quant_snapshot_store(o.best, P, g, rows.x, {rows.c.a, rows.c.b, rows.c.c}, {rows.f.a, rows.f.b, rows.f.c});
     }
-    // this wave's partial row (see wave_partial_row)
-#pragma unroll
-    for (int k = 0; k < GI2D_QT_RS_SUMS; ++k) sums[k] = wave_sum(sums[k]);
-    if ((threadIdx.x & 63) == 0) {
-        float4 *r4 = reinterpret_cast<float4 *>(Q.partial + (size_t)quant_wave_row(block) * GI2D_QT_ROW);
-#pragma unroll
-        for (int k = 0; k < GI2D_QT_RS_SUMS / 4; ++k)
-            r4[k] = make_float4(sums[4 * k], sums[4 * k + 1], sums[4 * k + 2], sums[4 * k + 3]);
-    }
+    wave_partial_row(sums, Q.partial + (size_t)quant_wave_row(block) * GI2D_QT_ROW);
 }
-
-// One workgroup: sums the partial rows in double (fixed order) and runs Adam on the 16 quantiser values.
-__device__ __forceinline__ void quant_finish_rs(int blocks, const QuantTrain &Q, const AdamStep &a_qxy,
+// ... and its closing step: Adam on the 16 quantiser values.
+__device__ __forceinline__ void quant_finish_rs(int rows, const QuantTrain &Q, const AdamStep &a_qxy,
                                                 const AdamStep &a_qcov, const AdamStep &a_qcol, const BestSnap &best) {
-#pragma clang fp contract(off)
-    __shared__ double lane_acc[256][GI2D_QT_RS_SUMS + 1];  // odd stride in 8-byte words
-    __shared__ double dred[16][GI2D_QT_RS_SUMS];
-    float q_p = 0.f, q_m = 0.f, q_v = 0.f;
-    if (threadIdx.x < GI2D_QT_RS_SUMS)
-        q_p = Q.qparams[threadIdx.x], q_m = Q.qm[threadIdx.x], q_v = Q.qv[threadIdx.x];
+    __shared__ double tot[16];
+    const QuantValue qv = quant_value_load(kQuantSlotsRS, Q);
     const bool snap = best.sse != nullptr && best.info[1] == best.step;
-    double acc[GI2D_QT_RS_SUMS];
-#pragma unroll
-    for (int k = 0; k < GI2D_QT_RS_SUMS; ++k) acc[k] = 0.0;
-    for (int b = threadIdx.x; b < blocks; b += (int)blockDim.x) {
-        const float4 *row = reinterpret_cast<const float4 *>(Q.partial + (size_t)b * GI2D_QT_ROW);
-        float4 r[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = row[k];
-        const float *f = reinterpret_cast<const float *>(r);
-#pragma unroll
-        for (int k = 0; k < GI2D_QT_RS_SUMS; ++k) acc[k] += (double)f[k];
-    }
-#pragma unroll
-    for (int k = 0; k < GI2D_QT_RS_SUMS; ++k) lane_acc[threadIdx.x][k] = acc[k];
-    __syncthreads();
-    const int k = threadIdx.x & 15, j = threadIdx.x >> 4;
-    {
-        double part = 0.0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) part += lane_acc[j * 16 + i][k];
-        dred[j][k] = part;
-    }
-    __syncthreads();
-    if (threadIdx.x < GI2D_QT_RS_SUMS) {
-        const int q = threadIdx.x;
-        // slot q of qparams -> (channel, scale or beta): xs xs xb xb | ss ss sb sb | rs rb | fs fs fs fb fb fb
-        int ch, isb;
-        if (q < 4) ch = q & 1, isb = q >> 1;
-        else if (q < 8) ch = 2 + (q & 1), isb = (q - 4) >> 1;
-        else if (q < 10) ch = 4, isb = q - 8;
-        else ch = 5 + (q - 10) % 3, isb = (q - 10) / 3;
-        double t = 0.0;
-        for (int w = 0; w < 16; ++w) t += dred[w][2 * ch + isb];
-        const float grad = (float)t;
-        const AdamStep &a = q < 4 ? a_qxy : (q < 10 ? a_qcov : a_qcol);
-        const float nv = adam(q_p, grad, q_m, q_v, a);
-        Q.qparams[q] = nv;
-        Q.qm[q] = q_m;
-        Q.qv[q] = q_v;
-        if (Q.dbg_q) Q.dbg_q[q] = grad;
-        if (snap && Q.best_q) Q.best_q[q] = nv;
-    }
+    quant_close_sums<16>(rows, Q.partial, tot, [](const float *) {});
+    if (threadIdx.x < 16) quant_value_step(threadIdx.x, qv, tot, Q, a_qxy, a_qcov, a_qcol, snap);
 }
 
 // ------------------------------------------------------------------ kernels of the quantisation-aware iteration
 // MODEL: 1 covariance, 2 rotation-scale.  Single-image forms take the image's argument blocks as kernel arguments; the
-// batched forms find theirs in the batch table by workgroup index (gi2d_batch.h), like the plain fitting kernels.
+// batched forms find theirs in the batch table by workgroup index (batch_slot), like the plain fitting kernels.
 // The closing step is a launch of its own (one workgroup per image).  Running it in the last workgroup of the producing
 // kernel instead (ticket + device-scope fences) was measured and dropped: on this 8-XCD part every workgroup's release
 // fence writes its L2 back, which made the update kernel 17 us slower to save a 4 us launch.
+// (batch_slot: workgroup b of a batched launch works on image k with pg_start[k] <= b < pg_start[k + 1], as that image's
+// workgroup `local`, both wave-uniform.  The plain batched kernels keep the two lines written out: their generated code
+// changes with the helper.)
+struct BatchSlot {
+    int k, local;
+};
+__device__ __forceinline__ BatchSlot batch_slot(const int *__restrict__ pg_start, int k_images) {
+    const int k = batch_find(pg_start, k_images, (int)blockIdx.x);
+    return {k, __builtin_amdgcn_readfirstlane((int)blockIdx.x - pg_start[k])};
+}
 template <int MODEL>
 __global__ __launch_bounds__(256) void train_project_fill_quant_kernel(UpdateArgs u, QuantTrain Q, int store_proj) {
-    if (MODEL == 2)
-        project_fill_quant_rs_body((int)blockIdx.x, u, Q, store_proj != 0);
-    else
-        project_fill_quant_body((int)blockIdx.x, u, Q, store_proj != 0);
+    project_fill_quant_body<MODEL>((int)blockIdx.x, u, Q, store_proj != 0);
 }
 template <int MODEL>
 __global__ __launch_bounds__(256) void train_project_fill_quant_batched_kernel(const BatchImage *__restrict__ imgs,
                                                                                const int *__restrict__ pg_start,
                                                                                int k_images, int store_proj) {
-    const int k = batch_find(pg_start, k_images, (int)blockIdx.x);
-    const int local = __builtin_amdgcn_readfirstlane((int)blockIdx.x - pg_start[k]);
-    if (MODEL == 2)
-        project_fill_quant_rs_body(local, imgs[k].u, imgs[k].q, store_proj != 0);
-    else
-        project_fill_quant_body(local, imgs[k].u, imgs[k].q, store_proj != 0);
+    const BatchSlot b = batch_slot(pg_start, k_images);
+    project_fill_quant_body<MODEL>(b.local, imgs[b.k].u, imgs[b.k].q, store_proj != 0);
 }
 template <int MODEL>
 __global__ __launch_bounds__(256) void train_reduce_update_quant_kernel(UpdateArgs u, QuantTrain Q, AdamStep a_xyz,
                                                                         AdamStep a_chol, AdamStep a_feat, int step) {
-    if (MODEL == 2)
-        reduce_update_quant_rs_body<true>((int)blockIdx.x, u, Q, a_xyz, a_chol, a_feat, step);
-    else
-        reduce_update_quant_body<true>((int)blockIdx.x, u, Q, a_xyz, a_chol, a_feat, step);
+    reduce_update_quant_body<true>(QuantModel<MODEL>{}, (int)blockIdx.x, u, Q, a_xyz, a_chol, a_feat, step);
 }
 template <int MODEL>
 __global__ __launch_bounds__(256) void train_reduce_update_quant_batched_kernel(const BatchImage *__restrict__ imgs,
@@ -1269,21 +1247,16 @@ __global__ __launch_bounds__(256) void train_reduce_update_quant_batched_kernel(
                                                                                 int k_images, AdamStep a_xyz,
                                                                                 AdamStep a_chol, AdamStep a_feat,
                                                                                 int step) {
-    const int k = batch_find(pg_start, k_images, (int)blockIdx.x);
-    const int local = __builtin_amdgcn_readfirstlane((int)blockIdx.x - pg_start[k]);
-    if (MODEL == 2)
-        reduce_update_quant_rs_body<false>(local, imgs[k].u, imgs[k].q, a_xyz, a_chol, a_feat, step);
-    else
-        reduce_update_quant_body<false>(local, imgs[k].u, imgs[k].q, a_xyz, a_chol, a_feat, step);
+    const BatchSlot b = batch_slot(pg_start, k_images);
+    reduce_update_quant_body<false>(QuantModel<MODEL>{}, b.local, imgs[b.k].u, imgs[b.k].q, a_xyz, a_chol, a_feat, step);
 }
 __global__ __launch_bounds__(256) void train_quant_range_kernel(UpdateArgs u, QuantTrain Q) {
     quant_range_body((int)blockIdx.x, u, Q);
 }
 __global__ __launch_bounds__(256) void train_quant_range_batched_kernel(const BatchImage *__restrict__ imgs,
                                                                         const int *__restrict__ pg_start, int k_images) {
-    const int k = batch_find(pg_start, k_images, (int)blockIdx.x);
-    const int local = __builtin_amdgcn_readfirstlane((int)blockIdx.x - pg_start[k]);
-    quant_range_body(local, imgs[k].u, imgs[k].q);
+    const BatchSlot b = batch_slot(pg_start, k_images);
+    quant_range_body(b.local, imgs[b.k].u, imgs[b.k].q);
 }
 // closing step; `rows`: partial rows (= waves) of the image's per-gaussian launch.  MODE 0: range only (covariance model,
 // start of a call), 1: covariance model, 2: rotation-scale model.
@@ -1293,14 +1266,12 @@ __device__ __forceinline__ void quant_finish_any(int rows, const UpdateArgs &u, 
                                                  int step) {
     BestSnap best = u.best;
     best.step = step;
-    if (MODE == 0) {
-        best.sse = nullptr;
-        quant_finish<true>(rows, u.P, Q, a_chol, a_qxy, a_qcov, a_qcol, nullptr, best);
-    } else if (MODE == 1) {
-        quant_finish<false>(rows, u.P, Q, a_chol, a_qxy, a_qcov, a_qcol, u.dbg_grads, best);
-    } else {
+    if constexpr (MODE == 0)
+        quant_finish_range(rows, Q);
+    else if constexpr (MODE == 1)
+        quant_finish_cov(rows, u.P, Q, a_chol, a_qxy, a_qcov, a_qcol, u.dbg_grads, best);
+    else
         quant_finish_rs(rows, Q, a_qxy, a_qcov, a_qcol, best);
-    }
 }
 template <int MODE>
 __global__ __launch_bounds__(256) void train_quant_finish_kernel(int rows, UpdateArgs u, QuantTrain Q, AdamStep a_chol,
@@ -1701,8 +1672,8 @@ struct OneImage {
         } else if (s->kind != 2) {
             const AdamStep z = idle_adam_step();
             hipLaunchKernelGGL(train_quant_range_kernel, gg, bb, 0, st, p.u, p.q);
-            hipLaunchKernelGGL(train_quant_finish_kernel<0>, dim3(1), dim3(256), 0, st, p.blocks * (p.bs / 64), p.u, p.q, z,
-                               z, z, z, 0);
+            hipLaunchKernelGGL(train_quant_finish_kernel<0>, dim3(1), dim3(kQuantCloseLanes), 0, st, p.blocks * (p.bs / 64),
+                               p.u, p.q, z, z, z, z, 0);
         }
     }
     // activations / quantisers + projection + fill
@@ -1750,8 +1721,8 @@ struct OneImage {
     void update_quant(const IterSteps &c, int step) const {
         hipLaunchKernelGGL(train_reduce_update_quant_kernel<M>, dim3(p.blocks), dim3(p.bs), 0, st, p.u, p.q, c.a[0], c.a[1],
                            c.a[2], step);
-        hipLaunchKernelGGL(train_quant_finish_kernel<M>, dim3(1), dim3(256), 0, st, p.blocks * (p.bs / 64), p.u, p.q,
-                           c.a[1], c.aq[0], c.aq[1], c.aq[2], step);
+        hipLaunchKernelGGL(train_quant_finish_kernel<M>, dim3(1), dim3(kQuantCloseLanes), 0, st, p.blocks * (p.bs / 64),
+                           p.u, p.q, c.a[1], c.aq[0], c.aq[1], c.aq[2], step);
     }
     int close() const {
         if (!loss) {
@@ -1792,8 +1763,8 @@ struct ImageBatch {
         } else if (kind != 2) {
             const AdamStep z = idle_adam_step();
             hipLaunchKernelGGL(train_quant_range_batched_kernel, gg, bb, 0, st, imgs, pg_start, k_images);
-            hipLaunchKernelGGL(train_quant_finish_batched_kernel<0>, gi, dim3(256), 0, st, imgs, pg_start, (int)bb.x / 64, z,
-                               z, z, z, 0);
+            hipLaunchKernelGGL(train_quant_finish_batched_kernel<0>, gi, dim3(kQuantCloseLanes), 0, st, imgs, pg_start,
+                               (int)bb.x / 64, z, z, z, z, 0);
         }
     }
     void project_fill_quant(bool store_proj) const {
@@ -1820,8 +1791,8 @@ struct ImageBatch {
     void update_quant(const IterSteps &c, int step) const {
         hipLaunchKernelGGL(train_reduce_update_quant_batched_kernel<M>, gg, bb, 0, st, imgs, pg_start, k_images, c.a[0],
                            c.a[1], c.a[2], step);
-        hipLaunchKernelGGL(train_quant_finish_batched_kernel<M>, gi, dim3(256), 0, st, imgs, pg_start, (int)bb.x / 64,
-                           c.a[1], c.aq[0], c.aq[1], c.aq[2], step);
+        hipLaunchKernelGGL(train_quant_finish_batched_kernel<M>, gi, dim3(kQuantCloseLanes), 0, st, imgs, pg_start,
+                           (int)bb.x / 64, c.a[1], c.aq[0], c.aq[1], c.aq[2], step);
     }
     int close() const {
         if (!losses) {

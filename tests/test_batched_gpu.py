@@ -329,8 +329,16 @@ def test_sixty_four_images_in_one_launch():
 QROWS = ("qparams", "qm", "qv", "best_qparams", "qfeat")
 
 
+# populations on the wave and workgroup edges the per-gaussian kernels index by: one below, at and one above a wave; one
+# above a 256-lane workgroup next to the smallest population the quantisers can be initialised from (N = 1 gives every
+# attribute an empty range: enable_quantize refuses it)
+WAVE_EDGES = [(17, 33, 63), (32, 48, 64), (48, 32, 65)]
+GROUP_EDGES = [(40, 40, 257), (16, 16, 2)]
+
+
 @pytest.mark.parametrize("kind,sizes", [("covariance", MIXED), ("scale_rot", UNIFORM), ("covariance", BIG),
-                                        ("scale_rot", BIG)])
+                                        ("scale_rot", BIG), ("covariance", WAVE_EDGES), ("scale_rot", WAVE_EDGES),
+                                        ("covariance", GROUP_EDGES), ("scale_rot", GROUP_EDGES)])
 def test_batched_quantised_iterations_equal_single_image_calls(kind, sizes):
     """Quantisation-aware iterations (train_iter_quantize) of K images with four launches per iteration for all of them
     == the same iterations image by image: parameters, Adam moments, the quantisers' learned values and their moments,
