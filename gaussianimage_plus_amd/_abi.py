@@ -1,9 +1,10 @@
 """ctypes signatures and structures read from the text of include/gi2d.h, the one place the C ABI is written down.
 
 parse(text) understands the subset of C that header is written in -- `/* */` comments, `#define NAME <integer>`,
-`typedef <pointer> name;`, `[typedef] struct name { fields } [name];` and function prototypes over scalar types and
-pointers -- and refuses everything else with a ValueError that quotes the declaration: a declaration it skipped would
-leave a function unbound or a structure short, which is worse than no binding at all.  Standard library only.
+`typedef <pointer> name;`, `[typedef] struct name { fields } [name];` and function prototypes over scalar types (`long
+long` among them) and pointers -- and refuses everything else with a ValueError that quotes the declaration: a
+declaration it skipped would leave a function unbound or a structure short, which is worse than no binding at all.
+Standard library only.
 """
 from __future__ import annotations
 
@@ -13,7 +14,7 @@ import re
 from typing import Dict, List, NamedTuple, Tuple
 
 _SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
-            "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64}
+            "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "long_long": C.c_longlong}
 _RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p}
 _POINTEES = set(_SCALARS) | {"void", "char"}  # what a `T *` may point to besides a struct or a pointer typedef
 
@@ -54,6 +55,7 @@ class _Parser:
         self.bounds = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\d+)[ \t]*$",
                                                             text, flags=re.M)}
         text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+        text = re.sub(r"\blong\s+long\b", "long_long", text)  # the one two-word scalar: read as one name (_SCALARS)
         text, wrapped = re.subn(r'extern\s+"C"\s*\{', "", text)
         if wrapped:
             body, brace, tail = text.rpartition("}")

@@ -70,6 +70,15 @@ only a fit reads, and its epilogue -- like that of gi2d_rasterize_forward_long_a
 conversion and the layout; its float32 "hwc" picture is the fitting forward's followed by a clamp, bit for bit, and every
 other format is `convert` of that.  The fallbacks draw in float32 and end in a clamp or in gi2d_codec_convert.
 
+SAMPLES (codec.Field, DESIGN.md 3.8 "Samples") are the fitted function at positions of the caller's choosing: a non-affine
+warp grid, a scattered batch of (x, y), the point under a cursor -- what no map on the gaussians can give.  Decoder.field
+runs the lists route's first two launches once under the identity map (gi2d_codec_decode_affine, gi2d_bin_gaussians) into
+tensors the Field owns; Field.sample then evaluates any number of float32 positions (gi2d_sample_points, csrc/gi2d_sample.hip):
+the tile of a position's nearest pixel, that tile's whole list in list order, the pair arithmetic of the lists route at the
+position itself.  On the integer lattice that is the identity affine view of the lists route bit for bit; between pixels it
+is point evaluation -- no low-pass, so a grid that reduces aliases (Overview and Affine are for that), and, like every view,
+cut by tile boxes, so not continuous across tile borders.
+
 Format version 1 (little-endian; INTEGRATION.md "Packed stream" has the record layout):
 
     0  magic "GI2D" | 4 version = 1 | 5 model kind (1 covariance, 2 scale-rot) | 6 payload coding (0 = fixed-length
@@ -97,6 +106,7 @@ kernels compute no address from stream content that is not masked or clamped to 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import dataclasses
 import math
@@ -1287,6 +1297,91 @@ def _stream_args(h, payload: torch.Tensor) -> tuple:
             h["fixed_payload_bytes"], h["clip_coe"])
 
 
+class Field:
+    """The fitted function of ONE stream, ready to be sampled at any position (Decoder.field makes it; DESIGN.md 3.8
+    "Samples"): the five per-gaussian arrays of the lists route under the identity map and the tile lists of the picture's
+    own 16x16 tile grid, in tensors of its own -- no later call of the Decoder touches them.  header: the parsed stream;
+    width, height: the picture's size; count: the number of (gaussian, tile) intersections; capacity: entries `ids` holds."""
+
+    def __init__(self, dev: torch.device, header: Dict[str, object], geometry: Sequence[torch.Tensor], ids: torch.Tensor,
+                 bins: torch.Tensor, status: torch.Tensor, capacity: int, count: int):
+        self.dev, self.header = dev, header
+        self.width, self.height = int(header["width"]), int(header["height"])
+        self.tiles = (_tiles(self.width), _tiles(self.height))
+        self.xys, self.radii, self.conics, self.num_tiles_hit, self.colors = geometry
+        self.ids, self.bins, self.status = ids, bins, status
+        self.capacity, self.count = int(capacity), int(count)
+
+    def identity_grid(self) -> torch.Tensor:
+        """The lattice of the picture itself, float32 [H, W, 2] on the field's device: entry (i, j) is (x, y) = (j, i).
+        sample(identity_grid()) is the identity affine view of the lists route, bit for bit."""
+        xs = torch.arange(self.width, dtype=torch.float32, device=self.dev)
+        ys = torch.arange(self.height, dtype=torch.float32, device=self.dev)
+        return torch.stack(torch.broadcast_tensors(xs[None, :], ys[:, None]), dim=2).contiguous()
+
+    def sample(self, points: torch.Tensor, out: Optional[torch.Tensor] = None, dtype=None, layout=None,
+               fill: Sequence[float] = (0.0, 0.0, 0.0), presort: Optional[bool] = None) -> torch.Tensor:
+        """The function at `points`: float32, contiguous, on the field's device, [P, 2] or a grid [Ho, Wo, 2] with (x, y)
+        last, in source pixel coordinates (pixel centres at integers).  -> [P, 3] or [Ho, Wo, 3] float32 by default;
+        dtype / layout as in decode: "chw" gives [3, P] or [3, Ho, Wo], "hwc4" [P, 4] or [Ho, Wo, 4].  A position outside
+        0 <= x <= W - 1, 0 <= y <= H - 1 (a NaN or an infinity too) gives `fill` (three finite floats) in the format.
+        presort: whether the work (never the output) is ordered by tile first -- gi2d_sample_point_keys, torch's stable
+        sort on the device, the permutation narrowed to int32.  None sorts a flat list and leaves a grid, whose 16x4
+        strips are coherent as they are, alone; True on a grid treats it as a flat list.  A sample's bits do not depend on
+        the choice.  No host wait.  ValueError, before any launch, for anything else."""
+        fmt = _format(dtype, layout)
+        if (not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() not in (2, 3)
+                or points.shape[-1] != 2):
+            raise ValueError("sample: points must be a float32 tensor of shape [P, 2] or [Ho, Wo, 2], (x, y) last")
+        if points.device != self.dev:
+            raise ValueError(f"sample: points live on {points.device}, the field on {self.dev}")
+        if not points.is_contiguous():
+            raise ValueError("sample: points must be contiguous")
+        if presort is not None and not isinstance(presort, bool):
+            raise ValueError(f"sample: presort {presort!r}: None, True or False")
+        try:
+            fill = tuple(fill)
+        except TypeError:
+            raise ValueError(f"sample: fill {fill!r}: three finite floats") from None
+        if len(fill) != 3:
+            raise ValueError(f"sample: fill {fill!r}: three finite floats")
+        _finite_numbers("sample", fill_r=fill[0], fill_g=fill[1], fill_b=fill[2])
+        with np.errstate(over="ignore"):
+            fill = tuple(float(np.float32(v)) for v in fill)
+        if not all(math.isfinite(v) for v in fill):
+            raise ValueError(f"sample: fill {fill}: not finite in float32")
+        grid = points.dim() == 3
+        p = points.numel() // 2
+        if grid:
+            shape = fmt.shape(points.shape[0], points.shape[1])
+        else:
+            shape = (3, p) if fmt.layout == "chw" else (p, 4 if fmt.layout == "hwc4" else 3)
+        if out is not None:
+            _check_out(out, shape, fmt.dtype, self.dev)
+        sort = (not grid) if presort is None else presort
+        if p > (0x7FFFFFFF if sort else 0x7FFFFFFF * 256):
+            raise ValueError(f"sample: {p} positions are more than one call takes")
+        if out is None:
+            out = torch.empty(shape, dtype=fmt.dtype, device=self.dev)
+        if p == 0:
+            return out
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        tx, ty = self.tiles
+        with torch.cuda.device(self.dev) if self.dev.type == "cuda" else contextlib.nullcontext():
+            st = _stream(self.dev)
+            perm = None
+            if sort:
+                keys = torch.empty(p, dtype=torch.int32, device=self.dev)
+                _lib.call("gi2d_sample_point_keys", p, ptr(points), self.width, self.height, tx, ty, ptr(keys), st)
+                perm = torch.sort(keys, stable=True).indices.to(torch.int32)
+            gw, gh = (points.shape[1], points.shape[0]) if grid and not sort else (0, 0)
+            _lib.call("gi2d_sample_points", self.header["num_points"], self.capacity, tx, ty, self.width, self.height,
+                      ptr(self.ids), ptr(self.bins), tx * ty, ptr(self.xys), ptr(self.conics), ptr(self.colors), None,
+                      ptr(self.status), p, ptr(points), None if perm is None else ptr(perm), gw, gh, (C.c_float * 3)(*fill),
+                      *fmt.ids, ptr(out), st)
+        return out
+
+
 class Decoder:
     """Decodes streams on one device.  Payload staging, the fast-path workspace and the status words are kept between
     calls and regrown only when a stream needs more; nothing of one stream survives into the next (the workspace is
@@ -1794,6 +1889,51 @@ class Decoder:
         images, aux = self._run([stream], [(view,)], _DEFAULT_FORMAT, geometry=True)
         return dict(zip(("xys", "radii", "conics", "num_tiles_hit", "colors"), aux), image=images[0])
 
+    def field(self, stream) -> Field:
+        """bytes (or an uploaded DeviceStream) -> the stream's Field, to be sampled at any position (Field.sample).  The
+        stream is parsed and checked as every decode does, a rANS payload expanded once, and the first two launches of the
+        lists route run under the identity map -- gi2d_codec_decode_affine (origin 0, B = I, prefilter 0, the stream's
+        radius_clip) and gi2d_bin_gaussians, lists of the capacity an overview starts with -- into tensors the Field owns,
+        not into the buffers the next overview overwrites.  {count, overflow} is read in ONE host wait, the only one of a
+        Field's life; lists that were cut at the capacity are binned again with room for exactly `count`."""
+        h = _headers([stream])[0]
+        ident = Affine(0.0, 0.0, 1.0, 0.0, 0.0, 1.0, h["width"], h["height"], 0.0).check(h)  # (<= 16384 tiles, as every view)
+        n, tx, ty = h["num_points"], *ident.tiles
+        rc = ident.radius_clip(h)
+        i32 = lambda count: torch.empty(count, dtype=torch.int32, device=self.dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        bin_bytes = _lib.load().gi2d_bin_workspace_bytes
+        with torch.cuda.device(self.dev):
+            payload = self._stage([stream], [h])[0]
+            status = torch.zeros(_STATUS_WORDS, dtype=torch.int32, device=self.dev)
+            st = _stream(self.dev)
+            coded = h["coding"] != CODING_FIXED
+            if coded:
+                self._next_token()
+                payload = self._expand(h, payload, status.data_ptr(),
+                                       torch.empty(h["fixed_payload_bytes"], dtype=torch.uint8, device=self.dev))
+            geo = self._aux(n)
+            cap = self._overview_list_capacity(n)
+            ids, bins = i32(cap), i32(2 * tx * ty)
+            _lib.call("gi2d_codec_decode_affine", *_stream_args(h, payload), h["height"], h["width"], ident.x0, ident.y0,
+                      *ident.inverse, *ident.prefilter, h["height"], h["width"], tx, ty, rc, *map(ptr, geo), st)
+
+            def bin_lists(capacity: int, ids: torch.Tensor) -> None:
+                binws = torch.empty(int(bin_bytes(capacity, tx * ty)), dtype=torch.uint8, device=self.dev)
+                _lib.call("gi2d_bin_gaussians", n, capacity, ptr(geo[0]), ptr(geo[1]), tx, ty, rc, ptr(ids), ptr(bins),
+                          status.data_ptr(), ptr(binws), binws.numel(), st)
+
+            bin_lists(cap, ids)
+            m, overflow, _, _, word = status[0:5].tolist()  # the host wait
+            if coded:
+                self._check_expanded(word)
+            self._overview_m = max(self._overview_m, m)
+            if overflow:
+                cap = max(1, m)
+                ids = i32(cap)
+                bin_lists(cap, ids)
+        return Field(self.dev, h, geo, ids, bins, status, cap, m)
+
 
 _decoders: Dict[torch.device, Decoder] = {}
 
@@ -1819,6 +1959,22 @@ def decode(blob, device: Union[str, torch.device] = "cuda:0", out: Optional[torc
         w, hh = (h["width"], h["height"]) if view is None else (view.width, view.height)
         _check_out(out, fmt.shape(hh, w), fmt.dtype)
     return _decoder(device).decode(blob, out=out, view=view, dtype=dtype, layout=layout)
+
+
+def field(blob, device: Union[str, torch.device] = "cuda:0") -> Field:
+    """One-shot Decoder.field (the Decoder kept per device): the stream's Field, to be sampled any number of times."""
+    _parse(blob)  # a malformed stream is refused before a device is even touched
+    return _decoder(device).field(blob)
+
+
+def sample(blob, points: torch.Tensor, device: Optional[Union[str, torch.device]] = None, out: Optional[torch.Tensor] = None,
+           dtype=None, layout=None, fill: Sequence[float] = (0.0, 0.0, 0.0), presort: Optional[bool] = None) -> torch.Tensor:
+    """One-shot field(blob).sample(points, ...) on the points' device (or `device`): a caller with more than one batch of
+    positions keeps the Field instead -- its lists are built once."""
+    if not isinstance(points, torch.Tensor):
+        raise ValueError("sample: points must be a float32 tensor of shape [P, 2] or [Ho, Wo, 2], (x, y) last")
+    return field(blob, points.device if device is None else device).sample(points, out=out, dtype=dtype, layout=layout,
+                                                                           fill=fill, presort=presort)
 
 
 def decode_batch(blobs, device: Union[str, torch.device] = "cuda:0", views=None, out: Optional[torch.Tensor] = None,

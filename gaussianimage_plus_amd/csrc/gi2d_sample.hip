@@ -1,0 +1,287 @@
+// Samples of a packed stream at positions of the caller's choosing (include/gi2d.h "samples"; DESIGN.md 3.8 "Samples"):
+// the fitted function evaluated at fp32 source positions -- a warp grid, a scattered batch, the point under a cursor --
+// from the five per-gaussian arrays and the tile lists of the capacity-free route under the identity map
+// (gi2d_codec_decode_affine + gi2d_bin_gaussians).  No new per-gaussian arithmetic: an entry is staged exactly as
+// gi2d_codec_overview.hip::raster_fwd_long_kernel stages it and added with the operations of
+// gi2d_long_core.h::long_pair in the same order, so on the integer lattice a sample repeats that kernel's pixel bit for bit.
+//
+//   keys     sample_keys_kernel, one lane per sample: position -> the index of the tile of its nearest pixel, or
+//            tiles_x * tiles_y for a position outside the sample grid (NaN and infinities included), which sorts last.
+//   samples  sample_points_kernel, 256 threads; the unit of work is a WAVE with 64 samples, and the four waves of a
+//            workgroup never meet (no workgroup barrier).  The samples of a wave do not share a tile, so the wave walks
+//            the tiles it holds one after the other (a waterfall): the key of the first unserved lane, read as a scalar,
+//            names the tile; its list is staged 64 entries at a time into the wave's own 2.5 KB of LDS, and the lanes
+//            whose key it is add the staged entries in list order.  Presorted or coherent samples take one to four
+//            trips; any order is correct.  Per staged batch the wave keeps only the entries whose alpha >= 1/255 box
+//            (cull_extent) meets the bounding box of the served lanes' positions -- a ballot compaction at the staging
+//            store that preserves list order; a dropped entry fails the pair test at every served sample.
+//
+// A sample's bits depend on the stream and its position alone: no atomics, and neither its place in the call nor its
+// neighbours enter its sum.  Nothing is read through an address formed from unchecked content: the tile comes from a
+// position that has passed the inside test and is clamped to the grid, list bounds are clamped to the capacity of the id
+// buffer, ids to [0, N), entries of `perm` to [0, P).
+#include <string>
+
+#include "gi2d_long_core.h"
+
+namespace gi2d {
+
+// the wave's staging block: the LongLds triple of 64 entries
+#define GI2D_SAMPLE_BATCH 64
+struct SampleLds {
+    float4 a[GI2D_SAMPLE_BATCH];  // gx, gy, ha, hb   (conic pre-scaled: scale_conic)
+    float4 b[GI2D_SAMPLE_BATCH];  // hc, opacity, cr, cg
+    float2 c[GI2D_SAMPLE_BATCH];  // cb, AlphaRule::lim
+};
+
+// Inside the picture's sample grid (0 <= x <= W - 1, 0 <= y <= H - 1: false for a NaN or an infinity) -> the tile of the
+// nearest pixel, clamped to the grid; tiles_x * tiles_y for a position outside.
+__device__ __forceinline__ int sample_key(float x, float y, int img_w, int img_h, int tiles_x, int tiles_y, bool &inside) {
+    inside = x >= 0.f && x <= (float)(img_w - 1) && y >= 0.f && y <= (float)(img_h - 1);
+    if (!inside) return tiles_x * tiles_y;
+    const int j = (int)floorf(x + 0.5f), i = (int)floorf(y + 0.5f);
+    const int tx = min(max(j >> 4, 0), tiles_x - 1), ty = min(max(i >> 4, 0), tiles_y - 1);
+    return ty * tiles_x + tx;
+}
+
+__global__ __launch_bounds__(256) void sample_keys_kernel(long long num_samples, const float2 *__restrict__ points,
+                                                          int img_w, int img_h, int tiles_x, int tiles_y,
+                                                          int32_t *__restrict__ keys) {
+    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= num_samples) return;
+    const float2 p = points[s];
+    bool inside;
+    keys[s] = sample_key(p.x, p.y, img_w, img_h, tiles_x, tiles_y, inside);
+}
+
+// one staged entry on this lane's sample: long_pair's operations, in its order, on the staged triple
+template <bool CLAMP>
+__device__ __forceinline__ void sample_pair(const float4 A, const float4 B, const float2 Cc, float px, float py, float &o0,
+                                            float &o1, float &o2) {
+    const unsigned lim = (unsigned)__float_as_int(Cc.y);
+    const float dy = A.y - py;
+    const float bdy = A.w * dy, cdy2 = __builtin_fmaf(B.x * dy, dy, 0.f);
+    const float dx = A.x - px;
+    const float sig = __builtin_fmaf(dx, __builtin_fmaf(A.z, dx, bdy), cdy2);
+    const float tt = B.y * pair_vis(sig);
+    const bool ok = CLAMP ? pair_lands_odd(sig, tt, lim) : pair_lands(sig, lim);
+    float am = ok ? tt : 0.f;
+    if (CLAMP) am = fminf(1.f, am);
+    o0 = __builtin_fmaf(B.z, am, o0);
+    o1 = __builtin_fmaf(B.w, am, o1);
+    o2 = __builtin_fmaf(Cc.x, am, o2);
+}
+
+// Smallest and largest of one float per lane over the wave, in every lane: the DPP steps of wave_inclusive_scan with
+// +inf / -inf where a step has no source lane.  Every lane of the wave must be active.
+__device__ __forceinline__ float wave_min_dpp(float x) {
+    int v = __float_as_int(x);
+#define GI2D_DPP_FMIN(ctrl, row_mask) \
+    v = __float_as_int(fminf(__int_as_float(v), __int_as_float(__builtin_amdgcn_update_dpp(0x7f800000, v, ctrl, row_mask, 0xf, false))))
+    GI2D_DPP_FMIN(0x111, 0xf);
+    GI2D_DPP_FMIN(0x112, 0xf);
+    GI2D_DPP_FMIN(0x114, 0xf);
+    GI2D_DPP_FMIN(0x118, 0xf);
+    GI2D_DPP_FMIN(0x142, 0xa);
+    GI2D_DPP_FMIN(0x143, 0xc);
+#undef GI2D_DPP_FMIN
+    return __int_as_float(__builtin_amdgcn_readlane(v, 63));
+}
+__device__ __forceinline__ float wave_max_dpp(float x) { return -wave_min_dpp(-x); }
+
+// DTYPE, LAYOUT: the element type and layout of the output (gi2d_pixel_format.h), with pix = the sample's index and
+// plane = P.  GRID: the positions are a [grid_h, grid_w, 2] lattice and the wave holds a 16x4 strip of it, the workgroup
+// a 16x16 block, so that neighbouring samples meet the same source tiles; else sample 64 * (global wave) + lane of the
+// flat list, through `perm` when there is one.  SKIP: the per-wave skip described above.
+template <int DTYPE, int LAYOUT, bool GRID, bool SKIP>
+__global__ __launch_bounds__(256) void sample_points_kernel(
+    int n, int capacity, int tiles_x, int tiles_y, int img_w, int img_h, const int32_t *__restrict__ gids_sorted,
+    const int2 *__restrict__ tile_bins, int tile_bins_rows, const float2 *__restrict__ xys,
+    const float *__restrict__ conics, const float *__restrict__ colors, const float *__restrict__ opacities,
+    const int32_t *__restrict__ status, long long num_samples, const float2 *__restrict__ points,
+    const int32_t *__restrict__ perm, int grid_w, int grid_h, float fill0, float fill1, float fill2, void *__restrict__ out_) {
+    typedef typename PixelType<DTYPE>::type T;
+    __shared__ SampleLds lds[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    SampleLds &sm = lds[wv];
+
+    // ---- lane -> sample
+    bool valid;
+    long long s;
+    if (GRID) {
+        const int blocks_x = (grid_w + 15) >> 4;
+        const int bx = (int)(blockIdx.x % (unsigned)blocks_x), by = (int)(blockIdx.x / (unsigned)blocks_x);
+        const int col = bx * 16 + (lane & 15), row = by * 16 + wv * 4 + (lane >> 4);
+        valid = col < grid_w && row < grid_h;
+        s = (long long)row * grid_w + col;
+    } else {
+        s = ((long long)blockIdx.x * 4 + wv) * 64 + lane;
+        valid = s < num_samples;
+        if (valid && perm != nullptr) s = min(max((long long)perm[s], 0ll), num_samples - 1);
+    }
+    float px = 0.f, py = 0.f;
+    if (valid) {
+        const float2 p = points[s];
+        px = p.x, py = p.y;
+    }
+    bool inside;
+    const int key = sample_key(px, py, img_w, img_h, tiles_x, tiles_y, inside);
+    inside = inside && valid;
+
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+    const bool nothing = status != nullptr && status[0] < 1;  // not a single intersection: an inside sample is ones
+    if (nothing) o0 = o1 = o2 = 1.f;
+
+    // ---- the tiles this wave holds, one after the other (wave-uniform: `todo` is a ballot)
+    unsigned long long todo = nothing ? 0ull : __ballot(inside);
+    while (todo != 0ull) {
+        const int t = wave_read_lane(key, __ffsll((long long)todo) - 1);  // a scalar: list bounds and staging are uniform
+        const bool mine = inside && key == t;  // (all of them unserved: the lanes of a tile are served together)
+        todo &= ~__ballot(mine);
+        int2 range = make_int2(0, 0);
+        if (t < tile_bins_rows) range = tile_bins[t];
+        const int start = min(max(range.x, 0), capacity);
+        const int end = min(max(range.y, start), capacity);
+        if (start >= end) continue;
+        float bx0 = 0.f, bx1 = 0.f, by0 = 0.f, by1 = 0.f;  // what the served lanes' positions span
+        if (SKIP) {
+            const float inf = __int_as_float(0x7f800000);
+            bx0 = wave_min_dpp(mine ? px : inf), bx1 = wave_max_dpp(mine ? px : -inf);
+            by0 = wave_min_dpp(mine ? py : inf), by1 = wave_max_dpp(mine ? py : -inf);
+        }
+        int g_next = start + lane < end ? gids_sorted[start + lane] : 0;  // (one batch ahead of its use)
+        for (int base = start; base < end; base += GI2D_SAMPLE_BATCH) {
+            const int m = min(GI2D_SAMPLE_BATCH, end - base);
+            const int g = min(max(g_next, 0), n - 1);
+            if (base + GI2D_SAMPLE_BATCH + lane < end) g_next = gids_sorted[base + GI2D_SAMPLE_BATCH + lane];
+            bool keep = false, clamp = false;
+            float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A;
+            float2 Cc = make_float2(0.f, 0.f);
+            if (lane < m) {
+                const float2 xy = xys[g];
+                const float a = conics[3 * g], b = conics[3 * g + 1], c = conics[3 * g + 2];
+                const float op = opacities ? opacities[g] : 1.f;
+                const AlphaRule ar = alpha_rule(xy.x, xy.y, a, b, c, op);
+                const ConicS sc = scale_conic(a, b, c);
+                clamp = ar.clamp;
+                A = make_float4(xy.x, xy.y, sc.ha, sc.hb);
+                B = make_float4(sc.hc, op, colors[3 * g], colors[3 * g + 1]);
+                Cc = make_float2(colors[3 * g + 2], __int_as_float((int)ar.lim));
+                keep = true;
+                if (SKIP) {
+                    float hx, hy;
+                    cull_extent(xy.x, xy.y, a, b, c, op, hx, hy);
+                    // hx < 0: can never land; GI2D_CULL_FULL: no finite box, every sample is evaluated
+                    keep = hx >= 0.f && (hx >= GI2D_CULL_FULL || (xy.y - hy <= by1 && xy.y + hy >= by0 &&
+                                                                  xy.x - hx <= bx1 && xy.x + hx >= bx0));
+                }
+            }
+            const bool clamp_any = __ballot(clamp) != 0ull;
+            const unsigned long long mask = __ballot(keep);
+            const int kept = __popcll(mask);
+            __builtin_amdgcn_wave_barrier();  // the block may still be read by the batch before this one
+            if (keep) {  // compacted in list order
+                const int slot = __popcll(mask & lanemask_lt());
+                sm.a[slot] = A, sm.b[slot] = B, sm.c[slot] = Cc;
+            }
+            __builtin_amdgcn_wave_barrier();  // wave-private block: DS ops of one wave complete in order
+            if (mine) {
+                if (clamp_any) {
+#pragma unroll 4
+                    for (int k = 0; k < kept; ++k) sample_pair<true>(sm.a[k], sm.b[k], sm.c[k], px, py, o0, o1, o2);
+                } else {
+#pragma unroll 4
+                    for (int k = 0; k < kept; ++k) sample_pair<false>(sm.a[k], sm.b[k], sm.c[k], px, py, o0, o1, o2);
+                }
+            }
+        }
+    }
+
+    // ---- stores: the format's conversion (which clamps) of the sum, of ones, or of the caller's fill
+    if (!valid) return;
+    if (!inside) o0 = fill0, o1 = fill1, o2 = fill2;
+    pixel_store_elements<LAYOUT>(pixel_convert<DTYPE>(o0), pixel_convert<DTYPE>(o1), pixel_convert<DTYPE>(o2),
+                                 pixel_convert<DTYPE>(1.f), (size_t)s, (size_t)num_samples, reinterpret_cast<T *>(out_));
+}
+
+}  // namespace gi2d
+
+using namespace gi2d;
+
+// samples of one launch: 2^31 - 1 workgroups of 256
+#define GI2D_SAMPLE_MAX (0x7fffffffLL * 256)
+
+static bool sample_grid_covers(int tiles_x, int tiles_y, unsigned w, unsigned h) {
+    return (long long)tiles_x * GI2D_TILE >= (long long)w && (long long)tiles_y * GI2D_TILE >= (long long)h;
+}
+
+extern "C" {
+
+int gi2d_sample_point_keys(long long num_samples, const float *points_xy, unsigned w, unsigned h, int tiles_x, int tiles_y,
+                           int32_t *keys, gi2d_stream_t st) {
+    const char *what = "sample point keys";
+    const auto fail = [&](const char *why) {
+        set_error((std::string(what) + ": " + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    };
+    if (num_samples < 0 || tiles_x < 0 || tiles_y < 0) return fail("negative size");
+    if (!sample_grid_covers(tiles_x, tiles_y, w, h)) return fail("tile grid does not cover the image");
+    if ((long long)tiles_x * tiles_y >= 0x7fffffffLL || w > 0x7fffffffu || h > 0x7fffffffu) return fail("tile grid too large");
+    if (num_samples > GI2D_SAMPLE_MAX) return fail("more samples than one launch's grid can hold");
+    if (num_samples == 0) return GI2D_OK;
+    if (!points_xy || !keys) return fail("null pointer");
+    hipLaunchKernelGGL(sample_keys_kernel, dim3((unsigned)((num_samples + 255) / 256)), dim3(256), 0, (hipStream_t)st,
+                       num_samples, (const float2 *)points_xy, (int)w, (int)h, tiles_x, tiles_y, keys);
+    return check_launch(what);
+}
+
+int gi2d_sample_points(int n, int capacity, int tiles_x, int tiles_y, unsigned w, unsigned h, const int32_t *gids,
+                       const int32_t *bins, int rows, const float *xys, const float *conics, const float *colors,
+                       const float *opac, const int32_t *status, long long num_samples, const float *points_xy,
+                       const int32_t *perm, int grid_w, int grid_h, const float *fill_host, int dtype, int layout, void *out,
+                       gi2d_stream_t st) {
+    const char *what = "sample points";
+    const auto fail = [&](const char *why) {
+        set_error((std::string(what) + ": " + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    };
+    if (!pixel_format_ok(dtype, layout)) return fail("unknown format (dtype 0..2, layout 0..2)");
+    if (n < 0 || capacity < 0 || tiles_x < 0 || tiles_y < 0 || rows < 0 || num_samples < 0 || grid_w < 0 || grid_h < 0)
+        return fail("negative size");
+    if (capacity > 0x7fffffff - GI2D_SAMPLE_BATCH) return fail("capacity too large for 32-bit list positions");
+    if (!sample_grid_covers(tiles_x, tiles_y, w, h)) return fail("tile grid does not cover the image");
+    if ((long long)tiles_x * tiles_y >= 0x7fffffffLL || w > 0x7fffffffu || h > 0x7fffffffu) return fail("tile grid too large");
+    if (grid_w > 0 && (long long)grid_w * grid_h != num_samples) return fail("grid_width * grid_height is not num_samples");
+    if (grid_w > 0 && perm) return fail("a permutation and a grid exclude each other");
+    if (num_samples > GI2D_SAMPLE_MAX || (perm && num_samples > 0x7fffffffLL))
+        return fail("more samples than one launch's grid (or a 32-bit permutation) can hold");
+    if (num_samples == 0) return GI2D_OK;
+    if (n == 0) capacity = 0, rows = 0;  // no gaussian: no list is read
+    if (!points_xy || !out || (rows > 0 && !bins) || (capacity > 0 && rows > 0 && (!gids || !xys || !conics || !colors)))
+        return fail("null pointer");
+    const float f0 = fill_host ? fill_host[0] : 0.f, f1 = fill_host ? fill_host[1] : 0.f, f2 = fill_host ? fill_host[2] : 0.f;
+#ifdef GI2D_SAMPLE_NO_SKIP /* development variant: the walk without the per-wave skip (timing aid) */
+    constexpr bool skip = false;
+#else
+    constexpr bool skip = true;
+#endif
+    // a grid: one workgroup per 16x16 block of the lattice (blocks <= samples); a flat list: 256 samples per workgroup
+    const long long blocks = grid_w > 0 ? (long long)((grid_w + 15) >> 4) * ((grid_h + 15) >> 4) : (num_samples + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail("more samples than one launch's grid can hold");
+#define GI2D_SAMPLE(D, L)                                                                                                \
+    if (grid_w > 0)                                                                                                      \
+        hipLaunchKernelGGL((sample_points_kernel<D, L, true, skip>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, \
+                           n, capacity, tiles_x, tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows,                \
+                           (const float2 *)xys, conics, colors, opac, status, num_samples, (const float2 *)points_xy,   \
+                           perm, grid_w, grid_h, f0, f1, f2, out);                                                       \
+    else                                                                                                                 \
+        hipLaunchKernelGGL((sample_points_kernel<D, L, false, skip>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, \
+                           n, capacity, tiles_x, tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows,                \
+                           (const float2 *)xys, conics, colors, opac, status, num_samples, (const float2 *)points_xy,   \
+                           perm, grid_w, grid_h, f0, f1, f2, out)
+    GI2D_FOR_FORMAT(dtype, layout, GI2D_SAMPLE)
+#undef GI2D_SAMPLE
+    return check_launch(what);
+}
+
+}  // extern "C"

@@ -893,6 +893,51 @@ int gi2d_rasterize_forward_long_as(int num_points, int capacity, int tiles_x, in
 int gi2d_codec_convert(int dtype, int layout, unsigned img_height, unsigned img_width, const float *src_hwc, void *dst,
                        gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ samples of a packed stream (DESIGN.md 3.8 "Samples")
+ * The fitted function at positions of the caller's choosing -- a non-affine warp grid, a scattered batch, the point under
+ * a cursor -- instead of on a lattice.  The gaussians and lists are those of the capacity-free route under the identity
+ * map: gi2d_codec_decode_affine (origin 0, B = I, prefilter 0, at the picture's own size, the stream's radius_clip) ->
+ * gi2d_bin_gaussians, both sync-free, once per stream; then any number of
+ *   gi2d_sample_points      points_xy f32[P,2] (x, y) in source pixel coordinates, pixel centres at integers -> out, P
+ *                          samples in the format.  The leading arguments are gi2d_rasterize_forward_long_as's, with the same
+ *                          meaning (capacity, clamped list bounds and ids, opacities NULL = all 1, status NULL = not looked
+ *                          at).  A position is INSIDE iff 0 <= x <= img_width - 1 and 0 <= y <= img_height - 1 (a NaN or an
+ *                          infinity is outside); an outside sample is `fill_host` (3 floats on the host, NULL = zeros) put
+ *                          through the format's conversion, and no address is formed from its position.  The tile of an
+ *                          inside sample is the tile of its nearest pixel, j = (int)floorf(x + 0.5f), i = (int)floorf(y +
+ *                          0.5f) -> (j >> 4, i >> 4) clamped to the grid (x = 15.5 belongs to pixel 16, tile 1); its value
+ *                          starts from 0 and takes EVERY entry of that tile's list, in list order, with the pair test and
+ *                          arithmetic of gi2d_rasterize_forward_long at (px, py) = (x, y), and is stored clamped to [0, 1]
+ *                          in the format; status[0] < 1 (no intersection at all) makes every inside sample ones.  So on the
+ *                          integer lattice of the picture the samples are gi2d_rasterize_forward_long_as's picture bit for
+ *                          bit; between pixels they are point evaluations of the same sum -- no low-pass (a grid that
+ *                          reduces aliases: that is what overviews and affine views are for), and, like every view, cut
+ *                          by tile boxes, so not continuous across tile borders.  No atomics: a sample's bits depend on
+ *                          the arrays and its position alone, not on its place in the call, its neighbours or `perm`.
+ *                          perm i32[P] (device, NULL = as given): lane s of the launch takes sample perm[s] (entries clamped
+ *                          to [0, P)) and writes ITS slot of out -- the order of the work, never of the output; a
+ *                          permutation that sorts by gi2d_sample_point_keys lets a wave meet one to four tiles.
+ *                          grid_width > 0: the positions are a [grid_height, grid_width, 2] lattice (grid_width *
+ *                          grid_height = P) and a wave takes a 16x4 strip of it, which serves a warp grid without a sort.
+ *                          out: elements of `dtype` with pix = the sample's index and plane = P -- GI2D_LAYOUT_HWC [P,3],
+ *                          GI2D_LAYOUT_CHW [3,P], GI2D_LAYOUT_HWC4 [P,4] (channel 3 = the element of 1.0); for a grid [Ho,
+ *                          Wo,3], [3,Ho,Wo], [Ho,Wo,4].  Aligned to its element size and nothing more.
+ *   gi2d_sample_point_keys  points_xy f32[P,2] -> keys i32[P] (device): the index of the sample's tile, tiles_x * tiles_y
+ *                          for a position outside (those sort to the end).
+ * Both refuse (-1, gi2d_last_error_string set) before any HIP call: an unknown format, a negative size, a NULL array with
+ * num_samples > 0, a tile grid that does not cover the image, grid_width * grid_height != num_samples when grid_width > 0,
+ * perm together with a grid, num_samples beyond what one launch's grid can hold (2^31 - 1 workgroups of 256 samples; with
+ * perm 2^31 - 1 samples).  num_samples = 0 is GI2D_OK without a launch. */
+int gi2d_sample_point_keys(long long num_samples, const float *points_xy, unsigned img_width, unsigned img_height,
+                           int tiles_x, int tiles_y, int32_t *keys, gi2d_stream_t stream);
+int gi2d_sample_points(int num_points, int capacity, int tiles_x, int tiles_y, unsigned img_width, unsigned img_height,
+                       const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, int tile_bins_rows,
+                       const float *xys, const float *conics, const float *colors, const float *opacities,
+                       const int32_t *status, long long num_samples, const float *points_xy,
+                       const int32_t *perm /* NULL: as given */, int grid_width /* 0: a flat list */, int grid_height,
+                       const float *fill_host /* 3 floats, NULL: zeros */, int dtype, int layout, void *out,
+                       gi2d_stream_t stream);
+
 /* ------------------------------------------------------------------ batched decode (DESIGN.md 3.8 "Batches")
  * K streams -> K pictures of ONE size and format in three launches: what the batched fitting calls above do for a fit,
  * for the decoder.  Picture k is, bit for bit, what workspace init + gi2d_codec_decode_bin (view = 0) or

@@ -1,0 +1,173 @@
+"""Sampling time of a packed stream (codec.Field, DESIGN.md 3.8 "Samples") on the two 768x512 fits of decode_time.py
+(N = 5 000 and N = 50 000, covariance model, 12 / 10 / 6 bits), payload on the device: one JSON line.
+
+Per fit, microseconds per call, each next to the route a caller has without samples, timed in the same run in ALTERNATION
+(region 1 of every entry of a row, then region 2 of every entry, ...):
+    field      Decoder.field(stream) alone: per-gaussian kernel under the identity map, binning, the host read of the count
+    crop       the identity lattice of a 224x224 window, as a grid: Field.sample against Decoder.decode(view=codec.Affine) of
+               the same window (the same function on the same lattice; the view shares a workgroup's staged list, sampling
+               stages per wave)
+    warp       a full-size radial-distortion grid [512, 768, 2]: Field.sample against the full decode followed by
+               torch.nn.functional.grid_sample (bilinear) with the same grid -- pixels interpolated, not the function evaluated
+    points     65 536 uniform random positions: Field.sample with and without presort against the full decode followed by an
+               index gather of the nearest pixel
+The conventions are decode_time.py's: a region is a host clock around `reps` back-to-back calls that ends in a device
+synchronise, no event pairs inside it; the figure is the median of five regions.  `version` names the library, so the same
+command under GI2D_LIB=<a development variant> GI2D_ALLOW_DEV_BUILD=1 (make VARIANT=sample_noskip
+EXTRA='-DGI2D_SAMPLE_NO_SKIP -DGI2D_DEV_VARIANT=sample_noskip') gives the rows without the per-wave skip; --streams PATH
+keeps the two fits' streams in an .npz, so that every process of a comparison samples the same streams.
+
+    python tools/sample_time.py [--reps 100] [--streams PATH] [--out-json profiles/sample_time.json] [--trace]
+--trace samples a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for the
+two kernels' own times.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+import zlib
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from gaussianimage_plus_amd import _lib, codec  # noqa: E402
+
+H, W = 512, 768
+DEV = "cuda:0"
+
+
+def streams_of(a):
+    """{N: stream bytes} of the fits -- read from --streams where that file exists, else fitted (and written there)."""
+    if a.streams and os.path.exists(a.streams):
+        z = np.load(a.streams)
+        return {int(k): z[k].tobytes() for k in z.files}
+    from decode_time import fitted
+    out = {}
+    for n in a.sizes:
+        fit, _ = fitted(n, a.iters)
+        fit.compress_wo_ec()
+        out[n] = fit.encode()
+    if a.streams:
+        np.savez(a.streams, **{str(n): np.frombuffer(b, np.uint8) for n, b in out.items()})
+    return out
+
+
+def alternating(row, entries, reps, regions=5):
+    """entries: {key: fn}.  Region r of every entry before region r + 1 of any; row[key + '_us'] = the median."""
+    for fn in entries.values():
+        for _ in range(max(10, reps // 10)):
+            fn()
+    torch.cuda.synchronize()
+    times = {key: [] for key in entries}
+    for _ in range(regions):
+        for key, fn in entries.items():
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+            times[key].append((time.perf_counter() - t0) / reps * 1e6)
+    for key, t in times.items():
+        row[key + "_us"] = round(statistics.median(t), 2)
+        row[key + "_us_range"] = [round(min(t), 2), round(max(t), 2)]
+        row[key + "_us_regions"] = [round(x, 2) for x in t]
+    return row
+
+
+def radial_grid():
+    """Barrel distortion about the picture's centre, every position inside: float32 [H, W, 2] (x, y) and the same grid in
+    grid_sample's normalised coordinates (align_corners=True: -1 and 1 are the centres of the first and last pixel)."""
+    yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
+    cx, cy = (W - 1) / 2, (H - 1) / 2
+    u, v = (xx - cx) / cx, (yy - cy) / cy
+    k = 1.0 - 0.15 * (u * u + v * v) / 2.0
+    pts = torch.stack([cx + cx * u * k, cy + cy * v * k], dim=2).float().to(DEV).contiguous()
+    norm = torch.stack([pts[..., 0] / cx - 1.0, pts[..., 1] / cy - 1.0], dim=2)[None].contiguous()
+    return pts, norm
+
+
+def crc(t):
+    """CRC-32 of a tensor's bytes: two libraries that give the same samples give the same number."""
+    return zlib.crc32(t.contiguous().cpu().numpy().tobytes())
+
+
+def psnr(a, b):
+    return round(10 * torch.log10(1.0 / torch.nn.functional.mse_loss(a.float(), b.float())).item(), 2)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=100)
+    ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[5000, 50000])
+    ap.add_argument("--streams", default=None, metavar="PATH")
+    ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--out-json", default=None, metavar="PATH")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "sample_time.py needs the GPU"
+    res = {"tool": "sample_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
+           "bits": [12, 10, 6], "reps": a.reps, "regions": 5, "sizes": {}}
+    warp, warp_norm = radial_grid()
+    rng = np.random.default_rng(20241021)
+    scattered = torch.from_numpy((rng.random((65536, 2)) * [W - 1, H - 1]).astype(np.float32)).to(DEV)
+    x0, y0, side = 272, 144, 224
+    for n, blob in streams_of(a).items():
+        dec = codec.Decoder(DEV)
+        up = dec.upload(blob)
+        fld = dec.field(up)
+        full = torch.empty(H, W, 3, device=DEV)
+        crop = fld.identity_grid()[y0:y0 + side, x0:x0 + side].contiguous()
+        window = codec.Affine(float(x0), float(y0), 1.0, 0.0, 0.0, 1.0, side, side, 0.0)
+        if a.trace:
+            for _ in range(30):
+                fld.sample(crop), fld.sample(warp), fld.sample(scattered), fld.sample(scattered, presort=False)
+            torch.cuda.synchronize()
+            continue
+        bins = fld.bins.reshape(-1, 2)
+        row = {"gaussians": fld.header["num_points"], "intersections": fld.count,
+               "longest_list": int((bins[:, 1] - bins[:, 0]).max()), "rows": {}}
+        row["rows"]["field"] = alternating({}, {"field": lambda: dec.field(up)}, max(10, a.reps // 4))
+
+        out_crop = torch.empty(side, side, 3, device=DEV)
+        view_crop = torch.empty(side, side, 3, device=DEV)
+        r = {"grid": [side, side], "crc32": crc(fld.sample(crop)), "max_abs_difference": float((fld.sample(crop) - dec.decode(up, view=window)).abs().max())}
+        row["rows"]["crop"] = alternating(r, {"sample": lambda: fld.sample(crop, out=out_crop),
+                                              "affine_view": lambda: dec.decode(up, out=view_crop, view=window)}, a.reps)
+
+        out_warp = torch.empty(H, W, 3, device=DEV)
+
+        def grid_sample_route():
+            img = dec.decode(up, out=full).permute(2, 0, 1)[None]
+            return torch.nn.functional.grid_sample(img, warp_norm, mode="bilinear", padding_mode="border", align_corners=True)
+
+        r = {"grid": [H, W], "crc32": crc(fld.sample(warp)), "psnr_db_against_grid_sample": psnr(fld.sample(warp), grid_sample_route()[0].permute(1, 2, 0))}
+        row["rows"]["warp"] = alternating(r, {"sample": lambda: fld.sample(warp, out=out_warp),
+                                              "sample_presorted": lambda: fld.sample(warp, out=out_warp, presort=True),
+                                              "grid_sample": grid_sample_route}, a.reps)
+
+        out_pts = torch.empty(scattered.shape[0], 3, device=DEV)
+
+        def gather_route():
+            img = dec.decode(up, out=full)
+            idx = (scattered + 0.5).floor().long()
+            return img[idx[:, 1], idx[:, 0]]
+
+        r = {"points": scattered.shape[0], "crc32": crc(fld.sample(scattered)), "psnr_db_against_nearest_pixel": psnr(fld.sample(scattered), gather_route())}
+        assert torch.equal(fld.sample(scattered), fld.sample(scattered, presort=False))
+        row["rows"]["points"] = alternating(r, {"sample_presort": lambda: fld.sample(scattered, out=out_pts),
+                                                "sample_as_given": lambda: fld.sample(scattered, out=out_pts, presort=False),
+                                                "decode_gather": gather_route}, a.reps)
+        res["sizes"][str(n)] = row
+    if not a.trace:
+        print(json.dumps(res))
+        if a.out_json:
+            with open(a.out_json, "w") as f:
+                json.dump(res, f, indent=1)
+                f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
