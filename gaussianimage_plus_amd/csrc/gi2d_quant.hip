@@ -212,14 +212,21 @@ __global__ __launch_bounds__(256) void quant_bwd_finish_kernel(QuantSpecDev sp, 
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        double vs = 0.0, vb = 0.0, nmin = 0.0, nmax = 0.0, qr = 1.0;
+        // vsq = sum over the log channels of v_scale[c] / qr[c]: every log channel has its own scale on the shared range.
+        // Channels of one depth (every layout the reference has) are summed first and divided once.
+        double vs = 0.0, vsq = 0.0, vb = 0.0, nmin = 0.0, nmax = 0.0, qr = 1.0;
         for (int c = 0; c < sp.channels; ++c) {
             if (sp.kind[c] == GI2D_QUANT_LOG) {
+                const double qc = (double)(sp.qmax[c] - sp.qmin[c]);
+                if (qc != qr) {
+                    vsq += vs / qr;
+                    vs = 0.0;
+                    qr = qc;
+                }
                 vs += tot[4 * c];
                 vb += tot[4 * c + 1];
                 nmin += tot[4 * c + 2];
                 nmax += tot[4 * c + 3];
-                qr = (double)(sp.qmax[c] - sp.qmin[c]);
                 v_params[2 * c] = 0.f;
                 v_params[2 * c + 1] = 0.f;
             } else {
@@ -229,8 +236,9 @@ __global__ __launch_bounds__(256) void quant_bwd_finish_kernel(QuantSpecDev sp, 
         }
         // scale = (max - beta) / (qmax - qmin) is part of the graph: beta also receives -v_scale/qr, max +v_scale/qr;
         // torch.min()/max() spread their gradient evenly over every element that attains the extreme
-        extras[0] = nmin > 0.0 ? (float)((vb - vs / qr) / nmin) : 0.f;
-        extras[1] = nmax > 0.0 ? (float)((vs / qr) / nmax) : 0.f;
+        vsq += vs / qr;
+        extras[0] = nmin > 0.0 ? (float)((vb - vsq) / nmin) : 0.f;
+        extras[1] = nmax > 0.0 ? (float)(vsq / nmax) : 0.f;
     }
 }
 

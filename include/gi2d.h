@@ -696,7 +696,8 @@ int gi2d_train_grow(const gi2d_train_state *state, int max_points, int budget_ca
  *   gi2d_quant_backward  given v_dequant: v_x f32[N,C] and v_params f32[C][2] = {v_scale, v_beta} (0 for log channels).
  *                        Follows the autograd graph of the forward as written, including the gradient that reaches the
  *                        elements at the extremes of the log range through beta = min() and scale = (max() - min())/Q
- *                        (spread evenly over ties, as torch.min()/max() do).
+ *                        (spread evenly over ties, as torch.min()/max() do).  Q is each log channel's own qmax - qmin:
+ *                        the range is shared, the scale on it is per channel.
  *   gi2d_quant_compress  forward with the per-channel ranges in `params` (no range pass): compress() :149-152, :243-255
  *   gi2d_quant_decompress code -> value: decompress() :154-156, :257-259
  *   gi2d_quant_half      FakeQuantizationHalf :27-37 (x.half().float()); its backward is the identity
