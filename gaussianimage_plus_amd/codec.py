@@ -77,7 +77,10 @@ tensors the Field owns; Field.sample then evaluates any number of float32 positi
 the tile of a position's nearest pixel, that tile's whole list in list order, the pair arithmetic of the lists route at the
 position itself.  On the integer lattice that is the identity affine view of the lists route bit for bit; between pixels it
 is point evaluation -- no low-pass, so a grid that reduces aliases (Overview and Affine are for that), and, like every view,
-cut by tile boxes, so not continuous across tile borders.
+cut by tile boxes, so not continuous across tile borders.  The fit has an exact derivative in the position, and
+Field.jacobian / Field.sample_vjp (gi2d_sample_points_grad, the same walk with six more sums) give it; Field.sample with
+points that require grad is differentiable in them through the latter -- a warp whose parameters are being estimated, a
+sub-pixel registration, an edge map -- once, no double backward.
 
 Format version 1 (little-endian; INTEGRATION.md "Packed stream" has the record layout):
 
@@ -1328,17 +1331,48 @@ class Field:
         presort: whether the work (never the output) is ordered by tile first -- gi2d_sample_point_keys, torch's stable
         sort on the device, the permutation narrowed to int32.  None sorts a flat list and leaves a grid, whose 16x4
         strips are coherent as they are, alone; True on a grid treats it as a flat list.  A sample's bits do not depend on
-        the choice.  No host wait.  ValueError, before any launch, for anything else."""
-        fmt = _format(dtype, layout)
+        the choice.  No host wait.  ValueError, before any launch, for anything else.
+        Points that require grad (under torch.is_grad_enabled()) make the call differentiable in them: the same launches
+        inside a torch.autograd.Function whose backward is one gated sample_vjp launch -- the exact derivative of the fit,
+        zero in a channel the clamp holds -- reusing the forward's permutation.  Such a call takes dtype None or
+        torch.float32, layout None or "hwc" and no `out` (ValueError otherwise).  No double backward."""
+        if isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled():
+            if dtype not in (None, torch.float32) or layout not in (None, "hwc") or out is not None:
+                raise ValueError("sample: points that require grad take dtype None or torch.float32, layout None or 'hwc' "
+                                 "and no out: only the float32 'hwc' samples are differentiable")
+            return _SampleFunction.apply(points, self, fill, presort)
+        return self._sample(points, out, dtype, layout, fill, presort)[0]
+
+    def _check_points(self, who: str, points, presort) -> Tuple[bool, int, bool]:
+        """The checks on `points` and `presort` every sampling call makes -> (a grid?, P, sort first?)."""
         if (not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() not in (2, 3)
                 or points.shape[-1] != 2):
-            raise ValueError("sample: points must be a float32 tensor of shape [P, 2] or [Ho, Wo, 2], (x, y) last")
+            raise ValueError(f"{who}: points must be a float32 tensor of shape [P, 2] or [Ho, Wo, 2], (x, y) last")
         if points.device != self.dev:
-            raise ValueError(f"sample: points live on {points.device}, the field on {self.dev}")
+            raise ValueError(f"{who}: points live on {points.device}, the field on {self.dev}")
         if not points.is_contiguous():
-            raise ValueError("sample: points must be contiguous")
+            raise ValueError(f"{who}: points must be contiguous")
         if presort is not None and not isinstance(presort, bool):
-            raise ValueError(f"sample: presort {presort!r}: None, True or False")
+            raise ValueError(f"{who}: presort {presort!r}: None, True or False")
+        grid = points.dim() == 3
+        p = points.numel() // 2
+        sort = (not grid) if presort is None else presort
+        if p > (0x7FFFFFFF if sort else 0x7FFFFFFF * 256):
+            raise ValueError(f"{who}: {p} positions are more than one call takes")
+        return grid, p, sort
+
+    def _sorted_by_tile(self, points: torch.Tensor, p: int, st) -> torch.Tensor:
+        """The int32 permutation that orders the positions by tile (outside ones last), stable; no host wait."""
+        keys = torch.empty(p, dtype=torch.int32, device=self.dev)
+        tx, ty = self.tiles
+        _lib.call("gi2d_sample_point_keys", p, C.c_void_p(points.data_ptr()), self.width, self.height, tx, ty,
+                  C.c_void_p(keys.data_ptr()), st)
+        return torch.sort(keys, stable=True).indices.to(torch.int32)
+
+    def _sample(self, points, out, dtype, layout, fill, presort) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """sample's checks and launches -> (the samples, the permutation the work was ordered by or None)."""
+        fmt = _format(dtype, layout)
+        grid, p, sort = self._check_points("sample", points, presort)
         try:
             fill = tuple(fill)
         except TypeError:
@@ -1350,37 +1384,96 @@ class Field:
             fill = tuple(float(np.float32(v)) for v in fill)
         if not all(math.isfinite(v) for v in fill):
             raise ValueError(f"sample: fill {fill}: not finite in float32")
-        grid = points.dim() == 3
-        p = points.numel() // 2
         if grid:
             shape = fmt.shape(points.shape[0], points.shape[1])
         else:
             shape = (3, p) if fmt.layout == "chw" else (p, 4 if fmt.layout == "hwc4" else 3)
         if out is not None:
             _check_out(out, shape, fmt.dtype, self.dev)
-        sort = (not grid) if presort is None else presort
-        if p > (0x7FFFFFFF if sort else 0x7FFFFFFF * 256):
-            raise ValueError(f"sample: {p} positions are more than one call takes")
         if out is None:
             out = torch.empty(shape, dtype=fmt.dtype, device=self.dev)
+        if p == 0:
+            return out, None
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        tx, ty = self.tiles
+        with torch.cuda.device(self.dev) if self.dev.type == "cuda" else contextlib.nullcontext():
+            st = _stream(self.dev)
+            perm = self._sorted_by_tile(points, p, st) if sort else None
+            gw, gh = (points.shape[1], points.shape[0]) if grid and not sort else (0, 0)
+            _lib.call("gi2d_sample_points", self.header["num_points"], self.capacity, tx, ty, self.width, self.height,
+                      ptr(self.ids), ptr(self.bins), tx * ty, ptr(self.xys), ptr(self.conics), ptr(self.colors), None,
+                      ptr(self.status), p, ptr(points), None if perm is None else ptr(perm), gw, gh, (C.c_float * 3)(*fill),
+                      *fmt.ids, ptr(out), st)
+        return out, perm
+
+    def jacobian(self, points: torch.Tensor, presort: Optional[bool] = None, clamped: bool = True,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The derivative of sample(points) in the positions (gi2d_sample_points_grad; DESIGN.md 3.8 "Sample gradients"):
+        float32 [P, 3, 2] or [Ho, Wo, 3, 2], the last axis (d/dx, d/dy) of the channel, in values per source pixel.  It is
+        the exact derivative of the fit's smooth pieces, term by term over the pairs that land -- the cut-off and the
+        tile borders are jumps of the function itself, not slopes.  clamped (the default): a channel whose sum the [0, 1]
+        clamp holds is zero, the derivative of the VALUE sample returns; False: the derivative of the unclamped sum.
+        An outside position (a NaN, an infinity) gives zeros.  points, presort: as in sample; no host wait.  ValueError,
+        before any launch, for anything else."""
+        return self._grad("jacobian", points, None, presort, clamped, out)
+
+    def sample_vjp(self, points: torch.Tensor, v: torch.Tensor, presort: Optional[bool] = None, clamped: bool = True,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The vector-Jacobian product of sample in its positions: float32 [P, 2] or [Ho, Wo, 2], entry s = sum over the
+        channels k, in order, of v[s][k] * jacobian[s][k] -- in one launch, without the Jacobian in memory.  v: float32,
+        contiguous, on the field's device, shaped like sample's float32 "hwc" output for these points ([P, 3] or [Ho, Wo,
+        3]).  What the backward of a differentiable sample calls.  Everything else as in jacobian."""
+        self._check_points("sample_vjp", points, presort)  # (v's shape is read off points)
+        want =(*points.shape[:-1], 3)
+        if (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != want or v.device != self.dev
+                or not v.is_contiguous()):
+            raise ValueError(f"sample_vjp: v must be a contiguous float32 tensor of shape {want} on {self.dev}")
+        return self._grad("sample_vjp", points, v, presort, clamped, out)
+
+    def _grad(self, who: str, points, v, presort, clamped, out, perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """jacobian (v None) and sample_vjp: the checks, the presort (or `perm`, a forward's own) and the one launch."""
+        grid, p, sort = self._check_points(who, points, presort)
+        if not isinstance(clamped, bool):
+            raise ValueError(f"{who}: clamped {clamped!r}: True or False")
+        shape = (*points.shape[:-1], 3, 2) if v is None else (*points.shape[:-1], 2)
+        if out is not None:
+            _check_out(out, shape, torch.float32, self.dev)
+        else:
+            out = torch.empty(shape, dtype=torch.float32, device=self.dev)
         if p == 0:
             return out
         ptr = lambda t: C.c_void_p(t.data_ptr())
         tx, ty = self.tiles
         with torch.cuda.device(self.dev) if self.dev.type == "cuda" else contextlib.nullcontext():
             st = _stream(self.dev)
-            perm = None
-            if sort:
-                keys = torch.empty(p, dtype=torch.int32, device=self.dev)
-                _lib.call("gi2d_sample_point_keys", p, ptr(points), self.width, self.height, tx, ty, ptr(keys), st)
-                perm = torch.sort(keys, stable=True).indices.to(torch.int32)
+            if sort and perm is None:
+                perm = self._sorted_by_tile(points, p, st)
             gw, gh = (points.shape[1], points.shape[0]) if grid and not sort else (0, 0)
-            _lib.call("gi2d_sample_points", self.header["num_points"], self.capacity, tx, ty, self.width, self.height,
+            _lib.call("gi2d_sample_points_grad", self.header["num_points"], self.capacity, tx, ty, self.width, self.height,
                       ptr(self.ids), ptr(self.bins), tx * ty, ptr(self.xys), ptr(self.conics), ptr(self.colors), None,
-                      ptr(self.status), p, ptr(points), None if perm is None else ptr(perm), gw, gh, (C.c_float * 3)(*fill),
-                      *fmt.ids, ptr(out), st)
+                      ptr(self.status), p, ptr(points), ptr(perm) if sort else None, gw, gh, int(clamped),
+                      None if v is None else ptr(v), ptr(out) if v is None else None, None if v is None else ptr(out), st)
         return out
 
+
+class _SampleFunction(torch.autograd.Function):
+    """Field.sample for points that require grad: the forward is sample's own launches, the backward one gated sample_vjp
+    launch on the permutation the forward sorted by.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, points, fld, fill, presort):
+        out, perm = fld._sample(points.detach(), None, None, None, fill, presort)
+        ctx.fld, ctx.presort = fld, presort
+        ctx.save_for_backward(points, *(() if perm is None else (perm,)))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v):
+        points, *perm = ctx.saved_tensors
+        v = v.to(torch.float32).contiguous()
+        grad = ctx.fld._grad("sample_vjp", points.detach(), v, ctx.presort, True, None, perm=perm[0] if perm else None)
+        return grad, None, None, None
 
 class Decoder:
     """Decodes streams on one device.  Payload staging, the fast-path workspace and the status words are kept between
@@ -1970,7 +2063,8 @@ def field(blob, device: Union[str, torch.device] = "cuda:0") -> Field:
 def sample(blob, points: torch.Tensor, device: Optional[Union[str, torch.device]] = None, out: Optional[torch.Tensor] = None,
            dtype=None, layout=None, fill: Sequence[float] = (0.0, 0.0, 0.0), presort: Optional[bool] = None) -> torch.Tensor:
     """One-shot field(blob).sample(points, ...) on the points' device (or `device`): a caller with more than one batch of
-    positions keeps the Field instead -- its lists are built once."""
+    positions keeps the Field instead -- its lists are built once.  Points that require grad make it differentiable in them
+    as Field.sample says (float32 "hwc", no `out`; no double backward)."""
     if not isinstance(points, torch.Tensor):
         raise ValueError("sample: points must be a float32 tensor of shape [P, 2] or [Ho, Wo, 2], (x, y) last")
     return field(blob, points.device if device is None else device).sample(points, out=out, dtype=dtype, layout=layout,

@@ -15,6 +15,8 @@
 //            trips; any order is correct.  Per staged batch the wave keeps only the entries whose alpha >= 1/255 box
 //            (cull_extent) meets the bounding box of the served lanes' positions -- a ballot compaction at the staging
 //            store that preserves list order; a dropped entry fails the pair test at every served sample.
+//   grads    sample_points_grad_kernel: the same walk with six more sums per lane, the derivative of the three channels
+//            in the position -- stored as the Jacobian [P,3,2] or contracted with a caller's v_out into the VJP [P,2].
 //
 // A sample's bits depend on the stream and its position alone: no atomics, and neither its place in the call nor its
 // neighbours enter its sum.  Nothing is read through an address formed from unchecked content: the tile comes from a
@@ -204,6 +206,178 @@ __global__ __launch_bounds__(256) void sample_points_kernel(
                                  pixel_convert<DTYPE>(1.f), (size_t)s, (size_t)num_samples, reinterpret_cast<T *>(out_));
 }
 
+// ---- the derivative of a sample in its position (include/gi2d.h "samples"; DESIGN.md 3.8 "Samples", "Sample gradients")
+// One staged entry on this lane's sample: sample_pair, operation for operation -- so o0..o2 carry the bits the value
+// kernel stores and the same pairs land -- plus the pair's six derivative terms.  With dx = gx - px the derivative of
+// alpha = opac exp(-sigma) in px is alpha (a dx + b dy); from the staged log2-scaled conic the two linear forms are
+//     lx = 2 ha dx + hb dy = log2(e) (a dx + b dy),     ly = hb dx + 2 hc dy = log2(e) (b dx + c dy)
+// and the factor ln 2 waits for the epilogue.  CLAMP: an entry on which min(1, .) binds (alpha above 1, or a NaN) is
+// flat there and adds nothing.
+template <bool CLAMP>
+__device__ __forceinline__ void sample_pair_grad(const float4 A, const float4 B, const float2 Cc, float px, float py,
+                                                 float &o0, float &o1, float &o2, float (&d)[6]) {
+    const unsigned lim = (unsigned)__float_as_int(Cc.y);
+    const float dy = A.y - py;
+    const float hcdy = B.x * dy;
+    const float bdy = A.w * dy, cdy2 = __builtin_fmaf(hcdy, dy, 0.f);
+    const float dx = A.x - px;
+    const float sig = __builtin_fmaf(dx, __builtin_fmaf(A.z, dx, bdy), cdy2);
+    const float tt = B.y * pair_vis(sig);
+    const bool ok = CLAMP ? pair_lands_odd(sig, tt, lim) : pair_lands(sig, lim);
+    float am = ok ? tt : 0.f;
+    if (CLAMP) am = fminf(1.f, am);
+    o0 = __builtin_fmaf(B.z, am, o0);
+    o1 = __builtin_fmaf(B.w, am, o1);
+    o2 = __builtin_fmaf(Cc.x, am, o2);
+    const float lx = __builtin_fmaf(2.f * A.z, dx, bdy);
+    const float ly = __builtin_fmaf(A.w, dx, 2.f * hcdy);
+    // a select, not a product with am: the forms of a pair that does not land may be infinite, and 0 * inf must not enter
+    const bool moves = CLAMP ? (ok && tt <= 1.f) : ok;
+    const float ax = moves ? tt * lx : 0.f, ay = moves ? tt * ly : 0.f;
+    d[0] = __builtin_fmaf(B.z, ax, d[0]);
+    d[1] = __builtin_fmaf(B.z, ay, d[1]);
+    d[2] = __builtin_fmaf(B.w, ax, d[2]);
+    d[3] = __builtin_fmaf(B.w, ay, d[3]);
+    d[4] = __builtin_fmaf(Cc.x, ax, d[4]);
+    d[5] = __builtin_fmaf(Cc.x, ay, d[5]);
+}
+
+// The walk below -- lane -> sample, the waterfall over the wave's tiles, the staging, the ballot compaction under SKIP -- is
+// sample_points_kernel's, line for line: ITS TWIN, to be changed together with it.  (Kept as a copy, not factored out,
+// so that the value kernel's device code stays what it was; DESIGN.md 3.8 "Sample gradients".)  Six more accumulators,
+// d[2 k + 0 | 1] = d o_k / d (px | py) over ln 2, and another epilogue:
+//   VJP = false   out = jacobian f32[P,3,2]: the six floats of sample s, 24 contiguous bytes, as three float2 stores
+//   VJP = true    out = v_points f32[P,2]: (sum_k v_out[s][k] d[k][x], sum_k v_out[s][k] d[k][y]), one float2 store
+// gate: channel k counts only where clamp01(o_k) == o_k, i.e. where the value the value kernel stored is the unclamped
+// sum (false for a NaN); outside samples and a field without a single intersection give zeros.
+template <bool GRID, bool SKIP, bool VJP>
+__global__ __launch_bounds__(256) void sample_points_grad_kernel(
+    int n, int capacity, int tiles_x, int tiles_y, int img_w, int img_h, const int32_t *__restrict__ gids_sorted,
+    const int2 *__restrict__ tile_bins, int tile_bins_rows, const float2 *__restrict__ xys,
+    const float *__restrict__ conics, const float *__restrict__ colors, const float *__restrict__ opacities,
+    const int32_t *__restrict__ status, long long num_samples, const float2 *__restrict__ points,
+    const int32_t *__restrict__ perm, int grid_w, int grid_h, int gate, const float *__restrict__ v_out,
+    float2 *__restrict__ out) {
+    __shared__ SampleLds lds[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    SampleLds &sm = lds[wv];
+
+    // ---- lane -> sample
+    bool valid;
+    long long s;
+    if (GRID) {
+        const int blocks_x = (grid_w + 15) >> 4;
+        const int bx = (int)(blockIdx.x % (unsigned)blocks_x), by = (int)(blockIdx.x / (unsigned)blocks_x);
+        const int col = bx * 16 + (lane & 15), row = by * 16 + wv * 4 + (lane >> 4);
+        valid = col < grid_w && row < grid_h;
+        s = (long long)row * grid_w + col;
+    } else {
+        s = ((long long)blockIdx.x * 4 + wv) * 64 + lane;
+        valid = s < num_samples;
+        if (valid && perm != nullptr) s = min(max((long long)perm[s], 0ll), num_samples - 1);
+    }
+    float px = 0.f, py = 0.f;
+    if (valid) {
+        const float2 p = points[s];
+        px = p.x, py = p.y;
+    }
+    bool inside;
+    const int key = sample_key(px, py, img_w, img_h, tiles_x, tiles_y, inside);
+    inside = inside && valid;
+
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+    float d[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const bool nothing = status != nullptr && status[0] < 1;  // not a single intersection: a constant, its derivative zero
+
+    // ---- the tiles this wave holds, one after the other (wave-uniform: `todo` is a ballot)
+    unsigned long long todo = nothing ? 0ull : __ballot(inside);
+    while (todo != 0ull) {
+        const int t = wave_read_lane(key, __ffsll((long long)todo) - 1);  // a scalar: list bounds and staging are uniform
+        const bool mine = inside && key == t;  // (all of them unserved: the lanes of a tile are served together)
+        todo &= ~__ballot(mine);
+        int2 range = make_int2(0, 0);
+        if (t < tile_bins_rows) range = tile_bins[t];
+        const int start = min(max(range.x, 0), capacity);
+        const int end = min(max(range.y, start), capacity);
+        if (start >= end) continue;
+        float bx0 = 0.f, bx1 = 0.f, by0 = 0.f, by1 = 0.f;  // what the served lanes' positions span
+        if (SKIP) {
+            const float inf = __int_as_float(0x7f800000);
+            bx0 = wave_min_dpp(mine ? px : inf), bx1 = wave_max_dpp(mine ? px : -inf);
+            by0 = wave_min_dpp(mine ? py : inf), by1 = wave_max_dpp(mine ? py : -inf);
+        }
+        int g_next = start + lane < end ? gids_sorted[start + lane] : 0;  // (one batch ahead of its use)
+        for (int base = start; base < end; base += GI2D_SAMPLE_BATCH) {
+            const int m = min(GI2D_SAMPLE_BATCH, end - base);
+            const int g = min(max(g_next, 0), n - 1);
+            if (base + GI2D_SAMPLE_BATCH + lane < end) g_next = gids_sorted[base + GI2D_SAMPLE_BATCH + lane];
+            bool keep = false, clamp = false;
+            float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A;
+            float2 Cc = make_float2(0.f, 0.f);
+            if (lane < m) {
+                const float2 xy = xys[g];
+                const float a = conics[3 * g], b = conics[3 * g + 1], c = conics[3 * g + 2];
+                const float op = opacities ? opacities[g] : 1.f;
+                const AlphaRule ar = alpha_rule(xy.x, xy.y, a, b, c, op);
+                const ConicS sc = scale_conic(a, b, c);
+                clamp = ar.clamp;
+                A = make_float4(xy.x, xy.y, sc.ha, sc.hb);
+                B = make_float4(sc.hc, op, colors[3 * g], colors[3 * g + 1]);
+                Cc = make_float2(colors[3 * g + 2], __int_as_float((int)ar.lim));
+                keep = true;
+                if (SKIP) {
+                    float hx, hy;
+                    cull_extent(xy.x, xy.y, a, b, c, op, hx, hy);
+                    // hx < 0: can never land; GI2D_CULL_FULL: no finite box, every sample is evaluated
+                    keep = hx >= 0.f && (hx >= GI2D_CULL_FULL || (xy.y - hy <= by1 && xy.y + hy >= by0 &&
+                                                                  xy.x - hx <= bx1 && xy.x + hx >= bx0));
+                }
+            }
+            const bool clamp_any = __ballot(clamp) != 0ull;
+            const unsigned long long mask = __ballot(keep);
+            const int kept = __popcll(mask);
+            __builtin_amdgcn_wave_barrier();  // the block may still be read by the batch before this one
+            if (keep) {  // compacted in list order
+                const int slot = __popcll(mask & lanemask_lt());
+                sm.a[slot] = A, sm.b[slot] = B, sm.c[slot] = Cc;
+            }
+            __builtin_amdgcn_wave_barrier();  // wave-private block: DS ops of one wave complete in order
+            if (mine) {
+                if (clamp_any) {
+#pragma unroll 4
+                    for (int k = 0; k < kept; ++k) sample_pair_grad<true>(sm.a[k], sm.b[k], sm.c[k], px, py, o0, o1, o2, d);
+                } else {
+#pragma unroll 4
+                    for (int k = 0; k < kept; ++k) sample_pair_grad<false>(sm.a[k], sm.b[k], sm.c[k], px, py, o0, o1, o2, d);
+                }
+            }
+        }
+    }
+
+    // ---- ln 2 once per sample, the gate, the stores (an outside sample and a field of nothing kept their zeros)
+    if (!valid) return;
+    const float ln2 = 0.6931471805599453f;
+    const bool g0 = !gate || clamp01(o0) == o0, g1 = !gate || clamp01(o1) == o1, g2 = !gate || clamp01(o2) == o2;
+    const float d0x = g0 ? d[0] * ln2 : 0.f, d0y = g0 ? d[1] * ln2 : 0.f;
+    const float d1x = g1 ? d[2] * ln2 : 0.f, d1y = g1 ? d[3] * ln2 : 0.f;
+    const float d2x = g2 ? d[4] * ln2 : 0.f, d2y = g2 ? d[5] * ln2 : 0.f;
+    if (VJP) {
+        const float v0 = v_out[3 * s], v1 = v_out[3 * s + 1], v2 = v_out[3 * s + 2];
+        float vx = 0.f, vy = 0.f;
+        // channel order; a channel the gate closes, an outside sample and a field of nothing leave their term out
+        // whatever v_out holds there, a NaN included
+        const bool live = inside && !nothing;
+        if (live && g0) vx = __builtin_fmaf(v0, d0x, vx), vy = __builtin_fmaf(v0, d0y, vy);
+        if (live && g1) vx = __builtin_fmaf(v1, d1x, vx), vy = __builtin_fmaf(v1, d1y, vy);
+        if (live && g2) vx = __builtin_fmaf(v2, d2x, vx), vy = __builtin_fmaf(v2, d2y, vy);
+        out[s] = make_float2(vx, vy);
+    } else {
+        out[3 * s] = make_float2(d0x, d0y);
+        out[3 * s + 1] = make_float2(d1x, d1y);
+        out[3 * s + 2] = make_float2(d2x, d2y);
+    }
+}
+
 }  // namespace gi2d
 
 using namespace gi2d;
@@ -281,6 +455,58 @@ int gi2d_sample_points(int n, int capacity, int tiles_x, int tiles_y, unsigned w
                            perm, grid_w, grid_h, f0, f1, f2, out)
     GI2D_FOR_FORMAT(dtype, layout, GI2D_SAMPLE)
 #undef GI2D_SAMPLE
+    return check_launch(what);
+}
+
+int gi2d_sample_points_grad(int n, int capacity, int tiles_x, int tiles_y, unsigned w, unsigned h, const int32_t *gids,
+                            const int32_t *bins, int rows, const float *xys, const float *conics, const float *colors,
+                            const float *opac, const int32_t *status, long long num_samples, const float *points_xy,
+                            const int32_t *perm, int grid_w, int grid_h, int gate, const float *v_out, float *jacobian,
+                            float *v_points, gi2d_stream_t st) {
+    const char *what = "sample points grad";
+    const auto fail = [&](const char *why) {
+        set_error((std::string(what) + ": " + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    };
+    // (the refusals of gi2d_sample_points, in its order, without the format's)
+    if (n < 0 || capacity < 0 || tiles_x < 0 || tiles_y < 0 || rows < 0 || num_samples < 0 || grid_w < 0 || grid_h < 0)
+        return fail("negative size");
+    if (capacity > 0x7fffffff - GI2D_SAMPLE_BATCH) return fail("capacity too large for 32-bit list positions");
+    if (!sample_grid_covers(tiles_x, tiles_y, w, h)) return fail("tile grid does not cover the image");
+    if ((long long)tiles_x * tiles_y >= 0x7fffffffLL || w > 0x7fffffffu || h > 0x7fffffffu) return fail("tile grid too large");
+    if (grid_w > 0 && (long long)grid_w * grid_h != num_samples) return fail("grid_width * grid_height is not num_samples");
+    if (grid_w > 0 && perm) return fail("a permutation and a grid exclude each other");
+    if (num_samples > GI2D_SAMPLE_MAX || (perm && num_samples > 0x7fffffffLL))
+        return fail("more samples than one launch's grid (or a 32-bit permutation) can hold");
+    const char *one = "exactly one of jacobian / v_points, v_points together with v_out";
+    if ((jacobian && v_points) || (v_points && !v_out) || (jacobian && v_out)) return fail(one);
+    float *out = v_out ? v_points : jacobian;
+    if (((uintptr_t)out & 7u) != 0) return fail("jacobian / v_points must be aligned to 8 bytes");
+    if (num_samples == 0) return GI2D_OK;
+    if (!out) return fail(one);  // (like every NULL array: only a call with samples misses it)
+    if (n == 0) capacity = 0, rows = 0;  // no gaussian: no list is read
+    if (!points_xy || (rows > 0 && !bins) || (capacity > 0 && rows > 0 && (!gids || !xys || !conics || !colors)))
+        return fail("null pointer");
+#ifdef GI2D_SAMPLE_NO_SKIP /* development variant: the walk without the per-wave skip (timing aid) */
+    constexpr bool skip = false;
+#else
+    constexpr bool skip = true;
+#endif
+    const long long blocks = grid_w > 0 ? (long long)((grid_w + 15) >> 4) * ((grid_h + 15) >> 4) : (num_samples + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail("more samples than one launch's grid can hold");
+#define GI2D_SAMPLE_GRAD(G, V)                                                                                           \
+    hipLaunchKernelGGL((sample_points_grad_kernel<G, skip, V>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, n, \
+                       capacity, tiles_x, tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows, (const float2 *)xys,  \
+                       conics, colors, opac, status, num_samples, (const float2 *)points_xy, perm, grid_w, grid_h,       \
+                       gate != 0 ? 1 : 0, v_out, (float2 *)out)
+    if (grid_w > 0) {
+        if (v_out) GI2D_SAMPLE_GRAD(true, true);
+        else GI2D_SAMPLE_GRAD(true, false);
+    } else {
+        if (v_out) GI2D_SAMPLE_GRAD(false, true);
+        else GI2D_SAMPLE_GRAD(false, false);
+    }
+#undef GI2D_SAMPLE_GRAD
     return check_launch(what);
 }
 

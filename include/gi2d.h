@@ -928,7 +928,27 @@ int gi2d_codec_convert(int dtype, int layout, unsigned img_height, unsigned img_
  * Both refuse (-1, gi2d_last_error_string set) before any HIP call: an unknown format, a negative size, a NULL array with
  * num_samples > 0, a tile grid that does not cover the image, grid_width * grid_height != num_samples when grid_width > 0,
  * perm together with a grid, num_samples beyond what one launch's grid can hold (2^31 - 1 workgroups of 256 samples; with
- * perm 2^31 - 1 samples).  num_samples = 0 is GI2D_OK without a launch. */
+ * perm 2^31 - 1 samples).  num_samples = 0 is GI2D_OK without a launch.
+ *   gi2d_sample_points_grad the derivative of those samples in their positions, the arguments of gi2d_sample_points up to
+ *                          grid_height with the same meaning.  For an inside position p = (px, py), over the same list in
+ *                          the same order, with dx = gx - px, dy = gy - py and alpha = opac exp(-sigma): a pair that lands
+ *                          (the very test of gi2d_sample_points, on the same fp32 sigma) adds colour_k alpha (a dx + b dy)
+ *                          to d o_k / d px and colour_k alpha (b dx + c dy) to d o_k / d py; a pair that does not land, or
+ *                          on which min(1, .) binds (opac > 1 or a non-finite gaussian), adds nothing -- the derivative
+ *                          of the smooth pieces, term by term; the cut-off and the tile borders are jumps of the function
+ *                          itself.  gate != 0: channel k is zero unless its unclamped sum o_k satisfies clamp01(o_k) ==
+ *                          o_k (false for a NaN) -- o_k is formed by the operations of gi2d_sample_points in its order,
+ *                          so the gate agrees with the value that call stored, bit for bit.  Outside positions (NaN,
+ *                          infinities) and status[0] < 1 give zeros.  Exactly one of
+ *                            v_out == NULL: jacobian f32[P,3,2] (device), [s][k] = (d o_k / d px, d o_k / d py);
+ *                            v_out f32[P,3] (device): v_points f32[P,2], [s] = sum over k, in channel order, of v_out[s][k]
+ *                              times row [s][k] of that Jacobian (a closed channel and an outside sample leave v_out unread
+ *                              in effect: their terms are left out, not multiplied by zero) -- the vector-Jacobian
+ *                              product autograd asks for.
+ *                          jacobian / v_points are aligned to 8 bytes.  No atomics: the bits depend on the arrays and the
+ *                          position alone.  Refusals: those of gi2d_sample_points without the format's, under the prefix
+ *                          "sample points grad"; a misaligned output; and anything but exactly one of jacobian / v_points,
+ *                          v_points together with v_out.  num_samples = 0 is GI2D_OK without a launch. */
 int gi2d_sample_point_keys(long long num_samples, const float *points_xy, unsigned img_width, unsigned img_height,
                            int tiles_x, int tiles_y, int32_t *keys, gi2d_stream_t stream);
 int gi2d_sample_points(int num_points, int capacity, int tiles_x, int tiles_y, unsigned img_width, unsigned img_height,
@@ -938,6 +958,14 @@ int gi2d_sample_points(int num_points, int capacity, int tiles_x, int tiles_y, u
                        const int32_t *perm /* NULL: as given */, int grid_width /* 0: a flat list */, int grid_height,
                        const float *fill_host /* 3 floats, NULL: zeros */, int dtype, int layout, void *out,
                        gi2d_stream_t stream);
+int gi2d_sample_points_grad(int num_points, int capacity, int tiles_x, int tiles_y, unsigned img_width, unsigned img_height,
+                            const int32_t *gaussian_ids_sorted, const int32_t *tile_bins, int tile_bins_rows,
+                            const float *xys, const float *conics, const float *colors, const float *opacities,
+                            const int32_t *status, long long num_samples, const float *points_xy,
+                            const int32_t *perm /* NULL: as given */, int grid_width /* 0: a flat list */, int grid_height,
+                            int gate, const float *v_out /* f32[P,3], or NULL */,
+                            float *jacobian /* f32[P,3,2]: iff v_out == NULL */,
+                            float *v_points /* f32[P,2]: iff v_out != NULL */, gi2d_stream_t stream);
 
 /* ------------------------------------------------------------------ batched decode (DESIGN.md 3.8 "Batches")
  * K streams -> K pictures of ONE size and format in three launches: what the batched fitting calls above do for a fit,

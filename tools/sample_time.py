@@ -17,9 +17,19 @@ command under GI2D_LIB=<a development variant> GI2D_ALLOW_DEV_BUILD=1 (make VARI
 EXTRA='-DGI2D_SAMPLE_NO_SKIP -DGI2D_DEV_VARIANT=sample_noskip') gives the rows without the per-wave skip; --streams PATH
 keeps the two fits' streams in an .npz, so that every process of a comparison samples the same streams.
 
-    python tools/sample_time.py [--reps 100] [--streams PATH] [--out-json profiles/sample_time.json] [--trace]
+    python tools/sample_time.py [--reps 100] [--streams PATH] [--out-json profiles/sample_time.json] [--trace] [--grad]
 --trace samples a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for the
 two kernels' own times.
+
+--grad times the derivative in the positions instead (DESIGN.md 3.8 "Sample gradients"; profiles/sample_grad_time.json), a
+run of its own with the same region discipline, on the warp grid and the 65 536 points:
+    sample_forward            Field.sample alone, the yardstick of the rows beside it
+    sample_forward_backward   Field.sample with points that require grad, then out.backward(w): autograd's route
+    sample_vjp                Field.sample_vjp(points, w) alone: the backward's one launch (with its presort on the points)
+    jacobian                  Field.jacobian(points) alone
+    grid_sample_forward_backward   the only other route to a gradient in the positions: full decode, then
+                              torch.nn.functional.grid_sample (bilinear) with a grid that requires grad, then backward(w)
+                              -- the slope between two neighbouring pixels, not the slope of the fit
 """
 import argparse
 import json
@@ -98,6 +108,44 @@ def psnr(a, b):
     return round(10 * torch.log10(1.0 / torch.nn.functional.mse_loss(a.float(), b.float())).item(), 2)
 
 
+def grad_rows(dec, up, fld, full, warp, warp_norm, scattered, reps):
+    """The --grad rows of one fit: {"warp": ..., "points": ...}."""
+    cx, cy = (W - 1) / 2, (H - 1) / 2
+    scattered_norm = torch.stack([scattered[:, 0] / cx - 1.0, scattered[:, 1] / cy - 1.0], dim=1)[None, None].contiguous()
+    rows = {}
+    for name, pts, norm in (("warp", warp, warp_norm), ("points", scattered, scattered_norm)):
+        gen = torch.Generator(device=DEV).manual_seed(7)
+        w = torch.randn((*pts.shape[:-1], 3), device=DEV, generator=gen)
+        w_nchw = (w.permute(2, 0, 1) if pts.dim() == 3 else w.t()[:, None, :])[None].contiguous()
+        p_req, norm_req = pts.clone().requires_grad_(True), norm.clone().requires_grad_(True)
+        out_val = torch.empty((*pts.shape[:-1], 3), device=DEV)
+        out_vjp, out_jac = torch.empty_like(pts), torch.empty((*pts.shape[:-1], 3, 2), device=DEV)
+
+        def autograd_route():
+            p_req.grad = None
+            fld.sample(p_req).backward(w)
+
+        def grid_sample_route():
+            norm_req.grad = None
+            img = dec.decode(up, out=full).permute(2, 0, 1)[None]
+            torch.nn.functional.grid_sample(img, norm_req, mode="bilinear", padding_mode="border",
+                                            align_corners=True).backward(w_nchw)
+
+        autograd_route(), grid_sample_route()
+        assert torch.equal(p_req.grad, fld.sample_vjp(pts, w))
+        # grid_sample's gradient is in normalised coordinates: per source pixel it is that over (cx, cy)
+        theirs = norm_req.grad.reshape(-1, 2) / torch.tensor([cx, cy], device=DEV)
+        ours = p_req.grad.reshape(-1, 2)
+        r = {"shape": list(pts.shape[:-1]), "crc32_vjp": crc(p_req.grad), "crc32_jacobian": crc(fld.jacobian(pts)),
+             "cosine_with_grid_sample_gradient": round(float(torch.nn.functional.cosine_similarity(ours.flatten(), theirs.flatten(), dim=0)), 4)}
+        rows[name] = alternating(r, {"sample_forward": lambda: fld.sample(pts, out=out_val),
+                                     "sample_forward_backward": autograd_route,
+                                     "sample_vjp": lambda: fld.sample_vjp(pts, w, out=out_vjp),
+                                     "jacobian": lambda: fld.jacobian(pts, out=out_jac),
+                                     "grid_sample_forward_backward": grid_sample_route}, reps)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=100)
@@ -105,10 +153,11 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[5000, 50000])
     ap.add_argument("--streams", default=None, metavar="PATH")
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--grad", action="store_true")
     ap.add_argument("--out-json", default=None, metavar="PATH")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "sample_time.py needs the GPU"
-    res = {"tool": "sample_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
+    res = {"tool": "sample_time --grad" if a.grad else "sample_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
            "bits": [12, 10, 6], "reps": a.reps, "regions": 5, "sizes": {}}
     warp, warp_norm = radial_grid()
     rng = np.random.default_rng(20241021)
@@ -124,11 +173,18 @@ def main():
         if a.trace:
             for _ in range(30):
                 fld.sample(crop), fld.sample(warp), fld.sample(scattered), fld.sample(scattered, presort=False)
+                if a.grad:
+                    fld.jacobian(warp), fld.jacobian(scattered)
+                    fld.sample_vjp(warp, torch.ones(H, W, 3, device=DEV)), fld.sample_vjp(scattered, torch.ones(65536, 3, device=DEV))
             torch.cuda.synchronize()
             continue
         bins = fld.bins.reshape(-1, 2)
         row = {"gaussians": fld.header["num_points"], "intersections": fld.count,
                "longest_list": int((bins[:, 1] - bins[:, 0]).max()), "rows": {}}
+        if a.grad:
+            row["rows"] = grad_rows(dec, up, fld, full, warp, warp_norm, scattered, a.reps)
+            res["sizes"][str(n)] = row
+            continue
         row["rows"]["field"] = alternating({}, {"field": lambda: dec.field(up)}, max(10, a.reps // 4))
 
         out_crop = torch.empty(side, side, 3, device=DEV)
