@@ -80,7 +80,11 @@ is point evaluation -- no low-pass, so a grid that reduces aliases (Overview and
 cut by tile boxes, so not continuous across tile borders.  The fit has an exact derivative in the position, and
 Field.jacobian / Field.sample_vjp (gi2d_sample_points_grad, the same walk with six more sums) give it; Field.sample with
 points that require grad is differentiable in them through the latter -- a warp whose parameters are being estimated, a
-sub-pixel registration, an edge map -- once, no double backward.
+sub-pixel registration, an edge map -- once, no double backward.  Where a warp reduces, a sample can carry a low-pass of
+its own: Decoder.field(stream, max_filter=v) widens the lists by the prefilter (v, 0, v) and keeps every gaussian's
+covariance (gi2d_codec_decode_field), and Field.sample(points, footprint=) then evaluates each (sample, gaussian) pair with
+covariance S + Q and colour * sqrt(det S / det(S + Q)) for the sample's own variance Q (gi2d_sample_points_filtered,
+csrc/gi2d_sample_filtered.hip); grid_footprints derives Q from a sampling grid.
 
 Format version 1 (little-endian; INTEGRATION.md "Packed stream" has the record layout):
 
@@ -1300,14 +1304,91 @@ def _stream_args(h, payload: torch.Tensor) -> tuple:
             h["fixed_payload_bytes"], h["clip_coe"])
 
 
+def _checked_max_filter(who: str, max_filter) -> float:
+    """max_filter as the float32 value the kernels receive: 0.0, or a variance in (0, MAX_AFFINE_PREFILTER]."""
+    _finite_numbers(who, max_filter=max_filter)
+    v = float(np.float32(max_filter))
+    if not 0.0 <= v <= MAX_AFFINE_PREFILTER or (v == 0.0 and float(max_filter) != 0.0):
+        raise ValueError(f"{who}: max_filter {float(max_filter)}: 0 (no filtered samples) or a variance in 0 .. "
+                         f"{MAX_AFFINE_PREFILTER:g} source pixels^2")
+    return v
+
+
+def grid_footprints(grid: torch.Tensor, limit: float) -> torch.Tensor:
+    """The footprints a sampling grid asks for (DESIGN.md 3.8 "Filtered samples"): float32 [Ho, Wo, 2] positions, (x, y)
+    last, on any device -> float32 [Ho, Wo, 3], (qxx, qxy, qyy) per sample in source pixels^2, for Field.sample(grid,
+    footprint=...).  Torch operations only, in float64 on the float32 positions:
+        J = [dp/dj, dp/di]   central differences inside the grid, one-sided ones on its border rows and columns (an axis
+                             of length 1 has the derivative 0)
+        Q = clip(J J^T - I) / 12, the eigenvalues clipped at 0: the variance of a box one output pixel wide, less the box
+                             the source pixel already is -- for a constant J = M it is M P M^T with Affine's default P
+                             wherever no eigenvalue is clipped or M is diagonal; where the grid magnifies, Q = 0
+        trace(Q) > limit:    Q * (limit / trace)
+    rounded to float32 so that every footprint passes the admission rule of gi2d_sample_points_filtered for max_filter =
+    limit IN fp32: qxy moves towards 0, one float32 at a time, where rounding leaves qxx * qyy < qxy * qxy, after one more
+    scaling by 1 - 2^-22 where the float32 sum exceeds the limit.  limit: a variance in (0, 4]."""
+    limit = _checked_max_filter("grid_footprints", limit)
+    if limit <= 0.0:
+        raise ValueError("grid_footprints: limit must be above 0")
+    if (not isinstance(grid, torch.Tensor) or grid.dtype != torch.float32 or grid.dim() != 3 or grid.shape[-1] != 2
+            or grid.shape[0] < 1 or grid.shape[1] < 1):
+        raise ValueError("grid_footprints: grid must be a float32 tensor of shape [Ho, Wo, 2], (x, y) last")
+    p = grid.detach().to(torch.float64)
+
+    def diff(axis: int) -> torch.Tensor:
+        n = p.shape[axis]
+        if n == 1:
+            return torch.zeros_like(p)
+        lo, hi = p.narrow(axis, 0, n - 1), p.narrow(axis, 1, n - 1)
+        first, last = (hi - lo).narrow(axis, 0, 1), (hi - lo).narrow(axis, n - 2, 1)
+        if n == 2:
+            return torch.cat((first, last), axis)
+        mid = (p.narrow(axis, 2, n - 2) - p.narrow(axis, 0, n - 2)) * 0.5
+        return torch.cat((first, mid, last), axis)
+
+    dj, di = diff(1), diff(0)
+    axx = dj[..., 0] * dj[..., 0] + di[..., 0] * di[..., 0] - 1.0
+    axy = dj[..., 0] * dj[..., 1] + di[..., 0] * di[..., 1]
+    ayy = dj[..., 1] * dj[..., 1] + di[..., 1] * di[..., 1] - 1.0
+    # the symmetric 2x2 eigen-decomposition in closed form: A = l1 P1 + l2 (I - P1), P1 = (A - l2 I) / (l1 - l2)
+    mean, half = (axx + ayy) * 0.5, (axx - ayy) * 0.5
+    d = torch.sqrt(half * half + axy * axy)
+    l1, l2 = torch.clamp(mean + d, min=0.0), torch.clamp(mean - d, min=0.0)
+    safe = torch.where(d > 0.0, d, torch.ones_like(d))
+    p1xx = torch.where(d > 0.0, (half + d) / (2.0 * safe), torch.ones_like(d))
+    p1xy = torch.where(d > 0.0, axy / (2.0 * safe), torch.zeros_like(d))
+    p1yy = torch.where(d > 0.0, (d - half) / (2.0 * safe), torch.ones_like(d))
+    l2_iso = torch.where(d > 0.0, l2, torch.zeros_like(d))  # (d == 0: A = l1 I, carried by P1 = I alone)
+    qxx = (l1 * p1xx + l2_iso * (1.0 - p1xx)) / 12.0
+    qxy = (l1 - l2_iso) * p1xy / 12.0
+    qyy = (l1 * p1yy + l2_iso * (1.0 - p1yy)) / 12.0
+    trace = qxx + qyy
+    scale = torch.where(trace > limit, limit / torch.where(trace > limit, trace, torch.ones_like(trace)), torch.ones_like(trace))
+    q = torch.stack((torch.clamp(qxx * scale, min=0.0), qxy * scale, torch.clamp(qyy * scale, min=0.0)), dim=-1).to(torch.float32)
+    over = (q[..., 0] + q[..., 2]) > limit
+    q = torch.where(over[..., None], q * float(np.float32(1.0 - 2.0 ** -22)), q)
+    zero = torch.zeros((), dtype=torch.float32, device=q.device)
+    while True:
+        bad = q[..., 0] * q[..., 2] < q[..., 1] * q[..., 1]
+        if not bool(bad.any()):
+            break
+        q[..., 1] = torch.where(bad, torch.nextafter(q[..., 1], zero), q[..., 1])
+    return q.contiguous()
+
+
 class Field:
     """The fitted function of ONE stream, ready to be sampled at any position (Decoder.field makes it; DESIGN.md 3.8
     "Samples"): the five per-gaussian arrays of the lists route under the identity map and the tile lists of the picture's
     own 16x16 tile grid, in tensors of its own -- no later call of the Decoder touches them.  header: the parsed stream;
-    width, height: the picture's size; count: the number of (gaussian, tile) intersections; capacity: entries `ids` holds."""
+    width, height: the picture's size; count: the number of (gaussian, tile) intersections; capacity: entries `ids` holds.
+    max_filter: 0.0, or the largest footprint variance (source pixels^2) its samples may ask for (Decoder.field; DESIGN.md
+    3.8 "Filtered samples"): the lists are then those of the identity view widened by that prefilter, `covs` holds every
+    gaussian's covariance before it, and `colors` / `conics` are the un-prefiltered ones."""
 
     def __init__(self, dev: torch.device, header: Dict[str, object], geometry: Sequence[torch.Tensor], ids: torch.Tensor,
-                 bins: torch.Tensor, status: torch.Tensor, capacity: int, count: int):
+                 bins: torch.Tensor, status: torch.Tensor, capacity: int, count: int, max_filter: float = 0.0,
+                 covs: Optional[torch.Tensor] = None):
+        self.max_filter, self.covs = float(max_filter), covs
         self.dev, self.header = dev, header
         self.width, self.height = int(header["width"]), int(header["height"])
         self.tiles = (_tiles(self.width), _tiles(self.height))
@@ -1323,7 +1404,7 @@ class Field:
         return torch.stack(torch.broadcast_tensors(xs[None, :], ys[:, None]), dim=2).contiguous()
 
     def sample(self, points: torch.Tensor, out: Optional[torch.Tensor] = None, dtype=None, layout=None,
-               fill: Sequence[float] = (0.0, 0.0, 0.0), presort: Optional[bool] = None) -> torch.Tensor:
+               fill: Sequence[float] = (0.0, 0.0, 0.0), presort: Optional[bool] = None, footprint=None) -> torch.Tensor:
         """The function at `points`: float32, contiguous, on the field's device, [P, 2] or a grid [Ho, Wo, 2] with (x, y)
         last, in source pixel coordinates (pixel centres at integers).  -> [P, 3] or [Ho, Wo, 3] float32 by default;
         dtype / layout as in decode: "chw" gives [3, P] or [3, Ho, Wo], "hwc4" [P, 4] or [Ho, Wo, 4].  A position outside
@@ -1335,7 +1416,16 @@ class Field:
         Points that require grad (under torch.is_grad_enabled()) make the call differentiable in them: the same launches
         inside a torch.autograd.Function whose backward is one gated sample_vjp launch -- the exact derivative of the fit,
         zero in a channel the clamp holds -- reusing the forward's permutation.  Such a call takes dtype None or
-        torch.float32, layout None or "hwc" and no `out` (ValueError otherwise).  No double backward."""
+        torch.float32, layout None or "hwc" and no `out` (ValueError otherwise).  No double backward.
+        footprint (DESIGN.md 3.8 "Filtered samples"; a field made with max_filter > 0 only): every sample is the function
+        LOW-PASSED with a gaussian of its own, of variance Q = (qxx, qxy, qyy) in source pixels^2 -- a float32 contiguous
+        tensor on the field's device shaped like points with 3 in place of 2; a number q, short for (q, 0, q) at every
+        sample; or "auto" for a grid, grid_footprints(points, self.max_filter).  A footprint that is not finite, not
+        positive semi-definite or whose trace exceeds max_filter is not admitted: the sample is `fill`, like an outside
+        one.  One launch of gi2d_sample_points_filtered in place of gi2d_sample_points; not differentiable (points that
+        require grad are refused)."""
+        if footprint is not None:
+            return self._sample(points, out, dtype, layout, fill, presort, footprint)[0]
         if isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled():
             if dtype not in (None, torch.float32) or layout not in (None, "hwc") or out is not None:
                 raise ValueError("sample: points that require grad take dtype None or torch.float32, layout None or 'hwc' "
@@ -1369,7 +1459,31 @@ class Field:
                   C.c_void_p(keys.data_ptr()), st)
         return torch.sort(keys, stable=True).indices.to(torch.int32)
 
-    def _sample(self, points, out, dtype, layout, fill, presort) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    def _check_footprint(self, footprint, points, grid: bool) -> torch.Tensor:
+        """The checks on `footprint` -> the float32 tensor the launch reads (a number is expanded, "auto" computed)."""
+        if self.max_filter <= 0.0:
+            raise ValueError("sample: footprint needs a field made with max_filter > 0 (Decoder.field(stream, max_filter=v))")
+        if points.requires_grad and torch.is_grad_enabled():
+            raise ValueError("sample: filtered samples are not differentiable: points that require grad take no footprint")
+        want = (*points.shape[:-1], 3)
+        if isinstance(footprint, str):
+            if footprint != "auto" or not grid:
+                raise ValueError(f"sample: footprint {footprint!r}: 'auto' (for a grid [Ho, Wo, 2]), a number or a tensor")
+            return grid_footprints(points, self.max_filter)
+        if not isinstance(footprint, torch.Tensor):
+            _finite_numbers("sample", footprint=footprint)
+            q = float(footprint)
+            with np.errstate(over="ignore"):
+                if not (q >= 0.0 and float(np.float32(q) + np.float32(q)) <= float(np.float32(self.max_filter))):
+                    raise ValueError(f"sample: footprint {q}: the variance (q, 0, q) must be >= 0 with 2 q <= max_filter = "
+                                     f"{self.max_filter}")
+            return torch.tensor((q, 0.0, q), dtype=torch.float32, device=self.dev).expand(want).contiguous()
+        if (footprint.dtype != torch.float32 or tuple(footprint.shape) != want or footprint.device != self.dev
+                or not footprint.is_contiguous()):
+            raise ValueError(f"sample: footprint must be a contiguous float32 tensor of shape {want} on {self.dev}")
+        return footprint
+
+    def _sample(self, points, out, dtype, layout, fill, presort, footprint=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """sample's checks and launches -> (the samples, the permutation the work was ordered by or None)."""
         fmt = _format(dtype, layout)
         grid, p, sort = self._check_points("sample", points, presort)
@@ -1390,6 +1504,8 @@ class Field:
             shape = (3, p) if fmt.layout == "chw" else (p, 4 if fmt.layout == "hwc4" else 3)
         if out is not None:
             _check_out(out, shape, fmt.dtype, self.dev)
+        if footprint is not None:  # (after every other check: "auto" launches torch kernels of its own)
+            footprint = self._check_footprint(footprint, points, grid)
         if out is None:
             out = torch.empty(shape, dtype=fmt.dtype, device=self.dev)
         if p == 0:
@@ -1400,6 +1516,12 @@ class Field:
             st = _stream(self.dev)
             perm = self._sorted_by_tile(points, p, st) if sort else None
             gw, gh = (points.shape[1], points.shape[0]) if grid and not sort else (0, 0)
+            if footprint is not None:
+                _lib.call("gi2d_sample_points_filtered", self.header["num_points"], self.capacity, tx, ty, self.width,
+                          self.height, ptr(self.ids), ptr(self.bins), tx * ty, ptr(self.xys), ptr(self.covs),
+                          ptr(self.colors), ptr(self.status), p, ptr(points), ptr(footprint), self.max_filter,
+                          None if perm is None else ptr(perm), gw, gh, (C.c_float * 3)(*fill), *fmt.ids, ptr(out), st)
+                return out, perm
             _lib.call("gi2d_sample_points", self.header["num_points"], self.capacity, tx, ty, self.width, self.height,
                       ptr(self.ids), ptr(self.bins), tx * ty, ptr(self.xys), ptr(self.conics), ptr(self.colors), None,
                       ptr(self.status), p, ptr(points), None if perm is None else ptr(perm), gw, gh, (C.c_float * 3)(*fill),
@@ -1982,15 +2104,22 @@ class Decoder:
         images, aux = self._run([stream], [(view,)], _DEFAULT_FORMAT, geometry=True)
         return dict(zip(("xys", "radii", "conics", "num_tiles_hit", "colors"), aux), image=images[0])
 
-    def field(self, stream) -> Field:
+    def field(self, stream, max_filter: float = 0.0) -> Field:
         """bytes (or an uploaded DeviceStream) -> the stream's Field, to be sampled at any position (Field.sample).  The
         stream is parsed and checked as every decode does, a rANS payload expanded once, and the first two launches of the
         lists route run under the identity map -- gi2d_codec_decode_affine (origin 0, B = I, prefilter 0, the stream's
         radius_clip) and gi2d_bin_gaussians, lists of the capacity an overview starts with -- into tensors the Field owns,
         not into the buffers the next overview overwrites.  {count, overflow} is read in ONE host wait, the only one of a
-        Field's life; lists that were cut at the capacity are binned again with room for exactly `count`."""
+        Field's life; lists that were cut at the capacity are binned again with room for exactly `count`.
+        max_filter = v in (0, 4] (ValueError otherwise): a field whose samples may carry footprints of trace <= v (Field.sample,
+        footprint=; DESIGN.md 3.8 "Filtered samples").  gi2d_codec_decode_field takes the first launch's place: the lists
+        are those of the identity view with the prefilter (v, 0, v) -- a gaussian radius_clip drops as it is but not once
+        widened is in them -- and the Field keeps every gaussian's covariance before the prefilter, its conic and its
+        colour without the prefilter's gain.  Such a field serves sample without a footprint, jacobian and sample_vjp
+        too, on the wider lists: not bit for bit what a max_filter = 0 field gives."""
+        max_filter = _checked_max_filter("field", max_filter)
         h = _headers([stream])[0]
-        ident = Affine(0.0, 0.0, 1.0, 0.0, 0.0, 1.0, h["width"], h["height"], 0.0).check(h)  # (<= 16384 tiles, as every view)
+        ident = Affine(0.0, 0.0, 1.0, 0.0, 0.0, 1.0, h["width"], h["height"], max_filter).check(h)  # (<= 16384 tiles, as every view)
         n, tx, ty = h["num_points"], *ident.tiles
         rc = ident.radius_clip(h)
         i32 = lambda count: torch.empty(count, dtype=torch.int32, device=self.dev)
@@ -2008,8 +2137,14 @@ class Decoder:
             geo = self._aux(n)
             cap = self._overview_list_capacity(n)
             ids, bins = i32(cap), i32(2 * tx * ty)
-            _lib.call("gi2d_codec_decode_affine", *_stream_args(h, payload), h["height"], h["width"], ident.x0, ident.y0,
-                      *ident.inverse, *ident.prefilter, h["height"], h["width"], tx, ty, rc, *map(ptr, geo), st)
+            covs = None
+            if max_filter > 0.0:
+                covs = torch.empty((n, 3), dtype=torch.float32, device=self.dev)
+                _lib.call("gi2d_codec_decode_field", *_stream_args(h, payload), h["height"], h["width"], max_filter, tx, ty,
+                          rc, *map(ptr, geo), ptr(covs), st)
+            else:
+                _lib.call("gi2d_codec_decode_affine", *_stream_args(h, payload), h["height"], h["width"], ident.x0, ident.y0,
+                          *ident.inverse, *ident.prefilter, h["height"], h["width"], tx, ty, rc, *map(ptr, geo), st)
 
             def bin_lists(capacity: int, ids: torch.Tensor) -> None:
                 binws = torch.empty(int(bin_bytes(capacity, tx * ty)), dtype=torch.uint8, device=self.dev)
@@ -2025,7 +2160,7 @@ class Decoder:
                 cap = max(1, m)
                 ids = i32(cap)
                 bin_lists(cap, ids)
-        return Field(self.dev, h, geo, ids, bins, status, cap, m)
+        return Field(self.dev, h, geo, ids, bins, status, cap, m, max_filter, covs)
 
 
 _decoders: Dict[torch.device, Decoder] = {}
@@ -2054,21 +2189,27 @@ def decode(blob, device: Union[str, torch.device] = "cuda:0", out: Optional[torc
     return _decoder(device).decode(blob, out=out, view=view, dtype=dtype, layout=layout)
 
 
-def field(blob, device: Union[str, torch.device] = "cuda:0") -> Field:
-    """One-shot Decoder.field (the Decoder kept per device): the stream's Field, to be sampled any number of times."""
+def field(blob, device: Union[str, torch.device] = "cuda:0", max_filter: float = 0.0) -> Field:
+    """One-shot Decoder.field (the Decoder kept per device): the stream's Field, to be sampled any number of times;
+    max_filter > 0: one whose samples may carry footprints."""
     _parse(blob)  # a malformed stream is refused before a device is even touched
-    return _decoder(device).field(blob)
+    _checked_max_filter("field", max_filter)
+    return _decoder(device).field(blob, max_filter=max_filter)
 
 
 def sample(blob, points: torch.Tensor, device: Optional[Union[str, torch.device]] = None, out: Optional[torch.Tensor] = None,
-           dtype=None, layout=None, fill: Sequence[float] = (0.0, 0.0, 0.0), presort: Optional[bool] = None) -> torch.Tensor:
+           dtype=None, layout=None, fill: Sequence[float] = (0.0, 0.0, 0.0), presort: Optional[bool] = None,
+           footprint=None, max_filter: float = 0.0) -> torch.Tensor:
     """One-shot field(blob).sample(points, ...) on the points' device (or `device`): a caller with more than one batch of
     positions keeps the Field instead -- its lists are built once.  Points that require grad make it differentiable in them
-    as Field.sample says (float32 "hwc", no `out`; no double backward)."""
+    as Field.sample says (float32 "hwc", no `out`; no double backward).  footprint, max_filter: filtered samples, as
+    Field.sample and Decoder.field say (a footprint needs max_filter > 0)."""
     if not isinstance(points, torch.Tensor):
         raise ValueError("sample: points must be a float32 tensor of shape [P, 2] or [Ho, Wo, 2], (x, y) last")
-    return field(blob, points.device if device is None else device).sample(points, out=out, dtype=dtype, layout=layout,
-                                                                           fill=fill, presort=presort)
+    if footprint is not None and _checked_max_filter("sample", max_filter) <= 0.0:
+        raise ValueError("sample: footprint needs max_filter > 0")
+    fld = field(blob, points.device if device is None else device, max_filter=max_filter)
+    return fld.sample(points, out=out, dtype=dtype, layout=layout, fill=fill, presort=presort, footprint=footprint)
 
 
 def decode_batch(blobs, device: Union[str, torch.device] = "cuda:0", views=None, out: Optional[torch.Tensor] = None,

@@ -1,0 +1,357 @@
+// Low-pass filtered samples of a packed stream (include/gi2d.h "filtered samples"; DESIGN.md 3.8 "Filtered samples"):
+// every sample carries the 2x2 variance Q of its own low-pass, and since a gaussian convolved with a gaussian is a
+// gaussian the filter is applied per (sample, gaussian) pair in closed form -- covariance T = S + Q, colour times
+// sqrt(det S / det T) -- which is elliptical-weighted-average filtering done on the fit instead of on pixels.
+//
+//   field    codec_decode_field_kernel, one lane per gaussian: the record under the identity map with the prefilter
+//            (max_filter, 0, max_filter) -> xys, radii, num_tiles_hit as gi2d_codec_decode_affine writes them (the device
+//            routines are the same: codec_values, affine_transform, project_values), so that gi2d_bin_gaussians builds
+//            lists wide enough for every admitted footprint; next to them the covariance S before the prefilter, the conic
+//            of S and the colour without the prefilter's gain.
+//   samples  sample_points_filtered_kernel: the walk of gi2d_sample.hip::sample_points_kernel -- a wave of 64 samples, no
+//            workgroup barrier, the waterfall over the tiles the wave holds, the list staged 64 entries at a time into the
+//            wave's own LDS -- with centre, S, det S and colour staged per entry and T inverted per pair.
+//
+// A sample's bits depend on the arrays, its position and its footprint alone: no atomics.  Nothing is read through an
+// address formed from unchecked content: the tile comes from a position that has passed the inside test and is clamped
+// to the grid, list bounds are clamped to the capacity of the id buffer, ids to [0, N), entries of `perm` to [0, P).
+#include <cmath>
+#include <string>
+
+#include "gi2d_codec_core.h"
+
+namespace gi2d {
+
+#define GI2D_FSAMPLE_BATCH 64
+struct FilteredLds {
+    float4 a[GI2D_FSAMPLE_BATCH];  // gx, gy, sxx, sxy
+    float4 b[GI2D_FSAMPLE_BATCH];  // syy, det S, cr, cg
+    float2 c[GI2D_FSAMPLE_BATCH];  // cb, max(det S, 0)
+};
+
+// a c - b b with one rounding's worth of error (Kahan's difference of products): the determinant of a narrow or a
+// rank-one matrix loses every digit to cancellation when it is formed as two rounded products
+__device__ __forceinline__ float det_sym(float a, float b, float c) {
+#pragma clang fp contract(off)
+    const float w = b * b;
+    const float e = __builtin_fmaf(-b, b, w);  // w - b b, exact
+    const float f = __builtin_fmaf(a, c, -w);
+    return f + e;
+}
+
+// (gi2d_sample.hip::sample_key: the inside rule and the tile rule of every sample)
+__device__ __forceinline__ int filtered_sample_key(float x, float y, int img_w, int img_h, int tiles_x, int tiles_y, bool &inside) {
+    inside = x >= 0.f && x <= (float)(img_w - 1) && y >= 0.f && y <= (float)(img_h - 1);
+    if (!inside) return tiles_x * tiles_y;
+    const int j = (int)floorf(x + 0.5f), i = (int)floorf(y + 0.5f);
+    const int tx = min(max(j >> 4, 0), tiles_x - 1), ty = min(max(i >> 4, 0), tiles_y - 1);
+    return ty * tiles_x + tx;
+}
+
+// The footprint is admitted iff it is finite, positive semi-definite and its trace -- which bounds the larger eigenvalue
+// -- is at most max_filter: separate fp32 operations (tests/helpers_sample_filtered.py restates them).
+__device__ __forceinline__ bool footprint_admitted(float qxx, float qxy, float qyy, float max_filter) {
+#pragma clang fp contract(off)
+    const float big = 3.4028235e38f;
+    const bool finite = __builtin_fabsf(qxx) <= big && __builtin_fabsf(qxy) <= big && __builtin_fabsf(qyy) <= big;
+    const float lhs = qxx * qyy, rhs = qxy * qxy, trace = qxx + qyy;
+    return finite && qxx >= 0.f && qyy >= 0.f && lhs >= rhs && trace <= max_filter;
+}
+
+// (gi2d_sample.hip::wave_min_dpp / wave_max_dpp)
+__device__ __forceinline__ float filtered_wave_min(float x) {
+    int v = __float_as_int(x);
+#define GI2D_DPP_FMIN(ctrl, row_mask) \
+    v = __float_as_int(fminf(__int_as_float(v), __int_as_float(__builtin_amdgcn_update_dpp(0x7f800000, v, ctrl, row_mask, 0xf, false))))
+    GI2D_DPP_FMIN(0x111, 0xf);
+    GI2D_DPP_FMIN(0x112, 0xf);
+    GI2D_DPP_FMIN(0x114, 0xf);
+    GI2D_DPP_FMIN(0x118, 0xf);
+    GI2D_DPP_FMIN(0x142, 0xa);
+    GI2D_DPP_FMIN(0x143, 0xc);
+#undef GI2D_DPP_FMIN
+    return __int_as_float(__builtin_amdgcn_readlane(v, 63));
+}
+__device__ __forceinline__ float filtered_wave_max(float x) { return -filtered_wave_min(-x); }
+
+// The footprint of one sample as the pair loop reads it.
+struct Footprint {
+    float qxx, qxy, qyy;
+    float m2qxy;  // -2 qxy
+    float det;    // det Q (det_sym)
+};
+
+// One staged entry on this lane's sample.  det T = det S + (sxx qyy + syy qxx - 2 sxy qxy) + det Q, three terms none of
+// which is negative for positive semi-definite S and Q, in place of txx tyy - txy txy whose two products cancel for a
+// narrow gaussian; one v_rcp_f32 gives the inverse's scale for the conic (pre-scaled by log2(e): scale_conic) and for
+// the gain sqrt(max(det S, 0) / det T); then the quadratic form and the pair test of sample_pair with the limit of
+// opacity 1.  An entry with !(det T > 0) -- a NaN too -- adds nothing, nor does a pair whose sigma is a NaN.
+__device__ __forceinline__ void filtered_pair(const float4 A, const float4 B, const float2 Cc, const Footprint q, unsigned lim,
+                                              float px, float py, float &o0, float &o1, float &o2) {
+#pragma clang fp contract(off)
+    const float txx = A.z + q.qxx, txy = A.w + q.qxy, tyy = B.x + q.qyy;
+    const float cross = __builtin_fmaf(A.z, q.qyy, __builtin_fmaf(B.x, q.qxx, A.w * q.m2qxy));
+    const float det1 = (cross + q.det) + B.y;
+    const float rc = __builtin_amdgcn_rcpf(det1);
+    const float hs = rc * (0.5f * 1.4426950408889634f);
+    const float ha = tyy * hs, hc = txx * hs, hb = txy * (-2.f * hs);
+    const float gain = __builtin_amdgcn_sqrtf(Cc.y * rc);
+    const float dy = A.y - py;
+    const float bdy = hb * dy, cdy2 = __builtin_fmaf(hc * dy, dy, 0.f);
+    const float dx = A.x - px;
+    const float sig = __builtin_fmaf(dx, __builtin_fmaf(ha, dx, bdy), cdy2);
+    const float tt = gain * pair_vis(sig);
+    const bool ok = det1 > 0.f && pair_lands(sig, lim);
+    const float am = ok ? tt : 0.f;
+    o0 = __builtin_fmaf(B.z, am, o0);
+    o1 = __builtin_fmaf(B.w, am, o1);
+    o2 = __builtin_fmaf(Cc.x, am, o2);
+}
+
+// The walk below -- lane -> sample, the waterfall over the wave's tiles, the staging, the ballot compaction under SKIP -- is
+// gi2d_sample.hip::sample_points_kernel's: ITS TWIN, to be changed together with it.  (Kept as a copy, not factored out,
+// so that the existing kernels' device code stays what it was; DESIGN.md 3.8 "Sample gradients".)  What differs: a sample
+// whose footprint is not admitted is outside; an entry is staged as (centre, S, det S, colour); SKIP tests the alpha >=
+// 1/255 box of the WIDEST admitted footprint, the conic of S + max_filter I, against the served lanes' positions --
+// T <= S + max_filter I for every admitted Q, so sigma under T is at least sigma under the widest, and an entry dropped
+// here fails the pair test at every served sample whatever its footprint is.
+template <int DTYPE, int LAYOUT, bool GRID, bool SKIP>
+__global__ __launch_bounds__(256) void sample_points_filtered_kernel(
+    int n, int capacity, int tiles_x, int tiles_y, int img_w, int img_h, const int32_t *__restrict__ gids_sorted,
+    const int2 *__restrict__ tile_bins, int tile_bins_rows, const float2 *__restrict__ xys,
+    const float *__restrict__ covs, const float *__restrict__ colors, const int32_t *__restrict__ status,
+    long long num_samples, const float2 *__restrict__ points, const float *__restrict__ footprints, float max_filter,
+    const int32_t *__restrict__ perm, int grid_w, int grid_h, float fill0, float fill1, float fill2, void *__restrict__ out_) {
+    typedef typename PixelType<DTYPE>::type T;
+    __shared__ FilteredLds lds[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    FilteredLds &sm = lds[wv];
+
+    // ---- lane -> sample
+    bool valid;
+    long long s;
+    if (GRID) {
+        const int blocks_x = (grid_w + 15) >> 4;
+        const int bx = (int)(blockIdx.x % (unsigned)blocks_x), by = (int)(blockIdx.x / (unsigned)blocks_x);
+        const int col = bx * 16 + (lane & 15), row = by * 16 + wv * 4 + (lane >> 4);
+        valid = col < grid_w && row < grid_h;
+        s = (long long)row * grid_w + col;
+    } else {
+        s = ((long long)blockIdx.x * 4 + wv) * 64 + lane;
+        valid = s < num_samples;
+        if (valid && perm != nullptr) s = min(max((long long)perm[s], 0ll), num_samples - 1);
+    }
+    float px = 0.f, py = 0.f;
+    Footprint q{0.f, 0.f, 0.f, 0.f, 0.f};
+    if (valid) {
+        const float2 p = points[s];
+        px = p.x, py = p.y;
+        q.qxx = footprints[3 * s], q.qxy = footprints[3 * s + 1], q.qyy = footprints[3 * s + 2];
+    }
+    bool inside;
+    const int key = filtered_sample_key(px, py, img_w, img_h, tiles_x, tiles_y, inside);
+    inside = inside && valid && footprint_admitted(q.qxx, q.qxy, q.qyy, max_filter);
+    q.m2qxy = -2.f * q.qxy;
+    q.det = det_sym(q.qxx, q.qxy, q.qyy);
+    // the limit of alpha_rule for opacity 1: bits(log2(255)) + 1
+    const unsigned lim = (unsigned)__float_as_int(__builtin_amdgcn_logf(255.f)) + 1u;
+
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+    const bool nothing = status != nullptr && status[0] < 1;  // not a single intersection: an inside sample is ones
+    if (nothing) o0 = o1 = o2 = 1.f;
+
+    // ---- the tiles this wave holds, one after the other (wave-uniform: `todo` is a ballot)
+    unsigned long long todo = nothing ? 0ull : __ballot(inside);
+    while (todo != 0ull) {
+        const int t = wave_read_lane(key, __ffsll((long long)todo) - 1);  // a scalar: list bounds and staging are uniform
+        const bool mine = inside && key == t;  // (all of them unserved: the lanes of a tile are served together)
+        todo &= ~__ballot(mine);
+        int2 range = make_int2(0, 0);
+        if (t >= 0 && t < tile_bins_rows) range = tile_bins[t];
+        const int start = min(max(range.x, 0), capacity);
+        const int end = min(max(range.y, start), capacity);
+        if (start >= end) continue;
+        float bx0 = 0.f, bx1 = 0.f, by0 = 0.f, by1 = 0.f;  // what the served lanes' positions span
+        if (SKIP) {
+            const float inf = __int_as_float(0x7f800000);
+            bx0 = filtered_wave_min(mine ? px : inf), bx1 = filtered_wave_max(mine ? px : -inf);
+            by0 = filtered_wave_min(mine ? py : inf), by1 = filtered_wave_max(mine ? py : -inf);
+        }
+        int g_next = start + lane < end ? gids_sorted[start + lane] : 0;  // (one batch ahead of its use)
+        for (int base = start; base < end; base += GI2D_FSAMPLE_BATCH) {
+            const int m = min(GI2D_FSAMPLE_BATCH, end - base);
+            const int g = min(max(g_next, 0), n - 1);
+            if (base + GI2D_FSAMPLE_BATCH + lane < end) g_next = gids_sorted[base + GI2D_FSAMPLE_BATCH + lane];
+            bool keep = false;
+            float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A;
+            float2 Cc = make_float2(0.f, 0.f);
+            if (lane < m) {
+                const float2 xy = xys[g];
+                const float sxx = covs[3 * g], sxy = covs[3 * g + 1], syy = covs[3 * g + 2];
+                const float det0 = det_sym(sxx, sxy, syy);  // the same for every sample: once, here
+                A = make_float4(xy.x, xy.y, sxx, sxy);
+                B = make_float4(syy, det0, colors[3 * g], colors[3 * g + 1]);
+                Cc = make_float2(colors[3 * g + 2], fmaxf(det0, 0.f));
+                keep = true;
+                if (SKIP) {
+                    // the widest admitted footprint's conic, formed once per staged entry
+                    const float wxx = sxx + max_filter, wyy = syy + max_filter;
+                    const float rw = __builtin_amdgcn_rcpf(det_sym(wxx, sxy, wyy));
+                    float hx, hy;
+                    cull_extent(xy.x, xy.y, wyy * rw, -sxy * rw, wxx * rw, 1.f, hx, hy);
+                    // hx < 0: can never land; GI2D_CULL_FULL: no finite box, every sample is evaluated
+                    keep = hx >= 0.f && (hx >= GI2D_CULL_FULL || (xy.y - hy <= by1 && xy.y + hy >= by0 &&
+                                                                  xy.x - hx <= bx1 && xy.x + hx >= bx0));
+                }
+            }
+            const unsigned long long mask = __ballot(keep);
+            const int kept = __popcll(mask);
+            __builtin_amdgcn_wave_barrier();  // the block may still be read by the batch before this one
+            if (keep) {  // compacted in list order
+                const int slot = __popcll(mask & lanemask_lt());
+                sm.a[slot] = A, sm.b[slot] = B, sm.c[slot] = Cc;
+            }
+            __builtin_amdgcn_wave_barrier();  // wave-private block: DS ops of one wave complete in order
+            if (mine) {
+#pragma unroll 2
+                for (int k = 0; k < kept; ++k) filtered_pair(sm.a[k], sm.b[k], sm.c[k], q, lim, px, py, o0, o1, o2);
+            }
+        }
+    }
+
+    // ---- stores: the format's conversion (which clamps) of the sum, of ones, or of the caller's fill
+    if (!valid) return;
+    if (!inside) o0 = fill0, o1 = fill1, o2 = fill2;
+    pixel_store_elements<LAYOUT>(pixel_convert<DTYPE>(o0), pixel_convert<DTYPE>(o1), pixel_convert<DTYPE>(o2),
+                                 pixel_convert<DTYPE>(1.f), (size_t)s, (size_t)num_samples, reinterpret_cast<T *>(out_));
+}
+
+// The per-gaussian kernel of a field that can be filtered.  wide: the identity map with the prefilter (max_filter, 0,
+// max_filter); its transform and projection are codec_decode_lists_kernel<KIND, CodecAffine>'s, so xys, radii and
+// num_tiles_hit are that kernel's bit for bit.  plain: the identity map without a prefilter, which leaves in v the
+// covariance S affine_transform forms before it adds P; its conic is the one project_values<kCovariance> forms
+// (cov2d_bounds) whether or not radius_clip drops the gaussian there.  The colour is the dequantised one.
+template <int KIND>
+__global__ __launch_bounds__(256) void codec_decode_field_kernel(
+    int n, CodecLayout lay, CodecSide side, const uint32_t *__restrict__ payload, long long last_dword, float clip_coe,
+    float img_w, float img_h, int tiles_x, int tiles_y, float radius_clip, CodecOut out, float *__restrict__ covs,
+    CodecAffine wide, CodecAffine plain) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    float v[GI2D_CODEC_FIELDS], s[GI2D_CODEC_FIELDS];
+    codec_values<KIND>(g, lay, side, payload, last_dword, v);
+#pragma unroll
+    for (int k = 0; k < GI2D_CODEC_FIELDS; ++k) s[k] = v[k];
+    const float c0 = v[5], c1 = v[6], c2 = v[7];
+    affine_transform<KIND>(s, plain);
+    affine_transform<KIND>(v, wide);
+    const ProjOut o = project_values<kCovariance>(clip_coe, make_float2(v[0], v[1]), v[2], v[3], v[4], img_w, img_h,
+                                                  tiles_x, tiles_y, radius_clip);
+    float k0 = 0.f, k1 = 0.f, k2 = 0.f, rmaj, rmin;
+    if (!cov2d_bounds(s[2], s[3], s[4], clip_coe, k0, k1, k2, rmaj, rmin)) k0 = k1 = k2 = 0.f;
+    out.xys[g] = o.xy;
+    out.radii[g] = o.radius;
+    out.conics[3 * g] = k0, out.conics[3 * g + 1] = k1, out.conics[3 * g + 2] = k2;
+    out.num_tiles_hit[g] = o.tiles_hit;
+    out.colors[3 * g] = c0, out.colors[3 * g + 1] = c1, out.colors[3 * g + 2] = c2;
+    covs[3 * g] = s[2], covs[3 * g + 1] = s[3], covs[3 * g + 2] = s[4];
+}
+
+}  // namespace gi2d
+
+using namespace gi2d;
+
+// samples of one launch: 2^31 - 1 workgroups of 256
+#define GI2D_FSAMPLE_MAX (0x7fffffffLL * 256)
+
+extern "C" {
+
+int gi2d_codec_decode_field(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, const float *side_host,
+                            const void *payload, size_t payload_bytes, float clip_coe, unsigned h, unsigned w_,
+                            float max_filter, int tiles_x, int tiles_y, float radius_clip, float *xys, int32_t *radii,
+                            float *conics, int32_t *num_tiles_hit, float *colors, float *covs, gi2d_stream_t st) {
+    const char *what = "codec decode field";
+    const auto fail = [&](const char *why) {
+        set_error((std::string(what) + ": " + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    };
+    if (!(max_filter > 0.f) || !(max_filter <= GI2D_CODEC_AFFINE_MAX_PREFILTER))
+        return fail("max_filter must lie in 0 (excluded) .. 4 source pixels^2");
+    const CodecAffine wide{0.f, 0.f, 1.f, 0.f, 0.f, 1.f, max_filter, 0.f, max_filter};
+    const CodecAffine plain{0.f, 0.f, 1.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+    if (const char *why = codec_affine_refused(wide, h, w_, h, w_)) return fail(why);
+    if (!std::isfinite(radius_clip)) return fail("radius_clip must be finite");
+    CodecLayout lay;
+    CodecSide side;
+    long long last;
+    if (const int rc = codec_stream_checked(what, kind, n, xy_bits, p0_bits, p1_bits, color_bits, side_host, payload,
+                                            payload_bytes, lay, side, last))
+        return rc;
+    if (tiles_x < 0 || tiles_y < 0) return fail("negative size");
+    if (n > 0 && (!xys || !radii || !conics || !num_tiles_hit || !colors || !covs)) return fail("null or misaligned pointer");
+    if ((long long)tiles_x * GI2D_TILE < (long long)w_ || (long long)tiles_y * GI2D_TILE < (long long)h)
+        return fail("tile grid does not cover the image");
+    if (n == 0) return GI2D_OK;
+    const CodecOut out{(float2 *)xys, radii, conics, num_tiles_hit, colors};
+    const auto kernel = kind == kCovariance ? codec_decode_field_kernel<kCovariance> : codec_decode_field_kernel<kScaleRot>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)st, n, lay, side,
+                       (const uint32_t *)payload, last, clip_coe, (float)w_, (float)h, tiles_x, tiles_y, radius_clip, out,
+                       covs, wide, plain);
+    return check_launch(what);
+}
+
+int gi2d_sample_points_filtered(int n, int capacity, int tiles_x, int tiles_y, unsigned w, unsigned h, const int32_t *gids,
+                                const int32_t *bins, int rows, const float *xys, const float *covs, const float *colors,
+                                const int32_t *status, long long num_samples, const float *points_xy,
+                                const float *footprints, float max_filter, const int32_t *perm, int grid_w, int grid_h,
+                                const float *fill_host, int dtype, int layout, void *out, gi2d_stream_t st) {
+    const char *what = "sample points filtered";
+    const auto fail = [&](const char *why) {
+        set_error((std::string(what) + ": " + why).c_str());
+        return GI2D_ERR_INVALID_ARGUMENT;
+    };
+    // (the refusals of gi2d_sample_points, in its order)
+    if (!pixel_format_ok(dtype, layout)) return fail("unknown format (dtype 0..2, layout 0..2)");
+    if (n < 0 || capacity < 0 || tiles_x < 0 || tiles_y < 0 || rows < 0 || num_samples < 0 || grid_w < 0 || grid_h < 0)
+        return fail("negative size");
+    if (capacity > 0x7fffffff - GI2D_FSAMPLE_BATCH) return fail("capacity too large for 32-bit list positions");
+    if ((long long)tiles_x * GI2D_TILE < (long long)w || (long long)tiles_y * GI2D_TILE < (long long)h)
+        return fail("tile grid does not cover the image");
+    if ((long long)tiles_x * tiles_y >= 0x7fffffffLL || w > 0x7fffffffu || h > 0x7fffffffu) return fail("tile grid too large");
+    if (grid_w > 0 && (long long)grid_w * grid_h != num_samples) return fail("grid_width * grid_height is not num_samples");
+    if (grid_w > 0 && perm) return fail("a permutation and a grid exclude each other");
+    if (num_samples > GI2D_FSAMPLE_MAX || (perm && num_samples > 0x7fffffffLL))
+        return fail("more samples than one launch's grid (or a 32-bit permutation) can hold");
+    if (!(max_filter > 0.f) || !(max_filter <= GI2D_CODEC_AFFINE_MAX_PREFILTER))
+        return fail("max_filter must lie in 0 (excluded) .. 4 source pixels^2");
+    if (num_samples == 0) return GI2D_OK;
+    if (n == 0) capacity = 0, rows = 0;  // no gaussian: no list is read
+    if (!points_xy || !footprints || !out || (rows > 0 && !bins) ||
+        (capacity > 0 && rows > 0 && (!gids || !xys || !covs || !colors)))
+        return fail("null pointer");
+    const float f0 = fill_host ? fill_host[0] : 0.f, f1 = fill_host ? fill_host[1] : 0.f, f2 = fill_host ? fill_host[2] : 0.f;
+#ifdef GI2D_SAMPLE_NO_SKIP /* development variant: the walk without the per-wave skip (timing aid) */
+    constexpr bool skip = false;
+#else
+    constexpr bool skip = true;
+#endif
+    // a grid: one workgroup per 16x16 block of the lattice (blocks <= samples); a flat list: 256 samples per workgroup
+    const long long blocks = grid_w > 0 ? (long long)((grid_w + 15) >> 4) * ((grid_h + 15) >> 4) : (num_samples + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail("more samples than one launch's grid can hold");
+#define GI2D_FSAMPLE(D, L)                                                                                               \
+    if (grid_w > 0)                                                                                                      \
+        hipLaunchKernelGGL((sample_points_filtered_kernel<D, L, true, skip>), dim3((unsigned)blocks), dim3(256), 0,      \
+                           (hipStream_t)st, n, capacity, tiles_x, tiles_y, (int)w, (int)h, gids, (const int2 *)bins,     \
+                           rows, (const float2 *)xys, covs, colors, status, num_samples, (const float2 *)points_xy,      \
+                           footprints, max_filter, perm, grid_w, grid_h, f0, f1, f2, out);                               \
+    else                                                                                                                 \
+        hipLaunchKernelGGL((sample_points_filtered_kernel<D, L, false, skip>), dim3((unsigned)blocks), dim3(256), 0,     \
+                           (hipStream_t)st, n, capacity, tiles_x, tiles_y, (int)w, (int)h, gids, (const int2 *)bins,     \
+                           rows, (const float2 *)xys, covs, colors, status, num_samples, (const float2 *)points_xy,      \
+                           footprints, max_filter, perm, grid_w, grid_h, f0, f1, f2, out)
+    GI2D_FOR_FORMAT(dtype, layout, GI2D_FSAMPLE)
+#undef GI2D_FSAMPLE
+    return check_launch(what);
+}
+
+}  // extern "C"

@@ -967,6 +967,53 @@ int gi2d_sample_points_grad(int num_points, int capacity, int tiles_x, int tiles
                             float *jacobian /* f32[P,3,2]: iff v_out == NULL */,
                             float *v_points /* f32[P,2]: iff v_out != NULL */, gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ filtered samples (DESIGN.md 3.8 "Filtered samples")
+ * Samples that carry a low-pass of their own: next to its position every sample has a FOOTPRINT Q = (qxx, qxy, qyy), the
+ * variance of a gaussian low-pass in source pixels^2, and its value is the fitted function convolved with that gaussian,
+ * at the position -- in closed form per (sample, gaussian) pair, since a gaussian convolved with a gaussian is a gaussian.
+ * What a warp whose local scale differs from sample to sample (lens distortion, perspective, flow, log-polar) needs where
+ * it reduces.  Two calls:
+ *   gi2d_codec_decode_field   gi2d_codec_decode_affine under the identity map (origin 0, B = I, at the picture's own size)
+ *                          with the prefilter (max_filter, 0, max_filter), 0 < max_filter <= 4: xys, radii and
+ *                          num_tiles_hit are that call's bit for bit, so gi2d_bin_gaussians builds lists that hold every
+ *                          gaussian a footprint of trace <= max_filter can make land -- one the stream's radius_clip drops
+ *                          as it is but not once widened among them.  Beside them, for EVERY gaussian: covs f32[N,3], the
+ *                          covariance S = (sxx, sxy, syy) that call forms before it adds the prefilter (either kind);
+ *                          conics, the conic of S as the covariance projection forms it (zeros where det S == 0) whether or
+ *                          not radius_clip drops the gaussian; colors, the dequantised colour WITHOUT the prefilter's
+ *                          gain.  All six arrays are required.  Refused: max_filter outside 0 (excluded) .. 4 or a NaN,
+ *                          and what gi2d_codec_decode_affine refuses.
+ *   gi2d_sample_points_filtered   the arguments of gi2d_sample_points with covs in place of conics and without
+ *                          opacities (all 1), plus footprints f32[P,3] (device, indexed like points_xy) and max_filter.
+ *                          The inside rule and the tile rule are gi2d_sample_points's.  The footprint is ADMITTED iff, in
+ *                          separate fp32 operations, its three numbers are finite, qxx >= 0, qyy >= 0, qxx * qyy >= qxy *
+ *                          qxy and qxx + qyy <= max_filter (the trace bounds the larger eigenvalue, so the lists of
+ *                          gi2d_codec_decode_field cover S + Q); a sample whose footprint is not admitted is outside: it is
+ *                          `fill_host`, and no address is formed from it.  The value starts from 0 and takes EVERY entry of
+ *                          the tile's list, in list order: T = S + Q, det0 = det S, det1 = det T; an entry with !(det1 > 0)
+ *                          adds nothing; gain = sqrt(max(det0, 0) / det1), (a, b, c) = (tyy, -txy, txx) / det1, sigma =
+ *                          (a dx^2 + c dy^2) / 2 + b dx dy with dx = gx - x, dy = gy - y, alpha = exp(-sigma); the pair
+ *                          lands iff sigma >= 0 and alpha >= 1/255 (both false for a NaN) -- the test of every decode at
+ *                          opacity 1; the gain goes into the colour, not into the test -- and adds colour * gain * alpha.
+ *                          Stored clamped to [0, 1] in the format; status[0] < 1 makes an inside, admitted sample ones.
+ *                          Q = 0 is the point sample of the same lists.  No atomics: a sample's bits depend on the arrays,
+ *                          its position and its footprint alone.  Refusals: those of gi2d_sample_points (footprints is one
+ *                          more array that may not be NULL) and max_filter as above, under the prefix "sample points
+ *                          filtered".  num_samples = 0 is GI2D_OK without a launch. */
+int gi2d_codec_decode_field(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
+                            const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
+                            unsigned img_height, unsigned img_width, float max_filter, int tiles_x, int tiles_y,
+                            float radius_clip, float *xys, int32_t *radii, float *conics, int32_t *num_tiles_hit,
+                            float *colors, float *covs, gi2d_stream_t stream);
+int gi2d_sample_points_filtered(int num_points, int capacity, int tiles_x, int tiles_y, unsigned img_width,
+                                unsigned img_height, const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                                int tile_bins_rows, const float *xys, const float *covs, const float *colors,
+                                const int32_t *status, long long num_samples, const float *points_xy,
+                                const float *footprints /* f32[P,3] */, float max_filter,
+                                const int32_t *perm /* NULL: as given */, int grid_width /* 0: a flat list */,
+                                int grid_height, const float *fill_host /* 3 floats, NULL: zeros */, int dtype, int layout,
+                                void *out, gi2d_stream_t stream);
+
 /* ------------------------------------------------------------------ batched decode (DESIGN.md 3.8 "Batches")
  * K streams -> K pictures of ONE size and format in three launches: what the batched fitting calls above do for a fit,
  * for the decoder.  Picture k is, bit for bit, what workspace init + gi2d_codec_decode_bin (view = 0) or

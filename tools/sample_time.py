@@ -17,7 +17,7 @@ command under GI2D_LIB=<a development variant> GI2D_ALLOW_DEV_BUILD=1 (make VARI
 EXTRA='-DGI2D_SAMPLE_NO_SKIP -DGI2D_DEV_VARIANT=sample_noskip') gives the rows without the per-wave skip; --streams PATH
 keeps the two fits' streams in an .npz, so that every process of a comparison samples the same streams.
 
-    python tools/sample_time.py [--reps 100] [--streams PATH] [--out-json profiles/sample_time.json] [--trace] [--grad]
+    python tools/sample_time.py [--reps 100] [--streams PATH] [--out-json profiles/sample_time.json] [--trace] [--grad | --filtered]
 --trace samples a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for the
 two kernels' own times.
 
@@ -30,6 +30,15 @@ run of its own with the same region discipline, on the warp grid and the 65 536 
     grid_sample_forward_backward   the only other route to a gradient in the positions: full decode, then
                               torch.nn.functional.grid_sample (bilinear) with a grid that requires grad, then backward(w)
                               -- the slope between two neighbouring pixels, not the slope of the fit
+
+--filtered times the low-pass filtered samples (DESIGN.md 3.8 "Filtered samples"; profiles/sample_filtered_time.json), a run
+of its own with the same region discipline, on a field made with max_filter = 1.5:
+    warp       the radial-distortion grid: the filtered sample with footprint="auto" computed outside the region, next to
+               the unfiltered sample on the same field and the unfiltered sample on a max_filter = 0 field (what the wider
+               lists cost alone)
+    reduce     a 170 x 256 radial grid that reduces about 3 x at its rim (2 x at the centre): the filtered sample next to
+               the full decode followed by torch.nn.functional.grid_sample, and codec.grid_footprints alone
+    field      Decoder.field(stream, max_filter=1.5) next to Decoder.field(stream)
 """
 import argparse
 import json
@@ -146,6 +155,56 @@ def grad_rows(dec, up, fld, full, warp, warp_norm, scattered, reps):
     return rows
 
 
+def reducing_grid():
+    """A 170 x 256 barrel grid over the whole picture: 2 x reduction at the centre, about 3 x at the rim -> float32 [170, 256,
+    2] (x, y), every position inside, and the same grid in grid_sample's normalised coordinates."""
+    ho, wo = 170, 256
+    yy, xx = torch.meshgrid(torch.arange(ho, dtype=torch.float64), torch.arange(wo, dtype=torch.float64), indexing="ij")
+    cx, cy = (W - 1) / 2, (H - 1) / 2
+    u, v = (xx - (wo - 1) / 2) / ((wo - 1) / 2), (yy - (ho - 1) / 2) / ((ho - 1) / 2)
+    r2 = (u * u + v * v) / 2.0
+    k = (2.0 / 3.0 + r2 / 3.0)  # radial scale 2/3 at the centre, 1 at the corners: the local reduction grows outwards
+    pts = torch.stack([cx + cx * u * k, cy + cy * v * k], dim=2).float().to(DEV).contiguous()
+    norm = torch.stack([pts[..., 0] / cx - 1.0, pts[..., 1] / cy - 1.0], dim=2)[None].contiguous()
+    return pts, norm
+
+
+def filtered_rows(dec, up, fld, full, warp, reps, max_filter=1.5):
+    """The --filtered rows of one fit: {"warp": ..., "reduce": ..., "field": ...}."""
+    wide = dec.field(up, max_filter=max_filter)
+    rows = {}
+    q_warp = codec.grid_footprints(warp, max_filter)
+    out = torch.empty(H, W, 3, device=DEV)
+    tr = q_warp[..., 0] + q_warp[..., 2]
+    r = {"grid": [H, W], "max_filter": max_filter, "intersections_wide": wide.count, "intersections_plain": fld.count,
+         "footprint_trace_max": float(tr.max()), "footprints_not_zero": float((tr > 0).float().mean()),
+         "crc32_filtered": crc(wide.sample(warp, footprint=q_warp)),
+         "psnr_db_filtered_against_unfiltered": psnr(wide.sample(warp, footprint=q_warp), fld.sample(warp))}
+    rows["warp"] = alternating(r, {"filtered": lambda: wide.sample(warp, footprint=q_warp, out=out),
+                                   "unfiltered_same_field": lambda: wide.sample(warp, out=out),
+                                   "unfiltered_plain_field": lambda: fld.sample(warp, out=out)}, reps)
+    red, red_norm = reducing_grid()
+    q_red = codec.grid_footprints(red, max_filter)
+    out_red = torch.empty(*red.shape[:2], 3, device=DEV)
+
+    def grid_sample_route():
+        img = dec.decode(up, out=full).permute(2, 0, 1)[None]
+        return torch.nn.functional.grid_sample(img, red_norm, mode="bilinear", padding_mode="border", align_corners=True)
+
+    tr = q_red[..., 0] + q_red[..., 2]
+    r = {"grid": list(red.shape[:2]), "footprint_trace_max": float(tr.max()), "footprint_trace_mean": float(tr.mean()),
+         "crc32_filtered": crc(wide.sample(red, footprint=q_red)),
+         "psnr_db_filtered_against_grid_sample": psnr(wide.sample(red, footprint=q_red), grid_sample_route()[0].permute(1, 2, 0)),
+         "psnr_db_unfiltered_against_grid_sample": psnr(fld.sample(red), grid_sample_route()[0].permute(1, 2, 0))}
+    rows["reduce"] = alternating(r, {"filtered": lambda: wide.sample(red, footprint=q_red, out=out_red),
+                                     "unfiltered_plain_field": lambda: fld.sample(red, out=out_red),
+                                     "grid_sample": grid_sample_route,
+                                     "grid_footprints": lambda: codec.grid_footprints(red, max_filter)}, reps)
+    rows["field"] = alternating({}, {"field_max_filter": lambda: dec.field(up, max_filter=max_filter),
+                                     "field": lambda: dec.field(up)}, max(10, reps // 4))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=100)
@@ -154,10 +213,12 @@ def main():
     ap.add_argument("--streams", default=None, metavar="PATH")
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--grad", action="store_true")
+    ap.add_argument("--filtered", action="store_true")
     ap.add_argument("--out-json", default=None, metavar="PATH")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "sample_time.py needs the GPU"
-    res = {"tool": "sample_time --grad" if a.grad else "sample_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
+    assert not (a.grad and a.filtered), "--grad and --filtered are runs of their own"
+    res = {"tool": "sample_time --grad" if a.grad else "sample_time --filtered" if a.filtered else "sample_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
            "bits": [12, 10, 6], "reps": a.reps, "regions": 5, "sizes": {}}
     warp, warp_norm = radial_grid()
     rng = np.random.default_rng(20241021)
@@ -170,6 +231,15 @@ def main():
         full = torch.empty(H, W, 3, device=DEV)
         crop = fld.identity_grid()[y0:y0 + side, x0:x0 + side].contiguous()
         window = codec.Affine(float(x0), float(y0), 1.0, 0.0, 0.0, 1.0, side, side, 0.0)
+        if a.trace and a.filtered:
+            wide = dec.field(up, max_filter=1.5)
+            red = reducing_grid()[0]
+            q_warp, q_red = codec.grid_footprints(warp, 1.5), codec.grid_footprints(red, 1.5)
+            for _ in range(30):
+                wide.sample(warp, footprint=q_warp), wide.sample(warp), fld.sample(warp)
+                wide.sample(red, footprint=q_red), fld.sample(red)
+            torch.cuda.synchronize()
+            continue
         if a.trace:
             for _ in range(30):
                 fld.sample(crop), fld.sample(warp), fld.sample(scattered), fld.sample(scattered, presort=False)
@@ -183,6 +253,10 @@ def main():
                "longest_list": int((bins[:, 1] - bins[:, 0]).max()), "rows": {}}
         if a.grad:
             row["rows"] = grad_rows(dec, up, fld, full, warp, warp_norm, scattered, a.reps)
+            res["sizes"][str(n)] = row
+            continue
+        if a.filtered:
+            row["rows"] = filtered_rows(dec, up, fld, full, warp, a.reps)
             res["sizes"][str(n)] = row
             continue
         row["rows"]["field"] = alternating({}, {"field": lambda: dec.field(up)}, max(10, a.reps // 4))
