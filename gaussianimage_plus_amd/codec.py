@@ -78,7 +78,7 @@ the tile of a position's nearest pixel, that tile's whole list in list order, th
 position itself.  On the integer lattice that is the identity affine view of the lists route bit for bit; between pixels it
 is point evaluation -- no low-pass, so a grid that reduces aliases (Overview and Affine are for that), and, like every view,
 cut by tile boxes, so not continuous across tile borders.  The fit has an exact derivative in the position, and
-Field.jacobian / Field.sample_vjp (gi2d_sample_points_grad, the same walk with six more sums) give it; Field.sample with
+Field.jacobian / Field.sample_vjp (gi2d_sample_points_grad, the same walk -- csrc/gi2d_sample_core.h) give it; Field.sample with
 points that require grad is differentiable in them through the latter -- a warp whose parameters are being estimated, a
 sub-pixel registration, an edge map -- once, no double backward.  Where a warp reduces, a sample can carry a low-pass of
 its own: Decoder.field(stream, max_filter=v) widens the lists by the prefilter (v, 0, v) and keeps every gaussian's
@@ -1511,22 +1511,29 @@ class Field:
         if p == 0:
             return out, None
         ptr = lambda t: C.c_void_p(t.data_ptr())
+        tail = ((C.c_float * 3)(*fill), *fmt.ids, ptr(out))
+        if footprint is not None:
+            perm = self._launch("gi2d_sample_points_filtered", points, grid, p, sort, forms=self.covs, opacities=(),
+                                own=(ptr(footprint), self.max_filter), tail=tail)
+        else:
+            perm = self._launch("gi2d_sample_points", points, grid, p, sort, forms=self.conics, opacities=(None,), tail=tail)
+        return out, perm
+
+    def _launch(self, entry: str, points, grid: bool, p: int, sort: bool, *, forms, opacities, tail, own=(), perm=None):
+        """One sampling launch: the device context, the stream, the presort (or `perm`, a forward's own), the grid's sizes
+        and the call -- `forms`: conics or covariances; `opacities`: that argument where the entry has one; `own`,
+        `tail`: what it takes before the permutation and after the grid's sizes.  -> the permutation used, or None."""
+        ptr = lambda t: C.c_void_p(t.data_ptr())
         tx, ty = self.tiles
         with torch.cuda.device(self.dev) if self.dev.type == "cuda" else contextlib.nullcontext():
             st = _stream(self.dev)
-            perm = self._sorted_by_tile(points, p, st) if sort else None
+            if sort and perm is None:
+                perm = self._sorted_by_tile(points, p, st)
             gw, gh = (points.shape[1], points.shape[0]) if grid and not sort else (0, 0)
-            if footprint is not None:
-                _lib.call("gi2d_sample_points_filtered", self.header["num_points"], self.capacity, tx, ty, self.width,
-                          self.height, ptr(self.ids), ptr(self.bins), tx * ty, ptr(self.xys), ptr(self.covs),
-                          ptr(self.colors), ptr(self.status), p, ptr(points), ptr(footprint), self.max_filter,
-                          None if perm is None else ptr(perm), gw, gh, (C.c_float * 3)(*fill), *fmt.ids, ptr(out), st)
-                return out, perm
-            _lib.call("gi2d_sample_points", self.header["num_points"], self.capacity, tx, ty, self.width, self.height,
-                      ptr(self.ids), ptr(self.bins), tx * ty, ptr(self.xys), ptr(self.conics), ptr(self.colors), None,
-                      ptr(self.status), p, ptr(points), None if perm is None else ptr(perm), gw, gh, (C.c_float * 3)(*fill),
-                      *fmt.ids, ptr(out), st)
-        return out, perm
+            _lib.call(entry, self.header["num_points"], self.capacity, tx, ty, self.width, self.height, ptr(self.ids),
+                      ptr(self.bins), tx * ty, ptr(self.xys), ptr(forms), ptr(self.colors), *opacities, ptr(self.status), p,
+                      ptr(points), *own, ptr(perm) if sort else None, gw, gh, *tail, st)
+        return perm if sort else None
 
     def jacobian(self, points: torch.Tensor, presort: Optional[bool] = None, clamped: bool = True,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1565,16 +1572,9 @@ class Field:
         if p == 0:
             return out
         ptr = lambda t: C.c_void_p(t.data_ptr())
-        tx, ty = self.tiles
-        with torch.cuda.device(self.dev) if self.dev.type == "cuda" else contextlib.nullcontext():
-            st = _stream(self.dev)
-            if sort and perm is None:
-                perm = self._sorted_by_tile(points, p, st)
-            gw, gh = (points.shape[1], points.shape[0]) if grid and not sort else (0, 0)
-            _lib.call("gi2d_sample_points_grad", self.header["num_points"], self.capacity, tx, ty, self.width, self.height,
-                      ptr(self.ids), ptr(self.bins), tx * ty, ptr(self.xys), ptr(self.conics), ptr(self.colors), None,
-                      ptr(self.status), p, ptr(points), ptr(perm) if sort else None, gw, gh, int(clamped),
-                      None if v is None else ptr(v), ptr(out) if v is None else None, None if v is None else ptr(out), st)
+        self._launch("gi2d_sample_points_grad", points, grid, p, sort, perm=perm, forms=self.conics, opacities=(None,),
+                     tail=(int(clamped), None if v is None else ptr(v), ptr(out) if v is None else None,
+                           None if v is None else ptr(out)))
         return out
 
 

@@ -18,33 +18,17 @@
 //   grads    sample_points_grad_kernel: the same walk with six more sums per lane, the derivative of the three channels
 //            in the position -- stored as the Jacobian [P,3,2] or contracted with a caller's v_out into the VJP [P,2].
 //
+// The pieces of the walk are gi2d_sample_core.h's, shared with gi2d_sample_filtered.hip: the gradient kernel is built from
+// all of them, the value kernel keeps the next-tile step and the staged batch in its own text, which keeps its device code
+// what it was (DESIGN.md 3.8 "One sample walk" has the measurements behind that).
+//
 // A sample's bits depend on the stream and its position alone: no atomics, and neither its place in the call nor its
 // neighbours enter its sum.  Nothing is read through an address formed from unchecked content: the tile comes from a
 // position that has passed the inside test and is clamped to the grid, list bounds are clamped to the capacity of the id
 // buffer, ids to [0, N), entries of `perm` to [0, P).
-#include <string>
-
-#include "gi2d_long_core.h"
+#include "gi2d_sample_core.h"
 
 namespace gi2d {
-
-// the wave's staging block: the LongLds triple of 64 entries
-#define GI2D_SAMPLE_BATCH 64
-struct SampleLds {
-    float4 a[GI2D_SAMPLE_BATCH];  // gx, gy, ha, hb   (conic pre-scaled: scale_conic)
-    float4 b[GI2D_SAMPLE_BATCH];  // hc, opacity, cr, cg
-    float2 c[GI2D_SAMPLE_BATCH];  // cb, AlphaRule::lim
-};
-
-// Inside the picture's sample grid (0 <= x <= W - 1, 0 <= y <= H - 1: false for a NaN or an infinity) -> the tile of the
-// nearest pixel, clamped to the grid; tiles_x * tiles_y for a position outside.
-__device__ __forceinline__ int sample_key(float x, float y, int img_w, int img_h, int tiles_x, int tiles_y, bool &inside) {
-    inside = x >= 0.f && x <= (float)(img_w - 1) && y >= 0.f && y <= (float)(img_h - 1);
-    if (!inside) return tiles_x * tiles_y;
-    const int j = (int)floorf(x + 0.5f), i = (int)floorf(y + 0.5f);
-    const int tx = min(max(j >> 4, 0), tiles_x - 1), ty = min(max(i >> 4, 0), tiles_y - 1);
-    return ty * tiles_x + tx;
-}
 
 __global__ __launch_bounds__(256) void sample_keys_kernel(long long num_samples, const float2 *__restrict__ points,
                                                           int img_w, int img_h, int tiles_x, int tiles_y,
@@ -74,27 +58,8 @@ __device__ __forceinline__ void sample_pair(const float4 A, const float4 B, cons
     o2 = __builtin_fmaf(Cc.x, am, o2);
 }
 
-// Smallest and largest of one float per lane over the wave, in every lane: the DPP steps of wave_inclusive_scan with
-// +inf / -inf where a step has no source lane.  Every lane of the wave must be active.
-__device__ __forceinline__ float wave_min_dpp(float x) {
-    int v = __float_as_int(x);
-#define GI2D_DPP_FMIN(ctrl, row_mask) \
-    v = __float_as_int(fminf(__int_as_float(v), __int_as_float(__builtin_amdgcn_update_dpp(0x7f800000, v, ctrl, row_mask, 0xf, false))))
-    GI2D_DPP_FMIN(0x111, 0xf);
-    GI2D_DPP_FMIN(0x112, 0xf);
-    GI2D_DPP_FMIN(0x114, 0xf);
-    GI2D_DPP_FMIN(0x118, 0xf);
-    GI2D_DPP_FMIN(0x142, 0xa);
-    GI2D_DPP_FMIN(0x143, 0xc);
-#undef GI2D_DPP_FMIN
-    return __int_as_float(__builtin_amdgcn_readlane(v, 63));
-}
-__device__ __forceinline__ float wave_max_dpp(float x) { return -wave_min_dpp(-x); }
-
 // DTYPE, LAYOUT: the element type and layout of the output (gi2d_pixel_format.h), with pix = the sample's index and
-// plane = P.  GRID: the positions are a [grid_h, grid_w, 2] lattice and the wave holds a 16x4 strip of it, the workgroup
-// a 16x16 block, so that neighbouring samples meet the same source tiles; else sample 64 * (global wave) + lane of the
-// flat list, through `perm` when there is one.  SKIP: the per-wave skip described above.
+// plane = P.  GRID, SKIP: gi2d_sample_core.h (sample_of_lane, sample_box).
 template <int DTYPE, int LAYOUT, bool GRID, bool SKIP>
 __global__ __launch_bounds__(256) void sample_points_kernel(
     int n, int capacity, int tiles_x, int tiles_y, int img_w, int img_h, const int32_t *__restrict__ gids_sorted,
@@ -104,23 +69,11 @@ __global__ __launch_bounds__(256) void sample_points_kernel(
     const int32_t *__restrict__ perm, int grid_w, int grid_h, float fill0, float fill1, float fill2, void *__restrict__ out_) {
     typedef typename PixelType<DTYPE>::type T;
     __shared__ SampleLds lds[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     SampleLds &sm = lds[wv];
 
-    // ---- lane -> sample
     bool valid;
-    long long s;
-    if (GRID) {
-        const int blocks_x = (grid_w + 15) >> 4;
-        const int bx = (int)(blockIdx.x % (unsigned)blocks_x), by = (int)(blockIdx.x / (unsigned)blocks_x);
-        const int col = bx * 16 + (lane & 15), row = by * 16 + wv * 4 + (lane >> 4);
-        valid = col < grid_w && row < grid_h;
-        s = (long long)row * grid_w + col;
-    } else {
-        s = ((long long)blockIdx.x * 4 + wv) * 64 + lane;
-        valid = s < num_samples;
-        if (valid && perm != nullptr) s = min(max((long long)perm[s], 0ll), num_samples - 1);
-    }
+    const long long s = sample_of_lane<GRID>(lane, wv, num_samples, perm, grid_w, grid_h, valid);
     float px = 0.f, py = 0.f;
     if (valid) {
         const float2 p = points[s];
@@ -137,25 +90,23 @@ __global__ __launch_bounds__(256) void sample_points_kernel(
     // ---- the tiles this wave holds, one after the other (wave-uniform: `todo` is a ballot)
     unsigned long long todo = nothing ? 0ull : __ballot(inside);
     while (todo != 0ull) {
-        const int t = wave_read_lane(key, __ffsll((long long)todo) - 1);  // a scalar: list bounds and staging are uniform
-        const bool mine = inside && key == t;  // (all of them unserved: the lanes of a tile are served together)
+        // (this step is sample_next_tile's, in the kernel's own text: DESIGN.md 3.8 "One sample walk")
+        const int t = wave_read_lane(key, __ffsll((long long)todo) - 1);
+        const bool mine = inside && key == t;
         todo &= ~__ballot(mine);
         int2 range = make_int2(0, 0);
         if (t < tile_bins_rows) range = tile_bins[t];
-        const int start = min(max(range.x, 0), capacity);
-        const int end = min(max(range.y, start), capacity);
-        if (start >= end) continue;
-        float bx0 = 0.f, bx1 = 0.f, by0 = 0.f, by1 = 0.f;  // what the served lanes' positions span
-        if (SKIP) {
-            const float inf = __int_as_float(0x7f800000);
-            bx0 = wave_min_dpp(mine ? px : inf), bx1 = wave_max_dpp(mine ? px : -inf);
-            by0 = wave_min_dpp(mine ? py : inf), by1 = wave_max_dpp(mine ? py : -inf);
-        }
-        int g_next = start + lane < end ? gids_sorted[start + lane] : 0;  // (one batch ahead of its use)
-        for (int base = start; base < end; base += GI2D_SAMPLE_BATCH) {
-            const int m = min(GI2D_SAMPLE_BATCH, end - base);
+        SampleTile tile;
+        tile.start = min(max(range.x, 0), capacity);
+        tile.end = min(max(range.y, tile.start), capacity);
+        if (tile.start >= tile.end) continue;
+        const SampleBox box = sample_box<SKIP>(mine, px, py);
+        int g_next = tile.start + lane < tile.end ? gids_sorted[tile.start + lane] : 0;  // (one batch ahead of its use)
+        for (int base = tile.start; base < tile.end; base += GI2D_SAMPLE_BATCH) {
+            // (this batch is sample_stage_batch's, in the kernel's own text: DESIGN.md 3.8 "One sample walk")
+            const int m = min(GI2D_SAMPLE_BATCH, tile.end - base);
             const int g = min(max(g_next, 0), n - 1);
-            if (base + GI2D_SAMPLE_BATCH + lane < end) g_next = gids_sorted[base + GI2D_SAMPLE_BATCH + lane];
+            if (base + GI2D_SAMPLE_BATCH + lane < tile.end) g_next = gids_sorted[base + GI2D_SAMPLE_BATCH + lane];
             bool keep = false, clamp = false;
             float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A;
             float2 Cc = make_float2(0.f, 0.f);
@@ -174,8 +125,8 @@ __global__ __launch_bounds__(256) void sample_points_kernel(
                     float hx, hy;
                     cull_extent(xy.x, xy.y, a, b, c, op, hx, hy);
                     // hx < 0: can never land; GI2D_CULL_FULL: no finite box, every sample is evaluated
-                    keep = hx >= 0.f && (hx >= GI2D_CULL_FULL || (xy.y - hy <= by1 && xy.y + hy >= by0 &&
-                                                                  xy.x - hx <= bx1 && xy.x + hx >= bx0));
+                    keep = hx >= 0.f && (hx >= GI2D_CULL_FULL || (xy.y - hy <= box.y1 && xy.y + hy >= box.y0 &&
+                                                                  xy.x - hx <= box.x1 && xy.x + hx >= box.x0));
                 }
             }
             const bool clamp_any = __ballot(clamp) != 0ull;
@@ -242,10 +193,8 @@ __device__ __forceinline__ void sample_pair_grad(const float4 A, const float4 B,
     d[5] = __builtin_fmaf(Cc.x, ay, d[5]);
 }
 
-// The walk below -- lane -> sample, the waterfall over the wave's tiles, the staging, the ballot compaction under SKIP -- is
-// sample_points_kernel's, line for line: ITS TWIN, to be changed together with it.  (Kept as a copy, not factored out,
-// so that the value kernel's device code stays what it was; DESIGN.md 3.8 "Sample gradients".)  Six more accumulators,
-// d[2 k + 0 | 1] = d o_k / d (px | py) over ln 2, and another epilogue:
+// sample_points_kernel's walk with six more accumulators, d[2 k + 0 | 1] = d o_k / d (px | py) over ln 2, and another
+// epilogue:
 //   VJP = false   out = jacobian f32[P,3,2]: the six floats of sample s, 24 contiguous bytes, as three float2 stores
 //   VJP = true    out = v_points f32[P,2]: (sum_k v_out[s][k] d[k][x], sum_k v_out[s][k] d[k][y]), one float2 store
 // gate: channel k counts only where clamp01(o_k) == o_k, i.e. where the value the value kernel stored is the unclamped
@@ -259,23 +208,12 @@ __global__ __launch_bounds__(256) void sample_points_grad_kernel(
     const int32_t *__restrict__ perm, int grid_w, int grid_h, int gate, const float *__restrict__ v_out,
     float2 *__restrict__ out) {
     __shared__ SampleLds lds[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     SampleLds &sm = lds[wv];
+    const PointEntry entry{xys, conics, colors, opacities};
 
-    // ---- lane -> sample
     bool valid;
-    long long s;
-    if (GRID) {
-        const int blocks_x = (grid_w + 15) >> 4;
-        const int bx = (int)(blockIdx.x % (unsigned)blocks_x), by = (int)(blockIdx.x / (unsigned)blocks_x);
-        const int col = bx * 16 + (lane & 15), row = by * 16 + wv * 4 + (lane >> 4);
-        valid = col < grid_w && row < grid_h;
-        s = (long long)row * grid_w + col;
-    } else {
-        s = ((long long)blockIdx.x * 4 + wv) * 64 + lane;
-        valid = s < num_samples;
-        if (valid && perm != nullptr) s = min(max((long long)perm[s], 0ll), num_samples - 1);
-    }
+    const long long s = sample_of_lane<GRID>(lane, wv, num_samples, perm, grid_w, grid_h, valid);
     float px = 0.f, py = 0.f;
     if (valid) {
         const float2 p = points[s];
@@ -292,56 +230,14 @@ __global__ __launch_bounds__(256) void sample_points_grad_kernel(
     // ---- the tiles this wave holds, one after the other (wave-uniform: `todo` is a ballot)
     unsigned long long todo = nothing ? 0ull : __ballot(inside);
     while (todo != 0ull) {
-        const int t = wave_read_lane(key, __ffsll((long long)todo) - 1);  // a scalar: list bounds and staging are uniform
-        const bool mine = inside && key == t;  // (all of them unserved: the lanes of a tile are served together)
-        todo &= ~__ballot(mine);
-        int2 range = make_int2(0, 0);
-        if (t < tile_bins_rows) range = tile_bins[t];
-        const int start = min(max(range.x, 0), capacity);
-        const int end = min(max(range.y, start), capacity);
-        if (start >= end) continue;
-        float bx0 = 0.f, bx1 = 0.f, by0 = 0.f, by1 = 0.f;  // what the served lanes' positions span
-        if (SKIP) {
-            const float inf = __int_as_float(0x7f800000);
-            bx0 = wave_min_dpp(mine ? px : inf), bx1 = wave_max_dpp(mine ? px : -inf);
-            by0 = wave_min_dpp(mine ? py : inf), by1 = wave_max_dpp(mine ? py : -inf);
-        }
-        int g_next = start + lane < end ? gids_sorted[start + lane] : 0;  // (one batch ahead of its use)
-        for (int base = start; base < end; base += GI2D_SAMPLE_BATCH) {
-            const int m = min(GI2D_SAMPLE_BATCH, end - base);
-            const int g = min(max(g_next, 0), n - 1);
-            if (base + GI2D_SAMPLE_BATCH + lane < end) g_next = gids_sorted[base + GI2D_SAMPLE_BATCH + lane];
-            bool keep = false, clamp = false;
-            float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A;
-            float2 Cc = make_float2(0.f, 0.f);
-            if (lane < m) {
-                const float2 xy = xys[g];
-                const float a = conics[3 * g], b = conics[3 * g + 1], c = conics[3 * g + 2];
-                const float op = opacities ? opacities[g] : 1.f;
-                const AlphaRule ar = alpha_rule(xy.x, xy.y, a, b, c, op);
-                const ConicS sc = scale_conic(a, b, c);
-                clamp = ar.clamp;
-                A = make_float4(xy.x, xy.y, sc.ha, sc.hb);
-                B = make_float4(sc.hc, op, colors[3 * g], colors[3 * g + 1]);
-                Cc = make_float2(colors[3 * g + 2], __int_as_float((int)ar.lim));
-                keep = true;
-                if (SKIP) {
-                    float hx, hy;
-                    cull_extent(xy.x, xy.y, a, b, c, op, hx, hy);
-                    // hx < 0: can never land; GI2D_CULL_FULL: no finite box, every sample is evaluated
-                    keep = hx >= 0.f && (hx >= GI2D_CULL_FULL || (xy.y - hy <= by1 && xy.y + hy >= by0 &&
-                                                                  xy.x - hx <= bx1 && xy.x + hx >= bx0));
-                }
-            }
-            const bool clamp_any = __ballot(clamp) != 0ull;
-            const unsigned long long mask = __ballot(keep);
-            const int kept = __popcll(mask);
-            __builtin_amdgcn_wave_barrier();  // the block may still be read by the batch before this one
-            if (keep) {  // compacted in list order
-                const int slot = __popcll(mask & lanemask_lt());
-                sm.a[slot] = A, sm.b[slot] = B, sm.c[slot] = Cc;
-            }
-            __builtin_amdgcn_wave_barrier();  // wave-private block: DS ops of one wave complete in order
+        SampleTile tile;
+        const bool mine = sample_next_tile(todo, key, inside, tile_bins, tile_bins_rows, capacity, tile);
+        if (tile.start >= tile.end) continue;
+        const SampleBox box = sample_box<SKIP>(mine, px, py);
+        int g_next = sample_first_id(lane, gids_sorted, tile);
+        for (int base = tile.start; base < tile.end; base += GI2D_SAMPLE_BATCH) {
+            bool clamp_any;
+            const int kept = sample_stage_batch<SKIP>(sm, entry, n, gids_sorted, base, tile.end, lane, box, g_next, clamp_any);
             if (mine) {
                 if (clamp_any) {
 #pragma unroll 4
@@ -382,22 +278,12 @@ __global__ __launch_bounds__(256) void sample_points_grad_kernel(
 
 using namespace gi2d;
 
-// samples of one launch: 2^31 - 1 workgroups of 256
-#define GI2D_SAMPLE_MAX (0x7fffffffLL * 256)
-
-static bool sample_grid_covers(int tiles_x, int tiles_y, unsigned w, unsigned h) {
-    return (long long)tiles_x * GI2D_TILE >= (long long)w && (long long)tiles_y * GI2D_TILE >= (long long)h;
-}
-
 extern "C" {
 
 int gi2d_sample_point_keys(long long num_samples, const float *points_xy, unsigned w, unsigned h, int tiles_x, int tiles_y,
                            int32_t *keys, gi2d_stream_t st) {
     const char *what = "sample point keys";
-    const auto fail = [&](const char *why) {
-        set_error((std::string(what) + ": " + why).c_str());
-        return GI2D_ERR_INVALID_ARGUMENT;
-    };
+    const auto fail = [&](const char *why) { return sample_refused(what, why); };
     if (num_samples < 0 || tiles_x < 0 || tiles_y < 0) return fail("negative size");
     if (!sample_grid_covers(tiles_x, tiles_y, w, h)) return fail("tile grid does not cover the image");
     if ((long long)tiles_x * tiles_y >= 0x7fffffffLL || w > 0x7fffffffu || h > 0x7fffffffu) return fail("tile grid too large");
@@ -415,44 +301,21 @@ int gi2d_sample_points(int n, int capacity, int tiles_x, int tiles_y, unsigned w
                        const int32_t *perm, int grid_w, int grid_h, const float *fill_host, int dtype, int layout, void *out,
                        gi2d_stream_t st) {
     const char *what = "sample points";
-    const auto fail = [&](const char *why) {
-        set_error((std::string(what) + ": " + why).c_str());
-        return GI2D_ERR_INVALID_ARGUMENT;
-    };
-    if (!pixel_format_ok(dtype, layout)) return fail("unknown format (dtype 0..2, layout 0..2)");
-    if (n < 0 || capacity < 0 || tiles_x < 0 || tiles_y < 0 || rows < 0 || num_samples < 0 || grid_w < 0 || grid_h < 0)
-        return fail("negative size");
-    if (capacity > 0x7fffffff - GI2D_SAMPLE_BATCH) return fail("capacity too large for 32-bit list positions");
-    if (!sample_grid_covers(tiles_x, tiles_y, w, h)) return fail("tile grid does not cover the image");
-    if ((long long)tiles_x * tiles_y >= 0x7fffffffLL || w > 0x7fffffffu || h > 0x7fffffffu) return fail("tile grid too large");
-    if (grid_w > 0 && (long long)grid_w * grid_h != num_samples) return fail("grid_width * grid_height is not num_samples");
-    if (grid_w > 0 && perm) return fail("a permutation and a grid exclude each other");
-    if (num_samples > GI2D_SAMPLE_MAX || (perm && num_samples > 0x7fffffffLL))
-        return fail("more samples than one launch's grid (or a 32-bit permutation) can hold");
+    if (!pixel_format_ok(dtype, layout)) return sample_refused(what, "unknown format (dtype 0..2, layout 0..2)");
+    SampleArgs a{n, capacity, tiles_x, tiles_y, w, h, gids, bins, rows, xys, conics, colors, num_samples, points_xy, perm,
+                 grid_w, grid_h};
+    if (sample_sizes_refused(what, a)) return GI2D_ERR_INVALID_ARGUMENT;
     if (num_samples == 0) return GI2D_OK;
-    if (n == 0) capacity = 0, rows = 0;  // no gaussian: no list is read
-    if (!points_xy || !out || (rows > 0 && !bins) || (capacity > 0 && rows > 0 && (!gids || !xys || !conics || !colors)))
-        return fail("null pointer");
+    const long long blocks = sample_arrays_checked(what, a, !out);
+    if (blocks < 0) return GI2D_ERR_INVALID_ARGUMENT;
     const float f0 = fill_host ? fill_host[0] : 0.f, f1 = fill_host ? fill_host[1] : 0.f, f2 = fill_host ? fill_host[2] : 0.f;
-#ifdef GI2D_SAMPLE_NO_SKIP /* development variant: the walk without the per-wave skip (timing aid) */
-    constexpr bool skip = false;
-#else
-    constexpr bool skip = true;
-#endif
-    // a grid: one workgroup per 16x16 block of the lattice (blocks <= samples); a flat list: 256 samples per workgroup
-    const long long blocks = grid_w > 0 ? (long long)((grid_w + 15) >> 4) * ((grid_h + 15) >> 4) : (num_samples + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail("more samples than one launch's grid can hold");
 #define GI2D_SAMPLE(D, L)                                                                                                \
-    if (grid_w > 0)                                                                                                      \
-        hipLaunchKernelGGL((sample_points_kernel<D, L, true, skip>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, \
-                           n, capacity, tiles_x, tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows,                \
-                           (const float2 *)xys, conics, colors, opac, status, num_samples, (const float2 *)points_xy,   \
-                           perm, grid_w, grid_h, f0, f1, f2, out);                                                       \
-    else                                                                                                                 \
-        hipLaunchKernelGGL((sample_points_kernel<D, L, false, skip>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, \
-                           n, capacity, tiles_x, tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows,                \
-                           (const float2 *)xys, conics, colors, opac, status, num_samples, (const float2 *)points_xy,   \
-                           perm, grid_w, grid_h, f0, f1, f2, out)
+    sample_for_flag(grid_w > 0, [&](auto grid) {                                                                         \
+        hipLaunchKernelGGL((sample_points_kernel<D, L, decltype(grid)::value, kSampleSkip>), dim3((unsigned)blocks),     \
+                           dim3(256), 0, (hipStream_t)st, n, a.capacity, tiles_x, tiles_y, (int)w, (int)h, gids,         \
+                           (const int2 *)bins, a.rows, (const float2 *)xys, conics, colors, opac, status, num_samples,     \
+                           (const float2 *)points_xy, perm, grid_w, grid_h, f0, f1, f2, out);                            \
+    })
     GI2D_FOR_FORMAT(dtype, layout, GI2D_SAMPLE)
 #undef GI2D_SAMPLE
     return check_launch(what);
@@ -464,49 +327,26 @@ int gi2d_sample_points_grad(int n, int capacity, int tiles_x, int tiles_y, unsig
                             const int32_t *perm, int grid_w, int grid_h, int gate, const float *v_out, float *jacobian,
                             float *v_points, gi2d_stream_t st) {
     const char *what = "sample points grad";
-    const auto fail = [&](const char *why) {
-        set_error((std::string(what) + ": " + why).c_str());
-        return GI2D_ERR_INVALID_ARGUMENT;
-    };
-    // (the refusals of gi2d_sample_points, in its order, without the format's)
-    if (n < 0 || capacity < 0 || tiles_x < 0 || tiles_y < 0 || rows < 0 || num_samples < 0 || grid_w < 0 || grid_h < 0)
-        return fail("negative size");
-    if (capacity > 0x7fffffff - GI2D_SAMPLE_BATCH) return fail("capacity too large for 32-bit list positions");
-    if (!sample_grid_covers(tiles_x, tiles_y, w, h)) return fail("tile grid does not cover the image");
-    if ((long long)tiles_x * tiles_y >= 0x7fffffffLL || w > 0x7fffffffu || h > 0x7fffffffu) return fail("tile grid too large");
-    if (grid_w > 0 && (long long)grid_w * grid_h != num_samples) return fail("grid_width * grid_height is not num_samples");
-    if (grid_w > 0 && perm) return fail("a permutation and a grid exclude each other");
-    if (num_samples > GI2D_SAMPLE_MAX || (perm && num_samples > 0x7fffffffLL))
-        return fail("more samples than one launch's grid (or a 32-bit permutation) can hold");
+    SampleArgs a{n, capacity, tiles_x, tiles_y, w, h, gids, bins, rows, xys, conics, colors, num_samples, points_xy, perm,
+                 grid_w, grid_h};
+    if (sample_sizes_refused(what, a)) return GI2D_ERR_INVALID_ARGUMENT;
     const char *one = "exactly one of jacobian / v_points, v_points together with v_out";
-    if ((jacobian && v_points) || (v_points && !v_out) || (jacobian && v_out)) return fail(one);
+    if ((jacobian && v_points) || (v_points && !v_out) || (jacobian && v_out)) return sample_refused(what, one);
     float *out = v_out ? v_points : jacobian;
-    if (((uintptr_t)out & 7u) != 0) return fail("jacobian / v_points must be aligned to 8 bytes");
+    if (((uintptr_t)out & 7u) != 0) return sample_refused(what, "jacobian / v_points must be aligned to 8 bytes");
     if (num_samples == 0) return GI2D_OK;
-    if (!out) return fail(one);  // (like every NULL array: only a call with samples misses it)
-    if (n == 0) capacity = 0, rows = 0;  // no gaussian: no list is read
-    if (!points_xy || (rows > 0 && !bins) || (capacity > 0 && rows > 0 && (!gids || !xys || !conics || !colors)))
-        return fail("null pointer");
-#ifdef GI2D_SAMPLE_NO_SKIP /* development variant: the walk without the per-wave skip (timing aid) */
-    constexpr bool skip = false;
-#else
-    constexpr bool skip = true;
-#endif
-    const long long blocks = grid_w > 0 ? (long long)((grid_w + 15) >> 4) * ((grid_h + 15) >> 4) : (num_samples + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail("more samples than one launch's grid can hold");
-#define GI2D_SAMPLE_GRAD(G, V)                                                                                           \
-    hipLaunchKernelGGL((sample_points_grad_kernel<G, skip, V>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, n, \
-                       capacity, tiles_x, tiles_y, (int)w, (int)h, gids, (const int2 *)bins, rows, (const float2 *)xys,  \
-                       conics, colors, opac, status, num_samples, (const float2 *)points_xy, perm, grid_w, grid_h,       \
-                       gate != 0 ? 1 : 0, v_out, (float2 *)out)
-    if (grid_w > 0) {
-        if (v_out) GI2D_SAMPLE_GRAD(true, true);
-        else GI2D_SAMPLE_GRAD(true, false);
-    } else {
-        if (v_out) GI2D_SAMPLE_GRAD(false, true);
-        else GI2D_SAMPLE_GRAD(false, false);
-    }
-#undef GI2D_SAMPLE_GRAD
+    if (!out) return sample_refused(what, one);  // (like every NULL array: only a call with samples misses it)
+    const long long blocks = sample_arrays_checked(what, a, false);
+    if (blocks < 0) return GI2D_ERR_INVALID_ARGUMENT;
+    sample_for_flag(grid_w > 0, [&](auto grid) {
+        sample_for_flag(v_out != nullptr, [&](auto vjp) {
+            hipLaunchKernelGGL((sample_points_grad_kernel<decltype(grid)::value, kSampleSkip, decltype(vjp)::value>),
+                               dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, n, a.capacity, tiles_x, tiles_y, (int)w,
+                               (int)h, gids, (const int2 *)bins, a.rows, (const float2 *)xys, conics, colors, opac, status,
+                               num_samples, (const float2 *)points_xy, perm, grid_w, grid_h, gate != 0 ? 1 : 0, v_out,
+                               (float2 *)out);
+        });
+    });
     return check_launch(what);
 }
 

@@ -8,9 +8,10 @@
 //            routines are the same: codec_values, affine_transform, project_values), so that gi2d_bin_gaussians builds
 //            lists wide enough for every admitted footprint; next to them the covariance S before the prefilter, the conic
 //            of S and the colour without the prefilter's gain.
-//   samples  sample_points_filtered_kernel: the walk of gi2d_sample.hip::sample_points_kernel -- a wave of 64 samples, no
-//            workgroup barrier, the waterfall over the tiles the wave holds, the list staged 64 entries at a time into the
-//            wave's own LDS -- with centre, S, det S and colour staged per entry and T inverted per pair.
+//   samples  sample_points_filtered_kernel: the walk of gi2d_sample.hip::sample_points_kernel, sharing what it shares
+//            (gi2d_sample_core.h) -- a wave of 64 samples, no workgroup barrier, the waterfall over the tiles the
+//            wave holds, the list staged 64 entries at a time into the wave's own LDS -- with centre, S, det S and colour
+//            staged per entry and T inverted per pair.
 //
 // A sample's bits depend on the arrays, its position and its footprint alone: no atomics.  Nothing is read through an
 // address formed from unchecked content: the tile comes from a position that has passed the inside test and is clamped
@@ -20,14 +21,9 @@
 
 #include "gi2d_codec_core.h"
 
-namespace gi2d {
+#include "gi2d_sample_core.h"
 
-#define GI2D_FSAMPLE_BATCH 64
-struct FilteredLds {
-    float4 a[GI2D_FSAMPLE_BATCH];  // gx, gy, sxx, sxy
-    float4 b[GI2D_FSAMPLE_BATCH];  // syy, det S, cr, cg
-    float2 c[GI2D_FSAMPLE_BATCH];  // cb, max(det S, 0)
-};
+namespace gi2d {
 
 // a c - b b with one rounding's worth of error (Kahan's difference of products): the determinant of a narrow or a
 // rank-one matrix loses every digit to cancellation when it is formed as two rounded products
@@ -39,15 +35,6 @@ __device__ __forceinline__ float det_sym(float a, float b, float c) {
     return f + e;
 }
 
-// (gi2d_sample.hip::sample_key: the inside rule and the tile rule of every sample)
-__device__ __forceinline__ int filtered_sample_key(float x, float y, int img_w, int img_h, int tiles_x, int tiles_y, bool &inside) {
-    inside = x >= 0.f && x <= (float)(img_w - 1) && y >= 0.f && y <= (float)(img_h - 1);
-    if (!inside) return tiles_x * tiles_y;
-    const int j = (int)floorf(x + 0.5f), i = (int)floorf(y + 0.5f);
-    const int tx = min(max(j >> 4, 0), tiles_x - 1), ty = min(max(i >> 4, 0), tiles_y - 1);
-    return ty * tiles_x + tx;
-}
-
 // The footprint is admitted iff it is finite, positive semi-definite and its trace -- which bounds the larger eigenvalue
 // -- is at most max_filter: separate fp32 operations (tests/helpers_sample_filtered.py restates them).
 __device__ __forceinline__ bool footprint_admitted(float qxx, float qxy, float qyy, float max_filter) {
@@ -57,22 +44,6 @@ __device__ __forceinline__ bool footprint_admitted(float qxx, float qxy, float q
     const float lhs = qxx * qyy, rhs = qxy * qxy, trace = qxx + qyy;
     return finite && qxx >= 0.f && qyy >= 0.f && lhs >= rhs && trace <= max_filter;
 }
-
-// (gi2d_sample.hip::wave_min_dpp / wave_max_dpp)
-__device__ __forceinline__ float filtered_wave_min(float x) {
-    int v = __float_as_int(x);
-#define GI2D_DPP_FMIN(ctrl, row_mask) \
-    v = __float_as_int(fminf(__int_as_float(v), __int_as_float(__builtin_amdgcn_update_dpp(0x7f800000, v, ctrl, row_mask, 0xf, false))))
-    GI2D_DPP_FMIN(0x111, 0xf);
-    GI2D_DPP_FMIN(0x112, 0xf);
-    GI2D_DPP_FMIN(0x114, 0xf);
-    GI2D_DPP_FMIN(0x118, 0xf);
-    GI2D_DPP_FMIN(0x142, 0xa);
-    GI2D_DPP_FMIN(0x143, 0xc);
-#undef GI2D_DPP_FMIN
-    return __int_as_float(__builtin_amdgcn_readlane(v, 63));
-}
-__device__ __forceinline__ float filtered_wave_max(float x) { return -filtered_wave_min(-x); }
 
 // The footprint of one sample as the pair loop reads it.
 struct Footprint {
@@ -108,13 +79,7 @@ __device__ __forceinline__ void filtered_pair(const float4 A, const float4 B, co
     o2 = __builtin_fmaf(Cc.x, am, o2);
 }
 
-// The walk below -- lane -> sample, the waterfall over the wave's tiles, the staging, the ballot compaction under SKIP -- is
-// gi2d_sample.hip::sample_points_kernel's: ITS TWIN, to be changed together with it.  (Kept as a copy, not factored out,
-// so that the existing kernels' device code stays what it was; DESIGN.md 3.8 "Sample gradients".)  What differs: a sample
-// whose footprint is not admitted is outside; an entry is staged as (centre, S, det S, colour); SKIP tests the alpha >=
-// 1/255 box of the WIDEST admitted footprint, the conic of S + max_filter I, against the served lanes' positions --
-// T <= S + max_filter I for every admitted Q, so sigma under T is at least sigma under the widest, and an entry dropped
-// here fails the pair test at every served sample whatever its footprint is.
+// sample_points_kernel with a footprint per sample: a sample whose footprint is not admitted is outside.
 template <int DTYPE, int LAYOUT, bool GRID, bool SKIP>
 __global__ __launch_bounds__(256) void sample_points_filtered_kernel(
     int n, int capacity, int tiles_x, int tiles_y, int img_w, int img_h, const int32_t *__restrict__ gids_sorted,
@@ -123,24 +88,12 @@ __global__ __launch_bounds__(256) void sample_points_filtered_kernel(
     long long num_samples, const float2 *__restrict__ points, const float *__restrict__ footprints, float max_filter,
     const int32_t *__restrict__ perm, int grid_w, int grid_h, float fill0, float fill1, float fill2, void *__restrict__ out_) {
     typedef typename PixelType<DTYPE>::type T;
-    __shared__ FilteredLds lds[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    FilteredLds &sm = lds[wv];
+    __shared__ SampleLds lds[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    SampleLds &sm = lds[wv];
 
-    // ---- lane -> sample
     bool valid;
-    long long s;
-    if (GRID) {
-        const int blocks_x = (grid_w + 15) >> 4;
-        const int bx = (int)(blockIdx.x % (unsigned)blocks_x), by = (int)(blockIdx.x / (unsigned)blocks_x);
-        const int col = bx * 16 + (lane & 15), row = by * 16 + wv * 4 + (lane >> 4);
-        valid = col < grid_w && row < grid_h;
-        s = (long long)row * grid_w + col;
-    } else {
-        s = ((long long)blockIdx.x * 4 + wv) * 64 + lane;
-        valid = s < num_samples;
-        if (valid && perm != nullptr) s = min(max((long long)perm[s], 0ll), num_samples - 1);
-    }
+    const long long s = sample_of_lane<GRID>(lane, wv, num_samples, perm, grid_w, grid_h, valid);
     float px = 0.f, py = 0.f;
     Footprint q{0.f, 0.f, 0.f, 0.f, 0.f};
     if (valid) {
@@ -149,7 +102,7 @@ __global__ __launch_bounds__(256) void sample_points_filtered_kernel(
         q.qxx = footprints[3 * s], q.qxy = footprints[3 * s + 1], q.qyy = footprints[3 * s + 2];
     }
     bool inside;
-    const int key = filtered_sample_key(px, py, img_w, img_h, tiles_x, tiles_y, inside);
+    const int key = sample_key(px, py, img_w, img_h, tiles_x, tiles_y, inside);
     inside = inside && valid && footprint_admitted(q.qxx, q.qxy, q.qyy, max_filter);
     q.m2qxy = -2.f * q.qxy;
     q.det = det_sym(q.qxx, q.qxy, q.qyy);
@@ -163,25 +116,23 @@ __global__ __launch_bounds__(256) void sample_points_filtered_kernel(
     // ---- the tiles this wave holds, one after the other (wave-uniform: `todo` is a ballot)
     unsigned long long todo = nothing ? 0ull : __ballot(inside);
     while (todo != 0ull) {
-        const int t = wave_read_lane(key, __ffsll((long long)todo) - 1);  // a scalar: list bounds and staging are uniform
-        const bool mine = inside && key == t;  // (all of them unserved: the lanes of a tile are served together)
+        // (this step is sample_next_tile's, in the kernel's own text: DESIGN.md 3.8 "One sample walk")
+        const int t = wave_read_lane(key, __ffsll((long long)todo) - 1);
+        const bool mine = inside && key == t;
         todo &= ~__ballot(mine);
         int2 range = make_int2(0, 0);
-        if (t >= 0 && t < tile_bins_rows) range = tile_bins[t];
-        const int start = min(max(range.x, 0), capacity);
-        const int end = min(max(range.y, start), capacity);
-        if (start >= end) continue;
-        float bx0 = 0.f, bx1 = 0.f, by0 = 0.f, by1 = 0.f;  // what the served lanes' positions span
-        if (SKIP) {
-            const float inf = __int_as_float(0x7f800000);
-            bx0 = filtered_wave_min(mine ? px : inf), bx1 = filtered_wave_max(mine ? px : -inf);
-            by0 = filtered_wave_min(mine ? py : inf), by1 = filtered_wave_max(mine ? py : -inf);
-        }
-        int g_next = start + lane < end ? gids_sorted[start + lane] : 0;  // (one batch ahead of its use)
-        for (int base = start; base < end; base += GI2D_FSAMPLE_BATCH) {
-            const int m = min(GI2D_FSAMPLE_BATCH, end - base);
+        if (t < tile_bins_rows) range = tile_bins[t];
+        SampleTile tile;
+        tile.start = min(max(range.x, 0), capacity);
+        tile.end = min(max(range.y, tile.start), capacity);
+        if (tile.start >= tile.end) continue;
+        const SampleBox box = sample_box<SKIP>(mine, px, py);
+        int g_next = tile.start + lane < tile.end ? gids_sorted[tile.start + lane] : 0;  // (one batch ahead of its use)
+        for (int base = tile.start; base < tile.end; base += GI2D_SAMPLE_BATCH) {
+            // (this batch is sample_stage_batch's, in the kernel's own text: DESIGN.md 3.8 "One sample walk")
+            const int m = min(GI2D_SAMPLE_BATCH, tile.end - base);
             const int g = min(max(g_next, 0), n - 1);
-            if (base + GI2D_FSAMPLE_BATCH + lane < end) g_next = gids_sorted[base + GI2D_FSAMPLE_BATCH + lane];
+            if (base + GI2D_SAMPLE_BATCH + lane < tile.end) g_next = gids_sorted[base + GI2D_SAMPLE_BATCH + lane];
             bool keep = false;
             float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A;
             float2 Cc = make_float2(0.f, 0.f);
@@ -200,8 +151,8 @@ __global__ __launch_bounds__(256) void sample_points_filtered_kernel(
                     float hx, hy;
                     cull_extent(xy.x, xy.y, wyy * rw, -sxy * rw, wxx * rw, 1.f, hx, hy);
                     // hx < 0: can never land; GI2D_CULL_FULL: no finite box, every sample is evaluated
-                    keep = hx >= 0.f && (hx >= GI2D_CULL_FULL || (xy.y - hy <= by1 && xy.y + hy >= by0 &&
-                                                                  xy.x - hx <= bx1 && xy.x + hx >= bx0));
+                    keep = hx >= 0.f && (hx >= GI2D_CULL_FULL || (xy.y - hy <= box.y1 && xy.y + hy >= box.y0 &&
+                                                                  xy.x - hx <= box.x1 && xy.x + hx >= box.x0));
                 }
             }
             const unsigned long long mask = __ballot(keep);
@@ -261,9 +212,6 @@ __global__ __launch_bounds__(256) void codec_decode_field_kernel(
 
 using namespace gi2d;
 
-// samples of one launch: 2^31 - 1 workgroups of 256
-#define GI2D_FSAMPLE_MAX (0x7fffffffLL * 256)
-
 extern "C" {
 
 int gi2d_codec_decode_field(int kind, int n, int xy_bits, int p0_bits, int p1_bits, int color_bits, const float *side_host,
@@ -306,49 +254,24 @@ int gi2d_sample_points_filtered(int n, int capacity, int tiles_x, int tiles_y, u
                                 const float *footprints, float max_filter, const int32_t *perm, int grid_w, int grid_h,
                                 const float *fill_host, int dtype, int layout, void *out, gi2d_stream_t st) {
     const char *what = "sample points filtered";
-    const auto fail = [&](const char *why) {
-        set_error((std::string(what) + ": " + why).c_str());
-        return GI2D_ERR_INVALID_ARGUMENT;
-    };
-    // (the refusals of gi2d_sample_points, in its order)
-    if (!pixel_format_ok(dtype, layout)) return fail("unknown format (dtype 0..2, layout 0..2)");
-    if (n < 0 || capacity < 0 || tiles_x < 0 || tiles_y < 0 || rows < 0 || num_samples < 0 || grid_w < 0 || grid_h < 0)
-        return fail("negative size");
-    if (capacity > 0x7fffffff - GI2D_FSAMPLE_BATCH) return fail("capacity too large for 32-bit list positions");
-    if ((long long)tiles_x * GI2D_TILE < (long long)w || (long long)tiles_y * GI2D_TILE < (long long)h)
-        return fail("tile grid does not cover the image");
-    if ((long long)tiles_x * tiles_y >= 0x7fffffffLL || w > 0x7fffffffu || h > 0x7fffffffu) return fail("tile grid too large");
-    if (grid_w > 0 && (long long)grid_w * grid_h != num_samples) return fail("grid_width * grid_height is not num_samples");
-    if (grid_w > 0 && perm) return fail("a permutation and a grid exclude each other");
-    if (num_samples > GI2D_FSAMPLE_MAX || (perm && num_samples > 0x7fffffffLL))
-        return fail("more samples than one launch's grid (or a 32-bit permutation) can hold");
+    if (!pixel_format_ok(dtype, layout)) return sample_refused(what, "unknown format (dtype 0..2, layout 0..2)");
+    SampleArgs a{n, capacity, tiles_x, tiles_y, w, h, gids, bins, rows, xys, covs, colors, num_samples, points_xy, perm,
+                 grid_w, grid_h};
+    if (sample_sizes_refused(what, a)) return GI2D_ERR_INVALID_ARGUMENT;
     if (!(max_filter > 0.f) || !(max_filter <= GI2D_CODEC_AFFINE_MAX_PREFILTER))
-        return fail("max_filter must lie in 0 (excluded) .. 4 source pixels^2");
+        return sample_refused(what, "max_filter must lie in 0 (excluded) .. 4 source pixels^2");
     if (num_samples == 0) return GI2D_OK;
-    if (n == 0) capacity = 0, rows = 0;  // no gaussian: no list is read
-    if (!points_xy || !footprints || !out || (rows > 0 && !bins) ||
-        (capacity > 0 && rows > 0 && (!gids || !xys || !covs || !colors)))
-        return fail("null pointer");
+    const long long blocks = sample_arrays_checked(what, a, !footprints || !out);
+    if (blocks < 0) return GI2D_ERR_INVALID_ARGUMENT;
     const float f0 = fill_host ? fill_host[0] : 0.f, f1 = fill_host ? fill_host[1] : 0.f, f2 = fill_host ? fill_host[2] : 0.f;
-#ifdef GI2D_SAMPLE_NO_SKIP /* development variant: the walk without the per-wave skip (timing aid) */
-    constexpr bool skip = false;
-#else
-    constexpr bool skip = true;
-#endif
-    // a grid: one workgroup per 16x16 block of the lattice (blocks <= samples); a flat list: 256 samples per workgroup
-    const long long blocks = grid_w > 0 ? (long long)((grid_w + 15) >> 4) * ((grid_h + 15) >> 4) : (num_samples + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail("more samples than one launch's grid can hold");
 #define GI2D_FSAMPLE(D, L)                                                                                               \
-    if (grid_w > 0)                                                                                                      \
-        hipLaunchKernelGGL((sample_points_filtered_kernel<D, L, true, skip>), dim3((unsigned)blocks), dim3(256), 0,      \
-                           (hipStream_t)st, n, capacity, tiles_x, tiles_y, (int)w, (int)h, gids, (const int2 *)bins,     \
-                           rows, (const float2 *)xys, covs, colors, status, num_samples, (const float2 *)points_xy,      \
-                           footprints, max_filter, perm, grid_w, grid_h, f0, f1, f2, out);                               \
-    else                                                                                                                 \
-        hipLaunchKernelGGL((sample_points_filtered_kernel<D, L, false, skip>), dim3((unsigned)blocks), dim3(256), 0,     \
-                           (hipStream_t)st, n, capacity, tiles_x, tiles_y, (int)w, (int)h, gids, (const int2 *)bins,     \
-                           rows, (const float2 *)xys, covs, colors, status, num_samples, (const float2 *)points_xy,      \
-                           footprints, max_filter, perm, grid_w, grid_h, f0, f1, f2, out)
+    sample_for_flag(grid_w > 0, [&](auto grid) {                                                                         \
+        hipLaunchKernelGGL((sample_points_filtered_kernel<D, L, decltype(grid)::value, kSampleSkip>),                    \
+                           dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)st, n, a.capacity, tiles_x, tiles_y, (int)w, \
+                           (int)h, gids, (const int2 *)bins, a.rows, (const float2 *)xys, covs, colors, status,            \
+                           num_samples, (const float2 *)points_xy, footprints, max_filter, perm, grid_w, grid_h, f0, f1, \
+                           f2, out);                                                                                     \
+    })
     GI2D_FOR_FORMAT(dtype, layout, GI2D_FSAMPLE)
 #undef GI2D_FSAMPLE
     return check_launch(what);
