@@ -84,7 +84,10 @@ sub-pixel registration, an edge map -- once, no double backward.  Where a warp r
 its own: Decoder.field(stream, max_filter=v) widens the lists by the prefilter (v, 0, v) and keeps every gaussian's
 covariance (gi2d_codec_decode_field), and Field.sample(points, footprint=) then evaluates each (sample, gaussian) pair with
 covariance S + Q and colour * sqrt(det S / det(S + Q)) for the sample's own variance Q (gi2d_sample_points_filtered,
-csrc/gi2d_sample_filtered.hip); grid_footprints derives Q from a sampling grid.
+csrc/gi2d_sample_filtered.hip); grid_footprints derives Q from a sampling grid.  The filtered sample is differentiable
+too, in the position and in Q: Field.jacobian / Field.sample_vjp with footprint= (and footprint_grad=True) give both
+derivatives (gi2d_sample_points_filtered_grad, csrc/gi2d_sample_filtered_grad.hip), and Field.sample_filtered is the
+autograd form -- a warp whose scale is being fitted sets the footprint, and the footprint's gradient reaches the scale.
 
 Format version 1 (little-endian; INTEGRATION.md "Packed stream" has the record layout):
 
@@ -1422,8 +1425,8 @@ class Field:
         tensor on the field's device shaped like points with 3 in place of 2; a number q, short for (q, 0, q) at every
         sample; or "auto" for a grid, grid_footprints(points, self.max_filter).  A footprint that is not finite, not
         positive semi-definite or whose trace exceeds max_filter is not admitted: the sample is `fill`, like an outside
-        one.  One launch of gi2d_sample_points_filtered in place of gi2d_sample_points; not differentiable (points that
-        require grad are refused)."""
+        one.  One launch of gi2d_sample_points_filtered in place of gi2d_sample_points.  This call is not the
+        differentiable one (points that require grad are refused): sample_filtered is."""
         if footprint is not None:
             return self._sample(points, out, dtype, layout, fill, presort, footprint)[0]
         if isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled():
@@ -1459,45 +1462,48 @@ class Field:
                   C.c_void_p(keys.data_ptr()), st)
         return torch.sort(keys, stable=True).indices.to(torch.int32)
 
-    def _check_footprint(self, footprint, points, grid: bool) -> torch.Tensor:
-        """The checks on `footprint` -> the float32 tensor the launch reads (a number is expanded, "auto" computed)."""
+    def _check_footprint(self, footprint, points, grid: bool, who: str = "sample") -> torch.Tensor:
+        """The checks on `footprint` -> the float32 tensor the launch reads (a number is expanded, "auto" computed).
+        who: "sample" refuses points that require grad; the calls that ARE derivatives take them as they are."""
         if self.max_filter <= 0.0:
-            raise ValueError("sample: footprint needs a field made with max_filter > 0 (Decoder.field(stream, max_filter=v))")
-        if points.requires_grad and torch.is_grad_enabled():
-            raise ValueError("sample: filtered samples are not differentiable: points that require grad take no footprint")
+            raise ValueError(f"{who}: footprint needs a field made with max_filter > 0 (Decoder.field(stream, max_filter=v))")
+        if who == "sample" and points.requires_grad and torch.is_grad_enabled():
+            raise ValueError("sample: points that require grad take no footprint here: sample_filtered(points, footprint) "
+                             "is the differentiable filtered sample")
         want = (*points.shape[:-1], 3)
         if isinstance(footprint, str):
             if footprint != "auto" or not grid:
-                raise ValueError(f"sample: footprint {footprint!r}: 'auto' (for a grid [Ho, Wo, 2]), a number or a tensor")
+                raise ValueError(f"{who}: footprint {footprint!r}: 'auto' (for a grid [Ho, Wo, 2]), a number or a tensor")
             return grid_footprints(points, self.max_filter)
         if not isinstance(footprint, torch.Tensor):
-            _finite_numbers("sample", footprint=footprint)
+            _finite_numbers(who, footprint=footprint)
             q = float(footprint)
             with np.errstate(over="ignore"):
                 if not (q >= 0.0 and float(np.float32(q) + np.float32(q)) <= float(np.float32(self.max_filter))):
-                    raise ValueError(f"sample: footprint {q}: the variance (q, 0, q) must be >= 0 with 2 q <= max_filter = "
+                    raise ValueError(f"{who}: footprint {q}: the variance (q, 0, q) must be >= 0 with 2 q <= max_filter = "
                                      f"{self.max_filter}")
             return torch.tensor((q, 0.0, q), dtype=torch.float32, device=self.dev).expand(want).contiguous()
         if (footprint.dtype != torch.float32 or tuple(footprint.shape) != want or footprint.device != self.dev
                 or not footprint.is_contiguous()):
-            raise ValueError(f"sample: footprint must be a contiguous float32 tensor of shape {want} on {self.dev}")
+            raise ValueError(f"{who}: footprint must be a contiguous float32 tensor of shape {want} on {self.dev}")
         return footprint
 
-    def _sample(self, points, out, dtype, layout, fill, presort, footprint=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-        """sample's checks and launches -> (the samples, the permutation the work was ordered by or None)."""
+    def _sample(self, points, out, dtype, layout, fill, presort, footprint=None, who: str = "sample"):
+        """sample's checks and launches -> (the samples, the permutation the work was ordered by or None, the footprint
+        tensor the launch read or None)."""
         fmt = _format(dtype, layout)
-        grid, p, sort = self._check_points("sample", points, presort)
+        grid, p, sort = self._check_points(who, points, presort)
         try:
             fill = tuple(fill)
         except TypeError:
-            raise ValueError(f"sample: fill {fill!r}: three finite floats") from None
+            raise ValueError(f"{who}: fill {fill!r}: three finite floats") from None
         if len(fill) != 3:
-            raise ValueError(f"sample: fill {fill!r}: three finite floats")
-        _finite_numbers("sample", fill_r=fill[0], fill_g=fill[1], fill_b=fill[2])
+            raise ValueError(f"{who}: fill {fill!r}: three finite floats")
+        _finite_numbers(who, fill_r=fill[0], fill_g=fill[1], fill_b=fill[2])
         with np.errstate(over="ignore"):
             fill = tuple(float(np.float32(v)) for v in fill)
         if not all(math.isfinite(v) for v in fill):
-            raise ValueError(f"sample: fill {fill}: not finite in float32")
+            raise ValueError(f"{who}: fill {fill}: not finite in float32")
         if grid:
             shape = fmt.shape(points.shape[0], points.shape[1])
         else:
@@ -1505,11 +1511,11 @@ class Field:
         if out is not None:
             _check_out(out, shape, fmt.dtype, self.dev)
         if footprint is not None:  # (after every other check: "auto" launches torch kernels of its own)
-            footprint = self._check_footprint(footprint, points, grid)
+            footprint = self._check_footprint(footprint, points, grid, who)
         if out is None:
             out = torch.empty(shape, dtype=fmt.dtype, device=self.dev)
         if p == 0:
-            return out, None
+            return out, None, footprint
         ptr = lambda t: C.c_void_p(t.data_ptr())
         tail = ((C.c_float * 3)(*fill), *fmt.ids, ptr(out))
         if footprint is not None:
@@ -1517,7 +1523,7 @@ class Field:
                                 own=(ptr(footprint), self.max_filter), tail=tail)
         else:
             perm = self._launch("gi2d_sample_points", points, grid, p, sort, forms=self.conics, opacities=(None,), tail=tail)
-        return out, perm
+        return out, perm, footprint
 
     def _launch(self, entry: str, points, grid: bool, p: int, sort: bool, *, forms, opacities, tail, own=(), perm=None):
         """One sampling launch: the device context, the stream, the presort (or `perm`, a forward's own), the grid's sizes
@@ -1535,47 +1541,100 @@ class Field:
                       ptr(points), *own, ptr(perm) if sort else None, gw, gh, *tail, st)
         return perm if sort else None
 
-    def jacobian(self, points: torch.Tensor, presort: Optional[bool] = None, clamped: bool = True,
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def sample_filtered(self, points: torch.Tensor, footprint, fill: Sequence[float] = (0.0, 0.0, 0.0),
+                        presort: Optional[bool] = None) -> torch.Tensor:
+        """The DIFFERENTIABLE filtered sample (DESIGN.md 3.8 "Filtered sample gradients"; a field made with max_filter > 0
+        only): sample(points, footprint=footprint, fill=fill, presort=presort) as float32 "hwc" -- the same launches, the
+        same bits -- differentiable in `points` and / or in a tensor `footprint`, whichever requires grad (under
+        torch.is_grad_enabled()): a torch.autograd.Function whose backward is ONE gated launch of
+        gi2d_sample_points_filtered_grad on the forward's permutation, which forms the footprint's sums only when the
+        footprint's gradient is asked for.  The gradient is the exact derivative of the fit's smooth pieces -- zero in a
+        channel the [0, 1] clamp holds, at an outside position and at a footprint that is not admitted (the admission
+        border, like the cut-off and the tile borders, is a jump of the function, not a slope).  A number or "auto" is a
+        constant: "auto" is grid_footprints of the DETACHED grid, so the dependence of an automatic footprint on the grid
+        is not differentiated -- form the footprint from the warp's parameters yourself where that matters.  Once
+        differentiable.  With nothing requiring grad it is sample(..., footprint=)."""
+        needs = [isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled() for t in (points, footprint)]
+        if footprint is None:
+            raise ValueError("sample_filtered: footprint: a tensor, a number or 'auto' (sample is the point sample)")
+        if not any(needs):
+            return self._sample(points, None, None, None, fill, presort, footprint, who="sample_filtered")[0]
+        return _FilteredSampleFunction.apply(points, footprint, self, fill, presort)
+
+    def jacobian(self, points: torch.Tensor, presort: Optional[bool] = None, clamped: bool = True, out=None, footprint=None,
+                 footprint_grad: bool = False):
         """The derivative of sample(points) in the positions (gi2d_sample_points_grad; DESIGN.md 3.8 "Sample gradients"):
         float32 [P, 3, 2] or [Ho, Wo, 3, 2], the last axis (d/dx, d/dy) of the channel, in values per source pixel.  It is
         the exact derivative of the fit's smooth pieces, term by term over the pairs that land -- the cut-off and the
         tile borders are jumps of the function itself, not slopes.  clamped (the default): a channel whose sum the [0, 1]
         clamp holds is zero, the derivative of the VALUE sample returns; False: the derivative of the unclamped sum.
         An outside position (a NaN, an infinity) gives zeros.  points, presort: as in sample; no host wait.  ValueError,
-        before any launch, for anything else."""
-        return self._grad("jacobian", points, None, presort, clamped, out)
+        before any launch, for anything else.
+        footprint (as in sample; DESIGN.md 3.8 "Filtered sample gradients"): the derivative of the FILTERED sample
+        sample(points, footprint=footprint) instead, in the same shape, by gi2d_sample_points_filtered_grad; a footprint
+        that is not admitted gives zeros.  footprint_grad=True (with a footprint only): a pair, the second element the
+        derivative in the footprint, float32 [P, 3, 3] or [Ho, Wo, 3, 3] with (d/dqxx, d/dqxy, d/dqyy) last, in values
+        per source pixel^2 -- qxy stands for both off-diagonal places of Q; `out` is then a pair too.  The position
+        result has the same bits with and without it."""
+        return self._grad("jacobian", points, None, presort, clamped, out, footprint=footprint, footprint_grad=footprint_grad)
 
     def sample_vjp(self, points: torch.Tensor, v: torch.Tensor, presort: Optional[bool] = None, clamped: bool = True,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out=None, footprint=None, footprint_grad: bool = False):
         """The vector-Jacobian product of sample in its positions: float32 [P, 2] or [Ho, Wo, 2], entry s = sum over the
         channels k, in order, of v[s][k] * jacobian[s][k] -- in one launch, without the Jacobian in memory.  v: float32,
         contiguous, on the field's device, shaped like sample's float32 "hwc" output for these points ([P, 3] or [Ho, Wo,
-        3]).  What the backward of a differentiable sample calls.  Everything else as in jacobian."""
+        3]).  What the backward of a differentiable sample calls.  Everything else as in jacobian: with a footprint the
+        product with the filtered sample's Jacobian, with footprint_grad=True a pair whose second element, float32 [P, 3]
+        or [Ho, Wo, 3], is the product with the footprint Jacobian."""
         self._check_points("sample_vjp", points, presort)  # (v's shape is read off points)
         want =(*points.shape[:-1], 3)
         if (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != want or v.device != self.dev
                 or not v.is_contiguous()):
             raise ValueError(f"sample_vjp: v must be a contiguous float32 tensor of shape {want} on {self.dev}")
-        return self._grad("sample_vjp", points, v, presort, clamped, out)
+        return self._grad("sample_vjp", points, v, presort, clamped, out, footprint=footprint, footprint_grad=footprint_grad)
 
-    def _grad(self, who: str, points, v, presort, clamped, out, perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _grad(self, who: str, points, v, presort, clamped, out, perm: Optional[torch.Tensor] = None, footprint=None,
+              footprint_grad: bool = False):
         """jacobian (v None) and sample_vjp: the checks, the presort (or `perm`, a forward's own) and the one launch."""
         grid, p, sort = self._check_points(who, points, presort)
         if not isinstance(clamped, bool):
             raise ValueError(f"{who}: clamped {clamped!r}: True or False")
-        shape = (*points.shape[:-1], 3, 2) if v is None else (*points.shape[:-1], 2)
-        if out is not None:
-            _check_out(out, shape, torch.float32, self.dev)
+        if not isinstance(footprint_grad, bool):
+            raise ValueError(f"{who}: footprint_grad {footprint_grad!r}: True or False")
+        if footprint_grad and footprint is None:
+            raise ValueError(f"{who}: footprint_grad needs a footprint")
+        lead = tuple(points.shape[:-1])
+        shapes = [(*lead, 3, 2) if v is None else (*lead, 2)]
+        if footprint_grad:
+            shapes.append((*lead, 3, 3) if v is None else (*lead, 3))
+        if out is None:
+            outs = [None] * len(shapes)
+        elif footprint_grad:
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise ValueError(f"{who}: with footprint_grad `out` is a pair of tensors of shapes {shapes[0]} and {shapes[1]}")
+            outs = list(out)
         else:
-            out = torch.empty(shape, dtype=torch.float32, device=self.dev)
+            outs = [out]
+        for o, shape in zip(outs, shapes):
+            if o is not None:
+                _check_out(o, shape, torch.float32, self.dev)
+        if footprint is not None:  # (after every other check: "auto" launches torch kernels of its own)
+            footprint = self._check_footprint(footprint, points, grid, who).detach()
+        outs = [torch.empty(shape, dtype=torch.float32, device=self.dev) if o is None else o for o, shape in zip(outs, shapes)]
+        result = tuple(outs) if footprint_grad else outs[0]
         if p == 0:
-            return out
+            return result
         ptr = lambda t: C.c_void_p(t.data_ptr())
-        self._launch("gi2d_sample_points_grad", points, grid, p, sort, perm=perm, forms=self.conics, opacities=(None,),
-                     tail=(int(clamped), None if v is None else ptr(v), ptr(out) if v is None else None,
-                           None if v is None else ptr(out)))
-        return out
+        vp = None if v is None else ptr(v)
+        if footprint is None:
+            self._launch("gi2d_sample_points_grad", points, grid, p, sort, perm=perm, forms=self.conics, opacities=(None,),
+                         tail=(int(clamped), vp, ptr(outs[0]) if v is None else None, None if v is None else ptr(outs[0])))
+        else:
+            mine = (ptr(outs[0]), ptr(outs[1]) if footprint_grad else None)
+            self._launch("gi2d_sample_points_filtered_grad", points, grid, p, sort, perm=perm, forms=self.covs, opacities=(),
+                         own=(ptr(footprint), self.max_filter),
+                         tail=(int(clamped), vp, *(mine if v is None else (None, None)), *((None, None) if v is None else mine)))
+        return result
 
 
 class _SampleFunction(torch.autograd.Function):
@@ -1584,7 +1643,7 @@ class _SampleFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, points, fld, fill, presort):
-        out, perm = fld._sample(points.detach(), None, None, None, fill, presort)
+        out, perm, _ = fld._sample(points.detach(), None, None, None, fill, presort)
         ctx.fld, ctx.presort = fld, presort
         ctx.save_for_backward(points, *(() if perm is None else (perm,)))
         return out
@@ -1596,6 +1655,32 @@ class _SampleFunction(torch.autograd.Function):
         v = v.to(torch.float32).contiguous()
         grad = ctx.fld._grad("sample_vjp", points.detach(), v, ctx.presort, True, None, perm=perm[0] if perm else None)
         return grad, None, None, None
+
+
+class _FilteredSampleFunction(torch.autograd.Function):
+    """Field.sample_filtered where the points or the footprint require grad: the forward is sample's own launches, the
+    backward one gated launch of gi2d_sample_points_filtered_grad on the permutation the forward sorted by, with the
+    footprint's sums only where ctx.needs_input_grad asks for them.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, points, footprint, fld, fill, presort):
+        given = footprint.detach() if isinstance(footprint, torch.Tensor) else footprint
+        out, perm, used = fld._sample(points.detach(), None, None, None, fill, presort, given, who="sample_filtered")
+        ctx.fld, ctx.presort = fld, presort
+        ctx.save_for_backward(points, used, *(() if perm is None else (perm,)))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v):
+        points, used, *perm = ctx.saved_tensors
+        v = v.to(torch.float32).contiguous()
+        foot = bool(ctx.needs_input_grad[1])
+        got = ctx.fld._grad("sample_vjp", points.detach(), v, ctx.presort, True, None, perm=perm[0] if perm else None,
+                            footprint=used, footprint_grad=foot)
+        gp, gq = got if foot else (got, None)
+        return (gp if ctx.needs_input_grad[0] else None), gq, None, None, None
+
 
 class Decoder:
     """Decodes streams on one device.  Payload staging, the fast-path workspace and the status words are kept between

@@ -21,63 +21,9 @@
 
 #include "gi2d_codec_core.h"
 
-#include "gi2d_sample_core.h"
+#include "gi2d_sample_filtered_core.h"
 
 namespace gi2d {
-
-// a c - b b with one rounding's worth of error (Kahan's difference of products): the determinant of a narrow or a
-// rank-one matrix loses every digit to cancellation when it is formed as two rounded products
-__device__ __forceinline__ float det_sym(float a, float b, float c) {
-#pragma clang fp contract(off)
-    const float w = b * b;
-    const float e = __builtin_fmaf(-b, b, w);  // w - b b, exact
-    const float f = __builtin_fmaf(a, c, -w);
-    return f + e;
-}
-
-// The footprint is admitted iff it is finite, positive semi-definite and its trace -- which bounds the larger eigenvalue
-// -- is at most max_filter: separate fp32 operations (tests/helpers_sample_filtered.py restates them).
-__device__ __forceinline__ bool footprint_admitted(float qxx, float qxy, float qyy, float max_filter) {
-#pragma clang fp contract(off)
-    const float big = 3.4028235e38f;
-    const bool finite = __builtin_fabsf(qxx) <= big && __builtin_fabsf(qxy) <= big && __builtin_fabsf(qyy) <= big;
-    const float lhs = qxx * qyy, rhs = qxy * qxy, trace = qxx + qyy;
-    return finite && qxx >= 0.f && qyy >= 0.f && lhs >= rhs && trace <= max_filter;
-}
-
-// The footprint of one sample as the pair loop reads it.
-struct Footprint {
-    float qxx, qxy, qyy;
-    float m2qxy;  // -2 qxy
-    float det;    // det Q (det_sym)
-};
-
-// One staged entry on this lane's sample.  det T = det S + (sxx qyy + syy qxx - 2 sxy qxy) + det Q, three terms none of
-// which is negative for positive semi-definite S and Q, in place of txx tyy - txy txy whose two products cancel for a
-// narrow gaussian; one v_rcp_f32 gives the inverse's scale for the conic (pre-scaled by log2(e): scale_conic) and for
-// the gain sqrt(max(det S, 0) / det T); then the quadratic form and the pair test of sample_pair with the limit of
-// opacity 1.  An entry with !(det T > 0) -- a NaN too -- adds nothing, nor does a pair whose sigma is a NaN.
-__device__ __forceinline__ void filtered_pair(const float4 A, const float4 B, const float2 Cc, const Footprint q, unsigned lim,
-                                              float px, float py, float &o0, float &o1, float &o2) {
-#pragma clang fp contract(off)
-    const float txx = A.z + q.qxx, txy = A.w + q.qxy, tyy = B.x + q.qyy;
-    const float cross = __builtin_fmaf(A.z, q.qyy, __builtin_fmaf(B.x, q.qxx, A.w * q.m2qxy));
-    const float det1 = (cross + q.det) + B.y;
-    const float rc = __builtin_amdgcn_rcpf(det1);
-    const float hs = rc * (0.5f * 1.4426950408889634f);
-    const float ha = tyy * hs, hc = txx * hs, hb = txy * (-2.f * hs);
-    const float gain = __builtin_amdgcn_sqrtf(Cc.y * rc);
-    const float dy = A.y - py;
-    const float bdy = hb * dy, cdy2 = __builtin_fmaf(hc * dy, dy, 0.f);
-    const float dx = A.x - px;
-    const float sig = __builtin_fmaf(dx, __builtin_fmaf(ha, dx, bdy), cdy2);
-    const float tt = gain * pair_vis(sig);
-    const bool ok = det1 > 0.f && pair_lands(sig, lim);
-    const float am = ok ? tt : 0.f;
-    o0 = __builtin_fmaf(B.z, am, o0);
-    o1 = __builtin_fmaf(B.w, am, o1);
-    o2 = __builtin_fmaf(Cc.x, am, o2);
-}
 
 // sample_points_kernel with a footprint per sample: a sample whose footprint is not admitted is outside.
 template <int DTYPE, int LAYOUT, bool GRID, bool SKIP>

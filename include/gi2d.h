@@ -999,7 +999,32 @@ int gi2d_sample_points_grad(int num_points, int capacity, int tiles_x, int tiles
  *                          Q = 0 is the point sample of the same lists.  No atomics: a sample's bits depend on the arrays,
  *                          its position and its footprint alone.  Refusals: those of gi2d_sample_points (footprints is one
  *                          more array that may not be NULL) and max_filter as above, under the prefix "sample points
- *                          filtered".  num_samples = 0 is GI2D_OK without a launch. */
+ *                          filtered".  num_samples = 0 is GI2D_OK without a launch.
+ *   gi2d_sample_points_filtered_grad   the derivative of those samples in their positions and in their footprints
+ *                          (DESIGN.md 3.8 "Filtered sample gradients"): the arguments of gi2d_sample_points_filtered up to
+ *                          grid_height with the same meaning.  Over the same list in the same order, with w = gain alpha,
+ *                          ux = a dx + b dy and uy = b dx + c dy, a pair that lands (the very test of
+ *                          gi2d_sample_points_filtered, on the same fp32 sigma) adds per channel k
+ *                            colour_k w ux to d o_k / d px,   colour_k w uy to d o_k / d py,
+ *                            colour_k w (ux ux - a) / 2 to d o_k / d qxx,   colour_k w (ux uy - b) to d o_k / d qxy,
+ *                            colour_k w (uy uy - c) / 2 to d o_k / d qyy
+ *                          (qxy fills both off-diagonal places of Q); a pair that does not land adds nothing.  gate != 0:
+ *                          channel k is zero unless its unclamped sum o_k satisfies clamp01(o_k) == o_k (false for a NaN)
+ *                          -- o_k is formed by the operations of gi2d_sample_points_filtered in its order, so the gate
+ *                          agrees with the value that call stored, bit for bit.  Outside positions, footprints that are
+ *                          not admitted and status[0] < 1 give zeros.  Two forms:
+ *                            v_out == NULL: jacobian_points f32[P,3,2] (device), [s][k] = (d o_k / d px, d o_k / d py),
+ *                              and, unless NULL, jacobian_footprints f32[P,3,3], [s][k] = the derivatives of o_k in
+ *                              (qxx, qxy, qyy); v_points and v_footprints are NULL;
+ *                            v_out f32[P,3] (device): v_points f32[P,2] and, unless NULL, v_footprints f32[P,3], [s] = the
+ *                              sum over k, in channel order, of v_out[s][k] times row [s][k] of those Jacobians (a closed
+ *                              channel, an outside and a not admitted sample leave v_out unread in effect: their terms
+ *                              are left out, not multiplied by zero); both jacobian pointers are NULL.
+ *                          jacobian_points / v_points are aligned to 8 bytes.  A NULL footprint output costs nothing: its
+ *                          sums are not formed, and the position outputs have the same bits either way.  No atomics.
+ *                          Refusals: those of gi2d_sample_points_filtered without the format's, under the prefix "sample
+ *                          points filtered grad"; a misaligned position output; any other combination of the five
+ *                          pointers.  num_samples = 0 is GI2D_OK without a launch. */
 int gi2d_codec_decode_field(int kind, int num_points, int xy_bits, int p0_bits, int p1_bits, int color_bits,
                             const float *side_host, const void *payload, size_t payload_bytes, float clip_coe,
                             unsigned img_height, unsigned img_width, float max_filter, int tiles_x, int tiles_y,
@@ -1013,6 +1038,18 @@ int gi2d_sample_points_filtered(int num_points, int capacity, int tiles_x, int t
                                 const int32_t *perm /* NULL: as given */, int grid_width /* 0: a flat list */,
                                 int grid_height, const float *fill_host /* 3 floats, NULL: zeros */, int dtype, int layout,
                                 void *out, gi2d_stream_t stream);
+int gi2d_sample_points_filtered_grad(int num_points, int capacity, int tiles_x, int tiles_y, unsigned img_width,
+                                     unsigned img_height, const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                                     int tile_bins_rows, const float *xys, const float *covs, const float *colors,
+                                     const int32_t *status, long long num_samples, const float *points_xy,
+                                     const float *footprints /* f32[P,3] */, float max_filter,
+                                     const int32_t *perm /* NULL: as given */, int grid_width /* 0: a flat list */,
+                                     int grid_height, int gate, const float *v_out /* f32[P,3], or NULL */,
+                                     float *jacobian_points /* f32[P,3,2]: iff v_out == NULL */,
+                                     float *jacobian_footprints /* f32[P,3,3] or NULL: only if v_out == NULL */,
+                                     float *v_points /* f32[P,2]: iff v_out != NULL */,
+                                     float *v_footprints /* f32[P,3] or NULL: only if v_out != NULL */,
+                                     gi2d_stream_t stream);
 
 /* ------------------------------------------------------------------ batched decode (DESIGN.md 3.8 "Batches")
  * K streams -> K pictures of ONE size and format in three launches: what the batched fitting calls above do for a fit,

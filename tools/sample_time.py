@@ -17,7 +17,8 @@ command under GI2D_LIB=<a development variant> GI2D_ALLOW_DEV_BUILD=1 (make VARI
 EXTRA='-DGI2D_SAMPLE_NO_SKIP -DGI2D_DEV_VARIANT=sample_noskip') gives the rows without the per-wave skip; --streams PATH
 keeps the two fits' streams in an .npz, so that every process of a comparison samples the same streams.
 
-    python tools/sample_time.py [--reps 100] [--streams PATH] [--out-json profiles/sample_time.json] [--trace] [--grad | --filtered]
+    python tools/sample_time.py [--reps 100] [--streams PATH] [--out-json profiles/sample_time.json] [--trace]
+                                [--grad | --filtered | --filtered-grad]
 --trace samples a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for the
 two kernels' own times.
 
@@ -39,6 +40,18 @@ of its own with the same region discipline, on a field made with max_filter = 1.
     reduce     a 170 x 256 radial grid that reduces about 3 x at its rim (2 x at the centre): the filtered sample next to
                the full decode followed by torch.nn.functional.grid_sample, and codec.grid_footprints alone
     field      Decoder.field(stream, max_filter=1.5) next to Decoder.field(stream)
+
+--filtered-grad times the derivative of the filtered sample in its positions and footprints (DESIGN.md 3.8 "Filtered sample
+gradients"; profiles/sample_filtered_grad_time.json), a run of its own with the same region discipline, on a max_filter =
+1.5 field, on the 170 x 256 reducing grid and on the 512 x 768 radial warp grid, footprints "auto" computed outside:
+    filtered_sample           Field.sample(grid, footprint=q) alone, the yardstick of the rows beside it
+    sample_vjp                Field.sample_vjp(grid, w, footprint=q): the position product alone
+    sample_vjp_footprint_grad the same with footprint_grad=True: both products in the one launch
+    jacobian                  Field.jacobian(grid, footprint=q), and jacobian_footprint_grad with footprint_grad=True
+    sample_filtered_forward_backward   Field.sample_filtered with points that require grad, then out.backward(w); and
+                              ..._both with points AND footprints that require grad
+    grid_sample_forward_backward   full decode, then torch.nn.functional.grid_sample with a grid that requires grad, then
+                              backward(w): the other route to a gradient in the positions (none exists for the footprint)
 """
 import argparse
 import json
@@ -205,6 +218,56 @@ def filtered_rows(dec, up, fld, full, warp, reps, max_filter=1.5):
     return rows
 
 
+def filtered_grad_rows(dec, up, full, warp, warp_norm, reps, max_filter=1.5):
+    """The --filtered-grad rows of one fit: {"reduce": ..., "warp": ...}."""
+    wide = dec.field(up, max_filter=max_filter)
+    red, red_norm = reducing_grid()
+    rows = {}
+    for name, pts, norm in (("reduce", red, red_norm), ("warp", warp, warp_norm)):
+        q = codec.grid_footprints(pts, max_filter)
+        lead = tuple(pts.shape[:-1])
+        gen = torch.Generator(device=DEV).manual_seed(7)
+        w = torch.randn((*lead, 3), device=DEV, generator=gen)
+        w_nchw = w.permute(2, 0, 1)[None].contiguous()
+        p_req, q_req, norm_req = pts.clone().requires_grad_(True), q.clone().requires_grad_(True), norm.clone().requires_grad_(True)
+        out_val, out_vp, out_vq = torch.empty((*lead, 3), device=DEV), torch.empty((*lead, 2), device=DEV), torch.empty((*lead, 3), device=DEV)
+        out_jp, out_jq = torch.empty((*lead, 3, 2), device=DEV), torch.empty((*lead, 3, 3), device=DEV)
+
+        def autograd_points():
+            p_req.grad = None
+            wide.sample_filtered(p_req, q).backward(w)
+
+        def autograd_both():
+            p_req.grad, q_req.grad = None, None
+            wide.sample_filtered(p_req, q_req).backward(w)
+
+        def grid_sample_route():
+            norm_req.grad = None
+            img = dec.decode(up, out=full).permute(2, 0, 1)[None]
+            torch.nn.functional.grid_sample(img, norm_req, mode="bilinear", padding_mode="border",
+                                            align_corners=True).backward(w_nchw)
+
+        autograd_both()
+        vp, vq = wide.sample_vjp(pts, w, footprint=q, footprint_grad=True)
+        assert torch.equal(p_req.grad, vp) and torch.equal(q_req.grad, vq)
+        assert torch.equal(wide.sample_vjp(pts, w, footprint=q), vp)
+        tr = q[..., 0] + q[..., 2]
+        r = {"grid": list(lead), "max_filter": max_filter, "intersections_wide": wide.count,
+             "footprint_trace_max": float(tr.max()), "footprints_not_zero": float((tr > 0).float().mean()),
+             "crc32_vjp_points": crc(vp), "crc32_vjp_footprints": crc(vq),
+             "crc32_jacobian_points": crc(wide.jacobian(pts, footprint=q))}
+        rows[name] = alternating(r, {
+            "filtered_sample": lambda: wide.sample(pts, footprint=q, out=out_val),
+            "sample_vjp": lambda: wide.sample_vjp(pts, w, footprint=q, out=out_vp),
+            "sample_vjp_footprint_grad": lambda: wide.sample_vjp(pts, w, footprint=q, footprint_grad=True, out=(out_vp, out_vq)),
+            "jacobian": lambda: wide.jacobian(pts, footprint=q, out=out_jp),
+            "jacobian_footprint_grad": lambda: wide.jacobian(pts, footprint=q, footprint_grad=True, out=(out_jp, out_jq)),
+            "sample_filtered_forward_backward": autograd_points,
+            "sample_filtered_forward_backward_both": autograd_both,
+            "grid_sample_forward_backward": grid_sample_route}, reps)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=100)
@@ -214,11 +277,13 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--grad", action="store_true")
     ap.add_argument("--filtered", action="store_true")
+    ap.add_argument("--filtered-grad", action="store_true")
     ap.add_argument("--out-json", default=None, metavar="PATH")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "sample_time.py needs the GPU"
-    assert not (a.grad and a.filtered), "--grad and --filtered are runs of their own"
-    res = {"tool": "sample_time --grad" if a.grad else "sample_time --filtered" if a.filtered else "sample_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
+    assert a.grad + a.filtered + a.filtered_grad <= 1, "--grad, --filtered and --filtered-grad are runs of their own"
+    res = {"tool": "sample_time --grad" if a.grad else "sample_time --filtered" if a.filtered else
+           "sample_time --filtered-grad" if a.filtered_grad else "sample_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
            "bits": [12, 10, 6], "reps": a.reps, "regions": 5, "sizes": {}}
     warp, warp_norm = radial_grid()
     rng = np.random.default_rng(20241021)
@@ -231,6 +296,15 @@ def main():
         full = torch.empty(H, W, 3, device=DEV)
         crop = fld.identity_grid()[y0:y0 + side, x0:x0 + side].contiguous()
         window = codec.Affine(float(x0), float(y0), 1.0, 0.0, 0.0, 1.0, side, side, 0.0)
+        if a.trace and a.filtered_grad:
+            wide = dec.field(up, max_filter=1.5)
+            for pts in (reducing_grid()[0], warp):
+                q, ones = codec.grid_footprints(pts, 1.5), torch.ones((*pts.shape[:-1], 3), device=DEV)
+                for _ in range(30):
+                    wide.sample(pts, footprint=q), wide.sample_vjp(pts, ones, footprint=q), wide.jacobian(pts, footprint=q)
+                    wide.sample_vjp(pts, ones, footprint=q, footprint_grad=True), wide.jacobian(pts, footprint=q, footprint_grad=True)
+            torch.cuda.synchronize()
+            continue
         if a.trace and a.filtered:
             wide = dec.field(up, max_filter=1.5)
             red = reducing_grid()[0]
@@ -253,6 +327,10 @@ def main():
                "longest_list": int((bins[:, 1] - bins[:, 0]).max()), "rows": {}}
         if a.grad:
             row["rows"] = grad_rows(dec, up, fld, full, warp, warp_norm, scattered, a.reps)
+            res["sizes"][str(n)] = row
+            continue
+        if a.filtered_grad:
+            row["rows"] = filtered_grad_rows(dec, up, full, warp, warp_norm, a.reps)
             res["sizes"][str(n)] = row
             continue
         if a.filtered:
