@@ -45,27 +45,6 @@ static std::string dev_switches() {
 #ifdef GI2D_INBOX_STATS
     add("GI2D_INBOX_STATS", "");
 #endif
-#ifdef GI2D_KNOCK_BOX_FILL
-    add("GI2D_KNOCK_BOX_FILL", "");
-#endif
-#ifdef GI2D_KEEP_SSE
-    add("GI2D_KEEP_SSE", "");
-#endif
-#ifdef GI2D_KEEP_VOPAC
-    add("GI2D_KEEP_VOPAC", "");
-#endif
-#ifdef GI2D_WIDE_FIT_ROWS
-    add("GI2D_WIDE_FIT_ROWS", "");
-#endif
-#ifdef GI2D_UPDATE_ROWS_AHEAD /* (only when given on the command line: the defaults are the row formats', gi2d_raster_core.h) */
-    add("GI2D_UPDATE_ROWS_AHEAD", GI2D_STR(GI2D_UPDATE_ROWS_AHEAD));
-#endif
-#ifdef GI2D_FIT_RANKS_EARLY /* (only when given on the command line: the default lives in gi2d_fast_internal.h) */
-    add("GI2D_FIT_RANKS_EARLY", GI2D_STR(GI2D_FIT_RANKS_EARLY));
-#endif
-#ifdef GI2D_HEAD_BALLOT_IDS /* (only when given on the command line: the default lives in gi2d_fast_internal.h) */
-    add("GI2D_HEAD_BALLOT_IDS", GI2D_STR(GI2D_HEAD_BALLOT_IDS));
-#endif
 #ifdef GI2D_DEV_VARIANT /* any other experiment: -DGI2D_DEV_VARIANT=name next to its own macros */
     add("GI2D_DEV_VARIANT", GI2D_STR(GI2D_DEV_VARIANT));
 #endif

@@ -153,16 +153,12 @@ struct InboxSrc {
 // answer, a thousand instructions later.  Measured (profiles/fit_rows_ab_measurements.txt): left to those lanes as a
 // dependent load in the kernel's tail -- one wave in five holds such a lane, and a launch ends with its slowest wave --
 // the update kernel takes 9.22-9.24 us instead of 8.71; requested with the first round of loads 8.96.
-#ifndef GI2D_FIT_RANKS_EARLY
-#define GI2D_FIT_RANKS_EARLY 2 /* tuning build: 0 a dependent load of the lanes that look, 1 with the first round of loads */
-#endif
 struct InboxSrcAt {
     const unsigned short *at;
-    uint4 first8;  // (unless GI2D_FIT_RANKS_EARLY == 0)
+    uint4 first8;
     bool on;
     __device__ __forceinline__ void load_first8() { first8 = *reinterpret_cast<const uint4 *>(at); }
     __device__ __forceinline__ unsigned get(int k) const {
-#if GI2D_FIT_RANKS_EARLY
         unsigned a0 = first8.x, a1 = first8.y, a2 = first8.z, a3 = first8.w;
         asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));  // (values, not loads: see InboxSrc::get)
         const int w = k >> 1;
@@ -171,9 +167,6 @@ struct InboxSrcAt {
         v = w == 2 ? a2 : v;
         v = w == 3 ? a3 : v;
         return (v >> (16 * (k & 1))) & 0xffffu;
-#else
-        return at[k];
-#endif
     }
 };
 template <class Fmt>
@@ -440,9 +433,6 @@ __device__ __forceinline__ FillPending fill_diff_begin(int g, bool member, int m
     }
     prev_box[g] = make_int4(nw.x, nw.y, f.pool, cap);
     if (!member) return f;  // its old entries are dropped by the tile pass (they fail the membership test)
-#ifdef GI2D_KNOCK_BOX_FILL /* development aid, WRONG RESULTS (a changed box enters no tile): the bound of what the walks cost */
-    if constexpr (INBOX) return f;
-#endif
     f.omnx = old.x & 0xffff, f.omxx = (int)((unsigned)old.x >> 16), f.omny = old.y & 0xffff,
     f.omxy = (int)((unsigned)old.y >> 16);
     f.mnx = mnx, f.mny = mny;
@@ -766,15 +756,14 @@ __device__ __forceinline__ HeadRow head_row_for(const int32_t *__restrict__ list
 // the smaller ones with ballots -- one round of LDS reads per id.  Where most of a wave's entries are appended ones (a
 // row's first pass after gi2d_fast_workspace_init) the lanes' own walks, all side by side, are the shorter way.  The
 // ranks are the same integers either way.
-#ifndef GI2D_HEAD_BALLOT_IDS /* (development aid: 0 leaves every id to its lane's walk) */
-#define GI2D_HEAD_BALLOT_IDS 8 /* ids per wave up to which they are ranked in turn: an id costs ceil(count_all / 64)
-                                  LDS rounds, the lanes' walks count_all trips for all of them together */
-#endif
+// ids per wave up to which they are ranked in turn: an id costs ceil(count_all / 64) LDS rounds, the lanes' walks
+// count_all trips for all of them together
+static constexpr int HEAD_BALLOT_IDS = 8;
 __device__ __forceinline__ void wave_rank_all(const int *ids, int count_all, bool has, int g, int &rank) {
     unsigned long long m = __ballot(has);
     if (m == 0ull) return;
     const int lane = threadIdx.x & 63;
-    if (__popcll(m) > GI2D_HEAD_BALLOT_IDS) {
+    if (__popcll(m) > HEAD_BALLOT_IDS) {
         if (has) {
             int r = 0;
             for (int q = 0; q < count_all; ++q) r += ((unsigned)ids[q] < (unsigned)g) ? 1 : 0;

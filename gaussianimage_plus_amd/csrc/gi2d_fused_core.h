@@ -147,9 +147,6 @@ __device__ __forceinline__ void fused_tile(
 #ifdef GI2D_KNOCK_CALL_STORES /* development aid: what the stores a fitting call can leave out cost at most (no image at all) */
     leave_image = true;
 #endif
-#ifdef GI2D_KEEP_SSE /* development aid: every pass sums and stores its tile's squared error */
-    leave_sse = false;
-#endif
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     const int pool_rows = tiles_x * tiles_y * GI2D_TILE_LIST_CAP;  // rows of `partial_big`, the row pool (PrevBox)
     static_assert(CAP <= GI2D_TILE_LIST_CAP, "at most the reference's 256 entries of a tile are rasterized");
@@ -296,11 +293,7 @@ __device__ __forceinline__ void fused_tile(
     // (INBOX: the pass that only gi2d_train_steps issues, between two update kernels of a fit -- its rows' v_opacity word
     // has no reader, so the hand-off's division is left out; every other instantiation serves the reduce calls as well.
     // Compact rows have no such word.)
-#ifdef GI2D_KEEP_VOPAC /* development aid: the division in every instantiation */
-    constexpr bool NO_VOPAC = false;
-#else
     constexpr bool NO_VOPAC = INBOX;
-#endif
     bwd_run_tile<false, false, true, WT, NO_VOPAC, FusedLdsT<CAP>, Fmt>(sm, len, cull, 0, tx0, ty0, dst, scan_incl, sm.scan_w,
                                                                         partial_g, rank_off);
     GI2D_TRACE(10);

@@ -446,33 +446,20 @@ static_assert(GI2D_BWD_ITEMS == 256, "an item's row in the hand-off buffer is it
 //   Rows of the pool (boxes of more than 32 tiles) carry no rank: ranks are read for boxes of at most eight tiles.
 // PIECES: float4 stored / loaded per row; STRIDE: float4 from one row to the next; PSTR: moments an item hands over in
 // the tile pass (bwd_run_tile; + 2 with the |v_xy| sums); AHEAD: rows the single-image update kernel requests up front
-// (-DGI2D_UPDATE_ROWS_AHEAD=k: a tuning build, both formats).
+// (2 wide, 4 compact: measured, profiles/round6_ab_measurements.txt and profiles/fit_rows_ab_measurements.txt).
 struct WideRows {
     static constexpr bool COMPACT = false;
     static constexpr int PIECES = 3, STRIDE = 4, PSTR = 9;
-#ifdef GI2D_UPDATE_ROWS_AHEAD
-    static constexpr int AHEAD = GI2D_UPDATE_ROWS_AHEAD;
-#else
     static constexpr int AHEAD = 2;
-#endif
 };
 struct FitRows {
     static constexpr bool COMPACT = true;
     static constexpr int PIECES = 2, STRIDE = 2, PSTR = 8;
-#ifdef GI2D_UPDATE_ROWS_AHEAD
-    static constexpr int AHEAD = GI2D_UPDATE_ROWS_AHEAD;
-#else
     static constexpr int AHEAD = 4;
-#endif
     __host__ __device__ static constexpr size_t rank_offset(size_t rows) { return rows * STRIDE * sizeof(float4); }
 };
-// what a fitting call on one image uses where its tile pass can store write-through (gi2d_train.hip::OneImage);
-// -DGI2D_WIDE_FIT_ROWS: the wide rows there too (the A/B build)
-#ifdef GI2D_WIDE_FIT_ROWS
-typedef WideRows FitCallRows;
-#else
+// what a fitting call on one image uses where its tile pass can store write-through (gi2d_train.hip::OneImage)
 typedef FitRows FitCallRows;
-#endif
 
 template <class Fmt, int PSTR, bool WT = false>
 __device__ __forceinline__ void store_partial_row(float4 *__restrict__ dst, const float (&acc)[PSTR], int tag,

@@ -391,9 +391,6 @@ __device__ __forceinline__ void train_reduce_update_body(int block, bool order_b
     if constexpr (Fmt::COMPACT && FILL_NEXT && INBOX) {
         inbox.src.at = reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(u.partial_g) +
                                                                 rank_offset_of<Fmt>(u.n)) + (size_t)(in_rows ? g : 0) * GI2D_FAST_S;
-#if GI2D_FIT_RANKS_EARLY == 1
-        inbox.src.load_first8();
-#endif
     }
     // the additive bound of this gaussian (one row for all when bound_stride == 0): used by both activations and the snapshot
     const Row3 bound_row = in_rows ? load_row3(P.bound, P.bound_stride ? g : 0) : Row3{0.f, 0.f, 0.f};
@@ -406,9 +403,9 @@ __device__ __forceinline__ void train_reduce_update_body(int block, bool order_b
     float acc[11];
     // (FILL_NEXT: with the sums come the ranks the tile pass staged this gaussian at -- what it needs to enter a
     // neighbouring tile through that tile's inbox instead of waiting for an atomic's answer: gi2d_fast_internal.h::Inbox)
-#if GI2D_FIT_RANKS_EARLY == 2
+    // (compact rows: the first eight ranks are requested HERE, behind the first round of loads -- 8.71 us; with that round
+    // itself 8.96, as a dependent load of the lanes that look, in the kernel's tail, 9.22-9.24: InboxSrcAt)
     if constexpr (Fmt::COMPACT && FILL_NEXT && INBOX) inbox.src.load_first8();
-#endif
     reduce_one<AHEAD, Fmt>(g, box, pbox.z, tiles_x * u.tiles_y * GI2D_TILE_LIST_CAP, u.partial_g, u.partial_big, acc,
                            FILL_NEXT && INBOX ? &inbox.src : nullptr, &ahead);
     if (g >= n) return;

@@ -26,10 +26,10 @@ _TILE = 16
 
 # The compiled op table (csrc/torch_ext/gi2d_torch_ext.cpp, built by __graft_entry__.build(): the pybind module of
 # ext.cpp:16-66 over the same C ABI).  The ctypes functions below are the fallback OF THE BINDING -- no C++ compiler at
-# hand, GI2D_BINDING=ctypes, or a development variant of the library selected with GI2D_LIB (the compiled module is
-# linked against the product library) -- never of the kernels.
+# hand, or a development variant of the library selected with GI2D_LIB (the compiled module is linked against the
+# product library) -- never of the kernels.
 _ext = None
-if os.environ.get("GI2D_BINDING", "compiled") != "ctypes" and not os.environ.get("GI2D_LIB"):
+if not os.environ.get("GI2D_LIB"):
     try:
         _lib.load()  # torch's HIP runtime and the (checked) product library first
         from ... import _gi2d_torch as _ext
