@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("GI2D_LIB") or os.path.join(_HERE, "libgi2d_hip.so")
 # include/gi2d.h is the only place the C ABI is written down: every argument list and structure below is read from it
 # (_abi.parse), once per process, at the first load() or struct().  csrc/torch_ext/build.py compiles against the same file.
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gi2d.h")
+STRUCT_HEADERS = ("gi2d_sample_field.h",)  # next to gi2d.h, which includes them: one structure each, no function
 
 _abi_parsed = None
 
@@ -33,7 +34,12 @@ def abi() -> _abi.Abi:
             raise RuntimeError(f"{HEADER_PATH} not found: the Python binding reads the C ABI from that header "
                                "(the package runs from a checkout, next to include/).")
         with open(HEADER_PATH) as f:
-            _abi_parsed = _abi.parse(f.read())
+            parsed = _abi.parse(f.read())
+        # the structure headers gi2d.h includes (they declare no function): their structures join the table
+        for name in STRUCT_HEADERS:
+            with open(os.path.join(os.path.dirname(HEADER_PATH), name)) as f:
+                parsed.structs.update(_abi.parse(f.read()).structs)
+        _abi_parsed = parsed
     return _abi_parsed
 
 

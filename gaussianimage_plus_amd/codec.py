@@ -1263,6 +1263,7 @@ def batch_shape(headers, views=None) -> Tuple[int, int]:
 _CPicture = _lib.struct("gi2d_codec_picture")
 _CAffine = _lib.struct("gi2d_codec_affine")  # the map of a picture whose descriptor says view = 2
 _CRansStream = _lib.struct("gi2d_codec_rans_stream")
+_CSampleField = _lib.struct("gi2d_sample_field")  # one Field as the batched sampling entries' table holds it
 
 
 def expansion_groups(headers) -> List[List[int]]:
@@ -1315,6 +1316,22 @@ def _checked_max_filter(who: str, max_filter) -> float:
         raise ValueError(f"{who}: max_filter {float(max_filter)}: 0 (no filtered samples) or a variance in 0 .. "
                          f"{MAX_AFFINE_PREFILTER:g} source pixels^2")
     return v
+
+
+def _checked_fill(who: str, fill) -> Tuple[float, float, float]:
+    """`fill` as the three finite float32 values a sampling launch receives."""
+    try:
+        fill = tuple(fill)
+    except TypeError:
+        raise ValueError(f"{who}: fill {fill!r}: three finite floats") from None
+    if len(fill) != 3:
+        raise ValueError(f"{who}: fill {fill!r}: three finite floats")
+    _finite_numbers(who, fill_r=fill[0], fill_g=fill[1], fill_b=fill[2])
+    with np.errstate(over="ignore"):
+        fill = tuple(float(np.float32(v)) for v in fill)
+    if not all(math.isfinite(v) for v in fill):
+        raise ValueError(f"{who}: fill {fill}: not finite in float32")
+    return fill
 
 
 def grid_footprints(grid: torch.Tensor, limit: float) -> torch.Tensor:
@@ -1493,17 +1510,7 @@ class Field:
         tensor the launch read or None)."""
         fmt = _format(dtype, layout)
         grid, p, sort = self._check_points(who, points, presort)
-        try:
-            fill = tuple(fill)
-        except TypeError:
-            raise ValueError(f"{who}: fill {fill!r}: three finite floats") from None
-        if len(fill) != 3:
-            raise ValueError(f"{who}: fill {fill!r}: three finite floats")
-        _finite_numbers(who, fill_r=fill[0], fill_g=fill[1], fill_b=fill[2])
-        with np.errstate(over="ignore"):
-            fill = tuple(float(np.float32(v)) for v in fill)
-        if not all(math.isfinite(v) for v in fill):
-            raise ValueError(f"{who}: fill {fill}: not finite in float32")
+        fill = _checked_fill(who, fill)
         if grid:
             shape = fmt.shape(points.shape[0], points.shape[1])
         else:
@@ -1680,6 +1687,239 @@ class _FilteredSampleFunction(torch.autograd.Function):
                             footprint=used, footprint_grad=foot)
         gp, gq = got if foot else (got, None)
         return (gp if ctx.needs_input_grad[0] else None), gq, None, None, None
+
+
+class FieldBatch:
+    """K Fields sampled together (Decoder.fields makes one from K streams, FieldBatch.of from existing Fields; DESIGN.md
+    3.8 "Batched samples"): one sampling launch per 64 pictures instead of one per picture, every picture at positions in
+    ITS OWN source pixel coordinates, and picture k's result bit for bit what batch[k]'s own call gives.  The fields live on
+    one device and are either all plain (max_filter == 0) or all made with max_filter > 0; they may differ in size, kind,
+    population and coding.  The device tables of the launches (one per group of 64 fields: the arrays, sizes and status row
+    of every field) are written here, once, and hold raw addresses of the Fields' tensors, so the batch keeps the Fields:
+    it stays valid after the caller has dropped every other reference.  len(batch), batch[k] and batch.fields give them."""
+
+    def __init__(self, fields: Sequence[Field]):
+        fields = tuple(fields)
+        if not fields or not all(isinstance(f, Field) for f in fields):
+            raise ValueError("FieldBatch: one or more codec.Field objects")
+        if any(f.dev != fields[0].dev for f in fields):
+            raise ValueError(f"FieldBatch: the fields live on different devices ({', '.join(sorted({str(f.dev) for f in fields}))})")
+        if len({f.max_filter > 0.0 for f in fields}) != 1:
+            raise ValueError("FieldBatch: either every field has max_filter == 0 or every field has max_filter > 0")
+        self.fields, self.dev = fields, fields[0].dev
+        self.filtered = fields[0].max_filter > 0.0
+        self.max_filter = min(f.max_filter for f in fields)  # what a footprint given as one number is held against
+        self._groups = []  # (first field, fields, the device table, the stride of the composite sort key)
+        size = _lib.load().gi2d_sample_batch_bytes
+        with torch.cuda.device(self.dev) if self.dev.type == "cuda" else contextlib.nullcontext():
+            st = _stream(self.dev)
+            for first in range(0, len(fields), BATCH_MAX):
+                group = fields[first:first + BATCH_MAX]
+                descs = (_CSampleField * len(group))()
+                for d, f in zip(descs, group):
+                    d.num_points, d.capacity, (d.tiles_x, d.tiles_y) = f.header["num_points"], f.capacity, f.tiles
+                    d.img_width, d.img_height, d.tile_bins_rows, d.max_filter = f.width, f.height, f.tiles[0] * f.tiles[1], f.max_filter
+                    d.gaussian_ids_sorted, d.tile_bins, d.status = f.ids.data_ptr(), f.bins.data_ptr(), f.status.data_ptr()
+                    d.xys, d.conics, d.colors = f.xys.data_ptr(), f.conics.data_ptr(), f.colors.data_ptr()
+                    d.covs = None if f.covs is None else f.covs.data_ptr()
+                table = torch.empty(int(size(len(group))), dtype=torch.uint8, device=self.dev)
+                _lib.call("gi2d_sample_batch_table", len(group), descs, C.c_void_p(table.data_ptr()), table.numel(), st)
+                self._groups.append((first, len(group), table, max(f.tiles[0] * f.tiles[1] for f in group) + 1))
+
+    @classmethod
+    def of(cls, fields: Sequence[Field]) -> "FieldBatch":
+        """A batch of existing Fields (one device; all plain or all made with max_filter > 0: ValueError otherwise)."""
+        return cls(fields)
+
+    def __len__(self) -> int:
+        return len(self.fields)
+
+    def __getitem__(self, k: int) -> Field:
+        return self.fields[k]
+
+    def sample(self, points: torch.Tensor, out: Optional[torch.Tensor] = None, dtype=None, layout=None,
+               fill: Sequence[float] = (0.0, 0.0, 0.0), presort: Optional[bool] = None, footprint=None) -> torch.Tensor:
+        """Field.sample for every picture of the batch in one launch per 64 pictures.  points: float32, contiguous, on the
+        batch's device, [K, Ho, Wo, 2] (one grid per picture) or [K, P, 2] (one flat list per picture), picture k's
+        positions in field k's source pixel coordinates.  -> [K, ...] with Field.sample's shape per picture ([K, Ho, Wo, 3],
+        [K, 3, Ho, Wo], [K, Ho, Wo, 4]; [K, P, 3], [K, 3, P], [K, P, 4]); slice k equals batch[k].sample(points[k], ...)
+        bit for bit, whatever the format, `presort` and K.  dtype, layout, fill, out: as there.  presort: as there (flat
+        lists are sorted, grids are not); a presorted call orders the work of ALL pictures of a group with ONE
+        gi2d_sample_point_keys_batched launch and ONE torch.sort.  footprint (a batch of max_filter > 0 fields): a float32
+        tensor shaped like points with 3 in place of 2, a number, or "auto" for grids (grid_footprints per picture, under the
+        picture's own max_filter); admission and fill are per sample, as in Field.sample.  Points that require grad (grad
+        enabled, no footprint) make the call differentiable in them through ONE autograd function, whose backward is one
+        gated VJP launch per 64 pictures on the forward's permutation: float32 "hwc", no `out`, no double backward.  No
+        host wait.  ValueError, before any launch, for anything else."""
+        if footprint is None and isinstance(points, torch.Tensor) and points.requires_grad and torch.is_grad_enabled():
+            if dtype not in (None, torch.float32) or layout not in (None, "hwc") or out is not None:
+                raise ValueError("sample: points that require grad take dtype None or torch.float32, layout None or 'hwc' "
+                                 "and no out: only the float32 'hwc' samples are differentiable")
+            return _BatchSampleFunction.apply(points, self, fill, presort)
+        return self._sample(points, out, dtype, layout, fill, presort, footprint)[0]
+
+    def sample_filtered(self, *args, **kwargs):
+        """Not batched: the differentiable filtered sample is Field.sample_filtered, per picture."""
+        raise ValueError("sample_filtered: gradients of filtered samples are not batched: call batch[k].sample_filtered(points[k], "
+                         "footprint[k]) per picture (FieldBatch.sample(points, footprint=) is the batched filtered value)")
+
+    def _check_points(self, who: str, points, presort) -> Tuple[bool, int, bool]:
+        """The checks on `points` and `presort` every batched call makes -> (grids?, P per picture, sort first?)."""
+        k = len(self.fields)
+        if (not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() not in (3, 4)
+                or points.shape[-1] != 2):
+            raise ValueError(f"{who}: points must be a float32 tensor of shape [K, P, 2] or [K, Ho, Wo, 2], (x, y) last")
+        if points.shape[0] != k:
+            raise ValueError(f"{who}: points hold {points.shape[0]} pictures, the batch {k} fields")
+        if points.device != self.dev:
+            raise ValueError(f"{who}: points live on {points.device}, the batch on {self.dev}")
+        if not points.is_contiguous():
+            raise ValueError(f"{who}: points must be contiguous")
+        if presort is not None and not isinstance(presort, bool):
+            raise ValueError(f"{who}: presort {presort!r}: None, True or False")
+        grid = points.dim() == 4
+        p = points.numel() // (2 * k)
+        sort = (not grid) if presort is None else presort
+        if p > (0x7FFFFFFF // min(k, BATCH_MAX) if sort else 0x7FFFFFFF * 256):
+            raise ValueError(f"{who}: {p} positions per picture are more than one call takes")
+        return grid, p, sort
+
+    def _check_footprint(self, footprint, points, grid: bool, who: str) -> torch.Tensor:
+        """The checks on `footprint` -> the float32 tensor [K, ..., 3] the launches read."""
+        if not self.filtered:
+            raise ValueError(f"{who}: footprint needs a batch of fields made with max_filter > 0 (Decoder.fields(streams, "
+                             "max_filter=v))")
+        if points.requires_grad and torch.is_grad_enabled():
+            raise ValueError(f"{who}: points that require grad take no footprint here: gradients of filtered samples are not "
+                             "batched, batch[k].sample_filtered(points[k], footprint[k]) is the differentiable filtered sample")
+        want = (*points.shape[:-1], 3)
+        if isinstance(footprint, str):
+            if footprint != "auto" or not grid:
+                raise ValueError(f"{who}: footprint {footprint!r}: 'auto' (for grids [K, Ho, Wo, 2]), a number or a tensor")
+            return torch.stack([grid_footprints(points[k], f.max_filter) for k, f in enumerate(self.fields)])
+        if not isinstance(footprint, torch.Tensor):
+            _finite_numbers(who, footprint=footprint)
+            q = float(footprint)
+            with np.errstate(over="ignore"):
+                if not (q >= 0.0 and float(np.float32(q) + np.float32(q)) <= float(np.float32(self.max_filter))):
+                    raise ValueError(f"{who}: footprint {q}: the variance (q, 0, q) must be >= 0 with 2 q <= the batch's smallest "
+                                     f"max_filter = {self.max_filter}")
+            return torch.tensor((q, 0.0, q), dtype=torch.float32, device=self.dev).expand(want).contiguous()
+        if (footprint.dtype != torch.float32 or tuple(footprint.shape) != want or footprint.device != self.dev
+                or not footprint.is_contiguous()):
+            raise ValueError(f"{who}: footprint must be a contiguous float32 tensor of shape {want} on {self.dev}")
+        return footprint
+
+    def _sample(self, points, out, dtype, layout, fill, presort, footprint=None, who: str = "sample"):
+        """sample's checks and launches -> (the samples, the permutations the groups' work was ordered by or None, the
+        footprint tensor the launches read or None)."""
+        fmt = _format(dtype, layout)
+        grid, p, sort = self._check_points(who, points, presort)
+        fill = _checked_fill(who, fill)
+        if grid:
+            shape = fmt.shape(points.shape[1], points.shape[2])
+        else:
+            shape = (3, p) if fmt.layout == "chw" else (p, 4 if fmt.layout == "hwc4" else 3)
+        shape = (len(self.fields), *shape)
+        if out is not None:
+            _check_out(out, shape, fmt.dtype, self.dev)
+        if footprint is not None:  # (after every other check: "auto" launches torch kernels of its own)
+            footprint = self._check_footprint(footprint, points, grid, who)
+        if out is None:
+            out = torch.empty(shape, dtype=fmt.dtype, device=self.dev)
+        if p == 0:
+            return out, None, footprint
+        tail = ((C.c_float * 3)(*fill), *fmt.ids, out)
+        if footprint is not None:
+            perms = self._launch("gi2d_sample_points_filtered_batched", points, grid, p, sort, (footprint, 0.0, *tail))
+        else:
+            perms = self._launch("gi2d_sample_points_batched", points, grid, p, sort, tail)
+        return out, perms, footprint
+
+    def _sorted_by_tile(self, at, count: int, p: int, table: torch.Tensor, stride: int, st) -> torch.Tensor:
+        """The int32 permutation that orders the count * p positions of a group by (picture, tile), stable: entries [k p,
+        (k + 1) p) are picture k's; no host wait."""
+        keys = torch.empty(count * p, dtype=torch.int32, device=self.dev)
+        _lib.call("gi2d_sample_point_keys_batched", count, C.c_void_p(table.data_ptr()), p, at, stride,
+                  C.c_void_p(keys.data_ptr()), st)
+        return torch.sort(keys, stable=True).indices.to(torch.int32)
+
+    def _launch(self, entry: str, points, grid: bool, p: int, sort: bool, tail, perms=None):
+        """One sampling launch per group of 64 fields: the device context, the stream, the presort (or `perms`, a forward's
+        own), the grids' sizes and the call.  tail: what the entry takes behind the grids' sizes; a tensor in it is a
+        [K, ...] array, passed as the address of the group's first picture.  -> the permutations used, or None."""
+        k = len(self.fields)
+        at = lambda t, first: C.c_void_p(t.data_ptr() + first * (t.numel() // k) * t.element_size())
+        used = []
+        with torch.cuda.device(self.dev) if self.dev.type == "cuda" else contextlib.nullcontext():
+            st = _stream(self.dev)
+            gw, gh = (points.shape[2], points.shape[1]) if grid and not sort else (0, 0)
+            for g, (first, count, table, stride) in enumerate(self._groups):
+                perm = None
+                if sort:
+                    perm = perms[g] if perms is not None else self._sorted_by_tile(at(points, first), count, p, table, stride, st)
+                    used.append(perm)
+                _lib.call(entry, count, C.c_void_p(table.data_ptr()), p, at(points, first),
+                          None if perm is None else C.c_void_p(perm.data_ptr()), gw, gh,
+                          *(at(a, first) if isinstance(a, torch.Tensor) else a for a in tail), st)
+        return used if sort else None
+
+    def jacobian(self, points: torch.Tensor, presort: Optional[bool] = None, clamped: bool = True, out=None, footprint=None,
+                 footprint_grad: bool = False) -> torch.Tensor:
+        """Field.jacobian for every picture: float32 [K, P, 3, 2] or [K, Ho, Wo, 3, 2], slice k bit for bit
+        batch[k].jacobian(points[k], ...); one gi2d_sample_points_grad_batched launch per 64 pictures.  points, presort:
+        as in sample; clamped, out: as in Field.jacobian.  Without footprints: a footprint is refused (ValueError)."""
+        return self._grad("jacobian", points, None, presort, clamped, out, footprint=footprint, footprint_grad=footprint_grad)
+
+    def sample_vjp(self, points: torch.Tensor, v: torch.Tensor, presort: Optional[bool] = None, clamped: bool = True,
+                   out=None, footprint=None, footprint_grad: bool = False) -> torch.Tensor:
+        """Field.sample_vjp for every picture: float32 [K, P, 2] or [K, Ho, Wo, 2]; v: float32, contiguous, on the batch's
+        device, shaped like sample's float32 "hwc" output for these points.  Everything else as in jacobian."""
+        self._check_points("sample_vjp", points, presort)  # (v's shape is read off points)
+        want = (*points.shape[:-1], 3)
+        if (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != want or v.device != self.dev
+                or not v.is_contiguous()):
+            raise ValueError(f"sample_vjp: v must be a contiguous float32 tensor of shape {want} on {self.dev}")
+        return self._grad("sample_vjp", points, v, presort, clamped, out, footprint=footprint, footprint_grad=footprint_grad)
+
+    def _grad(self, who: str, points, v, presort, clamped, out, perms=None, footprint=None, footprint_grad: bool = False):
+        """jacobian (v None) and sample_vjp: the checks, the presort (or `perms`, a forward's own) and the launches."""
+        grid, p, sort = self._check_points(who, points, presort)
+        if footprint is not None or footprint_grad:
+            raise ValueError(f"{who}: gradients of filtered samples are not batched: call batch[k].sample_filtered or "
+                             f"batch[k].{who}(..., footprint=) per picture")
+        if not isinstance(clamped, bool):
+            raise ValueError(f"{who}: clamped {clamped!r}: True or False")
+        shape = (*points.shape[:-1], 3, 2) if v is None else (*points.shape[:-1], 2)
+        if out is not None:
+            _check_out(out, shape, torch.float32, self.dev)
+        else:
+            out = torch.empty(shape, dtype=torch.float32, device=self.dev)
+        if p == 0:
+            return out
+        self._launch("gi2d_sample_points_grad_batched", points, grid, p, sort, perms=perms,
+                     tail=(int(clamped), v, out if v is None else None, None if v is None else out))
+        return out
+
+
+class _BatchSampleFunction(torch.autograd.Function):
+    """FieldBatch.sample for points that require grad: the forward is sample's own launches, the backward one gated
+    sample_vjp launch per group on the permutations the forward sorted by.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, points, batch, fill, presort):
+        out, perms, _ = batch._sample(points.detach(), None, None, None, fill, presort)
+        ctx.batch, ctx.presort = batch, presort
+        ctx.save_for_backward(points, *(perms or ()))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v):
+        points, *perms = ctx.saved_tensors
+        v = v.to(torch.float32).contiguous()
+        grad = ctx.batch._grad("sample_vjp", points.detach(), v, ctx.presort, True, None, perms=perms or None)
+        return grad, None, None, None
 
 
 class Decoder:
@@ -2204,48 +2444,106 @@ class Decoder:
         too, on the wider lists: not bit for bit what a max_filter = 0 field gives."""
         max_filter = _checked_max_filter("field", max_filter)
         h = _headers([stream])[0]
-        ident = Affine(0.0, 0.0, 1.0, 0.0, 0.0, 1.0, h["width"], h["height"], max_filter).check(h)  # (<= 16384 tiles, as every view)
-        n, tx, ty = h["num_points"], *ident.tiles
-        rc = ident.radius_clip(h)
-        i32 = lambda count: torch.empty(count, dtype=torch.int32, device=self.dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        bin_bytes = _lib.load().gi2d_bin_workspace_bytes
+        self._field_view(h, max_filter)
         with torch.cuda.device(self.dev):
             payload = self._stage([stream], [h])[0]
             status = torch.zeros(_STATUS_WORDS, dtype=torch.int32, device=self.dev)
-            st = _stream(self.dev)
             coded = h["coding"] != CODING_FIXED
             if coded:
                 self._next_token()
                 payload = self._expand(h, payload, status.data_ptr(),
                                        torch.empty(h["fixed_payload_bytes"], dtype=torch.uint8, device=self.dev))
-            geo = self._aux(n)
-            cap = self._overview_list_capacity(n)
-            ids, bins = i32(cap), i32(2 * tx * ty)
-            covs = None
-            if max_filter > 0.0:
-                covs = torch.empty((n, 3), dtype=torch.float32, device=self.dev)
-                _lib.call("gi2d_codec_decode_field", *_stream_args(h, payload), h["height"], h["width"], max_filter, tx, ty,
-                          rc, *map(ptr, geo), ptr(covs), st)
-            else:
-                _lib.call("gi2d_codec_decode_affine", *_stream_args(h, payload), h["height"], h["width"], ident.x0, ident.y0,
-                          *ident.inverse, *ident.prefilter, h["height"], h["width"], tx, ty, rc, *map(ptr, geo), st)
-
-            def bin_lists(capacity: int, ids: torch.Tensor) -> None:
-                binws = torch.empty(int(bin_bytes(capacity, tx * ty)), dtype=torch.uint8, device=self.dev)
-                _lib.call("gi2d_bin_gaussians", n, capacity, ptr(geo[0]), ptr(geo[1]), tx, ty, rc, ptr(ids), ptr(bins),
-                          status.data_ptr(), ptr(binws), binws.numel(), st)
-
-            bin_lists(cap, ids)
-            m, overflow, _, _, word = status[0:5].tolist()  # the host wait
+            part = self._field_begin(h, payload, status, max_filter)
+            m, overflow, _, _, word = self._read_status(status[None])[0]  # the host wait
             if coded:
                 self._check_expanded(word)
-            self._overview_m = max(self._overview_m, m)
-            if overflow:
-                cap = max(1, m)
-                ids = i32(cap)
-                bin_lists(cap, ids)
-        return Field(self.dev, h, geo, ids, bins, status, cap, m, max_filter, covs)
+            return self._field_finish(part, m, overflow)
+
+    def fields(self, streams, max_filter: float = 0.0) -> FieldBatch:
+        """K streams (bytes or uploaded DeviceStreams, any coding) -> the FieldBatch of the K Fields `field` makes of them,
+        each with tensors of its own and bit for bit what field(streams[k], max_filter) gives -- with ONE host wait for all
+        K: the coded payloads are expanded together (_expand_all), every stream's two launches queued, the K status rows,
+        which live in one [K, words] tensor, read once behind the last launch, and the Fields whose lists were cut at the
+        capacity then binned again with room for exactly their count (no second read).  Every stream and max_filter are
+        checked before anything touches the device (ValueError).  K >= 1; the batch's launches take up to 64 fields each."""
+        max_filter = _checked_max_filter("fields", max_filter)
+        streams = list(streams)
+        headers = _headers(streams)
+        if not headers:
+            raise ValueError("fields: one or more streams")
+        for h in headers:
+            self._field_view(h, max_filter)
+        with torch.cuda.device(self.dev):
+            payloads = self._stage(streams, headers)
+            rows = torch.zeros(len(headers), _STATUS_WORDS, dtype=torch.int32, device=self.dev)
+            self._next_token()
+            coded = [k for k, h in enumerate(headers) if h["coding"] != CODING_FIXED]
+            for k in coded:  # (the expansion of stream k goes into a buffer of its own, as in field)
+                payloads[k] = (payloads[k], torch.empty(headers[k]["fixed_payload_bytes"], dtype=torch.uint8, device=self.dev))
+            self._expand_all([(headers[k], payloads[k][0], rows[k].data_ptr(), payloads[k][1]) for k in coded])
+            for k in coded:
+                payloads[k] = payloads[k][1]
+            parts = [self._field_begin(h, payload, rows[k], max_filter)
+                     for k, (h, payload) in enumerate(zip(headers, payloads))]
+            status = self._read_status(rows)  # the host wait
+            for k, (h, row) in enumerate(zip(headers, status)):
+                if h["coding"] != CODING_FIXED:
+                    self._check_expanded(row[4], f" {k}")
+            return FieldBatch([self._field_finish(part, row[0], row[1]) for part, row in zip(parts, status)])
+
+    @staticmethod
+    def _field_view(h, max_filter: float) -> Affine:
+        """The identity view a Field's lists are built under, checked against the stream (<= 16384 tiles, as every view)."""
+        return Affine(0.0, 0.0, 1.0, 0.0, 0.0, 1.0, h["width"], h["height"], max_filter).check(h)
+
+    @staticmethod
+    def _read_status(rows: torch.Tensor) -> List[List[int]]:
+        """Words 0..4 of the status rows [K, words] on the host -- M, overflow, .., .., rANS: the host wait of field / fields."""
+        return rows[:, 0:5].tolist()
+
+    def _field_begin(self, h, payload: torch.Tensor, status: torch.Tensor, max_filter: float) -> dict:
+        """The tensors and the two launches of a Field (the per-gaussian kernel under the identity map, gi2d_bin_gaussians
+        at the capacity an overview starts with) on the coding-0 payload, with the status row `status`; no host wait.
+        -> what _field_finish needs."""
+        ident = self._field_view(h, max_filter)
+        n, tx, ty = h["num_points"], *ident.tiles
+        rc = ident.radius_clip(h)
+        i32 = lambda count: torch.empty(count, dtype=torch.int32, device=self.dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        bin_bytes = _lib.load().gi2d_bin_workspace_bytes
+        st = _stream(self.dev)
+        geo = self._aux(n)
+        cap = self._overview_list_capacity(n)
+        ids, bins = i32(cap), i32(2 * tx * ty)
+        covs = None
+        if max_filter > 0.0:
+            covs = torch.empty((n, 3), dtype=torch.float32, device=self.dev)
+            _lib.call("gi2d_codec_decode_field", *_stream_args(h, payload), h["height"], h["width"], max_filter, tx, ty,
+                      rc, *map(ptr, geo), ptr(covs), st)
+        else:
+            _lib.call("gi2d_codec_decode_affine", *_stream_args(h, payload), h["height"], h["width"], ident.x0, ident.y0,
+                      *ident.inverse, *ident.prefilter, h["height"], h["width"], tx, ty, rc, *map(ptr, geo), st)
+
+        def bin_lists(capacity: int, ids: torch.Tensor) -> None:
+            binws = torch.empty(int(bin_bytes(capacity, tx * ty)), dtype=torch.uint8, device=self.dev)
+            _lib.call("gi2d_bin_gaussians", n, capacity, ptr(geo[0]), ptr(geo[1]), tx, ty, rc, ptr(ids), ptr(bins),
+                      status.data_ptr(), ptr(binws), binws.numel(), st)
+
+        bin_lists(cap, ids)
+        return dict(header=h, geo=geo, ids=ids, bins=bins, status=status, cap=cap, covs=covs, max_filter=max_filter,
+                    bin_lists=bin_lists, i32=i32)
+
+    def _field_finish(self, part: dict, m: int, overflow: int) -> Field:
+        """The Field of _field_begin once its status row has been read: lists cut at the capacity are binned again with
+        room for exactly `m` entries."""
+        cap, ids = part["cap"], part["ids"]
+        self._overview_m = max(self._overview_m, m)
+        if overflow:
+            cap = max(1, m)
+            ids = part["i32"](cap)
+            part["bin_lists"](cap, ids)
+        return Field(self.dev, part["header"], part["geo"], ids, part["bins"], part["status"], cap, m, part["max_filter"],
+                     part["covs"])
 
 
 _decoders: Dict[torch.device, Decoder] = {}
@@ -2280,6 +2578,14 @@ def field(blob, device: Union[str, torch.device] = "cuda:0", max_filter: float =
     _parse(blob)  # a malformed stream is refused before a device is even touched
     _checked_max_filter("field", max_filter)
     return _decoder(device).field(blob, max_filter=max_filter)
+
+
+def fields(blobs, device: Union[str, torch.device] = "cuda:0", max_filter: float = 0.0) -> FieldBatch:
+    """One-shot Decoder.fields (the Decoder kept per device): K streams -> their FieldBatch, with one host wait for all."""
+    blobs = list(blobs)
+    _headers(blobs)  # a malformed stream or a bad max_filter is refused before a device is even touched
+    _checked_max_filter("fields", max_filter)
+    return _decoder(device).fields(blobs, max_filter=max_filter)
 
 
 def sample(blob, points: torch.Tensor, device: Optional[Union[str, torch.device]] = None, out: Optional[torch.Tensor] = None,

@@ -20,7 +20,8 @@
 //
 // The pieces of the walk are gi2d_sample_core.h's, shared with gi2d_sample_filtered.hip: the gradient kernel is built from
 // all of them, the value kernel keeps the next-tile step and the staged batch in its own text, which keeps its device code
-// what it was (DESIGN.md 3.8 "One sample walk" has the measurements behind that).
+// what it was (DESIGN.md 3.8 "One sample walk" has the measurements behind that).  The pair functions sample_pair and
+// sample_pair_grad stand in that header too: gi2d_sample_batch.hip applies the same text to K fields per launch.
 //
 // A sample's bits depend on the stream and its position alone: no atomics, and neither its place in the call nor its
 // neighbours enter its sum.  Nothing is read through an address formed from unchecked content: the tile comes from a
@@ -38,24 +39,6 @@ __global__ __launch_bounds__(256) void sample_keys_kernel(long long num_samples,
     const float2 p = points[s];
     bool inside;
     keys[s] = sample_key(p.x, p.y, img_w, img_h, tiles_x, tiles_y, inside);
-}
-
-// one staged entry on this lane's sample: long_pair's operations, in its order, on the staged triple
-template <bool CLAMP>
-__device__ __forceinline__ void sample_pair(const float4 A, const float4 B, const float2 Cc, float px, float py, float &o0,
-                                            float &o1, float &o2) {
-    const unsigned lim = (unsigned)__float_as_int(Cc.y);
-    const float dy = A.y - py;
-    const float bdy = A.w * dy, cdy2 = __builtin_fmaf(B.x * dy, dy, 0.f);
-    const float dx = A.x - px;
-    const float sig = __builtin_fmaf(dx, __builtin_fmaf(A.z, dx, bdy), cdy2);
-    const float tt = B.y * pair_vis(sig);
-    const bool ok = CLAMP ? pair_lands_odd(sig, tt, lim) : pair_lands(sig, lim);
-    float am = ok ? tt : 0.f;
-    if (CLAMP) am = fminf(1.f, am);
-    o0 = __builtin_fmaf(B.z, am, o0);
-    o1 = __builtin_fmaf(B.w, am, o1);
-    o2 = __builtin_fmaf(Cc.x, am, o2);
 }
 
 // DTYPE, LAYOUT: the element type and layout of the output (gi2d_pixel_format.h), with pix = the sample's index and
@@ -157,42 +140,8 @@ __global__ __launch_bounds__(256) void sample_points_kernel(
                                  pixel_convert<DTYPE>(1.f), (size_t)s, (size_t)num_samples, reinterpret_cast<T *>(out_));
 }
 
-// ---- the derivative of a sample in its position (include/gi2d.h "samples"; DESIGN.md 3.8 "Samples", "Sample gradients")
-// One staged entry on this lane's sample: sample_pair, operation for operation -- so o0..o2 carry the bits the value
-// kernel stores and the same pairs land -- plus the pair's six derivative terms.  With dx = gx - px the derivative of
-// alpha = opac exp(-sigma) in px is alpha (a dx + b dy); from the staged log2-scaled conic the two linear forms are
-//     lx = 2 ha dx + hb dy = log2(e) (a dx + b dy),     ly = hb dx + 2 hc dy = log2(e) (b dx + c dy)
-// and the factor ln 2 waits for the epilogue.  CLAMP: an entry on which min(1, .) binds (alpha above 1, or a NaN) is
-// flat there and adds nothing.
-template <bool CLAMP>
-__device__ __forceinline__ void sample_pair_grad(const float4 A, const float4 B, const float2 Cc, float px, float py,
-                                                 float &o0, float &o1, float &o2, float (&d)[6]) {
-    const unsigned lim = (unsigned)__float_as_int(Cc.y);
-    const float dy = A.y - py;
-    const float hcdy = B.x * dy;
-    const float bdy = A.w * dy, cdy2 = __builtin_fmaf(hcdy, dy, 0.f);
-    const float dx = A.x - px;
-    const float sig = __builtin_fmaf(dx, __builtin_fmaf(A.z, dx, bdy), cdy2);
-    const float tt = B.y * pair_vis(sig);
-    const bool ok = CLAMP ? pair_lands_odd(sig, tt, lim) : pair_lands(sig, lim);
-    float am = ok ? tt : 0.f;
-    if (CLAMP) am = fminf(1.f, am);
-    o0 = __builtin_fmaf(B.z, am, o0);
-    o1 = __builtin_fmaf(B.w, am, o1);
-    o2 = __builtin_fmaf(Cc.x, am, o2);
-    const float lx = __builtin_fmaf(2.f * A.z, dx, bdy);
-    const float ly = __builtin_fmaf(A.w, dx, 2.f * hcdy);
-    // a select, not a product with am: the forms of a pair that does not land may be infinite, and 0 * inf must not enter
-    const bool moves = CLAMP ? (ok && tt <= 1.f) : ok;
-    const float ax = moves ? tt * lx : 0.f, ay = moves ? tt * ly : 0.f;
-    d[0] = __builtin_fmaf(B.z, ax, d[0]);
-    d[1] = __builtin_fmaf(B.z, ay, d[1]);
-    d[2] = __builtin_fmaf(B.w, ax, d[2]);
-    d[3] = __builtin_fmaf(B.w, ay, d[3]);
-    d[4] = __builtin_fmaf(Cc.x, ax, d[4]);
-    d[5] = __builtin_fmaf(Cc.x, ay, d[5]);
-}
-
+// ---- the derivative of a sample in its position (include/gi2d.h "samples"; DESIGN.md 3.8 "Samples", "Sample gradients"):
+// the pair function is gi2d_sample_core.h::sample_pair_grad.
 // sample_points_kernel's walk with six more accumulators, d[2 k + 0 | 1] = d o_k / d (px | py) over ln 2, and another
 // epilogue:
 //   VJP = false   out = jacobian f32[P,3,2]: the six floats of sample s, 24 contiguous bytes, as three float2 stores

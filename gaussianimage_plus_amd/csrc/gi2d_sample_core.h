@@ -1,9 +1,11 @@
-// What the sample kernels share (gi2d_sample.hip, gi2d_sample_filtered.hip; DESIGN.md 3.8 "One sample walk"): the wave's
-// staging block, the key of a position, the lane -> sample map, the next tile of the wave's waterfall, the served lanes'
-// box and one staged batch of a tile's list.  A kernel keeps its two loops (`while (todo)`, `for (base ...)`), its pair
-// loop, its accumulators and its epilogue: the pair loop stays in the kernel's own text because handing it to a shared
-// template changes how its unrolled body is packed.  The value and the filtered kernel also restate the next-tile step and
-// the staged batch in their own text, each under a comment naming the piece; DESIGN.md 3.8 has the measurements behind that.
+// What the sample kernels share (gi2d_sample.hip, gi2d_sample_filtered.hip, gi2d_sample_batch.hip; DESIGN.md 3.8 "One sample
+// walk", "Batched samples"): the wave's staging block, the key of a position, the lane -> sample map, the next tile of the
+// wave's waterfall, the served lanes' box, one staged batch of a tile's list, and the pair functions of the value and the
+// gradient kernel, which the single and the batched kernels apply as one text.  A kernel keeps its two loops (`while
+// (todo)`, `for (base ...)`), its pair loop, its accumulators and its epilogue: the pair loop stays in the kernel's own text
+// because handing it to a shared template changes how its unrolled body is packed.  The single value and filtered kernels
+// also restate the next-tile step and the staged batch in their own text, each under a comment naming the piece; DESIGN.md
+// 3.8 has the measurements behind that.
 #pragma once
 
 #include <string>
@@ -170,6 +172,61 @@ struct PointEntry {
         return true;
     }
 };
+
+// ---- the pair functions of the value and the gradient kernel (gi2d_sample.hip, gi2d_sample_batch.hip: one text)
+// one staged entry on this lane's sample: long_pair's operations, in its order, on the staged triple
+template <bool CLAMP>
+__device__ __forceinline__ void sample_pair(const float4 A, const float4 B, const float2 Cc, float px, float py, float &o0,
+                                            float &o1, float &o2) {
+    const unsigned lim = (unsigned)__float_as_int(Cc.y);
+    const float dy = A.y - py;
+    const float bdy = A.w * dy, cdy2 = __builtin_fmaf(B.x * dy, dy, 0.f);
+    const float dx = A.x - px;
+    const float sig = __builtin_fmaf(dx, __builtin_fmaf(A.z, dx, bdy), cdy2);
+    const float tt = B.y * pair_vis(sig);
+    const bool ok = CLAMP ? pair_lands_odd(sig, tt, lim) : pair_lands(sig, lim);
+    float am = ok ? tt : 0.f;
+    if (CLAMP) am = fminf(1.f, am);
+    o0 = __builtin_fmaf(B.z, am, o0);
+    o1 = __builtin_fmaf(B.w, am, o1);
+    o2 = __builtin_fmaf(Cc.x, am, o2);
+}
+
+// ---- the derivative of a sample in its position (include/gi2d.h "samples"; DESIGN.md 3.8 "Sample gradients")
+// One staged entry on this lane's sample: sample_pair, operation for operation -- so o0..o2 carry the bits the value
+// kernel stores and the same pairs land -- plus the pair's six derivative terms.  With dx = gx - px the derivative of
+// alpha = opac exp(-sigma) in px is alpha (a dx + b dy); from the staged log2-scaled conic the two linear forms are
+//     lx = 2 ha dx + hb dy = log2(e) (a dx + b dy),     ly = hb dx + 2 hc dy = log2(e) (b dx + c dy)
+// and the factor ln 2 waits for the epilogue.  CLAMP: an entry on which min(1, .) binds (alpha above 1, or a NaN) is
+// flat there and adds nothing.
+template <bool CLAMP>
+__device__ __forceinline__ void sample_pair_grad(const float4 A, const float4 B, const float2 Cc, float px, float py,
+                                                 float &o0, float &o1, float &o2, float (&d)[6]) {
+    const unsigned lim = (unsigned)__float_as_int(Cc.y);
+    const float dy = A.y - py;
+    const float hcdy = B.x * dy;
+    const float bdy = A.w * dy, cdy2 = __builtin_fmaf(hcdy, dy, 0.f);
+    const float dx = A.x - px;
+    const float sig = __builtin_fmaf(dx, __builtin_fmaf(A.z, dx, bdy), cdy2);
+    const float tt = B.y * pair_vis(sig);
+    const bool ok = CLAMP ? pair_lands_odd(sig, tt, lim) : pair_lands(sig, lim);
+    float am = ok ? tt : 0.f;
+    if (CLAMP) am = fminf(1.f, am);
+    o0 = __builtin_fmaf(B.z, am, o0);
+    o1 = __builtin_fmaf(B.w, am, o1);
+    o2 = __builtin_fmaf(Cc.x, am, o2);
+    const float lx = __builtin_fmaf(2.f * A.z, dx, bdy);
+    const float ly = __builtin_fmaf(A.w, dx, 2.f * hcdy);
+    // a select, not a product with am: the forms of a pair that does not land may be infinite, and 0 * inf must not enter
+    const bool moves = CLAMP ? (ok && tt <= 1.f) : ok;
+    const float ax = moves ? tt * lx : 0.f, ay = moves ? tt * ly : 0.f;
+    d[0] = __builtin_fmaf(B.z, ax, d[0]);
+    d[1] = __builtin_fmaf(B.z, ay, d[1]);
+    d[2] = __builtin_fmaf(B.w, ax, d[2]);
+    d[3] = __builtin_fmaf(B.w, ay, d[3]);
+    d[4] = __builtin_fmaf(Cc.x, ax, d[4]);
+    d[5] = __builtin_fmaf(Cc.x, ay, d[5]);
+}
 
 // ---- the host side of the sampling entries
 

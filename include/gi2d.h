@@ -1051,6 +1051,68 @@ int gi2d_sample_points_filtered_grad(int num_points, int capacity, int tiles_x, 
                                      float *v_footprints /* f32[P,3] or NULL: only if v_out != NULL */,
                                      gi2d_stream_t stream);
 
+/* ------------------------------------------------------------------ batched samples (DESIGN.md 3.8 "Batched samples")
+ * K fields sampled in ONE launch: what gi2d_codec_decode_batch does for the decode, for the sampling entries above.  Every
+ * picture has the same number P of samples (samples_per_field), at positions in ITS OWN source pixel coordinates; the
+ * fields may differ in size, kind and population.  Picture k's samples are, bit for bit, the single entry's on field k:
+ * the kernels run the same walk with the same pair arithmetic in the same order, a workgroup (blockIdx.y = the picture)
+ * reads its field from a table in HBM.
+ *   gi2d_sample_field      (gi2d_sample_field.h, included here) one field: what the single entries take per field, with the
+ *                          same meaning -- num_points,
+ *                          capacity, the tile grid, the picture's size, the lists (gaussian_ids_sorted, tile_bins,
+ *                          tile_bins_rows), xys, conics, colors, opacities (NULL = all 1), status (NULL = not looked at);
+ *                          covs and max_filter > 0 for a field of gi2d_codec_decode_field, covs = NULL and max_filter = 0
+ *                          for a plain one.
+ *   gi2d_sample_batch_bytes   the device table of `num_fields` fields (16-byte aligned); a size query.
+ *   gi2d_sample_batch_table   1 <= num_fields <= 64.  Checks every field with the per-field refusals of the single entries
+ *                          (sizes; a tile grid that does not cover the image; a NULL array of a field with lists) and
+ *                          max_filter (0 .. 4, above 0 exactly where covs is given); refuses (-1, gi2d_last_error_string
+ *                          set, the message names the field) before any HIP call, as it does a NULL pointer and a table
+ *                          that is too small or misaligned.  Then the table is written stream-ordered by kernels that
+ *                          carry the descriptors as kernel arguments (no host-to-device copy, no pinned buffer).  The table
+ *                          holds nothing a sampling call changes: write it once, sample any number of times; the arrays
+ *                          it points to must outlive it.
+ * The sampling entries take num_fields, the table, samples_per_field, points_xy f32[K,P,2], perm, grid_width, grid_height
+ * and then the single entry's own tail; every output is [K, ...] with picture k at k * (one picture's bytes):
+ *   gi2d_sample_points_batched            out: K pictures of P samples in the format (gi2d_sample_points).
+ *   gi2d_sample_points_grad_batched       jacobian f32[K,P,3,2], or v_out f32[K,P,3] -> v_points f32[K,P,2]
+ *                          (gi2d_sample_points_grad).
+ *   gi2d_sample_points_filtered_batched   footprints f32[K,P,3]; a sample is admitted against ITS field's max_filter
+ *                          (the argument max_filter = 0), or against the smaller of the two (0 < max_filter <= 4); a field
+ *                          without covs admits nothing: its samples are the fill (gi2d_sample_points_filtered).
+ * perm i32[K P] (device, NULL = as given): lane i of picture k takes sample perm[k P + i] - k P, the entry clamped to
+ * [k P, (k + 1) P - 1] first, so no content leads a lane to another picture's sample; a permutation that sorts
+ *   gi2d_sample_point_keys_batched        keys[k P + s] = k * stride + the key gi2d_sample_point_keys gives sample s on
+ *                          field k (at most stride - 1); stride: the largest tiles_x * tiles_y + 1 of the fields
+ * (stable) is k-major, and within a picture in tile order.  grid_width > 0: every picture's positions are a [grid_height,
+ * grid_width, 2] lattice.  Refusals (-1, before any HIP call), under prefixes of their own ("sample points batched", ...):
+ * num_fields outside 1 .. 64, an unknown format, a negative size, grid_width * grid_height != samples_per_field, perm
+ * together with a grid, more samples than a launch's grid holds (with perm: K P above 2^31 - 1), a NULL or misaligned
+ * table, a NULL array, a misaligned gradient output, anything but exactly one of jacobian / v_points, max_filter outside
+ * 0 .. 4, num_fields * stride at or above 2^31.  samples_per_field = 0 is GI2D_OK without a launch. */
+#include "gi2d_sample_field.h" /* struct gi2d_sample_field (a header of its own, which this one brings along) */
+size_t gi2d_sample_batch_bytes(int num_fields);
+int gi2d_sample_batch_table(int num_fields, const struct gi2d_sample_field *fields, void *table, size_t table_bytes,
+                            gi2d_stream_t stream);
+int gi2d_sample_point_keys_batched(int num_fields, const void *table, long long samples_per_field,
+                                   const float *points_xy, int stride, int32_t *keys, gi2d_stream_t stream);
+int gi2d_sample_points_batched(int num_fields, const void *table, long long samples_per_field, const float *points_xy,
+                               const int32_t *perm /* NULL: as given */, int grid_width /* 0: flat lists */,
+                               int grid_height, const float *fill_host /* 3 floats, NULL: zeros */, int dtype, int layout,
+                               void *out, gi2d_stream_t stream);
+int gi2d_sample_points_grad_batched(int num_fields, const void *table, long long samples_per_field,
+                                    const float *points_xy, const int32_t *perm /* NULL: as given */,
+                                    int grid_width /* 0: flat lists */, int grid_height, int gate,
+                                    const float *v_out /* f32[K,P,3], or NULL */,
+                                    float *jacobian /* f32[K,P,3,2]: iff v_out == NULL */,
+                                    float *v_points /* f32[K,P,2]: iff v_out != NULL */, gi2d_stream_t stream);
+int gi2d_sample_points_filtered_batched(int num_fields, const void *table, long long samples_per_field,
+                                        const float *points_xy, const int32_t *perm /* NULL: as given */,
+                                        int grid_width /* 0: flat lists */, int grid_height,
+                                        const float *footprints /* f32[K,P,3] */, float max_filter /* 0: the fields' own */,
+                                        const float *fill_host /* 3 floats, NULL: zeros */, int dtype, int layout,
+                                        void *out, gi2d_stream_t stream);
+
 /* ------------------------------------------------------------------ batched decode (DESIGN.md 3.8 "Batches")
  * K streams -> K pictures of ONE size and format in three launches: what the batched fitting calls above do for a fit,
  * for the decoder.  Picture k is, bit for bit, what workspace init + gi2d_codec_decode_bin (view = 0) or

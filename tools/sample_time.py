@@ -18,7 +18,7 @@ EXTRA='-DGI2D_SAMPLE_NO_SKIP -DGI2D_DEV_VARIANT=sample_noskip') gives the rows w
 keeps the two fits' streams in an .npz, so that every process of a comparison samples the same streams.
 
     python tools/sample_time.py [--reps 100] [--streams PATH] [--out-json profiles/sample_time.json] [--trace]
-                                [--grad | --filtered | --filtered-grad]
+                                [--grad | --filtered | --filtered-grad | --batch]
 --trace samples a few dozen times and nothing else: run it under `rocprofv3 --kernel-trace --stats -- python ...` for the
 two kernels' own times.
 
@@ -52,6 +52,18 @@ gradients"; profiles/sample_filtered_grad_time.json), a run of its own with the 
                               ..._both with points AND footprints that require grad
     grid_sample_forward_backward   full decode, then torch.nn.functional.grid_sample with a grid that requires grad, then
                               backward(w): the other route to a gradient in the positions (none exists for the footprint)
+
+--batch times K pictures per call (DESIGN.md 3.8 "Batched samples"; profiles/sample_batch_time.json), a run of its own with the
+same region discipline, for K = 1, 8, 64 Fields of the uploaded stream; every figure is microseconds PER PICTURE:
+    grid       a 224 x 224 radial-distortion grid per picture: FieldBatch.sample next to the loop of K Field.sample calls on
+               the same Fields (a caller's route without the batch) and to Decoder.decode_batch with K codec.Affine crops of
+               224 x 224 (the yardstick of the session: a different picture)
+    flat       4 096 random positions per picture, presorted: FieldBatch.sample next to the loop
+    grad       the grid, forward + backward through autograd: one function for the K pictures next to K single ones
+    fields     Decoder.fields of the K streams next to K Decoder.field calls
+`difference_us` is loop - batch per picture; it `counts` only where it exceeds `widest_range_us`, the widest min-to-max range
+of the regions of the row's entries.  With --trace: the batched and the single calls of K = 64, a few dozen times, for a
+kernel trace of its own.
 """
 import argparse
 import json
@@ -268,6 +280,87 @@ def filtered_grad_rows(dec, up, full, warp, warp_norm, reps, max_filter=1.5):
     return rows
 
 
+def radial_window(x0, y0, side):
+    """Barrel distortion about the centre of the side x side window at (x0, y0), every position inside the window: float32
+    [side, side, 2] (x, y)."""
+    yy, xx = torch.meshgrid(torch.arange(side, dtype=torch.float64), torch.arange(side, dtype=torch.float64), indexing="ij")
+    c = (side - 1) / 2
+    u, v = (xx - c) / c, (yy - c) / c
+    k = 1.0 - 0.15 * (u * u + v * v) / 2.0
+    return torch.stack([x0 + c + c * u * k, y0 + c + c * v * k], dim=2).float().to(DEV).contiguous()
+
+
+def per_picture(row, k):
+    """alternating's figures are per call: per picture they are that over K; then the claim's test on loop against batch."""
+    for key in [key for key in row if "_us" in key]:
+        row[key] = [round(x / k, 3) for x in row[key]] if isinstance(row[key], list) else round(row[key] / k, 3)
+    if "loop_us" in row and "batch_us" in row:
+        row["difference_us"] = round(row["loop_us"] - row["batch_us"], 3)
+        row["widest_range_us"] = round(max(r[1] - r[0] for key, r in row.items() if key.endswith("_us_range")), 3)
+        row["counts"] = abs(row["difference_us"]) > row["widest_range_us"]
+        row["batch_wins"] = bool(row["counts"] and row["difference_us"] > 0)
+    return row
+
+
+def batch_rows(dec, up, reps, x0, y0, side, trace=False):
+    """The --batch rows of one fit: {"K=1": {"grid": ..., "flat": ..., "grad": ..., "fields": ...}, ...}."""
+    window = codec.Affine(float(x0), float(y0), 1.0, 0.0, 0.0, 1.0, side, side, 0.0)
+    grid1 = radial_window(x0, y0, side)
+    rng = np.random.default_rng(20241021)
+    flat1 = torch.from_numpy((rng.random((4096, 2)) * [W - 1, H - 1]).astype(np.float32)).to(DEV)
+    rows = {}
+    for k in ((64,) if trace else (1, 8, 64)):
+        batch = dec.fields([up] * k)
+        grids, flats = grid1.expand(k, side, side, 2).contiguous(), flat1.expand(k, 4096, 2).contiguous()
+        out_g, out_f = torch.empty(k, side, side, 3, device=DEV), torch.empty(k, 4096, 3, device=DEV)
+        out_d = torch.empty(k, side, side, 3, device=DEV)
+        w = torch.randn(k, side, side, 3, device=DEV, generator=torch.Generator(device=DEV).manual_seed(7))
+        g_req, singles_req = grids.clone().requires_grad_(True), [grids[j].clone().requires_grad_(True) for j in range(k)]
+
+        def loop_grid():
+            for j in range(k):
+                batch[j].sample(grids[j], out=out_g[j])
+
+        def loop_flat():
+            for j in range(k):
+                batch[j].sample(flats[j], out=out_f[j])
+
+        def batch_grad():
+            g_req.grad = None
+            batch.sample(g_req).backward(w)
+
+        def loop_grad():
+            for j in range(k):
+                singles_req[j].grad = None
+                batch[j].sample(singles_req[j]).backward(w[j])
+
+        def loop_fields():
+            for _ in range(k):
+                dec.field(up)
+
+        batch.sample(grids, out=out_g), batch_grad(), loop_grad()
+        assert torch.equal(out_g, torch.stack([batch[j].sample(grids[j]) for j in range(k)]))
+        assert torch.equal(g_req.grad, torch.stack([p.grad for p in singles_req]))
+        assert torch.equal(batch.sample(flats), torch.stack([batch[j].sample(flats[j]) for j in range(k)]))
+        if trace:
+            for _ in range(30):
+                batch.sample(grids, out=out_g), batch.sample(flats, out=out_f), batch_grad()
+                loop_grid(), loop_flat(), loop_grad()
+            torch.cuda.synchronize()
+            continue
+        n = max(10, 2 * reps // k)
+        rows[f"K={k}"] = {
+            "grid": per_picture(alternating({"grid": [side, side], "reps": n}, {
+                "batch": lambda: batch.sample(grids, out=out_g), "loop": loop_grid,
+                "decode_batch_affine": lambda: dec.decode_batch([up] * k, views=[window] * k, out=out_d)}, n), k),
+            "flat": per_picture(alternating({"points": 4096, "reps": n}, {
+                "batch": lambda: batch.sample(flats, out=out_f), "loop": loop_flat}, n), k),
+            "grad": per_picture(alternating({"grid": [side, side], "reps": n}, {"batch": batch_grad, "loop": loop_grad}, n), k),
+            "fields": per_picture(alternating({"reps": max(5, n // 4)}, {
+                "batch": lambda: dec.fields([up] * k), "loop": loop_fields}, max(5, n // 4)), k)}
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=100)
@@ -278,11 +371,12 @@ def main():
     ap.add_argument("--grad", action="store_true")
     ap.add_argument("--filtered", action="store_true")
     ap.add_argument("--filtered-grad", action="store_true")
+    ap.add_argument("--batch", action="store_true")
     ap.add_argument("--out-json", default=None, metavar="PATH")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "sample_time.py needs the GPU"
-    assert a.grad + a.filtered + a.filtered_grad <= 1, "--grad, --filtered and --filtered-grad are runs of their own"
-    res = {"tool": "sample_time --grad" if a.grad else "sample_time --filtered" if a.filtered else
+    assert a.grad + a.filtered + a.filtered_grad + a.batch <= 1, "--grad, --filtered, --filtered-grad and --batch are runs of their own"
+    res = {"tool": "sample_time --batch" if a.batch else "sample_time --grad" if a.grad else "sample_time --filtered" if a.filtered else
            "sample_time --filtered-grad" if a.filtered_grad else "sample_time", "lib": _lib.version(), "device": torch.cuda.get_device_name(0), "image": [W, H],
            "bits": [12, 10, 6], "reps": a.reps, "regions": 5, "sizes": {}}
     warp, warp_norm = radial_grid()
@@ -296,6 +390,11 @@ def main():
         full = torch.empty(H, W, 3, device=DEV)
         crop = fld.identity_grid()[y0:y0 + side, x0:x0 + side].contiguous()
         window = codec.Affine(float(x0), float(y0), 1.0, 0.0, 0.0, 1.0, side, side, 0.0)
+        if a.batch:
+            rows = batch_rows(dec, up, a.reps, x0, y0, side, trace=a.trace)
+            if not a.trace:
+                res["sizes"][str(n)] = {"gaussians": fld.header["num_points"], "intersections": fld.count, "rows": rows}
+            continue
         if a.trace and a.filtered_grad:
             wide = dec.field(up, max_filter=1.5)
             for pts in (reducing_grid()[0], warp):
